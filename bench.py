@@ -15,7 +15,10 @@ step     : one pass of the hot path over one block: fabgpu_p256_verify_batch_dev
 Timing   : W warm-up steps, then exactly K steps bracketed by barrier + torch.cuda.synchronize(); max over ranks.  In front of the W
            warm-up steps: --clock-warmup (60) untimed launches of the same kernel - the GPU idles while the batch is synthesised on the
            CPU, and its next ~25 launches would run at idle clocks (0.735 instead of 0.635 ms: tools/gpu_r05_gap_probe.py).
-Same JSON line, outside that timed region (SURVEY.md 8(d) "Timing protocol"):
+A plain run stops there: it prints the line (the contract's keys, validated_tx_per_s, config) and nothing else is launched.
+--dump-outputs DIR writes what the last timed step returned, rank 0's verdict bits, as DIR/verdict.npy (float32, one per tuple;
+with N > 1 also DIR/verdict_all_ranks.npy, the all-gathered bitmap): the inputs are seeded, so two builds compare output for output.
+--full adds, in the same JSON line and outside that timed region (SURVEY.md 8(d) "Timing protocol"):
   dispersion      median / p95 of individually timed steps (HIP events), device-resident leg
   pcie_inclusive  the host-pointer C ABI the cgo provider calls (staging copy + H2D + kernel + D2H), wall clock per call,
                   median / p95 - never `value`
@@ -206,17 +209,19 @@ def compact_line(out, detail_path="bench_detail.json"):
     line["config"] = {"workload": str(cfg.get("workload", ""))[:150], "tuples_per_gpu": cfg.get("tuples_per_gpu"), "tx_per_block": cfg.get("tx_per_block"),
                       "endorsements_per_tx": cfg.get("endorsements_per_tx"), "seed": cfg.get("seed"), "parallelism": cfg.get("parallelism"),
                       "clock_warmup_launches": cfg.get("clock_warmup_launches")}
-    line["roofline"] = {"bound": rf.get("bound"), "achieved": rf.get("achieved"), "peak": rf.get("peak"), "unit": rf.get("unit"), "frac": rf.get("frac"),
-                        "traffic": rf.get("traffic"), "traffic_source": str(rf.get("traffic_source") or "")[:110], "algorithmic_bytes": rf.get("algorithmic_bytes"),
-                        "kernel": str(rf.get("kernel", "")).split(" (")[0], "kernel_ms": rf.get("kernel_ms"),
-                        "hbm_achieved_GBps": _dig(rf, "hbm", "achieved"), "hbm_frac": _dig(rf, "hbm", "frac")}
+    if rf:                                               # (a run without --full measures no roofline)
+        line["roofline"] = {"bound": rf.get("bound"), "achieved": rf.get("achieved"), "peak": rf.get("peak"), "unit": rf.get("unit"), "frac": rf.get("frac"),
+                            "traffic": rf.get("traffic"), "traffic_source": str(rf.get("traffic_source") or "")[:110], "algorithmic_bytes": rf.get("algorithmic_bytes"),
+                            "kernel": str(rf.get("kernel", "")).split(" (")[0], "kernel_ms": rf.get("kernel_ms"),
+                            "hbm_achieved_GBps": _dig(rf, "hbm", "achieved"), "hbm_frac": _dig(rf, "hbm", "frac")}
     if cb:
         line["cpu_baseline"] = {"value": cb.get("value"), "unit": cb.get("unit"), "cores": cb.get("cores"), "kind": cb.get("kind"),
                                 "cpu_model": cb.get("cpu_model"), "single_thread": _dig(cb, "single_thread", "value"),
                                 "sample": "30000-tuple block x reps, OpenSSL 3 ECDSA_do_verify + bccsp/sw gates (proxy: no Go toolchain), median of 5 at the cgroup CPU quota"}
         if "error" in cb:
             line["cpu_baseline"] = {"error": str(cb["error"])[:120]}
-    line["parity"] = str(out.get("parity", ""))[:120]
+    if "parity" in out:
+        line["parity"] = str(out["parity"])[:120]
     extras = {
         "validated_tx_per_s": out.get("validated_tx_per_s"),
         "value_pcie_inclusive": out.get("value_pcie_inclusive"),
@@ -284,7 +289,8 @@ def compact_line(out, detail_path="bench_detail.json"):
             text = json.dumps(line, separators=(",", ":"))
     if len(text) >= COMPACT_LIMIT:
         line["config"]["workload"] = line["config"]["workload"][:40]
-        line["parity"] = line["parity"][:40]
+        if "parity" in line:
+            line["parity"] = line["parity"][:40]
         text = json.dumps(line, separators=(",", ":"))
     return text
 
@@ -1061,7 +1067,10 @@ def main():
     ap.add_argument("--no-two-streams", action="store_true", help="skip the leg that runs two blocks in flight on one GPU (alternating HIP streams; reported as "
                     "value_two_blocks_in_flight, never as `value`)")
     ap.add_argument("--two-streams", action="store_true", help="(accepted for compatibility: the two-blocks-in-flight leg runs by default since round 6)")
-    ap.add_argument("--no-extras", action="store_true", help="only the contract's timed region (no pcie / configs[2] / configs[3] / cpu legs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything else: dispersion, roofline, parity against "
+                    "the generator and the oracle, the pcie / configs[2] / configs[3] / configs[4] / block-pass / cpu legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: dispersion, roofline and parity only (no pcie / configs[2] / configs[3] / cpu legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the verdicts of the last timed step as DIR/verdict.npy (float32; rank 0)")
     ap.add_argument("--tx", type=int, default=N_TX, help="tx per block (default = BASELINE configs[1]; other values are exploration only)")
     ap.add_argument("--pair-table", choices=("auto", "lds", "global"), default="auto", help="where the two-lane verify kernel keeps its per-signature table "
                     "(FABGPU_FLAG_PAIR_TABLE_*; A/B runs - the default decides by batch size)")
@@ -1197,8 +1206,43 @@ def main():
     sync_all()
     dt = max_over_ranks(time.perf_counter() - t0)
     stream_ms_per_step = ev0.elapsed_time(ev1) / args.steps      # HIP events on the launch stream over the timed region
+    ms_per_step = dt / args.steps * 1e3
+    head = {
+        "metric": "ECDSA P-256 verifies/sec (whole node)", "value": n * world / (dt / args.steps), "unit": "verifies/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64",
+        "data": "synthetic" + (" - DRY RUN of the multi-rank code path (FABGPU_BENCH_BACKEND=%s): ranks share devices, numbers are meaningless" % backend if dry else ""),
+        "config": {"workload": ("BASELINE.json configs[1]" if n_tx == N_TX else "EXPLORATION (not the BASELINE config)") + ": block of %d tx x 3 endorsements = %d P-256 tuples per GPU, " % (n_tx, n) +
+                               "verify-only kernel via the C ABI, fresh keypair per signature, 1% invalid" +
+                               ("; %d GPUs = %d such blocks in flight (one per GPU: blocks-in-flight throughput, NOT one block sharded - that is configs2_strong)" % (world, world) if world > 1 else ""),
+                   "tuples_per_gpu": n, "tx_per_block": n_tx, "endorsements_per_tx": N_ENDORSE, "seed": SEED, "clock_warmup_launches": clock_warmup_done,
+                   "parallelism": "1 block per GPU%s" % (" + RCCL all-gather of verdict bitmaps" if world > 1 else "")},
+        "validated_tx_per_s": n_tx * world / (dt / args.steps),
+    }
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned, read back before anything else is launched
+        last = (state["k"] - 1) & 1 if world > 1 else 0
+        dump = {"verdict": fabgpu.unpack_bits(words2[last].cpu().numpy().view(np.uint64), n)}
+        if world > 1:
+            dump["verdict_all_ranks"] = np.concatenate([fabgpu.unpack_bits(w, n) for w in merged2[last].cpu().numpy().view(np.uint64).reshape(world, words_n)])
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a.astype(np.float32))
 
-    # ---- everything below is OUTSIDE the contract's timed region ----
+    def finish():
+        if world > 1:
+            dist.barrier(group=cpu_group)      # ranks > 0 wait here (on the host) while rank 0 runs its extra legs
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        if rank == 0:
+            emit(head)
+        finish()
+        return
+
+    # ---- everything below is OUTSIDE the contract's timed region, and runs with --full only ----
     # per-launch kernel duration (HIP events on the launch stream, one pair per launch): roofline + dispersion
     each = timed_each(stream, verify_only, max(20, min(50, args.steps)))
     kernel_ms = statistics.median(each)
@@ -1296,22 +1340,10 @@ def main():
                 mac_peak_what = "MAC/s of every SIMD issuing independent v_mad_i64_i32 for >= 5 ms, the best of 1 / 2 / 4 wavefronts per SIMD, measured in this run on this box"
             except Exception as e:                                                                     # noqa: BLE001
                 mac_ceiling = {"error": repr(e)[:200]}
-        ms_per_step = dt / args.steps * 1e3
-        total = n * world
-        value = total / (dt / args.steps)
         kernel_s = (stream_ms_per_step if world == 1 else kernel_ms) * 1e-3
         achieved = ALGO_BYTES_PER_VERIFY * n / kernel_s / 1e9
         out = {
-            "metric": "ECDSA P-256 verifies/sec (whole node)", "value": value, "unit": "verifies/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64",
-            "data": "synthetic" + (" - DRY RUN of the multi-rank code path (FABGPU_BENCH_BACKEND=%s): ranks share devices, numbers are meaningless" % backend if dry else ""),
-            "config": {"workload": ("BASELINE.json configs[1]" if n_tx == N_TX else "EXPLORATION (not the BASELINE config)") + ": block of %d tx x 3 endorsements = %d P-256 tuples per GPU, " % (n_tx, n) +
-                                   "verify-only kernel via the C ABI, fresh keypair per signature, 1% invalid" +
-                                   ("; %d GPUs = %d such blocks in flight (one per GPU: blocks-in-flight throughput, NOT one block sharded - that is configs2_strong)" % (world, world) if world > 1 else ""),
-                       "tuples_per_gpu": n, "tx_per_block": n_tx, "endorsements_per_tx": N_ENDORSE, "seed": SEED, "clock_warmup_launches": clock_warmup_done,
-                       "parallelism": "1 block per GPU%s" % (" + RCCL all-gather of verdict bitmaps" if world > 1 else "")},
-            "validated_tx_per_s": n_tx * world / (dt / args.steps),
+            **head,
             "value_from_idle_clocks": from_idle,
             "dispersion": {"median_ms": statistics.median(each), "p95_ms": pctl(each, 0.95), "min_ms": min(each), "iters": len(each),
                            "what": "fabgpu_p256_verify_batch_dev, inputs resident in HBM, one HIP event pair per launch"},
@@ -1451,11 +1483,7 @@ def main():
             except Exception as e:                                                                         # noqa: BLE001
                 out["cpu_baseline"] = {"error": repr(e)[:300]}
         emit(out)
-    if world > 1:
-        dist.barrier(group=cpu_group)      # ranks > 0 wait here (on the host) while rank 0 runs its extra legs
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

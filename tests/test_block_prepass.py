@@ -1,11 +1,12 @@
 """Block-level pre-verify pass: the C++ block walker + x509 key extraction on the CPU, the whole pass
 on the GPU.  Synthetic blocks come from tests/blockbuilder.py (an independent encoder), identities from
 tests/golden/block_identities.json (openssl-generated, test-only keys), signatures from the oracle."""
-import glob
+import base64
 import hashlib
 import json
 import os
 import subprocess
+import tarfile
 
 import numpy as np
 import pytest
@@ -16,7 +17,7 @@ import fabgpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = json.load(open(os.path.join(ROOT, "tests", "golden", "block_identities.json")))["identities"]
-REF = "/root/reference"
+REFDATA = os.path.join(ROOT, "tests", "golden", "ref_testdata.tar.xz")      # the reference's data fixtures (tests/golden/gen_ref_testdata.py)
 
 
 def test_x509_key_extraction_on_generated_identities():
@@ -31,43 +32,47 @@ def test_x509_key_extraction_on_generated_identities():
     assert fabgpu.x509_p256_pubkey(b"not a pem") is None
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
+def _reference_certificates():
+    """the first certificate of every *.pem of the reference (DER): ref_cert_chains.json holds the ECDSA-signed ones, the archive the rest"""
+    ders = [base64.b64decode(c) for c in json.load(open(os.path.join(ROOT, "tests", "golden", "ref_cert_chains.json")))["certs"].values()]
+    with tarfile.open(REFDATA) as tf:
+        ders += [tf.extractfile(m).read() for m in tf.getmembers() if m.name.startswith("certs/")]
+    return ders
+
+
 def test_x509_key_extraction_equals_openssl_on_the_reference_certificates():
     """Every certificate fixture of the reference: the C++ SPKI walker and `openssl x509 -pubkey` agree on (curve, Qx, Qy)."""
-    pems = sorted(glob.glob(REF + "/**/*.pem", recursive=True))
     checked = 0
-    for path in pems:
-        txt = open(path, "rb").read()
-        if b"BEGIN CERTIFICATE" not in txt:
-            continue
-        r = subprocess.run(["openssl", "x509", "-in", path, "-noout", "-text"], capture_output=True, text=True)
+    for der in _reference_certificates():
+        b64 = base64.b64encode(der)
+        txt = b"-----BEGIN CERTIFICATE-----\n" + b"".join(b64[i:i + 64] + b"\n" for i in range(0, len(b64), 64)) + b"-----END CERTIFICATE-----\n"
+        r = subprocess.run(["openssl", "x509", "-noout", "-text"], input=txt, capture_output=True)
         if r.returncode != 0:
             continue
-        is_p256 = "ASN1 OID: prime256v1" in r.stdout
+        text = r.stdout.decode()
+        is_p256 = "ASN1 OID: prime256v1" in text
         got = fabgpu.x509_p256_pubkey(txt)
-        assert (got is not None) == is_p256, path
+        assert (got is not None) == is_p256, hashlib.sha256(der).hexdigest()
         if is_p256:
             import re
-            pub = re.sub(r"[^0-9a-f]", "", re.search(r"pub:\s*((?:[0-9a-f:]+\s*)+)ASN1 OID", r.stdout).group(1))
-            assert got[0].hex() == pub[2:66] and got[1].hex() == pub[66:130], path
+            pub = re.sub(r"[^0-9a-f]", "", re.search(r"pub:\s*((?:[0-9a-f:]+\s*)+)ASN1 OID", text).group(1))
+            assert got[0].hex() == pub[2:66] and got[1].hex() == pub[66:130], hashlib.sha256(der).hexdigest()
             checked += 1
     assert checked >= 100
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 def test_block_walker_on_the_reference_block_fixtures():
     """The reference's own marshalled blocks pin the outer layers of the walker (Block, BlockData, Envelope, Payload, Header,
     ChannelHeader, SignatureHeader): one CONFIG envelope on the expected channel."""
     seen = 0
-    for path, channel in ((REF + "/orderer/common/cluster/testdata/mychannel.block", "mychannel"),
-                          (REF + "/orderer/consensus/etcdraft/testdata/mychannel.block", "mychannel")):
-        if not os.path.exists(path):
-            continue
-        p = fabgpu.block_parse(open(path, "rb").read())
-        assert p["n_tx"] == 1 and p["channel_id"] == channel and list(p["tx_type"]) == [1]      # HeaderType CONFIG
-        assert p["n_prefixes"] == 0 and p["n_tuples"] <= 1
-        seen += 1
-    assert seen >= 1
+    with tarfile.open(REFDATA) as tf:
+        for path, channel in (("orderer/common/cluster/testdata/mychannel.block", "mychannel"),
+                              ("orderer/consensus/etcdraft/testdata/mychannel.block", "mychannel")):
+            p = fabgpu.block_parse(tf.extractfile(path).read())
+            assert p["n_tx"] == 1 and p["channel_id"] == channel and list(p["tx_type"]) == [1]      # HeaderType CONFIG
+            assert p["n_prefixes"] == 0 and p["n_tuples"] <= 1
+            seen += 1
+    assert seen == 2
 
 
 def _sign(ident, msg, k):

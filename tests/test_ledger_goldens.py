@@ -24,7 +24,6 @@ import fabgpu
 import fabric_decode as fd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 FIX = json.load(open(os.path.join(ROOT, "tests", "golden", "ledger_blocks.json")))["blocks"]
 BLOCKS = [(b, base64.b64decode(b["block_b64"])) for b in FIX]
 V20 = [(b, raw) for b, raw in BLOCKS if b["source"] == "v20"]
@@ -51,15 +50,26 @@ def cut(arena, span):
     return arena[span[0]:span[0] + span[1]]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 def test_fixture_file_is_what_the_generator_extracts_from_the_reference(tmp_path):
+    """The generator, run over the block files of the reference's sample ledger archives (tests/golden/ref_testdata.tar.xz, packed
+    back into archives of their own), writes exactly the committed ledger_blocks.json."""
     import subprocess
     import sys
+    import tarfile
+    import zipfile
+    ref = tmp_path / "reference"
+    with tarfile.open(os.path.join(ROOT, "tests", "golden", "ref_testdata.tar.xz")) as tf:
+        for m in tf.getmembers():
+            if ".zip/" in m.name:
+                rel, member = m.name.split(".zip/")
+                (ref / rel).parent.mkdir(parents=True, exist_ok=True)
+                with zipfile.ZipFile(ref / (rel + ".zip"), "a") as zf:
+                    zf.writestr(member, tf.extractfile(m).read())
     gen = os.path.join(ROOT, "tests", "golden", "gen_ledger_block_fixtures.py")
     src = open(gen).read().replace('os.path.join(os.path.dirname(os.path.abspath(__file__)), "ledger_blocks.json")', repr(str(tmp_path / "out.json")))
     p = tmp_path / "gen.py"
     p.write_text(src)
-    subprocess.run([sys.executable, str(p), REF], check=True, capture_output=True)
+    subprocess.run([sys.executable, str(p), str(ref)], check=True, capture_output=True)
     assert json.load(open(tmp_path / "out.json")) == json.load(open(os.path.join(ROOT, "tests", "golden", "ledger_blocks.json")))
 
 

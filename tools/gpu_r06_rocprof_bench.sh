@@ -8,7 +8,7 @@ O=$R/gpurun_out
 mkdir -p $O
 for i in 1 2; do
   rm -rf /tmp/prof_bench
-  ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_rocprof_run${i}.out 2> $O/r06_rocprof_run${i}.err )
+  ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r06_rocprof_run${i}.out 2> $O/r06_rocprof_run${i}.err )
   tail -n1 $O/r06_rocprof_run${i}.out > $O/r06_rocprof_run${i}_line.json
   f=$(find /tmp/prof_bench -name "*.db" -printf "%s %p\n" 2>/dev/null | sort -n | tail -1 | cut -d" " -f2)
   python $R/profiles/summarize_rocprof.py "$f" > $O/r06_rocprof_run${i}_stats.txt 2>&1
