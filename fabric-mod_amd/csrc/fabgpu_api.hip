@@ -131,6 +131,7 @@ struct fabgpu_ctx {
     bool nym_two_phase = true;   // !FABGPU_FLAG_NYM_FUSED_HASH (idemix four-lane form: commitments, then challenges with eight lanes on a message)
     bool allow_wide = true;   // !FABGPU_FLAG_NO_WIDE (registered keys: eight lanes per signature in two phases for launches <= WIDE_LAUNCH_MAX)
     int pair_table_lds = -1;       // the verify-only pair kernel's per-signature table: 1 in LDS, 0 in the global workspace, -1 by batch size (kernels.h)
+    bool pair_solo = false;        // FABGPU_FLAG_PAIR_SOLO: the LDS-table pair kernel without helper waves
     hipStream_t stream = nullptr;
     // FABGPU_FAULT_INJECT (tests of the failure contract only): "launch" makes every kernel submission report hipErrorLaunchFailure,
     // "oom" makes every workspace / staging allocation fail.  A non-zero return must then reach the caller and no verdict may be written.
@@ -371,7 +372,7 @@ int fabgpu_init(const fabgpu_cfg* cfg, fabgpu_ctx** out) {
     *out = nullptr;
     if (cfg && (cfg->flags & ~(uint32_t)(FABGPU_FLAG_ONE_LANE_ONLY | FABGPU_FLAG_TIME_KERNELS | FABGPU_FLAG_NO_QUAD | FABGPU_FLAG_PAIR_TABLE_LDS |
                                           FABGPU_FLAG_PAIR_TABLE_GLOBAL | FABGPU_FLAG_NO_WIDE | FABGPU_FLAG_NYM_FUSED_HASH | FABGPU_FLAG_NYM_NO_SIDE_STREAM |
-                                          FABGPU_FLAG_KEY_TABLES_16BIT)) != 0) return FABGPU_EINVAL;
+                                          FABGPU_FLAG_KEY_TABLES_16BIT | FABGPU_FLAG_PAIR_SOLO)) != 0) return FABGPU_EINVAL;
     if (cfg && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_LDS) && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_GLOBAL)) return FABGPU_EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return FABGPU_ENODEV;
@@ -395,10 +396,13 @@ int fabgpu_init(const fabgpu_cfg* cfg, fabgpu_ctx** out) {
     // (the wide form is built from the two-lane form's reasons: a context that may not use two lanes per signature does not use eight)
     ctx->allow_wide = ctx->allow_pair && !(cfg && (cfg->flags & FABGPU_FLAG_NO_WIDE));
     ctx->pair_table_lds = cfg && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_LDS) ? 1 : (cfg && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_GLOBAL) ? 0 : pair_table_default());
-    // The LDS form of the pair kernel asks for 130 KiB of dynamic LDS per workgroup (p256_pair29.h PAIR_LDS_CELLS_PER_SIG): a device that
-    // grants less keeps the table in the global workspace instead of failing every large launch.  (That allocation is also
-    // what keeps other kernels off the launch's CUs - more than the 84 KiB the pass reserves for that purpose.)
-    if (std::max<size_t>(prop.sharedMemPerBlock, prop.maxSharedMemoryPerMultiProcessor) < pair_table_lds_bytes()) ctx->pair_table_lds = 0;
+    ctx->pair_solo = cfg && (cfg->flags & FABGPU_FLAG_PAIR_SOLO);
+    // The LDS form of the pair kernel asks for 157 KiB of dynamic LDS per workgroup (130 KiB of tables, p256_pair29.h PAIR_LDS_CELLS_PER_SIG,
+    // and the helper waves' handoff, PAIR_HAND_WORDS; 130 KiB in the one-wave form): a device that grants less keeps the table in the
+    // global workspace instead of failing every large launch.  (That allocation is also what keeps other kernels off the
+    // launch's CUs - more than the 84 KiB the pass reserves for that purpose.)
+    if (std::max<size_t>(prop.sharedMemPerBlock, prop.maxSharedMemoryPerMultiProcessor) < (ctx->pair_solo ? pair_table_lds_solo_bytes() : pair_table_lds_bytes()))
+        ctx->pair_table_lds = 0;
     ctx->time_kernels = cfg && (cfg->flags & FABGPU_FLAG_TIME_KERNELS);
     DeviceGuard g(dev);
     int rc = FABGPU_OK;
@@ -563,7 +567,7 @@ int fabgpu_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* qx, cons
     int rc = ctx->acquire_qws(verify_workspace_bytes((uint32_t)n, ctx->allow_pair), &wi, &wsp, st);
     if (rc != FABGPU_OK) return rc;
     if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    hipError_t err = launch_p256_verify((uint32_t)n, qx, qy, e, r, s, ctx->d_gtab, wsp, verdict_bits, status, ctx->allow_pair, st, 0, ctx->pair_table_lds);
+    hipError_t err = launch_p256_verify((uint32_t)n, qx, qy, e, r, s, ctx->d_gtab, wsp, verdict_bits, status, ctx->allow_pair, st, 0, ctx->pair_table_lds, ctx->pair_solo);
     if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
     ctx->release_qws(wi, st);
     ctx->timed = ctx->time_kernels;
@@ -2602,7 +2606,8 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
             void* wsp = nullptr;
             int r2 = ctx->acquire_qws(verify_workspace_bytes(tot.creators, true), &wi, &wsp, s2);
             if (r2 != FABGPU_OK) return r2;
-            e = launch_p256_verify(tot.creators, a.qx, a.qy, dt + o_dig, a.r, a.s, ctx->d_gtab, wsp, dt + o_bitc, dt + o_dst, true, s2, exclusive ? 84u << 10 : 0u, ctx->pair_table_lds);
+            e = launch_p256_verify(tot.creators, a.qx, a.qy, dt + o_dig, a.r, a.s, ctx->d_gtab, wsp, dt + o_bitc, dt + o_dst, true, s2, exclusive ? 84u << 10 : 0u, ctx->pair_table_lds,
+                                   ctx->pair_solo);
             ctx->release_qws(wi, s2);
         }
         return hip_to_rc(e);

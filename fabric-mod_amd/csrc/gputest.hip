@@ -343,3 +343,27 @@ extern "C" int gputest_mac_ceiling(int waves_per_simd, uint32_t iters, double* o
     hipFree(d);
     return rc;
 }
+
+// ---- wave placement of a 512-thread workgroup --------------------------------------------------------------------------------------
+// The helper-wave pair kernel (kernels.hip p256_verify_pair_lds_kernel) assumes that wavefront k and wavefront k + 4 of its 512-thread
+// workgroup share a SIMD (main wave k and helper wave k + 4 serve the same signatures).  This probe launches workgroups of that shape
+// with the same dynamic LDS (one workgroup per CU) and records the HW_ID register (a read: s_getreg_b32) of every wavefront:
+// out[8 g + w] = HW_ID of wavefront w of workgroup g (bits 5:4 SIMD, 11:8 CU, 12 SH, 15:13 SE).  Placement decides speed only.
+__global__ void __launch_bounds__(512, 1) gputest_wave_placement_kernel(uint32_t* __restrict__ out) {
+    extern __shared__ uint32_t placement_lds[];
+    const uint32_t id = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // hwreg(HW_REG_HW_ID, 0, 32)
+    placement_lds[threadIdx.x] = id;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) out[blockIdx.x * 8 + (threadIdx.x >> 6)] = placement_lds[threadIdx.x];
+}
+
+extern "C" int gputest_wave_placement(uint32_t wgs, uint32_t lds_bytes, uint32_t* out) {
+    if (!out || wgs == 0 || lds_bytes < 512 * 4) return 1;
+    uint32_t* d = nullptr;
+    if (hipMalloc(&d, sizeof(uint32_t) * 8 * wgs) != hipSuccess) return 3;
+    hipLaunchKernelGGL(gputest_wave_placement_kernel, dim3(wgs), dim3(512), lds_bytes, 0, d);
+    int rc = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : 4;
+    if (rc == 0 && hipMemcpy(out, d, sizeof(uint32_t) * 8 * wgs, hipMemcpyDeviceToHost) != hipSuccess) rc = 5;
+    hipFree(d);
+    return rc;
+}

@@ -125,9 +125,10 @@ __global__ void __launch_bounds__(BLOCK, 1) p256_verify_pair_kernel(uint32_t n, 
 }
 
 // The same with the per-signature table in LDS (PairQTabLds: 8 entries, signed 4-bit windows) instead of the global workspace: no
-// table traffic at all (p256_pair29.h says what that is worth).  Dynamic LDS: 128 signatures x 1040 bytes.
+// table traffic at all (p256_pair29.h says what that is worth).  Dynamic LDS: 128 signatures x 1040 bytes.  One wave per SIMD: the
+// A/B form of the helper-wave kernel below (FABGPU_FLAG_PAIR_SOLO).
 template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK, 1) p256_verify_pair_lds_kernel(uint32_t n, const uint8_t* __restrict__ qx, const uint8_t* __restrict__ qy,
+__global__ void __launch_bounds__(BLOCK, 1) p256_verify_pair_lds_solo_kernel(uint32_t n, const uint8_t* __restrict__ qx, const uint8_t* __restrict__ qy,
                                                                              const uint8_t* __restrict__ e, const uint8_t* __restrict__ r,
                                                                              const uint8_t* __restrict__ s, const int32_t* __restrict__ gtab,
                                                                              uint64_t* __restrict__ verdict_bits, uint8_t* __restrict__ status) {
@@ -150,6 +151,64 @@ __global__ void __launch_bounds__(BLOCK, 1) p256_verify_pair_lds_kernel(uint32_t
         load_be_field(vs, s, ic);
         uint32_t st = p256_verify_pair29<PairQTabLds, 4>(vqx, vqy, ve, vr, vs, gtab, qtab, odd);
         pair_emit_verdict(i, n, active, odd, st, verdict32, status);
+    }
+}
+
+// The LDS-table pair kernel with HELPER WAVES (p256_pair29.h, "HELPER-WAVE FORM"): 2 x BLOCK threads, the same 128 signatures per
+// tile.  Threads 0..BLOCK-1 (main) run the u2*Q chain and emit the verdicts; threads BLOCK..2 BLOCK-1 (helper) run s^-1, u1, u2 and
+// u1*G on the same SIMDs and hand u2 and S over through LDS.  Every wave reaches both barriers of every tile (tail lanes compute on
+// the last tuple, as in the other kernels).  Dynamic LDS: pair_table_lds_bytes().
+template <int BLOCK>
+__global__ void __launch_bounds__(2 * BLOCK, 1) p256_verify_pair_lds_kernel(uint32_t n, const uint8_t* __restrict__ qx, const uint8_t* __restrict__ qy,
+                                                                                 const uint8_t* __restrict__ e, const uint8_t* __restrict__ r,
+                                                                                 const uint8_t* __restrict__ s, const int32_t* __restrict__ gtab,
+                                                                                 uint64_t* __restrict__ verdict_bits, uint8_t* __restrict__ status) {
+    extern __shared__ uint4 pair_lds[];
+    constexpr int NP = BLOCK / 2;
+    // wave-uniform by construction (BLOCK is a multiple of 64); readfirstlane makes the role a scalar branch for the compiler too
+    const bool helper = __builtin_amdgcn_readfirstlane(threadIdx.x) >= (uint32_t)BLOCK;
+    const uint32_t lane = threadIdx.x & (uint32_t)(BLOCK - 1);
+    const bool odd = (lane & 1) != 0;
+    const uint32_t pairidx = lane >> 1;
+    PairQTabLds qtab = PairQTabLds::of(pair_lds, pairidx);
+    const PairHandoffLds<BLOCK> hand = PairHandoffLds<BLOCK>::of(reinterpret_cast<uint32_t*>(pair_lds + NP * PAIR_LDS_CELLS_PER_SIG), lane);
+    uint32_t* verdict32 = reinterpret_cast<uint32_t*>(verdict_bits);
+    const uint32_t ntiles = (n + NP - 1) / NP;
+    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        uint32_t i = tile * NP + pairidx;
+        bool active = i < n;
+        uint32_t ic = active ? i : (n - 1);
+        u256 u1;                      // helper
+        uint32_t early = 0;           // helper: range gates
+        pair_pt Qp, T;                // main
+        bool q_ok = false, t_inf = true;
+        if (helper) {
+            u256 ve, vr, vs;
+            load_be_field(ve, e, ic);
+            load_be_field(vr, r, ic);
+            load_be_field(vs, s, ic);
+            pair_helper_scalars29(u1, early, ve, vr, vs, hand, odd);
+        } else {
+            u256 vqx, vqy;
+            load_be_field(vqx, qx, ic);
+            load_be_field(vqy, qy, ic);
+            q_ok = pair_main_table29(Qp, vqx, vqy, qtab, odd);
+        }
+        __syncthreads();              // A: u2 in LDS
+        if (helper) {
+            pair_helper_comb29(u1, early, gtab, hand, odd);
+        } else {
+            u256 u2;
+            hand.get_u2(u2);
+            pair_u2_mult29<PairQTabLds, 4>(T, t_inf, u2, Qp, qtab, odd);
+        }
+        __syncthreads();              // B: S, s_inf and the gate status in LDS
+        if (!helper) {
+            u256 vr;                  // (loaded here, not kept in registers across the chain)
+            load_be_field(vr, r, ic);
+            uint32_t st = pair_main_finish29(T, t_inf, q_ok, vr, hand, odd);
+            pair_emit_verdict(i, n, active, odd, st, verdict32, status);
+        }
     }
 }
 
@@ -431,14 +490,17 @@ VerifyGeom verify_geom(uint32_t n, bool allow_pair) {
 // Where the two-lanes-per-signature verify-only kernel keeps its per-signature table when the context does not say
 // (FABGPU_FLAG_PAIR_TABLE_LDS / _GLOBAL in fabgpu_cfg.flags force one; bench.py --pair-table for A/B runs): -1 = by batch size (launch_p256_verify).
 int pair_table_default() { return -1; }
-size_t pair_table_lds_bytes() { return (size_t)(VERIFY_BLOCK / 2) * PAIR_LDS_CELLS_PER_SIG * 16; }
+// helper-wave form: the 128 tables + the handoff (PAIR_HAND_WORDS per main lane) = 133 120 + 27 648 = 160 768 bytes of the CU's 163 840
+size_t pair_table_lds_bytes() { return (size_t)(VERIFY_BLOCK / 2) * PAIR_LDS_CELLS_PER_SIG * 16 + (size_t)VERIFY_BLOCK * PAIR_HAND_WORDS * 4; }
+size_t pair_table_lds_solo_bytes() { return (size_t)(VERIFY_BLOCK / 2) * PAIR_LDS_CELLS_PER_SIG * 16; }
 size_t verify_workspace_bytes(uint32_t n, bool allow_pair) {
     VerifyGeom g = verify_geom(n, allow_pair);
     if (g.pair) return (size_t)g.wgs * (g.block / 2) * QWS_PAIR_UINT4_PER_SIG * 16;
     return (size_t)g.wgs * g.block * QWS_UINT4_PER_LANE * 16;
 }
 hipError_t launch_p256_verify(uint32_t n, const void* qx, const void* qy, const void* e, const void* r, const void* s,
-                              const void* gtab, void* qws, void* verdict_bits, void* status, bool allow_pair, hipStream_t st, uint32_t lds_reserve, int table_lds) {
+                              const void* gtab, void* qws, void* verdict_bits, void* status, bool allow_pair, hipStream_t st, uint32_t lds_reserve, int table_lds,
+                              bool pair_solo) {
     if (n == 0) return hipSuccess;
     VerifyGeom g = verify_geom(n, allow_pair);
     dim3 grid(g.wgs), block(g.block);
@@ -447,8 +509,15 @@ hipError_t launch_p256_verify(uint32_t n, const void* qx, const void* qy, const 
     // moves 94 MB through the memory system per launch instead of 279 MB); in the global workspace for smaller ones, where the LDS
     // form's 13 extra additions show as latency (10 000 tuples: 0.624 against 0.614 ms; 1 000: 0.618 against 0.603 ms).
     if (table_lds < 0) table_lds = n > (uint32_t)PAIR_TABLE_LDS_FROM ? 1 : 0;
+    // The LDS form with helper waves (two waves per SIMD: the scalar part and u1*G beside the u2*Q chain) unless the context asks for
+    // the one-wave form (FABGPU_FLAG_PAIR_SOLO, A/B runs).
+    if (g.pair && table_lds && !pair_solo) {
+        hipLaunchKernelGGL(p256_verify_pair_lds_kernel<VERIFY_BLOCK>, grid, dim3(2 * VERIFY_BLOCK), pair_table_lds_bytes(), st, n, (const uint8_t*)qx,
+                           (const uint8_t*)qy, (const uint8_t*)e, (const uint8_t*)r, (const uint8_t*)s, (const int32_t*)gtab, (uint64_t*)verdict_bits, (uint8_t*)status);
+        return hipGetLastError();
+    }
     if (g.pair && table_lds) {
-        hipLaunchKernelGGL(p256_verify_pair_lds_kernel<VERIFY_BLOCK>, grid, block, (size_t)(VERIFY_BLOCK / 2) * PAIR_LDS_CELLS_PER_SIG * 16, st, n, (const uint8_t*)qx,
+        hipLaunchKernelGGL(p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK>, grid, block, pair_table_lds_solo_bytes(), st, n, (const uint8_t*)qx,
                            (const uint8_t*)qy, (const uint8_t*)e, (const uint8_t*)r, (const uint8_t*)s, (const int32_t*)gtab, (uint64_t*)verdict_bits, (uint8_t*)status);
         return hipGetLastError();
     }
@@ -520,7 +589,8 @@ int warm_kernel_functions_kernels() {
     int ok = 0;
     hipFuncAttributes a;
     const void* fns[] = {(const void*)p256_verify_kernel<VERIFY_BLOCK>, (const void*)p256_verify_pair_kernel<VERIFY_BLOCK>,
-                         (const void*)p256_verify_pair_lds_kernel<VERIFY_BLOCK>, (const void*)p256_verify_keyed_kernel<VERIFY_BLOCK>,
+                         (const void*)p256_verify_pair_lds_kernel<VERIFY_BLOCK>, (const void*)p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK>,
+                         (const void*)p256_verify_keyed_kernel<VERIFY_BLOCK>,
                          (const void*)p256_verify_keyed_pair_kernel<VERIFY_BLOCK>, (const void*)sha256_p256_verify_keyed_kernel<VERIFY_BLOCK>,
                          (const void*)sha256_p256_verify_keyed_pair_kernel<VERIFY_BLOCK>, (const void*)sha256_p256_verify_pair_kernel<VERIFY_BLOCK>,
                          (const void*)sha256_p256_verify_kernel<VERIFY_BLOCK>, (const void*)sha256_midstate_kernel, (const void*)gather_spans_kernel};

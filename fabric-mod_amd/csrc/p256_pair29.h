@@ -343,19 +343,11 @@ __device__ __forceinline__ void pair_final_add29(pair_pt& Rr, bool& r_inf, const
 // |d| == n (mod 2^W).  n mod 32 = 17 > 16: never for W = 5.  n mod 16 = 1: for W = 4 EXACTLY ONE scalar, u2 = n - 2
 // (digit -1 on top of M = n - 1: T = -Q, addend -Q).  That scalar is recognised up front and its product, -2Q, is taken from the
 // table (entry 2, negated) instead of from the loop.
+// Per-signature table j*Q, j = 1..2^(W-1), from Q in pair state (first part of pair_combined_mult29).
 template <class QTab, int W = 5>
-__device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, const u256& u1, const u256& u2, const fe& QX, const fe& QY,
-                                                     const int32_t* __restrict__ gtab, const QTab& qtab, bool odd) {
-    static_assert(W == 4 || W == 5, "signed 4- or 5-bit windows");
-    constexpr int TAB = 1 << (W - 1);                 // entries j*Q, j = 1..TAB
-    constexpr int NWIN = (257 + W - 1) / W;           // windows over bits -1 .. 256 of a scalar below n
-    const fe ONE = {FE29_R1};
+__device__ __forceinline__ void pair_qtab_build29(const pair_pt& Qp, const fe& QX, const fe& QY, const QTab& qtab, bool odd) {
+    constexpr int TAB = 1 << (W - 1);
     PAIR_TMPS;
-    pair_pt Qp;
-    Qp.A = QX;
-    fe_sel(Qp.B, odd, ONE, QY);
-
-    // --- per-signature table j*Q, j = 1..TAB ---
     qtab.store_state(1, Qp, odd);
 #pragma unroll 1
     for (int j = 2; j <= TAB; j += 2) {
@@ -369,14 +361,21 @@ __device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, c
             qtab.store_state(j + 1, d1, odd);
         }
     }
+}
 
-    // --- T = u2 * Q : NWIN signed W-bit windows (same recoding as p256_combined_mult29 for W = 5) ---
+// T = u2 * Q over the table pair_qtab_build29 wrote (second part of pair_combined_mult29): NWIN signed W-bit windows, the same
+// recoding as p256_combined_mult29 for W = 5, and for W = 4 the scalar u2 = n - 2 (see pair_combined_mult29).
+template <class QTab, int W = 5>
+__device__ __forceinline__ void pair_u2_mult29(pair_pt& T, bool& t_inf, const u256& u2, const pair_pt& Qp, const QTab& qtab, bool odd) {
+    constexpr int TAB = 1 << (W - 1);                 // entries j*Q, j = 1..TAB
+    constexpr int NWIN = (257 + W - 1) / W;           // windows over bits -1 .. 256 of a scalar below n
+    PAIR_TMPS;
     uint32_t kw[9];
 #pragma unroll
     for (int i = 0; i < 8; i++) kw[i] = u2.w[i];
     kw[8] = 0;
-    pair_pt T = Qp;
-    bool t_inf = true;
+    T = Qp;
+    t_inf = true;
 #pragma unroll 1
     for (int i = NWIN - 1; i >= 0; i--) {
         uint32_t field;                               // bits W i - 1 .. W i + W - 1 of the scalar (bit -1 = 0)
@@ -418,7 +417,7 @@ __device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, c
         t_inf = t_inf & (mag == 0);
     }
     if (W == 4) {
-        // u2 = n - 2: the one scalar whose last addition is a doubling (see above).  (n - 2) Q = -2Q: entry 2, Y negated.
+        // u2 = n - 2: the one scalar whose last addition is a doubling (see pair_combined_mult29).  (n - 2) Q = -2Q: entry 2, Y negated.
         const u256 NM2 = {{0xFC63254Fu, 0xF3B9CAC2u, 0xA7179E84u, 0xBCE6FAADu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0x00000000u, 0xFFFFFFFFu}};
         bool special = true;
 #pragma unroll
@@ -433,6 +432,30 @@ __device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, c
             pair_sel(T, special, two, T);
         }
     }
+}
+
+// R = u1*G + u2*Q on a lane pair.  Q: affine Montgomery (both lanes hold both coordinates).  Returns the pair state of R;
+// r_inf as in p256_combined_mult29.  W = width of the signed (Booth) windows over u2: 5 (a 16-entry table j*Q, 52 windows: the
+// global-workspace table) or 4 (8 entries, 65 windows: the LDS table).
+//
+// No addition inside the loop may meet P == +-Q (the addition formulas do not handle it).  Before window i is added T = M Q with M a
+// non-zero multiple of 2^W and the addend is d Q, |d| <= 2^(W-1).  M == +-d (mod n) needs M = n +- |d| (M >= 2^W > |d|), possible
+// only at the last window, where M = u2 - d: M = n - d gives u2 = n, impossible; M = n + d with d < 0 gives u2 = n - 2|d| and needs
+// |d| == n (mod 2^W).  n mod 32 = 17 > 16: never for W = 5.  n mod 16 = 1: for W = 4 EXACTLY ONE scalar, u2 = n - 2
+// (digit -1 on top of M = n - 1: T = -Q, addend -Q).  That scalar is recognised up front and its product, -2Q, is taken from the
+// table (entry 2, negated) instead of from the loop.
+template <class QTab, int W = 5>
+__device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, const u256& u1, const u256& u2, const fe& QX, const fe& QY,
+                                                     const int32_t* __restrict__ gtab, const QTab& qtab, bool odd) {
+    static_assert(W == 4 || W == 5, "signed 4- or 5-bit windows");
+    const fe ONE = {FE29_R1};
+    pair_pt Qp;
+    Qp.A = QX;
+    fe_sel(Qp.B, odd, ONE, QY);
+    pair_qtab_build29<QTab, W>(Qp, QX, QY, qtab, odd);
+    pair_pt T;
+    bool t_inf;
+    pair_u2_mult29<QTab, W>(T, t_inf, u2, Qp, qtab, odd);
 
     // --- S = u1 * G (16-bit comb), then R = S + T ---
     pair_pt S;
@@ -519,6 +542,110 @@ __device__ __forceinline__ uint32_t p256_verify_keyed_pair29(const u256& e, cons
     bool r_inf;
     if (__all(ktab16 != nullptr)) pair_combined_mult_keyed29<GTab16>(Rr, r_inf, u1, u2, gtab, ktab16, odd);
     else pair_combined_mult_keyed29<KeyTab8>(Rr, r_inf, u1, u2, gtab, ktab, odd);
+    bool ok = pair_x_equals_r29(Rr, r_inf, r);
+    uint32_t st = ok ? ST_VALID : ST_BAD_MATH;
+    return early != ST_VALID ? early : st;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// HELPER-WAVE FORM of the LDS-table pair kernel (p256_verify_pair_lds_kernel: 512 threads, two waves per SIMD).  The 256 doublings of
+// u2*Q are one serial chain; the inversion s^-1 mod n, u1 and u2, and u1*G on the 16-bit comb do not depend on it.  A workgroup
+// therefore runs two roles over the same 128 signatures: MAIN waves (threads 0..255) gate Q, build the 8-entry LDS table, run the
+// 65 windows and the final addition and check; HELPER waves (threads 256..511, lane t + 256 serves the same signature and the same
+// lane-pair parity as main lane t) do the scalar part and u1*G beside them, in the issue slots a lone wave per SIMD leaves idle.
+// Per tile (A, B: workgroup barriers):
+//     helper:  range gates, s^-1, u1, u2 -> u2 to LDS           | A |  u1*G -> S, s_inf, gate status to LDS | B |
+//     main:    Q gates, table j*Q                               | A |  u2 from LDS, T = u2*Q               | B |  S from LDS, R = S + T, x(R) == r
+// The two handoff regions are disjoint: the helper writes the next tile's u2 after B, when main has read this tile's; it writes the next
+// tile's S after the next A, when main has read this tile's.  Two barriers per tile suffice.
+// Layout after the 128 tables: word w of lane t (0..255) at word w * 256 + t (consecutive lanes, consecutive banks).
+constexpr int PAIR_HAND_U2_WORDS = 8;                   // u2
+constexpr int PAIR_HAND_S_WORDS = 9 + 9 + 1;            // S.A, S.B, s_inf | gate status << 1
+constexpr int PAIR_HAND_WORDS = PAIR_HAND_U2_WORDS + PAIR_HAND_S_WORDS;
+
+template <int LANES>
+struct PairHandoffLds {
+    uint32_t* u2;   // (LDS) this lane's first u2 word
+    uint32_t* s;    // (LDS) this lane's first S word
+    static __device__ __forceinline__ PairHandoffLds of(uint32_t* base, uint32_t lane) {
+        return PairHandoffLds{base + lane, base + PAIR_HAND_U2_WORDS * LANES + lane};
+    }
+    __device__ __forceinline__ void put_u2(const u256& v) const {
+#pragma unroll
+        for (int w = 0; w < 8; w++) u2[w * LANES] = v.w[w];
+    }
+    __device__ __forceinline__ void get_u2(u256& v) const {
+#pragma unroll
+        for (int w = 0; w < 8; w++) v.w[w] = u2[w * LANES];
+    }
+    __device__ __forceinline__ void put_s(const pair_pt& S, bool s_inf, uint32_t early) const {
+#pragma unroll
+        for (int l = 0; l < 9; l++) s[l * LANES] = (uint32_t)S.A.v[l];
+#pragma unroll
+        for (int l = 0; l < 9; l++) s[(9 + l) * LANES] = (uint32_t)S.B.v[l];
+        s[18 * LANES] = (s_inf ? 1u : 0u) | (early << 1);
+    }
+    __device__ __forceinline__ void get_s(pair_pt& S, bool& s_inf, uint32_t& early) const {
+#pragma unroll
+        for (int l = 0; l < 9; l++) S.A.v[l] = (int32_t)s[l * LANES];
+#pragma unroll
+        for (int l = 0; l < 9; l++) S.B.v[l] = (int32_t)s[(9 + l) * LANES];
+        uint32_t f = s[18 * LANES];
+        s_inf = (f & 1u) != 0;
+        early = f >> 1;
+    }
+};
+
+// Helper, before barrier A: range gates and the scalars; u2 goes to LDS, u1 and the gate status stay.
+template <class Hand>
+__device__ __forceinline__ void pair_helper_scalars29(u256& u1, uint32_t& early, const u256& e, const u256& r, const u256& s, const Hand& hand,
+                                                      bool odd) {
+    early = range_status(r, s);
+    u256 u2;
+    pair_ecdsa_scalars29(u1, u2, e, r, s, odd);
+    hand.put_u2(u2);
+}
+
+// Helper, between A and B: S = u1*G on the 16-bit comb (seeded with G: the seed is any valid point, and this role has no Q), to LDS.
+template <class Hand>
+__device__ __forceinline__ void pair_helper_comb29(const u256& u1, uint32_t early, const int32_t* __restrict__ gtab, const Hand& hand, bool odd) {
+    const fe ONE = {FE29_R1};
+    fe gx, gy;
+    GTab16 gt{gtab};
+    gt.load(0, 1u, gx, gy);
+    pair_pt seed, S;
+    seed.A = gx;
+    fe_sel(seed.B, odd, ONE, gy);
+    bool s_inf;
+    pair_comb_mult29<GTab16>(S, s_inf, u1, gtab, seed, odd);
+    hand.put_s(S, s_inf, early);
+}
+
+// Main, before barrier A: Q gates and the table.  Returns q_ok; Qp = Q in pair state.
+template <class QTab>
+__device__ __forceinline__ bool pair_main_table29(pair_pt& Qp, const u256& qx, const u256& qy, const QTab& qtab, bool odd) {
+    const u256 P = FAB_P256_P;
+    const fe ONE = {FE29_R1};
+    bool q_in_field = lt256(qx, P) & lt256(qy, P);
+    fe QX, QY;
+    fe_to_mont(QX, qx);
+    fe_to_mont(QY, qy);
+    bool q_ok = q_in_field & on_curve29(QX, QY);
+    Qp.A = QX;
+    fe_sel(Qp.B, odd, ONE, QY);
+    pair_qtab_build29<QTab, 4>(Qp, QX, QY, qtab, odd);
+    return q_ok;
+}
+
+// Main, after barrier B: R = S + T, x(R) == r, and the status (valid on the EVEN lane) exactly as p256_verify_pair29 combines it.
+template <class Hand>
+__device__ __forceinline__ uint32_t pair_main_finish29(const pair_pt& T, bool t_inf, bool q_ok, const u256& r, const Hand& hand, bool odd) {
+    pair_pt S, Rr;
+    bool s_inf, r_inf;
+    uint32_t early;
+    hand.get_s(S, s_inf, early);
+    if (early == ST_VALID && !q_ok) early = ST_OFF_CURVE;
+    pair_final_add29(Rr, r_inf, S, s_inf, T, t_inf, odd);
     bool ok = pair_x_equals_r29(Rr, r_inf, r);
     uint32_t st = ok ? ST_VALID : ST_BAD_MATH;
     return early != ST_VALID ? early : st;
