@@ -1,6 +1,9 @@
-// GPU-SIDE TEST HOOKS - built into libfabgpu_gputest.so, never into the product library.  They run single generated
-// instruction streams (pair29_gcn.h) on one wavefront so that tests/test_gpu_parity.py can compare every output register
-// with the reference interpreter of gcn_dsl.py.
+// GPU-SIDE TEST HOOKS - built into libfabgpu_gputest.so, never into the product library.  Two kinds:
+//   * single generated instruction streams (pair29_gcn.h) on one wavefront, so that tests/test_gpu_parity.py can compare every
+//     output register with the reference interpreter of gcn_dsl.py;
+//   * the device compilation of the product headers one primitive at a time (field, scalar, inversion, point and scalar-loop code)
+//     over grids of many wavefronts, for tests/test_device_primitives.py to compare with big integers ("primitives on many
+//     wavefronts", below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -365,5 +368,297 @@ extern "C" int gputest_wave_placement(uint32_t wgs, uint32_t lds_bytes, uint32_t
     int rc = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : 4;
     if (rc == 0 && hipMemcpy(out, d, sizeof(uint32_t) * 8 * wgs, hipMemcpyDeviceToHost) != hipSuccess) rc = 5;
     hipFree(d);
+    return rc;
+}
+
+// ---- primitives on many wavefronts ---------------------------------------------------------------------------------------------------
+// The DEVICE compilation of the product headers, one primitive at a time, for tests/test_device_primitives.py: wherever a header
+// branches on __HIP_DEVICE_COMPILE__ (the generated asm of fe29_gcn.h / bn29_gcn.h / one29_gcn.h, the mac of fp256.h, the ballots that
+// end modinv and pair_modinv) the host tests run something else.  n items over a grid of 256-thread workgroups; one lane per item, or
+// one lane PAIR per item for the pair primitives (every lane of the pair writes its own result).  Lanes past the end clamp to the
+// last item - they take part in every ballot and DPP exchange - and write nothing.
+namespace {
+constexpr uint32_t PRIM_BLOCK = 256;
+constexpr uint32_t PRIM_MAX_ITEMS = 1u << 22;
+
+struct DevBufs {   // the device buffers of one hook call, released together
+    std::vector<void*> held;
+    ~DevBufs() {
+        for (void* q : held) hipFree(q);
+    }
+    void* get(size_t bytes) {
+        void* q = nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+        held.push_back(q);
+        return q;
+    }
+    void* put(const void* src, size_t bytes) {
+        void* q = get(bytes);
+        if (q && bytes && hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return q;
+    }
+};
+inline dim3 prim_grid(size_t lanes) { return dim3((unsigned)((lanes + PRIM_BLOCK - 1) / PRIM_BLOCK)); }
+inline int prim_sync() { return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -2; }
+inline bool prim_back(void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
+
+template <class F>
+__device__ __forceinline__ void prim_load_fe(F& r, const int32_t* p) {
+#pragma unroll
+    for (int l = 0; l < 9; l++) r.v[l] = p[l];
+}
+template <class F>
+__device__ __forceinline__ void prim_store_fe(int32_t* p, const F& a) {
+#pragma unroll
+    for (int l = 0; l < 9; l++) p[l] = a.v[l];
+}
+}  // namespace
+
+// Field operations of fe (P-256, fe29.h) and fbn (FP256BN, bn29.h).  form 0: a, b are 32 big-endian bytes per item, brought into the
+// field on the device (fe_to_mont);  form 1: nine int32 limbs per item, used as they are.
+// op: 0 a * b   1 a^2   2 (a + b) * (a - b)   3 (2a) * b   4 fe_weak_norm(a)   5 a itself (form 0: the to_mont -> from_mont round trip)
+// out per item: limbs[9] of the result, canon[32] = fe_from_mont(result) big-endian, zero = fe_is_zero(result)
+template <class F>
+__global__ void __launch_bounds__(PRIM_BLOCK) gputest_field_kernel(int op, int form, uint32_t n, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                                    int32_t* __restrict__ limbs, uint8_t* __restrict__ canon, uint32_t* __restrict__ zero) {
+    const uint32_t i = blockIdx.x * PRIM_BLOCK + threadIdx.x;
+    const bool active = i < n;
+    const uint32_t ic = active ? i : n - 1;
+    F A, B, Rr, t1, t2;
+    if (form == 0) {
+        u256 x, y;
+        from_be32(x, a + 32 * (size_t)ic);
+        from_be32(y, b + 32 * (size_t)ic);
+        fe_to_mont(A, x);
+        fe_to_mont(B, y);
+    } else {
+        prim_load_fe(A, reinterpret_cast<const int32_t*>(a) + 9 * (size_t)ic);
+        prim_load_fe(B, reinterpret_cast<const int32_t*>(b) + 9 * (size_t)ic);
+    }
+    if (op == 0) {
+        fe_mul(Rr, A, B);
+    } else if (op == 1) {
+        fe_sqr(Rr, A);
+    } else if (op == 2) {
+        fe_add(t1, A, B);
+        fe_sub(t2, A, B);
+        fe_mul(Rr, t1, t2);
+    } else if (op == 3) {
+        fe_dbl(t1, A);
+        fe_mul(Rr, t1, B);
+    } else if (op == 4) {
+        fe_weak_norm(Rr, A);
+    } else {
+        Rr = A;
+    }
+    u256 c;
+    fe_from_mont(c, Rr);
+    const bool z = fe_is_zero(Rr);
+    if (active) {
+        prim_store_fe(limbs + 9 * (size_t)i, Rr);
+        to_be32(canon + 32 * (size_t)i, c);
+        zero[i] = z ? 1u : 0u;
+    }
+}
+
+// field: 0 P-256, 1 FP256BN.  0 ok, -1 allocation or copy in, -2 launch or kernel, -3 arguments, -4 copy out.
+extern "C" int gputest_field_op(int field, int op, int form, uint32_t n, const void* a, const void* b, int32_t* limbs, uint8_t* canon, uint32_t* zero) {
+    if ((field | 1) != 1 || op < 0 || op > 5 || (form | 1) != 1 || n == 0 || n > PRIM_MAX_ITEMS || !a || !b || !limbs || !canon || !zero) return -3;
+    const size_t in_bytes = (size_t)n * (form ? 36 : 32);
+    DevBufs d;
+    const uint8_t* da = (const uint8_t*)d.put(a, in_bytes);
+    const uint8_t* db = (const uint8_t*)d.put(b, in_bytes);
+    int32_t* dl = (int32_t*)d.get((size_t)n * 36);
+    uint8_t* dc = (uint8_t*)d.get((size_t)n * 32);
+    uint32_t* dz = (uint32_t*)d.get((size_t)n * 4);
+    if (!da || !db || !dl || !dc || !dz) return -1;
+    if (field == 0) hipLaunchKernelGGL(gputest_field_kernel<fe>, prim_grid(n), dim3(PRIM_BLOCK), 0, 0, op, form, n, da, db, dl, dc, dz);
+    else hipLaunchKernelGGL(gputest_field_kernel<fbn>, prim_grid(n), dim3(PRIM_BLOCK), 0, 0, op, form, n, da, db, dl, dc, dz);
+    int rc = prim_sync();
+    if (rc == 0 && !(prim_back(limbs, dl, (size_t)n * 36) && prim_back(canon, dc, (size_t)n * 32) && prim_back(zero, dz, (size_t)n * 4))) rc = -4;
+    return rc;
+}
+
+// The scalar field mod n and the 256-bit helpers of fp256.h / p256_point.h.  a, b, c: 32 big-endian bytes per item.
+// op: 0 fn_to_mont(a)   1 fn_mul(a, b)   2 sub256(a, b): out0 = difference, flag = borrow   3 sel256(c odd, a, b)   4 flag = lt256(a, b)
+//     5 flag = range_status(r = a, s = b)   6 ecdsa_scalars29(e = a, r = b, s = c): out0 = u1, out1 = u2
+//     7 pair_ecdsa_scalars29, one lane pair per item
+// out per LANE (ops 0..6: lane = item; op 7: lanes 2k and 2k + 1 serve item k): out0[32] out1[32] big-endian, flag
+__global__ void __launch_bounds__(PRIM_BLOCK) gputest_scalar_kernel(int op, uint32_t n, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                                     const uint8_t* __restrict__ c, uint8_t* __restrict__ out, uint32_t* __restrict__ flag) {
+    const uint32_t t = blockIdx.x * PRIM_BLOCK + threadIdx.x;
+    const uint32_t i = op == 7 ? t >> 1 : t;
+    const bool odd = op == 7 && (t & 1u) != 0;
+    const bool active = i < n;
+    const uint32_t ic = active ? i : n - 1;
+    u256 A, B, C, o0 = zero256(), o1 = zero256();
+    uint32_t f = 0;
+    from_be32(A, a + 32 * (size_t)ic);
+    from_be32(B, b + 32 * (size_t)ic);
+    from_be32(C, c + 32 * (size_t)ic);
+    if (op == 0) fn_to_mont(o0, A);
+    else if (op == 1) fn_mul(o0, A, B);
+    else if (op == 2) f = sub256(o0, A, B);
+    else if (op == 3) sel256(o0, (C.w[0] & 1u) != 0, A, B);
+    else if (op == 4) f = lt256(A, B) ? 1u : 0u;
+    else if (op == 5) f = range_status(A, B);
+    else if (op == 6) ecdsa_scalars29(o0, o1, A, B, C);
+    else pair_ecdsa_scalars29(o0, o1, A, B, C, odd);
+    if (active) {
+        to_be32(out + 64 * (size_t)t, o0);
+        to_be32(out + 64 * (size_t)t + 32, o1);
+        flag[t] = f;
+    }
+}
+
+extern "C" int gputest_scalar_op(int op, uint32_t n, const uint8_t* a, const uint8_t* b, const uint8_t* c, uint8_t* out, uint32_t* flag) {
+    if (op < 0 || op > 7 || n == 0 || n > PRIM_MAX_ITEMS || !a || !b || !c || !out || !flag) return -3;
+    const size_t lanes = (size_t)n * (op == 7 ? 2 : 1);
+    DevBufs d;
+    const uint8_t* da = (const uint8_t*)d.put(a, (size_t)n * 32);
+    const uint8_t* db = (const uint8_t*)d.put(b, (size_t)n * 32);
+    const uint8_t* dc = (const uint8_t*)d.put(c, (size_t)n * 32);
+    uint8_t* dout = (uint8_t*)d.get(lanes * 64);
+    uint32_t* df = (uint32_t*)d.get(lanes * 4);
+    if (!da || !db || !dc || !dout || !df) return -1;
+    hipLaunchKernelGGL(gputest_scalar_kernel, prim_grid(lanes), dim3(PRIM_BLOCK), 0, 0, op, n, da, db, dc, dout, df);
+    int rc = prim_sync();
+    if (rc == 0 && !(prim_back(out, dout, lanes * 64) && prim_back(flag, df, lanes * 4))) rc = -4;
+    return rc;
+}
+
+// Safegcd inversion (modinv30.h modinv; p256_pair29.h pair_modinv).  which: 0 mod n, 1 mod p (P-256), 2 mod the FP256BN prime (what
+// bn_affine29 inverts by).  pair: one lane pair per item through pair_modinv, each lane's result written on its own.
+// in: 32 big-endian bytes per item;  out: 32 per LANE.
+// One instantiation per modulus: the kernels hand modinv a compile-time constant, so inv30 and the modulus limbs are immediates here too.
+template <int WHICH>
+__global__ void __launch_bounds__(PRIM_BLOCK) gputest_modinv_kernel(int pair, uint32_t n, const uint8_t* __restrict__ in, uint8_t* __restrict__ out) {
+    const uint32_t t = blockIdx.x * PRIM_BLOCK + threadIdx.x;
+    const uint32_t i = pair ? t >> 1 : t;
+    const bool active = i < n;
+    const uint32_t ic = active ? i : n - 1;
+    const modinv_info NI = MODINV_N_INFO, PI = MODINV_P_INFO, BI = MODINV_BNP_INFO;
+    const modinv_info& mi = WHICH == 0 ? NI : (WHICH == 1 ? PI : BI);   // WHICH is a template argument: the choice folds away
+    u256 x, w;
+    from_be32(x, in + 32 * (size_t)ic);
+    if (pair) pair_modinv(w, x, mi, (t & 1u) != 0);
+    else modinv(w, x, mi);
+    if (active) to_be32(out + 32 * (size_t)t, w);
+}
+
+extern "C" int gputest_modinv(int which, int pair, uint32_t n, const uint8_t* in, uint8_t* out) {
+    if (which < 0 || which > 2 || (pair | 1) != 1 || n == 0 || n > PRIM_MAX_ITEMS || !in || !out) return -3;
+    const size_t lanes = (size_t)n * (pair ? 2 : 1);
+    DevBufs d;
+    const uint8_t* din = (const uint8_t*)d.put(in, (size_t)n * 32);
+    uint8_t* dout = (uint8_t*)d.get(lanes * 32);
+    if (!din || !dout) return -1;
+    if (which == 0) hipLaunchKernelGGL(gputest_modinv_kernel<0>, prim_grid(lanes), dim3(PRIM_BLOCK), 0, 0, pair, n, din, dout);
+    else if (which == 1) hipLaunchKernelGGL(gputest_modinv_kernel<1>, prim_grid(lanes), dim3(PRIM_BLOCK), 0, 0, pair, n, din, dout);
+    else hipLaunchKernelGGL(gputest_modinv_kernel<2>, prim_grid(lanes), dim3(PRIM_BLOCK), 0, 0, pair, n, din, dout);
+    int rc = prim_sync();
+    if (rc == 0 && !prim_back(out, dout, lanes * 32)) rc = -4;
+    return rc;
+}
+
+// The one-lane point operations as the device resolves them (p256_verify29.h: the programs of one29_gcn.h) on raw limbs.
+// in per item: X1 Y1 Z1 X2 Y2 Z2 (6 x 9 int32; op 2 reads X2, Y2 as the affine addend, ops 0 and 3 read the first point only)
+// op: 0 pt_dbl29   1 pt_add29   2 pt_add_mixed29   3 flag = on_curve29(X1, Y1)
+// out per item: X Y Z H RR (5 x 9 int32; H, RR zero for ops 0 and 3), flag
+__global__ void __launch_bounds__(PRIM_BLOCK) gputest_point_kernel(int op, uint32_t n, const int32_t* __restrict__ in, int32_t* __restrict__ out, uint32_t* __restrict__ flag) {
+    const uint32_t i = blockIdx.x * PRIM_BLOCK + threadIdx.x;
+    const bool active = i < n;
+    const uint32_t ic = active ? i : n - 1;
+    const int32_t* p = in + 54 * (size_t)ic;
+    jac29 P1, P2, Rr;
+    fe h, rr;
+    prim_load_fe(P1.X, p); prim_load_fe(P1.Y, p + 9); prim_load_fe(P1.Z, p + 18);
+    prim_load_fe(P2.X, p + 27); prim_load_fe(P2.Y, p + 36); prim_load_fe(P2.Z, p + 45);
+    Rr = P1;
+#pragma unroll
+    for (int l = 0; l < 9; l++) h.v[l] = rr.v[l] = 0;
+    uint32_t f = 0;
+    if (op == 0) pt_dbl29(Rr, P1);
+    else if (op == 1) pt_add29(Rr, P1, P2, h, rr);
+    else if (op == 2) pt_add_mixed29(Rr, P1, P2.X, P2.Y, h, rr);
+    else f = on_curve29(P1.X, P1.Y) ? 1u : 0u;
+    if (active) {
+        int32_t* o = out + 45 * (size_t)i;
+        prim_store_fe(o, Rr.X); prim_store_fe(o + 9, Rr.Y); prim_store_fe(o + 18, Rr.Z);
+        prim_store_fe(o + 27, h); prim_store_fe(o + 36, rr);
+        flag[i] = f;
+    }
+}
+
+extern "C" int gputest_point_op(int op, uint32_t n, const int32_t* in, int32_t* out, uint32_t* flag) {
+    if (op < 0 || op > 3 || n == 0 || n > PRIM_MAX_ITEMS || !in || !out || !flag) return -3;
+    DevBufs d;
+    const int32_t* din = (const int32_t*)d.put(in, (size_t)n * 54 * 4);
+    int32_t* dout = (int32_t*)d.get((size_t)n * 45 * 4);
+    uint32_t* df = (uint32_t*)d.get((size_t)n * 4);
+    if (!din || !dout || !df) return -1;
+    hipLaunchKernelGGL(gputest_point_kernel, prim_grid(n), dim3(PRIM_BLOCK), 0, 0, op, n, din, dout, df);
+    int rc = prim_sync();
+    if (rc == 0 && !(prim_back(out, dout, (size_t)n * 45 * 4) && prim_back(flag, df, (size_t)n * 4))) rc = -4;
+    return rc;
+}
+
+// R = u1*G + u2*Q on ONE lane, the way the one-lane kernels compute it.  keyed == 0: p256_combined_mult29 (kernels.hip
+// p256_verify_kernel: comb_mult29 over the generator table, the Booth-window chain over a per-lane table in a global workspace,
+// final_add29), Q per item;  keyed == 1: p256_combined_mult_keyed29 with the 8-bit comb table of ONE key (key_xy64, big-endian x y) -
+// the qx, qy columns of `in` are not read.  in per item: u1 u2 qx qy (4 x 32 big-endian);  out per item: X Y Z (3 x 9 int32), r_inf
+__global__ void __launch_bounds__(PRIM_BLOCK) gputest_combined_kernel(int keyed, uint32_t n, const uint8_t* __restrict__ in, const int32_t* __restrict__ gtab,
+                                                                       const int32_t* __restrict__ ktab, uint4* __restrict__ qws, int32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * PRIM_BLOCK + threadIdx.x;
+    const bool active = i < n;
+    const uint32_t ic = active ? i : n - 1;
+    GlobalQTab29<PRIM_BLOCK> qtab = GlobalQTab29<PRIM_BLOCK>::of(qws + (size_t)blockIdx.x * (16 * 8 * PRIM_BLOCK), threadIdx.x);
+    GTab16 gt{gtab};
+    u256 u1, u2, qx, qy;
+    from_be32(u1, in + 128 * (size_t)ic);
+    from_be32(u2, in + 128 * (size_t)ic + 32);
+    from_be32(qx, in + 128 * (size_t)ic + 64);
+    from_be32(qy, in + 128 * (size_t)ic + 96);
+    jac29 Rr;
+    bool inf;
+    if (keyed) {
+        KeyTab8 kt{ktab};
+        p256_combined_mult_keyed29(Rr, inf, u1, u2, gt, kt);
+    } else {
+        const fe ONE = {FE29_R1};
+        jac29 Q;
+        fe_to_mont(Q.X, qx);
+        fe_to_mont(Q.Y, qy);
+        Q.Z = ONE;
+        p256_combined_mult29(Rr, inf, u1, u2, Q, gt, qtab);
+    }
+    if (active) {
+        int32_t* o = out + 28 * (size_t)i;
+        prim_store_fe(o, Rr.X); prim_store_fe(o + 9, Rr.Y); prim_store_fe(o + 18, Rr.Z);
+        o[27] = inf ? 1 : 0;
+    }
+}
+
+extern "C" int gputest_combined(int keyed, uint32_t n, const uint8_t* key_xy64, const uint8_t* in, int32_t* out) {
+    if ((keyed | 1) != 1 || n == 0 || n > 65536 || !in || !out || (keyed && !key_xy64)) return -3;
+    std::vector<int32_t> tab(GTab16::TABLE_WORDS), ktab(KeyTab8::TABLE_WORDS, 0);
+    build_g_comb_table16(tab.data());
+    if (keyed) {
+        u256 x, y;
+        from_be32(x, key_xy64);
+        from_be32(y, key_xy64 + 32);
+        build_key_comb_table8(ktab.data(), x, y);
+    }
+    const dim3 grid = prim_grid(n);
+    DevBufs d;
+    const uint8_t* din = (const uint8_t*)d.put(in, (size_t)n * 128);
+    const int32_t* dtab = (const int32_t*)d.put(tab.data(), sizeof(int32_t) * GTab16::TABLE_WORDS);
+    const int32_t* dkt = (const int32_t*)d.put(ktab.data(), sizeof(int32_t) * KeyTab8::TABLE_WORDS);
+    uint4* dws = (uint4*)d.get((size_t)grid.x * PRIM_BLOCK * 16 * 8 * sizeof(uint4));
+    int32_t* dout = (int32_t*)d.get((size_t)n * 28 * 4);
+    if (!din || !dtab || !dkt || !dws || !dout) return -1;
+    hipLaunchKernelGGL(gputest_combined_kernel, grid, dim3(PRIM_BLOCK), 0, 0, keyed, n, din, dtab, dkt, dws, dout);
+    int rc = prim_sync();
+    if (rc == 0 && !prim_back(out, dout, (size_t)n * 28 * 4)) rc = -4;
     return rc;
 }

@@ -13,6 +13,7 @@ import pytest
 import bccsp_sw_oracle as po
 import coracle
 import fabgpu
+import scalar_sets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
@@ -263,15 +264,9 @@ def test_combined_mult_adversarial_scalars(hosttest):
         return po.pt_add(po.pt_mul(u1, G) if u1 else None, po.pt_mul(u2, Q))
     dq = rng.randrange(1, N)
     Q = po.pt_mul(dq, G)
-    u2s = [1, 2, 15, 16, 17, 31, 32, 33, (1 << 255), (1 << 256) % N, N - 1, N - 2, N - 16, N - 17, N >> 1, (1 << 250) - 1,
-           int("5" * 64, 16) % N, int("a" * 63, 16), int("f" * 63, 16), int("84210" * 12, 16) % N, int("7bdef" * 12, 16) % N]
-    for w in (0, 1, 25, 50, 51):
-        for d in range(1, 32):
-            v = (d << (5 * w)) % N
-            if v:
-                u2s.append(v)
-    u2s += [rng.randrange(1, N) for _ in range(40)]
-    u1s = [0, 1, 255, 256, 65535, 65536, (1 << 240), (1 << 248), N - 1, int("ff00" * 16, 16) % N, int("ffff0000" * 8, 16) % N, int("0001" * 16, 16)] + [rng.randrange(N) for _ in range(8)]
+    u2s = scalar_sets.adversarial_u2s(rng)
+    u1s = scalar_sets.adversarial_u1s(rng)
+    assert len(u2s) >= 21 + 5 * 30 + 40 and len(u1s) == 20
     for k, u2 in enumerate(u2s):
         u1 = u1s[k % len(u1s)]
         assert run(u1, u2, Q) == want(u1, u2, Q), (hex(u1), hex(u2))

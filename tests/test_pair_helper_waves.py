@@ -8,6 +8,7 @@ import pytest
 import bccsp_sw_oracle as po
 import coracle
 import fabgpu
+import scalar_sets
 
 pytestmark = pytest.mark.gpu
 
@@ -97,9 +98,8 @@ def test_recoding_edge_scalars(forms):
     """Valid signatures whose u2 = r / s is n - 2 (the scalar whose product the main wave takes from the table) and the other
     recoding edges, each beside a signature of the same key with another s."""
     rng = np.random.default_rng(11)
-    targets = [po.N - 2, po.N - 1, po.N - 3, po.N - 16, po.N - 17, po.N - 18, po.N - 32, po.N - 34, 1, 2, 3, 7, 8, 9, 15, 16, 17, 31, 32, 33,
-               (1 << 255) - 1, 1 << 255, (1 << 255) + 8, (1 << 256) % po.N, int("8" * 64, 16) % po.N, int("7" * 64, 16), int("f" * 63, 16),
-               int("1" * 64, 16), po.N >> 1, (po.N >> 1) + 1]
+    targets = scalar_sets.edge_u2_targets()
+    assert len(targets) == 30
     rows, expect = [], []
     for u2 in targets:
         for _ in range(200):
