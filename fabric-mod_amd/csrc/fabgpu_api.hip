@@ -567,7 +567,14 @@ int fabgpu_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* qx, cons
     int rc = ctx->acquire_qws(verify_workspace_bytes((uint32_t)n, ctx->allow_pair), &wi, &wsp, st);
     if (rc != FABGPU_OK) return rc;
     if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    hipError_t err = launch_p256_verify((uint32_t)n, qx, qy, e, r, s, ctx->d_gtab, wsp, verdict_bits, status, ctx->allow_pair, st, 0, ctx->pair_table_lds, ctx->pair_solo);
+    VerifyLaunch v;
+    v.n = (uint32_t)n;
+    v.qx = qx; v.qy = qy; v.qws = wsp;
+    v.e = e; v.r = r; v.s = s;
+    v.gtab = ctx->d_gtab;
+    v.verdict_bits = verdict_bits; v.status = status;
+    v.allow_pair = ctx->allow_pair; v.table_lds = ctx->pair_table_lds; v.pair_solo = ctx->pair_solo;
+    hipError_t err = launch_verify(v, st);
     if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
     ctx->release_qws(wi, st);
     ctx->timed = ctx->time_kernels;
@@ -601,7 +608,15 @@ int fabgpu_sha256_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* a
     int rc = ctx->acquire_qws(verify_workspace_bytes((uint32_t)n, ctx->allow_pair), &wi, &wsp, st);
     if (rc != FABGPU_OK) return rc;
     if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    hipError_t err = launch_sha256_p256_verify((uint32_t)n, arena, arena_bytes, off, qx, qy, r, s, ctx->d_gtab, wsp, verdict_bits, status, ctx->allow_pair, ShaPrefixArgs(), st);
+    VerifyLaunch v;
+    v.n = (uint32_t)n;
+    v.qx = qx; v.qy = qy; v.qws = wsp;
+    v.arena = arena; v.arena_bytes = arena_bytes; v.off = off;
+    v.r = r; v.s = s;
+    v.gtab = ctx->d_gtab;
+    v.verdict_bits = verdict_bits; v.status = status;
+    v.allow_pair = ctx->allow_pair;
+    hipError_t err = launch_verify(v, st);
     if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
     ctx->release_qws(wi, st);
     ctx->timed = ctx->time_kernels;
@@ -1067,7 +1082,14 @@ int fabgpu_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* ke
         return hip_to_rc(launched(ctx, err));
     }
     if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    hipError_t err = launch_p256_verify_keyed((uint32_t)n, key_id, nkeys, (const void*)kt, e, r, s, ctx->d_gtab, verdict_bits, status, ctx->allow_pair, st);
+    VerifyLaunch v;
+    v.n = (uint32_t)n;
+    v.key_id = key_id; v.nkeys = nkeys; v.ktabs = (const void*)kt;
+    v.e = e; v.r = r; v.s = s;
+    v.gtab = ctx->d_gtab;
+    v.verdict_bits = verdict_bits; v.status = status;
+    v.allow_pair = ctx->allow_pair;
+    hipError_t err = launch_verify(v, st);
     if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
     ctx->timed = ctx->time_kernels;
     return hip_to_rc(launched(ctx, err));
@@ -1114,8 +1136,15 @@ int fabgpu_sha256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const v
     if (ctx->allow_wide && n <= (size_t)WIDE_LAUNCH_MAX)
         return keyed_wide_identity_dev(ctx, (uint32_t)n, arena, arena_bytes, off, key_id, nkeys, (const void*)kt, r, s, verdict_bits, status, ShaPrefixArgs(), st);
     if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    hipError_t err = launch_sha256_p256_verify_keyed((uint32_t)n, arena, arena_bytes, off, key_id, nkeys, (const void*)kt, r, s, ctx->d_gtab, verdict_bits,
-                                                     status, ctx->allow_pair, ShaPrefixArgs(), st);
+    VerifyLaunch v;
+    v.n = (uint32_t)n;
+    v.key_id = key_id; v.nkeys = nkeys; v.ktabs = (const void*)kt;
+    v.arena = arena; v.arena_bytes = arena_bytes; v.off = off;
+    v.r = r; v.s = s;
+    v.gtab = ctx->d_gtab;
+    v.verdict_bits = verdict_bits; v.status = status;
+    v.allow_pair = ctx->allow_pair;
+    hipError_t err = launch_verify(v, st);
     if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
     ctx->timed = ctx->time_kernels;
     return hip_to_rc(launched(ctx, err));
@@ -1354,6 +1383,13 @@ int fabgpu_identity_verify_batch_dev(fabgpu_ctx* ctx, const fabgpu_identity_batc
     DeviceGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     hipError_t err;
+    VerifyLaunch v;
+    v.n = (uint32_t)n;
+    v.arena = b->arena; v.arena_bytes = b->arena_bytes; v.off = b->off; v.pa = pa;
+    v.r = b->r; v.s = b->s;
+    v.gtab = ctx->d_gtab;
+    v.verdict_bits = b->verdict_bits; v.status = b->status;
+    v.allow_pair = ctx->allow_pair;
     if (keyed) {
         uint32_t nkeys;
         const int32_t** kt;
@@ -1374,8 +1410,8 @@ int fabgpu_identity_verify_batch_dev(fabgpu_ctx* ctx, const fabgpu_identity_batc
             return hip_to_rc(err);
         }
         if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-        err = launch_sha256_p256_verify_keyed((uint32_t)n, b->arena, b->arena_bytes, b->off, b->key_id, nkeys, (const void*)kt, b->r, b->s, ctx->d_gtab,
-                                              b->verdict_bits, b->status, ctx->allow_pair, pa, st);
+        v.key_id = b->key_id; v.nkeys = nkeys; v.ktabs = (const void*)kt;
+        err = launch_verify(v, st);
         if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
     } else {
         size_t wi = 0;
@@ -1383,8 +1419,8 @@ int fabgpu_identity_verify_batch_dev(fabgpu_ctx* ctx, const fabgpu_identity_batc
         int rc = ctx->acquire_qws(verify_workspace_bytes((uint32_t)n, ctx->allow_pair), &wi, &wsp, st);
         if (rc != FABGPU_OK) return rc;
         if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-        err = launch_sha256_p256_verify((uint32_t)n, b->arena, b->arena_bytes, b->off, b->qx, b->qy, b->r, b->s, ctx->d_gtab, wsp,
-                                        b->verdict_bits, b->status, ctx->allow_pair, pa, st);
+        v.qx = b->qx; v.qy = b->qy; v.qws = wsp;
+        err = launch_verify(v, st);
         if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
         ctx->release_qws(wi, st);
     }
@@ -2581,33 +2617,48 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
             p.pre_idx = a.pre_idx + row0;
         }
         if (p.digests) p.digests = dt + o_dig + 32 * (size_t)row0;
+        VerifyLaunch v;
+        v.n = n;
+        v.arena = sl->d; v.arena_bytes = arena_bytes; v.off = a.off2 + 2 * (size_t)row0; v.pa = p;
+        v.r = a.r + 32 * (size_t)row0; v.s = a.s + 32 * (size_t)row0;
+        v.gtab = ctx->d_gtab;
+        v.verdict_bits = bits; v.status = dt + o_dst + row0;
+        v.allow_pair = pair;
         hipError_t e;
         if (keyed) {
-            e = launch_sha256_p256_verify_keyed(n, sl->d, arena_bytes, a.off2 + 2 * (size_t)row0, a.key_id + row0, nkeys, (const void*)kt, a.r + 32 * (size_t)row0,
-                                                a.s + 32 * (size_t)row0, ctx->d_gtab, bits, dt + o_dst + row0, pair, p, ls);
+            v.key_id = a.key_id + row0; v.nkeys = nkeys; v.ktabs = (const void*)kt;
+            e = launch_verify(v, ls);
         } else {
             size_t wi = 0;
             void* wsp = nullptr;
             int r2 = ctx->acquire_qws(verify_workspace_bytes(n, pair), &wi, &wsp, ls);
             if (r2 != FABGPU_OK) return r2;
-            e = launch_sha256_p256_verify(n, sl->d, arena_bytes, a.off2 + 2 * (size_t)row0, a.qx + 32 * (size_t)row0, a.qy + 32 * (size_t)row0,
-                                          a.r + 32 * (size_t)row0, a.s + 32 * (size_t)row0, ctx->d_gtab, wsp, bits, dt + o_dst + row0, pair, p, ls);
+            v.qx = a.qx + 32 * (size_t)row0; v.qy = a.qy + 32 * (size_t)row0; v.qws = wsp;
+            e = launch_verify(v, ls);
             ctx->release_qws(wi, ls);
         }
         return hip_to_rc(e);
     };
     // the creators of a split submission: rows [0, n_creators), digests ready (or about to be: same stream), arithmetic only
     auto verify_creators = [&](bool keyed) -> int {
+        VerifyLaunch v;
+        v.n = tot.creators;
+        v.e = dt + o_dig; v.r = a.r; v.s = a.s;
+        v.gtab = ctx->d_gtab;
+        v.verdict_bits = dt + o_bitc; v.status = dt + o_dst;
+        v.allow_pair = true; v.lds_reserve = exclusive ? 84u << 10 : 0u;
         hipError_t e;
         if (keyed) {
-            e = launch_p256_verify_keyed(tot.creators, a.key_id, nkeys, (const void*)kt, dt + o_dig, a.r, a.s, ctx->d_gtab, dt + o_bitc, dt + o_dst, true, s2, exclusive ? 84u << 10 : 0u);
+            v.key_id = a.key_id; v.nkeys = nkeys; v.ktabs = (const void*)kt;
+            e = launch_verify(v, s2);
         } else {
             size_t wi = 0;
             void* wsp = nullptr;
             int r2 = ctx->acquire_qws(verify_workspace_bytes(tot.creators, true), &wi, &wsp, s2);
             if (r2 != FABGPU_OK) return r2;
-            e = launch_p256_verify(tot.creators, a.qx, a.qy, dt + o_dig, a.r, a.s, ctx->d_gtab, wsp, dt + o_bitc, dt + o_dst, true, s2, exclusive ? 84u << 10 : 0u, ctx->pair_table_lds,
-                                   ctx->pair_solo);
+            v.qx = a.qx; v.qy = a.qy; v.qws = wsp;
+            v.table_lds = ctx->pair_table_lds; v.pair_solo = ctx->pair_solo;
+            e = launch_verify(v, s2);
             ctx->release_qws(wi, s2);
         }
         return hip_to_rc(e);

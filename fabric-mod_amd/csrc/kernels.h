@@ -39,7 +39,7 @@ int pair_table_default();
 size_t pair_table_lds_bytes();        // dynamic LDS one workgroup of the LDS-table pair kernel (helper-wave form) asks for
 size_t pair_table_lds_solo_bytes();   // ... of its one-wave-per-SIMD form (FABGPU_FLAG_PAIR_SOLO)
 constexpr int PAIR_TABLE_LDS_FROM = 16384;   // launches of more tuples than this keep the pair kernel's per-signature table in LDS
-// the mid-state kernel of a prefixed batch alone (the fused launchers run it themselves unless pa.mid_ready)
+// the mid-state kernel of a prefixed batch alone (a fused launch_verify runs it itself unless pa.mid_ready)
 hipError_t launch_sha256_midstates(const void* arena, size_t arena_bytes, const ShaPrefixArgs& pa, hipStream_t st);   // honours pa.lds_reserve
 hipError_t launch_sha256_batch(uint32_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, hipStream_t st, uint32_t lds_spread = 0);
 // n messages given as (start, end) pairs -> n x 32 digest bytes
@@ -48,18 +48,27 @@ hipError_t launch_sha256_spans(uint32_t n, const void* arena, size_t arena_bytes
 // gathered messages (pieces of the arena stitched into `scratch` at out_off[j] .. out_off[j+1]) -> n x 32 digest bytes
 hipError_t launch_gather_sha256(uint32_t n, const void* arena, size_t arena_bytes, const void* spans, const void* out_off, void* scratch,
                                 size_t scratch_bytes, void* digests, hipStream_t st, uint32_t lds_reserve = 0, uint32_t lds_spread = 0);
-hipError_t launch_p256_verify(uint32_t n, const void* qx, const void* qy, const void* e, const void* r, const void* s,
-                              const void* gtab, void* qws, void* verdict_bits, void* status, bool allow_pair, hipStream_t st,
-                              uint32_t lds_reserve = 0, int table_lds = 0,    // lds_reserve: see ShaPrefixArgs; table_lds: 1 PairQTabLds, 0 global, -1 by size
-                              bool pair_solo = false);                        // LDS table: the one-wave form instead of the helper-wave form
-hipError_t launch_sha256_p256_verify(uint32_t n, const void* arena, size_t arena_bytes, const void* off, const void* qx,
-                                     const void* qy, const void* r, const void* s, const void* gtab, void* qws,
-                                     void* verdict_bits, void* status, bool allow_pair, const ShaPrefixArgs& pa, hipStream_t st);
-hipError_t launch_p256_verify_keyed(uint32_t n, const void* key_id, uint32_t nkeys, const void* ktabs, const void* e, const void* r, const void* s,
-                                    const void* gtab, void* verdict_bits, void* status, bool allow_pair, hipStream_t st, uint32_t lds_reserve = 0);
-hipError_t launch_sha256_p256_verify_keyed(uint32_t n, const void* arena, size_t arena_bytes, const void* off, const void* key_id, uint32_t nkeys,
-                                           const void* ktabs, const void* r, const void* s, const void* gtab, void* verdict_bits, void* status,
-                                           bool allow_pair, const ShaPrefixArgs& pa, hipStream_t st);
+// One ECDSA P-256 verify launch, by field name.  Two pairs of alternatives, exactly one of each named (launch_verify returns
+// hipErrorInvalidValue otherwise): the key fresh or registered, the digest given or hashed from the message in the same kernel.
+struct VerifyLaunch {
+    uint32_t n = 0;
+    const void *qx = nullptr, *qy = nullptr;          // fresh key: n x 32 bytes each ...
+    void* qws = nullptr;                              // ... and verify_workspace_bytes(n, allow_pair) bytes for the per-signature tables
+    const void *key_id = nullptr, *ktabs = nullptr;   // or registered key: n ids into the device's array of key tables (KTAB_STRIDE) ...
+    uint32_t nkeys = 0;                               // ... of nkeys keys
+    const void* e = nullptr;                          // digest given: n x 32 bytes
+    const void *arena = nullptr, *off = nullptr;      // or messages: arena[off[i], off[i+1]), possibly behind shared prefixes (pa; the
+    size_t arena_bytes = 0;                           // mid-state kernel runs first unless pa.mid_ready)
+    ShaPrefixArgs pa;
+    const void *r = nullptr, *s = nullptr, *gtab = nullptr;
+    void *verdict_bits = nullptr, *status = nullptr;  // status: optional
+    bool allow_pair = false;                          // two lanes per signature up to VERIFY_PAIR_MAX
+    uint32_t lds_reserve = 0;                         // see ShaPrefixArgs; a launch that hashes takes pa.lds_reserve instead
+    // fresh key, digest given, two lanes per signature only:
+    int table_lds = 0;                                // the per-signature table: 1 PairQTabLds, 0 global workspace, -1 by size (PAIR_TABLE_LDS_FROM)
+    bool pair_solo = false;                           // LDS table: the one-wave form instead of the helper-wave form
+};
+hipError_t launch_verify(const VerifyLaunch& v, hipStream_t st);
 
 // ---- wide_kernels.hip: a registered key's verification on eight lanes per signature, in two phases (p256_wide29.h) ----
 // For launches of at most WIDE_LAUNCH_MAX signatures (they cannot fill the chip: their time is one wavefront's instruction stream).

@@ -66,62 +66,159 @@ __global__ void __launch_bounds__(256) sha256_midstate_kernel(uint32_t m, const 
 // ------------------------------------------------------------------------------------------------
 // ECDSA P-256 verify
 // ------------------------------------------------------------------------------------------------
-// Persistent workgroups: a bounded number of slots, each walking the BLOCK-signature tiles  blockIdx.x, blockIdx.x + gridDim.x, ...
-// (the per-lane j*Q workspace is sized by slots, not by the batch).
+// Persistent workgroups: a bounded number of slots, each walking the tiles  blockIdx.x, blockIdx.x + gridDim.x, ...  of BLOCK / LANES
+// signatures (the per-lane j*Q workspace is sized by slots, not by the batch).
 // One 256-thread workgroup per CU = one wave per SIMD.  A second wave per SIMD was measured (BLOCK = 512, round-1 PMC runs in
 // profiles/): each wave then takes 1.5x the cycles, but the chip also drops from ~2.0 to ~1.6 GHz - the integer multiplier
 // array is power-limited - so whole-job throughput does not move; one wave per SIMD keeps the latency of a block minimal.
+//
+// Nine of the ten kernels below are verify_tiles, one loop over three choices: where the digest comes from (DigestGiven / DigestHashed),
+// where the key comes from and which core runs on it (FreshKey / RegisteredKey), and with them how many lanes own a signature (TileGeom).
+
+// Lane geometry.  LANES = 1: one signature per lane.  LANES = 2 (p256_pair29.h): lane 2k / 2k+1 of a wave own signature k of the
+// tile - 128 signatures per 256-thread workgroup, for batches that cannot fill the chip with one signature per lane.
+struct TileRow {
+    uint32_t i;    // the row of the batch this lane stands for in this tile
+    uint32_t ic;   // the row it reads: i, or the last row of the batch on a tail lane
+    bool active;   // i < n
+};
+template <int BLOCK, int LANES>
+struct TileGeom {
+    static_assert(LANES == 1 || LANES == 2, "one or two lanes per signature");
+    static constexpr uint32_t PER_WG = BLOCK / LANES;   // signatures per workgroup and tile
+    static __device__ __forceinline__ bool odd(uint32_t lane) { return LANES == 2 && (lane & 1) != 0; }   // the second lane of a pair
+    static __device__ __forceinline__ uint32_t sub(uint32_t lane) { return lane / LANES; }                // the lane's signature within a tile
+    static __device__ __forceinline__ uint32_t ntiles(uint32_t n) { return (n + PER_WG - 1) / PER_WG; }
+    // CONSENSUS-CRITICAL, and only here: tail lanes compute on the last tuple (every lane runs the whole instruction stream, reaches
+    // every ballot and every barrier, and reads inside the batch) and write nothing; of a pair only the even lane writes.
+    static __device__ __forceinline__ TileRow row(uint32_t tile, uint32_t sub, uint32_t n) {
+        const uint32_t i = tile * PER_WG + sub;
+        const bool active = i < n;
+        return TileRow{i, active ? i : (n - 1), active};
+    }
+    static __device__ __forceinline__ bool writes(const TileRow& t, bool odd) { return t.active && !odd; }
+    static __device__ __forceinline__ void emit(const TileRow& t, uint32_t n, bool odd, uint32_t st, uint64_t* verdict_bits, uint8_t* status) {
+        if constexpr (LANES == 1) emit_verdict(t.i, t.active, st, verdict_bits, status);
+        else pair_emit_verdict(t.i, n, t.active, odd, st, reinterpret_cast<uint32_t*>(verdict_bits), status);   // the even lane carries the verdict
+    }
+};
+
+// Digest source: the caller's e ...
+struct DigestGiven {
+    static constexpr bool BEFORE_KEY = false;   // one more load, behind the key's
+    const uint8_t* e;
+    __device__ __forceinline__ void operator()(u256& ve, const TileRow& t, bool) const { load_be_field(ve, e, t.ic); }
+};
+// ... or identity.Verify fused: e = SHA-256(msg) stays in registers (and leaves the chip only if pre.digests asks).  With two lanes per
+// signature both lanes of a pair hash the (same) message - the hash is 18 % of the stream and does not split across lanes.
+struct DigestHashed {
+    static constexpr bool BEFORE_KEY = true;    // the key is read behind the hash: nothing of it is live across the SHA-256 stream
+    const uint32_t* arena32;
+    uint32_t arena_words;
+    const uint32_t* off;
+    const sha_prefixes pre;
+    __device__ __forceinline__ void operator()(u256& ve, const TileRow& t, bool writes) const {
+        uint32_t h[8];
+        sha256_message(arena32, arena_words, off, pre, t.ic, t.active, h);
+        emit_digest(pre, t.i, writes, h);
+#pragma unroll
+        for (int k = 0; k < 8; k++) ve.w[k] = h[7 - k];   // digest big-endian -> integer limbs
+    }
+};
+
+// Key and core.  Fresh keys: (qx, qy) by row and a table of j*Q per signature that the core builds - GlobalQTab29 (one lane),
+// PairQTab (global workspace, 16 entries, 5-bit windows) or PairQTabLds (LDS, 8 entries, signed 4-bit windows: W = 4).
+template <int LANE_COUNT, class QTab, int W = 5>
+struct FreshKey {
+    static constexpr int LANES = LANE_COUNT;
+    const uint8_t *qx, *qy;
+    const int32_t* gtab;
+    QTab qtab;
+    struct Row { u256 x, y; };
+    __device__ __forceinline__ void load(Row& k, uint32_t ic) const {
+        load_be_field(k.x, qx, ic);
+        load_be_field(k.y, qy, ic);
+    }
+    __device__ __forceinline__ uint32_t verify(const Row& k, const u256& e, const u256& r, const u256& s, bool odd) {
+        if constexpr (LANES == 1) {
+            GTab16 gt{gtab};
+            return p256_verify_core29(k.x, k.y, e, r, s, gt, qtab);
+        } else {
+            return p256_verify_pair29<QTab, W>(k.x, k.y, e, r, s, gtab, qtab, odd);
+        }
+    }
+};
+// Registered public keys (fabgpu_p256_key_register): every signature names a key whose 8-bit comb table is resident on the
+// device, so u2*Q is 32 mixed additions like u1*G: no doublings, no per-lane table, no workspace.  ktabs[KTAB_STRIDE k] = table of key k,
+// ktabs[KTAB_STRIDE k + 1] = its 16-bit comb or nullptr (round 6, FABGPU_FLAG_KEY_TABLES_16BIT: 16 mixed additions when a whole wavefront has them).
+// An out-of-range key id reports status 4 ("use bccsp/sw"), never a verdict.
+template <int LANE_COUNT>
+struct RegisteredKey {
+    static constexpr int LANES = LANE_COUNT;
+    const uint32_t* key_id;
+    uint32_t nkeys;
+    const int32_t* const* ktabs;
+    const int32_t* gtab;
+    struct Row { const int32_t *kt, *kt16; uint32_t kid; };
+    __device__ __forceinline__ void load(Row& k, uint32_t ic) const {
+        k.kid = key_id[ic];
+        bool kok = k.kid < nkeys;
+        const int32_t* const* slot = ktabs + KTAB_STRIDE * (size_t)(kok ? k.kid : 0);
+        k.kt = slot[0];
+        k.kt16 = slot[1];
+    }
+    __device__ __forceinline__ uint32_t verify(const Row& k, const u256& e, const u256& r, const u256& s, bool odd) {
+        uint32_t st;
+        if constexpr (LANES == 1) {
+            GTab16 gt{gtab};
+            st = __all(k.kt16 != nullptr) ? p256_verify_keyed_core29(e, r, s, gt, GTab16{k.kt16}) : p256_verify_keyed_core29(e, r, s, gt, KeyTab8{k.kt});
+        } else {
+            st = p256_verify_keyed_pair29(e, r, s, gtab, k.kt, k.kt16, odd);
+        }
+        if (!(k.kid < nkeys)) st = ST_OFF_CURVE;
+        return st;
+    }
+};
+
+template <int BLOCK, class Digest, class Key>
+__device__ __forceinline__ void verify_tiles(uint32_t n, const Digest& digest, Key key, const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    using Geom = TileGeom<BLOCK, Key::LANES>;
+    const bool odd = Geom::odd(threadIdx.x);
+    const uint32_t sub = Geom::sub(threadIdx.x);
+    const uint32_t ntiles = Geom::ntiles(n);
+    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const TileRow t = Geom::row(tile, sub, n);
+        u256 ve, vr, vs;
+        typename Key::Row k;
+        if constexpr (Digest::BEFORE_KEY) digest(ve, t, Geom::writes(t, odd));
+        key.load(k, t.ic);
+        if constexpr (!Digest::BEFORE_KEY) digest(ve, t, Geom::writes(t, odd));
+        load_be_field(vr, r, t.ic);
+        load_be_field(vs, s, t.ic);
+        uint32_t st = key.verify(k, ve, vr, vs, odd);
+        Geom::emit(t, n, odd, st, verdict_bits, status);
+    }
+}
+
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK, 2) p256_verify_kernel(uint32_t n, const uint8_t* __restrict__ qx, const uint8_t* __restrict__ qy,
                                                                     const uint8_t* __restrict__ e, const uint8_t* __restrict__ r,
                                                                     const uint8_t* __restrict__ s, const int32_t* __restrict__ gtab,
                                                                     uint4* __restrict__ qws, uint64_t* __restrict__ verdict_bits,
                                                                     uint8_t* __restrict__ status) {
-    GlobalQTab29<BLOCK> qtab = GlobalQTab29<BLOCK>::of(qws + (size_t)blockIdx.x * (QWS_UINT4_PER_LANE * BLOCK), threadIdx.x);
-    GTab16 gt{gtab};
-    const uint32_t ntiles = (n + BLOCK - 1) / BLOCK;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        uint32_t i = tile * BLOCK + threadIdx.x;
-        bool active = i < n;
-        uint32_t ic = active ? i : (n - 1);
-        u256 vqx, vqy, ve, vr, vs;
-        load_be_field(vqx, qx, ic);
-        load_be_field(vqy, qy, ic);
-        load_be_field(ve, e, ic);
-        load_be_field(vr, r, ic);
-        load_be_field(vs, s, ic);
-        uint32_t st = p256_verify_core29(vqx, vqy, ve, vr, vs, gt, qtab);
-        emit_verdict(i, active, st, verdict_bits, status);
-    }
+    using QTab = GlobalQTab29<BLOCK>;
+    verify_tiles<BLOCK>(n, DigestGiven{e}, FreshKey<1, QTab>{qx, qy, gtab, QTab::of(qws + (size_t)blockIdx.x * (QWS_UINT4_PER_LANE * BLOCK), threadIdx.x)}, r, s, verdict_bits, status);
 }
 
-// Two lanes per signature (p256_pair29.h): 128 signatures per 256-thread workgroup, for batches that cannot fill the chip
-// with one signature per lane.  Lane 2k / 2k+1 of a wave own signature k; the even lane carries the verdict.
+// Two lanes per signature, the per-signature table in the global workspace.
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK, 1) p256_verify_pair_kernel(uint32_t n, const uint8_t* __restrict__ qx, const uint8_t* __restrict__ qy,
                                                                          const uint8_t* __restrict__ e, const uint8_t* __restrict__ r,
                                                                          const uint8_t* __restrict__ s, const int32_t* __restrict__ gtab,
                                                                          uint4* __restrict__ qws, uint64_t* __restrict__ verdict_bits,
                                                                          uint8_t* __restrict__ status) {
-    constexpr int NP = BLOCK / 2;
-    const bool odd = (threadIdx.x & 1) != 0;
-    const uint32_t pairidx = threadIdx.x >> 1;
-    PairQTab<NP> qtab = PairQTab<NP>::of(qws + (size_t)blockIdx.x * (QWS_PAIR_UINT4_PER_SIG * NP), pairidx);
-    uint32_t* verdict32 = reinterpret_cast<uint32_t*>(verdict_bits);
-    const uint32_t ntiles = (n + NP - 1) / NP;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        uint32_t i = tile * NP + pairidx;
-        bool active = i < n;
-        uint32_t ic = active ? i : (n - 1);
-        u256 vqx, vqy, ve, vr, vs;
-        load_be_field(vqx, qx, ic);
-        load_be_field(vqy, qy, ic);
-        load_be_field(ve, e, ic);
-        load_be_field(vr, r, ic);
-        load_be_field(vs, s, ic);
-        uint32_t st = p256_verify_pair29(vqx, vqy, ve, vr, vs, gtab, qtab, odd);
-        pair_emit_verdict(i, n, active, odd, st, verdict32, status);
-    }
+    using QTab = PairQTab<BLOCK / 2>;
+    verify_tiles<BLOCK>(n, DigestGiven{e}, FreshKey<2, QTab>{qx, qy, gtab, QTab::of(qws + (size_t)blockIdx.x * (QWS_PAIR_UINT4_PER_SIG * (BLOCK / 2)), threadIdx.x >> 1)}, r, s, verdict_bits, status);
 }
 
 // The same with the per-signature table in LDS (PairQTabLds: 8 entries, signed 4-bit windows) instead of the global workspace: no
@@ -133,65 +230,44 @@ __global__ void __launch_bounds__(BLOCK, 1) p256_verify_pair_lds_solo_kernel(uin
                                                                              const uint8_t* __restrict__ s, const int32_t* __restrict__ gtab,
                                                                              uint64_t* __restrict__ verdict_bits, uint8_t* __restrict__ status) {
     extern __shared__ uint4 pair_lds[];
-    constexpr int NP = BLOCK / 2;
-    const bool odd = (threadIdx.x & 1) != 0;
-    const uint32_t pairidx = threadIdx.x >> 1;
-    PairQTabLds qtab = PairQTabLds::of(pair_lds, pairidx);
-    uint32_t* verdict32 = reinterpret_cast<uint32_t*>(verdict_bits);
-    const uint32_t ntiles = (n + NP - 1) / NP;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        uint32_t i = tile * NP + pairidx;
-        bool active = i < n;
-        uint32_t ic = active ? i : (n - 1);
-        u256 vqx, vqy, ve, vr, vs;
-        load_be_field(vqx, qx, ic);
-        load_be_field(vqy, qy, ic);
-        load_be_field(ve, e, ic);
-        load_be_field(vr, r, ic);
-        load_be_field(vs, s, ic);
-        uint32_t st = p256_verify_pair29<PairQTabLds, 4>(vqx, vqy, ve, vr, vs, gtab, qtab, odd);
-        pair_emit_verdict(i, n, active, odd, st, verdict32, status);
-    }
+    verify_tiles<BLOCK>(n, DigestGiven{e}, FreshKey<2, PairQTabLds, 4>{qx, qy, gtab, PairQTabLds::of(pair_lds, threadIdx.x >> 1)}, r, s, verdict_bits, status);
 }
 
 // The LDS-table pair kernel with HELPER WAVES (p256_pair29.h, "HELPER-WAVE FORM"): 2 x BLOCK threads, the same 128 signatures per
 // tile.  Threads 0..BLOCK-1 (main) run the u2*Q chain and emit the verdicts; threads BLOCK..2 BLOCK-1 (helper) run s^-1, u1, u2 and
-// u1*G on the same SIMDs and hand u2 and S over through LDS.  Every wave reaches both barriers of every tile (tail lanes compute on
-// the last tuple, as in the other kernels).  Dynamic LDS: pair_table_lds_bytes().
+// u1*G on the same SIMDs and hand u2 and S over through LDS.  Every wave reaches both barriers of every tile (TileGeom::row).
+// Two roles and two barriers: a tile loop of its own, on the same geometry.  Dynamic LDS: pair_table_lds_bytes().
 template <int BLOCK>
 __global__ void __launch_bounds__(2 * BLOCK, 1) p256_verify_pair_lds_kernel(uint32_t n, const uint8_t* __restrict__ qx, const uint8_t* __restrict__ qy,
                                                                                  const uint8_t* __restrict__ e, const uint8_t* __restrict__ r,
                                                                                  const uint8_t* __restrict__ s, const int32_t* __restrict__ gtab,
                                                                                  uint64_t* __restrict__ verdict_bits, uint8_t* __restrict__ status) {
     extern __shared__ uint4 pair_lds[];
-    constexpr int NP = BLOCK / 2;
+    using Geom = TileGeom<BLOCK, 2>;
     // wave-uniform by construction (BLOCK is a multiple of 64); readfirstlane makes the role a scalar branch for the compiler too
     const bool helper = __builtin_amdgcn_readfirstlane(threadIdx.x) >= (uint32_t)BLOCK;
     const uint32_t lane = threadIdx.x & (uint32_t)(BLOCK - 1);
-    const bool odd = (lane & 1) != 0;
-    const uint32_t pairidx = lane >> 1;
-    PairQTabLds qtab = PairQTabLds::of(pair_lds, pairidx);
-    const PairHandoffLds<BLOCK> hand = PairHandoffLds<BLOCK>::of(reinterpret_cast<uint32_t*>(pair_lds + NP * PAIR_LDS_CELLS_PER_SIG), lane);
-    uint32_t* verdict32 = reinterpret_cast<uint32_t*>(verdict_bits);
-    const uint32_t ntiles = (n + NP - 1) / NP;
+    const bool odd = Geom::odd(lane);
+    const uint32_t sub = Geom::sub(lane);
+    PairQTabLds qtab = PairQTabLds::of(pair_lds, sub);
+    const PairHandoffLds<BLOCK> hand = PairHandoffLds<BLOCK>::of(reinterpret_cast<uint32_t*>(pair_lds + Geom::PER_WG * PAIR_LDS_CELLS_PER_SIG), lane);
+    const uint32_t ntiles = Geom::ntiles(n);
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        uint32_t i = tile * NP + pairidx;
-        bool active = i < n;
-        uint32_t ic = active ? i : (n - 1);
+        const TileRow t = Geom::row(tile, sub, n);
         u256 u1;                      // helper
         uint32_t early = 0;           // helper: range gates
         pair_pt Qp, T;                // main
         bool q_ok = false, t_inf = true;
         if (helper) {
             u256 ve, vr, vs;
-            load_be_field(ve, e, ic);
-            load_be_field(vr, r, ic);
-            load_be_field(vs, s, ic);
+            load_be_field(ve, e, t.ic);
+            load_be_field(vr, r, t.ic);
+            load_be_field(vs, s, t.ic);
             pair_helper_scalars29(u1, early, ve, vr, vs, hand, odd);
         } else {
             u256 vqx, vqy;
-            load_be_field(vqx, qx, ic);
-            load_be_field(vqy, qy, ic);
+            load_be_field(vqx, qx, t.ic);
+            load_be_field(vqy, qy, t.ic);
             q_ok = pair_main_table29(Qp, vqx, vqy, qtab, odd);
         }
         __syncthreads();              // A: u2 in LDS
@@ -205,41 +281,20 @@ __global__ void __launch_bounds__(2 * BLOCK, 1) p256_verify_pair_lds_kernel(uint
         __syncthreads();              // B: S, s_inf and the gate status in LDS
         if (!helper) {
             u256 vr;                  // (loaded here, not kept in registers across the chain)
-            load_be_field(vr, r, ic);
+            load_be_field(vr, r, t.ic);
             uint32_t st = pair_main_finish29(T, t_inf, q_ok, vr, hand, odd);
-            pair_emit_verdict(i, n, active, odd, st, verdict32, status);
+            Geom::emit(t, n, odd, st, verdict_bits, status);
         }
     }
 }
 
-// Registered public keys (fabgpu_p256_key_register): every signature names a key whose 8-bit comb table is resident on the
-// device, so u2*Q is 32 mixed additions like u1*G: no doublings, no per-lane table, no workspace.  ktabs[KTAB_STRIDE k] = table of key k,
-// ktabs[KTAB_STRIDE k + 1] = its 16-bit comb or nullptr (round 6, FABGPU_FLAG_KEY_TABLES_16BIT: 16 mixed additions when a whole wavefront has them).
-// An out-of-range key id reports status 4 ("use bccsp/sw"), never a verdict.
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK, 2) p256_verify_keyed_kernel(uint32_t n, const uint32_t* __restrict__ key_id, uint32_t nkeys,
                                                                           const int32_t* const* __restrict__ ktabs, const uint8_t* __restrict__ e,
                                                                           const uint8_t* __restrict__ r, const uint8_t* __restrict__ s,
                                                                           const int32_t* __restrict__ gtab, uint64_t* __restrict__ verdict_bits,
                                                                           uint8_t* __restrict__ status) {
-    GTab16 gt{gtab};
-    const uint32_t ntiles = (n + BLOCK - 1) / BLOCK;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        uint32_t i = tile * BLOCK + threadIdx.x;
-        bool active = i < n;
-        uint32_t ic = active ? i : (n - 1);
-        uint32_t kid = key_id[ic];
-        bool kok = kid < nkeys;
-        KeyTab8 kt{ktabs[KTAB_STRIDE * (size_t)(kok ? kid : 0)]};
-        const int32_t* kt16 = ktabs[KTAB_STRIDE * (size_t)(kok ? kid : 0) + 1];
-        u256 ve, vr, vs;
-        load_be_field(ve, e, ic);
-        load_be_field(vr, r, ic);
-        load_be_field(vs, s, ic);
-        uint32_t st = __all(kt16 != nullptr) ? p256_verify_keyed_core29(ve, vr, vs, gt, GTab16{kt16}) : p256_verify_keyed_core29(ve, vr, vs, gt, kt);
-        if (!kok) st = ST_OFF_CURVE;
-        emit_verdict(i, active, st, verdict_bits, status);
-    }
+    verify_tiles<BLOCK>(n, DigestGiven{e}, RegisteredKey<1>{key_id, nkeys, ktabs, gtab}, r, s, verdict_bits, status);
 }
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK, 2) p256_verify_keyed_pair_kernel(uint32_t n, const uint32_t* __restrict__ key_id, uint32_t nkeys,
@@ -247,30 +302,10 @@ __global__ void __launch_bounds__(BLOCK, 2) p256_verify_keyed_pair_kernel(uint32
                                                                                const uint8_t* __restrict__ r, const uint8_t* __restrict__ s,
                                                                                const int32_t* __restrict__ gtab, uint64_t* __restrict__ verdict_bits,
                                                                                uint8_t* __restrict__ status) {
-    constexpr int NP = BLOCK / 2;
-    const bool odd = (threadIdx.x & 1) != 0;
-    const uint32_t pairidx = threadIdx.x >> 1;
-    uint32_t* verdict32 = reinterpret_cast<uint32_t*>(verdict_bits);
-    const uint32_t ntiles = (n + NP - 1) / NP;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        uint32_t i = tile * NP + pairidx;
-        bool active = i < n;
-        uint32_t ic = active ? i : (n - 1);
-        uint32_t kid = key_id[ic];
-        bool kok = kid < nkeys;
-        const int32_t* kt = ktabs[KTAB_STRIDE * (size_t)(kok ? kid : 0)];
-        const int32_t* kt16 = ktabs[KTAB_STRIDE * (size_t)(kok ? kid : 0) + 1];
-        u256 ve, vr, vs;
-        load_be_field(ve, e, ic);
-        load_be_field(vr, r, ic);
-        load_be_field(vs, s, ic);
-        uint32_t st = p256_verify_keyed_pair29(ve, vr, vs, gtab, kt, kt16, odd);
-        if (!kok) st = ST_OFF_CURVE;
-        pair_emit_verdict(i, n, active, odd, st, verdict32, status);
-    }
+    verify_tiles<BLOCK>(n, DigestGiven{e}, RegisteredKey<2>{key_id, nkeys, ktabs, gtab}, r, s, verdict_bits, status);
 }
 
-// identity.Verify fused, registered keys: SHA-256 then the keyed core; the digest stays in registers.
+// identity.Verify fused (SHA-256 then the core; the digest stays in registers): registered keys ...
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK, 2) sha256_p256_verify_keyed_kernel(uint32_t n, const uint32_t* __restrict__ arena32, uint32_t arena_words,
                                                                                  const uint32_t* __restrict__ off, const uint32_t* __restrict__ key_id,
@@ -278,28 +313,7 @@ __global__ void __launch_bounds__(BLOCK, 2) sha256_p256_verify_keyed_kernel(uint
                                                                                  const uint8_t* __restrict__ r, const uint8_t* __restrict__ s,
                                                                                  const int32_t* __restrict__ gtab, uint64_t* __restrict__ verdict_bits,
                                                                                  uint8_t* __restrict__ status, sha_prefixes pre) {
-    GTab16 gt{gtab};
-    const uint32_t ntiles = (n + BLOCK - 1) / BLOCK;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        uint32_t i = tile * BLOCK + threadIdx.x;
-        bool active = i < n;
-        uint32_t ic = active ? i : (n - 1);
-        uint32_t h[8];
-        sha256_message(arena32, arena_words, off, pre, ic, active, h);
-        emit_digest(pre, i, active, h);
-        uint32_t kid = key_id[ic];
-        bool kok = kid < nkeys;
-        KeyTab8 kt{ktabs[KTAB_STRIDE * (size_t)(kok ? kid : 0)]};
-        const int32_t* kt16 = ktabs[KTAB_STRIDE * (size_t)(kok ? kid : 0) + 1];
-        u256 ve, vr, vs;
-#pragma unroll
-        for (int k = 0; k < 8; k++) ve.w[k] = h[7 - k];
-        load_be_field(vr, r, ic);
-        load_be_field(vs, s, ic);
-        uint32_t st = __all(kt16 != nullptr) ? p256_verify_keyed_core29(ve, vr, vs, gt, GTab16{kt16}) : p256_verify_keyed_core29(ve, vr, vs, gt, kt);
-        if (!kok) st = ST_OFF_CURVE;
-        emit_verdict(i, active, st, verdict_bits, status);
-    }
+    verify_tiles<BLOCK>(n, DigestHashed{arena32, arena_words, off, pre}, RegisteredKey<1>{key_id, nkeys, ktabs, gtab}, r, s, verdict_bits, status);
 }
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK, 2) sha256_p256_verify_keyed_pair_kernel(uint32_t n, const uint32_t* __restrict__ arena32, uint32_t arena_words,
@@ -308,35 +322,10 @@ __global__ void __launch_bounds__(BLOCK, 2) sha256_p256_verify_keyed_pair_kernel
                                                                                       const uint8_t* __restrict__ r, const uint8_t* __restrict__ s,
                                                                                       const int32_t* __restrict__ gtab, uint64_t* __restrict__ verdict_bits,
                                                                                       uint8_t* __restrict__ status, sha_prefixes pre) {
-    constexpr int NP = BLOCK / 2;
-    const bool odd = (threadIdx.x & 1) != 0;
-    const uint32_t pairidx = threadIdx.x >> 1;
-    uint32_t* verdict32 = reinterpret_cast<uint32_t*>(verdict_bits);
-    const uint32_t ntiles = (n + NP - 1) / NP;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        uint32_t i = tile * NP + pairidx;
-        bool active = i < n;
-        uint32_t ic = active ? i : (n - 1);
-        uint32_t h[8];
-        sha256_message(arena32, arena_words, off, pre, ic, active, h);
-        emit_digest(pre, i, active && !odd, h);
-        uint32_t kid = key_id[ic];
-        bool kok = kid < nkeys;
-        const int32_t* kt = ktabs[KTAB_STRIDE * (size_t)(kok ? kid : 0)];
-        const int32_t* kt16 = ktabs[KTAB_STRIDE * (size_t)(kok ? kid : 0) + 1];
-        u256 ve, vr, vs;
-#pragma unroll
-        for (int k = 0; k < 8; k++) ve.w[k] = h[7 - k];
-        load_be_field(vr, r, ic);
-        load_be_field(vs, s, ic);
-        uint32_t st = p256_verify_keyed_pair29(ve, vr, vs, gtab, kt, kt16, odd);
-        if (!kok) st = ST_OFF_CURVE;
-        pair_emit_verdict(i, n, active, odd, st, verdict32, status);
-    }
+    verify_tiles<BLOCK>(n, DigestHashed{arena32, arena_words, off, pre}, RegisteredKey<2>{key_id, nkeys, ktabs, gtab}, r, s, verdict_bits, status);
 }
 
-// identity.Verify fused, two lanes per signature: both lanes of a pair hash the (same) message - the hash is 18 % of the
-// stream and does not split across lanes - and keep the digest in registers.
+// ... and fresh ones, with two lanes per signature and with one
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK, 1) sha256_p256_verify_pair_kernel(uint32_t n, const uint32_t* __restrict__ arena32, uint32_t arena_words,
                                                                                 const uint32_t* __restrict__ off, const uint8_t* __restrict__ qx,
@@ -344,32 +333,10 @@ __global__ void __launch_bounds__(BLOCK, 1) sha256_p256_verify_pair_kernel(uint3
                                                                                 const uint8_t* __restrict__ s, const int32_t* __restrict__ gtab,
                                                                                 uint4* __restrict__ qws, uint64_t* __restrict__ verdict_bits,
                                                                                 uint8_t* __restrict__ status, sha_prefixes pre) {
-    constexpr int NP = BLOCK / 2;
-    const bool odd = (threadIdx.x & 1) != 0;
-    const uint32_t pairidx = threadIdx.x >> 1;
-    PairQTab<NP> qtab = PairQTab<NP>::of(qws + (size_t)blockIdx.x * (QWS_PAIR_UINT4_PER_SIG * NP), pairidx);
-    uint32_t* verdict32 = reinterpret_cast<uint32_t*>(verdict_bits);
-    const uint32_t ntiles = (n + NP - 1) / NP;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        uint32_t i = tile * NP + pairidx;
-        bool active = i < n;
-        uint32_t ic = active ? i : (n - 1);
-        uint32_t h[8];
-        sha256_message(arena32, arena_words, off, pre, ic, active, h);
-        emit_digest(pre, i, active && !odd, h);
-        u256 vqx, vqy, ve, vr, vs;
-#pragma unroll
-        for (int k = 0; k < 8; k++) ve.w[k] = h[7 - k];
-        load_be_field(vqx, qx, ic);
-        load_be_field(vqy, qy, ic);
-        load_be_field(vr, r, ic);
-        load_be_field(vs, s, ic);
-        uint32_t st = p256_verify_pair29(vqx, vqy, ve, vr, vs, gtab, qtab, odd);
-        pair_emit_verdict(i, n, active, odd, st, verdict32, status);
-    }
+    using QTab = PairQTab<BLOCK / 2>;
+    verify_tiles<BLOCK>(n, DigestHashed{arena32, arena_words, off, pre},
+                        FreshKey<2, QTab>{qx, qy, gtab, QTab::of(qws + (size_t)blockIdx.x * (QWS_PAIR_UINT4_PER_SIG * (BLOCK / 2)), threadIdx.x >> 1)}, r, s, verdict_bits, status);
 }
-
-// identity.Verify fused: e = SHA-256(msg) stays in registers
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK, 2) sha256_p256_verify_kernel(uint32_t n, const uint32_t* __restrict__ arena32, uint32_t arena_words,
                                                                            const uint32_t* __restrict__ off, const uint8_t* __restrict__ qx,
@@ -377,26 +344,9 @@ __global__ void __launch_bounds__(BLOCK, 2) sha256_p256_verify_kernel(uint32_t n
                                                                            const uint8_t* __restrict__ s, const int32_t* __restrict__ gtab,
                                                                            uint4* __restrict__ qws, uint64_t* __restrict__ verdict_bits,
                                                                            uint8_t* __restrict__ status, sha_prefixes pre) {
-    GlobalQTab29<BLOCK> qtab = GlobalQTab29<BLOCK>::of(qws + (size_t)blockIdx.x * (QWS_UINT4_PER_LANE * BLOCK), threadIdx.x);
-    GTab16 gt{gtab};
-    const uint32_t ntiles = (n + BLOCK - 1) / BLOCK;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        uint32_t i = tile * BLOCK + threadIdx.x;
-        bool active = i < n;
-        uint32_t ic = active ? i : (n - 1);
-        uint32_t h[8];
-        sha256_message(arena32, arena_words, off, pre, ic, active, h);
-        emit_digest(pre, i, active, h);
-        u256 vqx, vqy, ve, vr, vs;
-#pragma unroll
-        for (int k = 0; k < 8; k++) ve.w[k] = h[7 - k];   // digest big-endian -> integer limbs
-        load_be_field(vqx, qx, ic);
-        load_be_field(vqy, qy, ic);
-        load_be_field(vr, r, ic);
-        load_be_field(vs, s, ic);
-        uint32_t st = p256_verify_core29(vqx, vqy, ve, vr, vs, gt, qtab);
-        emit_verdict(i, active, st, verdict_bits, status);
-    }
+    using QTab = GlobalQTab29<BLOCK>;
+    verify_tiles<BLOCK>(n, DigestHashed{arena32, arena_words, off, pre},
+                        FreshKey<1, QTab>{qx, qy, gtab, QTab::of(qws + (size_t)blockIdx.x * (QWS_UINT4_PER_LANE * BLOCK), threadIdx.x)}, r, s, verdict_bits, status);
 }
 
 // Stitches the pieces of gathered messages (fabgpu_identity_batch.gather_spans) into consecutive bytes: one WAVEFRONT per message,
@@ -424,15 +374,16 @@ __global__ void __launch_bounds__(256) gather_spans_kernel(uint32_t n, const uin
 // ------------------------------------------------------------------------------------------------
 // launchers (host)
 // ------------------------------------------------------------------------------------------------
+static void launch_midstate_kernel(const void* arena, size_t arena_bytes, const ShaPrefixArgs& pa, uint32_t lds, hipStream_t st) {
+    dim3 grid((pa.m + 255) / 256), block(256);
+    hipLaunchKernelGGL(sha256_midstate_kernel, grid, block, lds, st, pa.m, (const uint32_t*)arena, (uint32_t)((arena_bytes + 3) / 4),
+                       (const uint32_t*)pa.pre_off, pa.spans ? 1u : 0u, (uint32_t*)pa.mid_scratch);
+}
 // Runs the mid-state kernel for a prefixed batch (no-op otherwise) and returns the descriptor the fused kernels take.
 static sha_prefixes launch_midstates(const void* arena, size_t arena_bytes, const ShaPrefixArgs& pa, hipStream_t st) {
     sha_prefixes pre{nullptr, nullptr, nullptr, 0, pa.spans ? 1u : 0u, (uint32_t*)pa.digests};
     if (pa.m == 0 || pa.pre_idx == nullptr) return pre;
-    if (!pa.mid_ready) {
-        dim3 grid((pa.m + 255) / 256), block(256);
-        hipLaunchKernelGGL(sha256_midstate_kernel, grid, block, 0, st, pa.m, (const uint32_t*)arena, (uint32_t)((arena_bytes + 3) / 4),
-                           (const uint32_t*)pa.pre_off, pre.spans, (uint32_t*)pa.mid_scratch);
-    }
+    if (!pa.mid_ready) launch_midstate_kernel(arena, arena_bytes, pa, 0, st);
     pre.pre_idx = (const uint32_t*)pa.pre_idx;
     pre.pre_off = (const uint32_t*)pa.pre_off;
     pre.mid = (const uint32_t*)pa.mid_scratch;
@@ -441,9 +392,7 @@ static sha_prefixes launch_midstates(const void* arena, size_t arena_bytes, cons
 }
 hipError_t launch_sha256_midstates(const void* arena, size_t arena_bytes, const ShaPrefixArgs& pa, hipStream_t st) {
     if (pa.m == 0) return hipSuccess;
-    dim3 grid((pa.m + 255) / 256), block(256);
-    hipLaunchKernelGGL(sha256_midstate_kernel, grid, block, pa.lds_reserve, st, pa.m, (const uint32_t*)arena, (uint32_t)((arena_bytes + 3) / 4),
-                       (const uint32_t*)pa.pre_off, pa.spans ? 1u : 0u, (uint32_t*)pa.mid_scratch);
+    launch_midstate_kernel(arena, arena_bytes, pa, pa.lds_reserve, st);
     return hipGetLastError();
 }
 hipError_t launch_sha256_batch(uint32_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, hipStream_t st, uint32_t lds_spread) {
@@ -488,7 +437,7 @@ VerifyGeom verify_geom(uint32_t n, bool allow_pair) {
     return g;
 }
 // Where the two-lanes-per-signature verify-only kernel keeps its per-signature table when the context does not say
-// (FABGPU_FLAG_PAIR_TABLE_LDS / _GLOBAL in fabgpu_cfg.flags force one; bench.py --pair-table for A/B runs): -1 = by batch size (launch_p256_verify).
+// (FABGPU_FLAG_PAIR_TABLE_LDS / _GLOBAL in fabgpu_cfg.flags force one; bench.py --pair-table for A/B runs): -1 = by batch size (launch_verify).
 int pair_table_default() { return -1; }
 // helper-wave form: the 128 tables + the handoff (PAIR_HAND_WORDS per main lane) = 133 120 + 27 648 = 160 768 bytes of the CU's 163 840
 size_t pair_table_lds_bytes() { return (size_t)(VERIFY_BLOCK / 2) * PAIR_LDS_CELLS_PER_SIG * 16 + (size_t)VERIFY_BLOCK * PAIR_HAND_WORDS * 4; }
@@ -498,86 +447,70 @@ size_t verify_workspace_bytes(uint32_t n, bool allow_pair) {
     if (g.pair) return (size_t)g.wgs * (g.block / 2) * QWS_PAIR_UINT4_PER_SIG * 16;
     return (size_t)g.wgs * g.block * QWS_UINT4_PER_LANE * 16;
 }
-hipError_t launch_p256_verify(uint32_t n, const void* qx, const void* qy, const void* e, const void* r, const void* s,
-                              const void* gtab, void* qws, void* verdict_bits, void* status, bool allow_pair, hipStream_t st, uint32_t lds_reserve, int table_lds,
-                              bool pair_solo) {
-    if (n == 0) return hipSuccess;
-    VerifyGeom g = verify_geom(n, allow_pair);
-    dim3 grid(g.wgs), block(g.block);
-    // The per-signature table of the pair kernel: in LDS when the launch is large (measured on MI355X, tools/gpu_pair_table_ab.py and
-    // tools/gpu_pmc_traffic.sh: at 30 000 tuples the two forms take the same time - 0.631 / 0.629 ms back to back - and the LDS form
-    // moves 94 MB through the memory system per launch instead of 279 MB); in the global workspace for smaller ones, where the LDS
-    // form's 13 extra additions show as latency (10 000 tuples: 0.624 against 0.614 ms; 1 000: 0.618 against 0.603 ms).
-    if (table_lds < 0) table_lds = n > (uint32_t)PAIR_TABLE_LDS_FROM ? 1 : 0;
-    // The LDS form with helper waves (two waves per SIMD: the scalar part and u1*G beside the u2*Q chain) unless the context asks for
-    // the one-wave form (FABGPU_FLAG_PAIR_SOLO, A/B runs).
-    if (g.pair && table_lds && !pair_solo) {
-        hipLaunchKernelGGL(p256_verify_pair_lds_kernel<VERIFY_BLOCK>, grid, dim3(2 * VERIFY_BLOCK), pair_table_lds_bytes(), st, n, (const uint8_t*)qx,
-                           (const uint8_t*)qy, (const uint8_t*)e, (const uint8_t*)r, (const uint8_t*)s, (const int32_t*)gtab, (uint64_t*)verdict_bits, (uint8_t*)status);
-        return hipGetLastError();
-    }
-    if (g.pair && table_lds) {
-        hipLaunchKernelGGL(p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK>, grid, block, pair_table_lds_solo_bytes(), st, n, (const uint8_t*)qx,
-                           (const uint8_t*)qy, (const uint8_t*)e, (const uint8_t*)r, (const uint8_t*)s, (const int32_t*)gtab, (uint64_t*)verdict_bits, (uint8_t*)status);
-        return hipGetLastError();
-    }
-    if (g.pair) {
-        hipLaunchKernelGGL(p256_verify_pair_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, (const uint8_t*)qx, (const uint8_t*)qy, (const uint8_t*)e,
-                           (const uint8_t*)r, (const uint8_t*)s, (const int32_t*)gtab, (uint4*)qws, (uint64_t*)verdict_bits, (uint8_t*)status);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(p256_verify_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, (const uint8_t*)qx, (const uint8_t*)qy, (const uint8_t*)e,
-                       (const uint8_t*)r, (const uint8_t*)s, (const int32_t*)gtab, (uint4*)qws, (uint64_t*)verdict_bits, (uint8_t*)status);
-    return hipGetLastError();
-}
-hipError_t launch_sha256_p256_verify(uint32_t n, const void* arena, size_t arena_bytes, const void* off, const void* qx,
-                                     const void* qy, const void* r, const void* s, const void* gtab, void* qws,
-                                     void* verdict_bits, void* status, bool allow_pair, const ShaPrefixArgs& pa, hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    sha_prefixes pre = launch_midstates(arena, arena_bytes, pa, st);
-    VerifyGeom g = verify_geom(n, allow_pair);
-    dim3 grid(g.wgs), block(g.block);
-    if (g.pair) {
-        hipLaunchKernelGGL(sha256_p256_verify_pair_kernel<VERIFY_BLOCK>, grid, block, pa.lds_reserve, st, n, (const uint32_t*)arena, (uint32_t)((arena_bytes + 3) / 4),
-                           (const uint32_t*)off, (const uint8_t*)qx, (const uint8_t*)qy, (const uint8_t*)r, (const uint8_t*)s,
-                           (const int32_t*)gtab, (uint4*)qws, (uint64_t*)verdict_bits, (uint8_t*)status, pre);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(sha256_p256_verify_kernel<VERIFY_BLOCK>, grid, block, pa.lds_reserve, st, n, (const uint32_t*)arena, (uint32_t)((arena_bytes + 3) / 4),
-                       (const uint32_t*)off, (const uint8_t*)qx, (const uint8_t*)qy, (const uint8_t*)r, (const uint8_t*)s,
-                       (const int32_t*)gtab, (uint4*)qws, (uint64_t*)verdict_bits, (uint8_t*)status, pre);
-    return hipGetLastError();
-}
 
-hipError_t launch_p256_verify_keyed(uint32_t n, const void* key_id, uint32_t nkeys, const void* ktabs, const void* e, const void* r, const void* s,
-                                    const void* gtab, void* verdict_bits, void* status, bool allow_pair, hipStream_t st, uint32_t lds_reserve) {
+// One ECDSA P-256 verify launch (kernels.h VerifyLaunch): picks the kernel by key source, digest source, batch size and table home.
+hipError_t launch_verify(const VerifyLaunch& v, hipStream_t st) {
+    const uint32_t n = v.n;
     if (n == 0) return hipSuccess;
-    VerifyGeom g = verify_geom(n, allow_pair);
+    const bool keyed = v.key_id != nullptr && v.ktabs != nullptr, fresh = v.qx != nullptr && v.qy != nullptr;
+    const bool hashed = v.off != nullptr, given = v.e != nullptr;
+    // exactly one of each pair of alternatives, none of them half-named, and no message bytes without an arena
+    if (keyed == fresh || hashed == given || keyed != (v.key_id != nullptr || v.ktabs != nullptr) || fresh != (v.qx != nullptr || v.qy != nullptr) ||
+        (hashed && v.arena == nullptr && v.arena_bytes != 0))
+        return hipErrorInvalidValue;
+    const uint8_t *qx = (const uint8_t*)v.qx, *qy = (const uint8_t*)v.qy, *e = (const uint8_t*)v.e, *r = (const uint8_t*)v.r, *s = (const uint8_t*)v.s;
+    const uint32_t *key_id = (const uint32_t*)v.key_id, *arena32 = (const uint32_t*)v.arena, *off = (const uint32_t*)v.off;
+    const uint32_t arena_words = (uint32_t)((v.arena_bytes + 3) / 4);
+    const int32_t* const* ktabs = (const int32_t* const*)v.ktabs;
+    const int32_t* gtab = (const int32_t*)v.gtab;
+    uint4* qws = (uint4*)v.qws;
+    uint64_t* verdict_bits = (uint64_t*)v.verdict_bits;
+    uint8_t* status = (uint8_t*)v.status;
+    sha_prefixes pre{};
+    if (hashed) pre = launch_midstates(v.arena, v.arena_bytes, v.pa, st);
+    VerifyGeom g = verify_geom(n, v.allow_pair);
     dim3 grid(g.wgs), block(g.block);
+    const uint32_t lds_reserve = hashed ? v.pa.lds_reserve : v.lds_reserve;   // (a fused launch carries its reservation with its prefixes)
+    if (!hashed && !keyed) {
+        // The per-signature table of the pair kernel: in LDS when the launch is large (measured on MI355X, tools/gpu_pair_table_ab.py and
+        // tools/gpu_pmc_traffic.sh: at 30 000 tuples the two forms take the same time - 0.631 / 0.629 ms back to back - and the LDS form
+        // moves 94 MB through the memory system per launch instead of 279 MB); in the global workspace for smaller ones, where the LDS
+        // form's 13 extra additions show as latency (10 000 tuples: 0.624 against 0.614 ms; 1 000: 0.618 against 0.603 ms).
+        const bool table_lds = v.table_lds < 0 ? n > (uint32_t)PAIR_TABLE_LDS_FROM : v.table_lds != 0;
+        // The LDS form with helper waves (two waves per SIMD: the scalar part and u1*G beside the u2*Q chain) unless the context asks for
+        // the one-wave form (FABGPU_FLAG_PAIR_SOLO, A/B runs).
+        if (g.pair && table_lds && !v.pair_solo)
+            hipLaunchKernelGGL(p256_verify_pair_lds_kernel<VERIFY_BLOCK>, grid, dim3(2 * VERIFY_BLOCK), pair_table_lds_bytes(), st, n, qx, qy, e, r, s, gtab, verdict_bits, status);
+        else if (g.pair && table_lds)
+            hipLaunchKernelGGL(p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK>, grid, block, pair_table_lds_solo_bytes(), st, n, qx, qy, e, r, s, gtab, verdict_bits, status);
+        else if (g.pair)
+            hipLaunchKernelGGL(p256_verify_pair_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, qx, qy, e, r, s, gtab, qws, verdict_bits, status);
+        else
+            hipLaunchKernelGGL(p256_verify_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, qx, qy, e, r, s, gtab, qws, verdict_bits, status);
+        return hipGetLastError();
+    }
+    if (hashed && !keyed) {
+        if (g.pair)
+            hipLaunchKernelGGL(sha256_p256_verify_pair_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, arena32, arena_words, off, qx, qy, r, s, gtab, qws,
+                               verdict_bits, status, pre);
+        else
+            hipLaunchKernelGGL(sha256_p256_verify_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, arena32, arena_words, off, qx, qy, r, s, gtab, qws,
+                               verdict_bits, status, pre);
+        return hipGetLastError();
+    }
+    if (!hashed) {
+        if (g.pair)
+            hipLaunchKernelGGL(p256_verify_keyed_pair_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, key_id, v.nkeys, ktabs, e, r, s, gtab, verdict_bits, status);
+        else
+            hipLaunchKernelGGL(p256_verify_keyed_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, key_id, v.nkeys, ktabs, e, r, s, gtab, verdict_bits, status);
+        return hipGetLastError();
+    }
     if (g.pair)
-        hipLaunchKernelGGL(p256_verify_keyed_pair_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, (const uint32_t*)key_id, nkeys, (const int32_t* const*)ktabs,
-                           (const uint8_t*)e, (const uint8_t*)r, (const uint8_t*)s, (const int32_t*)gtab, (uint64_t*)verdict_bits, (uint8_t*)status);
+        hipLaunchKernelGGL(sha256_p256_verify_keyed_pair_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, arena32, arena_words, off, key_id, v.nkeys, ktabs,
+                           r, s, gtab, verdict_bits, status, pre);
     else
-        hipLaunchKernelGGL(p256_verify_keyed_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, (const uint32_t*)key_id, nkeys, (const int32_t* const*)ktabs,
-                           (const uint8_t*)e, (const uint8_t*)r, (const uint8_t*)s, (const int32_t*)gtab, (uint64_t*)verdict_bits, (uint8_t*)status);
-    return hipGetLastError();
-}
-
-hipError_t launch_sha256_p256_verify_keyed(uint32_t n, const void* arena, size_t arena_bytes, const void* off, const void* key_id, uint32_t nkeys,
-                                           const void* ktabs, const void* r, const void* s, const void* gtab, void* verdict_bits, void* status,
-                                           bool allow_pair, const ShaPrefixArgs& pa, hipStream_t st) {
-    if (n == 0) return hipSuccess;
-    sha_prefixes pre = launch_midstates(arena, arena_bytes, pa, st);
-    VerifyGeom g = verify_geom(n, allow_pair);
-    dim3 grid(g.wgs), block(g.block);
-    if (g.pair)
-        hipLaunchKernelGGL(sha256_p256_verify_keyed_pair_kernel<VERIFY_BLOCK>, grid, block, pa.lds_reserve, st, n, (const uint32_t*)arena,
-                           (uint32_t)((arena_bytes + 3) / 4), (const uint32_t*)off, (const uint32_t*)key_id, nkeys, (const int32_t* const*)ktabs,
-                           (const uint8_t*)r, (const uint8_t*)s, (const int32_t*)gtab, (uint64_t*)verdict_bits, (uint8_t*)status, pre);
-    else
-        hipLaunchKernelGGL(sha256_p256_verify_keyed_kernel<VERIFY_BLOCK>, grid, block, pa.lds_reserve, st, n, (const uint32_t*)arena,
-                           (uint32_t)((arena_bytes + 3) / 4), (const uint32_t*)off, (const uint32_t*)key_id, nkeys, (const int32_t* const*)ktabs,
-                           (const uint8_t*)r, (const uint8_t*)s, (const int32_t*)gtab, (uint64_t*)verdict_bits, (uint8_t*)status, pre);
+        hipLaunchKernelGGL(sha256_p256_verify_keyed_kernel<VERIFY_BLOCK>, grid, block, lds_reserve, st, n, arena32, arena_words, off, key_id, v.nkeys, ktabs,
+                           r, s, gtab, verdict_bits, status, pre);
     return hipGetLastError();
 }
 
