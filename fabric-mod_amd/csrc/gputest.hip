@@ -527,6 +527,41 @@ extern "C" int gputest_scalar_op(int op, uint32_t n, const uint8_t* a, const uin
     return rc;
 }
 
+// The GLV decomposition of the pseudonym kernels (bn_nym29.h bn_glv_decompose: mul512 / sub256 chains, whose device compilation is the
+// mac of fp256.h).  in: 32 big-endian bytes per item (any 256-bit value);  out per item: m1[32] m2[32] big-endian magnitudes, then one
+// little-endian flag word, bit 0 = k1 negative, bit 1 = k2 negative.
+constexpr uint32_t GLV_ROW_BYTES = 68;
+__global__ void __launch_bounds__(PRIM_BLOCK) gputest_bn_glv_decompose_kernel(uint32_t n, const uint8_t* __restrict__ in, uint8_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * PRIM_BLOCK + threadIdx.x;
+    const bool active = i < n;
+    const uint32_t ic = active ? i : n - 1;
+    u256 k, m1, m2;
+    bool n1, n2;
+    from_be32(k, in + 32 * (size_t)ic);
+    bn_glv_decompose(m1, n1, m2, n2, k);
+    if (active) {
+        uint8_t* o = out + GLV_ROW_BYTES * (size_t)i;
+        to_be32(o, m1);
+        to_be32(o + 32, m2);
+        o[64] = (uint8_t)((n1 ? 1u : 0u) | (n2 ? 2u : 0u));
+        o[65] = 0;
+        o[66] = 0;
+        o[67] = 0;
+    }
+}
+
+extern "C" int gputest_bn_glv_decompose(uint32_t n, const uint8_t* in, uint8_t* out) {
+    if (n == 0 || n > PRIM_MAX_ITEMS || !in || !out) return -3;
+    DevBufs d;
+    const uint8_t* din = (const uint8_t*)d.put(in, (size_t)n * 32);
+    uint8_t* dout = (uint8_t*)d.get((size_t)n * GLV_ROW_BYTES);
+    if (!din || !dout) return -1;
+    hipLaunchKernelGGL(gputest_bn_glv_decompose_kernel, prim_grid(n), dim3(PRIM_BLOCK), 0, 0, n, din, dout);
+    int rc = prim_sync();
+    if (rc == 0 && !prim_back(out, dout, (size_t)n * GLV_ROW_BYTES)) rc = -4;
+    return rc;
+}
+
 // Safegcd inversion (modinv30.h modinv; p256_pair29.h pair_modinv).  which: 0 mod n, 1 mod p (P-256), 2 mod the FP256BN prime (what
 // bn_affine29 inverts by).  pair: one lane pair per item through pair_modinv, each lane's result written on its own.
 // in: 32 big-endian bytes per item;  out: 32 per LANE.

@@ -1058,7 +1058,7 @@ def test_the_gpu_test_library_exports_the_primitive_hooks_and_the_product_does_n
     import fabgpu
     fabgpu.load()
     hooks = {"gputest_field_op", "gputest_scalar_op", "gputest_modinv", "gputest_point_op", "gputest_combined", "gputest_pair_combined",
-             "gputest_pair_verify"}
+             "gputest_pair_verify", "gputest_bn_glv_decompose"}
     nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "fabric-mod_amd", "lib", "libfabgpu_gputest.so")], capture_output=True,
                         text=True, check=True).stdout
     assert hooks <= {ln.split()[-1] for ln in nm.splitlines() if ln.split()}
