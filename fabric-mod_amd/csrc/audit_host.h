@@ -1,0 +1,36 @@
+// CPU audit of what the provider hands out from the device (DESIGN.md 4.4e addendum): SHA-256 and one ECDSA P-256 verification on the
+// calling thread, and the rule that decides which hits are audited.  Host code only; no device, no libcrypto.
+//
+// The verification is the one-lane code the kernels are compiled from (fe29.h / ec29.h / modinv30.h / p256_verify29.h), compiled for the
+// host, behind the host gates of bccsp_host.cpp (DER unmarshal, r, s > 0, low-S, key on the curve, hashToInt); SHA-256 is plain C++ (the
+// device's uses GCN builtins).  So the audit catches wrong memory, a stale table, a race between passes, a kernel that was miscompiled
+// or mis-scheduled, a hardware fault - and it does NOT catch an arithmetic mistake in the shared source: both compilations would
+// make it.  That is what the oracle parity tests are for.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <atomic>
+
+namespace fab {
+namespace bccsp {
+
+void audit_sha256(const uint8_t* msg, size_t len, uint8_t* out32);
+// bccsp.Verify(k, sig, digest) as bccsp/sw decides it (bccsp/sw/impl.go:247-270 -> ecdsa.go:41-57): true = (true, nil), false =
+// everything else - a signature that does not unmarshal, r or s <= 0, high S, r >= n, a key that is not on the curve, an empty
+// signature or digest, a signature that does not verify.
+bool audit_p256_verify(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig_der, size_t siglen, const uint8_t* digest, size_t dlen);
+
+// Which hits are audited: no randomness.  Hit number h (1-based) is audited iff h * permille / 1000 != (h - 1) * permille / 1000:
+// 1000 every hit, 250 exactly every fourth (h = 4, 8, ..), 0 none; over H hits exactly H * permille / 1000 audits.
+inline bool audit_sampled(uint64_t h, uint32_t permille) { return h * permille / 1000 != (h - 1) * permille / 1000; }
+struct AuditSampler {
+    std::atomic<uint64_t> hits{0};
+    bool hit(uint32_t permille) {
+        if (!permille) return false;                        // (the default: hits are not even counted)
+        return audit_sampled(hits.fetch_add(1, std::memory_order_relaxed) + 1, permille);
+    }
+};
+
+}  // namespace bccsp
+}  // namespace fab

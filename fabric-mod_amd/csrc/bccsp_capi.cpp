@@ -64,6 +64,8 @@ int fabgpu_csp_new2(const fabgpu_csp_opts* o, fabgpu_csp** out, char* err, size_
         po.pass_timing = v.pass_timing;
         po.pass_hash_memo = v.pass_hash_memo;
         po.hash_memo_blocks = v.hash_memo_blocks;
+        if (v.audit_permille > 1000) return FABGPU_EINVAL;
+        po.audit_permille = v.audit_permille;
     }
     fabgpu_csp* h = new fabgpu_csp();
     Error e = GPUCSP::New(po, h->csp);
@@ -104,6 +106,28 @@ int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value) {
     return FABGPU_OK;
 }
 
+// ---- CPU audit and poisoning (GPUCSP::Poison; fabgpu_bccsp.h "CPU audit") ----
+int fabgpu_csp_poison(fabgpu_csp* csp, const char* why) {
+    if (!csp) return FABGPU_EINVAL;
+    csp->csp->Poison(std::string("by hand: ") + (why ? why : ""));
+    return FABGPU_OK;
+}
+int fabgpu_csp_poisoned(fabgpu_csp* csp, char* why, size_t cap) {
+    if (!csp) return FABGPU_EINVAL;
+    std::string w;
+    const bool p = csp->csp->Poisoned(&w);
+    put_err(why, cap, w);
+    return p ? 1 : 0;
+}
+int fabgpu_csp_audit_stats(fabgpu_csp* csp, uint64_t* out, int cap) {
+    if (!csp || !out || cap < 0) return FABGPU_EINVAL;
+    uint64_t v[GPUCSP::AUDIT_STATS];
+    csp->csp->AuditStats(v);
+    const int n = cap < (int)GPUCSP::AUDIT_STATS ? cap : (int)GPUCSP::AUDIT_STATS;
+    for (int i = 0; i < n; i++) out[i] = v[i];
+    return n;
+}
+
 int fabgpu_csp_key_import(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, int* on_curve, char* err, size_t errcap) {
     if (!csp) return FABGPU_EINVAL;
     ECDSAPublicKey k;
@@ -125,6 +149,7 @@ int fabgpu_csp_hash_memo_stats(fabgpu_csp* csp, uint64_t* hits, uint64_t* misses
 }
 int fabgpu_csp_hash(fabgpu_csp* csp, const uint8_t* msg, size_t len, const char* alg, uint8_t* digest32, char* err, size_t errcap) {
     if (!csp || !digest32) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
     HashOpts o;
     if (alg) o.algorithm = alg;
     std::vector<uint8_t> d;
@@ -137,6 +162,7 @@ int fabgpu_csp_hash(fabgpu_csp* csp, const uint8_t* msg, size_t len, const char*
 int fabgpu_csp_verify(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen,
                       const uint8_t* digest, size_t dlen, int* valid, int* flags, char* err, size_t errcap) {
     if (!csp || !valid) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
     ECDSAPublicKey k;
     const ECDSAPublicKey* kp = nullptr;
     if (qx32 && qy32) {
@@ -151,12 +177,18 @@ int fabgpu_csp_verify(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32,
     *valid = r.valid ? 1 : 0;
     if (flags) *flags = r.needs_sw ? 1 : 0;
     put_err(err, errcap, r.err.ok() ? "" : r.err.msg);
+    if (csp->csp->Poisoned()) {                              // this call's own audit, or another thread's while it was in flight
+        *valid = 0;
+        put_err(err, errcap, GPUCSP::PoisonedText());
+        return FABGPU_EPOISONED;
+    }
     return FABGPU_OK;
 }
 
 int fabgpu_csp_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen,
                                 const uint8_t* digest, size_t dlen, int* valid, int* flags, char* err, size_t errcap) {
     if (!csp || !valid) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
     ECDSAPublicKey k;
     const ECDSAPublicKey* kp = nullptr;
     if (qx32 && qy32) {
@@ -171,12 +203,18 @@ int fabgpu_csp_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, const uint
     *valid = r.valid ? 1 : 0;
     if (flags) *flags = r.needs_sw ? 1 : 0;
     put_err(err, errcap, r.err.ok() ? "" : r.err.msg);
+    if (csp->csp->Poisoned()) {                              // this call's own audit, or another thread's while it was in flight
+        *valid = 0;
+        put_err(err, errcap, GPUCSP::PoisonedText());
+        return FABGPU_EPOISONED;
+    }
     return FABGPU_OK;
 }
 
 int fabgpu_csp_identity_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, const uint8_t* msg, size_t msglen,
                                          const uint8_t* sig, size_t siglen, char* err, size_t errcap) {
     if (!csp || (msglen && !msg)) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
     ECDSAPublicKey k;
     const ECDSAPublicKey* kp = nullptr;
     if (qx32 && qy32) {
@@ -186,7 +224,12 @@ int fabgpu_csp_identity_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, c
     bool infra = false;
     std::string out = csp->csp->IdentityVerifyCoalesced(kp, msg, msglen, sig, siglen, &infra);
     put_err(err, errcap, out);
-    return infra ? FABGPU_ELAUNCH : FABGPU_OK;
+    if (infra) return FABGPU_ELAUNCH;
+    if (csp->csp->Poisoned()) {
+        put_err(err, errcap, GPUCSP::PoisonedText());
+        return FABGPU_EPOISONED;
+    }
+    return FABGPU_OK;
 }
 
 int fabgpu_csp_coalescer_configure(fabgpu_csp* csp, uint32_t window_us, uint32_t max_batch) {
@@ -205,6 +248,7 @@ int fabgpu_csp_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* qx, const 
                             const uint32_t* sig_off, const uint8_t* dig_arena, const uint32_t* dig_off, uint8_t* valid,
                             char* errs, size_t errstride) {
     if (!csp || (n && (!qx || !qy || !sig_off || !dig_off || !valid))) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
     std::vector<ECDSAPublicKey> keys(n);
     std::vector<VerifyItem> items(n);
     for (size_t i = 0; i < n; i++) {
@@ -218,13 +262,15 @@ int fabgpu_csp_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* qx, const 
         valid[i] = res[i].valid ? 1 : 0;
         if (errs && errstride) put_err(errs + i * errstride, errstride, res[i].err.ok() ? "" : res[i].err.msg);
     }
-    return FABGPU_OK;
+    // (an item whose audit failed carries PoisonedText instead of "valid"; the whole answer is then not to be used)
+    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
 }
 
 int fabgpu_csp_identity_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena,
                                      const uint32_t* msg_off, const uint8_t* sig_arena, const uint32_t* sig_off, char* errs,
                                      size_t errstride) {
     if (!csp || (n && (!qx || !qy || !msg_off || !sig_off || !errs || !errstride))) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
     std::vector<ECDSAPublicKey> keys(n);
     std::vector<IdentityItem> items(n);
     for (size_t i = 0; i < n; i++) {
@@ -235,13 +281,14 @@ int fabgpu_csp_identity_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* q
     Error e = csp->csp->IdentityVerifyBatch(items, out);
     if (!e.ok()) return FABGPU_ELAUNCH;
     for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, out[i]);
-    return FABGPU_OK;
+    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
 }
 
 int fabgpu_csp_block_preverify(fabgpu_csp* csp, const uint8_t* block, size_t len, uint32_t* n_tx, uint8_t* tx_flags, uint8_t* tx_type,
                                uint32_t cap_tx, uint32_t* n_tuples, uint32_t* tuple_tx, uint8_t* tuple_kind, uint8_t* tuple_status,
                                uint32_t cap_tuples) {
     if (!csp || !block || !n_tx || !n_tuples) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
     const bool timing = csp->csp->GetOption("pass_timing") > 0;           // stage breakdown on stderr (tools/bench_block.py --timing)
     auto t0 = std::chrono::steady_clock::now();
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -308,6 +355,7 @@ int fabgpu_csp_block_pass_abandon(fabgpu_csp* csp) { return csp ? (csp->abandon(
 int fabgpu_csp_block_preverify2(fabgpu_csp* csp, fabgpu_block_pass* ps) {
     if (!csp || !ps || !ps->block) return FABGPU_EINVAL;
     if (ps->flags & ~(uint32_t)(FABGPU_PASS_SEED_MEMO | FABGPU_PASS_NO_BLOCK_SIGS)) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
     auto t0 = std::chrono::steady_clock::now();
     const bool timing = csp->csp->GetOption("pass_timing") > 0;
     // (a memo-seeding pass keeps the block's bytes in host memory of the device context: the digest memo compares bccsp.Hash callers' bytes with them)
@@ -581,6 +629,7 @@ int fabgpu_csp_idemix_nym_verify_batch(fabgpu_csp* csp, int64_t issuer_id, size_
                                        const uint8_t* sig_arena, const uint32_t* sig_off, const uint8_t* msg_arena, const uint32_t* msg_off,
                                        uint8_t* valid, uint8_t* flags, char* errs, size_t errstride) {
     if (!csp || (n && (!nym_off || !sig_off || !msg_off || !valid || !flags || !errs || !errstride))) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
     IdemixCSP ic(csp->csp->flat_ctx());
     IdemixIssuerPublicKey ipk;
     ipk.issuer_id = issuer_id;
@@ -602,6 +651,7 @@ int fabgpu_csp_idemix_nym_verify_batch(fabgpu_csp* csp, int64_t issuer_id, size_
         valid[i] = res[i].valid ? 1 : 0;
         flags[i] = res[i].needs_sw ? 1 : 0;
         put_err(errs + i * errstride, errstride, key_ok[i] ? (res[i].err.ok() ? "" : res[i].err.msg) : import_err[i]);
+        if (valid[i]) csp->csp->NoteUnauditedNym(1);        // no host FP256BN verification: counted, so that the gap shows
     }
     return FABGPU_OK;
 }

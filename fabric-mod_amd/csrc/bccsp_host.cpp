@@ -11,6 +11,8 @@
 //   msp/identities.go:169-196    identity.Verify              -> GPUCSP::IdentityVerifyBatch
 // There is no CPU implementation of the curve arithmetic or of SHA-256 in here: every verdict comes
 // from the HIP kernels through the C ABI; without a device fabgpu_init fails and so does this layer.
+// (audit_host.cpp re-computes a sampled share of those verdicts and digests on the CPU before they are handed out - it can only
+// ever turn an answer into a miss or poison the provider, never supply a verdict of its own.)
 #include <random>
 
 #include "bccsp_host.h"
@@ -223,6 +225,7 @@ Error GPUCSP::New(const ProviderOptions& opts, std::unique_ptr<GPUCSP>& out) {
     std::unique_ptr<GPUCSP> p(new GPUCSP());
     p->opts_ = opts;
     p->opts_.devices = devices;
+    p->audit_permille_.store(opts.audit_permille > 1000 ? 1000 : opts.audit_permille, std::memory_order_relaxed);
     for (int32_t ord : devices) {
         fabgpu_cfg cfg;
         memset(&cfg, 0, sizeof(cfg));
@@ -281,6 +284,11 @@ int64_t GPUCSP::SetOption(const std::string& name, int64_t value) const {
         opts_.pass_stage_min_bytes = value;
         return prev;
     }
+    if (name == "audit_permille") {                              // (0 .. 1000; anything else is refused like an unknown name)
+        if (value < 0 || value > 1000) return INT64_MIN;
+        opts_.audit_permille = (uint32_t)value;
+        return (int64_t)audit_permille_.exchange((uint32_t)value, std::memory_order_relaxed);
+    }
     for (const OptField& o : kIntOpts)
         if (name == o.name) {
             const int64_t prev = opts_.*(o.f);
@@ -293,6 +301,7 @@ int64_t GPUCSP::GetOption(const std::string& name) const {
     std::lock_guard<std::mutex> lk(opt_mu_);
     if (name == "pass_stage_min_bytes") return opts_.pass_stage_min_bytes;
     if (name == "n_devices") return (int64_t)devs_.size();
+    if (name == "audit_permille") return (int64_t)AuditPermille();
     if (name == "registrations_dropped") return (int64_t)reg_dropped_.load(std::memory_order_relaxed);        // (read-only counters)
     if (name == "registration_id_mismatches") return (int64_t)reg_id_mismatches_.load(std::memory_order_relaxed);
     for (const OptField& o : kIntOpts)
@@ -703,6 +712,12 @@ Error GPUCSP::VerifyBatch(const std::vector<VerifyItem>& items, std::vector<Veri
         results[i].err = Error();
         if (st[i] == FABGPU_ST_HIGH_S || st[i] == FABGPU_ST_OFF_CURVE)   // cannot happen: host gate already decided
             return Error("internal inconsistency between host gate and device status");
+        // a sampled "valid" is verified again on the CPU before it leaves (rejects are re-checked by bccsp/sw on the Go side anyway)
+        if (results[i].valid && !AuditDirect(*items[i].key, items[i].sig, items[i].siglen, items[i].digest, items[i].dlen, "bccsp.Verify")) {
+            results[i] = VerifyResult();
+            results[i].err = Error(PoisonedText());
+            results[i].poisoned = true;
+        }
     }
     return Error();
 }
@@ -764,6 +779,8 @@ Error GPUCSP::IdentityVerifyBatch(const std::vector<IdentityItem>& items, std::v
         if (!submitted[i]) continue;
         bool ok = ((bits[i >> 6] >> (i & 63)) & 1) && st[i] == FABGPU_ST_VALID;
         out[i] = ok ? "" : "The signature is invalid";
+        // as in VerifyBatch; a sampled message is hashed again first
+        if (ok && !AuditDirect(*items[i].key, items[i].sig, items[i].siglen, nullptr, 0, "identity.Verify", items[i].msg, items[i].msglen)) out[i] = PoisonedText();
     }
     return Error();
 }
@@ -934,8 +951,8 @@ inline void prefetch_span(const uint8_t* p, size_t n) {
 }
 }  // namespace
 
-int GPUCSP::MemoLookup(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, uint8_t* status,
-                       const uint8_t* issuer_hash32) const {
+int GPUCSP::MemoFind(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, uint8_t* status,
+                     const uint8_t* issuer_hash32, uint64_t* seq, uint32_t* entry) const {
     if (!qx32 || !qy32 || !sig || !digest || siglen == 0 || dlen == 0 || siglen > 1024 || dlen > 1024) return 1;
     uint8_t key[1 + 32 + 64 + 8 + 2048];
     const size_t kl = MemoKeyBytes(siglen, dlen, issuer_hash32 != nullptr);
@@ -949,6 +966,8 @@ int GPUCSP::MemoLookup(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* 
     };
     auto hit = [&](const BlockMemo& bm, uint32_t e) {
         if (status) *status = bm.status_v[e - 1];
+        *seq = bm.seq;
+        *entry = e - 1;
         t_hint.gen = bm.gen;
         t_hint.entry = e - 1;
         memo_hits_.add(1);
@@ -997,7 +1016,7 @@ int GPUCSP::MemoLookup(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* 
 }
 // bccsp.Hash for bytes a pass has already hashed (bccsp_host.h).  The fingerprint (and the hint above) only choose where to look; what
 // is answered is decided by comparing the caller's bytes with the block's, every one of them.
-int GPUCSP::HashLookup(const uint8_t* msg, size_t len, uint8_t* digest32) const {
+int GPUCSP::HashFind(const uint8_t* msg, size_t len, uint8_t* digest32, uint64_t* seq, uint32_t* entry) const {
     if (!msg || !digest32 || len < walk::HASH_MEMO_MIN_LEN || len > 0x7FFFFFF0ull) return 1;
     std::shared_lock<BigReaderLock> lk(memo_mu_);
     auto usable = [](const BlockMemo& bm) { return bm.n && bm.hslots_v && bm.hspans_v && bm.copy.p; };
@@ -1023,6 +1042,8 @@ int GPUCSP::HashLookup(const uint8_t* msg, size_t len, uint8_t* digest32) const 
     auto hit = [&](const BlockMemo& bm, uint32_t e0) {
         const uint8_t* d = bm.digests_v ? bm.digests_v + 32 * (size_t)e0 : bm.keys_v + bm.key_off_v[e0 + 1] - 32;
         memcpy(digest32, d, 32);
+        *seq = bm.seq;
+        *entry = e0;
         __builtin_prefetch(bm.keys_v + bm.key_off_v[e0], 0, 3);            // (the Verify that follows compares this entry's key)
         t_hint.gen = bm.gen;
         t_hint.entry = e0;
@@ -1064,6 +1085,114 @@ int GPUCSP::HashLookup(const uint8_t* msg, size_t len, uint8_t* digest32) const 
     }
     hash_misses_.add(1);
     return 1;
+}
+// ---- CPU audit of what the lookups and the direct calls hand out; poisoning (bccsp_host.h, audit_host.h) -----------------------------
+namespace {
+struct AuditClock {                                          // time spent auditing, added to the provider's counter when the audit is over
+    std::atomic<uint64_t>& ns;
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    ~AuditClock() { ns.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(), std::memory_order_relaxed); }
+};
+std::string hex8(const uint8_t* p) {
+    static const char* H = "0123456789abcdef";
+    std::string s;
+    for (int i = 0; i < 8; i++) { s.push_back(H[p[i] >> 4]); s.push_back(H[p[i] & 15]); }
+    return s;
+}
+}  // namespace
+const char* GPUCSP::PoisonedText() { return "GPU provider poisoned: the CPU audit disagrees with the device (use bccsp/sw)"; }
+void GPUCSP::Poison(const std::string& why) const {
+    {
+        std::lock_guard<std::mutex> lk(poison_mu_);
+        if (poison_why_.empty()) poison_why_ = why.empty() ? "poisoned" : why;   // (the first reason stays)
+    }
+    if (!poisoned_.exchange(true, std::memory_order_acq_rel))
+        fprintf(stderr, "fabgpu: provider poisoned, everything is left to bccsp/sw from now on: %s\n", why.c_str());
+}
+bool GPUCSP::Poisoned(std::string* why) const {
+    if (!poisoned_.load(std::memory_order_acquire)) return false;
+    if (why) {
+        std::lock_guard<std::mutex> lk(poison_mu_);
+        *why = poison_why_;
+    }
+    return true;
+}
+void GPUCSP::AuditStats(uint64_t out[AUDIT_STATS]) const {
+    for (int i = 0; i < AUDIT_STATS; i++) out[i] = audit_count_[i].load(std::memory_order_relaxed);
+}
+void GPUCSP::NoteUnauditedNym(uint64_t n) const {
+    if (n && AuditPermille()) audit_count_[AUDIT_SKIPPED_NYM].fetch_add(n, std::memory_order_relaxed);
+}
+bool GPUCSP::AuditDirect(const ECDSAPublicKey& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
+                         const uint8_t* msg, size_t msglen) const {
+    if (!audit_sample_[AUDIT_DIRECT].hit(AuditPermille())) return true;
+    bool accept;
+    {
+        AuditClock clk{audit_count_[AUDIT_NS]};
+        uint8_t dg[32];
+        if (msg || msglen) {
+            audit_sha256(msg, msglen, dg);
+            digest = dg;
+            dlen = 32;
+        }
+        accept = audit_p256_verify(k.x, k.y, sig, siglen, digest, dlen);
+    }
+    audit_count_[AUDIT_DIRECT].fetch_add(1, std::memory_order_relaxed);
+    if (accept) return true;
+    audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
+    Poison(std::string("direct call: the device accepted a signature in ") + what + " that the CPU audit rejects (key X " + hex8(k.x) + "..)");
+    return false;
+}
+int GPUCSP::MemoLookup(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, uint8_t* status,
+                       const uint8_t* issuer_hash32) const {
+    if (poisoned_.load(std::memory_order_acquire)) return 1;
+    uint64_t seq = 0;
+    uint32_t entry = 0;
+    uint8_t st = 0xFF;
+    if (MemoFind(qx32, qy32, sig, siglen, digest, dlen, &st, issuer_hash32, &seq, &entry) != 0) return 1;
+    if (issuer_hash32) {
+        NoteUnauditedNym(1);                                                 // a pseudonym entry: no host FP256BN verification here
+    } else if (audit_sample_[AUDIT_VERDICT].hit(AuditPermille())) {
+        bool accept;
+        {
+            AuditClock clk{audit_count_[AUDIT_NS]};
+            accept = audit_p256_verify(qx32, qy32, sig, siglen, digest, dlen);
+        }
+        audit_count_[AUDIT_VERDICT].fetch_add(1, std::memory_order_relaxed);
+        if (accept != (st == FABGPU_ST_VALID)) {
+            audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
+            Poison("verdict memo: block " + std::to_string(seq) + " entry " + std::to_string(entry) + " holds status " + std::to_string(st) + ", the CPU audit says " +
+                   (accept ? "valid" : "invalid") + " (key X " + hex8(qx32) + "..)");
+            return 1;
+        }
+    }
+    if (poisoned_.load(std::memory_order_acquire)) return 1;                 // (another thread's audit failed meanwhile)
+    if (status) *status = st;
+    return 0;
+}
+int GPUCSP::HashLookup(const uint8_t* msg, size_t len, uint8_t* digest32) const {
+    if (poisoned_.load(std::memory_order_acquire)) return 1;
+    uint64_t seq = 0;
+    uint32_t entry = 0;
+    uint8_t dg[32];
+    if (!digest32 || HashFind(msg, len, dg, &seq, &entry) != 0) return 1;
+    if (audit_sample_[AUDIT_DIGEST].hit(AuditPermille())) {
+        uint8_t want[32];
+        {
+            AuditClock clk{audit_count_[AUDIT_NS]};
+            audit_sha256(msg, len, want);
+        }
+        audit_count_[AUDIT_DIGEST].fetch_add(1, std::memory_order_relaxed);
+        if (memcmp(want, dg, 32) != 0) {
+            audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
+            Poison("digest memo: block " + std::to_string(seq) + " entry " + std::to_string(entry) + " holds digest " + hex8(dg) + ".., the CPU audit computes " + hex8(want) +
+                   ".. over the same " + std::to_string(len) + " bytes");
+            return 1;
+        }
+    }
+    if (poisoned_.load(std::memory_order_acquire)) return 1;
+    memcpy(digest32, dg, 32);
+    return 0;
 }
 void GPUCSP::HashMemoStats(uint64_t* hits, uint64_t* misses, uint64_t* blocks_held, uint64_t* bytes_held, uint64_t* refused) const {
     if (hits) *hits = hash_hits_.load();
@@ -1418,13 +1547,17 @@ void GPUCSP::SeedMemo(const uint8_t* block, const ParsedBlock& pb, BlockVerdicts
                     bm->hslots_v = bm->hspans_v = nullptr;
                 }
             }
-            PublishMemo(bm);
+            if (!PublishMemo(bm)) out.memo_seeded = 0;
         }
     }
 }
-void GPUCSP::PublishMemo(const std::shared_ptr<BlockMemo>& bm) const {
+bool GPUCSP::PublishMemo(const std::shared_ptr<BlockMemo>& bm) const {
     bm->gen = g_memo_gen.fetch_add(1, std::memory_order_relaxed);     // (a recycled table is a new table to every thread's hint)
     std::unique_lock<BigReaderLock> lk(memo_mu_);
+    if (poisoned_.load(std::memory_order_acquire)) {                   // a pass that was in flight when the audit failed: it seeds nothing
+        bm->ReleaseCopy();
+        return false;
+    }
     memo_blocks_.push_back(bm);
     size_t total = 0;
     for (const auto& b : memo_blocks_) total += b->n;
@@ -1435,6 +1568,7 @@ void GPUCSP::PublishMemo(const std::shared_ptr<BlockMemo>& bm) const {
         if (memo_free_.size() < memo_free_max_) memo_free_.push_back(memo_blocks_.front());
         memo_blocks_.pop_front();
     }
+    return true;
 }
 
 // ---- the pass with the walk on the device (block_walk_dev.h) ----------------------------------------------------------------
@@ -1999,7 +2133,7 @@ int GPUCSP::PreVerifyBlockOnDevice(const uint8_t* block, size_t len, ParsedBlock
         } else {
             dev_bm->hslots_v = dev_bm->hspans_v = nullptr;
         }
-        PublishMemo(dev_bm);
+        if (!PublishMemo(dev_bm)) out.memo_seeded = 0;
         dev_bm.reset();                                                    // (published: not for the free list)
         out.ms_memo = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk_memo).count();
     }

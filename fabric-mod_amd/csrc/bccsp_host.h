@@ -26,6 +26,7 @@
 #include "block_prepass.h"
 #include "block_walk_dev.h"
 #include "coalescer.h"
+#include "audit_host.h"
 
 namespace fab {
 namespace bccsp {
@@ -74,6 +75,7 @@ struct VerifyResult {  // (valid bool, err error)
     Error err;
     bool needs_sw = false;        // tuple the GPU provider refuses to decide (off-curve key)
     bool infrastructure = false;  // device failure: caller falls back to bccsp/sw
+    bool poisoned = false;        // the CPU audit of this "valid" disagreed (or the provider was poisoned before the call): no verdict
 };
 struct IdentityItem {
     const ECDSAPublicKey* key;
@@ -136,6 +138,7 @@ struct ProviderOptions {
     int pass_hash_memo = 0;            // < 0: memo-seeding passes keep no host copy of their block and bccsp.Hash is never answered from the
                                        // digest memo (default on: HashLookup)
     uint32_t hash_memo_blocks = 0;     // per device: host copies of blocks kept at a time for the digest memo (0: 8; at most 64)
+    uint32_t audit_permille = 0;       // share of the digests / verdicts handed out that is re-computed on the CPU first (0 .. 1000; 0: none)
 };
 constexpr int kMaxProviderDevices = 64;   // contexts per provider (8 GPUs x up to 8 contexts each)
 
@@ -256,6 +259,19 @@ class GPUCSP {
     // Registers an idemix issuer on EVERY device of the pool, under one lock, so that its id is the same everywhere (ids are handed
     // out in order of registration per context); -1: not accelerated.  ipk_raw: marshalled idemix.IssuerPublicKey.
     int64_t ImportIdemixIssuer(const uint8_t* ipk_raw, size_t len, std::string* err = nullptr) const;
+    // ---- CPU audit of what the device hands out, and poisoning (audit_host.h; DESIGN.md 4.4e addendum) ----
+    // With audit_permille > 0 a fixed share of the digest-memo hits, of the verdict-memo hits for P-256 entries and of the "valid"
+    // answers of the direct calls is re-computed on the calling thread before it is returned.  The first disagreement poisons the
+    // provider: one flag for every context of the pool and every thread, never cleared.  From then on every lookup misses, every
+    // verify / identity / nym / hash / block-pass entry of the C surface answers FABGPU_EPOISONED without launching anything, and a
+    // pass already in flight finishes but publishes no memo table.  Idemix pseudonym entries are not audited (no host FP256BN
+    // verification here): they are counted in AuditStats instead.
+    enum : int { AUDIT_DIGEST = 0, AUDIT_VERDICT = 1, AUDIT_DIRECT = 2, AUDIT_MISMATCHES = 3, AUDIT_SKIPPED_NYM = 4, AUDIT_NS = 5, AUDIT_STATS = 6 };
+    void Poison(const std::string& why) const;                 // the first reason is kept
+    bool Poisoned(std::string* why = nullptr) const;
+    void AuditStats(uint64_t out[AUDIT_STATS]) const;
+    static const char* PoisonedText();                         // the error text of an item whose audit failed
+    void NoteUnauditedNym(uint64_t n) const;                   // pseudonym results handed out while auditing is on
     fabgpu_ctx* ctx() const { return devs_[0]->ctx; }          // the first context (tests, single-device callers)
     // the context a flat batch (Verify / VerifyBatch / IdentityVerifyBatch / a coalesced launch) runs on: round the ring
     fabgpu_ctx* flat_ctx() const { return devs_[flat_rr_.fetch_add(1, std::memory_order_relaxed) % devs_.size()]->ctx; }
@@ -263,6 +279,27 @@ class GPUCSP {
 
    private:
     GPUCSP() {}
+    friend struct TestAccess;                               // testhooks.cpp (libfabgpu_testhooks.so): edits a memo table to show that the audit sees it
+    // the lookups proper (shared lock inside); the public entries check the poison flag and audit a sampled hit after the lock is gone.
+    // A hit names its table and entry for the audit's report.
+    int MemoFind(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, uint8_t* status,
+                 const uint8_t* issuer_hash32, uint64_t* seq, uint32_t* entry) const;
+    int HashFind(const uint8_t* msg, size_t len, uint8_t* digest32, uint64_t* seq, uint32_t* entry) const;
+    uint32_t AuditPermille() const { return audit_permille_.load(std::memory_order_relaxed); }
+    // true: the device's "valid" for this signature stands (not sampled, or the CPU agrees); false: the provider is now poisoned.
+    // msg != nullptr: the digest is SHA-256(msg), computed here (identity.Verify)
+    bool AuditDirect(const ECDSAPublicKey& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
+                     const uint8_t* msg = nullptr, size_t msglen = 0) const;
+    // Every lookup of every validator thread READS the two switches and, while auditing is on, BUMPS its kind's hit counter: the
+    // switches share a cache line nobody writes, each counter has a line of its own (the memo's counters are sharded for the same
+    // reason - reader_lock.h - but a sampling rule that is exact over all threads needs ONE counter per kind).
+    alignas(64) mutable std::atomic<uint32_t> audit_permille_{0};
+    mutable std::atomic<bool> poisoned_{false};
+    struct alignas(64) HitCounter : AuditSampler {};
+    mutable HitCounter audit_sample_[3];                    // one hit counter per audited kind (AUDIT_DIGEST / _VERDICT / _DIRECT)
+    alignas(64) mutable std::atomic<uint64_t> audit_count_[AUDIT_STATS] = {};   // (written by audits only)
+    alignas(64) mutable std::mutex poison_mu_;
+    mutable std::string poison_why_;
     // One device context of the pool and the provider's per-device state: the device's copy of the identity cache and its version.
     struct Dev {
         fabgpu_ctx* ctx = nullptr;
@@ -376,7 +413,7 @@ class GPUCSP {
         fabgpu_ctx* pin_ctx = nullptr;
         ~BlockMemo();
     };
-    void PublishMemo(const std::shared_ptr<BlockMemo>& bm) const;   // push under the lock, oldest blocks out while over capacity
+    bool PublishMemo(const std::shared_ptr<BlockMemo>& bm) const;   // push under the lock, oldest blocks out while over capacity; false: poisoned, nothing published
     mutable std::vector<std::shared_ptr<BlockMemo>> memo_free_;    // evicted tables, recycled: 7 MB of fresh pages per block otherwise
     mutable size_t memo_free_max_ = 4, scratch_free_max_ = 4;      // (both grow with the pool and with ProviderOptions::concurrent_passes)
     mutable BigReaderLock memo_mu_;                       // readers (every bccsp.Verify of every validator thread) share no cache line: reader_lock.h

@@ -357,6 +357,7 @@ const char* fabgpu_strerror(int code) {
         case FABGPU_ENOMEM: return "host or device allocation failed";
         case FABGPU_ELAUNCH: return "HIP launch/copy/execution failure";
         case FABGPU_ETOOBIG: return "batch or arena exceeds 32-bit offsets";
+        case FABGPU_EPOISONED: return "provider poisoned: a CPU audit disagreed with the device; fall back to bccsp/sw";
         default: return "unknown fabgpu error";
     }
 }

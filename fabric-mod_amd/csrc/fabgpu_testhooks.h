@@ -57,6 +57,16 @@ int fabgpu_csp_idfix_probe(fabgpu_csp* csp, uint32_t n, const uint8_t* arena, si
 /* TEST HOOK (device): the same gate in the wavefront form the kernels run, over n signatures = arena[spans[2i], spans[2i+1]) */
 int fabgpu_csp_gate_probe(fabgpu_csp* csp, uint32_t n, const uint8_t* arena, size_t arena_len, const uint32_t* spans, uint8_t* code, uint8_t* r, uint8_t* s);
 uint64_t fabgpu_identity_table_hash(const uint8_t* p, size_t len);
+/* TEST HOOKS (pure host): the provider's CPU audit (audit_host.h): its SHA-256; its bccsp.Verify over a P-256 key, a DER signature and a
+ * digest of any length (1 accept, 0 reject); its sampling rule over n_hits simulated hits of one counter (audited[h - 1] = 1 where hit
+ * h is audited; returns the number of audited hits) */
+void fabgpu_test_audit_sha256(const uint8_t* msg, size_t len, uint8_t* out32);
+int fabgpu_test_audit_p256_verify(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig_der, size_t siglen, const uint8_t* digest, size_t dlen);
+long long fabgpu_test_audit_sample(uint32_t permille, uint32_t n_hits, uint8_t* audited);
+/* TEST HOOK: corrupts one entry of the memo table published under block_seq - host memory of the library, nothing is launched.  kind 0
+ * flips one bit of the index-th stored digest, kind 1 toggles the index-th stored status between valid and bad-signature.
+ * 0 done, 1 nothing to corrupt (no such table, no digest memo, a status that is neither), FABGPU_EINVAL. */
+int fabgpu_csp_test_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, int kind, uint32_t index);
 
 
 #ifdef __cplusplus

@@ -16,6 +16,36 @@
 
 using namespace fab::bccsp;
 
+// the provider's friend (bccsp_host.h): edits one entry of a published memo table in place - host memory of the library, nothing is launched
+namespace fab {
+namespace bccsp {
+struct TestAccess {
+    static int memo_corrupt(const GPUCSP& c, uint64_t block_seq, int kind, uint32_t index) {
+        std::unique_lock<BigReaderLock> lk(c.memo_mu_);
+        for (const auto& b : c.memo_blocks_) {
+            GPUCSP::BlockMemo& bm = *b;
+            if (bm.seq != block_seq || !bm.n) continue;
+            if (index >= bm.n_entries) return FABGPU_EINVAL;
+            if (kind == 0) {
+                if (!bm.hslots_v || !bm.hspans_v || !bm.copy.p) return 1;                        // the block has no digest memo
+                const uint8_t* d = bm.digests_v ? bm.digests_v + 32 * (size_t)index : bm.keys_v + bm.key_off_v[index + 1] - 32;
+                const_cast<uint8_t*>(d)[0] ^= 0x01;
+                return FABGPU_OK;
+            }
+            if (kind == 1) {
+                uint8_t* st = const_cast<uint8_t*>(bm.status_v) + index;
+                if (*st != FABGPU_ST_VALID && *st != FABGPU_ST_BAD_MATH) return 1;              // neither valid nor bad-signature: left alone
+                *st = *st == FABGPU_ST_VALID ? FABGPU_ST_BAD_MATH : FABGPU_ST_VALID;
+                return FABGPU_OK;
+            }
+            return FABGPU_EINVAL;
+        }
+        return 1;                                                                                // no table under that block_seq
+    }
+};
+}  // namespace bccsp
+}  // namespace fab
+
 namespace {
 void put_err(char* dst, size_t cap, const std::string& s) {
     if (!dst || cap == 0) return;
@@ -246,6 +276,30 @@ int fabgpu_csp_gate_probe(fabgpu_csp* csp, uint32_t n, const uint8_t* arena, siz
 }
 // TEST HOOK (pure host): the table hash of identity bytes (block_walk_core.h id_hash_host)
 uint64_t fabgpu_identity_table_hash(const uint8_t* p, size_t len) { return walk::id_hash_host(p, (uint32_t)len); }
+
+// TEST HOOKS (pure host): the provider's CPU audit (audit_host.h) - its SHA-256, its bccsp.Verify (1 accept, 0 reject), and its
+// sampling rule run over n_hits simulated hits of one counter (audited[h - 1] = 1 where hit h is audited; returns how many are)
+void fabgpu_test_audit_sha256(const uint8_t* msg, size_t len, uint8_t* out32) { audit_sha256(msg, len, out32); }
+int fabgpu_test_audit_p256_verify(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig_der, size_t siglen, const uint8_t* digest, size_t dlen) {
+    return audit_p256_verify(qx32, qy32, sig_der, siglen, digest, dlen) ? 1 : 0;
+}
+long long fabgpu_test_audit_sample(uint32_t permille, uint32_t n_hits, uint8_t* audited) {
+    AuditSampler s;
+    long long n = 0;
+    for (uint32_t h = 0; h < n_hits; h++) {
+        const bool a = s.hit(permille);
+        if (audited) audited[h] = a ? 1 : 0;
+        n += a ? 1 : 0;
+    }
+    return n;
+}
+// TEST HOOK: corrupts one entry of the memo table published under block_seq, in the library's host memory (nothing is launched):
+// kind 0 flips one bit of the index-th stored digest (what fabgpu_csp_hash_lookup hands out), kind 1 toggles the index-th stored status
+// between valid and bad-signature (what fabgpu_csp_memo_lookup hands out).  0 done, 1 nothing to corrupt there, FABGPU_EINVAL.
+int fabgpu_csp_test_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, int kind, uint32_t index) {
+    if (!csp) return FABGPU_EINVAL;
+    return TestAccess::memo_corrupt(*csp->csp, block_seq, kind, index);
+}
 
 
 }  // extern "C"

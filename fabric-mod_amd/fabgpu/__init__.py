@@ -26,6 +26,7 @@ _LIB_PATH = os.environ.get("FABGPU_LIB_PATH") or os.path.join(os.path.dirname(_H
 
 FABGPU_OK = 0
 FABGPU_EINVAL = -1
+FABGPU_EPOISONED = -6    # fabgpu.h: the provider's CPU audit disagreed with the device once; it serves nothing any more
 FLAG_ONE_LANE_ONLY = 1   # fabgpu.h FABGPU_FLAG_ONE_LANE_ONLY
 FLAG_TIME_KERNELS = 2    # fabgpu.h FABGPU_FLAG_TIME_KERNELS
 FLAG_NYM_NO_SIDE_STREAM = 128  # fabgpu.h FABGPU_FLAG_NYM_NO_SIDE_STREAM (idemix four-lane form: fixed-base terms inside the commitment kernel)
@@ -47,6 +48,11 @@ _sz = ctypes.c_size_t
 
 class FabgpuError(RuntimeError):
     """Infrastructure failure (non-zero FABGPU_E*): the Go provider would fall back to bccsp/sw."""
+
+
+class PoisonedError(FabgpuError):
+    """FABGPU_EPOISONED: a CPU audit of this provider disagreed with the device (or poison() was called); every later call is refused
+    and the Go provider serves everything from bccsp/sw."""
 
 
 class BCCSPError(Exception):
@@ -88,6 +94,12 @@ class _CspOpts(ctypes.Structure):
                 ("hash_memo_blocks", ctypes.c_uint32)]
 
 
+class _CspOptsAudit(ctypes.Structure):
+    """fabgpu_csp_opts with the field appended for the CPU audit: audit_permille lies in what used to be the struct's tail padding, so
+    the size is _CspOpts's (what GPUCSP hands to fabgpu_csp_new2)."""
+    _fields_ = _CspOpts._fields_ + [("audit_permille", ctypes.c_uint32)]
+
+
 class _Cfg(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("max_batch", ctypes.c_uint32), ("max_arena", ctypes.c_uint32),
                 ("flags", ctypes.c_uint32)]
@@ -118,6 +130,7 @@ ABI_SYMBOLS = [
     "fabgpu_p256_key_register_many", "fabgpu_csp_new2", "fabgpu_csp_device_count", "fabgpu_csp_ctx_of", "fabgpu_csp_passes_per_device",
     "fabgpu_csp_route_block", "fabgpu_csp_set_option", "fabgpu_csp_get_option",
     "fabgpu_csp_hash_lookup", "fabgpu_csp_hash_memo_stats",
+    "fabgpu_csp_poison", "fabgpu_csp_poisoned", "fabgpu_csp_audit_stats",
 ]
 
 # what libfabgpu_testhooks.so exports (fabric-mod_amd/csrc/fabgpu_testhooks.h): probes, walker comparisons, the synthetic block generator, the
@@ -126,6 +139,7 @@ HOOK_SYMBOLS = [
     "fabgpu_synth_batch", "fabgpu_last_kernel_ms", "fabgpu_csp_block_walk_compare", "fabgpu_block_walk_twopass_compare", "fabgpu_gate_sig_fast",
     "fabgpu_gate_sig_any", "fabgpu_csp_idfix_probe", "fabgpu_csp_gate_probe", "fabgpu_identity_table_hash", "fabgpu_test_nym_side_after",
     "fabgpu_test_key_table", "fabgpu_test_key_table_host", "fabgpu_test_gtab_compare_with_host", "fabgpu_test_key_tables16",
+    "fabgpu_test_audit_sha256", "fabgpu_test_audit_p256_verify", "fabgpu_test_audit_sample", "fabgpu_csp_test_memo_corrupt",
 ]
 _HOOKS_PATH = os.path.join(os.path.dirname(_LIB_PATH), "libfabgpu_testhooks.so")
 
@@ -165,6 +179,12 @@ def load_hooks():
     H.fabgpu_identity_table_hash.argtypes = [ctypes.c_char_p, _sz]
     H.fabgpu_identity_table_hash.restype = ctypes.c_uint64
     H.fabgpu_synth_batch.argtypes = [_sz, ctypes.c_uint64, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_int]
+    H.fabgpu_test_audit_sha256.argtypes = [ctypes.c_char_p, _sz, ctypes.c_char_p]
+    H.fabgpu_test_audit_sha256.restype = None
+    H.fabgpu_test_audit_p256_verify.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz]
+    H.fabgpu_test_audit_sample.argtypes = [ctypes.c_uint32, ctypes.c_uint32, _u8p]
+    H.fabgpu_test_audit_sample.restype = ctypes.c_longlong
+    H.fabgpu_csp_test_memo_corrupt.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32]
     _hooks = H
     return H
 
@@ -214,7 +234,7 @@ def load():
     L.fabgpu_hash_to_int.argtypes = [ctypes.c_char_p, _sz, ctypes.c_char_p]
     L.fabgpu_hash_to_int.restype = None
     L.fabgpu_csp_new.argtypes = [ctypes.POINTER(_Cfg), ctypes.POINTER(_vp), ctypes.c_char_p, _sz]
-    L.fabgpu_csp_new2.argtypes = [ctypes.POINTER(_CspOpts), ctypes.POINTER(_vp), ctypes.c_char_p, _sz]
+    L.fabgpu_csp_new2.argtypes = [ctypes.POINTER(_CspOptsAudit), ctypes.POINTER(_vp), ctypes.c_char_p, _sz]
     L.fabgpu_csp_device_count.argtypes = [_vp]
     L.fabgpu_csp_ctx_of.argtypes = [_vp, ctypes.c_int]
     L.fabgpu_csp_ctx_of.restype = _vp
@@ -253,6 +273,9 @@ def load():
     L.fabgpu_csp_memo_set_capacity.argtypes = [_vp, ctypes.c_uint64]
     L.fabgpu_csp_hash_lookup.argtypes = [_vp, ctypes.c_char_p, _sz, ctypes.c_char_p]
     L.fabgpu_csp_hash_memo_stats.argtypes = [_vp, _u64p, _u64p, _u64p, _u64p, _u64p]
+    L.fabgpu_csp_poison.argtypes = [_vp, ctypes.c_char_p]
+    L.fabgpu_csp_poisoned.argtypes = [_vp, ctypes.c_char_p, _sz]
+    L.fabgpu_csp_audit_stats.argtypes = [_vp, _u64p, ctypes.c_int]
     L.fabgpu_csp_identity_cache_limits.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
     L.fabgpu_csp_identity_cache_size.argtypes = [_vp, _u64p]
     L.fabgpu_csp_pass_routes.argtypes = [_vp, _u64p, _u64p, ctypes.c_char_p, _sz]
@@ -279,6 +302,8 @@ def strerror(code: int) -> str:
 
 
 def _check(rc: int, what: str):
+    if rc == FABGPU_EPOISONED:
+        raise PoisonedError("%s refused: %s (%d)" % (what, strerror(rc), rc))
     if rc != FABGPU_OK:
         raise FabgpuError("%s failed: %s (%d)" % (what, strerror(rc), rc))
 
@@ -683,7 +708,8 @@ class GPUCSP:
         """device: ONE context on that HIP ordinal (fabgpu_csp_new).  devices: one context per entry - an ordinal may repeat; an empty
         list means every visible device - behind ONE provider (fabgpu_csp_new2: what bccsp/factory builds from the `GPU:` section).
         switches: pass_device_walk / pass_stage_min_bytes / pass_device_memo / pass_host_counts / pass_timing / pass_hash_memo (0 default,
-        > 0 on, < 0 off), hash_memo_blocks (host copies of blocks the digest memo keeps per device)."""
+        > 0 on, < 0 off), hash_memo_blocks (host copies of blocks the digest memo keeps per device), audit_permille (0 .. 1000: the share
+        of digests / verdicts handed out that is re-computed on the CPU first; 0, the default: none - poison / poisoned / audit_stats)."""
         L = load()
         h = _vp()
         err = ctypes.create_string_buffer(512)
@@ -693,8 +719,8 @@ class GPUCSP:
         else:
             devs = [device] if devices is None else list(devices)
             arr = (ctypes.c_int32 * max(1, len(devs)))(*devs)
-            o = _CspOpts()
-            o.size, o.n_devices, o.devices = ctypes.sizeof(_CspOpts), len(devs), arr
+            o = _CspOptsAudit()
+            o.size, o.n_devices, o.devices = ctypes.sizeof(_CspOptsAudit), len(devs), arr
             o.ctx_flags, o.concurrent_passes, o.expect_block_bytes, o.expect_tuples = flags, concurrent_passes, expect_block_bytes, expect_tuples
             for k, v in switches.items():
                 if not hasattr(o, k):
@@ -730,6 +756,26 @@ class GPUCSP:
         v = ctypes.c_int64(0)
         _check(self._L.fabgpu_csp_get_option(self._h, name.encode(), ctypes.byref(v)), "fabgpu_csp_get_option(%s)" % name)
         return int(v.value)
+
+    def poison(self, why: str = "") -> None:
+        """Retires the provider for good (what a failed CPU audit does): lookups miss, every other call raises PoisonedError."""
+        _check(self._L.fabgpu_csp_poison(self._h, why.encode()), "fabgpu_csp_poison")
+
+    def poisoned(self) -> Optional[str]:
+        """None, or the FIRST reason the provider was poisoned for."""
+        why = ctypes.create_string_buffer(512)
+        rc = self._L.fabgpu_csp_poisoned(self._h, why, 512)
+        if rc < 0:
+            raise FabgpuError("fabgpu_csp_poisoned: %s" % strerror(rc))
+        return (why.value.decode() or "poisoned") if rc else None
+
+    def audit_stats(self) -> dict:
+        """Counters of the CPU audit (audit_permille): audits per kind, mismatches, pseudonym results handed out unaudited, time spent."""
+        v = (ctypes.c_uint64 * 6)()
+        n = self._L.fabgpu_csp_audit_stats(self._h, v, 6)
+        if n != 6:
+            raise FabgpuError("fabgpu_csp_audit_stats: %s" % strerror(n))
+        return dict(zip(("digest_audits", "verdict_audits", "direct_audits", "mismatches", "skipped_nym", "audit_ns"), (int(x) for x in v)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1094,6 +1140,35 @@ def identity_table_hash(b: bytes) -> int:
 
 PASS_SEED_MEMO, PASS_NO_BLOCK_SIGS = 1, 2
 TUPLE_ST_SKIPPED = 8
+
+
+def audit_sha256(msg: bytes) -> bytes:
+    """TEST HOOK (pure host): the SHA-256 of the provider's CPU audit."""
+    out = ctypes.create_string_buffer(32)
+    load_hooks().fabgpu_test_audit_sha256(msg, len(msg), out)
+    return out.raw
+
+
+def audit_p256_verify(qx32: bytes, qy32: bytes, sig: bytes, digest: bytes) -> bool:
+    """TEST HOOK (pure host): bccsp.Verify(k, sig, digest) as the provider's CPU audit decides it - True only for (true, nil)."""
+    return bool(load_hooks().fabgpu_test_audit_p256_verify(qx32, qy32, sig, len(sig), digest, len(digest)))
+
+
+def audit_sample(permille: int, n_hits: int) -> np.ndarray:
+    """TEST HOOK (pure host): which of n_hits consecutive hits of one counter the audit samples (bool per hit, hit 1 first)."""
+    a = np.zeros(max(1, n_hits), np.uint8)
+    n = load_hooks().fabgpu_test_audit_sample(permille, n_hits, _p8(a))
+    assert n == int(a[:n_hits].sum())
+    return a[:n_hits].astype(bool)
+
+
+def memo_corrupt(csp: "GPUCSP", block_seq: int, kind: int, index: int) -> int:
+    """TEST HOOK: corrupts entry `index` of the memo table under block_seq in host memory - kind 0 one bit of its stored digest, kind 1
+    its stored status (valid <-> bad signature).  0 done, 1 nothing to corrupt there."""
+    rc = load_hooks().fabgpu_csp_test_memo_corrupt(csp._h, block_seq, kind, index)
+    if rc < 0:
+        raise FabgpuError("fabgpu_csp_test_memo_corrupt: %s" % strerror(rc))
+    return rc
 
 
 def preverify_block2(csp: "GPUCSP", block: bytes, block_seq: int = 0, seed_memo: bool = False, block_sigs: bool = True, lean: bool = False):

@@ -60,7 +60,15 @@ type GPUOpts struct {
 	// (fabgpu_csp_verify_coalesced).  For the orderer (General.BCCSP in orderer.yaml): its Broadcast handlers reach
 	// identity.Verify one message per goroutine behind SigFilter and no block pass precedes them.  Leave it off on peers.
 	CoalesceVerify bool `mapstructure:"coalesceverify" json:"coalesceverify" yaml:"CoalesceVerify"`
+	// AuditPermille: the share (0 .. 1000) of the digests and verdicts the provider is about to hand out from the device that it
+	// re-computes on the CPU first; the first disagreement poisons the provider for good and everything is served by bccsp/sw from then
+	// on (gpu.go Provider.Poisoned; metrics fabgpu_audit_mismatches, fabgpu_poisoned).  Unset means 1 - one hit in a thousand, about
+	// thirty verdicts and thirty digests of a 10 000-transaction block; `AuditPermille: 0` switches the audit off, 1000 audits everything.
+	AuditPermille *int `mapstructure:"auditpermille" json:"auditpermille,omitempty" yaml:"AuditPermille,omitempty"`
 }
+
+// DefaultAuditPermille is what GPUOpts.AuditPermille means when the `GPU:` section does not set it.
+const DefaultAuditPermille = 1
 
 // GPUFactory is the factory of the GPU-accelerated BCCSP.
 type GPUFactory struct{}
@@ -81,7 +89,7 @@ func (f *GPUFactory) Get(config *FactoryOpts) (bccsp.BCCSP, error) {
 	if err != nil {
 		return nil, errors.Wrapf(err, "Failed initializing the software BCCSP behind the GPU provider")
 	}
-	var opts gpu.Options
+	opts := gpu.Options{AuditPermille: DefaultAuditPermille}
 	if g := config.GPUOpts; g != nil {
 		if g.Device != nil {
 			if len(g.Devices) == 0 {
@@ -92,7 +100,13 @@ func (f *GPUFactory) Get(config *FactoryOpts) (bccsp.BCCSP, error) {
 		}
 		opts = gpu.Options{Devices: g.Devices, ConcurrentPasses: g.ConcurrentPasses, ExpectBlockBytes: g.ExpectBlockBytes,
 			ExpectTuples: g.ExpectTuples, MemoBlocks: g.MemoBlocks, HostWalk: g.HostWalk, PassTiming: g.PassTiming,
-			NoHashMemo: g.NoHashMemo, HashMemoBlocks: g.HashMemoBlocks, KeyTables16: g.KeyTables16}
+			NoHashMemo: g.NoHashMemo, HashMemoBlocks: g.HashMemoBlocks, KeyTables16: g.KeyTables16, AuditPermille: DefaultAuditPermille}
+		if g.AuditPermille != nil {
+			if *g.AuditPermille < 0 || *g.AuditPermille > 1000 {
+				return nil, errors.Errorf("Invalid GPU opts: AuditPermille [%d] must be 0 .. 1000", *g.AuditPermille)
+			}
+			opts.AuditPermille = *g.AuditPermille
+		}
 	}
 	csp, err := gpu.New(swCSP, opts)
 	if err != nil {

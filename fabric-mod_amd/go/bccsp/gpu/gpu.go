@@ -93,6 +93,12 @@ type Provider struct {
 	coalesce bool
 	// noHashMemo: Options.NoHashMemo - Hash goes straight to bccsp/sw
 	noHashMemo bool
+	// poisoned (atomic, 0 / 1): the library's CPU audit disagreed with the device once (Options.AuditPermille; fabgpu_bccsp.h "CPU
+	// audit") and the library answers FABGPU_EPOISONED / misses for good.  Set when a call returns FABGPU_EPOISONED or the metrics
+	// refresher sees the flag; from then on no call crosses cgo any more: Hash, Verify and everything else is the embedded bccsp/sw's,
+	// PreVerifyBlock returns an error (validation proceeds on bccsp/sw) and HasBlock answers false.  Never cleared: the peer is
+	// restarted after whoever runs it has looked at the reason (PoisonedReason; the library also prints it to stderr).
+	poisoned uint32
 	// room for per-transaction flags, remembered from block to block (atomic max): the library answers FABGPU_ETOOBIG - nothing was
 	// launched, the upload has been waited for (the library never reads the block after a call returned) and is kept for the retry,
 	// which finds it again - only when a block outgrows every block before it
@@ -125,6 +131,11 @@ type Options struct {
 	KeyTables16      bool  // FABGPU_FLAG_KEY_TABLES_16BIT: every imported key also gets a 16-bit comb table on the device (80 MiB each, the first 64 keys)
 	HostWalk         bool  // keep the envelope walk on the host (A/B runs)
 	PassTiming       bool  // stage breakdown of every pass on stderr
+	// AuditPermille (0 .. 1000): the library re-computes this share of the digests and verdicts it is about to hand out from the device
+	// on the CPU first - digest-memo hits, verdict-memo hits of P-256 entries, "valid" answers of the coalesced Verify - and poisons
+	// the provider at the first disagreement (hit h of a kind is audited iff h*permille/1000 != (h-1)*permille/1000: no randomness).
+	// GPUFactory passes 1 unless the operator says otherwise; 0 switches the audit off.  Idemix pseudonym entries are not audited.
+	AuditPermille int
 }
 
 // SetCoalesce switches the coalesced device path for memo misses on or off (GPUOpts.CoalesceVerify in gpufactory.go).
@@ -233,6 +244,10 @@ func New(swCSP bccsp.BCCSP, opts Options) (bccsp.BCCSP, error) {
 		keep = 64
 	}
 	o.hash_memo_blocks = C.uint32_t(keep)
+	if opts.AuditPermille < 0 || opts.AuditPermille > 1000 {
+		return nil, errors.Errorf("Invalid GPU opts: AuditPermille [%d] must be 0 .. 1000", opts.AuditPermille)
+	}
+	o.audit_permille = C.uint32_t(opts.AuditPermille)
 	var csp *C.fabgpu_csp
 	errbuf := make([]byte, 256)
 	if rc := C.fabgpu_csp_new2(&o, &csp, (*C.char)(unsafe.Pointer(&errbuf[0])), C.size_t(len(errbuf))); rc != 0 {
@@ -287,6 +302,51 @@ func (p *Provider) Close() {
 		}
 		C.fabgpu_csp_free(p.csp)
 	})
+}
+
+// Poisoned: the library's CPU audit found the device disagreeing with the CPU (or the library was poisoned by hand) and this provider
+// serves everything from the embedded bccsp/sw from now on.
+func (p *Provider) Poisoned() bool {
+	if atomic.LoadUint32(&p.poisoned) != 0 {
+		return true
+	}
+	if C.fabgpu_csp_poisoned(p.csp, nil, 0) == 1 {
+		p.markPoisoned()
+		return true
+	}
+	return false
+}
+
+// PoisonedReason: the first reason the library was poisoned for ("" while it is not).
+func (p *Provider) PoisonedReason() string {
+	why := make([]byte, 512)
+	if C.fabgpu_csp_poisoned(p.csp, (*C.char)(unsafe.Pointer(&why[0])), C.size_t(len(why))) != 1 {
+		return ""
+	}
+	n := 0
+	for n < len(why) && why[n] != 0 {
+		n++
+	}
+	return string(why[:n])
+}
+
+// markPoisoned is the switch to bccsp/sw: after it no method of the provider calls into the library's lookups, verifies or passes.
+func (p *Provider) markPoisoned() {
+	if atomic.CompareAndSwapUint32(&p.poisoned, 0, 1) {
+		if m := p.metrics(); m != nil {
+			m.poisoned.Set(1)
+		}
+	}
+}
+
+// AuditStats: what the library's CPU audit has done - audits of digest-memo hits, of verdict-memo hits and of direct calls, mismatches
+// (the first one poisons), pseudonym results handed out unaudited, and the time the audits took on the calling goroutines' threads.
+func (p *Provider) AuditStats() (digest, verdict, direct, mismatches, skippedNym uint64, spent time.Duration) {
+	var v [6]C.uint64_t
+	if C.fabgpu_csp_audit_stats(p.csp, &v[0], 6) != 6 {
+		return
+	}
+	return uint64(v[0]), uint64(v[1]), uint64(v[2]), uint64(v[3]), uint64(v[4]), time.Duration(v[5])
 }
 
 // be32 is big.Int.FillBytes for Go 1.14: the value as exactly 32 big-endian bytes (callers guarantee BitLen <= 256).
@@ -348,7 +408,7 @@ func (p *Provider) xyOf(k bccsp.Key) (xy [64]byte, ok bool) {
 // launch costs more than one CPU verification.  With SetCoalesce(true) a miss joins whatever other misses are in flight
 // (fabgpu_csp_verify_coalesced): the orderer's case.
 func (p *Provider) Verify(k bccsp.Key, signature, digest []byte, opts bccsp.SignerOpts) (bool, error) {
-	if len(signature) != 0 && len(digest) != 0 {
+	if len(signature) != 0 && len(digest) != 0 && atomic.LoadUint32(&p.poisoned) == 0 {
 		if xy, ok := p.xyOf(k); ok {
 			var st C.uint8_t
 			hit := C.fabgpu_csp_memo_lookup(p.csp, (*C.uint8_t)(unsafe.Pointer(&xy[0])), (*C.uint8_t)(unsafe.Pointer(&xy[32])),
@@ -367,6 +427,9 @@ func (p *Provider) Verify(k bccsp.Key, signature, digest []byte, opts bccsp.Sign
 					(*C.uint8_t)(unsafe.Pointer(&digest[0])), C.size_t(len(digest)), &valid, &flags, &errbuf[0], C.size_t(len(errbuf)))
 				if rc == 0 && valid == 1 && errbuf[0] == 0 {
 					return true, nil
+				}
+				if rc == C.FABGPU_EPOISONED { // this call's audit failed, or an earlier one: bccsp/sw below, and from now on
+					p.markPoisoned()
 				}
 			}
 		}
@@ -391,7 +454,7 @@ const hashMemoMinLen = 64
 // Before round 6 Hash always went to bccsp/sw: the validators then re-hashed on the CPU every byte the device had just hashed (100 MB
 // per 10 000-transaction block), which was three to four times the cost of the GPU pass itself.
 func (p *Provider) Hash(msg []byte, opts bccsp.HashOpts) ([]byte, error) {
-	if _, isSHA256 := opts.(*bccsp.SHA256Opts); isSHA256 && len(msg) >= hashMemoMinLen && !p.noHashMemo {
+	if _, isSHA256 := opts.(*bccsp.SHA256Opts); isSHA256 && len(msg) >= hashMemoMinLen && !p.noHashMemo && atomic.LoadUint32(&p.poisoned) == 0 {
 		digest := make([]byte, 32)
 		if C.fabgpu_csp_hash_lookup(p.csp, (*C.uint8_t)(unsafe.Pointer(&msg[0])), C.size_t(len(msg)), (*C.uint8_t)(unsafe.Pointer(&digest[0]))) == 0 {
 			return digest, nil
@@ -412,6 +475,9 @@ func (p *Provider) HashMemoStats() (hits, misses, blocksHeld, bytesHeld, refused
 func (p *Provider) PreVerifyBlock(blockBytes []byte, blockSeq uint64) (*PassSummary, error) {
 	if len(blockBytes) == 0 {
 		return nil, errors.New("empty block")
+	}
+	if atomic.LoadUint32(&p.poisoned) != 0 {
+		return nil, errors.New("fabgpu: provider poisoned by its CPU audit, validation runs on bccsp/sw")
 	}
 	// one pass per block name at a time: whoever comes second (the validator wrapper while the arrival hook's pass is still
 	// running, a gossiped duplicate) waits for the first and finds the memo seeded
@@ -449,6 +515,9 @@ func (p *Provider) PreVerifyBlock(blockBytes []byte, blockSeq uint64) (*PassSumm
 			}
 			continue
 		}
+		if rc == C.FABGPU_EPOISONED {
+			p.markPoisoned()
+		}
 		if rc != 0 {
 			p.metrics().passFailed()
 			return nil, errors.Errorf("fabgpu: %s", C.GoString(C.fabgpu_strerror(rc)))
@@ -469,7 +538,7 @@ func (p *Provider) EvictBlock(blockSeq uint64) {
 // MemoLookup exposes the verdict memo to the other verifier of this delivery (bccsp/idemixgpu: pseudonym signatures are memoised
 // under key = Nym.x || Nym.y, digest = SHA-256(message)).  hit == false: ask the software verifier.
 func (p *Provider) MemoLookup(qx, qy *[32]byte, signature, digest []byte) (status uint8, hit bool) {
-	if len(signature) == 0 || len(digest) == 0 {
+	if len(signature) == 0 || len(digest) == 0 || atomic.LoadUint32(&p.poisoned) != 0 {
 		return 0, false
 	}
 	var st C.uint8_t
@@ -482,7 +551,7 @@ func (p *Provider) MemoLookup(qx, qy *[32]byte, signature, digest []byte) (statu
 // (issuerHash = idemix.IssuerPublicKey.Hash of bccsp.IdemixNymSignerOpts.IssuerPK) - two channels may define one idemix MSP id with
 // different issuer keys, and provider and memo are shared by all channels.
 func (p *Provider) MemoLookupNym(issuerHash, nymX, nymY *[32]byte, signature, digest []byte) (status uint8, hit bool) {
-	if len(signature) == 0 || len(digest) == 0 {
+	if len(signature) == 0 || len(digest) == 0 || atomic.LoadUint32(&p.poisoned) != 0 {
 		return 0, false
 	}
 	var st C.uint8_t
@@ -497,6 +566,9 @@ func (p *Provider) MemoLookupNym(issuerHash, nymX, nymY *[32]byte, signature, di
 func (p *Provider) HasBlock(blockSeq uint64) bool {
 	if running, ok := p.inflight.Load(blockSeq); ok {
 		<-running.(chan struct{}) // a pass under this name is in flight: its verdicts are a few hundred microseconds away
+	}
+	if atomic.LoadUint32(&p.poisoned) != 0 {
+		return false
 	}
 	var n C.uint64_t
 	return C.fabgpu_csp_memo_has_block(p.csp, C.uint64_t(blockSeq), &n) == 0 && n > 0
@@ -571,12 +643,22 @@ var (
 		Help: "Verdict memo: entries held, bccsp.Verify lookups answered (hits), lookups left to bccsp/sw (misses), entries evicted; digest memo: bccsp.Hash calls answered (hash_hits) / left to bccsp/sw (hash_misses), block copies held, copies refused",
 		LabelNames: []string{"what"}, StatsdFormat: "%{#fqname}.%{what}",
 	}
+	auditMismatchOpts = metrics.CounterOpts{
+		Namespace: "fabgpu", Name: "audit_mismatches",
+		Help: "Results of the device that the provider's sampled CPU audit re-computed and found different (the first one poisons the provider)",
+	}
+	poisonedOpts = metrics.GaugeOpts{
+		Namespace: "fabgpu", Name: "poisoned",
+		Help: "1 once the GPU provider has retired itself after a CPU audit mismatch and serves everything from bccsp/sw, else 0",
+	}
 )
 
 type passMetrics struct {
 	duration         metrics.Histogram
 	tx, sigs, failed metrics.Counter
 	routes, memo     metrics.Gauge
+	auditMismatches  metrics.Counter
+	poisoned         metrics.Gauge
 }
 
 func (m *passMetrics) passDone(d time.Duration, nTx, nSig, seeded int) {
@@ -605,7 +687,9 @@ func (p *Provider) RegisterMetrics(mp metrics.Provider, refresh time.Duration) {
 		m := &passMetrics{
 			duration: mp.NewHistogram(passDurationOpts), tx: mp.NewCounter(passTxOpts), sigs: mp.NewCounter(passSigOpts),
 			failed: mp.NewCounter(passFailedOpts), routes: mp.NewGauge(passRouteOpts), memo: mp.NewGauge(memoOpts),
+			auditMismatches: mp.NewCounter(auditMismatchOpts), poisoned: mp.NewGauge(poisonedOpts),
 		}
+		m.poisoned.Set(0)
 		if refresh <= 0 {
 			refresh = 5 * time.Second
 		}
@@ -616,6 +700,7 @@ func (p *Provider) RegisterMetrics(mp metrics.Provider, refresh time.Duration) {
 			defer close(p.metricsDone)
 			t := time.NewTicker(refresh)
 			defer t.Stop()
+			var mismatchesSeen uint64
 			for {
 				select {
 				case <-p.stopMetrics:
@@ -638,6 +723,13 @@ func (p *Provider) RegisterMetrics(mp metrics.Provider, refresh time.Duration) {
 				m.memo.With("what", "hash_misses").Set(float64(hm))
 				m.memo.With("what", "hash_blocks_held").Set(float64(hb))
 				m.memo.With("what", "hash_copies_refused").Set(float64(hr))
+				if _, _, _, mm, _, _ := p.AuditStats(); mm > mismatchesSeen {
+					m.auditMismatches.Add(float64(mm - mismatchesSeen))
+					mismatchesSeen = mm
+				}
+				if p.Poisoned() { // (a lookup that met the mismatch only answers "miss": this is where the Go side learns of it)
+					m.poisoned.Set(1)
+				}
 			}
 		}()
 	})

@@ -45,6 +45,7 @@ extern "C" {
 #define FABGPU_ENOMEM (-3)     /* host or device allocation failed */
 #define FABGPU_ELAUNCH (-4)    /* kernel launch / execution / copy failed */
 #define FABGPU_ETOOBIG (-5)    /* batch or arena larger than the ABI's 32-bit offsets allow */
+#define FABGPU_EPOISONED (-6)  /* the provider's CPU audit disagreed with the device once (fabgpu_bccsp.h): it serves nothing any more */
 
 /* ---- per-tuple status codes (data) ----
  * What bccsp/sw would have returned for the tuple, see SURVEY.md Appendix A:

@@ -48,6 +48,10 @@ typedef struct fabgpu_csp_opts {
                                       always misses (default on) */
     uint32_t hash_memo_blocks;     /* per device: host copies of blocks the digest memo keeps at a time, each as large as its block, pinned
                                       (0: 8; at most 64).  A block beyond that simply has no digest memo: its messages are hashed on the CPU */
+    uint32_t audit_permille;       /* 0 .. 1000: share of what the provider hands out from the device that it re-computes on the CPU first
+                                      (see "CPU audit" below; 0, the default: none).  fabgpu_csp_new2 answers FABGPU_EINVAL beyond 1000.
+                                      On LP64 the field occupies what was the struct's tail padding - sizeof has not changed -, so a caller
+                                      built against the older header hands over whatever its padding held: as ever, zero the struct first */
 } fabgpu_csp_opts;
 int fabgpu_csp_new2(const fabgpu_csp_opts* opts, fabgpu_csp** out, char* err, size_t errcap);
 void fabgpu_csp_free(fabgpu_csp* csp);
@@ -58,12 +62,37 @@ fabgpu_ctx* fabgpu_csp_ctx_of(fabgpu_csp* csp, int d);
 int fabgpu_csp_passes_per_device(fabgpu_csp* csp, uint64_t* passes, int cap);
 int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pass named block_seq would go right now */
 /* the switches above on a living provider (tests, A/B runs): "pass_device_walk", "pass_stage_min_bytes", "pass_device_memo",
- * "pass_host_counts", "pass_skip_hash_checks", "pass_timing", "pass_hash_memo" - same convention: 0 the default, > 0 on / the threshold, < 0 off; get also
+ * "pass_host_counts", "pass_skip_hash_checks", "pass_timing", "pass_hash_memo" - same convention: 0 the default, > 0 on / the threshold, < 0 off;
+ * "audit_permille" (0 .. 1000, FABGPU_EINVAL outside); get also
  * answers "n_devices" and two counters: "registrations_dropped" (key / issuer tables that could not be brought onto every device of the
  * pool after three attempts - those identities verify on the fresh-key kernels / bccsp/idemix) and "registration_id_mismatches".
  * FABGPU_EINVAL: no such option. */
 int fabgpu_csp_set_option(fabgpu_csp* csp, const char* name, int64_t value, int64_t* previous);
 int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value);
+
+/* ---- CPU audit of device results, and poisoning ----
+ * Digests and verdicts the provider hands out were computed by kernels; nothing outside the device checks them (a validator that takes
+ * its digest from fabgpu_csp_hash_lookup no longer cross-checks the device's SHA-256 with its own).  With audit_permille > 0 the provider
+ * re-computes a fixed share of them on the calling thread, in host code, before they are returned:
+ *   - fabgpu_csp_hash_lookup hits: SHA-256 of the caller's message;
+ *   - fabgpu_csp_memo_lookup hits: bccsp.Verify(k, sig, digest) as bccsp/sw decides it, against stored status 0 / anything else;
+ *   - "valid" answers of fabgpu_csp_verify, _verify_batch, _verify_coalesced, _identity_verify_batch, _identity_verify_coalesced
+ *     (the identity calls hash the message again first).  Rejects are not sampled: the Go side re-checks every reject in bccsp/sw.
+ * Idemix pseudonym entries (fabgpu_csp_memo_lookup_nym, fabgpu_csp_idemix_nym_verify_batch) are NOT audited; they are counted.
+ * Sampling has no randomness: one hit counter per kind, hit number h (1-based) is audited iff h*permille/1000 != (h-1)*permille/1000 -
+ * 1000 audits every hit, 250 exactly every fourth, 0 none.
+ * The first disagreement POISONS the provider, for good: one flag shared by every context of the pool and every thread.  The lookup
+ * that found it answers a miss (the caller computes for itself); a direct call reports that item with an error text instead of
+ * "valid" and returns FABGPU_EPOISONED.  From then on every memo and digest lookup misses; every verify, identity, nym, hash and
+ * block-pass entry point returns FABGPU_EPOISONED without launching anything (a direct call that was in flight returns it too: its
+ * outputs are not to be used); a pass already in flight finishes but seeds no memo; fabgpu_csp_free still works.  The Go provider
+ * serves everything from bccsp/sw from then on.
+ * fabgpu_csp_poison poisons by hand (why may be NULL); fabgpu_csp_poisoned returns 1 / 0 and the FIRST reason (why may be NULL).
+ * fabgpu_csp_audit_stats: out[0] digest audits, [1] verdict audits, [2] direct-call audits, [3] mismatches, [4] pseudonym results
+ * handed out unaudited while audit_permille > 0, [5] nanoseconds spent auditing; returns how many were written (cap < 6: the first cap). */
+int fabgpu_csp_poison(fabgpu_csp* csp, const char* why);
+int fabgpu_csp_poisoned(fabgpu_csp* csp, char* why, size_t cap);
+int fabgpu_csp_audit_stats(fabgpu_csp* csp, uint64_t* out, int cap);
 
 /* BCCSP.KeyImport for a P-256 public key (bccsp/sw/keyimport.go:103-134; pattern bccsp/pkcs11/pkcs11.go:148-179): checks
  * curve membership and registers the key's comb table on the device (fabgpu_p256_key_register), so that batches whose

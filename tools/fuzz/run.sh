@@ -45,6 +45,6 @@ open("/tmp/cert.pem", "w").write(ids[0]["pem"])
 open("/tmp/ipk.bin", "wb").write(bytes.fromhex(json.load(open(ROOT + "/tests/golden/idemix_fixtures.json"))["msps"]["MSP1OU1"]["ipk"]))
 PY
 $CXX $FLAGS tools/fuzz/fuzz_walk.cpp $SRC/block_prepass.cpp $SRC/idemix_host.cpp tools/fuzz/stubs.cpp -o /tmp/fuzz_walk -lpthread
-$CXX $FLAGS tools/fuzz/fuzz_cert.cpp $SRC/block_prepass.cpp $SRC/bccsp_host.cpp $SRC/idemix_host.cpp tools/fuzz/stubs.cpp -o /tmp/fuzz_cert -lpthread
+$CXX $FLAGS tools/fuzz/fuzz_cert.cpp $SRC/block_prepass.cpp $SRC/bccsp_host.cpp $SRC/audit_host.cpp $SRC/idemix_host.cpp tools/fuzz/stubs.cpp -o /tmp/fuzz_cert -lpthread
 /tmp/fuzz_walk
 /tmp/fuzz_cert

@@ -22,7 +22,9 @@
  * What it prints (one JSON line): the pass as the binding calls it (first block of a fresh provider, i.e. over its caps; warm blocks),
  * the validators' CPU residue per block (hashing + memo lookups on T threads), and end-to-end validated tx/s of the two-stage pipeline.
  *
- * usage: go_call_replay <block file> [blocks=12] [validator threads=16] [devices=1] [hash memo=1] [arrivals in flight=1] [blocks pre-verified ahead=arrivals]
+ * usage: go_call_replay [--audit-permille N] <block file> [blocks=12] [validator threads=16] [devices=1] [hash memo=1] [arrivals in flight=1] [blocks pre-verified ahead=arrivals]
+ *   --audit-permille N   GPUOpts.AuditPermille (0 .. 1000; here 0 unless given, gpufactory.go defaults to 1): the provider re-computes that
+ *                        share of the digests and verdicts it hands out on the CPU first; the line then carries the audit's counters and its time
  * Test / bench infrastructure: links the product library through its C ABI only (include/fabgpu*.h) + libcrypto for the CPU SHA-256.
  */
 #define _GNU_SOURCE
@@ -250,8 +252,17 @@ static double median(double* v, int n) {
 }
 
 int main(int argc, char** argv) {
+    long audit_permille = 0;
+    for (int i = 1; i + 1 < argc; i++)
+        if (strcmp(argv[i], "--audit-permille") == 0) {       /* taken out of argv: the positional arguments keep their places */
+            audit_permille = atol(argv[i + 1]);
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    if (audit_permille < 0 || audit_permille > 1000) { fprintf(stderr, "--audit-permille takes 0 .. 1000\n"); return 2; }
     if (argc < 2) {
-        fprintf(stderr, "usage: %s <block file> [blocks=12] [validator threads=16] [devices=1] [hash memo=1] [arrivals in flight=1] [window=arrivals]\n", argv[0]);
+        fprintf(stderr, "usage: %s [--audit-permille N] <block file> [blocks=12] [validator threads=16] [devices=1] [hash memo=1] [arrivals in flight=1] [window=arrivals]\n", argv[0]);
         return 2;
     }
     int n_blocks = argc > 2 ? atoi(argv[2]) : 12, n_thr = argc > 3 ? atoi(argv[3]) : 16, n_dev = argc > 4 ? atoi(argv[4]) : 1;
@@ -327,6 +338,7 @@ int main(int argc, char** argv) {
     o.devices = devs;
     o.concurrent_passes = g_arrivals > 2 ? (uint32_t)g_arrivals : 2; /* GPUOpts.ConcurrentPasses */
     o.pass_hash_memo = g_hash_memo ? 0 : -1;   /* (GPUOpts.HashMemo: on unless the operator switched it off) */
+    o.audit_permille = (uint32_t)audit_permille;   /* GPUOpts.AuditPermille */
     o.pass_timing = getenv("GO_REPLAY_PASS_TIMING") ? 1 : 0; /* stage breakdown of every pass on stderr (probes only) */
     o.expect_block_bytes = len + 4096;
     o.expect_tuples = n_tuples + 64;
@@ -469,7 +481,15 @@ int main(int argc, char** argv) {
            (unsigned long long)mismatches, (unsigned long long)hits, (unsigned long long)misses, wall, wall / n_blocks,
            (double)n_tx * n_blocks / (wall * 1e-3), (unsigned long long)dw, (unsigned long long)hw);
     for (int d = 0; d < nd; d++) printf("%s%llu", d ? ", " : "", (unsigned long long)per_dev[d]);
-    printf("]}\n");
+    uint64_t au[6] = {0, 0, 0, 0, 0, 0};
+    fabgpu_csp_audit_stats(g_csp, au, 6);
+    char poisoned_why[256];
+    const int poisoned = fabgpu_csp_poisoned(g_csp, poisoned_why, sizeof(poisoned_why));
+    printf("], \"audit_permille\": %ld, \"audit\": {\"digest_audits\": %llu, \"verdict_audits\": %llu, \"direct_audits\": %llu, \"mismatches\": %llu, "
+           "\"skipped_nym\": %llu, \"audit_ns\": %llu, \"audit_ms_per_block\": %.4f, \"poisoned\": %d}}\n",
+           audit_permille, (unsigned long long)au[0], (unsigned long long)au[1], (unsigned long long)au[2], (unsigned long long)au[3], (unsigned long long)au[4],
+           (unsigned long long)au[5], au[5] * 1e-6 / n_blocks, poisoned);
+    if (poisoned) fprintf(stderr, "provider poisoned: %s\n", poisoned_why);
     fabgpu_csp_free(g_csp);
     return 0;
 }
