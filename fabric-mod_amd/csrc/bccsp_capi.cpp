@@ -128,6 +128,11 @@ int fabgpu_csp_audit_stats(fabgpu_csp* csp, uint64_t* out, int cap) {
     return n;
 }
 
+int fabgpu_csp_key_table_stats(fabgpu_csp* csp, int d, uint64_t* out, int cap) {
+    if (!csp || cap < 0 || (cap > 0 && !out)) return FABGPU_EINVAL;
+    return csp->csp->KeyTableStats(d, out, cap);
+}
+
 int fabgpu_csp_key_import(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, int* on_curve, char* err, size_t errcap) {
     if (!csp) return FABGPU_EINVAL;
     ECDSAPublicKey k;

@@ -224,6 +224,7 @@ Error GPUCSP::New(const ProviderOptions& opts, std::unique_ptr<GPUCSP>& out) {
     if ((int)devices.size() > kMaxProviderDevices) return Error("Failed initializing GPU BCCSP: more device contexts than the provider takes");
     std::unique_ptr<GPUCSP> p(new GPUCSP());
     p->opts_ = opts;
+    p->retire_evicted_.store(opts.retire_evicted_keys > 0, std::memory_order_relaxed);
     p->opts_.devices = devices;
     p->audit_permille_.store(opts.audit_permille > 1000 ? 1000 : opts.audit_permille, std::memory_order_relaxed);
     for (int32_t ord : devices) {
@@ -275,7 +276,8 @@ const OptField kIntOpts[] = {{"pass_device_walk", &ProviderOptions::pass_device_
                              {"pass_host_counts", &ProviderOptions::pass_host_counts},
                              {"pass_skip_hash_checks", &ProviderOptions::pass_skip_hash_checks},
                              {"pass_timing", &ProviderOptions::pass_timing},
-                             {"pass_hash_memo", &ProviderOptions::pass_hash_memo}};
+                             {"pass_hash_memo", &ProviderOptions::pass_hash_memo},
+                             {"retire_evicted_keys", &ProviderOptions::retire_evicted_keys}};
 }  // namespace
 int64_t GPUCSP::SetOption(const std::string& name, int64_t value) const {
     std::lock_guard<std::mutex> lk(opt_mu_);
@@ -293,6 +295,7 @@ int64_t GPUCSP::SetOption(const std::string& name, int64_t value) const {
         if (name == o.name) {
             const int64_t prev = opts_.*(o.f);
             opts_.*(o.f) = (int)value;
+            if (name == "retire_evicted_keys") retire_evicted_.store(value > 0, std::memory_order_relaxed);
             return prev;
         }
     return INT64_MIN;
@@ -313,6 +316,7 @@ int64_t GPUCSP::GetOption(const std::string& name) const {
 // contexts behind its back makes the ids differ - then the key simply has no table here (-1) and verifies on the fresh-key kernels.
 int64_t GPUCSP::RegisterKeyOnAllDevices(const uint8_t* qx32, const uint8_t* qy32, const int32_t* prebuilt_table) const {
     std::lock_guard<std::mutex> lk(reg_mu_);
+    FlushRetirementsRegLocked();
     if (!HealPendingRegistrationsLocked()) return -1;       // (nothing new is installed while an earlier registration is still lopsided)
     const int G = (int)devs_.size();
     fabgpu_ctx* cs[kMaxProviderDevices];
@@ -347,6 +351,7 @@ int64_t GPUCSP::RegisterKeyOnAllDevices(const uint8_t* qx32, const uint8_t* qy32
 bool GPUCSP::RegisterKeysOnAllDevices(const std::vector<std::pair<std::string, CachedIdentity>>& keys, std::vector<int64_t>& ids) const {
     if (keys.empty()) return true;
     std::lock_guard<std::mutex> lk(reg_mu_);
+    FlushRetirementsRegLocked();
     if (!HealPendingRegistrationsLocked()) return false;
     const int G = (int)devs_.size(), n = (int)keys.size();
     std::vector<uint8_t> qxy((size_t)64 * n);
@@ -573,7 +578,15 @@ Error GPUCSP::KeyImport(const uint8_t* qx32, const uint8_t* qy32, ECDSAPublicKey
     memcpy(out.y, qy32, 32);
     out.on_curve = PublicKeyOnCurve(qx32, qy32);
     // a long-lived identity's key gets its comb table on the device (best effort: on failure the fresh-key kernels serve it)
-    if (out.on_curve && device_table) (void)RegisterKeyOnAllDevices(qx32, qy32);
+    if (out.on_curve && device_table) {
+        {
+            std::string k((const char*)qx32, 32);
+            k.append((const char*)qy32, 32);
+            std::lock_guard<std::mutex> lk(retire_mu_);
+            imported_keys_.insert(std::move(k));            // (an imported key's table is the caller's: no eviction retires it)
+        }
+        (void)RegisterKeyOnAllDevices(qx32, qy32);
+    }
     return Error();
 }
 
@@ -1241,25 +1254,90 @@ void GPUCSP::MemoSetCapacity(size_t max_entries) const {
     memo_cap_ = max_entries ? max_entries : 1;
 }
 void GPUCSP::SetIdentityCacheLimits(size_t max_identities, size_t max_registered_keys, uint32_t register_after_hits) const {
-    std::lock_guard<std::mutex> lk(idmu_);
-    id_max_ = max_identities ? max_identities : 1;
-    id_max_registered_ = max_registered_keys;
-    id_register_after_ = register_after_hits ? register_after_hits : 1;
-    EvictIdentitiesLocked();
-    id_version_.fetch_add(1, std::memory_order_release);
+    {
+        std::lock_guard<std::mutex> lk(idmu_);
+        id_max_ = max_identities ? max_identities : 1;
+        id_max_registered_ = max_registered_keys;
+        id_register_after_ = register_after_hits ? register_after_hits : 1;
+        EvictIdentitiesLocked();
+        id_version_.fetch_add(1, std::memory_order_release);
+    }
+    FlushRetirements();
 }
 // (idmu_ held) the LRU bound.  An identity that owned a device comb table gives its place in the table budget back: the table itself
 // stays registered with the context (launches in flight may still name it; fabgpu_p256_key_register finds it again by key should the
 // identity return), but id_registered_ counts the tables of CACHED identities - otherwise a provider that churned through more than
 // id_max_registered_ registered identities could never register another one and stayed on the fresh-key kernels for good.
+// With retire_evicted_keys the table goes too: the key is queued here and retired on every device by FlushRetirements (an identity
+// whose registration is still under way is queued by RegisterQueued, when that registration finds the identity gone).
 void GPUCSP::EvictIdentitiesLocked() const {
     while (idcache_.size() > id_max_) {
-        const CachedIdentity& c = idlru_.back().second;
+        const CachedIdentity c = idlru_.back().second;
         if ((c.key_id >= 0 || c.registering) && id_registered_ > 0) id_registered_--;
         idserial_.erase(c.serial);
         idcache_.erase(idlru_.back().first);
         idlru_.pop_back();
+        if (c.p256 && c.key_id >= 0 && retire_evicted_.load(std::memory_order_relaxed)) QueueRetirementLocked(c.qx, c.qy);
     }
+}
+void GPUCSP::QueueRetirementLocked(const uint8_t* qx32, const uint8_t* qy32) const {
+    for (const auto& kv : idlru_) {
+        const CachedIdentity& o = kv.second;
+        if (o.p256 && (o.key_id >= 0 || o.registering) && !memcmp(o.qx, qx32, 32) && !memcmp(o.qy, qy32, 32)) return;   // (two certificates, one key)
+    }
+    std::string k((const char*)qx32, 32);
+    k.append((const char*)qy32, 32);
+    std::lock_guard<std::mutex> lk(retire_mu_);
+    retire_queue_.push_back(std::move(k));
+}
+void GPUCSP::FlushRetirements() const {
+    {
+        std::lock_guard<std::mutex> lk(retire_mu_);
+        if (retire_queue_.empty()) return;
+    }
+    std::lock_guard<std::mutex> lk(reg_mu_);
+    FlushRetirementsRegLocked();
+}
+void GPUCSP::FlushRetirementsRegLocked() const {
+    std::vector<std::string> q;
+    {
+        std::lock_guard<std::mutex> lk(retire_mu_);
+        if (retire_queue_.empty()) return;
+        q.swap(retire_queue_);
+        for (auto& k : q)
+            if (imported_keys_.count(k)) k.clear();
+    }
+    {
+        // an identity with this key may be back in the cache since the key was queued, and may have been handed the still-registered
+        // id by an idempotent registration: then the table stays (lock order reg_mu_, then idmu_: nothing takes reg_mu_ while it holds idmu_)
+        std::lock_guard<std::mutex> lk(idmu_);
+        for (auto& k : q) {
+            if (k.empty()) continue;
+            for (const auto& kv : idlru_) {
+                const CachedIdentity& o = kv.second;
+                if (o.p256 && (o.key_id >= 0 || o.registering) && !memcmp(o.qx, k.data(), 32) && !memcmp(o.qy, k.data() + 32, 32)) {
+                    k.clear();
+                    break;
+                }
+            }
+        }
+    }
+    const int G = (int)devs_.size();
+    fabgpu_ctx* cs[kMaxProviderDevices];
+    for (int g = 0; g < G; g++) cs[g] = devs_[(size_t)g]->ctx;
+    for (const std::string& k : q) {
+        if (k.empty()) continue;
+        const int rc = fabgpu_p256_key_unregister_many(cs, G, (const uint8_t*)k.data(), (const uint8_t*)k.data() + 32);
+        if (rc == FABGPU_OK || rc == 2) keys_retired_.fetch_add(1, std::memory_order_relaxed);
+        if (rc == 2) reg_id_mismatches_.fetch_add(1, std::memory_order_relaxed);      // (some devices had the key and some had not: the pool was lopsided)
+    }
+}
+int GPUCSP::KeyTableStats(int d, uint64_t* out, int cap) const {
+    if (d < 0 || d >= (int)devs_.size()) return FABGPU_EINVAL;
+    const int n = fabgpu_p256_key_table_stats(devs_[(size_t)d]->ctx, out, cap);
+    if (n < 0) return n;
+    if (cap > n) out[n] = keys_retired_.load(std::memory_order_relaxed);
+    return n + 1;
 }
 void GPUCSP::InsertIdentityLocked(std::string&& key, CachedIdentity ci, bool evict_now) const {
     ci.table_hash = walk::id_hash_host((const uint8_t*)key.data(), (uint32_t)key.size(), idtab_seed_);
@@ -1307,7 +1385,10 @@ int64_t GPUCSP::RegisterIdemixMSP(const std::string& mspid, const uint8_t* ipk_r
 
 // identities that earned a device comb table during a block: built and uploaded outside idmu_ (6 ms of host work each)
 void GPUCSP::RegisterQueued(const std::vector<std::string>& to_register) const {
-    if (to_register.empty()) return;
+    if (to_register.empty()) {
+        FlushRetirements();                                  // (what this pass evicted)
+        return;
+    }
     std::vector<std::pair<std::string, CachedIdentity>> todo;
     {
         std::lock_guard<std::mutex> lk(idmu_);
@@ -1341,9 +1422,12 @@ void GPUCSP::RegisterQueued(const std::vector<std::string>& to_register) const {
             it->second->second.registering = false;
             if (ok) it->second->second.key_id = id;
             else if (id_registered_ > 0) id_registered_--;
+        } else if (ok && retire_evicted_.load(std::memory_order_relaxed)) {
+            QueueRetirementLocked(kv.second.qx, kv.second.qy);      // (evicted while its table was being built)
         }
         if (ok) id_version_.fetch_add(1, std::memory_order_release);    // (a failed attempt changed nothing the devices' tables show)
     }
+    FlushRetirements();
 }
 
 void GPUCSP::SeedMemo(const uint8_t* block, const ParsedBlock& pb, BlockVerdicts& out, const PassOptions& opt, std::vector<uint32_t>& sel_scratch,
@@ -2541,6 +2625,11 @@ Error GPUCSP::PreVerifyParsed(const uint8_t* block, const ParsedBlock& pb, Block
         dv.passes.fetch_add(1, std::memory_order_relaxed);
         for (size_t j = 0; j < n; j++) {
             bool bit = (bits[j >> 6] >> (j & 63)) & 1;
+            if (all_keyed && st[j] == FABGPU_ST_OFF_CURVE) {
+                // (the id was retired between the cache lookup above and the launch - key_slots.h: "use bccsp/sw", never "invalid")
+                out.tuple_status[sub[j]] = TUPLE_ST_NEEDS_SW;
+                continue;
+            }
             out.tuple_status[sub[j]] = (bit && st[j] == FABGPU_ST_VALID) ? FABGPU_ST_VALID : (st[j] == FABGPU_ST_VALID ? FABGPU_ST_BAD_MATH : st[j]);
             out.tuple_hashed[sub[j]] = 1;
             if (want_digests) memcpy(&out.tuple_digest[32 * (size_t)sub[j]], &dig[32 * j], 32);

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include <memory>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -138,6 +139,8 @@ struct ProviderOptions {
     int pass_hash_memo = 0;            // < 0: memo-seeding passes keep no host copy of their block and bccsp.Hash is never answered from the
                                        // digest memo (default on: HashLookup)
     uint32_t hash_memo_blocks = 0;     // per device: host copies of blocks kept at a time for the digest memo (0: 8; at most 64)
+    int retire_evicted_keys = 0;       // > 0: an identity the cache evicts gives its device comb table up too (fabgpu_p256_key_unregister on every
+                                       // device; default off: the table stays registered with the contexts)
     uint32_t audit_permille = 0;       // share of the digests / verdicts handed out that is re-computed on the CPU first (0 .. 1000; 0: none)
 };
 constexpr int kMaxProviderDevices = 64;   // contexts per provider (8 GPUs x up to 8 contexts each)
@@ -222,6 +225,8 @@ class GPUCSP {
     // identity cache bounds (msp/cache/cache.go keeps 100 deserialized identities; the pass sees every client certificate too)
     void SetIdentityCacheLimits(size_t max_identities, size_t max_registered_keys, uint32_t register_after_hits) const;
     size_t IdentityCacheSize() const;
+    // fabgpu_p256_key_table_stats of device context d, then (out[FABGPU_KEY_TABLE_STATS]) the keys this provider has retired
+    int KeyTableStats(int d, uint64_t* out, int cap) const;
     // device-route statistics since construction: launches repeated after a wrong "everybody is registered" prediction, tuples whose
     // certificate the device decoded itself, identities that entered the cache that way, signatures that took the general DER parser
     void PassStats(uint64_t out[4]) const;
@@ -365,6 +370,18 @@ class GPUCSP {
     mutable std::atomic<uint64_t> pass_relaunches_{0}, pass_decoded_{0}, pass_learned_{0}, pass_general_der_{0};
     void EvictIdentitiesLocked() const;
     void RegisterQueued(const std::vector<std::string>& to_register) const;
+    // retire_evicted_keys.  EvictIdentitiesLocked (idmu_ held) only QUEUES the evicted identity's key; the queue is emptied under reg_mu_
+    // - the lock every registration holds - before each registration and at the end of each pass: every device retires the same keys
+    // in the same order between the same two registrations, so the pool keeps agreeing on ids (key_slots.h).  Keys that came in through
+    // KeyImport are never retired, nor a key another cached identity still holds a table for.
+    void QueueRetirementLocked(const uint8_t* qx32, const uint8_t* qy32) const;
+    void FlushRetirements() const;
+    void FlushRetirementsRegLocked() const;
+    mutable std::atomic<bool> retire_evicted_{false};
+    mutable std::mutex retire_mu_;                           // retire_queue_, imported_keys_ (a leaf: nothing is taken under it)
+    mutable std::vector<std::string> retire_queue_;          // qx || qy
+    mutable std::set<std::string> imported_keys_;
+    mutable std::atomic<uint64_t> keys_retired_{0};
     bool RegisterKeysOnAllDevices(const std::vector<std::pair<std::string, CachedIdentity>>& keys, std::vector<int64_t>& ids) const;
     void SeedMemo(const uint8_t* block, const ParsedBlock& pb, BlockVerdicts& out, const PassOptions& opt, std::vector<uint32_t>& sel_scratch, int gate_max,
                   BlockUpload* up = nullptr) const;

@@ -695,9 +695,16 @@ __device__ __forceinline__ void walk_status_part(const WalkArrays& a, uint32_t i
             const bool from_all = in_c ? a.all_creators != 0 : a.all_others != 0;
             const bool bit = from_all ? ((a.verdict_bits_all[row >> 6] >> (row & 63)) & 1) : (((in_c ? a.verdict_bits_c : a.verdict_bits)[j >> 6] >> (j & 63)) & 1);
             const uint8_t ds = a.dev_status[row];
-            st = (bit && ds == FABGPU_ST_VALID) ? FABGPU_ST_VALID : (ds == FABGPU_ST_VALID ? FABGPU_ST_BAD_MATH : ds);
-            hashed = 1;
-            by_ecdsa = true;
+            if (ds == FABGPU_ST_OFF_CURVE && (a.tflags[i] & TF_KEYED)) {
+                // A registered key is on the curve (the registration's gate): status 4 on its row means the ID was not the key's any more -
+                // retired, perhaps its slot reused, between the identity table this pass read and its launch (key_slots.h).  "Use
+                // bccsp/sw", as fabgpu.h says: not decided here, no memo entry - never "invalid".
+                st = (uint8_t)bccsp::TUPLE_ST_NEEDS_SW;
+            } else {
+                st = (bit && ds == FABGPU_ST_VALID) ? FABGPU_ST_VALID : (ds == FABGPU_ST_VALID ? FABGPU_ST_BAD_MATH : ds);
+                hashed = 1;
+                by_ecdsa = true;
+            }
         }
         a.tuple_status[i] = st;
         a.tuple_hashed[i] = hashed;

@@ -8,6 +8,8 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <condition_variable>
+#include <initializer_list>
 #include <memory>
 #include <sys/mman.h>
 #include <set>
@@ -20,6 +22,7 @@
 
 #include "../../include/fabgpu.h"
 #include "kernels.h"
+#include "key_slots.h"
 #include "block_walk_dev.h"
 #include "worker_pool.h"
 #include "bn_tables29.h"
@@ -164,10 +167,38 @@ struct fabgpu_ctx {
     std::vector<QWs> qws;
     // Registered public keys: one 640 KiB comb table each, resident on the device; d_ktabs mirrors the pointer array.
     std::mutex kmu;
-    std::vector<int32_t*> ktabs;
-    std::map<std::string, uint32_t> key_ids;   // qx||qy -> id
-    const int32_t** d_ktabs = nullptr;      // KTAB_STRIDE pointers per key: [2 k] the 8-bit comb, [2 k + 1] the 16-bit comb or nullptr
-    size_t d_ktabs_cap = 0;                 // (in keys)
+    std::vector<int32_t*> ktabs;            // per SLOT (kslots.high_water() of them): the 8-bit comb d_ktabs shows for it
+    std::map<std::string, uint32_t> key_ids;   // qx||qy -> id, live keys only
+    const int32_t** d_ktabs = nullptr;      // KTAB_STRIDE words per slot (kernels.h): the 8-bit comb, the 16-bit comb or nullptr, the generation
+    size_t d_ktabs_cap = 0;                 // (in slots)
+    // Retiring keys (fabgpu_p256_key_unregister; key_slots.h has the ids).  A retirement takes the key out of key_ids and leaves the
+    // device alone; the slot and its tables then pass two waits before anything of them is used again:
+    //   phase 1  behind events recorded AT the retirement on every stream that has carried a keyed launch (and on the 16-bit builder's,
+    //            if the key had a build queued): whatever was enqueued before the retirement finds the old key and answers for it;
+    //   phase 2  at a moment when no launcher is between its snapshot of (nkeys, d_ktabs) and its last keyed enqueue
+    //            (keyed_launchers == 0) the host sets the slot's generation word to KTAB_GEN_NONE, and events recorded THEN have completed: nothing
+    //            that could have seen the old generation is running.  Only now the tables go to the free lists and the slot may be
+    //            handed out again - pointers first, the new generation last, both written by the host before the new id is returned.
+    // Phases advance on the registration paths (kdrain_advance_locked), never on a verify call or a block pass; a registration whose
+    // slot (the LOWEST reclaimable one, always) is still draining waits for that slot's events with hipEventSynchronize.
+    fab::KeySlots kslots;
+    std::vector<std::string> kname;         // per slot: its tenant's qx||qy
+    std::vector<uint32_t> kgen_dev;         // per slot: the generation word the device shows
+    struct KeyDrain {
+        uint32_t slot = 0;
+        int phase = 1;
+        std::vector<hipEvent_t> evs;
+        int32_t* t8 = nullptr;
+        void* t16 = nullptr;
+        int idx16 = -1;
+    };
+    std::vector<KeyDrain> kdrains;          // oldest first
+    std::vector<hipEvent_t> kev_pool;
+    std::vector<hipStream_t> keyed_streams; // every stream a keyed launch was queued on (KeyedSnap)
+    std::mutex keyed_lm;                    // (a leaf, taken under kmu or alone)
+    std::condition_variable keyed_cv;
+    int keyed_launchers = 0;                // launchers between their snapshot under kmu and their last keyed enqueue (keyed_lm)
+    hipStream_t stream_kslot = nullptr;     // the host's few-byte writes into d_ktabs
     std::vector<void*> retired;   // outgrown d_ktabs arrays, freed at shutdown
     // Round 6, FABGPU_FLAG_KEY_TABLES_16BIT: a registered key also gets a 16-bit comb (CombTab<16>, 80 MiB - the generator's own format),
     // built on stream_keytab BEHIND the registration (nobody waits for it; its pointer reaches d_ktabs[2 k + 1] by a copy queued after
@@ -175,17 +206,25 @@ struct fabgpu_ctx {
     bool key_tables_16 = false;
     hipStream_t stream_keytab16 = nullptr;  // (its own: a registration waits on stream_keytab for the 8-bit table and must not find an 80 MiB build queued there)
     static constexpr size_t KTAB16_MAX = 64;
-    std::vector<void*> ktab16;              // per key id: the table, or nullptr
+    std::vector<void*> ktab16;              // per slot: the table, or nullptr
+    std::vector<int> ktab16_idx;            // per slot: which room and pinned head its build used, or -1
+    std::vector<void*> ktab16_free;         // tables, rooms + heads of retired keys, drained
+    std::vector<int> ktab16_idx_free;
+    size_t ktab16_idx_next = 0;             // rooms + heads handed out for the first time so far
+    // a REUSED slot's 16-bit pointer is not written from the builder's stream: the host writes it, under kmu, once the build's event
+    // has completed (k16_publish_locked, on the next registration, retirement or stats call - never on a verify call or a pass)
+    struct Pending16 { uint32_t slot; void* tab; hipEvent_t built; };
+    std::vector<Pending16> k16_pending;
     std::vector<void*> ktab16_slabs;        // tables come from slabs of KTAB16_SLAB (the first one at fabgpu_init: a registration must not pay for an 80 MiB hipMalloc)
     static constexpr size_t KTAB16_SLAB = 8;
     size_t ktab16_carved = 0;               // tables handed out of the slabs so far
     void* ktab16_rooms = nullptr;           // KTAB16_MAX builders' rooms (key + pointer + scratch), one allocation
-    uint8_t* ktab16_heads = nullptr;        // pinned host memory, KTAB16_MAX x 128 bytes: what each build's upload reads (never reused: the copies are asynchronous)
+    uint8_t* ktab16_heads = nullptr;        // pinned host memory, KTAB16_MAX x 128 bytes: what each build's upload reads (reused only behind the build's drain: the copies are asynchronous)
     size_t ktab16_room_bytes = 0;
-    size_t ktab16_count = 0;
+    size_t ktab16_count = 0;                // LIVE keys with a 16-bit table (built or building); KTAB16_MAX caps live + draining ones
     // Where the tables live: slabs of KTAB_SLAB tables (a table is never freed before shutdown, and hipMalloc / hipFree per table were
     // most of what a registration cost once the tables were built on the device: 4.7 ms of runtime calls around 0.8 ms of kernels for a
-    // channel's six signers).  ktab_free: tables whose installation failed.  All under kmu.
+    // channel's six signers).  ktab_free: tables whose installation failed, and those of retired keys once drained.  All under kmu.
     static constexpr size_t KTAB_SLAB = 32;
     std::vector<void*> ktab_slabs;
     size_t ktab_slab_used = KTAB_SLAB;
@@ -492,6 +531,7 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
         if (ctx->d_ktab_in) hipFree(ctx->d_ktab_in);
         if (ctx->d_ktab_scr) hipFree(ctx->d_ktab_scr);
         if (ctx->stream_keytab) hipStreamDestroy(ctx->stream_keytab);
+        if (ctx->stream_kslot) hipStreamDestroy(ctx->stream_kslot);
         for (auto* t : ctx->itabs) hipFree(t);
         if (ctx->d_issuers) hipFree(ctx->d_issuers);
         ctx->nym.release();
@@ -522,6 +562,10 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
             if (sl.d) hipFree(sl.d);
         if (ctx->stream_keytab16) { hipStreamSynchronize(ctx->stream_keytab16); hipStreamDestroy(ctx->stream_keytab16); }       // (16-bit key tables may still be building)
         if (ctx->d_ktabs) hipFree((void*)ctx->d_ktabs);
+        for (auto& d : ctx->kdrains)
+            for (hipEvent_t e : d.evs) hipEventDestroy(e);
+        for (auto& p : ctx->k16_pending) hipEventDestroy(p.built);
+        for (hipEvent_t e : ctx->kev_pool) hipEventDestroy(e);
         for (void* t : ctx->ktab16_slabs)
             if (t) hipFree(t);
         if (ctx->ktab16_rooms) hipFree(ctx->ktab16_rooms);
@@ -760,6 +804,155 @@ int fabgpu_idemix_nym_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* ar
 // one key's comb table into one context: id of the key there (idempotent per (qx, qy)); `tab` = the table, built by the caller
 static int key_install_table_locked(fabgpu_ctx* ctx, const std::string& k, int32_t* d, uint32_t* key_id);
 static void key_queue_table16_locked(fabgpu_ctx* ctx, const std::string& k, uint32_t id);
+
+// ---- retiring keys: the two waits between a retirement and the reuse of its slot and tables (fabgpu_ctx::kslots has the story) ----
+// (kmu held, the context's device current) a few bytes of the host's into d_ktabs, complete on return.  Not with hipMemcpy: that one
+// runs on the null stream and waits for every blocking stream of the process.
+static bool kslot_write_locked(fabgpu_ctx* ctx, size_t word, const void* src, size_t bytes) {
+    if (!ctx->stream_kslot && hipStreamCreateWithFlags(&ctx->stream_kslot, hipStreamNonBlocking) != hipSuccess) return false;
+    hipError_t e = hipMemcpyAsync((void*)(ctx->d_ktabs + word), src, bytes, hipMemcpyHostToDevice, ctx->stream_kslot);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream_kslot);      // (a stream of its own: the copy is all that is ever queued there)
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e == hipSuccess;
+}
+static hipEvent_t kev_get_locked(fabgpu_ctx* ctx) {
+    hipEvent_t e = nullptr;
+    if (!ctx->kev_pool.empty()) {
+        e = ctx->kev_pool.back();
+        ctx->kev_pool.pop_back();
+    } else if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        e = nullptr;
+    }
+    return e;
+}
+// events behind everything queued so far on the streams that carry keyed launches (with16: and on the 16-bit builder's).  A stream the
+// caller has destroyed since (a keyed _dev call's stream must be idle by then) refuses the record and is forgotten.  false: an event
+// could not be made or recorded on a stream of the context's own - the caller falls back to waiting for those streams.
+static bool kdrain_record_locked(fabgpu_ctx* ctx, fabgpu_ctx::KeyDrain& d, bool with16) {
+    bool ok = true;
+    auto one = [&](hipStream_t s, bool own) {
+        hipEvent_t e = kev_get_locked(ctx);
+        if (e && hipEventRecord(e, s) == hipSuccess) {
+            d.evs.push_back(e);
+            return true;
+        }
+        (void)hipGetLastError();
+        if (e) ctx->kev_pool.push_back(e);
+        if (own) {
+            ok = ok && hipStreamSynchronize(s) == hipSuccess;
+            (void)hipGetLastError();
+        }
+        return own;
+    };
+    for (size_t i = 0; i < ctx->keyed_streams.size();) {
+        hipStream_t s = ctx->keyed_streams[i];
+        const bool own = s == ctx->stream || s == ctx->stream2 || s == ctx->stream3 || s == ctx->stream4;
+        if (one(s, own)) i++;
+        else ctx->keyed_streams.erase(ctx->keyed_streams.begin() + (long)i);
+    }
+    if (with16 && ctx->stream_keytab16) one(ctx->stream_keytab16, true);
+    return ok;
+}
+static bool kdrain_events_done_locked(fabgpu_ctx* ctx, fabgpu_ctx::KeyDrain& d, bool wait) {
+    while (!d.evs.empty()) {
+        hipError_t e = wait ? hipEventSynchronize(d.evs.back()) : hipEventQuery(d.evs.back());
+        if (e == hipErrorNotReady) {
+            (void)hipGetLastError();
+            return false;
+        }
+        if (e != hipSuccess) (void)hipGetLastError();      // (a failed device: nothing of it runs any more)
+        ctx->kev_pool.push_back(d.evs.back());
+        d.evs.pop_back();
+    }
+    return true;
+}
+// One retired slot as far as it goes without waiting for a launch or a launcher (wait: all the way).  true: drained - tables on the
+// free lists, slot reclaimable.  The step from phase 1 to phase 2 needs a moment at which no launcher is between its snapshot of
+// (nkeys, d_ktabs) and its last keyed enqueue: kmu is held, so no new snapshot is taken while the generation word is written and the
+// second set of events recorded - whoever took a snapshot earlier has enqueued (the events cover it), whoever takes one later finds
+// KTAB_GEN_NONE.  Without `wait` a launcher under way just postpones the step; with it the caller sleeps on keyed_cv (launchers
+// never take kmu while they are counted, so they finish).
+static bool kdrain_step_locked(fabgpu_ctx* ctx, fabgpu_ctx::KeyDrain& d, bool wait) {
+    if (d.phase == 1) {
+        if (!kdrain_events_done_locked(ctx, d, wait)) return false;
+        {
+            std::unique_lock<std::mutex> ll(ctx->keyed_lm);
+            if (ctx->keyed_launchers != 0 && !wait) return false;
+            ctx->keyed_cv.wait(ll, [&] { return ctx->keyed_launchers == 0; });
+        }
+        const uint64_t none = KTAB_GEN_NONE;
+        if (!kslot_write_locked(ctx, KTAB_STRIDE * (size_t)d.slot + 2, &none, sizeof(none))) return false;   // (stays in phase 1: tried again)
+        ctx->kgen_dev[d.slot] = KTAB_GEN_NONE;
+        kdrain_record_locked(ctx, d, false);
+        d.phase = 2;
+    }
+    if (!kdrain_events_done_locked(ctx, d, wait)) return false;
+    if (d.t8) ctx->ktab_free.push_back(d.t8);
+    if (d.t16) ctx->ktab16_free.push_back(d.t16);
+    if (d.idx16 >= 0) ctx->ktab16_idx_free.push_back(d.idx16);
+    ctx->kslots.drained(d.slot);                    // (a parked slot stays parked)
+    return true;
+}
+static void kdrain_advance_locked(fabgpu_ctx* ctx) {
+    for (size_t i = 0; i < ctx->kdrains.size();) {
+        if (kdrain_step_locked(ctx, ctx->kdrains[i], false)) ctx->kdrains.erase(ctx->kdrains.begin() + (long)i);
+        else i++;
+    }
+}
+static bool kdrain_wait_slot_locked(fabgpu_ctx* ctx, uint32_t slot) {
+    for (size_t i = 0; i < ctx->kdrains.size(); i++)
+        if (ctx->kdrains[i].slot == slot) {
+            if (!kdrain_step_locked(ctx, ctx->kdrains[i], true)) return false;
+            ctx->kdrains.erase(ctx->kdrains.begin() + (long)i);
+            return true;
+        }
+    return !ctx->kslots.draining(slot);
+}
+// 16-bit combs of reused slots whose build has finished: the host writes their pointers
+static void k16_publish_locked(fabgpu_ctx* ctx) {
+    for (size_t i = 0; i < ctx->k16_pending.size();) {
+        auto& p = ctx->k16_pending[i];
+        hipError_t e = hipEventQuery(p.built);
+        if (e == hipErrorNotReady) {
+            (void)hipGetLastError();
+            i++;
+            continue;
+        }
+        if (e == hipSuccess && ctx->ktab16[p.slot] == p.tab) {
+            DeviceGuard g(ctx->device);
+            (void)kslot_write_locked(ctx, KTAB_STRIDE * (size_t)p.slot + 1, &p.tab, sizeof(void*));     // (not written: served by the 8-bit comb)
+        }
+        ctx->kev_pool.push_back(p.built);
+        ctx->k16_pending.erase(ctx->k16_pending.begin() + (long)i);
+    }
+}
+// What a keyed launch site needs of the key table, taken under kmu, and the launcher's place in keyed_launchers until its last keyed
+// launch is queued (the destructor).  The streams it will queue keyed launches on are remembered for the retirements' events.
+// Nothing between the constructor and the destructor may take kmu.
+static_assert(KEY_SLOT_BITS == (int)fab::KeySlots::SLOT_BITS && FABGPU_MAX_KEYS == (1 << KEY_SLOT_BITS) && fab::KeySlots::MAX_SLOTS == FABGPU_MAX_KEYS,
+              "the kernels' slot bits (kernels.h), the allocator's (key_slots.h) and the public cap on live keys (fabgpu.h) are one number");
+static_assert(KTAB_GEN_NONE > fab::KeySlots::GEN_LAST, "no id may carry the generation word of a slot between two tenants");
+struct KeyedSnap {
+    fabgpu_ctx* ctx;
+    uint32_t nkeys = 0;
+    const int32_t** kt = nullptr;
+    KeyedSnap(fabgpu_ctx* c, std::initializer_list<hipStream_t> streams) : ctx(c) {
+        std::lock_guard<std::mutex> lk(ctx->kmu);
+        nkeys = ctx->kslots.high_water();
+        kt = ctx->d_ktabs;
+        for (hipStream_t s : streams)
+            if (std::find(ctx->keyed_streams.begin(), ctx->keyed_streams.end(), s) == ctx->keyed_streams.end()) ctx->keyed_streams.push_back(s);
+        std::lock_guard<std::mutex> ll(ctx->keyed_lm);
+        ctx->keyed_launchers++;
+    }
+    ~KeyedSnap() {
+        std::lock_guard<std::mutex> ll(ctx->keyed_lm);
+        if (--ctx->keyed_launchers == 0) ctx->keyed_cv.notify_all();
+    }
+    KeyedSnap(const KeyedSnap&) = delete;
+    KeyedSnap& operator=(const KeyedSnap&) = delete;
+};
 // (kmu held, the context's device current) room for one table: out of the current slab, a new slab when that is used up
 static int32_t* ktab_alloc_locked(fabgpu_ctx* ctx) {
     if (!ctx->ktab_free.empty()) {
@@ -784,8 +977,9 @@ static int key_install(fabgpu_ctx* ctx, const std::string& k, const std::vector<
         *key_id = it->second;
         return FABGPU_OK;
     }
-    if (ctx->ktabs.size() >= FABGPU_MAX_KEYS) return FABGPU_ENOMEM;
+    if (ctx->kslots.next_slot() < 0) return FABGPU_ENOMEM;
     DeviceGuard g(ctx->device);
+    kdrain_advance_locked(ctx);
     std::vector<int32_t> own;
     if (!tab_in) {
         u256 qx, qy;
@@ -809,8 +1003,12 @@ static int key_install(fabgpu_ctx* ctx, const std::string& k, const std::vector<
 // d_ktabs[2 id + 1].  Nothing waits: the registration returns, launches on other streams use the 8-bit comb until the pointer is there.
 // kmu is held.  Failures (memory, a launch) leave the key without a 16-bit comb.
 static void key_queue_table16_locked(fabgpu_ctx* ctx, const std::string& k, uint32_t id) {
+    const uint32_t slot = fab::KeySlots::slot_of(id);
+    const bool first_tenant = fab::KeySlots::gen_of(id) == 0;
     if (ctx->ktab16_count >= fabgpu_ctx::KTAB16_MAX || ctx->fault) return;
-    if (ctx->ktab16.size() <= id) ctx->ktab16.resize((size_t)id + 1, nullptr);
+    if (ctx->ktab16_idx_free.empty() && ctx->ktab16_idx_next >= fabgpu_ctx::KTAB16_MAX) return;      // (every room is live or draining)
+    if (ctx->ktab16.size() <= slot) ctx->ktab16.resize((size_t)slot + 1, nullptr);
+    if (ctx->ktab16_idx.size() <= slot) ctx->ktab16_idx.resize((size_t)slot + 1, -1);
     if (!ctx->stream_keytab16 && hipStreamCreateWithFlags(&ctx->stream_keytab16, hipStreamNonBlocking) != hipSuccess) return;
     const size_t tab_bytes = sizeof(int32_t) * GTab16::TABLE_WORDS;
     if (!ctx->ktab16_rooms) {
@@ -821,7 +1019,8 @@ static void key_queue_table16_locked(fabgpu_ctx* ctx, const std::string& k, uint
             return;
         }
     }
-    if (ctx->ktab16_carved == ctx->ktab16_slabs.size() * fabgpu_ctx::KTAB16_SLAB) {
+    const bool tab_reused = !ctx->ktab16_free.empty();
+    if (!tab_reused && ctx->ktab16_carved == ctx->ktab16_slabs.size() * fabgpu_ctx::KTAB16_SLAB) {
         void* slab = nullptr;
         if (hipMalloc(&slab, tab_bytes * fabgpu_ctx::KTAB16_SLAB) != hipSuccess) {
             (void)hipGetLastError();
@@ -829,8 +1028,10 @@ static void key_queue_table16_locked(fabgpu_ctx* ctx, const std::string& k, uint
         }
         ctx->ktab16_slabs.push_back(slab);
     }
-    void* tab = (uint8_t*)ctx->ktab16_slabs.back() + tab_bytes * (ctx->ktab16_carved % fabgpu_ctx::KTAB16_SLAB);
-    void* room = (uint8_t*)ctx->ktab16_rooms + ctx->ktab16_room_bytes * ctx->ktab16_count;
+    void* tab = tab_reused ? ctx->ktab16_free.back() : (uint8_t*)ctx->ktab16_slabs.back() + tab_bytes * (ctx->ktab16_carved % fabgpu_ctx::KTAB16_SLAB);
+    const bool idx_reused = !ctx->ktab16_idx_free.empty();
+    const size_t idx = idx_reused ? (size_t)ctx->ktab16_idx_free.back() : ctx->ktab16_idx_next;
+    void* room = (uint8_t*)ctx->ktab16_rooms + ctx->ktab16_room_bytes * idx;
     hipStream_t st = ctx->stream_keytab16;
     // room: [0, 64) the key, [64, 72) the table's address (what the entries kernel reads), [128, ...) scratch
     if (!ctx->ktab16_heads && hipHostMalloc((void**)&ctx->ktab16_heads, 128 * fabgpu_ctx::KTAB16_MAX, hipHostMallocDefault) != hipSuccess) {
@@ -838,28 +1039,65 @@ static void key_queue_table16_locked(fabgpu_ctx* ctx, const std::string& k, uint
         ctx->ktab16_heads = nullptr;
         return;
     }
-    uint8_t* head = ctx->ktab16_heads + 128 * ctx->ktab16_count;
+    uint8_t* head = ctx->ktab16_heads + 128 * idx;
     memcpy(head, k.data(), 64);
     memcpy(head + 64, &tab, sizeof(void*));
+    hipEvent_t built = first_tenant ? nullptr : kev_get_locked(ctx);
+    if (!first_tenant && !built) return;
     hipError_t e = hipMemcpyAsync(room, head, 72, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = launch_keytab16_build(1, room, (void* const*)((uint8_t*)room + 64), (uint8_t*)room + 128, st);
-    if (e == hipSuccess) e = hipMemcpyAsync((void*)(ctx->d_ktabs + KTAB_STRIDE * (size_t)id + 1), (uint8_t*)room + 64, sizeof(void*), hipMemcpyDeviceToDevice, st);
+    // a slot's first tenant: the pointer follows the build on the builder's stream, as ever.  A reused slot: the host writes it (k16_publish_locked)
+    if (e == hipSuccess && first_tenant) e = hipMemcpyAsync((void*)(ctx->d_ktabs + KTAB_STRIDE * (size_t)slot + 1), (uint8_t*)room + 64, sizeof(void*), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && !first_tenant) e = hipEventRecord(built, st);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        hipStreamSynchronize(st);                       // (the table's place in the slab and the room are simply used again by the next key)
+        hipStreamSynchronize(st);                       // (the table and the room are simply used again by the next key)
+        if (built) ctx->kev_pool.push_back(built);
         return;
     }
-    ctx->ktab16[id] = tab;
-    ctx->ktab16_carved++;
+    if (built) ctx->k16_pending.push_back({slot, tab, built});
+    ctx->ktab16[slot] = tab;
+    ctx->ktab16_idx[slot] = (int)idx;
+    if (tab_reused) ctx->ktab16_free.pop_back();
+    else ctx->ktab16_carved++;
+    if (idx_reused) ctx->ktab16_idx_free.pop_back();
+    else ctx->ktab16_idx_next++;
     ctx->ktab16_count++;
 }
 
 static int key_install_table_locked(fabgpu_ctx* ctx, const std::string& k, int32_t* d, uint32_t* key_id) {
-    if (ctx->ktabs.size() >= FABGPU_MAX_KEYS) {
+    kdrain_advance_locked(ctx);
+    if (!ctx->k16_pending.empty()) k16_publish_locked(ctx);
+    const int64_t next = ctx->kslots.next_slot();
+    if (next < 0) {
         ctx->ktab_free.push_back(d);
         return FABGPU_ENOMEM;
     }
-    // grow the device-side pointer array by doubling; the old array is only released at shutdown, so launches already in
+    const uint32_t slot = (uint32_t)next;
+    if (slot < ctx->ktabs.size()) {
+        // A retired key's slot, the lowest there is.  Still draining: wait for ITS events (key_slots.h: never another slot).  Then nothing
+        // on the device can name the slot with a generation it shows (KTAB_GEN_NONE): the pointers first, the new generation last.
+        if (!kdrain_wait_slot_locked(ctx, slot)) {
+            ctx->ktab_free.push_back(d);
+            return FABGPU_ELAUNCH;
+        }
+        const int32_t* ptrs[2] = {d, nullptr};
+        const uint64_t gen = (uint64_t)ctx->kslots.generation(slot) + 1;
+        if (!kslot_write_locked(ctx, KTAB_STRIDE * (size_t)slot, ptrs, sizeof(ptrs)) || !kslot_write_locked(ctx, KTAB_STRIDE * (size_t)slot + 2, &gen, sizeof(gen))) {
+            ctx->ktab_free.push_back(d);
+            return FABGPU_ELAUNCH;
+        }
+        ctx->ktabs[slot] = d;
+        if (slot < ctx->ktab16.size()) ctx->ktab16[slot] = nullptr;
+        if (slot < ctx->ktab16_idx.size()) ctx->ktab16_idx[slot] = -1;
+        ctx->kgen_dev[slot] = (uint32_t)gen;
+        ctx->kname[slot] = k;
+        *key_id = ctx->kslots.take(slot);
+        ctx->key_ids[k] = *key_id;
+        if (ctx->key_tables_16) key_queue_table16_locked(ctx, k, *key_id);
+        return FABGPU_OK;
+    }
+    // grow the device-side array by doubling; the old array is only released at shutdown, so launches already in
     // flight on other streams keep reading a valid (shorter) array
     if (ctx->ktabs.size() + 1 > ctx->d_ktabs_cap) {
         size_t cap = ctx->d_ktabs_cap ? ctx->d_ktabs_cap * 2 : 64;
@@ -869,12 +1107,15 @@ static int key_install_table_locked(fabgpu_ctx* ctx, const std::string& k, int32
             return FABGPU_ENOMEM;
         }
         if (!ctx->ktabs.empty()) {
-            // (the 16-bit builds queued on stream_keytab write their pointers into the OLD array: let them land before it is copied)
-            if (ctx->ktab16_count && ctx->stream_keytab16) hipStreamSynchronize(ctx->stream_keytab16);
+            // (the 16-bit builds queued on stream_keytab write their pointers into the OLD array: let them land before it is copied.
+            //  A launcher that still holds the old array is counted in keyed_launchers like any other: a slot retired from now on waits
+            //  for it, and an id handed out from now on is simply out of its range)
+            if (ctx->stream_keytab16) hipStreamSynchronize(ctx->stream_keytab16);
             std::vector<const int32_t*> both(ctx->ktabs.size() * KTAB_STRIDE, nullptr);
             for (size_t i = 0; i < ctx->ktabs.size(); i++) {
                 both[KTAB_STRIDE * i] = ctx->ktabs[i];
                 both[KTAB_STRIDE * i + 1] = i < ctx->ktab16.size() ? (const int32_t*)ctx->ktab16[i] : nullptr;
+                both[KTAB_STRIDE * i + 2] = (const int32_t*)(uintptr_t)ctx->kgen_dev[i];
             }
             hipMemcpy((void*)nd, both.data(), both.size() * sizeof(int32_t*), hipMemcpyHostToDevice);
         }
@@ -882,13 +1123,15 @@ static int key_install_table_locked(fabgpu_ctx* ctx, const std::string& k, int32
         ctx->d_ktabs = nd;
         ctx->d_ktabs_cap = cap;
     }
-    const int32_t* slot[KTAB_STRIDE] = {d, nullptr};
-    if (hipMemcpy((void*)(ctx->d_ktabs + KTAB_STRIDE * ctx->ktabs.size()), slot, sizeof(slot), hipMemcpyHostToDevice) != hipSuccess) {
+    const int32_t* slotw[KTAB_STRIDE] = {d, nullptr, nullptr, nullptr};      // (generation 0)
+    if (hipMemcpy((void*)(ctx->d_ktabs + KTAB_STRIDE * ctx->ktabs.size()), slotw, sizeof(slotw), hipMemcpyHostToDevice) != hipSuccess) {
         ctx->ktab_free.push_back(d);
         return FABGPU_ELAUNCH;
     }
     ctx->ktabs.push_back(d);
-    *key_id = (uint32_t)(ctx->ktabs.size() - 1);
+    ctx->kgen_dev.push_back(0);
+    ctx->kname.push_back(k);
+    *key_id = ctx->kslots.take(slot);
     ctx->key_ids[k] = *key_id;
     if (ctx->key_tables_16) key_queue_table16_locked(ctx, k, *key_id);    // (best effort: a key without one is served by its 8-bit comb)
     return FABGPU_OK;
@@ -917,7 +1160,8 @@ static int key_register_batch_dev(fabgpu_ctx* ctx, int n, const uint8_t* qxy, ui
             for (int j : todo) dup = dup || names[(size_t)j] == names[(size_t)i];
             if (!dup && ctx->key_ids.find(names[(size_t)i]) == ctx->key_ids.end()) todo.push_back(i);
         }
-        if (ctx->ktabs.size() + todo.size() > FABGPU_MAX_KEYS) return FABGPU_ENOMEM;
+        if (todo.size() > ctx->kslots.room()) return FABGPU_ENOMEM;
+        kdrain_advance_locked(ctx);
         for (size_t t = 0; t < todo.size(); t++) {
             int32_t* d = ktab_alloc_locked(ctx);
             if (!d) {
@@ -1050,7 +1294,62 @@ int fabgpu_p256_key_lookup(fabgpu_ctx* ctx, const uint8_t* qx32, const uint8_t* 
 int fabgpu_p256_key_count(fabgpu_ctx* ctx) {
     if (!ctx) return FABGPU_EINVAL;
     std::lock_guard<std::mutex> lk(ctx->kmu);
-    return (int)ctx->ktabs.size();
+    return (int)ctx->kslots.n_live();
+}
+
+int fabgpu_p256_key_unregister(fabgpu_ctx* ctx, uint32_t key_id) {
+    if (!ctx) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->kmu);
+    if (!ctx->kslots.live(key_id)) return 1;
+    const uint32_t slot = fab::KeySlots::slot_of(key_id);
+    DeviceGuard g(ctx->device);
+    if (!ctx->k16_pending.empty()) k16_publish_locked(ctx);
+    ctx->key_ids.erase(ctx->kname[slot]);
+    ctx->kslots.retire(key_id);
+    // the device keeps showing the key: what is queued already answers for it.  The slot and its tables wait (fabgpu_ctx::kslots)
+    fabgpu_ctx::KeyDrain d;
+    d.slot = slot;
+    d.t8 = ctx->ktabs[slot];
+    d.t16 = slot < ctx->ktab16.size() ? ctx->ktab16[slot] : nullptr;
+    d.idx16 = slot < ctx->ktab16_idx.size() ? ctx->ktab16_idx[slot] : -1;
+    if (d.t16) {
+        ctx->ktab16_count--;
+        for (size_t i = 0; i < ctx->k16_pending.size(); i++)
+            if (ctx->k16_pending[i].slot == slot) {      // (a build still queued: its pointer is never published; the builder's stream is among the events)
+                d.evs.push_back(ctx->k16_pending[i].built);
+                ctx->k16_pending.erase(ctx->k16_pending.begin() + (long)i);
+                break;
+            }
+    }
+    kdrain_record_locked(ctx, d, d.t16 != nullptr);
+    ctx->kdrains.push_back(std::move(d));
+    return FABGPU_OK;
+}
+
+int fabgpu_p256_key_unregister_many(fabgpu_ctx* const* ctxs, int n, const uint8_t* qx32, const uint8_t* qy32) {
+    if (!ctxs || n <= 0 || !qx32 || !qy32) return FABGPU_EINVAL;
+    for (int g = 0; g < n; g++)
+        if (!ctxs[g]) return FABGPU_EINVAL;
+    int had = 0;
+    for (int g = 0; g < n; g++) {
+        uint32_t id = 0;
+        if (fabgpu_p256_key_lookup(ctxs[g], qx32, qy32, &id) == FABGPU_OK && fabgpu_p256_key_unregister(ctxs[g], id) == FABGPU_OK) had++;
+    }
+    return had == n ? FABGPU_OK : (had == 0 ? 1 : 2);
+}
+
+int fabgpu_p256_key_table_stats(fabgpu_ctx* ctx, uint64_t* out, int cap) {
+    if (!ctx || (cap > 0 && !out)) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->kmu);
+    if (!ctx->k16_pending.empty()) k16_publish_locked(ctx);
+    uint64_t bytes = (uint64_t)ctx->ktab_slabs.size() * fabgpu_ctx::KTAB_SLAB * sizeof(int32_t) * KeyTab8::TABLE_WORDS +
+                     (uint64_t)ctx->ktab16_slabs.size() * fabgpu_ctx::KTAB16_SLAB * sizeof(int32_t) * GTab16::TABLE_WORDS +
+                     (ctx->ktab16_rooms ? (uint64_t)ctx->ktab16_room_bytes * fabgpu_ctx::KTAB16_MAX : 0) +
+                     (uint64_t)ctx->d_ktabs_cap * KTAB_STRIDE * sizeof(void*);
+    const uint64_t v[FABGPU_KEY_TABLE_STATS] = {ctx->kslots.n_live(), ctx->kslots.n_draining(), ctx->kslots.n_reused(), ctx->kslots.n_parked(),
+                                                (uint64_t)ctx->ktab16_count, bytes, ctx->kslots.high_water()};
+    for (int i = 0; i < cap && i < FABGPU_KEY_TABLE_STATS; i++) out[i] = v[i];
+    return FABGPU_KEY_TABLE_STATS;
 }
 
 int fabgpu_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* key_id, const void* e, const void* r, const void* s,
@@ -1058,16 +1357,12 @@ int fabgpu_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* ke
     if (!ctx || (n && (!key_id || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
     if (n > 0xFFFFFFF0ull) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
-    uint32_t nkeys;
-    const int32_t** kt;
-    {
-        std::lock_guard<std::mutex> lk(ctx->kmu);
-        nkeys = (uint32_t)ctx->ktabs.size();
-        kt = ctx->d_ktabs;
-    }
+    hipStream_t st = (hipStream_t)stream;
+    KeyedSnap snap(ctx, {st});
+    const uint32_t nkeys = snap.nkeys;
+    const int32_t** kt = snap.kt;
     if (nkeys == 0) return FABGPU_EINVAL;
     DeviceGuard g(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
     if (ctx->allow_wide && n <= (size_t)WIDE_LAUNCH_MAX) {
         // a launch that cannot fill the chip: eight lanes per signature, the digest-independent half first (kernels.h, p256_wide29.h)
         size_t wi = 0;
@@ -1124,16 +1419,12 @@ int fabgpu_sha256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const v
     if (!ctx || (n && (!arena || !off || !key_id || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
     if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
-    uint32_t nkeys;
-    const int32_t** kt;
-    {
-        std::lock_guard<std::mutex> lk(ctx->kmu);
-        nkeys = (uint32_t)ctx->ktabs.size();
-        kt = ctx->d_ktabs;
-    }
+    hipStream_t st = (hipStream_t)stream;
+    KeyedSnap snap(ctx, {st});
+    const uint32_t nkeys = snap.nkeys;
+    const int32_t** kt = snap.kt;
     if (nkeys == 0) return FABGPU_EINVAL;
     DeviceGuard g(ctx->device);
-    hipStream_t st = (hipStream_t)stream;
     if (ctx->allow_wide && n <= (size_t)WIDE_LAUNCH_MAX)
         return keyed_wide_identity_dev(ctx, (uint32_t)n, arena, arena_bytes, off, key_id, nkeys, (const void*)kt, r, s, verdict_bits, status, ShaPrefixArgs(), st);
     if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
@@ -1392,13 +1683,9 @@ int fabgpu_identity_verify_batch_dev(fabgpu_ctx* ctx, const fabgpu_identity_batc
     v.verdict_bits = b->verdict_bits; v.status = b->status;
     v.allow_pair = ctx->allow_pair;
     if (keyed) {
-        uint32_t nkeys;
-        const int32_t** kt;
-        {
-            std::lock_guard<std::mutex> lk(ctx->kmu);
-            nkeys = (uint32_t)ctx->ktabs.size();
-            kt = ctx->d_ktabs;
-        }
+        KeyedSnap snap(ctx, {st});
+        const uint32_t nkeys = snap.nkeys;
+        const int32_t** kt = snap.kt;
         if (nkeys == 0) return FABGPU_EINVAL;
         if (ctx->allow_wide && n <= (size_t)WIDE_LAUNCH_MAX) {
             int rc = keyed_wide_identity_dev(ctx, (uint32_t)n, b->arena, b->arena_bytes, b->off, b->key_id, nkeys, (const void*)kt, b->r, b->s, b->verdict_bits,
@@ -2444,13 +2731,9 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
     // the main stream looks identities up and gates signatures
     hipStream_t sc = s2;                                                   // the creators' stream
     bool memo_early_pending = false;
-    uint32_t nkeys = 0;
-    const int32_t** kt = nullptr;
-    {
-        std::lock_guard<std::mutex> klk(ctx->kmu);
-        nkeys = (uint32_t)ctx->ktabs.size();
-        kt = ctx->d_ktabs;
-    }
+    KeyedSnap snap(ctx, {st, s2, s3, s4});                                // (until the pass returns: a mispredicted class is launched again at its very end)
+    const uint32_t nkeys = snap.nkeys;
+    const int32_t** kt = snap.kt;
     bool keyed_c = ctx->pred_keyed_creators && nkeys != 0, keyed_o = ctx->pred_keyed_others && nkeys != 0;
     if (!a.split) keyed_c = keyed_o = keyed_c && keyed_o;                  // one launch serves both classes
     // A block of a few hundred transactions (what a default network cuts: sampleconfig/configtx.yaml:284 MaxMessageCount 500) cannot
@@ -2997,7 +3280,9 @@ int64_t key_tables16_check(fabgpu_ctx* ctx, uint32_t key_id) {
     {
         std::lock_guard<std::mutex> lk(ctx->kmu);
         if (ctx->stream_keytab16 && hipStreamSynchronize(ctx->stream_keytab16) != hipSuccess) return -2;
-        if (key_id >= ctx->ktabs.size()) return -2;
+        if (!ctx->kslots.live(key_id)) return -2;
+        if (!ctx->k16_pending.empty()) k16_publish_locked(ctx);
+        key_id = fab::KeySlots::slot_of(key_id);
         count = (int64_t)ctx->ktab16_count;
         t8 = ctx->ktabs[key_id];
         t16 = key_id < ctx->ktab16.size() ? ctx->ktab16[key_id] : nullptr;
@@ -3024,8 +3309,8 @@ int key_table_copy(fabgpu_ctx* ctx, uint32_t key_id, int32_t* out) {
     int32_t* d = nullptr;
     {
         std::lock_guard<std::mutex> lk(ctx->kmu);
-        if (key_id >= ctx->ktabs.size()) return FABGPU_EINVAL;
-        d = ctx->ktabs[key_id];
+        if (!ctx->kslots.live(key_id)) return FABGPU_EINVAL;
+        d = ctx->ktabs[fab::KeySlots::slot_of(key_id)];
     }
     DeviceGuard g(ctx->device);
     return hip_to_rc(hipMemcpy(out, d, sizeof(int32_t) * KeyTab8::TABLE_WORDS, hipMemcpyDeviceToHost));

@@ -67,6 +67,17 @@ long long fabgpu_test_audit_sample(uint32_t permille, uint32_t n_hits, uint8_t* 
  * flips one bit of the index-th stored digest, kind 1 toggles the index-th stored status between valid and bad-signature.
  * 0 done, 1 nothing to corrupt (no such table, no digest memo, a status that is neither), FABGPU_EINVAL. */
 int fabgpu_csp_test_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, int kind, uint32_t index);
+/* TEST HOOK: the allocator of key slots and ids by itself (csrc/key_slots.h; no device, no context).  gen_last: the last generation a
+ * slot may reach (0xFFFFF in the product).  register: the id of the next registration, or -1 when no slot can be had; a lowest slot
+ * that is still draining is waited for, i.e. drained on the spot and counted.  retire: 0 retired, 1 not live.  drain: what a context
+ * does once a retired slot's events have completed (1 if the slot was draining).  stats: live, draining, reused, parked, slots ever
+ * used, registrations that had to wait. */
+void* fabgpu_test_key_slots_new(uint32_t gen_last);
+void fabgpu_test_key_slots_free(void* h);
+long long fabgpu_test_key_slots_register(void* h);
+int fabgpu_test_key_slots_retire(void* h, uint32_t key_id);
+int fabgpu_test_key_slots_drain(void* h, uint32_t slot);
+void fabgpu_test_key_slots_stats(void* h, uint64_t* out6);
 
 
 #ifdef __cplusplus

@@ -5,7 +5,13 @@
 #include <stdint.h>
 
 namespace fab {
-constexpr int KTAB_STRIDE = 2;       // the device's array of key tables: [2 k] the 8-bit comb of key k (CombTab<8>, 640 KiB), [2 k + 1] its 16-bit comb (80 MiB) or nullptr
+// The device's array of key tables: KTAB_STRIDE 8-byte words (one 32-byte line) per SLOT.  [4 k] the 8-bit comb of slot k's tenant (CombTab<8>,
+// 640 KiB), [4 k + 1] its 16-bit comb (80 MiB) or nullptr, [4 k + 2] the tenant's generation in the low 32 bits (KTAB_GEN_NONE while the
+// slot is between two tenants), [4 k + 3] unused.  A key id is generation << KEY_SLOT_BITS | slot (key_slots.h); a row whose id names a
+// slot >= nkeys or another generation than the slot's answers status 4 and reads no table of the slot.
+constexpr int KTAB_STRIDE = 4;
+constexpr int KEY_SLOT_BITS = 12;
+constexpr uint32_t KTAB_GEN_NONE = 0xFFFFFFFFu;      // no id carries it: generations have 32 - KEY_SLOT_BITS bits
 constexpr int VERIFY_BLOCK = 256;         // 4 wavefronts per workgroup, one per SIMD
 constexpr int VERIFY_MAX_WGS = 256;       // persistent workgroup slots: one per CU (see kernels.hip for why not two)
 constexpr int VERIFY_PAIR_MAX = 32768;    // up to here two lanes per signature (one round of 256 workgroups x 128 signatures)
@@ -55,7 +61,7 @@ struct VerifyLaunch {
     const void *qx = nullptr, *qy = nullptr;          // fresh key: n x 32 bytes each ...
     void* qws = nullptr;                              // ... and verify_workspace_bytes(n, allow_pair) bytes for the per-signature tables
     const void *key_id = nullptr, *ktabs = nullptr;   // or registered key: n ids into the device's array of key tables (KTAB_STRIDE) ...
-    uint32_t nkeys = 0;                               // ... of nkeys keys
+    uint32_t nkeys = 0;                               // ... of nkeys slots (the high-water mark: retired slots stay below it)
     const void* e = nullptr;                          // digest given: n x 32 bytes
     const void *arena = nullptr, *off = nullptr;      // or messages: arena[off[i], off[i+1]), possibly behind shared prefixes (pa; the
     size_t arena_bytes = 0;                           // mid-state kernel runs first unless pa.mid_ready)

@@ -151,7 +151,9 @@ struct FreshKey {
 // Registered public keys (fabgpu_p256_key_register): every signature names a key whose 8-bit comb table is resident on the
 // device, so u2*Q is 32 mixed additions like u1*G: no doublings, no per-lane table, no workspace.  ktabs[KTAB_STRIDE k] = table of key k,
 // ktabs[KTAB_STRIDE k + 1] = its 16-bit comb or nullptr (round 6, FABGPU_FLAG_KEY_TABLES_16BIT: 16 mixed additions when a whole wavefront has them).
-// An out-of-range key id reports status 4 ("use bccsp/sw"), never a verdict.
+// An id that is out of range, or that names another generation than the slot's present tenant (a retired key: key_slots.h), reports
+// status 4 ("use bccsp/sw"), never a verdict - and reads none of the slot's tables, which may be another key's by now or half way
+// there: such a row runs on the generator's table and its result is dropped.
 template <int LANE_COUNT>
 struct RegisteredKey {
     static constexpr int LANES = LANE_COUNT;
@@ -159,13 +161,15 @@ struct RegisteredKey {
     uint32_t nkeys;
     const int32_t* const* ktabs;
     const int32_t* gtab;
-    struct Row { const int32_t *kt, *kt16; uint32_t kid; };
+    struct Row { const int32_t *kt, *kt16; bool kok; };
     __device__ __forceinline__ void load(Row& k, uint32_t ic) const {
-        k.kid = key_id[ic];
-        bool kok = k.kid < nkeys;
-        const int32_t* const* slot = ktabs + KTAB_STRIDE * (size_t)(kok ? k.kid : 0);
-        k.kt = slot[0];
-        k.kt16 = slot[1];
+        const uint32_t kid = key_id[ic], sl = kid & ((1u << KEY_SLOT_BITS) - 1u);
+        const bool inr = sl < nkeys;
+        const int32_t* const* slot = ktabs + KTAB_STRIDE * (size_t)(inr ? sl : 0);
+        const int32_t *t8 = slot[0], *t16 = slot[1];
+        k.kok = inr && (uint32_t)(uintptr_t)slot[2] == (kid >> KEY_SLOT_BITS);
+        k.kt = k.kok ? t8 : gtab;              // (a 16-bit comb is larger than an 8-bit one: every index of the latter lies inside)
+        k.kt16 = k.kok ? t16 : nullptr;
     }
     __device__ __forceinline__ uint32_t verify(const Row& k, const u256& e, const u256& r, const u256& s, bool odd) {
         uint32_t st;
@@ -175,7 +179,7 @@ struct RegisteredKey {
         } else {
             st = p256_verify_keyed_pair29(e, r, s, gtab, k.kt, k.kt16, odd);
         }
-        if (!(k.kid < nkeys)) st = ST_OFF_CURVE;
+        if (!k.kok) st = ST_OFF_CURVE;
         return st;
     }
 };

@@ -12,6 +12,7 @@
 #include "bccsp_capi_private.h"
 #include "block_walk_dev.h"
 #include "fabgpu_testhooks.h"
+#include "key_slots.h"
 #include "idemix_host.h"
 
 using namespace fab::bccsp;
@@ -302,4 +303,37 @@ int fabgpu_csp_test_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, int kind, 
 }
 
 
+
+// ---- key slots (key_slots.h) ----
+namespace {
+struct SlotsProbe {
+    fab::KeySlots slots;
+    uint64_t waits = 0;
+    explicit SlotsProbe(uint32_t gen_last) : slots(gen_last) {}
+};
+}  // namespace
+void* fabgpu_test_key_slots_new(uint32_t gen_last) { return new SlotsProbe(gen_last); }
+void fabgpu_test_key_slots_free(void* h) { delete (SlotsProbe*)h; }
+long long fabgpu_test_key_slots_register(void* h) {
+    SlotsProbe& p = *(SlotsProbe*)h;
+    const int64_t slot = p.slots.next_slot();
+    if (slot < 0) return -1;
+    if (p.slots.draining((uint32_t)slot)) {
+        p.waits++;
+        p.slots.drained((uint32_t)slot);
+    }
+    return (long long)p.slots.take((uint32_t)slot);
+}
+int fabgpu_test_key_slots_retire(void* h, uint32_t key_id) { return ((SlotsProbe*)h)->slots.retire(key_id); }
+int fabgpu_test_key_slots_drain(void* h, uint32_t slot) {
+    SlotsProbe& p = *(SlotsProbe*)h;
+    if (!p.slots.draining(slot)) return 0;
+    p.slots.drained(slot);
+    return 1;
+}
+void fabgpu_test_key_slots_stats(void* h, uint64_t* out6) {
+    const SlotsProbe& p = *(SlotsProbe*)h;
+    out6[0] = p.slots.n_live(); out6[1] = p.slots.n_draining(); out6[2] = p.slots.n_reused();
+    out6[3] = p.slots.n_parked(); out6[4] = p.slots.high_water(); out6[5] = p.waits;
+}
 }  // extern "C"

@@ -30,9 +30,13 @@ __global__ void __launch_bounds__(64 * W, 1) p256_wide_pre_kernel(uint32_t n, co
         const uint32_t i = tile * PER + (lane >> 3);
         const bool active = i < n;
         const uint32_t ic = active ? i : (n - 1);
-        const uint32_t kid = key_id[ic];
-        const bool kok = kid < nkeys;
-        KeyTab8 kt{ktabs[KTAB_STRIDE * (size_t)(kok ? kid : 0)]};
+        // (a slot out of range or another generation than its tenant's: status 4, and none of the slot's tables is read - kernels.hip RegisteredKey)
+        const uint32_t kid = key_id[ic], sl = kid & ((1u << KEY_SLOT_BITS) - 1u);
+        const bool inr = sl < nkeys;
+        const int32_t* const* slot = ktabs + KTAB_STRIDE * (size_t)(inr ? sl : 0);
+        const int32_t* t8 = slot[0];
+        const bool kok = inr && (uint32_t)(uintptr_t)slot[2] == (kid >> KEY_SLOT_BITS);
+        KeyTab8 kt{kok ? t8 : gtab};
         u256 vr, vs;
         load_be_field(vr, r, ic);
         load_be_field(vs, s, ic);

@@ -105,6 +105,9 @@ class _Cfg(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
+# what fabgpu_p256_key_table_stats reports, in order
+KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "live_16bit", "bytes_held", "slots_used")
+
 # every symbol include/fabgpu.h and include/fabgpu_bccsp.h declare (tests check the export list)
 ABI_SYMBOLS = [
     "fabgpu_init", "fabgpu_shutdown", "fabgpu_device_count", "fabgpu_strerror", "fabgpu_abi_version",
@@ -131,6 +134,7 @@ ABI_SYMBOLS = [
     "fabgpu_csp_route_block", "fabgpu_csp_set_option", "fabgpu_csp_get_option",
     "fabgpu_csp_hash_lookup", "fabgpu_csp_hash_memo_stats",
     "fabgpu_csp_poison", "fabgpu_csp_poisoned", "fabgpu_csp_audit_stats",
+    "fabgpu_p256_key_unregister", "fabgpu_p256_key_unregister_many", "fabgpu_p256_key_table_stats", "fabgpu_csp_key_table_stats",
 ]
 
 # what libfabgpu_testhooks.so exports (fabric-mod_amd/csrc/fabgpu_testhooks.h): probes, walker comparisons, the synthetic block generator, the
@@ -140,6 +144,8 @@ HOOK_SYMBOLS = [
     "fabgpu_gate_sig_any", "fabgpu_csp_idfix_probe", "fabgpu_csp_gate_probe", "fabgpu_identity_table_hash", "fabgpu_test_nym_side_after",
     "fabgpu_test_key_table", "fabgpu_test_key_table_host", "fabgpu_test_gtab_compare_with_host", "fabgpu_test_key_tables16",
     "fabgpu_test_audit_sha256", "fabgpu_test_audit_p256_verify", "fabgpu_test_audit_sample", "fabgpu_csp_test_memo_corrupt",
+    "fabgpu_test_key_slots_new", "fabgpu_test_key_slots_free", "fabgpu_test_key_slots_register", "fabgpu_test_key_slots_retire",
+    "fabgpu_test_key_slots_drain", "fabgpu_test_key_slots_stats",
 ]
 _HOOKS_PATH = os.path.join(os.path.dirname(_LIB_PATH), "libfabgpu_testhooks.so")
 
@@ -185,6 +191,16 @@ def load_hooks():
     H.fabgpu_test_audit_sample.argtypes = [ctypes.c_uint32, ctypes.c_uint32, _u8p]
     H.fabgpu_test_audit_sample.restype = ctypes.c_longlong
     H.fabgpu_csp_test_memo_corrupt.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32]
+    H.fabgpu_test_key_slots_new.argtypes = [ctypes.c_uint32]
+    H.fabgpu_test_key_slots_new.restype = _vp
+    H.fabgpu_test_key_slots_free.argtypes = [_vp]
+    H.fabgpu_test_key_slots_free.restype = None
+    H.fabgpu_test_key_slots_register.argtypes = [_vp]
+    H.fabgpu_test_key_slots_register.restype = ctypes.c_longlong
+    H.fabgpu_test_key_slots_retire.argtypes = [_vp, ctypes.c_uint32]
+    H.fabgpu_test_key_slots_drain.argtypes = [_vp, ctypes.c_uint32]
+    H.fabgpu_test_key_slots_stats.argtypes = [_vp, _u64p]
+    H.fabgpu_test_key_slots_stats.restype = None
     _hooks = H
     return H
 
@@ -216,6 +232,10 @@ def load():
     L.fabgpu_p256_key_register.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, _u32p]
     L.fabgpu_p256_key_lookup.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, _u32p]
     L.fabgpu_p256_key_count.argtypes = [_vp]
+    L.fabgpu_p256_key_unregister.argtypes = [_vp, ctypes.c_uint32]
+    L.fabgpu_p256_key_unregister_many.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p]
+    L.fabgpu_p256_key_table_stats.argtypes = [_vp, _u64p, ctypes.c_int]
+    L.fabgpu_csp_key_table_stats.argtypes = [_vp, ctypes.c_int, _u64p, ctypes.c_int]
     L.fabgpu_p256_verify_batch_keyed.argtypes = [_vp, _sz, _u32p, _u8p, _u8p, _u8p, _u64p, _u8p]
     L.fabgpu_p256_verify_batch_keyed_dev.argtypes = [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.fabgpu_sha256_p256_verify_batch_keyed.argtypes = [_vp, _sz, _u8p, _u32p, _u32p, _u8p, _u8p, _u64p, _u8p]
@@ -438,7 +458,30 @@ class Context:
         return int(kid.value)
 
     def key_count(self) -> int:
+        """Live registered keys."""
         return self._L.fabgpu_p256_key_count(self._h)
+
+    def key_lookup(self, qx32: bytes, qy32: bytes) -> Optional[int]:
+        """The id of a live registered key, or None."""
+        kid = ctypes.c_uint32(0)
+        rc = self._L.fabgpu_p256_key_lookup(self._h, bytes(qx32), bytes(qy32), ctypes.byref(kid))
+        if rc < 0:
+            raise FabgpuError("fabgpu_p256_key_lookup: %s" % strerror(rc))
+        return int(kid.value) if rc == 0 else None
+
+    def key_unregister(self, key_id: int) -> bool:
+        """Retires a registered key (its slot and tables serve later registrations, under other ids).  False: the id was not live."""
+        rc = self._L.fabgpu_p256_key_unregister(self._h, int(key_id))
+        if rc < 0:
+            raise FabgpuError("fabgpu_p256_key_unregister: %s" % strerror(rc))
+        return rc == 0
+
+    def key_table_stats(self) -> dict:
+        v = (ctypes.c_uint64 * len(KEY_TABLE_STATS))()
+        n = self._L.fabgpu_p256_key_table_stats(self._h, v, len(KEY_TABLE_STATS))
+        if n != len(KEY_TABLE_STATS):
+            raise FabgpuError("fabgpu_p256_key_table_stats: %s" % strerror(n))
+        return dict(zip(KEY_TABLE_STATS, (int(x) for x in v)))
 
     def p256_verify_batch_keyed(self, key_id, e, r, s, want_status=True):
         e, r, s = map(_a8, (e, r, s))
@@ -704,12 +747,14 @@ class GPUCSP:
     """The accelerated verbs of bccsp.BCCSP (bccsp/bccsp.go:90-134); everything else the Go provider delegates to bccsp/sw."""
 
     def __init__(self, device: int = -1, devices: Optional[Sequence[int]] = None, flags: int = 0, concurrent_passes: int = 0,
-                 expect_block_bytes: int = 0, expect_tuples: int = 0, **switches):
+                 expect_block_bytes: int = 0, expect_tuples: int = 0, retire_evicted_keys: int = 0, **switches):
         """device: ONE context on that HIP ordinal (fabgpu_csp_new).  devices: one context per entry - an ordinal may repeat; an empty
         list means every visible device - behind ONE provider (fabgpu_csp_new2: what bccsp/factory builds from the `GPU:` section).
         switches: pass_device_walk / pass_stage_min_bytes / pass_device_memo / pass_host_counts / pass_timing / pass_hash_memo (0 default,
         > 0 on, < 0 off), hash_memo_blocks (host copies of blocks the digest memo keeps per device), audit_permille (0 .. 1000: the share
-        of digests / verdicts handed out that is re-computed on the CPU first; 0, the default: none - poison / poisoned / audit_stats)."""
+        of digests / verdicts handed out that is re-computed on the CPU first; 0, the default: none - poison / poisoned / audit_stats).
+        retire_evicted_keys (0, the default: off): an identity the cache evicts gives its device comb table up as well (set_option of the
+        same name; key_table_stats)."""
         L = load()
         h = _vp()
         err = ctypes.create_string_buffer(512)
@@ -730,6 +775,8 @@ class GPUCSP:
         if rc != FABGPU_OK:
             raise FabgpuError(err.value.decode() or strerror(rc))
         self._h, self._L = h, L
+        if retire_evicted_keys:
+            self.set_option("retire_evicted_keys", retire_evicted_keys)
 
     def device_count(self) -> int:
         """Device contexts behind this provider."""
@@ -791,6 +838,15 @@ class GPUCSP:
     def key_count(self, d: int = 0) -> int:
         """Number of public keys whose comb table is resident on device context d of the pool."""
         return self._L.fabgpu_p256_key_count(self._L.fabgpu_csp_ctx_of(self._h, d))
+
+    def key_table_stats(self, d: int = 0) -> dict:
+        """Key-table counters of device context d, and `retired`: keys this provider retired for evicted identities (retire_evicted_keys)."""
+        names = KEY_TABLE_STATS + ("retired",)
+        v = (ctypes.c_uint64 * len(names))()
+        n = self._L.fabgpu_csp_key_table_stats(self._h, d, v, len(names))
+        if n != len(names):
+            raise FabgpuError("fabgpu_csp_key_table_stats: %s" % strerror(n))
+        return dict(zip(names, (int(x) for x in v)))
 
     def key_import(self, raw, opts=None) -> ECDSAPublicKey:
         """KeyImport(raw, &bccsp.ECDSAGoPublicKeyImportOpts{}) (bccsp/sw/keyimport.go:103-112): raw = (X, Y)."""

@@ -65,6 +65,11 @@ type GPUOpts struct {
 	// on (gpu.go Provider.Poisoned; metrics fabgpu_audit_mismatches, fabgpu_poisoned).  Unset means 1 - one hit in a thousand, about
 	// thirty verdicts and thirty digests of a 10 000-transaction block; `AuditPermille: 0` switches the audit off, 1000 audits everything.
 	AuditPermille *int `mapstructure:"auditpermille" json:"auditpermille,omitempty" yaml:"AuditPermille,omitempty"`
+	// RetireEvictedKeys: an identity that the provider's identity cache evicts also gives up its comb table on every device
+	// (fabgpu_bccsp.h option "retire_evicted_keys"), so a peer whose clients come and go keeps registering the keys that are hot now;
+	// without it a context stops registering after 4096 keys and serves every later identity on the fresh-key kernels until the
+	// peer restarts.  Unset means true; `RetireEvictedKeys: false` keeps every table registered for the life of the process.
+	RetireEvictedKeys *bool `mapstructure:"retireevictedkeys" json:"retireevictedkeys,omitempty" yaml:"RetireEvictedKeys,omitempty"`
 }
 
 // DefaultAuditPermille is what GPUOpts.AuditPermille means when the `GPU:` section does not set it.
@@ -89,7 +94,7 @@ func (f *GPUFactory) Get(config *FactoryOpts) (bccsp.BCCSP, error) {
 	if err != nil {
 		return nil, errors.Wrapf(err, "Failed initializing the software BCCSP behind the GPU provider")
 	}
-	opts := gpu.Options{AuditPermille: DefaultAuditPermille}
+	opts := gpu.Options{AuditPermille: DefaultAuditPermille, RetireEvictedKeys: true}
 	if g := config.GPUOpts; g != nil {
 		if g.Device != nil {
 			if len(g.Devices) == 0 {
@@ -100,7 +105,10 @@ func (f *GPUFactory) Get(config *FactoryOpts) (bccsp.BCCSP, error) {
 		}
 		opts = gpu.Options{Devices: g.Devices, ConcurrentPasses: g.ConcurrentPasses, ExpectBlockBytes: g.ExpectBlockBytes,
 			ExpectTuples: g.ExpectTuples, MemoBlocks: g.MemoBlocks, HostWalk: g.HostWalk, PassTiming: g.PassTiming,
-			NoHashMemo: g.NoHashMemo, HashMemoBlocks: g.HashMemoBlocks, KeyTables16: g.KeyTables16, AuditPermille: DefaultAuditPermille}
+			NoHashMemo: g.NoHashMemo, HashMemoBlocks: g.HashMemoBlocks, KeyTables16: g.KeyTables16, AuditPermille: DefaultAuditPermille, RetireEvictedKeys: true}
+		if g.RetireEvictedKeys != nil {
+			opts.RetireEvictedKeys = *g.RetireEvictedKeys
+		}
 		if g.AuditPermille != nil {
 			if *g.AuditPermille < 0 || *g.AuditPermille > 1000 {
 				return nil, errors.Errorf("Invalid GPU opts: AuditPermille [%d] must be 0 .. 1000", *g.AuditPermille)

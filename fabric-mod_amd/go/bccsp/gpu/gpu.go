@@ -136,6 +136,9 @@ type Options struct {
 	// the provider at the first disagreement (hit h of a kind is audited iff h*permille/1000 != (h-1)*permille/1000: no randomness).
 	// GPUFactory passes 1 unless the operator says otherwise; 0 switches the audit off.  Idemix pseudonym entries are not audited.
 	AuditPermille int
+	// RetireEvictedKeys: identities the identity cache evicts give their device comb tables up (option "retire_evicted_keys";
+	// KeyTableStats, gauges bccsp_gpu_key_tables).  GPUFactory passes true unless the operator says otherwise.
+	RetireEvictedKeys bool
 }
 
 // SetCoalesce switches the coalesced device path for memo misses on or off (GPUOpts.CoalesceVerify in gpufactory.go).
@@ -253,6 +256,15 @@ func New(swCSP bccsp.BCCSP, opts Options) (bccsp.BCCSP, error) {
 	if rc := C.fabgpu_csp_new2(&o, &csp, (*C.char)(unsafe.Pointer(&errbuf[0])), C.size_t(len(errbuf))); rc != 0 {
 		return nil, errors.Errorf("Failed initializing GPU BCCSP: %s (%s)", C.GoString(C.fabgpu_strerror(rc)), C.GoString((*C.char)(unsafe.Pointer(&errbuf[0]))))
 	}
+	if opts.RetireEvictedKeys {
+		name := C.CString("retire_evicted_keys")
+		rc := C.fabgpu_csp_set_option(csp, name, 1, nil)
+		C.free(unsafe.Pointer(name))
+		if rc != 0 {
+			C.fabgpu_csp_free(csp)
+			return nil, errors.Errorf("Failed initializing GPU BCCSP: retire_evicted_keys: %s", C.GoString(C.fabgpu_strerror(rc)))
+		}
+	}
 	if opts.MemoBlocks > 0 {
 		// (peer.gossip.state.blockBufferSize blocks may be waiting for their validators: the memo must hold them all, or it drops the
 		// oldest - the block the committer needs next - and every block of a catch-up is passed twice)
@@ -347,6 +359,17 @@ func (p *Provider) AuditStats() (digest, verdict, direct, mismatches, skippedNym
 		return
 	}
 	return uint64(v[0]), uint64(v[1]), uint64(v[2]), uint64(v[3]), uint64(v[4]), time.Duration(v[5])
+}
+
+// KeyTableStats: the registered keys' tables on device context d - keys live, slots draining behind a retirement, registrations that
+// reused a retired slot, slots parked for good, bytes of device memory held - and the keys this provider has retired for evicted
+// identities (fabgpu_csp_key_table_stats).
+func (p *Provider) KeyTableStats(d int) (live, draining, reused, parked, bytesHeld, retired uint64) {
+	var v [8]C.uint64_t
+	if C.fabgpu_csp_key_table_stats(p.csp, C.int(d), &v[0], 8) != 8 {
+		return
+	}
+	return uint64(v[0]), uint64(v[1]), uint64(v[2]), uint64(v[3]), uint64(v[5]), uint64(v[7])
 }
 
 // be32 is big.Int.FillBytes for Go 1.14: the value as exactly 32 big-endian bytes (callers guarantee BitLen <= 256).
@@ -647,6 +670,11 @@ var (
 		Namespace: "fabgpu", Name: "audit_mismatches",
 		Help: "Results of the device that the provider's sampled CPU audit re-computed and found different (the first one poisons the provider)",
 	}
+	keyTablesOpts = metrics.GaugeOpts{
+		Namespace: "bccsp", Subsystem: "gpu", Name: "key_tables",
+		Help: "Comb tables of registered P-256 keys on the first device context: keys live, slots draining behind a retirement, keys retired for evicted identities, registrations that reused a retired slot, slots parked for good, bytes of device memory held",
+		LabelNames: []string{"what"}, StatsdFormat: "%{#fqname}.%{what}",
+	}
 	poisonedOpts = metrics.GaugeOpts{
 		Namespace: "fabgpu", Name: "poisoned",
 		Help: "1 once the GPU provider has retired itself after a CPU audit mismatch and serves everything from bccsp/sw, else 0",
@@ -659,6 +687,7 @@ type passMetrics struct {
 	routes, memo     metrics.Gauge
 	auditMismatches  metrics.Counter
 	poisoned         metrics.Gauge
+	keyTables        metrics.Gauge
 }
 
 func (m *passMetrics) passDone(d time.Duration, nTx, nSig, seeded int) {
@@ -688,6 +717,7 @@ func (p *Provider) RegisterMetrics(mp metrics.Provider, refresh time.Duration) {
 			duration: mp.NewHistogram(passDurationOpts), tx: mp.NewCounter(passTxOpts), sigs: mp.NewCounter(passSigOpts),
 			failed: mp.NewCounter(passFailedOpts), routes: mp.NewGauge(passRouteOpts), memo: mp.NewGauge(memoOpts),
 			auditMismatches: mp.NewCounter(auditMismatchOpts), poisoned: mp.NewGauge(poisonedOpts),
+			keyTables: mp.NewGauge(keyTablesOpts),
 		}
 		m.poisoned.Set(0)
 		if refresh <= 0 {
@@ -723,6 +753,13 @@ func (p *Provider) RegisterMetrics(mp metrics.Provider, refresh time.Duration) {
 				m.memo.With("what", "hash_misses").Set(float64(hm))
 				m.memo.With("what", "hash_blocks_held").Set(float64(hb))
 				m.memo.With("what", "hash_copies_refused").Set(float64(hr))
+				kl, kd, kr, kp, kb, kret := p.KeyTableStats(0)
+				m.keyTables.With("what", "live").Set(float64(kl))
+				m.keyTables.With("what", "draining").Set(float64(kd))
+				m.keyTables.With("what", "retired").Set(float64(kret))
+				m.keyTables.With("what", "reused").Set(float64(kr))
+				m.keyTables.With("what", "parked").Set(float64(kp))
+				m.keyTables.With("what", "bytes_held").Set(float64(kb))
 				if _, _, _, mm, _, _ := p.AuditStats(); mm > mismatchesSeen {
 					m.auditMismatches.Add(float64(mm - mismatchesSeen))
 					mismatchesSeen = mm

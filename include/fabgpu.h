@@ -133,15 +133,32 @@ int fabgpu_sha256_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* a
  * id verify with 64 mixed additions and no doublings (about 3.5x fewer instructions than a fresh key).  Verdicts are
  * bit-identical to fabgpu_p256_verify_batch on the same (key, e, r, s).
  * fabgpu_p256_key_register: idempotent per (qx, qy); FABGPU_EINVAL for a point that is not on P-256 (the KeyImport gate:
- * such keys stay with bccsp/sw), FABGPU_ENOMEM when FABGPU_MAX_KEYS tables exist.  A key id out of range in a batch
- * yields status 4 for that tuple. */
+ * such keys stay with bccsp/sw), FABGPU_ENOMEM when FABGPU_MAX_KEYS keys are LIVE (registered and not retired; with
+ * FABGPU_FLAG_KEY_TABLES_16BIT the 64 16-bit combs are a cap on live tables in the same way).
+ * A key id is an opaque 32-bit value: generation << 12 | slot.  A context that never retires a key hands out 0, 1, 2 ... in
+ * registration order.  fabgpu_p256_key_unregister retires a key: lookup no longer finds it, key_count no longer counts it, and its
+ * slot - with the next generation, so under a DIFFERENT id - and its tables serve a later registration once every launch that
+ * may still name the old id has finished (nothing is unmapped before fabgpu_shutdown).  An id never means two keys: a tuple that
+ * names an id out of range or a retired id gets that key's own verdict (a batch queued before the retirement always does) or
+ * status 4 ("use bccsp/sw"), never another key's verdict.  A stream handed to a keyed _dev entry point must be idle when the
+ * caller destroys it. */
 #define FABGPU_MAX_KEYS 4096
 int fabgpu_p256_key_register(fabgpu_ctx* ctx, const uint8_t* qx32, const uint8_t* qy32, uint32_t* key_id);
 /* The same key on n contexts - a provider that drives every GPU of the node (fabgpu_csp_new2) keeps each registered key's table on
  * each of them: built once on the host, uploaded n times.  key_ids[g] = the key's id on ctxs[g]. */
 int fabgpu_p256_key_register_many(fabgpu_ctx* const* ctxs, int n, const uint8_t* qx32, const uint8_t* qy32, uint32_t* key_ids);
 int fabgpu_p256_key_lookup(fabgpu_ctx* ctx, const uint8_t* qx32, const uint8_t* qy32, uint32_t* key_id); /* 0 found, 1 not registered */
-int fabgpu_p256_key_count(fabgpu_ctx* ctx);
+int fabgpu_p256_key_count(fabgpu_ctx* ctx);                      /* live keys */
+/* 0: retired; 1: the id is not live (never handed out, or retired before: idempotent).  Does not wait for the device. */
+int fabgpu_p256_key_unregister(fabgpu_ctx* ctx, uint32_t key_id);
+/* The key retired on each of n contexts, in the order given.  0: retired on all of them; 1: none of them had it; 2: retired on
+ * those that had it, but not all did - contexts that were meant to hold the same keys did not. */
+int fabgpu_p256_key_unregister_many(fabgpu_ctx* const* ctxs, int n, const uint8_t* qx32, const uint8_t* qy32);
+/* out[0 .. min(cap, FABGPU_KEY_TABLE_STATS)): live keys, slots draining (retired, not yet reusable), registrations that reused a
+ * slot, slots parked for good (their 2^20 generations are used up), live 16-bit tables, bytes of device memory the tables' slabs
+ * hold, slots ever used.  Returns FABGPU_KEY_TABLE_STATS. */
+#define FABGPU_KEY_TABLE_STATS 7
+int fabgpu_p256_key_table_stats(fabgpu_ctx* ctx, uint64_t* out, int cap);
 int fabgpu_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint32_t* key_id, const uint8_t* e, const uint8_t* r,
                                    const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
 int fabgpu_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* key_id, const void* e, const void* r, const void* s,

@@ -66,9 +66,17 @@ int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pa
  * "audit_permille" (0 .. 1000, FABGPU_EINVAL outside); get also
  * answers "n_devices" and two counters: "registrations_dropped" (key / issuer tables that could not be brought onto every device of the
  * pool after three attempts - those identities verify on the fresh-key kernels / bccsp/idemix) and "registration_id_mismatches".
+ * "retire_evicted_keys" (default off; > 0 on): an identity that the identity cache evicts (fabgpu_csp_identity_cache_limits) also gives
+ * up its device comb table - fabgpu_p256_key_unregister on every device of the pool, the same keys in the same order everywhere, so
+ * the devices keep agreeing on key ids - and a provider whose signers come and go keeps registering the hot ones for as long as it
+ * lives, where it otherwise stops after FABGPU_MAX_KEYS registrations.  Keys that came in through fabgpu_csp_key_import are never
+ * retired this way.
  * FABGPU_EINVAL: no such option. */
 int fabgpu_csp_set_option(fabgpu_csp* csp, const char* name, int64_t value, int64_t* previous);
 int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value);
+/* fabgpu_p256_key_table_stats of device context d, followed by (out[FABGPU_KEY_TABLE_STATS]) the number of keys the provider has
+ * retired for evicted identities; returns how many values there are (FABGPU_KEY_TABLE_STATS + 1; the first cap are written). */
+int fabgpu_csp_key_table_stats(fabgpu_csp* csp, int d, uint64_t* out, int cap);
 
 /* ---- CPU audit of device results, and poisoning ----
  * Digests and verdicts the provider hands out were computed by kernels; nothing outside the device checks them (a validator that takes
