@@ -1,4 +1,4 @@
-// CPU audit of device results (audit_host.h): SHA-256 in plain C++, ECDSA P-256 verification through the kernels' own one-lane header
+// CPU audit of device results (audit_host.h): SHA-256 in plain C++, SHA3-256 through sha3_256.h, ECDSA P-256 verification through the kernels' own one-lane header
 // code compiled for the host.  Linked into libfabgpu.so; nothing here touches a device.
 #include "audit_host.h"
 
@@ -9,6 +9,7 @@
 
 #include "bccsp_host.h"
 #include "p256_tables29.h"
+#include "sha3_256.h"
 
 namespace fab {
 namespace bccsp {
@@ -66,6 +67,9 @@ void audit_sha256(const uint8_t* msg, size_t len, uint8_t* out32) {
         out32[4 * i + 3] = (uint8_t)h[i];
     }
 }
+
+// SHA3-256 (FIPS 202): the stream code of the device's lanes over the caller's bytes
+void audit_sha3_256(const uint8_t* msg, size_t len, uint8_t* out32) { sha3_256_host(msg, len, out32); }
 
 // ------------------------------------------------------------------------------------------------
 // ECDSA P-256

@@ -16,6 +16,8 @@ namespace fab {
 namespace bccsp {
 
 void audit_sha256(const uint8_t* msg, size_t len, uint8_t* out32);
+// SHA3-256 through the kernels' own header (sha3_256.h) compiled for the host
+void audit_sha3_256(const uint8_t* msg, size_t len, uint8_t* out32);
 // bccsp.Verify(k, sig, digest) as bccsp/sw decides it (bccsp/sw/impl.go:247-270 -> ecdsa.go:41-57): true = (true, nil), false =
 // everything else - a signature that does not unmarshal, r or s <= 0, high S, r >= n, a key that is not on the curve, an empty
 // signature or digest, a signature that does not verify.

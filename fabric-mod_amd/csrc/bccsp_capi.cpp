@@ -218,8 +218,18 @@ int fabgpu_csp_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, const uint
 
 int fabgpu_csp_identity_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, const uint8_t* msg, size_t msglen,
                                          const uint8_t* sig, size_t siglen, char* err, size_t errcap) {
+    return fabgpu_csp_identity_verify_coalesced2(csp, qx32, qy32, msg, msglen, sig, siglen, "SHA2", err, errcap);
+}
+int fabgpu_csp_identity_verify_coalesced2(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, const uint8_t* msg, size_t msglen,
+                                          const uint8_t* sig, size_t siglen, const char* hash_family, char* err, size_t errcap) {
     if (!csp || (msglen && !msg)) return FABGPU_EINVAL;
     if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
+    bool sha3 = false;
+    std::string ferr;
+    if (!csp->csp->HashFamily(hash_family, &sha3, &ferr)) {
+        put_err(err, errcap, ferr);
+        return FABGPU_OK;
+    }
     ECDSAPublicKey k;
     const ECDSAPublicKey* kp = nullptr;
     if (qx32 && qy32) {
@@ -227,7 +237,7 @@ int fabgpu_csp_identity_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, c
         kp = &k;
     }
     bool infra = false;
-    std::string out = csp->csp->IdentityVerifyCoalesced(kp, msg, msglen, sig, siglen, &infra);
+    std::string out = csp->csp->IdentityVerifyCoalesced(kp, msg, msglen, sig, siglen, &infra, sha3);
     put_err(err, errcap, out);
     if (infra) return FABGPU_ELAUNCH;
     if (csp->csp->Poisoned()) {
@@ -274,8 +284,19 @@ int fabgpu_csp_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* qx, const 
 int fabgpu_csp_identity_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena,
                                      const uint32_t* msg_off, const uint8_t* sig_arena, const uint32_t* sig_off, char* errs,
                                      size_t errstride) {
+    return fabgpu_csp_identity_verify_batch2(csp, n, qx, qy, msg_arena, msg_off, sig_arena, sig_off, "SHA2", errs, errstride);
+}
+int fabgpu_csp_identity_verify_batch2(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena,
+                                      const uint32_t* msg_off, const uint8_t* sig_arena, const uint32_t* sig_off, const char* hash_family,
+                                      char* errs, size_t errstride) {
     if (!csp || (n && (!qx || !qy || !msg_off || !sig_off || !errs || !errstride))) return FABGPU_EINVAL;
     if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
+    bool sha3 = false;
+    std::string ferr;
+    if (!csp->csp->HashFamily(hash_family, &sha3, &ferr)) {               // identity.Verify fails before it hashes: every item, the same text
+        for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, ferr);
+        return FABGPU_OK;
+    }
     std::vector<ECDSAPublicKey> keys(n);
     std::vector<IdentityItem> items(n);
     for (size_t i = 0; i < n; i++) {
@@ -283,7 +304,7 @@ int fabgpu_csp_identity_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* q
         items[i] = {&keys[i], msg_arena + msg_off[i], msg_off[i + 1] - msg_off[i], sig_arena + sig_off[i], sig_off[i + 1] - sig_off[i]};
     }
     std::vector<std::string> out;
-    Error e = csp->csp->IdentityVerifyBatch(items, out);
+    Error e = csp->csp->IdentityVerifyBatch(items, out, sha3);
     if (!e.ok()) return FABGPU_ELAUNCH;
     for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, out[i]);
     return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;

@@ -225,6 +225,7 @@ Error GPUCSP::New(const ProviderOptions& opts, std::unique_ptr<GPUCSP>& out) {
     std::unique_ptr<GPUCSP> p(new GPUCSP());
     p->opts_ = opts;
     p->retire_evicted_.store(opts.retire_evicted_keys > 0, std::memory_order_relaxed);
+    p->hash_sha3_.store(opts.hash_sha3 > 0, std::memory_order_relaxed);
     p->opts_.devices = devices;
     p->audit_permille_.store(opts.audit_permille > 1000 ? 1000 : opts.audit_permille, std::memory_order_relaxed);
     for (int32_t ord : devices) {
@@ -277,7 +278,8 @@ const OptField kIntOpts[] = {{"pass_device_walk", &ProviderOptions::pass_device_
                              {"pass_skip_hash_checks", &ProviderOptions::pass_skip_hash_checks},
                              {"pass_timing", &ProviderOptions::pass_timing},
                              {"pass_hash_memo", &ProviderOptions::pass_hash_memo},
-                             {"retire_evicted_keys", &ProviderOptions::retire_evicted_keys}};
+                             {"retire_evicted_keys", &ProviderOptions::retire_evicted_keys},
+                             {"hash_sha3", &ProviderOptions::hash_sha3}};
 }  // namespace
 int64_t GPUCSP::SetOption(const std::string& name, int64_t value) const {
     std::lock_guard<std::mutex> lk(opt_mu_);
@@ -296,6 +298,7 @@ int64_t GPUCSP::SetOption(const std::string& name, int64_t value) const {
             const int64_t prev = opts_.*(o.f);
             opts_.*(o.f) = (int)value;
             if (name == "retire_evicted_keys") retire_evicted_.store(value > 0, std::memory_order_relaxed);
+            if (name == "hash_sha3") hash_sha3_.store(value > 0, std::memory_order_relaxed);
             return prev;
         }
     return INT64_MIN;
@@ -611,12 +614,29 @@ static bool all_registered(fabgpu_ctx* ctx, size_t n, const std::vector<uint8_t>
 // bccsp/sw/impl.go:177-194
 Error GPUCSP::Hash(const uint8_t* msg, size_t len, const HashOpts* opts, std::vector<uint8_t>& digest) const {
     if (opts == nullptr) return Error("Invalid opts. It must not be nil.");
-    if (opts->algorithm != "SHA256") return Error("Unsupported 'HashOpt' provided [" + opts->algorithm + "]");
+    const bool sha3 = opts->algorithm == "SHA3_256" && Sha3Enabled();       // (bccsp/sw/new.go:77: SHA3_256Opts -> sha3.New256)
+    if (opts->algorithm != "SHA256" && !sha3) return Error("Unsupported 'HashOpt' provided [" + opts->algorithm + "]");
     uint32_t off[2] = {0, (uint32_t)len};
     digest.assign(32, 0);
-    int rc = fabgpu_sha256_batch(flat_ctx(), 1, msg, off, digest.data());
-    if (rc != FABGPU_OK) return Error(std::string("Failed hashing with opts [SHA256]: ") + fabgpu_strerror(rc));
+    int rc = sha3 ? fabgpu_sha3_256_batch(flat_ctx(), 1, msg, off, digest.data()) : fabgpu_sha256_batch(flat_ctx(), 1, msg, off, digest.data());
+    if (rc != FABGPU_OK) return Error("Failed hashing with opts [" + opts->algorithm + "]: " + fabgpu_strerror(rc));
     return Error();
+}
+// msp/identities.go:216-224 getHashOpt
+bool GPUCSP::HashFamily(const char* family, bool* sha3, std::string* err) const {
+    const std::string f = family ? family : "";
+    *sha3 = false;
+    if (f == "SHA2") return true;
+    if (f == "SHA3") {
+        if (!Sha3Enabled()) {
+            if (err) *err = "failed computing digest: SHA3 is served by bccsp/sw, not by the GPU provider";
+            return false;
+        }
+        *sha3 = true;
+        return true;
+    }
+    if (err) *err = "hash familiy not recognized [" + f + "]";               // (the reference's spelling)
+    return false;
 }
 
 namespace {
@@ -751,7 +771,7 @@ VerifyResult GPUCSP::Verify(const ECDSAPublicKey* k, const uint8_t* sig, size_t 
 
 // msp/identities.go:169-196 over a flattened batch: digest = Hash(msg); Verify(pk, sig, digest); the hash is fused
 // into the verify kernel.  out[i]: "" (nil) or the error text identity.Verify would return.
-Error GPUCSP::IdentityVerifyBatch(const std::vector<IdentityItem>& items, std::vector<std::string>& out) const {
+Error GPUCSP::IdentityVerifyBatch(const std::vector<IdentityItem>& items, std::vector<std::string>& out, bool sha3) const {
     const size_t n = items.size();
     out.assign(n, std::string());
     if (n == 0) return Error();
@@ -784,16 +804,22 @@ Error GPUCSP::IdentityVerifyBatch(const std::vector<IdentityItem>& items, std::v
     off[n] = (uint32_t)arena.size();
     std::vector<uint32_t> ids;
     fabgpu_ctx* const ctx_ = flat_ctx();
-    int rc = all_registered(ctx_, n, submitted, qx.data(), qy.data(), ids)
-                 ? fabgpu_sha256_p256_verify_batch_keyed(ctx_, n, arena.data(), off.data(), ids.data(), r.data(), s.data(), bits.data(), st.data())
-                 : fabgpu_sha256_p256_verify_batch(ctx_, n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data());
+    if (sha3 && !Sha3Enabled()) return Error("SHA3 is served by bccsp/sw, not by the GPU provider");
+    const bool keyed = all_registered(ctx_, n, submitted, qx.data(), qy.data(), ids);
+    int rc;
+    if (sha3)   // an MSP of the SHA3 family: SHA3-256 launch, then the verify-only kernels over its digests (fabgpu.h)
+        rc = keyed ? fabgpu_sha3_256_p256_verify_batch_keyed(ctx_, n, arena.data(), off.data(), ids.data(), r.data(), s.data(), bits.data(), st.data())
+                   : fabgpu_sha3_256_p256_verify_batch(ctx_, n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data());
+    else
+        rc = keyed ? fabgpu_sha256_p256_verify_batch_keyed(ctx_, n, arena.data(), off.data(), ids.data(), r.data(), s.data(), bits.data(), st.data())
+                   : fabgpu_sha256_p256_verify_batch(ctx_, n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data());
     if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
     for (size_t i = 0; i < n; i++) {
         if (!submitted[i]) continue;
         bool ok = ((bits[i >> 6] >> (i & 63)) & 1) && st[i] == FABGPU_ST_VALID;
         out[i] = ok ? "" : "The signature is invalid";
         // as in VerifyBatch; a sampled message is hashed again first
-        if (ok && !AuditDirect(*items[i].key, items[i].sig, items[i].siglen, nullptr, 0, "identity.Verify", items[i].msg, items[i].msglen)) out[i] = PoisonedText();
+        if (ok && !AuditDirect(*items[i].key, items[i].sig, items[i].siglen, nullptr, 0, "identity.Verify", items[i].msg, items[i].msglen, sha3)) out[i] = PoisonedText();
     }
     return Error();
 }
@@ -831,7 +857,7 @@ VerifyResult GPUCSP::VerifyCoalesced(const ECDSAPublicKey* k, const uint8_t* sig
 }
 
 std::string GPUCSP::IdentityVerifyCoalesced(const ECDSAPublicKey* k, const uint8_t* msg, size_t msglen, const uint8_t* sig, size_t siglen,
-                                            bool* infrastructure) const {
+                                            bool* infrastructure, bool sha3) const {
     if (infrastructure) *infrastructure = false;
     static const uint8_t one_digest[1] = {1};
     Gate g = gate_item(k, sig, siglen, one_digest, 1);           // as in IdentityVerifyBatch: the digest is non-empty by construction
@@ -839,13 +865,14 @@ std::string GPUCSP::IdentityVerifyCoalesced(const ECDSAPublicKey* k, const uint8
     CoReqI req;
     req.item = {k, msg, msglen, sig, siglen};
     req.infra = false;
-    co_identity_.submit(&req, [this](std::vector<CoReqI*>& batch) {
+    // one queue per hash family: a launch hashes every message of its batch the same way
+    (sha3 ? co_identity_sha3_ : co_identity_).submit(&req, [this, sha3](std::vector<CoReqI*>& batch) {
         std::vector<std::string> out;
         Error e;
         try {
             std::vector<IdentityItem> items(batch.size());
             for (size_t i = 0; i < batch.size(); i++) items[i] = batch[i]->item;
-            e = IdentityVerifyBatch(items, out);
+            e = IdentityVerifyBatch(items, out, sha3);
         } catch (const std::exception& x) {
             e = Error(std::string("GPU verify failed: ") + x.what());
         }
@@ -861,15 +888,17 @@ std::string GPUCSP::IdentityVerifyCoalesced(const ECDSAPublicKey* k, const uint8
 void GPUCSP::CoalescerConfigure(uint32_t window_us, uint32_t max_batch) const {
     co_verify_.configure(window_us, max_batch);
     co_identity_.configure(window_us, max_batch);
+    co_identity_sha3_.configure(window_us, max_batch);
 }
 
 void GPUCSP::CoalescerStats(uint64_t* calls, uint64_t* launches, uint64_t* largest_batch) const {
-    uint64_t c[2], l[2], g[2];
+    uint64_t c[3], l[3], g[3];
     co_verify_.stats(&c[0], &l[0], &g[0]);
     co_identity_.stats(&c[1], &l[1], &g[1]);
-    if (calls) *calls = c[0] + c[1];
-    if (launches) *launches = l[0] + l[1];
-    if (largest_batch) *largest_batch = g[0] > g[1] ? g[0] : g[1];
+    co_identity_sha3_.stats(&c[2], &l[2], &g[2]);
+    if (calls) *calls = c[0] + c[1] + c[2];
+    if (launches) *launches = l[0] + l[1] + l[2];
+    if (largest_batch) *largest_batch = std::max(g[0], std::max(g[1], g[2]));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1137,14 +1166,15 @@ void GPUCSP::NoteUnauditedNym(uint64_t n) const {
     if (n && AuditPermille()) audit_count_[AUDIT_SKIPPED_NYM].fetch_add(n, std::memory_order_relaxed);
 }
 bool GPUCSP::AuditDirect(const ECDSAPublicKey& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
-                         const uint8_t* msg, size_t msglen) const {
+                         const uint8_t* msg, size_t msglen, bool sha3) const {
     if (!audit_sample_[AUDIT_DIRECT].hit(AuditPermille())) return true;
     bool accept;
     {
         AuditClock clk{audit_count_[AUDIT_NS]};
         uint8_t dg[32];
         if (msg || msglen) {
-            audit_sha256(msg, msglen, dg);
+            if (sha3) audit_sha3_256(msg, msglen, dg);          // the family the call hashed with
+            else audit_sha256(msg, msglen, dg);
             digest = dg;
             dlen = 32;
         }

@@ -141,6 +141,8 @@ struct ProviderOptions {
     uint32_t hash_memo_blocks = 0;     // per device: host copies of blocks kept at a time for the digest memo (0: 8; at most 64)
     int retire_evicted_keys = 0;       // > 0: an identity the cache evicts gives its device comb table up too (fabgpu_p256_key_unregister on every
                                        // device; default off: the table stays registered with the contexts)
+    int hash_sha3 = 0;                 // > 0: Hash serves SHA3_256Opts and identity.Verify an MSP of the SHA3 hash family on the device (SetOption
+                                       // of the same name; default off: "Unsupported 'HashOpt' provided [SHA3_256]", as bccsp/sw is asked then)
     uint32_t audit_permille = 0;       // share of the digests / verdicts handed out that is re-computed on the CPU first (0 .. 1000; 0: none)
 };
 constexpr int kMaxProviderDevices = 64;   // contexts per provider (8 GPUs x up to 8 contexts each)
@@ -178,13 +180,18 @@ class GPUCSP {
     void HashMemoStats(uint64_t* hits, uint64_t* misses, uint64_t* blocks_held, uint64_t* bytes_held, uint64_t* refused) const;
     VerifyResult Verify(const ECDSAPublicKey* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) const;
     Error VerifyBatch(const std::vector<VerifyItem>& items, std::vector<VerifyResult>& results) const;
-    Error IdentityVerifyBatch(const std::vector<IdentityItem>& items, std::vector<std::string>& out) const;
+    // sha3: the MSP's SignatureHashFamily is SHA3 - digest = SHA3-256(msg) (msp/identities.go:216-224); needs the hash_sha3 option
+    Error IdentityVerifyBatch(const std::vector<IdentityItem>& items, std::vector<std::string>& out, bool sha3 = false) const;
+    // "SHA2" / "SHA3" -> *sha3; anything else: false, and *err holds identity.getHashOpt's text.  "SHA3" with the hash_sha3 option off:
+    // false, and *err says who serves it.
+    bool HashFamily(const char* family, bool* sha3, std::string* err) const;
+    bool Sha3Enabled() const { return hash_sha3_.load(std::memory_order_relaxed); }
     // The same two one-signature verbs for callers that arrive MANY AT A TIME on their own threads (orderer Broadcast handlers behind
     // SigFilter, validator goroutines on memo misses): blocking, same answers, calls in flight together share a launch (coalescer.h).
     VerifyResult VerifyCoalesced(const ECDSAPublicKey* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) const;
     // identity.Verify(msg, sig): "" (nil) or the error text; *infrastructure = true when the device failed (no verdict)
     std::string IdentityVerifyCoalesced(const ECDSAPublicKey* k, const uint8_t* msg, size_t msglen, const uint8_t* sig, size_t siglen,
-                                        bool* infrastructure) const;
+                                        bool* infrastructure, bool sha3 = false) const;
     void CoalescerConfigure(uint32_t window_us, uint32_t max_batch) const;
     void CoalescerStats(uint64_t* calls, uint64_t* launches, uint64_t* largest_batch) const;
     // Block-level pre-verify pass (block_prepass.h): one fused launch for every creator / endorsement signature of the block.
@@ -294,7 +301,7 @@ class GPUCSP {
     // true: the device's "valid" for this signature stands (not sampled, or the CPU agrees); false: the provider is now poisoned.
     // msg != nullptr: the digest is SHA-256(msg), computed here (identity.Verify)
     bool AuditDirect(const ECDSAPublicKey& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
-                     const uint8_t* msg = nullptr, size_t msglen = 0) const;
+                     const uint8_t* msg = nullptr, size_t msglen = 0, bool sha3 = false) const;
     // Every lookup of every validator thread READS the two switches and, while auditing is on, BUMPS its kind's hit counter: the
     // switches share a cache line nobody writes, each counter has a line of its own (the memo's counters are sharded for the same
     // reason - reader_lock.h - but a sampling rule that is exact over all threads needs ONE counter per kind).
@@ -378,6 +385,7 @@ class GPUCSP {
     void FlushRetirements() const;
     void FlushRetirementsRegLocked() const;
     mutable std::atomic<bool> retire_evicted_{false};
+    mutable std::atomic<bool> hash_sha3_{false};             // the hash_sha3 option
     mutable std::mutex retire_mu_;                           // retire_queue_, imported_keys_ (a leaf: nothing is taken under it)
     mutable std::vector<std::string> retire_queue_;          // qx || qy
     mutable std::set<std::string> imported_keys_;
@@ -483,6 +491,7 @@ class GPUCSP {
     };
     mutable Coalescer<CoReqV> co_verify_;
     mutable Coalescer<CoReqI> co_identity_;
+    mutable Coalescer<CoReqI> co_identity_sha3_;                      // a launch hashes with ONE family: SHA3 callers queue apart
     mutable std::mutex pass_mu_;                                      // guards scratch_free_
     mutable std::vector<std::unique_ptr<PassScratch>> scratch_free_;
 };

@@ -1650,6 +1650,146 @@ int fabgpu_sha256_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8
     return FABGPU_OK;
 }
 
+// ---- SHA3-256 (sha3_kernels.hip): an MSP of the SHA3 hash family (msp/identities.go:216-224) ---------------------------------
+// Hash, then verify: two launches on one stream.  The SHA3 launch writes its digests into a context-owned n x 32 byte device buffer -
+// one of the pooled workspaces, under their rule (acquire_qws: reserved until an event is recorded behind the launch that read it) -
+// and the unchanged verify-only entry point consumes that buffer as `e`: the digest never leaves the chip, and the verify kernel is
+// chosen by n and the context's flags exactly as for a caller who brings digests.
+int fabgpu_sha3_256_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, void* stream) {
+    if (!ctx || (n && (!arena || !off || !digests))) return FABGPU_EINVAL;
+    if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
+    hipError_t err = launch_sha3_256_batch((uint32_t)n, arena, arena_bytes, off, false, digests, st);
+    if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
+    ctx->timed = ctx->time_kernels;
+    return hip_to_rc(launched(ctx, err));
+}
+
+// the digests of a (possibly prefixed) batch into `dig`, then the verify-only entry point over them; key_id == nullptr: fresh keys
+static int sha3_then_verify_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, ShaPrefixArgs pa, const void* qx,
+                                const void* qy, const void* key_id, const void* r, const void* s, void* verdict_bits, void* status, hipStream_t st) {
+    size_t di = 0;
+    void* dig = pa.digests;
+    const bool pooled = dig == nullptr;
+    if (pooled) {
+        int rc = ctx->acquire_qws(n * 32, &di, &dig, st);
+        if (rc != FABGPU_OK) return rc;
+    }
+    hipError_t err = hipSuccess;
+    if (pa.m && pa.pre_idx && !pa.mid_ready) err = launch_sha3_256_midstates(arena, arena_bytes, pa, st);
+    pa.digests = dig;
+    if (err == hipSuccess) err = launch_sha3_256_messages((uint32_t)n, arena, arena_bytes, off, pa, st);
+    int rc = hip_to_rc(launched(ctx, err));
+    if (rc == FABGPU_OK)
+        rc = key_id ? fabgpu_p256_verify_batch_keyed_dev(ctx, n, key_id, dig, r, s, verdict_bits, status, st)
+                    : fabgpu_p256_verify_batch_dev(ctx, n, qx, qy, dig, r, s, verdict_bits, status, st);
+    if (pooled) ctx->release_qws(di, st);
+    return rc;
+}
+
+int fabgpu_sha3_256_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, const void* qx,
+                                          const void* qy, const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
+    if (!ctx || (n && (!arena || !off || !qx || !qy || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    DeviceGuard g(ctx->device);
+    return sha3_then_verify_dev(ctx, n, arena, arena_bytes, off, ShaPrefixArgs(), qx, qy, nullptr, r, s, verdict_bits, status, (hipStream_t)stream);
+}
+
+int fabgpu_sha3_256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, const void* key_id,
+                                                const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
+    if (!ctx || (n && (!arena || !off || !key_id || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    DeviceGuard g(ctx->device);
+    return sha3_then_verify_dev(ctx, n, arena, arena_bytes, off, ShaPrefixArgs(), nullptr, nullptr, key_id, r, s, verdict_bits, status, (hipStream_t)stream);
+}
+
+int fabgpu_sha3_256_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, uint8_t* digests) {
+    if (!ctx || (n && (!off || !digests))) return FABGPU_EINVAL;
+    if (n > 0x7FFFFFF0ull / 32) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    size_t ab = 0;
+    int rc = stage_messages(ctx, n, arena, off, &ab);
+    if (rc) return rc;
+    if ((rc = ctx->out.ensure(n * 32))) return rc;
+    rc = fabgpu_sha3_256_batch_dev(ctx, n, ctx->arena.d, ab, ctx->offs.d, ctx->out.d, ctx->stream);
+    if (rc) return rc;
+    hipError_t err = hipMemcpyAsync(ctx->out.h, ctx->out.d, n * 32, hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+    if (err != hipSuccess) return hip_to_rc(err);
+    memcpy(digests, ctx->out.h, n * 32);
+    return FABGPU_OK;
+}
+
+int fabgpu_sha3_256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx, const uint8_t* qy,
+                                      const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    if (!ctx || (n && (!off || !qx || !qy || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    size_t ab = 0;
+    int rc = stage_messages(ctx, n, arena, off, &ab);
+    if (rc) return rc;
+    const size_t fb = n * 32, words = (n + 63) / 64;
+    const size_t st_off = round_up(words * 8, 64);
+    if ((rc = ctx->fields.ensure(4 * fb)) || (rc = ctx->out.ensure(st_off + n))) return rc;
+    uint8_t* h = (uint8_t*)ctx->fields.h;
+    memcpy(h, qx, fb); memcpy(h + fb, qy, fb); memcpy(h + 2 * fb, r, fb); memcpy(h + 3 * fb, s, fb);
+    uint8_t* d = (uint8_t*)ctx->fields.d;
+    uint8_t* dout = (uint8_t*)ctx->out.d;
+    hipError_t err = hipMemcpyAsync(d, h, 4 * fb, hipMemcpyHostToDevice, ctx->stream);
+    if (err != hipSuccess) return hip_to_rc(err);
+    rc = fabgpu_sha3_256_p256_verify_batch_dev(ctx, n, ctx->arena.d, ab, ctx->offs.d, d, d + fb, d + 2 * fb, d + 3 * fb, dout,
+                                               status ? dout + st_off : nullptr, ctx->stream);
+    if (rc) return rc;
+    err = hipMemcpyAsync(ctx->out.h, dout, status ? st_off + n : words * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+    if (err != hipSuccess) return hip_to_rc(err);
+    memcpy(verdict_bits, ctx->out.h, words * 8);
+    if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
+    return FABGPU_OK;
+}
+
+int fabgpu_sha3_256_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
+                                            const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    if (!ctx || (n && (!off || !key_id || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    size_t ab = 0;
+    int rc = stage_messages(ctx, n, arena, off, &ab);
+    if (rc) return rc;
+    const size_t fb = n * 32, kb = round_up(n * 4, 64), words = (n + 63) / 64;
+    const size_t st_off = round_up(words * 8, 64);
+    if ((rc = ctx->keyed.ensure(kb + 2 * fb)) || (rc = ctx->out.ensure(st_off + n))) return rc;
+    uint8_t* h = (uint8_t*)ctx->keyed.h;
+    memcpy(h, key_id, n * 4); memcpy(h + kb, r, fb); memcpy(h + kb + fb, s, fb);
+    uint8_t* d = (uint8_t*)ctx->keyed.d;
+    uint8_t* dout = (uint8_t*)ctx->out.d;
+    hipError_t err = hipMemcpyAsync(d, h, kb + 2 * fb, hipMemcpyHostToDevice, ctx->stream);
+    if (err != hipSuccess) return hip_to_rc(err);
+    rc = fabgpu_sha3_256_p256_verify_batch_keyed_dev(ctx, n, ctx->arena.d, ab, ctx->offs.d, d, d + kb, d + kb + fb, dout,
+                                                     status ? dout + st_off : nullptr, ctx->stream);
+    if (rc) return rc;
+    err = hipMemcpyAsync(ctx->out.h, dout, status ? st_off + n : words * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+    if (err != hipSuccess) return hip_to_rc(err);
+    memcpy(verdict_bits, ctx->out.h, words * 8);
+    if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
+    return FABGPU_OK;
+}
+
 // ---- identity.Verify over a described batch: optional shared prefixes, fresh or registered keys ------------------------
 int fabgpu_identity_verify_batch_dev(fabgpu_ctx* ctx, const fabgpu_identity_batch* b, void* mid_scratch, void* stream) {
     if (!ctx || !b) return FABGPU_EINVAL;
@@ -1659,7 +1799,7 @@ int fabgpu_identity_verify_batch_dev(fabgpu_ctx* ctx, const fabgpu_identity_batc
     const bool prefixed = b->n_prefixes != 0 && b->pre_idx != nullptr;
     if (!b->arena || !b->off || !b->r || !b->s || !b->verdict_bits || (!keyed && (!b->qx || !b->qy))) return FABGPU_EINVAL;
     if (prefixed && (!b->pre_off || !mid_scratch)) return FABGPU_EINVAL;
-    if (b->flags & ~(uint32_t)FABGPU_IDB_SPANS) return FABGPU_EINVAL;
+    if (b->flags & ~(uint32_t)(FABGPU_IDB_SPANS | FABGPU_IDB_SHA3_256)) return FABGPU_EINVAL;
     if (n > 0xFFFFFFF0ull || b->arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
     if (b->n_gather && (!b->gather_spans || !b->gather_digests || !b->gather_off || !b->gather_scratch || b->gather_scratch_bytes > 0xFFFFFFFFull))
         return FABGPU_EINVAL;
@@ -1675,6 +1815,17 @@ int fabgpu_identity_verify_batch_dev(fabgpu_ctx* ctx, const fabgpu_identity_batc
     DeviceGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
     hipError_t err;
+    if (b->flags & FABGPU_IDB_SHA3_256) {
+        // messages and prefixes under SHA3-256 (mid_scratch: n_prefixes x 200 bytes), the verification over the digests; the gathered
+        // digests stay SHA-256 - TxID and proposal hash are SHA-256 whatever the MSP's family (protoutil/proputils.go:357-375)
+        int rc = sha3_then_verify_dev(ctx, n, b->arena, b->arena_bytes, b->off, pa, b->qx, b->qy, b->key_id, b->r, b->s, b->verdict_bits, b->status, st);
+        if (rc != FABGPU_OK) return rc;
+        err = hipSuccess;
+        if (b->n_gather)
+            err = launch_gather_sha256(b->n_gather, b->arena, b->arena_bytes, b->gather_spans, b->gather_off, b->gather_scratch, b->gather_scratch_bytes,
+                                       b->gather_digests, st);
+        return hip_to_rc(err);
+    }
     VerifyLaunch v;
     v.n = (uint32_t)n;
     v.arena = b->arena; v.arena_bytes = b->arena_bytes; v.off = b->off; v.pa = pa;
@@ -1969,7 +2120,8 @@ int fabgpu_identity_verify_batch(fabgpu_ctx* ctx, const fabgpu_identity_batch* b
     const uint8_t* arena = (const uint8_t*)b->arena;
     const bool spans = (b->flags & FABGPU_IDB_SPANS) != 0;
     const bool staged = (b->flags & FABGPU_IDB_ARENA_STAGED) != 0;
-    if (b->flags & ~(uint32_t)(FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED)) return FABGPU_EINVAL;
+    if (b->flags & ~(uint32_t)(FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED | FABGPU_IDB_SHA3_256)) return FABGPU_EINVAL;
+    const size_t mid_bytes = (b->flags & FABGPU_IDB_SHA3_256) ? 200 : 32;   // a SHA3-256 mid-state is the whole Keccak state
     const size_t nn = b->n_nym;            // pseudonym signatures over the same arena, on the second stream
     if (nn && (!spans || !b->nym_off || !b->nym_issuer || !b->nym_fields || !b->nym_verdict_bits)) return FABGPU_EINVAL;
     if (nn > 0x7FFFFFF0ull / 200) return FABGPU_ETOOBIG;
@@ -2058,7 +2210,7 @@ int fabgpu_identity_verify_batch(fabgpu_ctx* ctx, const fabgpu_identity_batch* b
     const size_t dg_off = round_up(st_off + n, 64);        // out buffer: verdict words | status bytes | digests
     int rc;
     if ((!staged && (rc = ctx->arena.ensure(ab + 64))) || (rc = ctx->offs.ensure(noff * 4)) || (rc = ctx->fields.ensure(4 * fb + ib)) ||
-        (rc = ctx->out.ensure(dg_off + (b->digests ? fb : 0))) || (rc = ctx->pre.ensure(pob + ib + (size_t)m * 32 + 64)))
+        (rc = ctx->out.ensure(dg_off + (b->digests ? fb : 0))) || (rc = ctx->pre.ensure(pob + ib + (size_t)m * mid_bytes + 64)))
         return rc;
     // small arenas go through the pinned staging buffer; big ones (a marshalled block) are handed to the driver directly -
     // one copy less on the host (the tail padding the kernels may touch is zeroed on the device)
@@ -2126,7 +2278,7 @@ int fabgpu_identity_verify_batch(fabgpu_ctx* ctx, const fabgpu_identity_batch* b
     uint8_t* pd = (uint8_t*)ctx->pre.d;
     uint8_t* dout = (uint8_t*)ctx->out.d;
     fabgpu_identity_batch d = *b;
-    d.flags = b->flags & FABGPU_IDB_SPANS;
+    d.flags = b->flags & (FABGPU_IDB_SPANS | FABGPU_IDB_SHA3_256);
     d.arena = staged ? sl->d : ctx->arena.d;
     d.arena_bytes = staged ? round_up(tail_used ? (size_t)tbase + b->tail_len : span, 4) + 64 : ab;
     d.tail = nullptr;

@@ -16,6 +16,7 @@
 #include "coalescer.h"
 #include "pass_route.h"
 #include "block_walk_core.h"
+#include "sha3_256.h"
 
 using namespace fab;
 
@@ -434,5 +435,20 @@ int hosttest_cert_key_offset_window(const uint8_t* der, size_t avail, size_t len
 // the digest memo's slot choice (block_walk_core.h msg_fingerprint) over the message a || b
 uint64_t fabgpu_hosttest_msg_fingerprint(const uint8_t* a, uint32_t alen, const uint8_t* b, uint32_t blen) {
     return bccsp::walk::msg_fingerprint(a, alen, b, blen);
+}
+// SHA3-256 over sha3_256.h compiled for the host: the stream code the kernels run, on a byte buffer
+void hosttest_sha3_256(const uint8_t* msg, size_t len, uint8_t* out32) { sha3_256_host(msg, len, out32); }
+// the 200-byte state after the whole 136-byte blocks of a prefix
+void hosttest_sha3_256_midstate(const uint8_t* prefix, size_t plen, uint8_t* out200) { sha3_256_host_midstate(prefix, plen, out200); }
+// mid-state of the prefix, then the prefix's leftover bytes followed by msg.  The message sits BEFORE the prefix in the buffer the stream
+// reads, three bytes in: its virtual start (start - leftover) is then negative or misaligned against the prefix, as in a marshalled block.
+void hosttest_sha3_256_prefixed(const uint8_t* prefix, size_t plen, const uint8_t* msg, size_t len, uint8_t* out32) {
+    uint8_t mid[200];
+    sha3_256_host_midstate(prefix, plen, mid);
+    std::vector<uint8_t> buf(3 + len + 5 + plen, 0xA5);
+    if (len) memcpy(buf.data() + 3, msg, len);
+    if (plen) memcpy(buf.data() + 3 + len + 5, prefix, plen);
+    const uint32_t base = (uint32_t)(plen / SHA3_256_RATE) * SHA3_256_RATE;
+    sha3_256_host_stream(buf.data(), buf.size(), mid, (uint32_t)(3 + len + 5) + base, (uint32_t)plen - base, 3, (uint32_t)len, out32);
 }
 }

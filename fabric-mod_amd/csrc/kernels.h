@@ -106,6 +106,16 @@ hipError_t launch_sha256_mixed(uint32_t n, const void* arena, size_t arena_bytes
 hipError_t launch_sha256_messages_coop(uint32_t n, const void* arena, size_t arena_bytes, const void* off, const ShaPrefixArgs& pa, hipStream_t st,
                                        uint32_t lds_spread = 0);
 
+// ---- sha3_kernels.hip: SHA3-256 (sha3_256.h), one message per lane at every size ----
+// A mid-state is the whole 200-byte Keccak state: pa.mid_scratch must be m x SHA3_MID_BYTES (8-byte aligned) for these three.
+constexpr size_t SHA3_MID_BYTES_HOST = 200;
+hipError_t launch_sha3_256_midstates(const void* arena, size_t arena_bytes, const ShaPrefixArgs& pa, hipStream_t st);
+// n (possibly prefixed: the mid-states must be in pa.mid_scratch) messages -> pa.digests (n x 32 bytes)
+hipError_t launch_sha3_256_messages(uint32_t n, const void* arena, size_t arena_bytes, const void* off, const ShaPrefixArgs& pa, hipStream_t st);
+// spans: off holds (start, end) pairs instead of n + 1 consecutive offsets
+hipError_t launch_sha3_256_batch(uint32_t n, const void* arena, size_t arena_bytes, const void* off, bool spans, void* digests, hipStream_t st);
+int warm_kernel_functions_sha3();
+
 // ---- idemix_kernels.hip: idemix pseudonym signatures on FP256BN ----
 // A registered issuer occupies one slot of idemix_issuer_dev_bytes() bytes in a device array; fill a host copy of the slot
 // with idemix_issuer_dev_fill (device pointers of the two comb tables + ipk.Hash) and copy it up.

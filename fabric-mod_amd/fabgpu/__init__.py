@@ -25,6 +25,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("FABGPU_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libfabgpu.so")
 
 FABGPU_OK = 0
+IDB_SHA3_256 = 4          # fabgpu.h FABGPU_IDB_SHA3_256
 FABGPU_EINVAL = -1
 FABGPU_EPOISONED = -6    # fabgpu.h: the provider's CPU audit disagreed with the device once; it serves nothing any more
 FLAG_ONE_LANE_ONLY = 1   # fabgpu.h FABGPU_FLAG_ONE_LANE_ONLY
@@ -115,6 +116,8 @@ ABI_SYMBOLS = [
     "fabgpu_p256_verify_batch_dev", "fabgpu_sha256_batch_dev", "fabgpu_sha256_p256_verify_batch_dev",
     "fabgpu_p256_key_register", "fabgpu_p256_key_lookup", "fabgpu_p256_key_count", "fabgpu_p256_verify_batch_keyed", "fabgpu_p256_verify_batch_keyed_dev",
     "fabgpu_sha256_p256_verify_batch_keyed", "fabgpu_sha256_p256_verify_batch_keyed_dev",
+    "fabgpu_sha3_256_batch", "fabgpu_sha3_256_batch_dev", "fabgpu_sha3_256_p256_verify_batch", "fabgpu_sha3_256_p256_verify_batch_dev",
+    "fabgpu_sha3_256_p256_verify_batch_keyed", "fabgpu_sha3_256_p256_verify_batch_keyed_dev",
     "fabgpu_identity_verify_batch", "fabgpu_identity_verify_batch_dev", "fabgpu_arena_stage",
     "fabgpu_idemix_issuer_register", "fabgpu_idemix_issuer_count", "fabgpu_idemix_nym_verify_batch", "fabgpu_idemix_nym_verify_batch_dev",
     "fabgpu_bn256_g1_on_curve",
@@ -124,6 +127,7 @@ ABI_SYMBOLS = [
     "fabgpu_csp_verify_batch", "fabgpu_csp_identity_verify_batch", "fabgpu_csp_block_preverify", "fabgpu_block_parse", "fabgpu_x509_p256_pubkey",
     "fabgpu_csp_idemix_issuer_import", "fabgpu_csp_idemix_nym_verify_batch", "fabgpu_csp_idemix_msp_register", "fabgpu_csp_idemix_msp_register2", "fabgpu_block_hash_checks",
     "fabgpu_block_tuples", "fabgpu_csp_block_preverify2", "fabgpu_csp_block_pass_abandon", "fabgpu_idemix_issuer_key_is_canonical", "fabgpu_csp_memo_lookup", "fabgpu_csp_memo_lookup_nym", "fabgpu_csp_memo_has_block", "fabgpu_csp_memo_evict_block",
+    "fabgpu_csp_identity_verify_batch2", "fabgpu_csp_identity_verify_coalesced2",
     "fabgpu_csp_verify_coalesced", "fabgpu_csp_identity_verify_coalesced", "fabgpu_csp_coalescer_configure", "fabgpu_csp_coalescer_stats",
     "fabgpu_csp_memo_stats", "fabgpu_csp_memo_set_capacity", "fabgpu_csp_identity_cache_limits", "fabgpu_csp_identity_cache_size",
     "fabgpu_multi_init", "fabgpu_multi_shutdown", "fabgpu_multi_device_count", "fabgpu_multi_p256_verify_batch",
@@ -240,6 +244,13 @@ def load():
     L.fabgpu_p256_verify_batch_keyed_dev.argtypes = [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.fabgpu_sha256_p256_verify_batch_keyed.argtypes = [_vp, _sz, _u8p, _u32p, _u32p, _u8p, _u8p, _u64p, _u8p]
     L.fabgpu_sha256_p256_verify_batch_keyed_dev.argtypes = [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    # SHA3-256: the argument lists of the sha256 namesakes
+    L.fabgpu_sha3_256_batch.argtypes = L.fabgpu_sha256_batch.argtypes
+    L.fabgpu_sha3_256_batch_dev.argtypes = L.fabgpu_sha256_batch_dev.argtypes
+    L.fabgpu_sha3_256_p256_verify_batch.argtypes = L.fabgpu_sha256_p256_verify_batch.argtypes
+    L.fabgpu_sha3_256_p256_verify_batch_dev.argtypes = L.fabgpu_sha256_p256_verify_batch_dev.argtypes
+    L.fabgpu_sha3_256_p256_verify_batch_keyed.argtypes = L.fabgpu_sha256_p256_verify_batch_keyed.argtypes
+    L.fabgpu_sha3_256_p256_verify_batch_keyed_dev.argtypes = L.fabgpu_sha256_p256_verify_batch_keyed_dev.argtypes
     L.fabgpu_arena_stage.argtypes = [_vp, _u8p, _sz, ctypes.POINTER(ctypes.c_uint64)]
     L.fabgpu_identity_verify_batch.argtypes = [_vp, ctypes.POINTER(_IdBatch)]
     L.fabgpu_identity_verify_batch_dev.argtypes = [_vp, ctypes.POINTER(_IdBatch), _vp, _vp]
@@ -274,6 +285,9 @@ def load():
     L.fabgpu_csp_verify_batch.argtypes = [_vp, _sz, _u8p, _u8p, _u8p, _u32p, _u8p, _u32p, _u8p, ctypes.c_char_p, _sz]
     L.fabgpu_csp_verify_coalesced.argtypes = L.fabgpu_csp_verify.argtypes
     L.fabgpu_csp_identity_verify_coalesced.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz]
+    L.fabgpu_csp_identity_verify_coalesced2.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.c_char_p,
+                                                        ctypes.c_char_p, _sz]
+    L.fabgpu_csp_identity_verify_batch2.argtypes = [_vp, _sz, _u8p, _u8p, _u8p, _u32p, _u8p, _u32p, ctypes.c_char_p, ctypes.c_char_p, _sz]
     L.fabgpu_csp_coalescer_configure.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32]
     L.fabgpu_csp_coalescer_stats.argtypes = [_vp, _u64p, _u64p, _u64p]
     L.fabgpu_csp_identity_verify_batch.argtypes = [_vp, _sz, _u8p, _u8p, _u8p, _u32p, _u8p, _u32p, ctypes.c_char_p, _sz]
@@ -451,6 +465,44 @@ class Context:
         _check(self._L.fabgpu_sha256_p256_verify_batch_dev(self._h, n, arena, arena_bytes, off, qx, qy, r, s, verdict_bits,
                                                             status or None, stream or None), "fabgpu_sha256_p256_verify_batch_dev")
 
+    # SHA3-256 (an MSP of the SHA3 hash family): the sha256 namesakes' shapes
+    def sha3_256_batch(self, arena, off):
+        arena = _a8(arena)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        n = off.size - 1
+        out = np.zeros((n, 32), dtype=np.uint8)
+        _check(self._L.fabgpu_sha3_256_batch(self._h, n, _p8(arena), off.ctypes.data_as(_u32p), _p8(out)), "fabgpu_sha3_256_batch")
+        return out
+
+    def sha3_256_p256_verify_batch(self, arena, off, qx=None, qy=None, r=None, s=None, key_id=None, want_status=True):
+        """Fresh keys (qx, qy) or registered ones (key_id)."""
+        arena, r, s = map(_a8, (arena, r, s))
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        n = off.size - 1
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8) if want_status else None
+        if key_id is not None:
+            key_id = np.ascontiguousarray(key_id, dtype=np.uint32)
+            _check(self._L.fabgpu_sha3_256_p256_verify_batch_keyed(self._h, n, _p8(arena), off.ctypes.data_as(_u32p), key_id.ctypes.data_as(_u32p),
+                                                                    _p8(r), _p8(s), bits.ctypes.data_as(_u64p), _p8(st)),
+                   "fabgpu_sha3_256_p256_verify_batch_keyed")
+        else:
+            qx, qy = _a8(qx), _a8(qy)
+            _check(self._L.fabgpu_sha3_256_p256_verify_batch(self._h, n, _p8(arena), off.ctypes.data_as(_u32p), _p8(qx), _p8(qy), _p8(r),
+                                                              _p8(s), bits.ctypes.data_as(_u64p), _p8(st)), "fabgpu_sha3_256_p256_verify_batch")
+        return unpack_bits(bits, n), st
+
+    def sha3_256_batch_dev(self, n, arena, arena_bytes, off, digests, stream=0):
+        _check(self._L.fabgpu_sha3_256_batch_dev(self._h, n, arena, arena_bytes, off, digests, stream or None), "fabgpu_sha3_256_batch_dev")
+
+    def sha3_256_p256_verify_batch_dev(self, n, arena, arena_bytes, off, qx, qy, r, s, verdict_bits, status, stream=0):
+        _check(self._L.fabgpu_sha3_256_p256_verify_batch_dev(self._h, n, arena, arena_bytes, off, qx, qy, r, s, verdict_bits,
+                                                              status or None, stream or None), "fabgpu_sha3_256_p256_verify_batch_dev")
+
+    def sha3_256_p256_verify_batch_keyed_dev(self, n, arena, arena_bytes, off, key_id, r, s, verdict_bits, status, stream=0):
+        _check(self._L.fabgpu_sha3_256_p256_verify_batch_keyed_dev(self._h, n, arena, arena_bytes, off, key_id, r, s, verdict_bits,
+                                                                    status or None, stream or None), "fabgpu_sha3_256_p256_verify_batch_keyed_dev")
+
     # registered public keys (bccsp.KeyImport): a comb table per key on the device, verification without doublings
     def key_register(self, qx32: bytes, qy32: bytes) -> int:
         kid = ctypes.c_uint32(0)
@@ -547,19 +599,21 @@ class Context:
         return int(tok.value)
 
     def identity_verify_batch(self, arena, off, r, s, qx=None, qy=None, key_id=None, pre_off=None, pre_idx=None, want_status=True, spans=False,
-                              gather_spans=None, stage_token=0, want_digests=False, tail=None, tail_base=0, nym=None):
+                              gather_spans=None, stage_token=0, want_digests=False, tail=None, tail_base=0, nym=None, sha3=False, flags=0):
         """fabgpu_identity_verify_batch: message i = [prefix pre_idx[i]] || arena[off[i], off[i+1]); keys by value or by id.
         gather_spans (m x 6 u32: three (start, end) pieces per gathered message): also returns their m x 32 digest bytes.
         want_digests: also returns (last) the n x 32 message digests as the fused kernel computed them.  tail / tail_base: bytes that
         are not in the arena but addressed at offsets >= tail_base (spans mode).  nym: pseudonym signatures over messages of the same
-        arena (spans mode), verified on a second stream in the same submission; returns (verdicts, statuses) of those last."""
+        arena (spans mode), verified on a second stream in the same submission; returns (verdicts, statuses) of those last.
+        sha3: FABGPU_IDB_SHA3_256 - messages, prefixes and the returned message digests under SHA3-256 (gathered digests stay SHA-256).
+        flags: further FABGPU_IDB_* bits, passed as they are."""
         arena, r, s = map(_a8, (arena, r, s))
         off = np.ascontiguousarray(off, dtype=np.uint32)
         n = off.size // 2 if spans else off.size - 1
         keep = [arena, off, r, s]
         b = _IdBatch()
         b.n = n
-        b.flags = (1 if spans else 0) | (2 if stage_token else 0)
+        b.flags = (1 if spans else 0) | (2 if stage_token else 0) | (IDB_SHA3_256 if sha3 else 0) | flags
         b.stage_token = stage_token
         b.arena, b.off, b.r, b.s = arena.ctypes.data, off.ctypes.data, r.ctypes.data, s.ctypes.data
         if key_id is not None:
@@ -747,14 +801,15 @@ class GPUCSP:
     """The accelerated verbs of bccsp.BCCSP (bccsp/bccsp.go:90-134); everything else the Go provider delegates to bccsp/sw."""
 
     def __init__(self, device: int = -1, devices: Optional[Sequence[int]] = None, flags: int = 0, concurrent_passes: int = 0,
-                 expect_block_bytes: int = 0, expect_tuples: int = 0, retire_evicted_keys: int = 0, **switches):
+                 expect_block_bytes: int = 0, expect_tuples: int = 0, retire_evicted_keys: int = 0, hash_sha3: int = 0, **switches):
         """device: ONE context on that HIP ordinal (fabgpu_csp_new).  devices: one context per entry - an ordinal may repeat; an empty
         list means every visible device - behind ONE provider (fabgpu_csp_new2: what bccsp/factory builds from the `GPU:` section).
         switches: pass_device_walk / pass_stage_min_bytes / pass_device_memo / pass_host_counts / pass_timing / pass_hash_memo (0 default,
         > 0 on, < 0 off), hash_memo_blocks (host copies of blocks the digest memo keeps per device), audit_permille (0 .. 1000: the share
         of digests / verdicts handed out that is re-computed on the CPU first; 0, the default: none - poison / poisoned / audit_stats).
         retire_evicted_keys (0, the default: off): an identity the cache evicts gives its device comb table up as well (set_option of the
-        same name; key_table_stats)."""
+        same name; key_table_stats).  hash_sha3 (0, the default: off): hash(msg, SHA3_256Opts()) and identities of the SHA3 hash family are
+        served on the device (set_option of the same name)."""
         L = load()
         h = _vp()
         err = ctypes.create_string_buffer(512)
@@ -777,6 +832,8 @@ class GPUCSP:
         self._h, self._L = h, L
         if retire_evicted_keys:
             self.set_option("retire_evicted_keys", retire_evicted_keys)
+        if hash_sha3:
+            self.set_option("hash_sha3", hash_sha3)
 
     def device_count(self) -> int:
         """Device contexts behind this provider."""
@@ -894,12 +951,13 @@ class GPUCSP:
             raise BCCSPError(err.value.decode())
         return bool(valid.value)
 
-    def identity_verify_coalesced(self, k: Optional[ECDSAPublicKey], msg: bytes, signature: bytes) -> Optional[str]:
-        """identity.Verify(msg, sig) through the coalescer: None (nil) or the error text."""
+    def identity_verify_coalesced(self, k: Optional[ECDSAPublicKey], msg: bytes, signature: bytes, hash_family: str = "SHA2") -> Optional[str]:
+        """identity.Verify(msg, sig) through the coalescer: None (nil) or the error text.  hash_family: the MSP's ("SHA2"; "SHA3" with
+        the hash_sha3 option on); callers of different families never share a launch."""
         err = ctypes.create_string_buffer(1024)
         qx, qy = (None, None) if k is None else k.xy_bytes()
-        _check(self._L.fabgpu_csp_identity_verify_coalesced(self._h, qx, qy, msg, len(msg), signature, len(signature), err, 1024),
-               "fabgpu_csp_identity_verify_coalesced")
+        _check(self._L.fabgpu_csp_identity_verify_coalesced2(self._h, qx, qy, msg, len(msg), signature, len(signature), hash_family.encode(), err, 1024),
+               "fabgpu_csp_identity_verify_coalesced2")
         return err.value.decode() or None
 
     def coalescer_configure(self, window_us: int = 50, max_batch: int = 32768) -> None:
@@ -928,8 +986,10 @@ class GPUCSP:
             out.append((bool(valid[i]), e or None))
         return out
 
-    def identity_verify_batch(self, keys: Sequence[ECDSAPublicKey], msgs: Sequence[bytes], sigs: Sequence[bytes]) -> List[Optional[str]]:
-        """identity.Verify (msp/identities.go:169-196) for n triples: None (nil) or the error text."""
+    def identity_verify_batch(self, keys: Sequence[ECDSAPublicKey], msgs: Sequence[bytes], sigs: Sequence[bytes],
+                              hash_family: str = "SHA2") -> List[Optional[str]]:
+        """identity.Verify (msp/identities.go:169-196) for n triples: None (nil) or the error text.  hash_family: the MSP's
+        SignatureHashFamily - "SHA2", or "SHA3" with the hash_sha3 option on; any other string gets getHashOpt's error text."""
         n = len(keys)
         qx = np.frombuffer(b"".join(k.x.to_bytes(32, "big") for k in keys), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
         qy = np.frombuffer(b"".join(k.y.to_bytes(32, "big") for k in keys), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
@@ -937,8 +997,8 @@ class GPUCSP:
         sa, so = _ragged(sigs)
         stride = 512
         errs = ctypes.create_string_buffer(max(1, n * stride))
-        _check(self._L.fabgpu_csp_identity_verify_batch(self._h, n, _p8(qx), _p8(qy), _p8(ma), mo.ctypes.data_as(_u32p), _p8(sa),
-                                                        so.ctypes.data_as(_u32p), errs, stride), "fabgpu_csp_identity_verify_batch")
+        _check(self._L.fabgpu_csp_identity_verify_batch2(self._h, n, _p8(qx), _p8(qy), _p8(ma), mo.ctypes.data_as(_u32p), _p8(sa),
+                                                         so.ctypes.data_as(_u32p), hash_family.encode(), errs, stride), "fabgpu_csp_identity_verify_batch2")
         return [(errs.raw[i * stride:(i + 1) * stride].split(b"\0", 1)[0].decode() or None) for i in range(n)]
 
     # ---- idemix creator signatures (bccsp/idemix/handlers) ----
@@ -997,10 +1057,11 @@ class Identity:
 
     def verify(self, msg: bytes, sig: bytes) -> None:
         """Returns None (nil) or raises BCCSPError with identity.Verify's error text."""
-        if self.hash_family != "SHA2":
+        sha3 = self.hash_family == "SHA3" and self.csp.get_option("hash_sha3") > 0     # (the provider serves the family only with its option on)
+        if self.hash_family != "SHA2" and not sha3:
             raise BCCSPError("hash familiy not recognized [%s]" % self.hash_family) if self.hash_family != "SHA3" else \
                 BCCSPError("failed computing digest: SHA3 is served by bccsp/sw, not by the GPU provider")
-        err = self.csp.identity_verify_batch([self.pk], [msg], [sig])[0]
+        err = self.csp.identity_verify_batch([self.pk], [msg], [sig], hash_family=self.hash_family)[0]
         if err:
             raise BCCSPError(err)
 

@@ -70,6 +70,10 @@ type GPUOpts struct {
 	// without it a context stops registering after 4096 keys and serves every later identity on the fresh-key kernels until the
 	// peer restarts.  Unset means true; `RetireEvictedKeys: false` keeps every table registered for the life of the process.
 	RetireEvictedKeys *bool `mapstructure:"retireevictedkeys" json:"retireevictedkeys,omitempty" yaml:"RetireEvictedKeys,omitempty"`
+	// SHA3: identities of an MSP whose SignatureHashFamily is SHA3 (msp/identities.go:216-224) are verified in batches on the device too
+	// (fabgpu_bccsp.h option "hash_sha3").  Unset means true; `SHA3: false` leaves the family to bccsp/sw.  The block pass hashes with
+	// SHA-256 either way: a SHA3 MSP's signatures are decided by bccsp/sw behind it.
+	SHA3 *bool `mapstructure:"sha3" json:"sha3,omitempty" yaml:"SHA3,omitempty"`
 }
 
 // DefaultAuditPermille is what GPUOpts.AuditPermille means when the `GPU:` section does not set it.
@@ -94,7 +98,7 @@ func (f *GPUFactory) Get(config *FactoryOpts) (bccsp.BCCSP, error) {
 	if err != nil {
 		return nil, errors.Wrapf(err, "Failed initializing the software BCCSP behind the GPU provider")
 	}
-	opts := gpu.Options{AuditPermille: DefaultAuditPermille, RetireEvictedKeys: true}
+	opts := gpu.Options{AuditPermille: DefaultAuditPermille, RetireEvictedKeys: true, SHA3: true}
 	if g := config.GPUOpts; g != nil {
 		if g.Device != nil {
 			if len(g.Devices) == 0 {
@@ -105,7 +109,10 @@ func (f *GPUFactory) Get(config *FactoryOpts) (bccsp.BCCSP, error) {
 		}
 		opts = gpu.Options{Devices: g.Devices, ConcurrentPasses: g.ConcurrentPasses, ExpectBlockBytes: g.ExpectBlockBytes,
 			ExpectTuples: g.ExpectTuples, MemoBlocks: g.MemoBlocks, HostWalk: g.HostWalk, PassTiming: g.PassTiming,
-			NoHashMemo: g.NoHashMemo, HashMemoBlocks: g.HashMemoBlocks, KeyTables16: g.KeyTables16, AuditPermille: DefaultAuditPermille, RetireEvictedKeys: true}
+			NoHashMemo: g.NoHashMemo, HashMemoBlocks: g.HashMemoBlocks, KeyTables16: g.KeyTables16, AuditPermille: DefaultAuditPermille, RetireEvictedKeys: true, SHA3: true}
+		if g.SHA3 != nil {
+			opts.SHA3 = *g.SHA3
+		}
 		if g.RetireEvictedKeys != nil {
 			opts.RetireEvictedKeys = *g.RetireEvictedKeys
 		}

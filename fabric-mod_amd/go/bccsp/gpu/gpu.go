@@ -139,6 +139,11 @@ type Options struct {
 	// RetireEvictedKeys: identities the identity cache evicts give their device comb tables up (option "retire_evicted_keys";
 	// KeyTableStats, gauges bccsp_gpu_key_tables).  GPUFactory passes true unless the operator says otherwise.
 	RetireEvictedKeys bool
+	// SHA3: the library serves the SHA3 hash family on the device (option "hash_sha3"): batched identity verification of an MSP whose
+	// SignatureHashFamily is SHA3 (fabgpu_csp_identity_verify_batch2 / _coalesced2 with family "SHA3").  One-message Hash calls stay with
+	// bccsp/sw whatever this says (Provider.Hash).  Not served: the block pass, which hashes with SHA-256 - a SHA3 MSP's signatures come
+	// back "not valid" from it and are decided by bccsp/sw.  GPUFactory passes true unless the operator says otherwise.
+	SHA3 bool
 }
 
 // SetCoalesce switches the coalesced device path for memo misses on or off (GPUOpts.CoalesceVerify in gpufactory.go).
@@ -263,6 +268,15 @@ func New(swCSP bccsp.BCCSP, opts Options) (bccsp.BCCSP, error) {
 		if rc != 0 {
 			C.fabgpu_csp_free(csp)
 			return nil, errors.Errorf("Failed initializing GPU BCCSP: retire_evicted_keys: %s", C.GoString(C.fabgpu_strerror(rc)))
+		}
+	}
+	if opts.SHA3 {
+		name := C.CString("hash_sha3")
+		rc := C.fabgpu_csp_set_option(csp, name, 1, nil)
+		C.free(unsafe.Pointer(name))
+		if rc != 0 {
+			C.fabgpu_csp_free(csp)
+			return nil, errors.Errorf("Failed initializing GPU BCCSP: hash_sha3: %s", C.GoString(C.fabgpu_strerror(rc)))
 		}
 	}
 	if opts.MemoBlocks > 0 {
@@ -472,8 +486,11 @@ const hashMemoMinLen = 64
 // (fabgpu_csp_hash_lookup): a block pass that seeded the verdict memo has hashed exactly these bytes on the device and kept the block in
 // host memory the library owns; the stored digest comes back ONLY when every byte of msg equals the bytes the device hashed (the
 // library compares them all - a fingerprint merely chooses where to look), so the digest is still bound to the validator's own bytes.
-// A miss - any other message, an evicted block, a switched-off memo - and every other HashOpts (SHA3, SHA384, nil: bccsp/sw's error
-// text, bccsp/sw/impl.go:179-181) go to bccsp/sw.  No PCIe round trip either way: a hit is a table probe and a memcmp.
+// A miss - any other message, an evicted block, a switched-off memo - and every other HashOpts (SHA384, nil: bccsp/sw's error
+// text, bccsp/sw/impl.go:179-181) go to bccsp/sw.  So does *bccsp.SHA3_256Opts, also with Options.SHA3 on: the device hashes SHA3-256
+// in batches (fabgpu_sha3_256_batch behind the identity batches of a SHA3 MSP), and one launch per message never pays - a 2 KB message
+// is a few microseconds of sha3.New256 against a PCIe round trip; the digest memo holds SHA-256 digests only.
+// No PCIe round trip either way: a hit is a table probe and a memcmp.
 // Before round 6 Hash always went to bccsp/sw: the validators then re-hashed on the CPU every byte the device had just hashed (100 MB
 // per 10 000-transaction block), which was three to four times the cost of the GPU pass itself.
 func (p *Provider) Hash(msg []byte, opts bccsp.HashOpts) ([]byte, error) {

@@ -170,6 +170,26 @@ int fabgpu_sha256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const v
                                               const void* key_id, const void* r, const void* s, void* verdict_bits, void* status,
                                               void* stream);
 
+/* ---- SHA3-256: an MSP whose SignatureHashFamily is SHA3 (msp/identities.go:216-224 -> bccsp.SHA3_256Opts) ----
+ * Argument lists, conventions and verdicts are those of the sha256 namesakes above; the digest is SHA3-256 (FIPS 202).  The curve
+ * arithmetic does not depend on the family: a SHA3-256 digest is 32 bytes, e is the digest itself.  Hash and verify are two launches on
+ * one stream - the digests go through a context-owned device buffer into the verify-only kernels, which are chosen by n and the
+ * context's flags as for fabgpu_p256_verify_batch(_keyed); no digest leaves the chip.  One message per lane at every size (there is
+ * no several-lanes-per-message form for small launches).  Not served: fabgpu_multi_*, and the block pass (fabgpu_bccsp.h), which
+ * hashes every signed message with SHA-256. */
+int fabgpu_sha3_256_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, uint8_t* digests);
+int fabgpu_sha3_256_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, void* stream);
+int fabgpu_sha3_256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx,
+                                      const uint8_t* qy, const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
+int fabgpu_sha3_256_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
+                                          const void* qx, const void* qy, const void* r, const void* s, void* verdict_bits,
+                                          void* status, void* stream);
+int fabgpu_sha3_256_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
+                                            const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
+int fabgpu_sha3_256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
+                                                const void* key_id, const void* r, const void* s, void* verdict_bits, void* status,
+                                                void* stream);
+
 /* ---- identity.Verify over a DESCRIBED batch: shared message prefixes, fresh or registered keys ----
  * The endorsements of one transaction all sign  prp || endorser_i  (core/common/validation/statebased/
  * validator_keylevel.go:246-258): the proposal-response payload is a shared PREFIX.  A batch may list m prefixes
@@ -178,7 +198,8 @@ int fabgpu_sha256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const v
  * messages continue from there.  Keys: either (qx, qy) per message or key_id per message (registered keys), not both.
  * Verdicts are those of fabgpu_sha256_p256_verify_batch on the concatenated messages.
  * Host variant: all pointers are host memory.  _dev: all pointers are device memory, arena_bytes = readable size of the
- * arena allocation, mid_scratch = n_prefixes x 32 bytes of device scratch, asynchronous on `stream`. */
+ * arena allocation, mid_scratch = n_prefixes x 32 bytes of device scratch (n_prefixes x 200 bytes, 8-byte aligned, with
+ * FABGPU_IDB_SHA3_256: a SHA3-256 mid-state is the whole Keccak state), asynchronous on `stream`. */
 typedef struct fabgpu_identity_batch {
     size_t n;
     const void* arena;
@@ -194,7 +215,7 @@ typedef struct fabgpu_identity_batch {
     const void* s;
     void* verdict_bits;          /* ceil(n/64) x u64 */
     void* status;                /* n bytes or NULL */
-    uint32_t flags;              /* FABGPU_IDB_* */
+    uint32_t flags;              /* FABGPU_IDB_* (FABGPU_IDB_SHA3_256: _dev callers size mid_scratch n_prefixes x 200 bytes) */
     /* Optional: more SHA-256 digests over the SAME arena in the same submission - the TxID and proposal-hash checks of
      * ValidateTransaction (protoutil/proputils.go:357-375, protoutil/txutils.go:431-447).  Message j is the
      * concatenation of up to three arena spans gather_spans[6j .. 6j+5] = (start, end) x 3 (an unused piece has start == end);
@@ -236,6 +257,11 @@ typedef struct fabgpu_identity_batch {
                              (a marshalled block), not consecutive */
 #define FABGPU_IDB_ARENA_STAGED 2u /* host variant: the arena is already on the device (fabgpu_arena_stage); `arena` is ignored, all
                                     offsets are offsets into the staged bytes */
+#define FABGPU_IDB_SHA3_256 4u /* messages and prefixes are hashed with SHA3-256 (136-byte blocks for the mid-states) and `digests`, if asked
+                                for, are SHA3-256: the batch of an MSP of the SHA3 family.  gather_digests stay SHA-256 - TxID and proposal
+                                hash are SHA-256 in the reference whatever the MSP's family (protoutil/proputils.go:357-375,
+                                protoutil/txutils.go:431-447) - and pseudonym signatures riding along (n_nym) are untouched.  Works with
+                                FABGPU_IDB_SPANS, FABGPU_IDB_ARENA_STAGED and the tail.  _dev: mid_scratch is n_prefixes x 200 bytes */
 /* Uploads `len` bytes to a context-owned device buffer and returns when they are there; *token names the upload.  Meant to run on
  * a helper thread WHILE the caller still prepares the batch that refers to these bytes (the block pre-verify pass parses a
  * 50 MB block while it travels).  A later fabgpu_identity_verify_batch with FABGPU_IDB_ARENA_STAGED and this token uses the

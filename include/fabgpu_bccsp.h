@@ -71,6 +71,12 @@ int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pa
  * the devices keep agreeing on key ids - and a provider whose signers come and go keeps registering the hot ones for as long as it
  * lives, where it otherwise stops after FABGPU_MAX_KEYS registrations.  Keys that came in through fabgpu_csp_key_import are never
  * retired this way.
+ * "hash_sha3" (default off; > 0 on): the provider serves the SHA3 hash family on the device - fabgpu_csp_hash answers "SHA3_256"
+ * (bccsp.SHA3_256Opts) through fabgpu_sha3_256_batch, and fabgpu_csp_identity_verify_batch2 / _coalesced2 take hash family "SHA3",
+ * what identity.Verify selects for an MSP whose SignatureHashFamily is SHA3 (msp/identities.go:216-224).  Off, every answer is what it
+ * was: "Unsupported 'HashOpt' provided [SHA3_256]", and family "SHA3" answers that bccsp/sw serves it.  NOT served either way: the
+ * block pass (it hashes every signed message with SHA-256, so a SHA3 MSP's signatures come back "not valid" from it and their
+ * validators' SHA3-256 digests can only miss the verdict memo, never hit a SHA-256 verdict) and the digest memo (SHA-256 only).
  * FABGPU_EINVAL: no such option. */
 int fabgpu_csp_set_option(fabgpu_csp* csp, const char* name, int64_t value, int64_t* previous);
 int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value);
@@ -85,7 +91,8 @@ int fabgpu_csp_key_table_stats(fabgpu_csp* csp, int d, uint64_t* out, int cap);
  *   - fabgpu_csp_hash_lookup hits: SHA-256 of the caller's message;
  *   - fabgpu_csp_memo_lookup hits: bccsp.Verify(k, sig, digest) as bccsp/sw decides it, against stored status 0 / anything else;
  *   - "valid" answers of fabgpu_csp_verify, _verify_batch, _verify_coalesced, _identity_verify_batch, _identity_verify_coalesced
- *     (the identity calls hash the message again first).  Rejects are not sampled: the Go side re-checks every reject in bccsp/sw.
+ *     (the identity calls hash the message again first - with SHA3-256, through the kernels' own sha3_256.h compiled for the host, when
+ *     the call's hash family is SHA3).  Rejects are not sampled: the Go side re-checks every reject in bccsp/sw.
  * Idemix pseudonym entries (fabgpu_csp_memo_lookup_nym, fabgpu_csp_idemix_nym_verify_batch) are NOT audited; they are counted.
  * Sampling has no randomness: one hit counter per kind, hit number h (1-based) is audited iff h*permille/1000 != (h-1)*permille/1000 -
  * 1000 audits every hit, 250 exactly every fourth, 0 none.
@@ -107,7 +114,7 @@ int fabgpu_csp_audit_stats(fabgpu_csp* csp, uint64_t* out, int cap);
  * signers were all imported this way run on the keyed kernels.  err: "" or the Go error text. */
 int fabgpu_csp_key_import(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, int* on_curve, char* err, size_t errcap);
 
-/* alg == NULL mirrors opts == nil. */
+/* alg == NULL mirrors opts == nil.  "SHA256"; "SHA3_256" with the hash_sha3 option on; anything else: "Unsupported 'HashOpt' provided [..]" */
 int fabgpu_csp_hash(fabgpu_csp* csp, const uint8_t* msg, size_t len, const char* alg, uint8_t* digest32, char* err, size_t errcap);
 
 /* BCCSP.Hash for bytes a memo-seeding block pass has ALREADY hashed on the device: the `digest, err := id.msp.bccsp.Hash(msg, hashOpt)` half
@@ -142,6 +149,11 @@ int fabgpu_csp_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, const uint
                                 const uint8_t* digest, size_t dlen, int* valid, int* flags, char* err, size_t errcap);
 int fabgpu_csp_identity_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, const uint8_t* msg, size_t msglen,
                                          const uint8_t* sig, size_t siglen, char* err, size_t errcap);
+/* ... with the MSP's hash family: "SHA2" (what the entry above means) or, with the hash_sha3 option on, "SHA3".  Callers of the two
+ * families never share a launch (a queue per family).  Any other string: err = "hash familiy not recognized [<family>]" - the
+ * reference's text and spelling (msp/identities.go:223) -, FABGPU_OK, nothing launched. */
+int fabgpu_csp_identity_verify_coalesced2(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, const uint8_t* msg, size_t msglen,
+                                          const uint8_t* sig, size_t siglen, const char* hash_family, char* err, size_t errcap);
 int fabgpu_csp_coalescer_configure(fabgpu_csp* csp, uint32_t window_us, uint32_t max_batch);
 int fabgpu_csp_coalescer_stats(fabgpu_csp* csp, uint64_t* calls, uint64_t* launches, uint64_t* largest_batch);
 
@@ -154,6 +166,11 @@ int fabgpu_csp_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* qx, const 
 int fabgpu_csp_identity_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena,
                                      const uint32_t* msg_off, const uint8_t* sig_arena, const uint32_t* sig_off, char* errs,
                                      size_t errstride);
+/* ... for identities of an MSP whose hash family is hash_family ("SHA2", "SHA3"; see fabgpu_csp_identity_verify_coalesced2): the digest is
+ * SHA3-256(msg) for "SHA3", computed by a launch of its own in front of the verify kernels; keyed when every signer is registered. */
+int fabgpu_csp_identity_verify_batch2(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena,
+                                      const uint32_t* msg_off, const uint8_t* sig_arena, const uint32_t* sig_off, const char* hash_family,
+                                      char* errs, size_t errstride);
 
 /* ---- block-level pre-verify pass (extensions/validation/validation.go:48-64 is the hook) ----
  * One fused launch for every signature of a marshalled common.Block:
