@@ -382,6 +382,39 @@ inline hipError_t launched(const fabgpu_ctx* ctx, hipError_t e) { return ctx->fa
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// what the _dev entry points refuse: more rows or arena bytes than the kernels' 32-bit indices hold
+inline bool dev_too_big(size_t n, size_t arena_bytes = 0) { return n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull; }
+
+// The bracket around what a _dev entry point queues on st: a pooled workspace of ws_bytes (0: none) handed to launch(wsp) and given
+// back behind it, the two timing events of FABGPU_FLAG_TIME_KERNELS (what fabgpu_last_kernel_ms reports), and the launch's result -
+// or the injected failure - as a return code.
+template <class Launch>
+int timed_launch(fabgpu_ctx* ctx, hipStream_t st, size_t ws_bytes, Launch&& launch) {
+    size_t wi = 0;
+    void* wsp = nullptr;
+    if (ws_bytes) {
+        int rc = ctx->acquire_qws(ws_bytes, &wi, &wsp, st);
+        if (rc != FABGPU_OK) return rc;
+    }
+    if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
+    hipError_t err = launch(wsp);
+    if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
+    if (ws_bytes) ctx->release_qws(wi, st);
+    ctx->timed = ctx->time_kernels;
+    return hip_to_rc(launched(ctx, err));
+}
+
+// the fields every form of the verify launch shares; the caller names its key source and its digest source
+VerifyLaunch verify_launch_common(const fabgpu_ctx* ctx, size_t n, const void* r, const void* s, void* verdict_bits, void* status) {
+    VerifyLaunch v;
+    v.n = (uint32_t)n;
+    v.r = r; v.s = s;
+    v.gtab = ctx->d_gtab;
+    v.verdict_bits = verdict_bits; v.status = status;
+    v.allow_pair = ctx->allow_pair;
+    return v;
+}
+
 }  // namespace
 
 extern "C" {
@@ -603,69 +636,45 @@ extern "C" {
 int fabgpu_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* qx, const void* qy, const void* e, const void* r,
                                  const void* s, void* verdict_bits, void* status, void* stream) {
     if (!ctx || (n && (!qx || !qy || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0xFFFFFFF0ull) return FABGPU_ETOOBIG;
+    if (dev_too_big(n)) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     DeviceGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    size_t wi = 0;
-    void* wsp = nullptr;
-    int rc = ctx->acquire_qws(verify_workspace_bytes((uint32_t)n, ctx->allow_pair), &wi, &wsp, st);
-    if (rc != FABGPU_OK) return rc;
-    if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    VerifyLaunch v;
-    v.n = (uint32_t)n;
-    v.qx = qx; v.qy = qy; v.qws = wsp;
-    v.e = e; v.r = r; v.s = s;
-    v.gtab = ctx->d_gtab;
-    v.verdict_bits = verdict_bits; v.status = status;
-    v.allow_pair = ctx->allow_pair; v.table_lds = ctx->pair_table_lds; v.pair_solo = ctx->pair_solo;
-    hipError_t err = launch_verify(v, st);
-    if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
-    ctx->release_qws(wi, st);
-    ctx->timed = ctx->time_kernels;
-    return hip_to_rc(launched(ctx, err));
+    VerifyLaunch v = verify_launch_common(ctx, n, r, s, verdict_bits, status);
+    v.qx = qx; v.qy = qy;
+    v.e = e;
+    v.table_lds = ctx->pair_table_lds; v.pair_solo = ctx->pair_solo;   // (the verify-only fresh-key form alone has the two table homes)
+    return timed_launch(ctx, st, verify_workspace_bytes((uint32_t)n, ctx->allow_pair), [&](void* wsp) {
+        v.qws = wsp;
+        return launch_verify(v, st);
+    });
 }
 
 int fabgpu_sha256_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests,
                             void* stream) {
     if (!ctx || (n && (!arena || !off || !digests))) return FABGPU_EINVAL;
-    if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
+    if (dev_too_big(n, arena_bytes)) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     DeviceGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    hipError_t err = launch_sha256_batch((uint32_t)n, arena, arena_bytes, off, digests, st);
-    if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
-    ctx->timed = ctx->time_kernels;
-    return hip_to_rc(launched(ctx, err));
+    return timed_launch(ctx, st, 0, [&](void*) { return launch_sha256_batch((uint32_t)n, arena, arena_bytes, off, digests, st); });
 }
 
 int fabgpu_sha256_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
                                         const void* qx, const void* qy, const void* r, const void* s, void* verdict_bits,
                                         void* status, void* stream) {
     if (!ctx || (n && (!arena || !off || !qx || !qy || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
+    if (dev_too_big(n, arena_bytes)) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     DeviceGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    size_t wi = 0;
-    void* wsp = nullptr;
-    int rc = ctx->acquire_qws(verify_workspace_bytes((uint32_t)n, ctx->allow_pair), &wi, &wsp, st);
-    if (rc != FABGPU_OK) return rc;
-    if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    VerifyLaunch v;
-    v.n = (uint32_t)n;
-    v.qx = qx; v.qy = qy; v.qws = wsp;
+    VerifyLaunch v = verify_launch_common(ctx, n, r, s, verdict_bits, status);
+    v.qx = qx; v.qy = qy;
     v.arena = arena; v.arena_bytes = arena_bytes; v.off = off;
-    v.r = r; v.s = s;
-    v.gtab = ctx->d_gtab;
-    v.verdict_bits = verdict_bits; v.status = status;
-    v.allow_pair = ctx->allow_pair;
-    hipError_t err = launch_verify(v, st);
-    if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
-    ctx->release_qws(wi, st);
-    ctx->timed = ctx->time_kernels;
-    return hip_to_rc(launched(ctx, err));
+    return timed_launch(ctx, st, verify_workspace_bytes((uint32_t)n, ctx->allow_pair), [&](void* wsp) {
+        v.qws = wsp;
+        return launch_verify(v, st);
+    });
 }
 
 // ---- idemix pseudonym signatures --------------------------------------------------------------------
@@ -1355,40 +1364,23 @@ int fabgpu_p256_key_table_stats(fabgpu_ctx* ctx, uint64_t* out, int cap) {
 int fabgpu_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* key_id, const void* e, const void* r, const void* s,
                                        void* verdict_bits, void* status, void* stream) {
     if (!ctx || (n && (!key_id || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0xFFFFFFF0ull) return FABGPU_ETOOBIG;
+    if (dev_too_big(n)) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     hipStream_t st = (hipStream_t)stream;
     KeyedSnap snap(ctx, {st});
-    const uint32_t nkeys = snap.nkeys;
-    const int32_t** kt = snap.kt;
-    if (nkeys == 0) return FABGPU_EINVAL;
+    if (snap.nkeys == 0) return FABGPU_EINVAL;
     DeviceGuard g(ctx->device);
-    if (ctx->allow_wide && n <= (size_t)WIDE_LAUNCH_MAX) {
+    if (ctx->allow_wide && n <= (size_t)WIDE_LAUNCH_MAX)
         // a launch that cannot fill the chip: eight lanes per signature, the digest-independent half first (kernels.h, p256_wide29.h)
-        size_t wi = 0;
-        void* wsp = nullptr;
-        int rc = ctx->acquire_qws(n * WIDE_SCRATCH_BYTES, &wi, &wsp, st);
-        if (rc != FABGPU_OK) return rc;
-        if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-        hipError_t err = launch_p256_wide_pre((uint32_t)n, key_id, nkeys, (const void*)kt, r, s, ctx->d_gtab, wsp, st);
-        if (err == hipSuccess) err = launch_p256_wide_post((uint32_t)n, e, r, ctx->d_gtab, wsp, verdict_bits, status, st);
-        if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
-        ctx->release_qws(wi, st);
-        ctx->timed = ctx->time_kernels;
-        return hip_to_rc(launched(ctx, err));
-    }
-    if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    VerifyLaunch v;
-    v.n = (uint32_t)n;
-    v.key_id = key_id; v.nkeys = nkeys; v.ktabs = (const void*)kt;
-    v.e = e; v.r = r; v.s = s;
-    v.gtab = ctx->d_gtab;
-    v.verdict_bits = verdict_bits; v.status = status;
-    v.allow_pair = ctx->allow_pair;
-    hipError_t err = launch_verify(v, st);
-    if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
-    ctx->timed = ctx->time_kernels;
-    return hip_to_rc(launched(ctx, err));
+        return timed_launch(ctx, st, n * WIDE_SCRATCH_BYTES, [&](void* wsp) {
+            hipError_t err = launch_p256_wide_pre((uint32_t)n, key_id, snap.nkeys, (const void*)snap.kt, r, s, ctx->d_gtab, wsp, st);
+            if (err == hipSuccess) err = launch_p256_wide_post((uint32_t)n, e, r, ctx->d_gtab, wsp, verdict_bits, status, st);
+            return err;
+        });
+    VerifyLaunch v = verify_launch_common(ctx, n, r, s, verdict_bits, status);
+    v.key_id = key_id; v.nkeys = snap.nkeys; v.ktabs = (const void*)snap.kt;
+    v.e = e;
+    return timed_launch(ctx, st, 0, [&](void*) { return launch_verify(v, st); });
 }
 
 // identity.Verify for registered keys on a launch that cannot fill the chip: the digest-independent half of the verification, the
@@ -1417,101 +1409,21 @@ static int keyed_wide_identity_dev(fabgpu_ctx* ctx, uint32_t n, const void* aren
 int fabgpu_sha256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
                                               const void* key_id, const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
     if (!ctx || (n && (!arena || !off || !key_id || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
+    if (dev_too_big(n, arena_bytes)) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     hipStream_t st = (hipStream_t)stream;
     KeyedSnap snap(ctx, {st});
-    const uint32_t nkeys = snap.nkeys;
-    const int32_t** kt = snap.kt;
-    if (nkeys == 0) return FABGPU_EINVAL;
+    if (snap.nkeys == 0) return FABGPU_EINVAL;
     DeviceGuard g(ctx->device);
     if (ctx->allow_wide && n <= (size_t)WIDE_LAUNCH_MAX)
-        return keyed_wide_identity_dev(ctx, (uint32_t)n, arena, arena_bytes, off, key_id, nkeys, (const void*)kt, r, s, verdict_bits, status, ShaPrefixArgs(), st);
-    if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    VerifyLaunch v;
-    v.n = (uint32_t)n;
-    v.key_id = key_id; v.nkeys = nkeys; v.ktabs = (const void*)kt;
+        return keyed_wide_identity_dev(ctx, (uint32_t)n, arena, arena_bytes, off, key_id, snap.nkeys, (const void*)snap.kt, r, s, verdict_bits, status, ShaPrefixArgs(), st);
+    VerifyLaunch v = verify_launch_common(ctx, n, r, s, verdict_bits, status);
+    v.key_id = key_id; v.nkeys = snap.nkeys; v.ktabs = (const void*)snap.kt;
     v.arena = arena; v.arena_bytes = arena_bytes; v.off = off;
-    v.r = r; v.s = s;
-    v.gtab = ctx->d_gtab;
-    v.verdict_bits = verdict_bits; v.status = status;
-    v.allow_pair = ctx->allow_pair;
-    hipError_t err = launch_verify(v, st);
-    if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
-    ctx->timed = ctx->time_kernels;
-    return hip_to_rc(launched(ctx, err));
+    return timed_launch(ctx, st, 0, [&](void*) { return launch_verify(v, st); });
 }
 
 // ---- host-pointer entry points (what the cgo provider binds) -----------------------------------------
-int fabgpu_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* e, const uint8_t* r,
-                             const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
-    if (!ctx || (n && (!qx || !qy || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
-    if (n == 0) return FABGPU_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    const size_t fb = n * 32, words = (n + 63) / 64;
-    const size_t st_off = round_up(words * 8, 64);
-    int rc;
-    if ((rc = ctx->fields.ensure(5 * fb)) || (rc = ctx->out.ensure(st_off + n))) return rc;
-    uint8_t* h = (uint8_t*)ctx->fields.h;
-    uint8_t* d = (uint8_t*)ctx->fields.d;
-    uint8_t* dout = (uint8_t*)ctx->out.d;
-    // Field by field: the copy of a field into the pinned staging buffer, then ITS transfer - the DMA of field k runs while the host
-    // copies field k + 1 (round 5; one transfer of all five behind all five copies left the bus idle for the copies' 0.15 ms and the
-    // host idle for the transfer's 0.1 ms).  Small batches stay one transfer: five API calls would cost more than they hide.
-    const uint8_t* src[5] = {qx, qy, e, r, s};
-    hipError_t err = hipSuccess;
-    if (fb >= ((size_t)256 << 10)) {
-        for (int f = 0; f < 5 && err == hipSuccess; f++) {
-            memcpy(h + (size_t)f * fb, src[f], fb);
-            err = hipMemcpyAsync(d + (size_t)f * fb, h + (size_t)f * fb, fb, hipMemcpyHostToDevice, ctx->stream);
-        }
-    } else {
-        for (int f = 0; f < 5; f++) memcpy(h + (size_t)f * fb, src[f], fb);
-        err = hipMemcpyAsync(d, h, 5 * fb, hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (err != hipSuccess) {
-        hipStreamSynchronize(ctx->stream);                  // (nothing may still be reading the staging buffer when the next call refills it)
-        return hip_to_rc(err);
-    }
-    rc = fabgpu_p256_verify_batch_dev(ctx, n, d, d + fb, d + 2 * fb, d + 3 * fb, d + 4 * fb, dout, status ? dout + st_off : nullptr, ctx->stream);
-    if (rc) return rc;
-    err = hipMemcpyAsync(ctx->out.h, dout, status ? st_off + n : words * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    memcpy(verdict_bits, ctx->out.h, words * 8);
-    if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
-    return FABGPU_OK;
-}
-
-int fabgpu_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint32_t* key_id, const uint8_t* e, const uint8_t* r, const uint8_t* s,
-                                   uint64_t* verdict_bits, uint8_t* status) {
-    if (!ctx || (n && (!key_id || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0x7FFFFFF0ull / 100) return FABGPU_ETOOBIG;
-    if (n == 0) return FABGPU_OK;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    const size_t fb = n * 32, kb = round_up(n * 4, 64), words = (n + 63) / 64;
-    const size_t st_off = round_up(words * 8, 64);
-    int rc;
-    if ((rc = ctx->keyed.ensure(kb + 3 * fb)) || (rc = ctx->out.ensure(st_off + n))) return rc;
-    uint8_t* h = (uint8_t*)ctx->keyed.h;
-    memcpy(h, key_id, n * 4); memcpy(h + kb, e, fb); memcpy(h + kb + fb, r, fb); memcpy(h + kb + 2 * fb, s, fb);
-    uint8_t* d = (uint8_t*)ctx->keyed.d;
-    uint8_t* dout = (uint8_t*)ctx->out.d;
-    hipError_t err = hipMemcpyAsync(d, h, kb + 3 * fb, hipMemcpyHostToDevice, ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    rc = fabgpu_p256_verify_batch_keyed_dev(ctx, n, d, d + kb, d + kb + fb, d + kb + 2 * fb, dout, status ? dout + st_off : nullptr, ctx->stream);
-    if (rc) return rc;
-    err = hipMemcpyAsync(ctx->out.h, dout, status ? st_off + n : words * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    memcpy(verdict_bits, ctx->out.h, words * 8);
-    if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
-    return FABGPU_OK;
-}
-
 // copy the span of the arena the offsets reference; returns rebased offsets in ctx->offs.h
 static int stage_messages(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, size_t* arena_bytes_out) {
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
@@ -1534,55 +1446,172 @@ static int stage_messages(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const
     return hip_to_rc(err);
 }
 
-int fabgpu_sha256_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, uint8_t* digests) {
+// What one host-pointer call stages through the context's pinned buffers, ctx->mu held: its messages (ctx->arena, ctx->offs), its
+// n x 32 byte fields behind an optional column of u32 ids (one Buf), and room in ctx->out for what comes back - verdict words, then
+// status bytes at st_off; or n digests.  A step is skipped once one before it has failed (rc), and every call returns through fetch().
+// THE FAILURE RULE, here and nowhere else: whatever failed - an allocation, an upload, the _dev call, the download - fetch() drains
+// ctx->stream before it returns and nothing is copied to the caller.  Non-zero return, the caller's arrays untouched, nothing in
+// flight: no transfer may still be reading a staging buffer when the next call refills it.
+struct HostStage {
+    fabgpu_ctx* ctx;
+    const size_t n, fb, words, st_off;   // rows; bytes of one field; verdict words; where the status bytes start in ctx->out
+    size_t kb = 0;                       // bytes of the id column in front of the fields: n ids padded to 64
+    size_t ab = 0;                       // bytes of the staged arena
+    uint8_t* d = nullptr;                // device base of ids | fields
+    const size_t out_bytes;              // what comes back at most: n digests, or the verdict words and the status bytes
+    int rc = FABGPU_OK;
+
+    HostStage(fabgpu_ctx* c, size_t rows, bool digests = false)
+        : ctx(c), n(rows), fb(rows * 32), words((rows + 63) / 64), st_off(round_up(words * 8, 64)), out_bytes(digests ? n * 32 : st_off + n) {}
+    int room(Buf& b, size_t bytes) const { return ctx->fault == 2 ? FABGPU_ENOMEM : b.ensure(bytes); }   // FABGPU_FAULT_INJECT=oom: no staging either
+    void messages(const uint8_t* arena, const uint32_t* off) {
+        if (rc == FABGPU_OK) rc = stage_messages(ctx, n, arena, off, &ab);
+    }
+    // ID_COLUMN: the fields sit behind an id column; ids may still be nullptr (the nym form's issuer ids are optional, their room is not).
+    // OVERLAP: for fields of 256 KiB and more - field by field: the copy of a field into the pinned staging buffer, then ITS transfer -
+    // the DMA of field k runs while the host copies field k + 1 (round 5; one transfer of all five behind all five copies left the bus
+    // idle for the copies' 0.15 ms and the host idle for the transfer's 0.1 ms).  Small batches stay one transfer: five API calls would
+    // cost more than they hide.
+    enum : unsigned { ID_COLUMN = 1, OVERLAP = 2 };
+    void fields(Buf& buf, unsigned how, const uint32_t* ids, std::initializer_list<const uint8_t*> src) {
+        if (rc != FABGPU_OK) return;
+        kb = (how & ID_COLUMN) ? round_up(n * 4, 64) : 0;
+        const size_t total = kb + src.size() * fb;
+        if ((rc = room(buf, total))) return;
+        uint8_t* h = (uint8_t*)buf.h;
+        d = (uint8_t*)buf.d;
+        if (ids) memcpy(h, ids, n * 4);
+        const bool each = (how & OVERLAP) && fb >= ((size_t)256 << 10);
+        hipError_t err = each && kb ? hipMemcpyAsync(d, h, kb, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;   // (the ids travel first)
+        size_t at = kb;
+        for (const uint8_t* f : src) {
+            if (err != hipSuccess) break;
+            memcpy(h + at, f, fb);
+            if (each) err = hipMemcpyAsync(d + at, h + at, fb, hipMemcpyHostToDevice, ctx->stream);
+            at += fb;
+        }
+        if (!each) err = hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, ctx->stream);
+        rc = hip_to_rc(err);
+    }
+    // behind the staging, before the _dev call: room for the results (the buffers are made in the order they always were)
+    bool ready() {
+        if (rc == FABGPU_OK) rc = room(ctx->out, out_bytes);
+        return rc == FABGPU_OK;
+    }
+    const void* ids() const { return d; }
+    const void* field(size_t f) const { return d + kb + f * fb; }
+    void* dout() const { return ctx->out.d; }
+    void* dstatus(const uint8_t* status) const { return status ? (uint8_t*)ctx->out.d + st_off : nullptr; }
+    // the first `bytes` of ctx->out to the host behind everything queued, and the wait for it
+    int fetch(size_t bytes) {
+        hipError_t err = rc == FABGPU_OK ? hipMemcpyAsync(ctx->out.h, ctx->out.d, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+        const hipError_t drained = hipStreamSynchronize(ctx->stream);
+        if (rc == FABGPU_OK) rc = hip_to_rc(err != hipSuccess ? err : drained);
+        return rc;
+    }
+    int fetch_verdicts(uint64_t* verdict_bits, uint8_t* status) {
+        if (fetch(status ? st_off + n : words * 8)) return rc;
+        memcpy(verdict_bits, ctx->out.h, words * 8);
+        if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
+        return FABGPU_OK;
+    }
+    int fetch_digests(uint8_t* digests) {
+        if (fetch(n * 32)) return rc;
+        memcpy(digests, ctx->out.h, n * 32);
+        return FABGPU_OK;
+    }
+};
+
+int fabgpu_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* e, const uint8_t* r,
+                             const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    if (!ctx || (n && (!qx || !qy || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    HostStage h(ctx, n);
+    h.fields(ctx->fields, HostStage::OVERLAP, nullptr, {qx, qy, e, r, s});
+    if (h.ready())
+        h.rc = fabgpu_p256_verify_batch_dev(ctx, n, h.field(0), h.field(1), h.field(2), h.field(3), h.field(4), h.dout(), h.dstatus(status), ctx->stream);
+    return h.fetch_verdicts(verdict_bits, status);
+}
+
+int fabgpu_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint32_t* key_id, const uint8_t* e, const uint8_t* r, const uint8_t* s,
+                                   uint64_t* verdict_bits, uint8_t* status) {
+    if (!ctx || (n && (!key_id || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (n > 0x7FFFFFF0ull / 100) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    HostStage h(ctx, n);
+    h.fields(ctx->keyed, HostStage::ID_COLUMN, key_id, {e, r, s});
+    if (h.ready())
+        h.rc = fabgpu_p256_verify_batch_keyed_dev(ctx, n, h.ids(), h.field(0), h.field(1), h.field(2), h.dout(), h.dstatus(status), ctx->stream);
+    return h.fetch_verdicts(verdict_bits, status);
+}
+
+// The three message-taking shapes, shared by the hash families: `dev` is the family's device-resident twin (SHA-256 here, SHA3-256
+// below).
+using HashDev = int (*)(fabgpu_ctx*, size_t, const void*, size_t, const void*, void*, void*);
+using HashVerifyDev = int (*)(fabgpu_ctx*, size_t, const void*, size_t, const void*, const void*, const void*, const void*, const void*, void*, void*, void*);
+using HashVerifyKeyedDev = int (*)(fabgpu_ctx*, size_t, const void*, size_t, const void*, const void*, const void*, const void*, void*, void*, void*);
+
+static int hash_batch_host(HashDev dev, fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, uint8_t* digests) {
     if (!ctx || (n && (!off || !digests))) return FABGPU_EINVAL;
     if (n > 0x7FFFFFF0ull / 32) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
-    size_t ab = 0;
-    int rc = stage_messages(ctx, n, arena, off, &ab);
-    if (rc) return rc;
-    if ((rc = ctx->out.ensure(n * 32))) return rc;
-    rc = fabgpu_sha256_batch_dev(ctx, n, ctx->arena.d, ab, ctx->offs.d, ctx->out.d, ctx->stream);
-    if (rc) return rc;
-    hipError_t err = hipMemcpyAsync(ctx->out.h, ctx->out.d, n * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    memcpy(digests, ctx->out.h, n * 32);
-    return FABGPU_OK;
+    HostStage h(ctx, n, true);
+    h.messages(arena, off);
+    if (h.ready()) h.rc = dev(ctx, n, ctx->arena.d, h.ab, ctx->offs.d, h.dout(), ctx->stream);
+    return h.fetch_digests(digests);
 }
 
-int fabgpu_sha256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx,
-                                    const uint8_t* qy, const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+static int hash_verify_host(HashVerifyDev dev, fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx, const uint8_t* qy,
+                            const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
     if (!ctx || (n && (!off || !qx || !qy || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
     if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
-    size_t ab = 0;
-    int rc = stage_messages(ctx, n, arena, off, &ab);
-    if (rc) return rc;
-    const size_t fb = n * 32, words = (n + 63) / 64;
-    const size_t st_off = round_up(words * 8, 64);
-    if ((rc = ctx->fields.ensure(4 * fb)) || (rc = ctx->out.ensure(st_off + n))) return rc;
-    uint8_t* h = (uint8_t*)ctx->fields.h;
-    memcpy(h, qx, fb); memcpy(h + fb, qy, fb); memcpy(h + 2 * fb, r, fb); memcpy(h + 3 * fb, s, fb);
-    uint8_t* d = (uint8_t*)ctx->fields.d;
-    uint8_t* dout = (uint8_t*)ctx->out.d;
-    hipError_t err = hipMemcpyAsync(d, h, 4 * fb, hipMemcpyHostToDevice, ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    rc = fabgpu_sha256_p256_verify_batch_dev(ctx, n, ctx->arena.d, ab, ctx->offs.d, d, d + fb, d + 2 * fb, d + 3 * fb, dout,
-                                             status ? dout + st_off : nullptr, ctx->stream);
-    if (rc) return rc;
-    err = hipMemcpyAsync(ctx->out.h, dout, status ? st_off + n : words * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    memcpy(verdict_bits, ctx->out.h, words * 8);
-    if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
-    return FABGPU_OK;
+    HostStage h(ctx, n);
+    h.messages(arena, off);
+    h.fields(ctx->fields, 0, nullptr, {qx, qy, r, s});
+    if (h.ready())
+        h.rc = dev(ctx, n, ctx->arena.d, h.ab, ctx->offs.d, h.field(0), h.field(1), h.field(2), h.field(3), h.dout(), h.dstatus(status), ctx->stream);
+    return h.fetch_verdicts(verdict_bits, status);
+}
+
+static int hash_verify_keyed_host(HashVerifyKeyedDev dev, fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
+                                  const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    if (!ctx || (n && (!off || !key_id || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    HostStage h(ctx, n);
+    h.messages(arena, off);
+    h.fields(ctx->keyed, HostStage::ID_COLUMN, key_id, {r, s});
+    if (h.ready()) h.rc = dev(ctx, n, ctx->arena.d, h.ab, ctx->offs.d, h.ids(), h.field(0), h.field(1), h.dout(), h.dstatus(status), ctx->stream);
+    return h.fetch_verdicts(verdict_bits, status);
+}
+
+int fabgpu_sha256_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, uint8_t* digests) {
+    return hash_batch_host(fabgpu_sha256_batch_dev, ctx, n, arena, off, digests);
+}
+
+int fabgpu_sha256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx,
+                                    const uint8_t* qy, const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    return hash_verify_host(fabgpu_sha256_p256_verify_batch_dev, ctx, n, arena, off, qx, qy, r, s, verdict_bits, status);
+}
+
+int fabgpu_sha256_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
+                                          const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    return hash_verify_keyed_host(fabgpu_sha256_p256_verify_batch_keyed_dev, ctx, n, arena, off, key_id, r, s, verdict_bits, status);
 }
 
 int fabgpu_idemix_nym_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* issuer_id,
@@ -1594,60 +1623,13 @@ int fabgpu_idemix_nym_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* are
     if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
-    size_t ab = 0;
-    int rc = stage_messages(ctx, n, arena, off, &ab);
-    if (rc) return rc;
-    const size_t fb = n * 32, kb = round_up(n * 4, 64), words = (n + 63) / 64;
-    const size_t st_off = round_up(words * 8, 64);
-    if ((rc = ctx->nym.ensure(kb + 6 * fb)) || (rc = ctx->out.ensure(st_off + n))) return rc;
-    uint8_t* h = (uint8_t*)ctx->nym.h;
-    if (issuer_id) memcpy(h, issuer_id, n * 4);
-    const uint8_t* src[6] = {nym_x, nym_y, proof_c, proof_s_sk, proof_s_r_nym, nonce};
-    for (int f = 0; f < 6; f++) memcpy(h + kb + f * fb, src[f], fb);
-    uint8_t* d = (uint8_t*)ctx->nym.d;
-    uint8_t* dout = (uint8_t*)ctx->out.d;
-    hipError_t err = hipMemcpyAsync(d, h, kb + 6 * fb, hipMemcpyHostToDevice, ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    rc = fabgpu_idemix_nym_verify_batch_dev(ctx, n, ctx->arena.d, ab, ctx->offs.d, issuer_id ? d : nullptr, d + kb, d + kb + fb, d + kb + 2 * fb,
-                                            d + kb + 3 * fb, d + kb + 4 * fb, d + kb + 5 * fb, dout, status ? dout + st_off : nullptr, ctx->stream);
-    if (rc) return rc;
-    err = hipMemcpyAsync(ctx->out.h, dout, status ? st_off + n : words * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    memcpy(verdict_bits, ctx->out.h, words * 8);
-    if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
-    return FABGPU_OK;
-}
-
-int fabgpu_sha256_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
-                                          const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
-    if (!ctx || (n && (!off || !key_id || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
-    if (n == 0) return FABGPU_OK;
-    if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    size_t ab = 0;
-    int rc = stage_messages(ctx, n, arena, off, &ab);
-    if (rc) return rc;
-    const size_t fb = n * 32, kb = round_up(n * 4, 64), words = (n + 63) / 64;
-    const size_t st_off = round_up(words * 8, 64);
-    if ((rc = ctx->keyed.ensure(kb + 2 * fb)) || (rc = ctx->out.ensure(st_off + n))) return rc;
-    uint8_t* h = (uint8_t*)ctx->keyed.h;
-    memcpy(h, key_id, n * 4); memcpy(h + kb, r, fb); memcpy(h + kb + fb, s, fb);
-    uint8_t* d = (uint8_t*)ctx->keyed.d;
-    uint8_t* dout = (uint8_t*)ctx->out.d;
-    hipError_t err = hipMemcpyAsync(d, h, kb + 2 * fb, hipMemcpyHostToDevice, ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    rc = fabgpu_sha256_p256_verify_batch_keyed_dev(ctx, n, ctx->arena.d, ab, ctx->offs.d, d, d + kb, d + kb + fb, dout,
-                                                   status ? dout + st_off : nullptr, ctx->stream);
-    if (rc) return rc;
-    err = hipMemcpyAsync(ctx->out.h, dout, status ? st_off + n : words * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    memcpy(verdict_bits, ctx->out.h, words * 8);
-    if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
-    return FABGPU_OK;
+    HostStage h(ctx, n);
+    h.messages(arena, off);
+    h.fields(ctx->nym, HostStage::ID_COLUMN, issuer_id, {nym_x, nym_y, proof_c, proof_s_sk, proof_s_r_nym, nonce});
+    if (h.ready())
+        h.rc = fabgpu_idemix_nym_verify_batch_dev(ctx, n, ctx->arena.d, h.ab, ctx->offs.d, issuer_id ? h.ids() : nullptr, h.field(0), h.field(1), h.field(2),
+                                                  h.field(3), h.field(4), h.field(5), h.dout(), h.dstatus(status), ctx->stream);
+    return h.fetch_verdicts(verdict_bits, status);
 }
 
 // ---- SHA3-256 (sha3_kernels.hip): an MSP of the SHA3 hash family (msp/identities.go:216-224) ---------------------------------
@@ -1657,15 +1639,11 @@ int fabgpu_sha256_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8
 // chosen by n and the context's flags exactly as for a caller who brings digests.
 int fabgpu_sha3_256_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, void* stream) {
     if (!ctx || (n && (!arena || !off || !digests))) return FABGPU_EINVAL;
-    if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
+    if (dev_too_big(n, arena_bytes)) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     DeviceGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    if (ctx->time_kernels) hipEventRecord(ctx->ev0, st);
-    hipError_t err = launch_sha3_256_batch((uint32_t)n, arena, arena_bytes, off, false, digests, st);
-    if (ctx->time_kernels) hipEventRecord(ctx->ev1, st);
-    ctx->timed = ctx->time_kernels;
-    return hip_to_rc(launched(ctx, err));
+    return timed_launch(ctx, st, 0, [&](void*) { return launch_sha3_256_batch((uint32_t)n, arena, arena_bytes, off, false, digests, st); });
 }
 
 // the digests of a (possibly prefixed) batch into `dig`, then the verify-only entry point over them; key_id == nullptr: fresh keys
@@ -1693,7 +1671,7 @@ static int sha3_then_verify_dev(fabgpu_ctx* ctx, size_t n, const void* arena, si
 int fabgpu_sha3_256_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, const void* qx,
                                           const void* qy, const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
     if (!ctx || (n && (!arena || !off || !qx || !qy || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
+    if (dev_too_big(n, arena_bytes)) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     DeviceGuard g(ctx->device);
     return sha3_then_verify_dev(ctx, n, arena, arena_bytes, off, ShaPrefixArgs(), qx, qy, nullptr, r, s, verdict_bits, status, (hipStream_t)stream);
@@ -1702,92 +1680,24 @@ int fabgpu_sha3_256_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void*
 int fabgpu_sha3_256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, const void* key_id,
                                                 const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
     if (!ctx || (n && (!arena || !off || !key_id || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
+    if (dev_too_big(n, arena_bytes)) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     DeviceGuard g(ctx->device);
     return sha3_then_verify_dev(ctx, n, arena, arena_bytes, off, ShaPrefixArgs(), nullptr, nullptr, key_id, r, s, verdict_bits, status, (hipStream_t)stream);
 }
 
 int fabgpu_sha3_256_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, uint8_t* digests) {
-    if (!ctx || (n && (!off || !digests))) return FABGPU_EINVAL;
-    if (n > 0x7FFFFFF0ull / 32) return FABGPU_ETOOBIG;
-    if (n == 0) return FABGPU_OK;
-    if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    size_t ab = 0;
-    int rc = stage_messages(ctx, n, arena, off, &ab);
-    if (rc) return rc;
-    if ((rc = ctx->out.ensure(n * 32))) return rc;
-    rc = fabgpu_sha3_256_batch_dev(ctx, n, ctx->arena.d, ab, ctx->offs.d, ctx->out.d, ctx->stream);
-    if (rc) return rc;
-    hipError_t err = hipMemcpyAsync(ctx->out.h, ctx->out.d, n * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    memcpy(digests, ctx->out.h, n * 32);
-    return FABGPU_OK;
+    return hash_batch_host(fabgpu_sha3_256_batch_dev, ctx, n, arena, off, digests);
 }
 
 int fabgpu_sha3_256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx, const uint8_t* qy,
                                       const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
-    if (!ctx || (n && (!off || !qx || !qy || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
-    if (n == 0) return FABGPU_OK;
-    if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    size_t ab = 0;
-    int rc = stage_messages(ctx, n, arena, off, &ab);
-    if (rc) return rc;
-    const size_t fb = n * 32, words = (n + 63) / 64;
-    const size_t st_off = round_up(words * 8, 64);
-    if ((rc = ctx->fields.ensure(4 * fb)) || (rc = ctx->out.ensure(st_off + n))) return rc;
-    uint8_t* h = (uint8_t*)ctx->fields.h;
-    memcpy(h, qx, fb); memcpy(h + fb, qy, fb); memcpy(h + 2 * fb, r, fb); memcpy(h + 3 * fb, s, fb);
-    uint8_t* d = (uint8_t*)ctx->fields.d;
-    uint8_t* dout = (uint8_t*)ctx->out.d;
-    hipError_t err = hipMemcpyAsync(d, h, 4 * fb, hipMemcpyHostToDevice, ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    rc = fabgpu_sha3_256_p256_verify_batch_dev(ctx, n, ctx->arena.d, ab, ctx->offs.d, d, d + fb, d + 2 * fb, d + 3 * fb, dout,
-                                               status ? dout + st_off : nullptr, ctx->stream);
-    if (rc) return rc;
-    err = hipMemcpyAsync(ctx->out.h, dout, status ? st_off + n : words * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    memcpy(verdict_bits, ctx->out.h, words * 8);
-    if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
-    return FABGPU_OK;
+    return hash_verify_host(fabgpu_sha3_256_p256_verify_batch_dev, ctx, n, arena, off, qx, qy, r, s, verdict_bits, status);
 }
 
 int fabgpu_sha3_256_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
                                             const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
-    if (!ctx || (n && (!off || !key_id || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
-    if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
-    if (n == 0) return FABGPU_OK;
-    if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    size_t ab = 0;
-    int rc = stage_messages(ctx, n, arena, off, &ab);
-    if (rc) return rc;
-    const size_t fb = n * 32, kb = round_up(n * 4, 64), words = (n + 63) / 64;
-    const size_t st_off = round_up(words * 8, 64);
-    if ((rc = ctx->keyed.ensure(kb + 2 * fb)) || (rc = ctx->out.ensure(st_off + n))) return rc;
-    uint8_t* h = (uint8_t*)ctx->keyed.h;
-    memcpy(h, key_id, n * 4); memcpy(h + kb, r, fb); memcpy(h + kb + fb, s, fb);
-    uint8_t* d = (uint8_t*)ctx->keyed.d;
-    uint8_t* dout = (uint8_t*)ctx->out.d;
-    hipError_t err = hipMemcpyAsync(d, h, kb + 2 * fb, hipMemcpyHostToDevice, ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    rc = fabgpu_sha3_256_p256_verify_batch_keyed_dev(ctx, n, ctx->arena.d, ab, ctx->offs.d, d, d + kb, d + kb + fb, dout,
-                                                     status ? dout + st_off : nullptr, ctx->stream);
-    if (rc) return rc;
-    err = hipMemcpyAsync(ctx->out.h, dout, status ? st_off + n : words * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    memcpy(verdict_bits, ctx->out.h, words * 8);
-    if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
-    return FABGPU_OK;
+    return hash_verify_keyed_host(fabgpu_sha3_256_p256_verify_batch_keyed_dev, ctx, n, arena, off, key_id, r, s, verdict_bits, status);
 }
 
 // ---- identity.Verify over a described batch: optional shared prefixes, fresh or registered keys ------------------------
