@@ -310,87 +310,20 @@ int fabgpu_csp_identity_verify_batch2(fabgpu_csp* csp, size_t n, const uint8_t* 
     return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
 }
 
-int fabgpu_csp_block_preverify(fabgpu_csp* csp, const uint8_t* block, size_t len, uint32_t* n_tx, uint8_t* tx_flags, uint8_t* tx_type,
-                               uint32_t cap_tx, uint32_t* n_tuples, uint32_t* tuple_tx, uint8_t* tuple_kind, uint8_t* tuple_status,
-                               uint32_t cap_tuples) {
-    if (!csp || !block || !n_tx || !n_tuples) return FABGPU_EINVAL;
+// The block pass behind both C entries: the walk on the device (block_walk_dev.h); a block it declines takes the host walk.
+// uncounted_tuples: what ps->n_tuples says when FABGPU_ETOOBIG comes before the device has counted the tuples (the transactions or the
+// tail did not fit).
+static int block_pass(fabgpu_csp* csp, fabgpu_block_pass* ps, uint32_t uncounted_tuples) {
     if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
+    const auto t0 = std::chrono::steady_clock::now();
     const bool timing = csp->csp->GetOption("pass_timing") > 0;           // stage breakdown on stderr (tools/bench_block.py --timing)
-    auto t0 = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    std::unique_ptr<GPUCSP::BlockUpload> up_p = csp->upload_for(block, len, 0, false);   // the block travels while it is walked
-    GPUCSP::BlockUpload& up = *up_p;
-    const bool per_tuple = tuple_tx != nullptr || tuple_kind != nullptr || tuple_status != nullptr;
-    static thread_local ParsedBlock pb;                     // storage reused from block to block (a few MB: no page faults per block)
-    static thread_local BlockVerdicts v;                    // answer arrays keep their capacity from block to block
-    bool done = false;
-    {   // the walk on the device (block_walk_dev.h); a block it declines takes the host walk below
-        const char* why = "";
-        uint32_t ntup = 0;
-        // (room for per-tuple answers only matters to a caller that asked for some)
-        const int r = csp->csp->PreVerifyBlockOnDevice(block, len, pb, v, up, PassOptions(), tuple_tx != nullptr || tuple_kind != nullptr ? GPUCSP::WANT_TUPLES : 0u, cap_tx,
-                                                       per_tuple ? cap_tuples : 0xFFFFFFFFu, &ntup, &why);
-        if (r != FABGPU_ETOOBIG) csp->note_route(r == 0, why);
-        if (r == FABGPU_ETOOBIG) {
-            *n_tx = pb.n_tx;
-            *n_tuples = ntup;
-            csp->park(std::move(up_p));                      // the retry finds its upload again
-            return FABGPU_ETOOBIG;
-        }
-        if (r < 0) return r == FABGPU_EINVAL || r == FABGPU_ENOMEM ? r : FABGPU_ELAUNCH;
-        done = r == 0;
-        if (timing && done)
-            fprintf(stderr, "fabgpu pass (device walk): total %.2f ms (outline + identity table %.2f, wait for upload %.2f, device %.2f, bookkeeping %.2f)\n",
-                    ms(t0, std::chrono::steady_clock::now()), v.ms_gates, v.ms_upload_wait, v.ms_device, v.ms_post);
-        if (timing && !done) fprintf(stderr, "fabgpu pass: device walk declined (%s)\n", why);
-    }
-    if (done) {
-        *n_tx = pb.n_tx;
-        *n_tuples = (uint32_t)v.tuple_status.size();
-    } else {
-        if (!ParseBlock(block, len, pb, WalkThreads())) return FABGPU_EINVAL;
-        auto t1 = std::chrono::steady_clock::now();
-        *n_tx = pb.n_tx;
-        *n_tuples = (uint32_t)pb.tuples.size();
-        if (pb.n_tx > cap_tx || (per_tuple && pb.tuples.size() > cap_tuples)) {          // counts are set: retry with room (nothing was launched)
-            csp->park(std::move(up_p));
-            return FABGPU_ETOOBIG;
-        }
-        Error e = csp->csp->PreVerifyParsed(block, pb, v, &up);
-        if (timing) {
-            auto t2 = std::chrono::steady_clock::now();
-            fprintf(stderr, "fabgpu pass: walk %.2f ms, gates + submission + flags %.2f ms (gates %.2f, wait for upload %.2f, device call %.2f, idemix creators %.2f, memo %.2f)\n", ms(t0, t1),
-                    ms(t1, t2), v.ms_gates, v.ms_upload_wait, v.ms_device, v.ms_nym, v.ms_memo);
-        }
-        if (!e.ok()) return FABGPU_ELAUNCH;
-    }
-    if (tx_flags && v.n_tx) memcpy(tx_flags, v.tx_flags.data(), v.n_tx);
-    if (tx_type && v.n_tx) memcpy(tx_type, v.tx_type.data(), v.n_tx);
-    size_t nt = v.tuple_status.size();
-    if (tuple_tx && nt) memcpy(tuple_tx, v.tuple_tx.data(), nt * 4);
-    if (tuple_kind && nt) memcpy(tuple_kind, v.tuple_kind.data(), nt);
-    if (tuple_status && nt) memcpy(tuple_status, v.tuple_status.data(), nt);
-    return FABGPU_OK;
-}
-
-// A caller that gives up after FABGPU_ETOOBIG (no retry will come) drops the upload the library kept for it.  1: one was dropped, 0: none.
-int fabgpu_csp_block_pass_abandon(fabgpu_csp* csp) { return csp ? (csp->abandon() ? 1 : 0) : FABGPU_EINVAL; }
-
-int fabgpu_csp_block_preverify2(fabgpu_csp* csp, fabgpu_block_pass* ps) {
-    if (!csp || !ps || !ps->block) return FABGPU_EINVAL;
-    if (ps->flags & ~(uint32_t)(FABGPU_PASS_SEED_MEMO | FABGPU_PASS_NO_BLOCK_SIGS)) return FABGPU_EINVAL;
-    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
-    auto t0 = std::chrono::steady_clock::now();
-    const bool timing = csp->csp->GetOption("pass_timing") > 0;
     // (a memo-seeding pass keeps the block's bytes in host memory of the device context: the digest memo compares bccsp.Hash callers' bytes with them)
-    std::unique_ptr<GPUCSP::BlockUpload> up_p = csp->upload_for(ps->block, ps->len, ps->block_seq, (ps->flags & FABGPU_PASS_SEED_MEMO) != 0);
+    std::unique_ptr<GPUCSP::BlockUpload> up_p = csp->upload_for(ps->block, ps->len, ps->block_seq, (ps->flags & FABGPU_PASS_SEED_MEMO) != 0);   // the block travels while it is walked
     GPUCSP::BlockUpload& up = *up_p;
     // room for per-tuple answers only matters to a caller that asked for some (the Go binding asks for flags alone)
     const bool per_tuple = ps->tuple_tx || ps->tuple_kind || ps->tuple_status || ps->tuple_spans || ps->tuple_digest || ps->tuple_hashed || ps->tuple_qxy;
     const uint32_t cap_tuples = per_tuple ? ps->cap_tuples : 0xFFFFFFFFu;
-    static thread_local ParsedBlock pb;
+    static thread_local ParsedBlock pb;                     // storage reused from block to block (a few MB: no page faults per block)
     static thread_local BlockVerdicts v;                    // answer arrays keep their capacity from block to block
     PassOptions opt;
     opt.seed_memo = (ps->flags & FABGPU_PASS_SEED_MEMO) != 0;
@@ -401,51 +334,45 @@ int fabgpu_csp_block_preverify2(fabgpu_csp* csp, fabgpu_block_pass* ps) {
     ps->memo_seeded = 0;
     ps->n_keyed = 0;
     ps->n_device_decoded = 0;
-    bool done = false;
-    {   // the walk on the device (block_walk_dev.h); a block it declines takes the host walk below
-        const char* why = "";
-        uint32_t ntup = 0;
-        const unsigned want = (ps->tuple_tx || ps->tuple_kind || ps->tuple_spans ? GPUCSP::WANT_TUPLES : 0u) | (ps->tuple_qxy ? GPUCSP::WANT_QXY : 0u);
-        const int r = csp->csp->PreVerifyBlockOnDevice(ps->block, ps->len, pb, v, up, opt, want, ps->cap_tx, cap_tuples, &ntup, &why);
-        if (r != FABGPU_ETOOBIG) csp->note_route(r == 0, why);
-        if (r == 0 || r == FABGPU_ETOOBIG) {
-            ps->n_tx = pb.n_tx;
-            ps->n_tuples = r == 0 ? (uint32_t)v.tuple_status.size() : (ntup ? ntup : ps->cap_tuples);   // (0: not counted yet - the transactions or the tail did not fit)
-            ps->n_block_sigs = pb.n_block_sigs;
-            ps->tail_base = pb.tail_base;
-            ps->tail_len = (uint32_t)pb.tail.size();
-            ps->block_sigs_understood = pb.block_sigs_understood ? 1 : 0;
-        }
-        if (r == FABGPU_ETOOBIG) {
-            csp->park(std::move(up_p));                      // the retry - same buffer, length and block_seq - finds its upload again
-            return FABGPU_ETOOBIG;
-        }
-        if (r < 0) return r == FABGPU_EINVAL || r == FABGPU_ENOMEM ? r : FABGPU_ELAUNCH;
-        done = r == 0;
-        if (timing) {
-            if (done)
-                fprintf(stderr, "fabgpu pass2 (device walk): total %.2f ms (outline + identity table %.2f, wait for upload %.2f, device %.2f, memo %.2f)\n",
-                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), v.ms_gates, v.ms_upload_wait, v.ms_device, v.ms_memo);
-            else
-                fprintf(stderr, "fabgpu pass2: device walk declined (%s)\n", why);
-        }
-    }
-    if (!done) {
-        if (!ParseBlock(ps->block, ps->len, pb, WalkThreads())) return FABGPU_EINVAL;
+    auto counts_out = [&](uint32_t n_tuples) {
         ps->n_tx = pb.n_tx;
-        ps->n_tuples = (uint32_t)pb.tuples.size();
+        ps->n_tuples = n_tuples;
         ps->n_block_sigs = pb.n_block_sigs;
         ps->tail_base = pb.tail_base;
         ps->tail_len = (uint32_t)pb.tail.size();
         ps->block_sigs_understood = pb.block_sigs_understood ? 1 : 0;
-        if (pb.n_tx > ps->cap_tx || pb.tuples.size() > cap_tuples || (ps->tail && pb.tail.size() > ps->tail_cap)) {
+    };
+    const char* why = "";
+    uint32_t ntup = 0;
+    const unsigned want = (ps->tuple_tx || ps->tuple_kind || ps->tuple_spans ? GPUCSP::WANT_TUPLES : 0u) | (ps->tuple_qxy ? GPUCSP::WANT_QXY : 0u);
+    const int r = csp->csp->PreVerifyBlockOnDevice(ps->block, ps->len, pb, v, up, opt, want, ps->cap_tx, cap_tuples, &ntup, &why);
+    if (r != FABGPU_ETOOBIG) csp->note_route(r == 0, why);
+    if (r == FABGPU_ETOOBIG) {
+        counts_out(ntup ? ntup : uncounted_tuples);
+        csp->park(std::move(up_p));                          // the retry - same buffer, length and block_seq - finds its upload again
+        return FABGPU_ETOOBIG;
+    }
+    if (r < 0) return r == FABGPU_EINVAL || r == FABGPU_ENOMEM ? r : FABGPU_ELAUNCH;
+    const bool done = r == 0;
+    if (timing && done)
+        fprintf(stderr, "fabgpu pass (device walk): total %.2f ms (outline + identity table %.2f, wait for upload %.2f, device %.2f, bookkeeping %.2f, memo %.2f)\n",
+                ms_since(t0), v.ms_gates, v.ms_upload_wait, v.ms_device, v.ms_post, v.ms_memo);
+    if (timing && !done) fprintf(stderr, "fabgpu pass: device walk declined (%s)\n", why);
+    if (done) {
+        counts_out((uint32_t)v.tuple_status.size());
+    } else {
+        if (!ParseBlock(ps->block, ps->len, pb, WalkThreads())) return FABGPU_EINVAL;
+        const double ms_walk = ms_since(t0);
+        const auto t1 = std::chrono::steady_clock::now();
+        counts_out((uint32_t)pb.tuples.size());
+        if (pb.n_tx > ps->cap_tx || pb.tuples.size() > cap_tuples || (ps->tail && pb.tail.size() > ps->tail_cap)) {   // counts are set: retry with room (nothing was launched)
             csp->park(std::move(up_p));
             return FABGPU_ETOOBIG;
         }
         Error e = csp->csp->PreVerifyParsed(ps->block, pb, v, &up, opt);
         if (timing)
-            fprintf(stderr, "fabgpu pass2: gates %.2f ms, wait for upload %.2f, device call %.2f, idemix creators %.2f, memo %.2f\n", v.ms_gates, v.ms_upload_wait,
-                    v.ms_device, v.ms_nym, v.ms_memo);
+            fprintf(stderr, "fabgpu pass: walk %.2f ms, gates + submission + flags %.2f ms (gates %.2f, wait for upload %.2f, device call %.2f, idemix creators %.2f, memo %.2f)\n",
+                    ms_walk, ms_since(t1), v.ms_gates, v.ms_upload_wait, v.ms_device, v.ms_nym, v.ms_memo);
         if (!e.ok()) return FABGPU_ELAUNCH;
     }
     const size_t nt = v.tuple_status.size();
@@ -476,6 +403,38 @@ int fabgpu_csp_block_preverify2(fabgpu_csp* csp, fabgpu_block_pass* ps) {
     ps->ms_stage[3] = (float)(done ? v.ms_post : v.ms_memo);
     ps->device_context = up.dev;
     return FABGPU_OK;
+}
+
+int fabgpu_csp_block_preverify(fabgpu_csp* csp, const uint8_t* block, size_t len, uint32_t* n_tx, uint8_t* tx_flags, uint8_t* tx_type,
+                               uint32_t cap_tx, uint32_t* n_tuples, uint32_t* tuple_tx, uint8_t* tuple_kind, uint8_t* tuple_status,
+                               uint32_t cap_tuples) {
+    if (!csp || !block || !n_tx || !n_tuples) return FABGPU_EINVAL;
+    fabgpu_block_pass ps;                                    // the second entry's call with no flags, block_seq 0 and these five arrays
+    memset(&ps, 0, sizeof(ps));
+    ps.block = block;
+    ps.len = len;
+    ps.cap_tx = cap_tx;
+    ps.cap_tuples = cap_tuples;
+    ps.n_tx = *n_tx;                                         // (an error that comes before the counts leaves the caller's two as they are)
+    ps.n_tuples = *n_tuples;
+    ps.tx_flags = tx_flags;
+    ps.tx_type = tx_type;
+    ps.tuple_tx = tuple_tx;
+    ps.tuple_kind = tuple_kind;
+    ps.tuple_status = tuple_status;
+    const int rc = block_pass(csp, &ps, 0);
+    *n_tx = ps.n_tx;
+    *n_tuples = ps.n_tuples;
+    return rc;
+}
+
+// A caller that gives up after FABGPU_ETOOBIG (no retry will come) drops the upload the library kept for it.  1: one was dropped, 0: none.
+int fabgpu_csp_block_pass_abandon(fabgpu_csp* csp) { return csp ? (csp->abandon() ? 1 : 0) : FABGPU_EINVAL; }
+
+int fabgpu_csp_block_preverify2(fabgpu_csp* csp, fabgpu_block_pass* ps) {
+    if (!csp || !ps || !ps->block) return FABGPU_EINVAL;
+    if (ps->flags & ~(uint32_t)(FABGPU_PASS_SEED_MEMO | FABGPU_PASS_NO_BLOCK_SIGS)) return FABGPU_EINVAL;
+    return block_pass(csp, ps, ps->cap_tuples);              // (n_tuples = cap_tuples: "this many fit" while the device has not counted)
 }
 
 // Which way the passes of this provider went: walked on the device / walked on the host, and why the last block was declined.

@@ -1413,6 +1413,36 @@ int64_t GPUCSP::RegisterIdemixMSP(const std::string& mspid, const uint8_t* ipk_r
     return k.issuer_id;
 }
 
+namespace {
+constexpr int kGateMax = 16;     // most worker threads a pass runs at once: the pool + the caller (worker_pool.h)
+// a stage clock of the pass: the milliseconds from its construction to the end of its scope go into `ms`
+struct StageClock {
+    double& ms;
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    ~StageClock() { ms = ms_since(t0); }
+};
+}  // namespace
+
+GPUCSP::ScratchLease::ScratchLease(const GPUCSP* c_) : c(c_) {
+    std::lock_guard<std::mutex> lk(c->pass_mu_);
+    if (!c->scratch_free_.empty()) {
+        p = std::move(c->scratch_free_.back());
+        c->scratch_free_.pop_back();
+    }
+    if (!p) p.reset(new PassScratch);
+}
+GPUCSP::ScratchLease::~ScratchLease() {
+    std::lock_guard<std::mutex> lk(c->pass_mu_);
+    if (c->scratch_free_.size() < c->scratch_free_max_) c->scratch_free_.push_back(std::move(p));
+}
+
+bool GPUCSP::EarnTableLocked(CachedIdentity& c) const {
+    if (!c.p256 || c.key_id >= 0 || c.registering || c.hits < id_register_after_ || id_registered_ >= id_max_registered_) return false;
+    c.registering = true;
+    id_registered_++;
+    return true;
+}
+
 // identities that earned a device comb table during a block: built and uploaded outside idmu_ (6 ms of host work each)
 void GPUCSP::RegisterQueued(const std::vector<std::string>& to_register) const {
     if (to_register.empty()) {
@@ -1466,21 +1496,8 @@ void GPUCSP::SeedMemo(const uint8_t* block, const ParsedBlock& pb, BlockVerdicts
     // verdict memo: one entry per tuple the device hashed and decided, keyed on (key, signature bytes, device digest).  The block's
     // table is built here, outside the memo lock, by the pass's worker threads; publishing it is one push under the lock.
     {
-        auto clk_memo = std::chrono::steady_clock::now();
-        struct MemoClock {
-            BlockVerdicts& o;
-            std::chrono::steady_clock::time_point t0;
-            ~MemoClock() { o.ms_memo = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-        } memo_clock{out, clk_memo};
-        std::shared_ptr<BlockMemo> bm;
-        {
-            std::unique_lock<BigReaderLock> lk(memo_mu_);
-            if (!memo_free_.empty()) {
-                bm = memo_free_.back();
-                memo_free_.pop_back();
-            }
-        }
-        if (!bm) bm.reset(new BlockMemo);
+        StageClock memo_clock{out.ms_memo};
+        std::shared_ptr<BlockMemo> bm = TakeMemoTable(/*prefer_pinned=*/false);
         bm->seq = opt.block_seq;
         bm->n = 0;
         // Which tuples get an entry: the ones the device hashed and decided with a status bccsp.Verify decides itself (0 valid, 1 bad math,
@@ -1611,10 +1628,7 @@ void GPUCSP::SeedMemo(const uint8_t* block, const ParsedBlock& pb, BlockVerdicts
             // The digest memo's index, the host's version of walk_memo_index_kernel: when the block's upload left a host copy of it
             // (BlockUpload::copy), every entry's message spans and a slot found from walk::msg_fingerprint of the message as it lies in
             // that copy.  Without a copy the table answers bccsp.Verify only.
-            host_copy_release(&bm->copy);
             bm->hslots_v = bm->hspans_v = nullptr;
-            bm->tail.clear();
-            bm->tail_base = 0;
             if (up) (void)up->join();                      // (usually long joined: the submission waited for it)
             if (up && up->copy.p && HashMemoEnabled()) {
                 try {
@@ -1651,16 +1665,11 @@ void GPUCSP::SeedMemo(const uint8_t* block, const ParsedBlock& pb, BlockVerdicts
                     else run_workers(ft, index_some);
                     bm->hslots_v = bm->hslots.data();
                     bm->hspans_v = bm->hspans.data();
-                    bm->copy = up->copy;
-                    up->copy = HostCopy();
-                    if (!pb.tail.empty()) {
-                        bm->tail = pb.tail;
-                        bm->tail_base = pb.tail_base;
-                    }
                 } catch (...) {                            // bad_alloc: the verdict memo stands, the digest memo does not
                     bm->hslots_v = bm->hspans_v = nullptr;
                 }
             }
+            MemoAdoptCopy(*bm, up, pb.tail.data(), pb.tail.size(), pb.tail_base);
             if (!PublishMemo(bm)) out.memo_seeded = 0;
         }
     }
@@ -1683,6 +1692,48 @@ bool GPUCSP::PublishMemo(const std::shared_ptr<BlockMemo>& bm) const {
         memo_blocks_.pop_front();
     }
     return true;
+}
+std::shared_ptr<GPUCSP::BlockMemo> GPUCSP::TakeMemoTable(bool prefer_pinned) const {
+    std::shared_ptr<BlockMemo> bm;
+    {
+        std::unique_lock<BigReaderLock> lk(memo_mu_);
+        if (prefer_pinned)
+            for (auto it = memo_free_.begin(); it != memo_free_.end(); ++it)
+                if ((*it)->pin) {
+                    bm = *it;
+                    memo_free_.erase(it);
+                    break;
+                }
+        if (!bm && !memo_free_.empty()) {
+            bm = memo_free_.back();
+            memo_free_.pop_back();
+        }
+    }
+    if (!bm) bm.reset(new BlockMemo);
+    return bm;
+}
+GPUCSP::MemoReturn::~MemoReturn() {
+    if (!bm) return;
+    std::unique_lock<BigReaderLock> lk(c->memo_mu_);
+    if (c->memo_free_.size() < c->memo_free_max_) c->memo_free_.push_back(bm);
+}
+void GPUCSP::MemoAdoptCopy(BlockMemo& bm, BlockUpload* up, const uint8_t* tail, size_t tail_len, uint32_t tail_base) {
+    host_copy_release(&bm.copy);
+    bm.tail.clear();
+    bm.tail_base = 0;
+    if (!bm.hslots_v || !bm.hspans_v || !up || !up->copy.p) {
+        bm.hslots_v = bm.hspans_v = nullptr;
+        return;
+    }
+    bm.copy = up->copy;
+    up->copy = HostCopy();
+    if (!tail || !tail_len) return;
+    try {
+        bm.tail.assign(tail, tail + tail_len);
+        bm.tail_base = tail_base;
+    } catch (...) {                                        // bad_alloc: the verdict memo stands, the digest memo does not
+        bm.hslots_v = bm.hspans_v = nullptr;
+    }
 }
 
 // ---- the pass with the walk on the device (block_walk_dev.h) ----------------------------------------------------------------
@@ -1793,325 +1844,230 @@ int GPUCSP::WalkBlockOnDevice(const uint8_t* block, size_t len, ParsedBlock& pb,
     return rc;
 }
 
-int GPUCSP::PreVerifyBlockOnDevice(const uint8_t* block, size_t len, ParsedBlock& pb, BlockVerdicts& out, BlockUpload& up, const PassOptions& opt,
-                                   unsigned want, uint32_t cap_tx, uint32_t cap_tuples, uint32_t* n_tuples_out, const char** why) const {
-    static const char* none = "";
-    const char* dummy;
-    if (!why) why = &dummy;
-    *why = none;
-    auto declined = [&](const char* w) {
-        *why = w;
-        return 1;
-    };
-    if (!DeviceWalkEnabled()) return declined("pass_device_walk is off");
-    if (!block || !up.started) return declined("the block was not staged ahead (small block)");
-    ProviderOptions po;
-    {
-        std::lock_guard<std::mutex> lk(opt_mu_);
-        po = opts_;
+// What the steps of one device-route pass share; WalkRequest::user of its two callbacks.
+struct GPUCSP::DevicePass {
+    const uint8_t* block;
+    size_t len;
+    ParsedBlock& pb;
+    BlockVerdicts& out;
+    PassScratch& ps;
+    BlockUpload& up;
+    const PassOptions& opt;
+    Dev& dv;
+    const std::vector<DevIdemixMsp>& msps;
+    bool want_tuples, want_digests, want_qxy, want_nym_issuer, host_counts;
+    uint32_t cap_tx, cap_tuples, n_skipped;
+    std::vector<uint8_t> issuer_hashes;   // 32 bytes per entry of msps, for the device-built memo
+    uint32_t n_tuples = 0;
+    bool too_big = false;
+    // the memo the device fills: a table out of the free list (its pinned room is reused), sized once the tuple count is known
+    BlockMemo* bm = nullptr;
+    bool hash_index = false;              // the upload left a host copy of the block: the device builds the digest memo's index too
+    std::vector<std::string> to_register;
+    std::vector<uint64_t> hit_serials;    // who this block named: they stay in front of the block's newcomers
+};
+
+// the idemix MSPs whose creators the pass verifies (an MSP id registered with two different issuer keys is not among them: its
+// creators stay with bccsp/idemix, as on the host route)
+bool GPUCSP::ListIdemixMsps(std::vector<DevIdemixMsp>& msps) const {
+    std::lock_guard<std::mutex> lk(idmu_);
+    for (const auto& kv : idemix_msps_) {
+        if (kv.second < 0) continue;
+        if (kv.first.size() > WALK_IDEMIX_MSPID_MAX || msps.size() >= WALK_IDEMIX_MSPS_MAX) return false;
+        DevIdemixMsp m;
+        memset(&m, 0, sizeof(m));
+        m.len = (uint32_t)kv.first.size();
+        m.issuer = (int32_t)kv.second;
+        memcpy(m.id, kv.first.data(), kv.first.size());
+        msps.push_back(m);
     }
-    if (po.pass_skip_hash_checks > 0) return declined("pass_skip_hash_checks");
-    Dev& dv = *devs_[(size_t)up.dev];                       // the device the block travelled to (StartBlockUpload chose it)
-    fabgpu_ctx* const ctx_ = dv.ctx;
-    std::atomic<uint64_t>& idtab_version_ = dv.idtab_version;
-    std::vector<uint64_t>& idtab_host_ = dv.idtab_host;
-    // the idemix MSPs whose creators the pass verifies (an MSP id registered with two different issuer keys is not among them: its
-    // creators stay with bccsp/idemix, as on the host route)
-    std::vector<DevIdemixMsp> msps;
-    {
-        std::lock_guard<std::mutex> lk(idmu_);
-        for (const auto& kv : idemix_msps_) {
-            if (kv.second < 0) continue;
-            if (kv.first.size() > WALK_IDEMIX_MSPID_MAX || msps.size() >= WALK_IDEMIX_MSPS_MAX)
-                return declined("more idemix MSPs (or a longer MSP id) than the device route carries");
-            DevIdemixMsp m;
-            memset(&m, 0, sizeof(m));
-            m.len = (uint32_t)kv.first.size();
-            m.issuer = (int32_t)kv.second;
-            memcpy(m.id, kv.first.data(), kv.first.size());
-            msps.push_back(m);
-        }
-    }
-    struct Lease {
-        const GPUCSP* c;
-        std::unique_ptr<PassScratch> p;
-        explicit Lease(const GPUCSP* c_) : c(c_) {
-            std::lock_guard<std::mutex> lk(c->pass_mu_);
-            if (!c->scratch_free_.empty()) {
-                p = std::move(c->scratch_free_.back());
-                c->scratch_free_.pop_back();
-            }
-            if (!p) p.reset(new PassScratch);
-        }
-        ~Lease() {
-            std::lock_guard<std::mutex> lk(c->pass_mu_);
-            if (c->scratch_free_.size() < c->scratch_free_max_) c->scratch_free_.push_back(std::move(p));
-        }
-    } lease(this);
-    PassScratch& ps = *lease.p;
-    auto clk0 = std::chrono::steady_clock::now();
-    if (!OutlineBlock(block, len, pb, ps.env_spans, ps.block_sigs, &ps.payload_spans)) return FABGPU_EINVAL;
-    // The caller's room for per-transaction answers is checked HERE - the outline knows the transaction count - before the upload is
-    // waited for and before anything is launched: a too-small array costs the caller the outline (0.15 ms for 10 000 transactions),
-    // not an upload and two kernels (ADVICE r3; the Go binding used to pay exactly that for every block over 1 024 transactions).
-    if (ps.env_spans.size() / 2 > cap_tx) {
-        pb.n_tx = (uint32_t)(ps.env_spans.size() / 2);
-        if (n_tuples_out) *n_tuples_out = 0;                // (not known yet: the device counts tuples)
-        return FABGPU_ETOOBIG;
-    }
-    // The verdict memo of a device-route pass is built by the device (round 3: block_walk_dev.h WalkOut::memo_*) into pinned memory of a
-    // BlockMemo: keys, offsets, statuses and the slot table come back as they are looked up - no tuple records, digests and keys to bring
-    // back, copy out and read 40 000 signatures out of the host's copy of the block for.  FABGPU_PASS_DEVICE_MEMO=0: SeedMemo, as before.
-    const bool dev_memo = opt.seed_memo && po.pass_device_memo >= 0;
-    const bool host_memo = opt.seed_memo && !dev_memo;
-    const bool want_digests = opt.want_digests || host_memo;
-    const bool want_tuples = (want & WANT_TUPLES) || host_memo, want_qxy = (want & WANT_QXY) || host_memo;
-    const uint32_t n_skipped = opt.block_sigs ? 0 : (uint32_t)ps.block_sigs.size();   // reported (TUPLE_ST_SKIPPED), not submitted
-    if (pb.tail.size() > opt.tail_cap) {                             // the caller wants the tail and has no room for it: say so before anything runs
-        if (n_tuples_out) *n_tuples_out = 0;
-        return FABGPU_ETOOBIG;
-    }
-    // OPTIONAL (FABGPU_PASS_HOST_COUNTS=1; off by default): while the block is on its way up, the per-envelope counts the device walk
-    // starts from (tuples, prefixes, hash checks, gathered bytes - walk::walk_envelope with the counting emitter, the code
-    // walk_count_kernel runs) taken here, on a few threads; the device then needs neither that kernel, nor the scan behind it, nor the
-    // wait for the totals in between.  Measured (round 3, 10 000 tx, tools/host_walk_probe.cpp + tools/gpu_probe_sizes.sh): the device
-    // phase drops 0.92 -> 0.85 ms, but the host's walk is a chain of DRAM misses per envelope - 8.2 ms on one thread, 1.2-1.7 ms on
-    // 8-12, about the whole upload - against 0.10 ms for the count kernel: 4 % off the pass for 8 ms of the peer's CPU per block.
-    // Not a trade a peer wants by default; the entry stays for hosts with idle cores (and as the second source the emit kernel's
-    // count check is tested against).
-    const bool host_counts = po.pass_host_counts > 0;                       // (read per pass: tests run both ways in one process)
+    return true;
+}
+
+// OPTIONAL (FABGPU_PASS_HOST_COUNTS=1; off by default): while the block is on its way up, the per-envelope counts the device walk
+// starts from (tuples, prefixes, hash checks, gathered bytes - walk::walk_envelope with the counting emitter, the code
+// walk_count_kernel runs) taken here, on a few threads; the device then needs neither that kernel, nor the scan behind it, nor the
+// wait for the totals in between.  Measured (round 3, 10 000 tx, tools/host_walk_probe.cpp + tools/gpu_probe_sizes.sh): the device
+// phase drops 0.92 -> 0.85 ms, but the host's walk is a chain of DRAM misses per envelope - 8.2 ms on one thread, 1.2-1.7 ms on
+// 8-12, about the whole upload - against 0.10 ms for the count kernel: 4 % off the pass for 8 ms of the peer's CPU per block.
+// Not a trade a peer wants by default; the entry stays for hosts with idle cores (and as the second source the emit kernel's
+// count check is tested against).
+void GPUCSP::CountEnvelopesOnHost(DevicePass& dp) {
+    PassScratch& ps = dp.ps;
+    const uint8_t* const block = dp.block;
+    const size_t len = dp.len;
     const uint32_t n_env = (uint32_t)(ps.env_spans.size() / 2);
-    if (host_counts && n_env) {
-        ps.env_counts.resize(4 * (size_t)n_env);
-        ps.env_type.resize(n_env);
-        ps.env_understood.resize(n_env);
-        std::atomic<uint32_t> next(0);
-        auto count_some = [&](int) {
-            for (;;) {
-                const uint32_t lo = next.fetch_add(64, std::memory_order_relaxed);
-                if (lo >= n_env) return;
-                const uint32_t hi = std::min(n_env, lo + 64);
-                for (uint32_t e = lo; e < hi; e++) {
-                    uint32_t off = ps.env_spans[2 * (size_t)e], elen = ps.env_spans[2 * (size_t)e + 1];
-                    if (off > len || elen > len - off) off = elen = 0;
-                    walk::CountEmitter em;
-                    uint8_t type = 255, understood = 0;
-                    walk::walk_envelope(block, block + off, elen, e, em, type, understood);
-                    uint32_t* c = &ps.env_counts[4 * (size_t)e];
-                    c[0] = em.nt; c[1] = em.np; c[2] = em.nc;
-                    c[3] = em.gb > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)em.gb;
-                    ps.env_type[e] = type;
-                    ps.env_understood[e] = understood;
-                }
-            }
-        };
-        const int nth = n_env >= 2048 ? std::min(WalkThreads(), 8) : 1;
-        if (nth == 1) count_some(0);
-        else run_workers(nth, count_some);
-    }
-    int rc = SyncDeviceIdentityTable(dv);
-    if (rc != FABGPU_OK) return declined("the identity cache could not be copied to the device");   // (the host walk will say what is wrong, if anything is)
-    std::shared_lock<std::shared_timed_mutex> rl(dv.idtab_rw);
-    if (idtab_version_ != id_version_.load(std::memory_order_acquire)) return declined("the identity cache changed under the pass");
-    out.ms_gates = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk0).count();   // (outline + table sync)
-    auto clk1 = std::chrono::steady_clock::now();
-    const uint64_t tok = up.join();
-    out.ms_upload_wait = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk1).count();
-    if (!tok) return declined("the upload failed");
-    struct Sizer {
-        ParsedBlock& pb;
-        BlockVerdicts& out;
-        PassScratch& ps;
-        bool want_tuples, want_digests, want_qxy, want_nym_issuer;
-        uint32_t cap_tx, cap_tuples, n_skipped;
-        uint32_t n_tuples = 0;
-        bool too_big = false;
-        // the memo the device fills: a table out of the free list (its pinned room is reused), sized once the tuple count is known
-        fabgpu_ctx* ctx = nullptr;
-        BlockMemo* bm = nullptr;
-        uint32_t n_creators_hint = 0;
-        bool hash_index = false;          // the upload left a host copy of the block: the device builds the digest memo's index too
-    } sz{pb, out, ps, want_tuples, want_digests, want_qxy, host_memo && !msps.empty(), cap_tx, cap_tuples, n_skipped};
-    sz.hash_index = up.copy.p != nullptr && up.copy.len == len && po.pass_hash_memo >= 0;
-    std::shared_ptr<BlockMemo> dev_bm;
-    if (dev_memo) {
-        {
-            std::unique_lock<BigReaderLock> lk(memo_mu_);
-            // (prefer a recycled table that already owns pinned room)
-            for (auto it = memo_free_.begin(); it != memo_free_.end(); ++it)
-                if ((*it)->pin) {
-                    dev_bm = *it;
-                    memo_free_.erase(it);
-                    break;
-                }
-            if (!dev_bm && !memo_free_.empty()) {
-                dev_bm = memo_free_.back();
-                memo_free_.pop_back();
+    ps.env_counts.resize(4 * (size_t)n_env);
+    ps.env_type.resize(n_env);
+    ps.env_understood.resize(n_env);
+    std::atomic<uint32_t> next(0);
+    auto count_some = [&](int) {
+        for (;;) {
+            const uint32_t lo = next.fetch_add(64, std::memory_order_relaxed);
+            if (lo >= n_env) return;
+            const uint32_t hi = std::min(n_env, lo + 64);
+            for (uint32_t e = lo; e < hi; e++) {
+                uint32_t off = ps.env_spans[2 * (size_t)e], elen = ps.env_spans[2 * (size_t)e + 1];
+                if (off > len || elen > len - off) off = elen = 0;
+                walk::CountEmitter em;
+                uint8_t type = 255, understood = 0;
+                walk::walk_envelope(block, block + off, elen, e, em, type, understood);
+                uint32_t* c = &ps.env_counts[4 * (size_t)e];
+                c[0] = em.nt; c[1] = em.np; c[2] = em.nc;
+                c[3] = em.gb > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)em.gb;
+                ps.env_type[e] = type;
+                ps.env_understood[e] = understood;
             }
         }
-        if (!dev_bm) dev_bm.reset(new BlockMemo);
-        sz.ctx = ctx_;
-        sz.bm = dev_bm.get();
+    };
+    const int nth = n_env >= 2048 ? std::min(WalkThreads(), 8) : 1;
+    if (nth == 1) count_some(0);
+    else run_workers(nth, count_some);
+}
+
+bool GPUCSP::WalkSizes(void* device_pass, const WalkCounts& c, WalkOut& o) {
+    DevicePass& z = *(DevicePass*)device_pass;
+    const size_t nt = (size_t)c.n_tuples + z.n_skipped;
+    z.n_tuples = (uint32_t)nt;
+    if (c.n_tx > z.cap_tx || nt > z.cap_tuples) {
+        z.too_big = true;
+        return false;
     }
-    WalkRequest rq;
-    rq.stage_token = tok;
-    rq.block_len = len;
+    z.out.tx_flags.resize(c.n_tx);
+    z.out.tx_type.resize(c.n_tx);
+    z.pb.tx_type.resize(c.n_tx);
+    z.pb.tx_understood.resize(c.n_tx);
+    z.out.tuple_status.resize(nt);
+    z.out.tuple_hashed.resize(nt);
+    o.tx_flags = z.out.tx_flags.data();
+    o.tx_type = z.out.tx_type.data();
+    o.tx_understood = z.pb.tx_understood.data();
+    o.tuple_status = z.out.tuple_status.data();
+    o.tuple_hashed = z.out.tuple_hashed.data();
+    z.ps.id_idx.resize(nt);                                          // (4 bytes per tuple: who was named, for the cache's bookkeeping)
+    o.id_idx = z.ps.id_idx.data();
+    if (z.want_tuples) {
+        z.pb.tuples.resize(nt);
+        o.tuples = z.pb.tuples.data();
+    }
+    if (z.want_digests) {
+        z.out.tuple_digest.resize(nt * 32);
+        o.tuple_digest = z.out.tuple_digest.data();
+    } else {
+        z.out.tuple_digest.clear();
+    }
+    if (z.want_nym_issuer) {                                         // which issuer an idemix creator's row was verified under (memo binding)
+        z.ps.nym_issuer_rank.resize(c.n_creators);
+        o.nym_issuer = z.ps.nym_issuer_rank.data();
+    }
+    if (z.want_qxy) {                                                // the key of every tuple's identity, as the device matched or decoded it
+        z.out.tuple_qxy.resize(nt * 64);
+        o.tuple_qxy = z.out.tuple_qxy.data();
+    } else {
+        z.out.tuple_qxy.clear();
+    }
+    if (z.bm && c.n_tuples) {
+        // room for the memo (MemoPinLayout)
+        uint32_t cap = 0;
+        size_t keys_cap = 0, total = 0, at[7];
+        MemoPinLayout(c.n_tuples, c.n_creators, &cap, &keys_cap, &total, at);
+        const size_t a_slots = at[0], a_off = at[1], a_st = at[2], a_dig = at[3], a_keys = at[4], a_hslots = at[5], a_hspans = at[6];
+        if (cap >= 2 * (uint64_t)c.n_tuples && keys_cap < 0xFFFFFFF0ull) {
+            if (z.bm->pin_cap < total) {
+                if (z.bm->pin) walk_pinned_free(z.bm->pin_ctx, z.bm->pin);
+                z.bm->pin = walk_pinned_alloc(z.dv.ctx, total + total / 4);
+                z.bm->pin_ctx = z.dv.ctx;
+                z.bm->pin_cap = z.bm->pin ? total + total / 4 : 0;
+            }
+            if (z.bm->pin) {
+                uint8_t* p = (uint8_t*)z.bm->pin;
+                o.memo_slots = (uint32_t*)(p + a_slots);
+                o.memo_slot_cap = cap;
+                o.memo_key_off = (uint32_t*)(p + a_off);
+                o.memo_status = p + a_st;
+                o.memo_digests = p + a_dig;
+                o.memo_keys = p + a_keys;
+                o.memo_keys_cap = keys_cap;
+                z.bm->mask = cap - 1;
+                z.bm->slots_v = o.memo_slots;
+                z.bm->key_off_v = o.memo_key_off;
+                z.bm->status_v = o.memo_status;
+                z.bm->digests_v = o.memo_digests;
+                z.bm->keys_v = o.memo_keys;
+                z.bm->hslots_v = z.bm->hspans_v = nullptr;
+                if (z.hash_index) {
+                    o.memo_hslots = (uint32_t*)(p + a_hslots);
+                    o.memo_hspans = (uint32_t*)(p + a_hspans);
+                    z.bm->hslots_v = o.memo_hslots;
+                    z.bm->hspans_v = o.memo_hspans;
+                }
+            }
+        }
+    }
+    return true;
+}
+uint8_t* GPUCSP::WalkMemoGrow(void* device_pass, size_t bytes) {
+    DevicePass& z = *(DevicePass*)device_pass;
+    if (!z.bm || bytes >= 0xFFFFFFF0ull) return nullptr;
+    if (z.bm->pin_keys_cap < bytes) {
+        if (z.bm->pin_keys) walk_pinned_free(z.bm->pin_ctx, z.bm->pin_keys);
+        z.bm->pin_keys = walk_pinned_alloc(z.dv.ctx, bytes + bytes / 4);
+        z.bm->pin_ctx = z.dv.ctx;
+        z.bm->pin_keys_cap = z.bm->pin_keys ? bytes + bytes / 4 : 0;
+    }
+    if (!z.bm->pin_keys) return nullptr;
+    z.bm->keys_v = (const uint8_t*)z.bm->pin_keys;
+    return (uint8_t*)z.bm->pin_keys;
+}
+
+void GPUCSP::BuildWalkRequest(DevicePass& dp, WalkRequest& rq, uint64_t stage_token) const {
+    PassScratch& ps = dp.ps;
+    rq.stage_token = stage_token;
+    rq.block_len = dp.len;
     rq.env_spans = ps.env_spans.data();
     rq.payload_spans = ps.payload_spans.data();
     rq.n_env = (uint32_t)(ps.env_spans.size() / 2);
-    if (host_counts && n_env) {
+    if (dp.host_counts && rq.n_env) {
         rq.host_counts = ps.env_counts.data();
         rq.host_tx_type = ps.env_type.data();
         rq.host_tx_understood = ps.env_understood.data();
     }
-    if (opt.block_sigs && !ps.block_sigs.empty()) {
+    if (dp.opt.block_sigs && !ps.block_sigs.empty()) {
         rq.block_sigs = ps.block_sigs.data();
         rq.n_block_sigs = (uint32_t)ps.block_sigs.size();
-        rq.tail = pb.tail.data();
-        rq.tail_base = pb.tail_base;
-        rq.tail_len = (uint32_t)pb.tail.size();
+        rq.tail = dp.pb.tail.data();
+        rq.tail_base = dp.pb.tail_base;
+        rq.tail_len = (uint32_t)dp.pb.tail.size();
     }
-    rq.user = &sz;
-    rq.sizes = [](void* user, const WalkCounts& c, WalkOut& o) {
-        Sizer& z = *(Sizer*)user;
-        const size_t nt = (size_t)c.n_tuples + z.n_skipped;
-        z.n_tuples = (uint32_t)nt;
-        if (c.n_tx > z.cap_tx || nt > z.cap_tuples) {
-            z.too_big = true;
-            return false;
-        }
-        z.out.tx_flags.resize(c.n_tx);
-        z.out.tx_type.resize(c.n_tx);
-        z.pb.tx_type.resize(c.n_tx);
-        z.pb.tx_understood.resize(c.n_tx);
-        z.out.tuple_status.resize(nt);
-        z.out.tuple_hashed.resize(nt);
-        o.tx_flags = z.out.tx_flags.data();
-        o.tx_type = z.out.tx_type.data();
-        o.tx_understood = z.pb.tx_understood.data();
-        o.tuple_status = z.out.tuple_status.data();
-        o.tuple_hashed = z.out.tuple_hashed.data();
-        z.ps.id_idx.resize(nt);                                          // (4 bytes per tuple: who was named, for the cache's bookkeeping)
-        o.id_idx = z.ps.id_idx.data();
-        if (z.want_tuples) {
-            z.pb.tuples.resize(nt);
-            o.tuples = z.pb.tuples.data();
-        }
-        if (z.want_digests) {
-            z.out.tuple_digest.resize(nt * 32);
-            o.tuple_digest = z.out.tuple_digest.data();
-        } else {
-            z.out.tuple_digest.clear();
-        }
-        if (z.want_nym_issuer) {                                         // which issuer an idemix creator's row was verified under (memo binding)
-            z.ps.nym_issuer_rank.resize(c.n_creators);
-            o.nym_issuer = z.ps.nym_issuer_rank.data();
-        }
-        if (z.want_qxy) {                                                // the key of every tuple's identity, as the device matched or decoded it
-            z.out.tuple_qxy.resize(nt * 64);
-            o.tuple_qxy = z.out.tuple_qxy.data();
-        } else {
-            z.out.tuple_qxy.clear();
-        }
-        if (z.bm && c.n_tuples) {
-            // room for the memo (MemoPinLayout)
-            uint32_t cap = 0;
-            size_t keys_cap = 0, total = 0, at[7];
-            MemoPinLayout(c.n_tuples, c.n_creators, &cap, &keys_cap, &total, at);
-            const size_t a_slots = at[0], a_off = at[1], a_st = at[2], a_dig = at[3], a_keys = at[4], a_hslots = at[5], a_hspans = at[6];
-            if (cap >= 2 * (uint64_t)c.n_tuples && keys_cap < 0xFFFFFFF0ull) {
-                if (z.bm->pin_cap < total) {
-                    if (z.bm->pin) walk_pinned_free(z.bm->pin_ctx, z.bm->pin);
-                    z.bm->pin = walk_pinned_alloc(z.ctx, total + total / 4);
-                    z.bm->pin_ctx = z.ctx;
-                    z.bm->pin_cap = z.bm->pin ? total + total / 4 : 0;
-                }
-                if (z.bm->pin) {
-                    uint8_t* p = (uint8_t*)z.bm->pin;
-                    o.memo_slots = (uint32_t*)(p + a_slots);
-                    o.memo_slot_cap = cap;
-                    o.memo_key_off = (uint32_t*)(p + a_off);
-                    o.memo_status = p + a_st;
-                    o.memo_digests = p + a_dig;
-                    o.memo_keys = p + a_keys;
-                    o.memo_keys_cap = keys_cap;
-                    z.bm->mask = cap - 1;
-                    z.bm->slots_v = o.memo_slots;
-                    z.bm->key_off_v = o.memo_key_off;
-                    z.bm->status_v = o.memo_status;
-                    z.bm->digests_v = o.memo_digests;
-                    z.bm->keys_v = o.memo_keys;
-                    z.bm->hslots_v = z.bm->hspans_v = nullptr;
-                    if (z.hash_index) {
-                        o.memo_hslots = (uint32_t*)(p + a_hslots);
-                        o.memo_hspans = (uint32_t*)(p + a_hspans);
-                        z.bm->hslots_v = o.memo_hslots;
-                        z.bm->hspans_v = o.memo_hspans;
-                    }
-                }
-            }
-        }
-        return true;
-    };
-    rq.memo_grow = [](void* user, size_t bytes) -> uint8_t* {
-        Sizer& z = *(Sizer*)user;
-        if (!z.bm || bytes >= 0xFFFFFFF0ull) return nullptr;
-        if (z.bm->pin_keys_cap < bytes) {
-            if (z.bm->pin_keys) walk_pinned_free(z.bm->pin_ctx, z.bm->pin_keys);
-            z.bm->pin_keys = walk_pinned_alloc(z.ctx, bytes + bytes / 4);
-            z.bm->pin_ctx = z.ctx;
-            z.bm->pin_keys_cap = z.bm->pin_keys ? bytes + bytes / 4 : 0;
-        }
-        if (!z.bm->pin_keys) return nullptr;
-        z.bm->keys_v = (const uint8_t*)z.bm->pin_keys;
-        return (uint8_t*)z.bm->pin_keys;
-    };
+    rq.user = &dp;
+    rq.sizes = &GPUCSP::WalkSizes;
+    rq.memo_grow = &GPUCSP::WalkMemoGrow;
     ps.learn.resize(WALK_LEARN_SLOTS);
     rq.learn_out = ps.learn.data();
-    rq.idemix_msps = msps.data();
-    rq.n_idemix_msps = (uint32_t)msps.size();
+    rq.idemix_msps = dp.msps.data();
+    rq.n_idemix_msps = (uint32_t)dp.msps.size();
     // (a pseudonym signature's memo entry is bound to the hash of the issuer key it was verified under: without every MSP's hash at hand
     //  the device makes no entries for pseudonym signatures at all)
-    std::vector<uint8_t> issuer_hashes;
-    if (dev_memo && !msps.empty()) {
+    if (dp.bm && !dp.msps.empty()) {
         std::lock_guard<std::mutex> lk(idmu_);
-        issuer_hashes.resize(32 * msps.size());
+        dp.issuer_hashes.resize(32 * dp.msps.size());
         bool all = true;
-        for (size_t m = 0; m < msps.size(); m++) {
-            auto it = idemix_issuer_hash_.find(msps[m].issuer);
+        for (size_t m = 0; m < dp.msps.size(); m++) {
+            auto it = idemix_issuer_hash_.find(dp.msps[m].issuer);
             if (it == idemix_issuer_hash_.end()) all = false;
-            else memcpy(&issuer_hashes[32 * m], it->second.data(), 32);
+            else memcpy(&dp.issuer_hashes[32 * m], it->second.data(), 32);
         }
-        if (all) rq.idemix_issuer_hashes = issuer_hashes.data();
+        if (all) rq.idemix_issuer_hashes = dp.issuer_hashes.data();
     }
-    struct MemoBack {                                                       // a table that was not published goes back to the free list
-        const GPUCSP* c;
-        std::shared_ptr<BlockMemo>& bm;
-        ~MemoBack() {
-            if (!bm) return;
-            std::unique_lock<BigReaderLock> lk(c->memo_mu_);
-            if (c->memo_free_.size() < c->memo_free_max_) c->memo_free_.push_back(bm);
-        }
-    } memo_back{this, dev_bm};
-    auto clk2 = std::chrono::steady_clock::now();
-    rc = walk_block_pass(ctx_, rq);
-    out.ms_device = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk2).count();
-    auto clk3 = std::chrono::steady_clock::now();
-    struct PostClock {
-        BlockVerdicts& o;
-        std::chrono::steady_clock::time_point t0;
-        ~PostClock() { o.ms_post = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-    } post_clock{out, clk3};
-    if (n_tuples_out) *n_tuples_out = sz.n_tuples;
-    if (rc == WALK_DECLINED) return declined(rq.declined_why);
-    if (rc == FABGPU_ETOOBIG && sz.too_big) return FABGPU_ETOOBIG;     // pb.n_tx / *n_tuples_out say what to make room for
-    if (rc == FABGPU_ETOOBIG) return declined("the block exceeds the device walk's limits");   // (not the caller's arrays: the host walk takes it)
-    if (rc != FABGPU_OK) return rc;
-    dv.passes.fetch_add(1, std::memory_order_relaxed);
-    pass_relaunches_.fetch_add(rq.relaunched, std::memory_order_relaxed);
-    pass_decoded_.fetch_add(rq.summary.n_unknown_identity, std::memory_order_relaxed);
-    pass_general_der_.fetch_add(rq.summary.n_general_der, std::memory_order_relaxed);
-    const size_t nt = sz.n_tuples, nd = nt - n_skipped;
+}
+
+// the answers as the host route reports them: the issuer of every pseudonym signature, the skipped block signatures, tuple_tx / _kind
+void GPUCSP::FinishDeviceAnswers(DevicePass& dp, const WalkRequest& rq) {
+    ParsedBlock& pb = dp.pb;
+    BlockVerdicts& out = dp.out;
+    PassScratch& ps = dp.ps;
+    const bool want_tuples = dp.want_tuples, want_digests = dp.want_digests, want_qxy = dp.want_qxy;
+    const size_t nt = dp.n_tuples, nd = nt - dp.n_skipped;
     out.n_tx = pb.n_tx;
     memcpy(pb.tx_type.data(), out.tx_type.data(), pb.n_tx);
     out.distinct_identities = 0;
@@ -2123,7 +2079,7 @@ int GPUCSP::PreVerifyBlockOnDevice(const uint8_t* block, size_t len, ParsedBlock
     out.n_keyed = (rq.keyed_creators ? rq.summary.n_hashed_creator : 0u) + (rq.keyed_others ? rq.summary.n_hashed_other : 0u);
     out.n_device_decoded = rq.summary.n_unknown_identity;
     out.tuple_nym_issuer.clear();
-    if (sz.want_nym_issuer && rq.summary.n_nym != 0 && want_tuples) {
+    if (dp.want_nym_issuer && rq.summary.n_nym != 0 && want_tuples) {
         // the memo binds a pseudonym signature's entry to the issuer it was verified under: issuer ids come back by creator rank, and
         // creator tuples appear in rank order (every tuple-yielding envelope yields exactly one, its first)
         out.tuple_nym_issuer.assign(nt, -1);
@@ -2157,156 +2113,343 @@ int GPUCSP::PreVerifyBlockOnDevice(const uint8_t* block, size_t len, ParsedBlock
     if (want_digests)
         for (size_t i = 0; i < nt; i++)
             if (!out.tuple_hashed[i]) memset(&out.tuple_digest[32 * i], 0, 32);   // as the host pass reports them
-    // What the host pass does per tuple for the cache - count who was named (a device comb table is earned by being named
-    // id_register_after_ times) and keep the LRU order fresh - from the identity indices, when they came back.
-    std::vector<std::string> to_register;
-    std::vector<uint64_t> hit_serials;                                  // who this block named: they stay in front of the block's newcomers
-    if (!idtab_host_.empty()) {
-        std::vector<uint32_t> hits(idtab_host_.size(), 0);
-        for (size_t i = 0; i < nd; i++)
-            if (ps.id_idx[i] < hits.size()) hits[ps.id_idx[i]]++;
-        std::lock_guard<std::mutex> lk(idmu_);
-        for (size_t k = 0; k < hits.size(); k++) {
-            if (!hits[k]) continue;
-            auto it = idserial_.find(idtab_host_[k]);
-            if (it == idserial_.end()) continue;                        // (evicted since the table was made)
-            hit_serials.push_back(idtab_host_[k]);
-            idlru_.splice(idlru_.begin(), idlru_, it->second);
-            CachedIdentity& c = it->second->second;
-            c.hits += hits[k];
-            if (c.p256 && c.key_id < 0 && !c.registering && c.hits >= id_register_after_ && id_registered_ < id_max_registered_) {
-                c.registering = true;
-                id_registered_++;
-                to_register.push_back(it->second->first);
-            }
-        }
+}
+
+// What the host pass does per tuple for the cache - count who was named (a device comb table is earned by being named
+// id_register_after_ times) and keep the LRU order fresh - from the identity indices, when they came back.
+void GPUCSP::CountDeviceHits(DevicePass& dp) const {
+    const std::vector<uint64_t>& idtab_host_ = dp.dv.idtab_host;
+    if (idtab_host_.empty()) return;
+    const size_t nd = dp.n_tuples - dp.n_skipped;
+    std::vector<uint32_t> hits(idtab_host_.size(), 0);
+    for (size_t i = 0; i < nd; i++)
+        if (dp.ps.id_idx[i] < hits.size()) hits[dp.ps.id_idx[i]]++;
+    std::lock_guard<std::mutex> lk(idmu_);
+    for (size_t k = 0; k < hits.size(); k++) {
+        if (!hits[k]) continue;
+        auto it = idserial_.find(idtab_host_[k]);
+        if (it == idserial_.end()) continue;                        // (evicted since the table was made)
+        dp.hit_serials.push_back(idtab_host_[k]);
+        idlru_.splice(idlru_.begin(), idlru_, it->second);
+        CachedIdentity& c = it->second->second;
+        c.hits += hits[k];
+        if (EarnTableLocked(c)) dp.to_register.push_back(it->second->first);
     }
+}
+
+// Identities the device decoded itself (nobody had met them) enter the cache here, with the key the device read out of the
+// certificate - the host route's "new identity" branch without decoding anything again.  At most WALK_LEARN_SLOTS per block; the
+// LRU bounds what unvalidated blocks can make the provider remember, and a comb table is still only earned by being named often.
+void GPUCSP::LearnDeviceIdentities(DevicePass& dp, const WalkRequest& rq) const {
+    if (!rq.summary.n_learn) return;
+    std::lock_guard<std::mutex> lk(idmu_);
+    bool grew = false;
+    for (const WalkLearn& l : dp.ps.learn) {
+        if (!l.tag || !l.ready || (uint64_t)l.off + l.len > dp.len) continue;
+        std::string key((const char*)dp.block + l.off, l.len);
+        if (idcache_.find(key) != idcache_.end()) continue;
+        CachedIdentity ci;
+        ci.p256 = l.ready == 1;
+        memcpy(ci.qx, l.qx, 32);
+        memcpy(ci.qy, l.qy, 32);
+        ci.hits = l.hits ? l.hits : 1;
+        if (EarnTableLocked(ci)) dp.to_register.push_back(key);
+        InsertIdentityLocked(std::move(key), ci, /*evict_now=*/false);
+        pass_learned_.fetch_add(1, std::memory_order_relaxed);
+        grew = true;
+    }
+    // The block's newcomers must not push out the identities the same block NAMED: with open-addressed learn slots a block can bring
+    // 128 of them, and a cache bound below that (tests; an operator's choice) would otherwise drop the channel's endorsers - named
+    // by every transaction, tables and all - because they were touched a moment BEFORE the newcomers were inserted in front of them.
+    if (!grew) return;
+    for (uint64_t serial : dp.hit_serials) {
+        auto it = idserial_.find(serial);
+        if (it != idserial_.end()) idlru_.splice(idlru_.begin(), idlru_, it->second);
+    }
+    EvictIdentitiesLocked();
+    id_version_.fetch_add(1, std::memory_order_release);
+}
+
+void GPUCSP::PublishDeviceMemo(DevicePass& dp, const WalkRequest& rq, std::shared_ptr<BlockMemo>& bm) const {
+    StageClock memo_clock{dp.out.ms_memo};
+    bm->seq = dp.opt.block_seq;
+    bm->n = rq.memo_live;
+    bm->n_entries = rq.memo_n;
+    dp.out.memo_seeded = rq.memo_live;
+    MemoAdoptCopy(*bm, &dp.up, rq.tail, rq.tail_len, rq.tail_base);
+    if (!PublishMemo(bm)) dp.out.memo_seeded = 0;
+    bm.reset();                                                        // (published: not for the free list)
+}
+
+int GPUCSP::PreVerifyBlockOnDevice(const uint8_t* block, size_t len, ParsedBlock& pb, BlockVerdicts& out, BlockUpload& up, const PassOptions& opt,
+                                   unsigned want, uint32_t cap_tx, uint32_t cap_tuples, uint32_t* n_tuples_out, const char** why) const {
+    static const char* none = "";
+    const char* dummy;
+    if (!why) why = &dummy;
+    *why = none;
+    auto declined = [&](const char* w) {
+        *why = w;
+        return 1;
+    };
+    if (!DeviceWalkEnabled()) return declined("pass_device_walk is off");
+    if (!block || !up.started) return declined("the block was not staged ahead (small block)");
+    ProviderOptions po;
+    {
+        std::lock_guard<std::mutex> lk(opt_mu_);
+        po = opts_;
+    }
+    if (po.pass_skip_hash_checks > 0) return declined("pass_skip_hash_checks");
+    Dev& dv = *devs_[(size_t)up.dev];                       // the device the block travelled to (StartBlockUpload chose it)
+    fabgpu_ctx* const ctx_ = dv.ctx;
+    std::atomic<uint64_t>& idtab_version_ = dv.idtab_version;
+    std::vector<DevIdemixMsp> msps;
+    if (!ListIdemixMsps(msps)) return declined("more idemix MSPs (or a longer MSP id) than the device route carries");
+    ScratchLease lease(this);
+    PassScratch& ps = *lease.p;
+    auto clk0 = std::chrono::steady_clock::now();
+    if (!OutlineBlock(block, len, pb, ps.env_spans, ps.block_sigs, &ps.payload_spans)) return FABGPU_EINVAL;
+    // The caller's room for per-transaction answers is checked HERE - the outline knows the transaction count - before the upload is
+    // waited for and before anything is launched: a too-small array costs the caller the outline (0.15 ms for 10 000 transactions),
+    // not an upload and two kernels (ADVICE r3; the Go binding used to pay exactly that for every block over 1 024 transactions).
+    if (ps.env_spans.size() / 2 > cap_tx) {
+        pb.n_tx = (uint32_t)(ps.env_spans.size() / 2);
+        if (n_tuples_out) *n_tuples_out = 0;                // (not known yet: the device counts tuples)
+        return FABGPU_ETOOBIG;
+    }
+    // The verdict memo of a device-route pass is built by the device (round 3: block_walk_dev.h WalkOut::memo_*) into pinned memory of a
+    // BlockMemo: keys, offsets, statuses and the slot table come back as they are looked up - no tuple records, digests and keys to bring
+    // back, copy out and read 40 000 signatures out of the host's copy of the block for.  FABGPU_PASS_DEVICE_MEMO=0: SeedMemo, as before.
+    const bool dev_memo = opt.seed_memo && po.pass_device_memo >= 0;
+    const bool host_memo = opt.seed_memo && !dev_memo;
+    const bool want_digests = opt.want_digests || host_memo;
+    const bool want_tuples = (want & WANT_TUPLES) || host_memo, want_qxy = (want & WANT_QXY) || host_memo;
+    const uint32_t n_skipped = opt.block_sigs ? 0 : (uint32_t)ps.block_sigs.size();   // reported (TUPLE_ST_SKIPPED), not submitted
+    if (pb.tail.size() > opt.tail_cap) {                             // the caller wants the tail and has no room for it: say so before anything runs
+        if (n_tuples_out) *n_tuples_out = 0;
+        return FABGPU_ETOOBIG;
+    }
+    DevicePass dp{block, len, pb, out, ps, up, opt, dv, msps, want_tuples, want_digests, want_qxy, host_memo && !msps.empty(), po.pass_host_counts > 0,
+                  cap_tx, cap_tuples, n_skipped};
+    if (dp.host_counts && ps.env_spans.size() >= 2) CountEnvelopesOnHost(dp);   // (the option is read per pass: tests run both ways in one process)
+    int rc = SyncDeviceIdentityTable(dv);
+    if (rc != FABGPU_OK) return declined("the identity cache could not be copied to the device");   // (the host walk will say what is wrong, if anything is)
+    std::shared_lock<std::shared_timed_mutex> rl(dv.idtab_rw);
+    if (idtab_version_ != id_version_.load(std::memory_order_acquire)) return declined("the identity cache changed under the pass");
+    out.ms_gates = ms_since(clk0);   // (outline + table sync)
+    auto clk1 = std::chrono::steady_clock::now();
+    const uint64_t tok = up.join();
+    out.ms_upload_wait = ms_since(clk1);
+    if (!tok) return declined("the upload failed");
+    dp.hash_index = up.copy.p != nullptr && up.copy.len == len && po.pass_hash_memo >= 0;
+    std::shared_ptr<BlockMemo> dev_bm;
+    if (dev_memo) {
+        dev_bm = TakeMemoTable(/*prefer_pinned=*/true);
+        dp.bm = dev_bm.get();
+    }
+    WalkRequest rq;
+    BuildWalkRequest(dp, rq, tok);
+    MemoReturn memo_back{this, dev_bm};
+    auto clk2 = std::chrono::steady_clock::now();
+    rc = walk_block_pass(ctx_, rq);
+    out.ms_device = ms_since(clk2);
+    StageClock post_clock{out.ms_post};
+    if (n_tuples_out) *n_tuples_out = dp.n_tuples;
+    if (rc == WALK_DECLINED) return declined(rq.declined_why);
+    if (rc == FABGPU_ETOOBIG && dp.too_big) return FABGPU_ETOOBIG;     // pb.n_tx / *n_tuples_out say what to make room for
+    if (rc == FABGPU_ETOOBIG) return declined("the block exceeds the device walk's limits");   // (not the caller's arrays: the host walk takes it)
+    if (rc != FABGPU_OK) return rc;
+    dv.passes.fetch_add(1, std::memory_order_relaxed);
+    pass_relaunches_.fetch_add(rq.relaunched, std::memory_order_relaxed);
+    pass_decoded_.fetch_add(rq.summary.n_unknown_identity, std::memory_order_relaxed);
+    pass_general_der_.fetch_add(rq.summary.n_general_der, std::memory_order_relaxed);
+    FinishDeviceAnswers(dp, rq);
+    CountDeviceHits(dp);
     rl.unlock();
-    // Identities the device decoded itself (nobody had met them) enter the cache here, with the key the device read out of the
-    // certificate - the host route's "new identity" branch without decoding anything again.  At most WALK_LEARN_SLOTS per block; the
-    // LRU bounds what unvalidated blocks can make the provider remember, and a comb table is still only earned by being named often.
-    if (rq.summary.n_learn) {
-        std::lock_guard<std::mutex> lk(idmu_);
-        bool grew = false;
-        for (const WalkLearn& l : ps.learn) {
-            if (!l.tag || !l.ready || (uint64_t)l.off + l.len > len) continue;
-            std::string key((const char*)block + l.off, l.len);
-            if (idcache_.find(key) != idcache_.end()) continue;
-            CachedIdentity ci;
-            ci.p256 = l.ready == 1;
-            memcpy(ci.qx, l.qx, 32);
-            memcpy(ci.qy, l.qy, 32);
-            ci.hits = l.hits ? l.hits : 1;
-            if (ci.p256 && ci.hits >= id_register_after_ && id_registered_ < id_max_registered_) {
-                ci.registering = true;
-                id_registered_++;
-                to_register.push_back(key);
-            }
-            InsertIdentityLocked(std::move(key), ci, /*evict_now=*/false);
-            pass_learned_.fetch_add(1, std::memory_order_relaxed);
-            grew = true;
-        }
-        // The block's newcomers must not push out the identities the same block NAMED: with open-addressed learn slots a block can bring
-        // 128 of them, and a cache bound below that (tests; an operator's choice) would otherwise drop the channel's endorsers - named
-        // by every transaction, tables and all - because they were touched a moment BEFORE the newcomers were inserted in front of them.
-        if (grew) {
-            for (uint64_t serial : hit_serials) {
-                auto it = idserial_.find(serial);
-                if (it != idserial_.end()) idlru_.splice(idlru_.begin(), idlru_, it->second);
-            }
-            EvictIdentitiesLocked();
-            id_version_.fetch_add(1, std::memory_order_release);
-        }
-    }
+    LearnDeviceIdentities(dp, rq);
     {
         const auto tq = std::chrono::steady_clock::now();
-        RegisterQueued(to_register);
-        if (po.pass_timing > 0 && !to_register.empty())
-            fprintf(stderr, "fabgpu pass: %zu identities earned their comb tables: %.2f ms\n", to_register.size(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq).count());
+        RegisterQueued(dp.to_register);
+        if (po.pass_timing > 0 && !dp.to_register.empty())
+            fprintf(stderr, "fabgpu pass: %zu identities earned their comb tables: %.2f ms\n", dp.to_register.size(), ms_since(tq));
     }
-    constexpr int gate_max = 16;
-    if (host_memo) SeedMemo(block, pb, out, opt, ps.sub, gate_max, &up);
-    if (dev_memo && dev_bm && rq.memo_live && dev_bm->slots_v) {
-        auto clk_memo = std::chrono::steady_clock::now();
-        dev_bm->seq = opt.block_seq;
-        dev_bm->n = rq.memo_live;
-        dev_bm->n_entries = rq.memo_n;
-        out.memo_seeded = rq.memo_live;
-        // the digest memo: the block's host copy (and the orderers' signature messages, which are not in the block) travel with the table
-        host_copy_release(&dev_bm->copy);
-        dev_bm->tail.clear();
-        dev_bm->tail_base = 0;
-        if (dev_bm->hslots_v && dev_bm->hspans_v && up.copy.p) {
-            dev_bm->copy = up.copy;
-            up.copy = HostCopy();
-            if (rq.tail && rq.tail_len) {
-                dev_bm->tail.assign(rq.tail, rq.tail + rq.tail_len);
-                dev_bm->tail_base = rq.tail_base;
-            }
-        } else {
-            dev_bm->hslots_v = dev_bm->hspans_v = nullptr;
-        }
-        if (!PublishMemo(dev_bm)) out.memo_seeded = 0;
-        dev_bm.reset();                                                    // (published: not for the free list)
-        out.ms_memo = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk_memo).count();
-    }
+    if (host_memo) SeedMemo(block, pb, out, opt, ps.sub, kGateMax, &up);
+    if (dev_memo && dev_bm && rq.memo_live && dev_bm->slots_v) PublishDeviceMemo(dp, rq, dev_bm);
     return 0;
 }
 
-Error GPUCSP::PreVerifyParsed(const uint8_t* block, const ParsedBlock& pb, BlockVerdicts& out, BlockUpload* up, const PassOptions& opt) const {
-    // `out` may come back from the previous block (the C entry points keep one per calling thread): its vectors keep their capacity -
-    // a fresh 3 MB of answer arrays per block is 700 page faults - and every element is (re)written below
-    const bool want_digests = opt.want_digests || opt.seed_memo;
-    const size_t nt = pb.tuples.size();
-    out.n_tx = pb.n_tx;
-    out.distinct_identities = 0;
-    out.ms_gates = out.ms_upload_wait = out.ms_device = 0;
-    out.memo_seeded = 0;
-    out.tx_type = pb.tx_type;
-    out.tx_flags.assign(pb.n_tx, TX_ALL_SIGNATURES_VALID);
-    for (uint32_t t = 0; t < pb.n_tx; t++)
-        if (!pb.tx_understood[t]) out.tx_flags[t] = TX_NOT_UNDERSTOOD;
-    out.tuple_tx.resize(nt);
-    out.tuple_kind.resize(nt);
-    out.tuple_status.assign(nt, FABGPU_ST_VALID);
-    out.tuple_qxy.resize(nt * 64);                       // written per tuple by the gates (key or zeros)
-    out.tuple_hashed.assign(nt, 0);
-    if (want_digests) out.tuple_digest.assign(nt * 32, 0);
-    else out.tuple_digest.clear();
-    out.n_block_sigs = pb.n_block_sigs;
-    out.block_sigs_understood = pb.block_sigs_understood ? 1 : 0;
-    // identities -> keys (cached across blocks), signatures -> (r, s) through the reference's gates.  Tuples are independent:
-    // blocks of 4096+ tuples are gated on worker threads (contiguous ranges), then compacted in order.
-    // The scratch below (8 MB for a 40 000-tuple block) is reused from block to block instead of being allocated - and page-faulted
-    // in - per call.  Passes of different callers run side by side, each on a set of its own (up to four are kept): one caller's gates
-    // and flags overlap another's device call (two callers, 10 000-tx blocks: 3.2 ms per block with one pass at a time).
-    struct Lease {
-        const GPUCSP* c;
-        std::unique_ptr<PassScratch> p;
-        explicit Lease(const GPUCSP* c_) : c(c_) {
-            std::lock_guard<std::mutex> lk(c->pass_mu_);
-            if (!c->scratch_free_.empty()) {
-                p = std::move(c->scratch_free_.back());
-                c->scratch_free_.pop_back();
-            }
-            if (!p) p.reset(new PassScratch);
-        }
-        ~Lease() {
-            std::lock_guard<std::mutex> lk(c->pass_mu_);
-            if (c->scratch_free_.size() < c->scratch_free_max_) c->scratch_free_.push_back(std::move(p));
-        }
-    } lease(this);
-    PassScratch& ps_ = *lease.p;
-    // the device this pass runs on: where its block travelled to, or - no upload - wherever the ring points
-    Dev& dv = *devs_[(size_t)(up && up->routed ? up->dev : RouteBlock(opt.block_seq))];
-    fabgpu_ctx* const ctx_ = dv.ctx;
-    bool skip_hash_checks;
-    {
-        std::lock_guard<std::mutex> lk(opt_mu_);
-        skip_hash_checks = opts_.pass_skip_hash_checks > 0;
-    }
+// What the steps of one host-route pass share.
+struct GPUCSP::HostPass {
+    const uint8_t* block;
+    const ParsedBlock& pb;
+    BlockVerdicts& out;
+    BlockUpload* up;
+    const PassOptions& opt;
+    PassScratch& ps;
+    Dev& dv;                              // the device this pass runs on
+    bool want_digests, skip_hash_checks;
+    size_t n = 0;                         // ECDSA tuples the gates let through, compacted into ps.sub .. ps.s
+    bool all_keyed = true;                // ... every one of them under a registered comb table
+    bool hashes_done = false;             // the TxID / proposal-hash digests came back in ps.hash_digests
+    bool nym_rode = false;                // the idemix creators' signatures (ps.nym_idx) rode in the ECDSA submission
+    std::vector<std::string> to_register; // guarded by idmu_
+};
+
+// The answer for one pseudonym signature.  status: FABGPU_NYM_VALID = 0, BAD_PROOF = 1 (= "signature invalid"), NEEDS_SW = 6 =
+// TUPLE_ST_NEEDS_SW.  NymVerifier.Verify receives the whole message, not a digest (bccsp/idemix/handlers/nymsigner.go:62-95): the memo
+// entry of a pseudonym signature is keyed on SHA-256(message) - digest32, computed by the device over the bytes the nym kernel verified
+// (nullptr: digests are not wanted), and by the Go wrapper over the bytes it is asked about.
+static void write_nym_result(BlockVerdicts& out, size_t i, uint8_t status, const uint8_t* digest32, const uint8_t* nym_x, const uint8_t* nym_y) {
+    out.tuple_status[i] = status;
+    if (!digest32 || status == FABGPU_NYM_NEEDS_SW) return;
+    memcpy(&out.tuple_digest[32 * i], digest32, 32);
+    out.tuple_hashed[i] = 1;
+    memcpy(&out.tuple_qxy[64 * i], nym_x, 32);                         // the pseudonym (Nym.x, Nym.y) in the key slot
+    memcpy(&out.tuple_qxy[64 * i + 32], nym_y, 32);
+}
+
+// identities -> keys (cached across blocks), signatures -> (r, s) through the reference's gates, for the tuples lo .. hi
+void GPUCSP::GateRange(HostPass& hp, const std::map<std::string, int64_t>& idemix_msps, size_t lo, size_t hi, uint32_t* fresh) const {
     typedef PassScratch::Gated Gated;
+    const uint8_t* const block = hp.block;
+    const ParsedBlock& pb = hp.pb;
+    BlockVerdicts& out = hp.out;
+    const PassOptions& opt = hp.opt;
+    std::vector<Gated>& gt = hp.ps.gt;
+    static const uint8_t one_digest[1] = {1};
+    // a block names few identities: a per-thread front cache (memcmp against the identities already met) keeps the shared
+    // map - and its 700-byte key copies - off the per-tuple path
+    struct Front {
+        const uint8_t* p;
+        uint32_t len;
+        CachedIdentity ci;
+        uint32_t hits;
+    };
+    std::vector<Front> front;
+    for (size_t i = lo; i < hi; i++) {
+        const BlockTuple& tp = pb.tuples[i];
+        Gated& g0 = gt[i];
+        g0.submit = false;
+        g0.nym = false;
+        out.tuple_tx[i] = tp.tx;
+        out.tuple_kind[i] = tp.kind;
+        memset(&out.tuple_qxy[64 * i], 0, 64);
+        if (tp.kind == TUPLE_BLOCK_SIG && !opt.block_sigs) {
+            out.tuple_status[i] = TUPLE_ST_SKIPPED;
+            continue;
+        }
+        CachedIdentity ci;
+        bool hit = false;
+        // An idemix creator carries a fresh pseudonym per transaction: it can be in no cache, so it is recognised first - without
+        // the shared map, its lock and its key copy (2 000 such creators in a block cost the gates 1.7 ms that way).  Precedence is
+        // kept: an identity that also yields a P-256 certificate key takes the certificate path below.
+        if (tp.kind == TUPLE_CREATOR && !idemix_msps.empty()) {
+            std::string mspid;
+            uint8_t tqx[32], tqy[32];
+            if (IdentityToIdemixNym(block + tp.identity.off, tp.identity.len, mspid, g0.qx, g0.qy) &&
+                !IdentityToP256(block + tp.identity.off, tp.identity.len, tqx, tqy)) {
+                // identity.Verify is NymSignature.Ver under the MSP's issuer key (msp/idemixmsp.go:584-599); an idemix identity is
+                // never an endorser (docs/source/idemix.rst:171-176)
+                auto im = idemix_msps.find(mspid);
+                NymSignatureFields sf;
+                if (im != idemix_msps.end() && im->second >= 0 && tp.sig.len != 0 && UnmarshalNymSignature(block + tp.sig.off, tp.sig.len, sf) &&
+                    sf.len[0] == 32 && sf.len[1] == 32 && sf.len[2] == 32 && sf.len[3] == 32) {
+                    memcpy(g0.r, sf.f[0], 32); memcpy(g0.s, sf.f[1], 32); memcpy(g0.srn, sf.f[2], 32); memcpy(g0.nonce, sf.f[3], 32);
+                    g0.key_id = im->second;
+                    g0.nym = true;
+                } else {
+                    out.tuple_status[i] = TUPLE_ST_NEEDS_SW;
+                }
+                continue;
+            }
+        }
+        for (Front& f : front)
+            if (f.len == tp.identity.len && memcmp(f.p, block + tp.identity.off, f.len) == 0) {
+                ci = f.ci;
+                f.hits++;
+                hit = true;
+                break;
+            }
+        if (!hit) {
+            bool transient = false, found = false;
+            std::string key((const char*)block + tp.identity.off, tp.identity.len);
+            {
+                std::lock_guard<std::mutex> lk(idmu_);
+                auto it = idcache_.find(key);
+                if (it != idcache_.end()) {
+                    idlru_.splice(idlru_.begin(), idlru_, it->second);      // most recently used
+                    ci = it->second->second;
+                    found = true;
+                }
+            }
+            if (!found) {
+                // decoded outside the lock (PEM + DER walk of ~800 untrusted bytes); NO device table here - that is earned
+                // by being named id_register_after_ times (flush below)
+                (*fresh)++;
+                ci.p256 = IdentityToP256(block + tp.identity.off, tp.identity.len, ci.qx, ci.qy) && PublicKeyOnCurve(ci.qx, ci.qy);
+                // idemix identities carry a fresh pseudonym per transaction: caching them would only churn the cache
+                std::string ms;
+                uint8_t tnx[32], tny[32];
+                transient = !ci.p256 && IdentityToIdemixNym(block + tp.identity.off, tp.identity.len, ms, tnx, tny);
+                if (!transient) {
+                    std::lock_guard<std::mutex> lk(idmu_);
+                    auto it = idcache_.find(key);
+                    if (it == idcache_.end()) {
+                        InsertIdentityLocked(std::string(key), ci);          // (the least recently used goes)
+                        id_version_.fetch_add(1, std::memory_order_release);   // (the device's copy of the cache is stale now)
+                    } else {
+                        ci = it->second->second;
+                    }
+                }
+            }
+            if (!transient && front.size() < 64) front.push_back({block + tp.identity.off, tp.identity.len, ci, 1});
+        }
+        if (ci.p256) {
+            memcpy(&out.tuple_qxy[64 * i], ci.qx, 32);
+            memcpy(&out.tuple_qxy[64 * i + 32], ci.qy, 32);
+        }
+        if (!ci.p256) {
+            out.tuple_status[i] = TUPLE_ST_NEEDS_SW;
+            continue;
+        }
+        if (tp.sig.len == 0) {
+            out.tuple_status[i] = TUPLE_ST_EMPTY_SIG;
+            continue;
+        }
+        ECDSAPublicKey k;
+        memcpy(k.x, ci.qx, 32);
+        memcpy(k.y, ci.qy, 32);
+        k.on_curve = true;
+        Gate g = gate_item(&k, block + tp.sig.off, tp.sig.len, one_digest, 1);
+        if (!g.submit) {
+            if (g.res.err.ok()) out.tuple_status[i] = FABGPU_ST_RANGE;                                   // r >= n: (false, nil)
+            else if (g.res.err.msg.find("Invalid S") != std::string::npos) out.tuple_status[i] = FABGPU_ST_HIGH_S;
+            else out.tuple_status[i] = TUPLE_ST_BAD_DER;
+            continue;
+        }
+        memcpy(g0.qx, ci.qx, 32); memcpy(g0.qy, ci.qy, 32); memcpy(g0.r, g.r32, 32); memcpy(g0.s, g.s32, 32);
+        g0.key_id = ci.key_id;
+        g0.submit = true;
+    }
+    // hit counts -> the shared cache; identities that have earned a device table are queued for registration
+    if (!front.empty()) {
+        std::lock_guard<std::mutex> lk(idmu_);
+        for (const Front& f : front) {
+            auto it = idcache_.find(std::string((const char*)f.p, f.len));
+            if (it == idcache_.end()) continue;
+            CachedIdentity& c = it->second->second;
+            c.hits += f.hits;
+            if (EarnTableLocked(c)) hp.to_register.push_back(it->first);
+        }
+    }
+}
+
+// Tuples are independent: blocks of 4096+ tuples are gated on worker threads (contiguous ranges), then compacted in order.
+Error GPUCSP::GateAndCompact(HostPass& hp) const {
+    typedef PassScratch::Gated Gated;
+    const ParsedBlock& pb = hp.pb;
+    BlockVerdicts& out = hp.out;
+    PassScratch& ps_ = hp.ps;
+    const size_t nt = pb.tuples.size();
     std::map<std::string, int64_t> idemix_msps;
     {
         std::lock_guard<std::mutex> lk(idmu_);
@@ -2315,142 +2458,8 @@ Error GPUCSP::PreVerifyParsed(const uint8_t* block, const ParsedBlock& pb, Block
     std::vector<Gated>& gt = ps_.gt;
     if (gt.size() < nt) gt.resize(nt);
     std::vector<uint32_t> new_ids(1, 0);
-    std::vector<std::string> to_register;                 // guarded by idmu_
-    auto gate_range = [&](size_t lo, size_t hi, uint32_t* fresh) {
-        static const uint8_t one_digest[1] = {1};
-        // a block names few identities: a per-thread front cache (memcmp against the identities already met) keeps the shared
-        // map - and its 700-byte key copies - off the per-tuple path
-        struct Front {
-            const uint8_t* p;
-            uint32_t len;
-            CachedIdentity ci;
-            uint32_t hits;
-        };
-        std::vector<Front> front;
-        for (size_t i = lo; i < hi; i++) {
-            const BlockTuple& tp = pb.tuples[i];
-            Gated& g0 = gt[i];
-            g0.submit = false;
-            g0.nym = false;
-            out.tuple_tx[i] = tp.tx;
-            out.tuple_kind[i] = tp.kind;
-            memset(&out.tuple_qxy[64 * i], 0, 64);
-            if (tp.kind == TUPLE_BLOCK_SIG && !opt.block_sigs) {
-                out.tuple_status[i] = TUPLE_ST_SKIPPED;
-                continue;
-            }
-            CachedIdentity ci;
-            bool hit = false;
-            // An idemix creator carries a fresh pseudonym per transaction: it can be in no cache, so it is recognised first - without
-            // the shared map, its lock and its key copy (2 000 such creators in a block cost the gates 1.7 ms that way).  Precedence is
-            // kept: an identity that also yields a P-256 certificate key takes the certificate path below.
-            if (tp.kind == TUPLE_CREATOR && !idemix_msps.empty()) {
-                std::string mspid;
-                uint8_t tqx[32], tqy[32];
-                if (IdentityToIdemixNym(block + tp.identity.off, tp.identity.len, mspid, g0.qx, g0.qy) &&
-                    !IdentityToP256(block + tp.identity.off, tp.identity.len, tqx, tqy)) {
-                    // identity.Verify is NymSignature.Ver under the MSP's issuer key (msp/idemixmsp.go:584-599); an idemix identity is
-                    // never an endorser (docs/source/idemix.rst:171-176)
-                    auto im = idemix_msps.find(mspid);
-                    NymSignatureFields sf;
-                    if (im != idemix_msps.end() && im->second >= 0 && tp.sig.len != 0 && UnmarshalNymSignature(block + tp.sig.off, tp.sig.len, sf) &&
-                        sf.len[0] == 32 && sf.len[1] == 32 && sf.len[2] == 32 && sf.len[3] == 32) {
-                        memcpy(g0.r, sf.f[0], 32); memcpy(g0.s, sf.f[1], 32); memcpy(g0.srn, sf.f[2], 32); memcpy(g0.nonce, sf.f[3], 32);
-                        g0.key_id = im->second;
-                        g0.nym = true;
-                    } else {
-                        out.tuple_status[i] = TUPLE_ST_NEEDS_SW;
-                    }
-                    continue;
-                }
-            }
-            for (Front& f : front)
-                if (f.len == tp.identity.len && memcmp(f.p, block + tp.identity.off, f.len) == 0) {
-                    ci = f.ci;
-                    f.hits++;
-                    hit = true;
-                    break;
-                }
-            if (!hit) {
-                bool transient = false, found = false;
-                std::string key((const char*)block + tp.identity.off, tp.identity.len);
-                {
-                    std::lock_guard<std::mutex> lk(idmu_);
-                    auto it = idcache_.find(key);
-                    if (it != idcache_.end()) {
-                        idlru_.splice(idlru_.begin(), idlru_, it->second);      // most recently used
-                        ci = it->second->second;
-                        found = true;
-                    }
-                }
-                if (!found) {
-                    // decoded outside the lock (PEM + DER walk of ~800 untrusted bytes); NO device table here - that is earned
-                    // by being named id_register_after_ times (flush below)
-                    (*fresh)++;
-                    ci.p256 = IdentityToP256(block + tp.identity.off, tp.identity.len, ci.qx, ci.qy) && PublicKeyOnCurve(ci.qx, ci.qy);
-                    // idemix identities carry a fresh pseudonym per transaction: caching them would only churn the cache
-                    std::string ms;
-                    uint8_t tnx[32], tny[32];
-                    transient = !ci.p256 && IdentityToIdemixNym(block + tp.identity.off, tp.identity.len, ms, tnx, tny);
-                    if (!transient) {
-                        std::lock_guard<std::mutex> lk(idmu_);
-                        auto it = idcache_.find(key);
-                        if (it == idcache_.end()) {
-                            InsertIdentityLocked(std::string(key), ci);          // (the least recently used goes)
-                            id_version_.fetch_add(1, std::memory_order_release);   // (the device's copy of the cache is stale now)
-                        } else {
-                            ci = it->second->second;
-                        }
-                    }
-                }
-                if (!transient && front.size() < 64) front.push_back({block + tp.identity.off, tp.identity.len, ci, 1});
-            }
-            if (ci.p256) {
-                memcpy(&out.tuple_qxy[64 * i], ci.qx, 32);
-                memcpy(&out.tuple_qxy[64 * i + 32], ci.qy, 32);
-            }
-            if (!ci.p256) {
-                out.tuple_status[i] = TUPLE_ST_NEEDS_SW;
-                continue;
-            }
-            if (tp.sig.len == 0) {
-                out.tuple_status[i] = TUPLE_ST_EMPTY_SIG;
-                continue;
-            }
-            ECDSAPublicKey k;
-            memcpy(k.x, ci.qx, 32);
-            memcpy(k.y, ci.qy, 32);
-            k.on_curve = true;
-            Gate g = gate_item(&k, block + tp.sig.off, tp.sig.len, one_digest, 1);
-            if (!g.submit) {
-                if (g.res.err.ok()) out.tuple_status[i] = FABGPU_ST_RANGE;                                   // r >= n: (false, nil)
-                else if (g.res.err.msg.find("Invalid S") != std::string::npos) out.tuple_status[i] = FABGPU_ST_HIGH_S;
-                else out.tuple_status[i] = TUPLE_ST_BAD_DER;
-                continue;
-            }
-            memcpy(g0.qx, ci.qx, 32); memcpy(g0.qy, ci.qy, 32); memcpy(g0.r, g.r32, 32); memcpy(g0.s, g.s32, 32);
-            g0.key_id = ci.key_id;
-            g0.submit = true;
-        }
-        // hit counts -> the shared cache; identities that have earned a device table are queued for registration
-        if (!front.empty()) {
-            std::lock_guard<std::mutex> lk(idmu_);
-            for (const Front& f : front) {
-                auto it = idcache_.find(std::string((const char*)f.p, f.len));
-                if (it == idcache_.end()) continue;
-                CachedIdentity& c = it->second->second;
-                c.hits += f.hits;
-                if (c.p256 && c.key_id < 0 && !c.registering && c.hits >= id_register_after_ && id_registered_ < id_max_registered_) {
-                    c.registering = true;
-                    id_registered_++;
-                    to_register.push_back(it->first);
-                }
-            }
-        }
-    };
     auto clk0 = std::chrono::steady_clock::now();
-    constexpr int gate_max = 16;
-    const int nthreads = std::min(gate_max, nt >= 16384 ? 16 : (nt >= 4096 ? 8 : 1));     // <= 16 = the pool + the caller: all of them run at once (they meet at a barrier)
+    const int nthreads = std::min(kGateMax, nt >= 16384 ? 16 : (nt >= 4096 ? 8 : 1));     // all of them run at once (they meet at a barrier)
     auto in_threads = [&](const std::function<void(int, size_t, size_t)>& fn) {       // fn(worker, lo, hi) over contiguous tuple ranges
         if (nthreads == 1) {
             fn(0, 0, nt);
@@ -2482,7 +2491,7 @@ Error GPUCSP::PreVerifyParsed(const uint8_t* block, const ParsedBlock& pb, Block
     std::mutex gm;
     in_threads([&](int w, size_t lo, size_t hi) {
         try {
-            gate_range(lo, hi, &new_ids[w]);
+            GateRange(hp, idemix_msps, lo, hi, &new_ids[w]);
         } catch (...) {
             gate_failed.store(true, std::memory_order_release);
             arrived.fetch_add(1, std::memory_order_acq_rel);
@@ -2496,7 +2505,7 @@ Error GPUCSP::PreVerifyParsed(const uint8_t* block, const ParsedBlock& pb, Block
             }
         cnt[w + 1] = c;
         {
-            double t = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk0).count();
+            double t = ms_since(clk0);
             std::lock_guard<std::mutex> lk(gm);
             if (t > ms_gates_max) ms_gates_max = t;
         }
@@ -2526,33 +2535,47 @@ Error GPUCSP::PreVerifyParsed(const uint8_t* block, const ParsedBlock& pb, Block
     out.ms_gates = ms_gates_max;
     size_t n = 0;
     for (int w = 0; w < nthreads; w++) n += cnt[w + 1];
-    bool all_keyed = true;
-    for (uint8_t k : keyed_w) all_keyed = all_keyed && k;
+    hp.n = n;
+    for (uint8_t k : keyed_w) hp.all_keyed = hp.all_keyed && k;
     // One identity without a device table sends the whole block down the fresh-key kernel.  Splitting such a block into a table
     // launch and a fresh-key launch was tried (round 2): submitted one after the other the two cost what the single launch costs,
     // within +-0.3 ms on a 10 000-transaction block - the fresh-key kernel is latency-bound below 32 768 tuples, so
     // taking tuples away from it does not shorten it.
-    out.n_keyed = all_keyed ? n : 0;
-    std::vector<uint8_t>& hash_digests = ps_.hash_digests;   // (scratch of the pass: reused from block to block, like everything below)
-    bool hashes_done = false;
-    // The block's idemix creators: their pseudonym signatures ride in the ECDSA submission (fabgpu_identity_batch.n_nym) - messages read
-    // from the block where it already sits on the device, the nym kernel on a stream of its own next to the ECDSA kernels, the
-    // SHA-256(message) the memo wants from the same gather launch as the TxID / proposal-hash digests.  (As separate blocking calls
-    // with their own copy of the messages, 2 000 idemix creators cost a 10 000-tx block 2 ms.)
-    std::vector<uint32_t>&ns = ps_.nym_idx, &nsp = ps_.nym_sp, &niss = ps_.nym_iss;
-    std::vector<uint8_t>&nfields = ps_.nym_fields, &nst = ps_.nym_st;
-    std::vector<uint64_t>& nbits = ps_.nym_bits;
+    out.n_keyed = hp.all_keyed ? n : 0;
+    // the block's idemix creators, in tuple order
+    std::vector<uint32_t>& ns = ps_.nym_idx;
     ns.clear();
     for (size_t i = 0; i < nt; i++)
         if (gt[i].nym) ns.push_back((uint32_t)i);
-    const size_t mn = ns.size();
     out.tuple_nym_issuer.clear();                            // (the memo binds a pseudonym signature's entry to the issuer it was verified under)
-    if (mn) {
+    if (!ns.empty()) {
         out.tuple_nym_issuer.assign(nt, -1);
         for (uint32_t i : ns) out.tuple_nym_issuer[i] = gt[i].key_id;
     }
-    bool nym_rode = false;
-    if (mn && n) {
+    return Error();
+}
+
+// The ECDSA tuples in one fabgpu_identity_batch, the block as their message arena.  The block's idemix creators ride along
+// (fabgpu_identity_batch.n_nym) - messages read from the block where it already sits on the device, the nym kernel on a stream of
+// its own next to the ECDSA kernels, the SHA-256(message) the memo wants from the same gather launch as the TxID / proposal-hash
+// digests.  (As separate blocking calls with their own copy of the messages, 2 000 idemix creators cost a 10 000-tx block 2 ms.)
+Error GPUCSP::SubmitIdentityBatch(HostPass& hp) const {
+    typedef PassScratch::Gated Gated;
+    const uint8_t* const block = hp.block;
+    const ParsedBlock& pb = hp.pb;
+    BlockVerdicts& out = hp.out;
+    BlockUpload* const up = hp.up;
+    PassScratch& ps_ = hp.ps;
+    const bool want_digests = hp.want_digests, all_keyed = hp.all_keyed;
+    const size_t n = hp.n;
+    std::vector<uint32_t>&sub = ps_.sub, &ids = ps_.ids, &off = ps_.off, &pre_idx = ps_.pre_idx;
+    std::vector<uint8_t>&qx = ps_.qx, &qy = ps_.qy, &r = ps_.r, &s = ps_.s, &hash_digests = ps_.hash_digests;
+    std::vector<uint32_t>&ns = ps_.nym_idx, &nsp = ps_.nym_sp, &niss = ps_.nym_iss;
+    std::vector<uint8_t>&nfields = ps_.nym_fields, &nst = ps_.nym_st;
+    std::vector<uint64_t>& nbits = ps_.nym_bits;
+    const std::vector<Gated>& gt = ps_.gt;
+    const size_t mn = ns.size();
+    if (mn) {
         nsp.resize(2 * mn);
         niss.resize(mn);
         nfields.resize(6 * 32 * mn);
@@ -2568,205 +2591,213 @@ Error GPUCSP::PreVerifyParsed(const uint8_t* block, const ParsedBlock& pb, Block
             for (int k = 0; k < 6; k++) memcpy(&nfields[32 * (mn * k + j)], col[k], 32);
         }
     }
-    if (n) {
-        std::vector<uint32_t>& pre_off = ps_.pre_off;
-        pre_off.resize(2 * pb.prefixes.size() + 2);
-        for (size_t p = 0; p < pb.prefixes.size(); p++) {
-            pre_off[2 * p] = pb.prefixes[p].off;
-            pre_off[2 * p + 1] = pb.prefixes[p].off + pb.prefixes[p].len;
+    std::vector<uint32_t>& pre_off = ps_.pre_off;
+    pre_off.resize(2 * pb.prefixes.size() + 2);
+    for (size_t p = 0; p < pb.prefixes.size(); p++) {
+        pre_off[2 * p] = pb.prefixes[p].off;
+        pre_off[2 * p + 1] = pb.prefixes[p].off + pb.prefixes[p].len;
+    }
+    std::vector<uint64_t>& bits = ps_.bits;
+    std::vector<uint8_t>& st = ps_.st;
+    bits.assign((n + 63) / 64, 0);
+    st.assign(n, 0);
+    fabgpu_identity_batch d;
+    memset(&d, 0, sizeof(d));
+    d.n = n;
+    d.arena = block;
+    d.off = off.data();
+    d.n_prefixes = (uint32_t)pb.prefixes.size();
+    d.pre_off = pre_off.data();
+    d.pre_idx = pre_idx.data();
+    if (all_keyed) {
+        d.key_id = ids.data();
+    } else {
+        d.qx = qx.data();
+        d.qy = qy.data();
+    }
+    d.r = r.data();
+    d.s = s.data();
+    d.verdict_bits = bits.data();
+    d.status = st.data();
+    d.flags = FABGPU_IDB_SPANS;
+    if (!pb.tail.empty()) {                           // the orderers' block-signature messages (block_prepass.h TUPLE_BLOCK_SIG)
+        d.tail = pb.tail.data();
+        d.tail_base = pb.tail_base;
+        d.tail_len = (uint32_t)pb.tail.size();
+    }
+    std::vector<uint8_t>& dig = ps_.dig;
+    if (want_digests) {
+        if (dig.size() < n * 32) dig.resize(n * 32);
+        d.digests = dig.data();
+    }
+    // the TxID and proposal-hash digests of the endorser transactions ride along (one upload of the block, one submission)
+    const size_t nh = hp.skip_hash_checks ? 0 : pb.hash_checks.size();   // the switch exists for A/B timing only
+    std::vector<uint32_t>& gsp = ps_.gsp;
+    const size_t nhn = want_digests ? mn : 0;          // + SHA-256 of every idemix creator's message (the memo's digest)
+    gsp.assign((nh + nhn) * 6, 0);
+    hash_digests.assign((nh + nhn) * 32, 0);
+    for (size_t j = 0; j < nh; j++)
+        for (int p = 0; p < 3; p++) {
+            const Span& sp = pb.hash_checks[j].piece[p];
+            gsp[6 * j + 2 * p] = sp.off;
+            gsp[6 * j + 2 * p + 1] = sp.off + sp.len;
         }
-        std::vector<uint64_t>& bits = ps_.bits;
-        std::vector<uint8_t>& st = ps_.st;
-        bits.assign((n + 63) / 64, 0);
-        st.assign(n, 0);
-        fabgpu_identity_batch d;
-        memset(&d, 0, sizeof(d));
-        d.n = n;
-        d.arena = block;
-        d.off = off.data();
-        d.n_prefixes = (uint32_t)pb.prefixes.size();
-        d.pre_off = pre_off.data();
-        d.pre_idx = pre_idx.data();
-        if (all_keyed) {
-            d.key_id = ids.data();
-        } else {
-            d.qx = qx.data();
-            d.qy = qy.data();
-        }
-        d.r = r.data();
-        d.s = s.data();
-        d.verdict_bits = bits.data();
-        d.status = st.data();
+    for (size_t j = 0; j < nhn; j++) {
+        gsp[6 * (nh + j)] = nsp[2 * j];
+        gsp[6 * (nh + j) + 1] = nsp[2 * j + 1];
+    }
+    if (nh + nhn) {
+        d.n_gather = (uint32_t)(nh + nhn);
+        d.gather_spans = gsp.data();
+        d.gather_digests = hash_digests.data();
+        hp.hashes_done = nh != 0;
+    }
+    if (mn) {
+        d.n_nym = (uint32_t)mn;
+        d.nym_off = nsp.data();
+        d.nym_issuer = niss.data();
+        d.nym_fields = nfields.data();
+        d.nym_verdict_bits = nbits.data();
+        d.nym_status = nst.data();
+    }
+    auto clk1 = std::chrono::steady_clock::now();
+    uint64_t tok = up ? up->join() : 0;
+    out.ms_upload_wait = ms_since(clk1);
+    auto clk2 = std::chrono::steady_clock::now();
+    int rc = FABGPU_EINVAL;
+    if (tok) {
+        d.flags = FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED;
+        d.stage_token = tok;
+        rc = fabgpu_identity_verify_batch(hp.dv.ctx, &d);      // FABGPU_EINVAL: somebody else's upload replaced ours -> resubmit with the bytes
         d.flags = FABGPU_IDB_SPANS;
-        if (!pb.tail.empty()) {                           // the orderers' block-signature messages (block_prepass.h TUPLE_BLOCK_SIG)
-            d.tail = pb.tail.data();
-            d.tail_base = pb.tail_base;
-            d.tail_len = (uint32_t)pb.tail.size();
-        }
-        std::vector<uint8_t>& dig = ps_.dig;
-        if (want_digests) {
-            if (dig.size() < n * 32) dig.resize(n * 32);
-            d.digests = dig.data();
-        }
-        // the TxID and proposal-hash digests of the endorser transactions ride along (one upload of the block, one submission)
-        const size_t nh = skip_hash_checks ? 0 : pb.hash_checks.size();   // the switch exists for A/B timing only
-        std::vector<uint32_t>& gsp = ps_.gsp;
-        const size_t nhn = want_digests ? mn : 0;          // + SHA-256 of every idemix creator's message (the memo's digest)
-        gsp.assign((nh + nhn) * 6, 0);
-        hash_digests.assign((nh + nhn) * 32, 0);
-        for (size_t j = 0; j < nh; j++)
-            for (int p = 0; p < 3; p++) {
-                const Span& sp = pb.hash_checks[j].piece[p];
-                gsp[6 * j + 2 * p] = sp.off;
-                gsp[6 * j + 2 * p + 1] = sp.off + sp.len;
-            }
-        for (size_t j = 0; j < nhn; j++) {
-            gsp[6 * (nh + j)] = nsp[2 * j];
-            gsp[6 * (nh + j) + 1] = nsp[2 * j + 1];
-        }
-        if (nh + nhn) {
-            d.n_gather = (uint32_t)(nh + nhn);
-            d.gather_spans = gsp.data();
-            d.gather_digests = hash_digests.data();
-            hashes_done = nh != 0;
-        }
-        if (mn) {
-            d.n_nym = (uint32_t)mn;
-            d.nym_off = nsp.data();
-            d.nym_issuer = niss.data();
-            d.nym_fields = nfields.data();
-            d.nym_verdict_bits = nbits.data();
-            d.nym_status = nst.data();
-        }
-        auto clk1 = std::chrono::steady_clock::now();
-        uint64_t tok = up ? up->join() : 0;
-        auto clk2 = std::chrono::steady_clock::now();
-        out.ms_upload_wait = std::chrono::duration<double, std::milli>(clk2 - clk1).count();
-        int rc = FABGPU_EINVAL;
-        if (tok) {
-            d.flags = FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED;
-            d.stage_token = tok;
-            rc = fabgpu_identity_verify_batch(ctx_, &d);      // FABGPU_EINVAL: somebody else's upload replaced ours -> resubmit with the bytes
-            d.flags = FABGPU_IDB_SPANS;
-        }
-        if (!tok || rc == FABGPU_EINVAL) rc = fabgpu_identity_verify_batch(ctx_, &d);
-        out.ms_device = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk2).count();
-        if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
-        dv.passes.fetch_add(1, std::memory_order_relaxed);
-        for (size_t j = 0; j < n; j++) {
-            bool bit = (bits[j >> 6] >> (j & 63)) & 1;
-            if (all_keyed && st[j] == FABGPU_ST_OFF_CURVE) {
-                // (the id was retired between the cache lookup above and the launch - key_slots.h: "use bccsp/sw", never "invalid")
-                out.tuple_status[sub[j]] = TUPLE_ST_NEEDS_SW;
-                continue;
-            }
-            out.tuple_status[sub[j]] = (bit && st[j] == FABGPU_ST_VALID) ? FABGPU_ST_VALID : (st[j] == FABGPU_ST_VALID ? FABGPU_ST_BAD_MATH : st[j]);
-            out.tuple_hashed[sub[j]] = 1;
-            if (want_digests) memcpy(&out.tuple_digest[32 * (size_t)sub[j]], &dig[32 * j], 32);
-        }
-        for (size_t j = 0; j < mn; j++) {   // FABGPU_NYM_VALID = 0, BAD_PROOF = 1 (= "signature invalid"), NEEDS_SW = 6 = TUPLE_ST_NEEDS_SW
-            out.tuple_status[ns[j]] = nst[j];
-            // NymVerifier.Verify receives the whole message, not a digest (bccsp/idemix/handlers/nymsigner.go:62-95): the memo entry of
-            // a pseudonym signature is keyed on SHA-256(message) - computed by the device over the bytes the nym kernel verified, and by
-            // the Go wrapper over the bytes it is asked about
-            if (!want_digests || nst[j] == FABGPU_NYM_NEEDS_SW) continue;
-            memcpy(&out.tuple_digest[32 * (size_t)ns[j]], &hash_digests[32 * (nh + j)], 32);
-            out.tuple_hashed[ns[j]] = 1;
-            memcpy(&out.tuple_qxy[64 * (size_t)ns[j]], gt[ns[j]].qx, 32);        // the pseudonym (Nym.x, Nym.y) in the key slot
-            memcpy(&out.tuple_qxy[64 * (size_t)ns[j] + 32], gt[ns[j]].qy, 32);
-        }
-        nym_rode = mn != 0;
     }
-    // idemix creators of a block WITHOUT any ECDSA tuple (nothing to ride on): their messages (the envelope payloads) are gathered into
-    // one arena for the nym entry point
-    auto clk_nym = std::chrono::steady_clock::now();
-    struct NymClock {
-        BlockVerdicts& o;
-        std::chrono::steady_clock::time_point t0;
-        ~NymClock() { o.ms_nym = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-    };
-    {
-        NymClock nym_clock{out, clk_nym};
-        const size_t m = nym_rode ? 0 : mn;
-        if (m) {
-            std::vector<uint8_t> cols[6], arena;
-            std::vector<uint32_t> iss(m), noff(m + 1, 0);
-            size_t total = 0;
-            for (size_t j = 0; j < m; j++) total += pb.tuples[ns[j]].suffix.len;
-            if (total > 0x7FFFFFFFull) return Error("idemix creator messages exceed 2 GiB");
-            arena.reserve(total + 1);
-            for (int k = 0; k < 6; k++) cols[k].reserve(m * 32);
-            for (size_t j = 0; j < m; j++) {
-                const Gated& g0 = gt[ns[j]];
-                const BlockTuple& tp = pb.tuples[ns[j]];
-                cols[0].insert(cols[0].end(), g0.qx, g0.qx + 32);
-                cols[1].insert(cols[1].end(), g0.qy, g0.qy + 32);
-                cols[2].insert(cols[2].end(), g0.r, g0.r + 32);
-                cols[3].insert(cols[3].end(), g0.s, g0.s + 32);
-                cols[4].insert(cols[4].end(), g0.srn, g0.srn + 32);
-                cols[5].insert(cols[5].end(), g0.nonce, g0.nonce + 32);
-                iss[j] = (uint32_t)g0.key_id;
-                arena.insert(arena.end(), block + tp.suffix.off, block + tp.suffix.off + tp.suffix.len);
-                noff[j + 1] = (uint32_t)arena.size();
-            }
-            if (arena.empty()) arena.push_back(0);
-            std::vector<uint64_t> bits((m + 63) / 64);
-            std::vector<uint8_t> st(m);
-            int rc = fabgpu_idemix_nym_verify_batch(ctx_, m, arena.data(), noff.data(), iss.data(), cols[0].data(), cols[1].data(), cols[2].data(),
-                                                    cols[3].data(), cols[4].data(), cols[5].data(), bits.data(), st.data());
-            if (rc != FABGPU_OK) return Error(std::string("GPU nym verify failed: ") + fabgpu_strerror(rc));
-            for (size_t j = 0; j < m; j++)   // FABGPU_NYM_VALID = 0, BAD_PROOF = 1 (= "signature invalid"), NEEDS_SW = 6 = TUPLE_ST_NEEDS_SW
-                out.tuple_status[ns[j]] = st[j];
-            if (want_digests) {
-                // NymVerifier.Verify receives the whole message, not a digest (bccsp/idemix/handlers/nymsigner.go:62-95): the memo
-                // entry of a pseudonym signature is keyed on SHA-256(message) - computed here by the device over the bytes the nym
-                // kernel just verified, and by the Go wrapper over the bytes it is asked about
-                std::vector<uint8_t> nd(m * 32);
-                rc = fabgpu_sha256_batch(ctx_, m, arena.data(), noff.data(), nd.data());
-                if (rc != FABGPU_OK) return Error(std::string("GPU hash failed: ") + fabgpu_strerror(rc));
-                for (size_t j = 0; j < m; j++) {
-                    if (st[j] == FABGPU_NYM_NEEDS_SW) continue;
-                    memcpy(&out.tuple_digest[32 * (size_t)ns[j]], &nd[32 * j], 32);
-                    out.tuple_hashed[ns[j]] = 1;
-                    memcpy(&out.tuple_qxy[64 * (size_t)ns[j]], gt[ns[j]].qx, 32);        // the pseudonym (Nym.x, Nym.y) in the key slot
-                    memcpy(&out.tuple_qxy[64 * (size_t)ns[j] + 32], gt[ns[j]].qy, 32);
-                }
-            }
+    if (!tok || rc == FABGPU_EINVAL) rc = fabgpu_identity_verify_batch(hp.dv.ctx, &d);
+    out.ms_device = ms_since(clk2);
+    if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
+    hp.dv.passes.fetch_add(1, std::memory_order_relaxed);
+    for (size_t j = 0; j < n; j++) {
+        bool bit = (bits[j >> 6] >> (j & 63)) & 1;
+        if (all_keyed && st[j] == FABGPU_ST_OFF_CURVE) {
+            // (the id was retired between the cache lookup above and the launch - key_slots.h: "use bccsp/sw", never "invalid")
+            out.tuple_status[sub[j]] = TUPLE_ST_NEEDS_SW;
+            continue;
         }
+        out.tuple_status[sub[j]] = (bit && st[j] == FABGPU_ST_VALID) ? FABGPU_ST_VALID : (st[j] == FABGPU_ST_VALID ? FABGPU_ST_BAD_MATH : st[j]);
+        out.tuple_hashed[sub[j]] = 1;
+        if (want_digests) memcpy(&out.tuple_digest[32 * (size_t)sub[j]], &dig[32 * j], 32);
     }
-    // TxID / proposal hash: compare what the device computed with what the block claims.  (No ECDSA tuple went to the device -
-    // a block of idemix creators only, say - means no submission the hashes could ride on: those checks stay with the Go validators.)
+    for (size_t j = 0; j < mn; j++)
+        write_nym_result(out, ns[j], nst[j], want_digests ? &hash_digests[32 * (nh + j)] : nullptr, gt[ns[j]].qx, gt[ns[j]].qy);
+    hp.nym_rode = mn != 0;
+    return Error();
+}
+
+// idemix creators of a block WITHOUT any ECDSA tuple (nothing to ride on): their messages (the envelope payloads) are gathered into
+// one arena for the nym entry point
+Error GPUCSP::VerifyNymsAlone(HostPass& hp) const {
+    typedef PassScratch::Gated Gated;
+    const uint8_t* const block = hp.block;
+    const ParsedBlock& pb = hp.pb;
+    const std::vector<uint32_t>& ns = hp.ps.nym_idx;
+    const std::vector<Gated>& gt = hp.ps.gt;
+    fabgpu_ctx* const ctx_ = hp.dv.ctx;
+    const size_t m = ns.size();
+    std::vector<uint8_t> cols[6], arena;
+    std::vector<uint32_t> iss(m), noff(m + 1, 0);
+    size_t total = 0;
+    for (size_t j = 0; j < m; j++) total += pb.tuples[ns[j]].suffix.len;
+    if (total > 0x7FFFFFFFull) return Error("idemix creator messages exceed 2 GiB");
+    arena.reserve(total + 1);
+    for (int k = 0; k < 6; k++) cols[k].reserve(m * 32);
+    for (size_t j = 0; j < m; j++) {
+        const Gated& g0 = gt[ns[j]];
+        const BlockTuple& tp = pb.tuples[ns[j]];
+        cols[0].insert(cols[0].end(), g0.qx, g0.qx + 32);
+        cols[1].insert(cols[1].end(), g0.qy, g0.qy + 32);
+        cols[2].insert(cols[2].end(), g0.r, g0.r + 32);
+        cols[3].insert(cols[3].end(), g0.s, g0.s + 32);
+        cols[4].insert(cols[4].end(), g0.srn, g0.srn + 32);
+        cols[5].insert(cols[5].end(), g0.nonce, g0.nonce + 32);
+        iss[j] = (uint32_t)g0.key_id;
+        arena.insert(arena.end(), block + tp.suffix.off, block + tp.suffix.off + tp.suffix.len);
+        noff[j + 1] = (uint32_t)arena.size();
+    }
+    if (arena.empty()) arena.push_back(0);
+    std::vector<uint64_t> bits((m + 63) / 64);
+    std::vector<uint8_t> st(m);
+    int rc = fabgpu_idemix_nym_verify_batch(ctx_, m, arena.data(), noff.data(), iss.data(), cols[0].data(), cols[1].data(), cols[2].data(),
+                                            cols[3].data(), cols[4].data(), cols[5].data(), bits.data(), st.data());
+    if (rc != FABGPU_OK) return Error(std::string("GPU nym verify failed: ") + fabgpu_strerror(rc));
+    std::vector<uint8_t> nd;
+    if (hp.want_digests) {
+        nd.resize(m * 32);
+        rc = fabgpu_sha256_batch(ctx_, m, arena.data(), noff.data(), nd.data());
+        if (rc != FABGPU_OK) return Error(std::string("GPU hash failed: ") + fabgpu_strerror(rc));
+    }
+    for (size_t j = 0; j < m; j++) write_nym_result(hp.out, ns[j], st[j], hp.want_digests ? &nd[32 * j] : nullptr, gt[ns[j]].qx, gt[ns[j]].qy);
+    return Error();
+}
+
+// TxID / proposal hash: compare what the device computed with what the block claims.  (No ECDSA tuple went to the device -
+// a block of idemix creators only, say - means no submission the hashes could ride on: those checks stay with the Go validators.)
+void GPUCSP::CompareHashesAndSummarize(HostPass& hp) {
+    const ParsedBlock& pb = hp.pb;
+    BlockVerdicts& out = hp.out;
     std::vector<uint8_t> bad_txid(pb.n_tx, 0), bad_phash(pb.n_tx, 0);
-    if (hashes_done)
+    if (hp.hashes_done)
         for (size_t j = 0; j < pb.hash_checks.size(); j++) {
             const BlockHashCheck& hc = pb.hash_checks[j];
-            if (HashCheckMatches(block, hc, hash_digests.data() + 32 * j)) continue;
+            if (HashCheckMatches(hp.block, hc, hp.ps.hash_digests.data() + 32 * j)) continue;
             if (hc.kind == HASH_TXID) bad_txid[hc.tx] = 1;
             else bad_phash[hc.tx] = 1;
         }
-    // per-transaction summary, in the order ValidateTransaction and then VSCC would reject (core/common/validation/msgvalidation.go:
-    // 248-320): not understood > bad creator signature > bad TxID > bad proposal hash > bad endorsement > "ask bccsp/sw" > all valid
-    std::vector<uint8_t> bad_creator(pb.n_tx, 0), bad_end(pb.n_tx, 0), sw(pb.n_tx, 0);
-    for (size_t i = 0; i < nt; i++) {
-        uint8_t stt = out.tuple_status[i];
-        if (stt == FABGPU_ST_VALID) continue;
-        uint32_t t = out.tuple_tx[i];
-        if (t >= pb.n_tx) continue;                        // block-level tuples (orderer signatures) do not flag a transaction
-        if (stt == TUPLE_ST_NEEDS_SW) sw[t] = 1;
-        else if (out.tuple_kind[i] == TUPLE_CREATOR) bad_creator[t] = 1;
-        else bad_end[t] = 1;
+    SummarizeTransactions(pb.n_tx, pb.tx_understood.data(), out.tuple_status.size(), out.tuple_tx.data(), out.tuple_kind.data(), out.tuple_status.data(),
+                          hp.hashes_done ? bad_txid.data() : nullptr, hp.hashes_done ? bad_phash.data() : nullptr, out.tx_flags.data());
+}
+
+Error GPUCSP::PreVerifyParsed(const uint8_t* block, const ParsedBlock& pb, BlockVerdicts& out, BlockUpload* up, const PassOptions& opt) const {
+    // `out` may come back from the previous block (the C entry points keep one per calling thread): its vectors keep their capacity -
+    // a fresh 3 MB of answer arrays per block is 700 page faults - and every element is (re)written below
+    const bool want_digests = opt.want_digests || opt.seed_memo;
+    const size_t nt = pb.tuples.size();
+    out.n_tx = pb.n_tx;
+    out.distinct_identities = 0;
+    out.ms_gates = out.ms_upload_wait = out.ms_device = 0;
+    out.memo_seeded = 0;
+    out.tx_type = pb.tx_type;
+    out.tx_flags.resize(pb.n_tx);                        // (written at the end: SummarizeTransactions)
+    out.tuple_tx.resize(nt);
+    out.tuple_kind.resize(nt);
+    out.tuple_status.assign(nt, FABGPU_ST_VALID);
+    out.tuple_qxy.resize(nt * 64);                       // written per tuple by the gates (key or zeros)
+    out.tuple_hashed.assign(nt, 0);
+    if (want_digests) out.tuple_digest.assign(nt * 32, 0);
+    else out.tuple_digest.clear();
+    out.n_block_sigs = pb.n_block_sigs;
+    out.block_sigs_understood = pb.block_sigs_understood ? 1 : 0;
+    // The scratch below (8 MB for a 40 000-tuple block) is reused from block to block instead of being allocated - and page-faulted
+    // in - per call.  Passes of different callers run side by side, each on a set of its own (up to four are kept): one caller's gates
+    // and flags overlap another's device call (two callers, 10 000-tx blocks: 3.2 ms per block with one pass at a time).
+    ScratchLease lease(this);
+    // the device this pass runs on: where its block travelled to, or - no upload - wherever the ring points
+    Dev& dv = *devs_[(size_t)(up && up->routed ? up->dev : RouteBlock(opt.block_seq))];
+    bool skip_hash_checks;
+    {
+        std::lock_guard<std::mutex> lk(opt_mu_);
+        skip_hash_checks = opts_.pass_skip_hash_checks > 0;
     }
-    for (uint32_t t = 0; t < pb.n_tx; t++) {
-        if (out.tx_flags[t] == TX_NOT_UNDERSTOOD) continue;
-        out.tx_flags[t] = bad_creator[t] ? TX_BAD_CREATOR_SIGNATURE
-                          : bad_txid[t]  ? TX_BAD_TXID
-                          : bad_phash[t] ? TX_BAD_PROPOSAL_HASH
-                          : bad_end[t]   ? TX_BAD_ENDORSEMENT
-                          : sw[t]        ? TX_NEEDS_SW
-                                         : TX_ALL_SIGNATURES_VALID;
+    HostPass hp{block, pb, out, up, opt, *lease.p, dv, want_digests, skip_hash_checks};
+    Error e = GateAndCompact(hp);
+    if (e.ok() && hp.n) e = SubmitIdentityBatch(hp);
+    if (!e.ok()) return e;
+    {   // idemix creators of a block WITHOUT any ECDSA tuple: nothing to ride on
+        StageClock nym_clock{out.ms_nym};
+        if (!hp.nym_rode && !hp.ps.nym_idx.empty()) e = VerifyNymsAlone(hp);
+        if (!e.ok()) return e;
     }
-    RegisterQueued(to_register);
-    if (opt.seed_memo) SeedMemo(block, pb, out, opt, ps_.sub, gate_max, up);
+    CompareHashesAndSummarize(hp);
+    RegisterQueued(hp.to_register);
+    if (opt.seed_memo) SeedMemo(block, pb, out, opt, hp.ps.sub, kGateMax, up);
     return Error();
 }
 

@@ -16,6 +16,7 @@
 #include <map>
 #include <array>
 #include <atomic>
+#include <chrono>
 #include <mutex>
 
 #include "reader_lock.h"
@@ -146,6 +147,11 @@ struct ProviderOptions {
     uint32_t audit_permille = 0;       // share of the digests / verdicts handed out that is re-computed on the CPU first (0 .. 1000; 0: none)
 };
 constexpr int kMaxProviderDevices = 64;   // contexts per provider (8 GPUs x up to 8 contexts each)
+
+// milliseconds since t0 (the stage clocks of the block pass and of its C entries)
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 class GPUCSP {
    public:
@@ -367,6 +373,10 @@ class GPUCSP {
     mutable uint64_t id_next_serial_ = 1;
     // (idmu_ held) a new cache entry at the front of the LRU list; evicts what no longer fits
     void InsertIdentityLocked(std::string&& key, CachedIdentity ci, bool evict_now = true) const;
+    // (idmu_ held) THE rule by which an identity earns a device comb table: a P-256 key without a table, nobody building one, named
+    // id_register_after_ times, room in the budget.  true: it is marked `registering` and counted in id_registered_ - the caller
+    // queues its key for RegisterQueued.
+    bool EarnTableLocked(CachedIdentity& c) const;
     mutable size_t id_max_ = 4096, id_max_registered_ = 256, id_registered_ = 0;
     mutable uint32_t id_register_after_ = 64;
     // Every device of the pool holds a copy of this cache (Dev::idtab_*), rebuilt before a pass on that device whenever id_version_ moved.
@@ -393,6 +403,25 @@ class GPUCSP {
     bool RegisterKeysOnAllDevices(const std::vector<std::pair<std::string, CachedIdentity>>& keys, std::vector<int64_t>& ids) const;
     void SeedMemo(const uint8_t* block, const ParsedBlock& pb, BlockVerdicts& out, const PassOptions& opt, std::vector<uint32_t>& sel_scratch, int gate_max,
                   BlockUpload* up = nullptr) const;
+    // The steps of the two routes of the block pass, in the order the routes run them (bccsp_host.cpp).  HostPass / DevicePass: what the
+    // steps of one pass share - plain structs of references and the few values one step leaves for the next.
+    struct HostPass;
+    struct DevicePass;
+    struct BlockMemo;
+    void GateRange(HostPass& hp, const std::map<std::string, int64_t>& idemix_msps, size_t lo, size_t hi, uint32_t* fresh) const;
+    Error GateAndCompact(HostPass& hp) const;
+    Error SubmitIdentityBatch(HostPass& hp) const;
+    Error VerifyNymsAlone(HostPass& hp) const;
+    static void CompareHashesAndSummarize(HostPass& hp);
+    bool ListIdemixMsps(std::vector<DevIdemixMsp>& msps) const;               // false: more (or longer) than the device route carries
+    static void CountEnvelopesOnHost(DevicePass& dp);
+    static bool WalkSizes(void* device_pass, const WalkCounts& c, WalkOut& o);     // WalkRequest::sizes / ::memo_grow (plain function pointers)
+    static uint8_t* WalkMemoGrow(void* device_pass, size_t bytes);
+    void BuildWalkRequest(DevicePass& dp, WalkRequest& rq, uint64_t stage_token) const;
+    static void FinishDeviceAnswers(DevicePass& dp, const WalkRequest& rq);
+    void CountDeviceHits(DevicePass& dp) const;
+    void LearnDeviceIdentities(DevicePass& dp, const WalkRequest& rq) const;
+    void PublishDeviceMemo(DevicePass& dp, const WalkRequest& rq, std::shared_ptr<BlockMemo>& bm) const;
     // verdict memo
     // One table per BLOCK (seeded once by the pass, dropped whole when the block's validation returns): an open-addressed index over
     // length-framed keys stored back to back - no allocation per entry, filled by the pass's worker threads in parallel (a
@@ -440,6 +469,18 @@ class GPUCSP {
     };
     bool PublishMemo(const std::shared_ptr<BlockMemo>& bm) const;   // push under the lock, oldest blocks out while over capacity; false: poisoned, nothing published
     mutable std::vector<std::shared_ptr<BlockMemo>> memo_free_;    // evicted tables, recycled: 7 MB of fresh pages per block otherwise
+    // A table for the block at hand: out of memo_free_ (prefer_pinned: one that already owns pinned room, if there is one) or a new one ...
+    std::shared_ptr<BlockMemo> TakeMemoTable(bool prefer_pinned) const;
+    // ... which goes back to memo_free_ (bounded by memo_free_max_) unless it was published: whoever publishes it resets `bm`
+    struct MemoReturn {
+        const GPUCSP* c;
+        std::shared_ptr<BlockMemo>& bm;
+        ~MemoReturn();
+    };
+    // The digest memo's share of a table about to be published: the upload's host copy of the block moves into it, with the orderers'
+    // signature messages (`tail`: they are not in the block) - when the table has an index over the copy (hslots_v / hspans_v) and the
+    // upload left one.  Otherwise the table answers bccsp.Verify only: its digest-memo views are cleared.
+    static void MemoAdoptCopy(BlockMemo& bm, BlockUpload* up, const uint8_t* tail, size_t tail_len, uint32_t tail_base);
     mutable size_t memo_free_max_ = 4, scratch_free_max_ = 4;      // (both grow with the pool and with ProviderOptions::concurrent_passes)
     mutable BigReaderLock memo_mu_;                       // readers (every bccsp.Verify of every validator thread) share no cache line: reader_lock.h
     mutable std::deque<std::shared_ptr<BlockMemo>> memo_blocks_;   // oldest first
@@ -494,6 +535,13 @@ class GPUCSP {
     mutable Coalescer<CoReqI> co_identity_sha3_;                      // a launch hashes with ONE family: SHA3 callers queue apart
     mutable std::mutex pass_mu_;                                      // guards scratch_free_
     mutable std::vector<std::unique_ptr<PassScratch>> scratch_free_;
+    // one set of scratch for the duration of a pass: out of scratch_free_ (or new), back into it (up to scratch_free_max_ are kept)
+    struct ScratchLease {
+        const GPUCSP* c;
+        std::unique_ptr<PassScratch> p;
+        explicit ScratchLease(const GPUCSP* c_);
+        ~ScratchLease();
+    };
 };
 
 }  // namespace bccsp

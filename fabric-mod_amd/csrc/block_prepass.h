@@ -61,6 +61,31 @@ enum : uint8_t {
 //                       SHA-256(Header.channel_header || TransactionAction.header || ChaincodeActionPayload.chaincode_proposal_payload),
 //                       compared with ProposalResponsePayload.proposal_hash
 
+// The per-transaction summary of a pass, in the order ValidateTransaction and then VSCC would reject (core/common/validation/
+// msgvalidation.go:248-320): not understood > bad creator signature > bad TxID > bad proposal hash > bad endorsement > "ask bccsp/sw" >
+// all valid.  (The device route states the same order in block_walk_kernels.hip.)  Plain arrays: n_tx bytes of tx_understood,
+// bad_txid, bad_phash (the latter two nullptr when no hash was computed) and tx_flags (out); the tuples' transaction, kind and status.
+// Block-level tuples (tuple_tx >= n_tx: orderer signatures) do not flag a transaction.
+inline void SummarizeTransactions(uint32_t n_tx, const uint8_t* tx_understood, size_t n_tuples, const uint32_t* tuple_tx, const uint8_t* tuple_kind,
+                                  const uint8_t* tuple_status, const uint8_t* bad_txid, const uint8_t* bad_phash, uint8_t* tx_flags) {
+    enum : uint8_t { CREATOR = 1, TXID = 2, PHASH = 4, ENDORSEMENT = 8, SW = 16 };   // what is wrong with a transaction, gathered in tx_flags
+    for (uint32_t t = 0; t < n_tx; t++) tx_flags[t] = (bad_txid && bad_txid[t] ? TXID : 0) | (bad_phash && bad_phash[t] ? PHASH : 0);
+    for (size_t i = 0; i < n_tuples; i++) {
+        if (tuple_status[i] == 0 /* FABGPU_ST_VALID */ || tuple_tx[i] >= n_tx) continue;
+        tx_flags[tuple_tx[i]] |= tuple_status[i] == TUPLE_ST_NEEDS_SW ? SW : tuple_kind[i] == TUPLE_CREATOR ? CREATOR : ENDORSEMENT;
+    }
+    for (uint32_t t = 0; t < n_tx; t++) {
+        const uint8_t bad = tx_flags[t];
+        tx_flags[t] = !tx_understood[t]   ? TX_NOT_UNDERSTOOD
+                      : bad & CREATOR     ? TX_BAD_CREATOR_SIGNATURE
+                      : bad & TXID        ? TX_BAD_TXID
+                      : bad & PHASH       ? TX_BAD_PROPOSAL_HASH
+                      : bad & ENDORSEMENT ? TX_BAD_ENDORSEMENT
+                      : bad & SW          ? TX_NEEDS_SW
+                                          : TX_ALL_SIGNATURES_VALID;
+    }
+}
+
 struct ParsedBlock {
     uint32_t n_tx = 0;
     std::vector<uint8_t> tx_type;         // ChannelHeader.type per envelope (-> 255 if not parsed)

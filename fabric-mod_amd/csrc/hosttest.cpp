@@ -16,6 +16,7 @@
 #include "coalescer.h"
 #include "pass_route.h"
 #include "block_walk_core.h"
+#include "block_prepass.h"
 #include "sha3_256.h"
 
 using namespace fab;
@@ -450,5 +451,11 @@ void hosttest_sha3_256_prefixed(const uint8_t* prefix, size_t plen, const uint8_
     if (plen) memcpy(buf.data() + 3 + len + 5, prefix, plen);
     const uint32_t base = (uint32_t)(plen / SHA3_256_RATE) * SHA3_256_RATE;
     sha3_256_host_stream(buf.data(), buf.size(), mid, (uint32_t)(3 + len + 5) + base, (uint32_t)plen - base, 3, (uint32_t)len, out32);
+}
+// the block pass's per-transaction summary (block_prepass.h SummarizeTransactions); hashes_done == 0: no TxID / proposal hash was computed
+void hosttest_summarize_transactions(uint32_t n_tx, const uint8_t* tx_understood, size_t n_tuples, const uint32_t* tuple_tx, const uint8_t* tuple_kind,
+                                     const uint8_t* tuple_status, int hashes_done, const uint8_t* bad_txid, const uint8_t* bad_phash, uint8_t* tx_flags) {
+    bccsp::SummarizeTransactions(n_tx, tx_understood, n_tuples, tuple_tx, tuple_kind, tuple_status, hashes_done ? bad_txid : nullptr,
+                                 hashes_done ? bad_phash : nullptr, tx_flags);
 }
 }

@@ -857,6 +857,54 @@ def test_idemix_creators_on_the_device_route(monkeypatch):
 
 
 @pytest.mark.gpu
+def test_idemix_creators_with_no_ecdsa_submission_to_ride_on(csp):
+    """A block whose only signatures are pseudonym signatures (three idemix creators, endorser lists empty), on the host route: there is
+    no fabgpu_identity_batch to ride in, so the nym entry point and the hash entry point are called on their own.  Statuses are
+    oracle/idemix_oracle.py's; digests, the pseudonym in the key slot and issuer-bound memo entries exist exactly for the two signatures
+    the device decided."""
+    import random as pyrandom
+    import idemix_oracle as io
+    from idemix_common import be32, fixtures
+    raw_ipk = bytes.fromhex(json.load(open(os.path.join(ROOT, "tests", "golden", "idemix_fixtures.json")))["msps"]["MSP1OU1"]["ipk"])
+    ipk, sk = fixtures()["MSP1OU1"]["ipk"], fixtures()["MSP1OU1"]["signer"].sk
+    prng, rng = pyrandom.Random(31), np.random.default_rng(31)
+    envs, want, nyms, payloads, sigs = [], [], [], [], []
+    for t, (mspid, flip) in enumerate([("IdemixMSP1", False), ("IdemixMSP1", True), ("UnknownIdemixMSP", False)]):
+        nym, r_nym = io.make_nym(sk, ipk, prng)
+        creator = bb.serialized_idemix_identity(mspid, be32(nym[0]), be32(nym[1]))
+        payload, _ = bb.consistent_endorser_tx("mychannel", creator, b"nonce%d" % t, bytes(rng.integers(0, 256, size=200, dtype=np.uint8)),
+                                               bytes(rng.integers(0, 256, size=300, dtype=np.uint8)), lambda prp: [])
+        sig = io.nym_sign(sk, nym, r_nym, ipk, payload, prng)
+        if flip:                                              # one bit of ProofSSk
+            sig = dict(sig, proof_s_sk=sig["proof_s_sk"][:-1] + bytes([sig["proof_s_sk"][-1] ^ 1]))
+        want.append(io.nym_verify(sig, nym, ipk, payload) if mspid == "IdemixMSP1" else io.NYM_NEEDS_SW)   # (an MSP id nobody registered)
+        nyms.append(be32(nym[0]) + be32(nym[1]))
+        payloads.append(payload)
+        sigs.append(io.nym_signature_marshal(sig))
+        envs.append(bb.envelope(payload, sigs[-1]))
+    assert want == [io.NYM_VALID, io.NYM_BAD_PROOF, io.NYM_NEEDS_SW]
+    assert csp.idemix_msp_register("IdemixMSP1", raw_ipk) >= 0
+    csp.set_option("pass_stage_min_bytes", 1 << 40)           # the host route
+    before = fabgpu.pass_routes(csp)
+    r = fabgpu.preverify_block2(csp, bb.block(9, envs), block_seq=30, seed_memo=True)
+    after = fabgpu.pass_routes(csp)
+    assert (after["device_walks"], after["host_walks"]) == (before["device_walks"], before["host_walks"] + 1)
+    assert r["tuple_kind"].tolist() == [0, 0, 0] and r["tuple_tx"].tolist() == [0, 1, 2]
+    assert r["tuple_status"].tolist() == want
+    assert r["tx_flags"].tolist() == [fabgpu.TX_ALL_SIGNATURES_VALID, fabgpu.TX_BAD_CREATOR_SIGNATURE, fabgpu.TX_NEEDS_SW]
+    assert r["tuple_hashed"].tolist() == [1, 1, 0] and r["memo_seeded"] == 2 and r["n_keyed"] == 0
+    ipk_hash = bytes(ipk.hash)
+    for i in range(3):
+        digest = hashlib.sha256(payloads[i]).digest()
+        decided = want[i] != io.NYM_NEEDS_SW
+        assert bytes(r["tuple_digest"][i]) == (digest if decided else bytes(32))
+        assert bytes(r["tuple_qxy"][i]) == (nyms[i] if decided else bytes(64))
+        assert fabgpu.memo_lookup_nym(csp, ipk_hash, nyms[i][:32], nyms[i][32:], sigs[i], digest) == (want[i] if decided else None)
+        assert fabgpu.memo_lookup(csp, nyms[i][:32], nyms[i][32:], sigs[i], digest) is None
+    assert fabgpu.memo_evict_block(csp, 30) == 2
+
+
+@pytest.mark.gpu
 def test_a_certificate_beyond_the_device_decoders_window_costs_its_own_transactions_only(csp, monkeypatch):
     """Round 3 declined the whole block for ONE identity whose PEM body exceeded the decoder's buffer (4 096 base64 digits): anybody who
     can submit a transaction could send every block down the 3.3x slower host walk.  Now the device decodes a certificate of any length
