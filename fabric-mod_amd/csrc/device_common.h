@@ -96,12 +96,15 @@ __device__ __forceinline__ void sha256_stream_t(const uint32_t* __restrict__ are
         maxblk = other > maxblk ? other : maxblk;
     }
     maxblk = __builtin_amdgcn_readfirstlane(maxblk);
-    const int32_t vstart = (int32_t)sb - (int32_t)a;   // B's bytes sit at stream position a: virtual start of the B stream
-    const uint32_t shift = (uint32_t)vstart & 3u;      // byte misalignment of the B stream
+    // B's bytes sit at stream position a: the B stream starts at arena byte sb - a, slightly negative for a prefixed lane whose own
+    // bytes start early.  Its first aligned dword is floor((sb - a) / 4), formed from sb's dword and a small signed remainder, never from
+    // a signed byte address: sb goes up to 2^32 - 1 (a dword index is 2^30 at the most).
+    const uint32_t shift = (sb - a) & 3u;              // byte misalignment of the B stream
+    const int32_t w0 = (int32_t)(sb >> 2) + (((int32_t)(sb & 3u) - (int32_t)a) >> 2);
     const int32_t last_word = arena_words ? (int32_t)arena_words - 1 : 0;
     uint32_t nxt[17];
     auto fetch = [&](uint32_t blk_, uint32_t (&dst)[17]) {
-        const int32_t wi_ = (vstart + (int32_t)(blk_ << 6)) >> 2;     // first aligned dword (may be negative in block 0 of a prefixed lane)
+        const int32_t wi_ = (int32_t)((uint32_t)w0 + (blk_ << 4));    // first aligned dword (may be negative in block 0 of a prefixed lane)
 #pragma unroll
         for (int k = 0; k < 17; k++) {
             int32_t idx = wi_ + k;

@@ -452,6 +452,30 @@ void hosttest_sha3_256_prefixed(const uint8_t* prefix, size_t plen, const uint8_
     const uint32_t base = (uint32_t)(plen / SHA3_256_RATE) * SHA3_256_RATE;
     sha3_256_host_stream(buf.data(), buf.size(), mid, (uint32_t)(3 + len + 5) + base, (uint32_t)plen - base, 3, (uint32_t)len, out32);
 }
+// An arena of 2^32 - 4 bytes that takes no memory: byte p is a fixed function of its position (the top byte of p times a 64-bit odd
+// constant; tests/test_sha3_host.py restates it), and a dword index is clamped to [0, last] as the device's Sha3DevArena clamps it.
+struct Sha3SyntheticArena {
+    static constexpr int32_t last = (int32_t)((0xFFFFFFFCull >> 2) - 1);
+    static uint8_t byte_at(uint64_t p) { return (uint8_t)((p * 0x9E3779B97F4A7C15ull) >> 56); }
+    uint32_t word(int32_t i) const {
+        i = i < last ? i : last;
+        i = i > 0 ? i : 0;
+        uint32_t v = 0;
+        for (int k = 0; k < 4; k++) v |= (uint32_t)byte_at((uint64_t)i * 4 + (uint64_t)k) << (8 * k);
+        return v;
+    }
+};
+// SHA3-256 of  arena[pre_start, pre_start + pre_len) || arena[start, start + len)  over that arena, the way the kernels take it: the
+// prefix's whole blocks by sha3_256_midstate, its leftover bytes and the message by sha3_256_stream.  Any offset up to 2^32 - 1.
+void hosttest_sha3_256_at(uint32_t start, uint32_t len, uint32_t pre_start, uint32_t pre_len, uint8_t* out32) {
+    Sha3SyntheticArena ar;
+    uint32_t a[SHA3_STATE_WORDS];
+    sha3_zero(a);
+    const uint32_t nfull = pre_len / SHA3_256_RATE, base = nfull * SHA3_256_RATE, la = pre_len - base;
+    sha3_256_midstate<Sha3SyntheticArena, false>(ar, a, pre_start, nfull, nfull);
+    sha3_256_stream<Sha3SyntheticArena, false>(ar, a, pre_start + base, la, start, len, true, pre_len != 0, sha3_256_blocks(la + len));
+    sha3_words_to_bytes(a, 8, out32);
+}
 // the block pass's per-transaction summary (block_prepass.h SummarizeTransactions); hashes_done == 0: no TxID / proposal hash was computed
 void hosttest_summarize_transactions(uint32_t n_tx, const uint8_t* tx_understood, size_t n_tuples, const uint32_t* tuple_tx, const uint8_t* tuple_kind,
                                      const uint8_t* tuple_status, int hashes_done, const uint8_t* bad_txid, const uint8_t* bad_phash, uint8_t* tx_flags) {

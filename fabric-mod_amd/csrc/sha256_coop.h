@@ -74,8 +74,10 @@ __device__ __forceinline__ void sha256_coop_ex(const uint32_t* __restrict__ firs
     auto chunk_fetch = [&](uint32_t c0, uint32_t (&raw)[17]) {
         const uint32_t pos = (c0 + sub) << 6;
         const bool in_first = pos + 64 <= pl;
-        const int32_t vstart = in_first ? (int32_t)ps : (int32_t)sb - (int32_t)pl;
-        fetch(in_first, (vstart + (int32_t)pos) >> 2, raw);
+        // arena address of message byte 0 under the block's span, in 64 bits: ps and sb go up to 2^32 - 1, and sb - pl is negative
+        // where the second span starts early (the dword index itself is 2^30 at the most, or a few dwords below zero)
+        const int64_t vstart = in_first ? (int64_t)ps : (int64_t)sb - (int64_t)pl;
+        fetch(in_first, (int32_t)((vstart + (int64_t)pos) >> 2), raw);
     };
     auto rounds = [&](const uint4 (&wk4)[16], uint32_t m) {
         uint32_t a = h[0], bb = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
@@ -102,8 +104,7 @@ __device__ __forceinline__ void sha256_coop_ex(const uint32_t* __restrict__ firs
             // ---- phase 1: this lane's block of the chunk -> W[t] + K[t], t = 0 .. 63 ----
             const uint32_t pos = (c0 + sub) << 6;                          // the block's byte position in the message
             const bool in_first = pos + 64 <= pl;                          // wholly inside the first span
-            const int32_t vstart = in_first ? (int32_t)ps : (int32_t)sb - (int32_t)pl;   // arena address of message byte 0 under the block's span
-            const uint32_t shift = (uint32_t)vstart & 3u;
+            const uint32_t shift = (in_first ? ps : sb - pl) & 3u;         // byte phase of message byte 0 under the block's span (chunk_fetch)
             uint32_t w[16], raw[17];
 #pragma unroll
             for (int k = 0; k < 17; k++) raw[k] = raw_next[k];             // fetched while the previous chunk's rounds ran

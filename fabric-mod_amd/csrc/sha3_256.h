@@ -146,10 +146,11 @@ FAB_HD void sha3_256_absorb(uint32_t (&a)[SHA3_STATE_WORDS], const uint32_t (&w)
 FAB_HD uint32_t sha3_256_blocks(uint32_t len) { return len / SHA3_256_RATE + 1; }
 
 // Words of an arena: Arena::word(i) is dword i of the allocation, i clamped to what may be read.
-// Raw dwords of rate block blk of a stream whose byte 0 sits at arena byte vstart (possibly negative: see sha3_256_stream).
+// Raw dwords of rate block blk of a stream whose byte 0 sits in arena dword w0 (possibly negative: see sha3_256_stream).  Dword
+// indices, never signed byte addresses: an arena byte offset goes up to 2^32 - 1, its dword index to 2^30.
 template <class Arena>
-FAB_HD void sha3_fetch(const Arena& ar, int32_t vstart, uint32_t blk, uint32_t (&dst)[SHA3_256_RATE_WORDS + 1]) {
-    const int32_t wi = (vstart + (int32_t)(blk * SHA3_256_RATE)) >> 2;   // first aligned dword (negative in block 0 of a prefixed lane whose own bytes start early)
+FAB_HD void sha3_fetch(const Arena& ar, int32_t w0, uint32_t blk, uint32_t (&dst)[SHA3_256_RATE_WORDS + 1]) {
+    const int32_t wi = (int32_t)((uint32_t)w0 + blk * (uint32_t)SHA3_256_RATE_WORDS);   // first aligned dword (negative in block 0 of a prefixed lane whose own bytes start early)
 #pragma unroll
     for (int k = 0; k < SHA3_256_RATE_WORDS + 1; k++) dst[k] = ar.word(wi + k);
 }
@@ -166,24 +167,25 @@ FAB_HD void sha3_256_stream(const Arena& ar, uint32_t (&a)[SHA3_STATE_WORDS], ui
                             bool any_prefix, uint32_t maxblk) {
     const uint32_t len = la + lb;
     const uint32_t nblk = active ? sha3_256_blocks(len) : 0;
-    const int32_t vstart = (int32_t)sb - (int32_t)la;   // B's bytes sit at stream position la
-    const uint32_t shift = (uint32_t)vstart & 3u;
+    // B's bytes sit at stream position la: the B stream starts at arena byte sb - la, whose dword is floor((sb - la) / 4)
+    const uint32_t shift = (sb - la) & 3u;
+    const int32_t w0 = (int32_t)(sb >> 2) + (((int32_t)(sb & 3u) - (int32_t)la) >> 2);
     uint32_t nxt[SHA3_256_RATE_WORDS + 1];
-    if (PREFETCH && maxblk) sha3_fetch(ar, vstart, 0, nxt);
+    if (PREFETCH && maxblk) sha3_fetch(ar, w0, 0, nxt);
     for (uint32_t blk = 0; blk < maxblk; blk++) {
         uint32_t raw[SHA3_256_RATE_WORDS + 1], w[SHA3_256_RATE_WORDS];
         if (PREFETCH) {
 #pragma unroll
             for (int k = 0; k < SHA3_256_RATE_WORDS + 1; k++) raw[k] = nxt[k];
-            if (blk + 1 < maxblk) sha3_fetch(ar, vstart, blk + 1, nxt);
+            if (blk + 1 < maxblk) sha3_fetch(ar, w0, blk + 1, nxt);
         } else {
-            sha3_fetch(ar, vstart, blk, raw);
+            sha3_fetch(ar, w0, blk, raw);
         }
 #pragma unroll
         for (int k = 0; k < SHA3_256_RATE_WORDS; k++) w[k] = k_bytes(raw[k + 1], raw[k], shift);
         if (any_prefix && blk == 0) {                    // uniform: the prefix tail A takes the first la bytes of the first block
             uint32_t rawA[SHA3_256_RATE_WORDS + 1];
-            sha3_fetch(ar, (int32_t)sa, 0, rawA);
+            sha3_fetch(ar, (int32_t)(sa >> 2), 0, rawA);
 #pragma unroll
             for (int k = 0; k < SHA3_256_RATE_WORDS; k++) {
                 const uint32_t keepA = k_low_bytes((int32_t)la - 4 * k);
@@ -208,15 +210,15 @@ template <class Arena, bool PREFETCH>
 FAB_HD void sha3_256_midstate(const Arena& ar, uint32_t (&a)[SHA3_STATE_WORDS], uint32_t start, uint32_t nfull, uint32_t maxfull) {
     const uint32_t shift = start & 3u;
     uint32_t nxt[SHA3_256_RATE_WORDS + 1];
-    if (PREFETCH && maxfull) sha3_fetch(ar, (int32_t)start, 0, nxt);
+    if (PREFETCH && maxfull) sha3_fetch(ar, (int32_t)(start >> 2), 0, nxt);
     for (uint32_t blk = 0; blk < maxfull; blk++) {
         uint32_t raw[SHA3_256_RATE_WORDS + 1], w[SHA3_256_RATE_WORDS];
         if (PREFETCH) {
 #pragma unroll
             for (int k = 0; k < SHA3_256_RATE_WORDS + 1; k++) raw[k] = nxt[k];
-            if (blk + 1 < maxfull) sha3_fetch(ar, (int32_t)start, blk + 1, nxt);
+            if (blk + 1 < maxfull) sha3_fetch(ar, (int32_t)(start >> 2), blk + 1, nxt);
         } else {
-            sha3_fetch(ar, (int32_t)start, blk, raw);
+            sha3_fetch(ar, (int32_t)(start >> 2), blk, raw);
         }
 #pragma unroll
         for (int k = 0; k < SHA3_256_RATE_WORDS; k++) w[k] = k_bytes(raw[k + 1], raw[k], shift);

@@ -119,7 +119,13 @@ int fabgpu_sha256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* ar
 
 /* Device-resident variants: all pointers are HIP device pointers (16-byte aligned), `stream` is a
  * hipStream_t (NULL = the null stream).  Asynchronous; the caller synchronises the stream.
- * arena_bytes = readable size of the arena allocation. */
+ * arena_bytes = readable size of the arena allocation.
+ * ADDRESS WIDTH.  A byte offset into an arena is a u32, so an arena may hold up to 2^32 - 1 bytes; a larger arena_bytes is refused
+ * with FABGPU_ETOOBIG.  The rule for every entry point that takes an arena (SHA-256, SHA3-256, the fused and keyed forms,
+ * fabgpu_identity_verify_batch_dev with its prefixes and gathered pieces, fabgpu_idemix_nym_verify_batch_dev): it hashes the bytes
+ * the offsets name, wherever they lie in an arena of a size it accepts, or it refuses the arena - it never answers from other
+ * bytes.  All of them accept the full 2^32 - 1.  One limit remains inside it: a single message (prefix included) must be shorter
+ * than 2^31 bytes; the kernels count the bytes left in a message in 31 bits and a longer one is not hashed correctly. */
 int fabgpu_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* qx, const void* qy, const void* e, const void* r,
                                  const void* s, void* verdict_bits, void* status, void* stream);
 int fabgpu_sha256_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,

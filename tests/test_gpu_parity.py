@@ -256,6 +256,7 @@ def test_arena_size_boundaries_of_the_32_bit_offsets(ctx):
     assert L.fabgpu_p256_verify_batch(ctx.handle, (0x7FFFFFF0 // 160) + 1, z.ctypes.data_as(u8), z.ctypes.data_as(u8), z.ctypes.data_as(u8), z.ctypes.data_as(u8),
                                       z.ctypes.data_as(u8), words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), None) == -5
     # a large but legal arena: 1.2 GB of messages in one launch (2 000 messages of 600 000 bytes: 9 375 blocks per lane)
+    # (offsets of 2^31 and more, up to an arena of 2^32 - 3 bytes: tests/test_hash_edges_gpu.py)
     m, ml = 2000, 600000
     big = np.random.default_rng(9).integers(0, 256, size=m * ml, dtype=np.uint8)
     boff = (np.arange(m + 1, dtype=np.uint64) * ml).astype(np.uint32)
@@ -263,6 +264,16 @@ def test_arena_size_boundaries_of_the_32_bit_offsets(ctx):
     import hashlib
     for i in (0, 1, 777, m - 1):
         assert d[i].tobytes() == hashlib.sha256(big[i * ml:(i + 1) * ml].tobytes()).digest()
+    # every arena size an entry point accepts it also hashes correctly (tests/test_hash_edges_gpu.py runs them at 2^32 - 3 bytes): all
+    # the message-taking device entry points draw the line at the same place, 2^32 - 1 accepted (n = 0: nothing is read), 2^32 refused
+    top = (1 << 32) - 1
+    for fn, tail in ((L.fabgpu_sha256_batch_dev, (1 << 20, None)), (L.fabgpu_sha3_256_batch_dev, (1 << 20, None)),
+                     (L.fabgpu_sha256_p256_verify_batch_dev, (1 << 20, 1 << 20, 1 << 20, 1 << 20, 1 << 20, None, None)),
+                     (L.fabgpu_sha3_256_p256_verify_batch_dev, (1 << 20, 1 << 20, 1 << 20, 1 << 20, 1 << 20, None, None)),
+                     (L.fabgpu_sha256_p256_verify_batch_keyed_dev, (1 << 20, 1 << 20, 1 << 20, 1 << 20, None, None)),
+                     (L.fabgpu_sha3_256_p256_verify_batch_keyed_dev, (1 << 20, 1 << 20, 1 << 20, 1 << 20, None, None))):
+        assert fn(ctx.handle, n, 1 << 20, top + 1, 1 << 20, *tail) == -5
+        assert fn(ctx.handle, 0, 1 << 20, top, 1 << 20, *tail) == 0
 
 
 # ---- registered public keys (bccsp.KeyImport -> per-key comb table) --------------------------------------

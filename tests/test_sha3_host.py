@@ -24,6 +24,8 @@ def hosttest():
     lib.hosttest_sha3_256_prefixed.restype = None
     lib.hosttest_sha3_256_midstate.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
     lib.hosttest_sha3_256_midstate.restype = None
+    lib.hosttest_sha3_256_at.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p]
+    lib.hosttest_sha3_256_at.restype = None
     return lib
 
 
@@ -116,3 +118,43 @@ def test_exported_midstate_is_the_plain_absorb_of_the_whole_blocks(hosttest, ple
     out = ctypes.create_string_buffer(200)
     hosttest.hosttest_sha3_256_midstate(prefix, plen, out)
     assert out.raw == _plain_absorb(prefix[:plen // RATE * RATE])
+
+
+# ---- arena offsets up to 2^32 - 1: the stream code over an arena of 2^32 - 4 bytes that exists only as a function of the position ----
+ARENA_BYTES = (1 << 32) - 4
+HIGH_STARTS = (0, (1 << 31) - 300, (1 << 31) - 1, 1 << 31, (1 << 31) + 1, (1 << 31) + 2, (1 << 31) + 3, 3 * (1 << 30) + 1, ARENA_BYTES - 500)
+HIGH_LENS = (0, 1, 135, 136, 137, 300, 409)
+HIGH_PREFIX_LENS = (135, 136, 272)
+
+
+def _arena_bytes(start: int, n: int) -> bytes:
+    """hosttest.cpp Sha3SyntheticArena::byte_at: the top byte of position * 0x9E3779B97F4A7C15 mod 2^64"""
+    p = np.arange(start, start + n, dtype=np.uint64)
+    return ((p * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(56)).astype(np.uint8).tobytes()
+
+
+def _sha3_at(lib, start, n, pre_start=0, pre_len=0) -> bytes:
+    out = ctypes.create_string_buffer(32)
+    lib.hosttest_sha3_256_at(start, n, pre_start, pre_len, out)
+    return out.raw
+
+
+def test_offsets_on_both_sides_of_2_to_the_31_and_at_the_arenas_end(hosttest):
+    """A byte offset is a u32 and goes up to the arena's size, 2^32 - 1 at the most: messages that start below, at, above and across
+    2^31, at every byte phase, and in the arena's last bytes (one ending on its last byte: the 35th dword of the last block is the
+    clamped one); then each behind a prefix that lies on the other side of 2^31, and behind one that crosses it."""
+    starts = HIGH_STARTS + tuple(ARENA_BYTES - n for n in HIGH_LENS if n)      # ... and ending on the arena's last byte
+    bad = []
+    for start in starts:
+        for n in HIGH_LENS:
+            if start + n > ARENA_BYTES:
+                continue
+            msg = _arena_bytes(start, n)
+            if _sha3_at(hosttest, start, n) != hashlib.sha3_256(msg).digest():
+                bad.append((start, n))
+            other_side = (1 << 31) + 4097 if start < (1 << 31) else 4099         # byte phases 1 and 3
+            for ps in (other_side, (1 << 31) - 101):
+                for pl in HIGH_PREFIX_LENS:
+                    if _sha3_at(hosttest, start, n, ps, pl) != hashlib.sha3_256(_arena_bytes(ps, pl) + msg).digest():
+                        bad.append((start, n, ps, pl))
+    assert not bad, "(start, length[, prefix start, prefix length]) that disagree with hashlib.sha3_256: %s" % [tuple(hex(x) for x in b) for b in bad]
