@@ -19,6 +19,7 @@
 #include "worker_pool.h"
 #include "idemix_host.h"
 #include "block_walk_dev.h"
+#include "walk_layout.h"
 #include "pass_route.h"
 
 #include <limits.h>
@@ -519,8 +520,7 @@ size_t GPUCSP::MemoPinLayout(uint32_t n_tuples, uint32_t n_creators, uint32_t* s
     // a slot table of at least twice the tuples, offsets, statuses, digests, and keys of 109 (141 for a pseudonym signature) +
     // signature bytes each - 96 bytes of signature on average are allowed for (an ECDSA signature has <= 72; a block whose keys do
     // not fit gets more room at the end of the pass: WalkRequest::memo_grow)
-    uint32_t cap = 16;
-    while (cap < 2 * (uint64_t)n_tuples && cap < (1u << 30)) cap <<= 1;
+    const uint32_t cap = walk_memo_slot_cap(n_tuples);              // (walk_layout.h: the pass's worst case is sized with the same table)
     const size_t kc = (size_t)n_tuples * (109 + 96) + (size_t)n_creators * 32 + 256;
     auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t a_slots = 0, a_off = up256((size_t)cap * 4), a_st = a_off + up256(((size_t)n_tuples + 1) * 4), a_dig = a_st + up256(n_tuples),

@@ -335,6 +335,8 @@ int key_table_copy(fabgpu_ctx* ctx, uint32_t key_id, int32_t* out);   // TEST HO
 int key_register_many_prebuilt(fabgpu_ctx* const* ctxs, int n, const uint8_t* qx32, const uint8_t* qy32, const int32_t* table, uint32_t* key_ids);
 // the duration of the last timed launch of a FABGPU_FLAG_TIME_KERNELS context (ms; < 0: none) - read by the test-hook library
 float ctx_last_kernel_ms(fabgpu_ctx* ctx);
+// TEST HOOK support: the capacities of the block pass's per-envelope, per-tuple, pinned, mapped and gather-scratch buffers (bytes)
+void walk_buffer_caps(fabgpu_ctx* ctx, uint64_t out[5]);
 // TEST HOOK: the idemix four-lane form orders its side launch BEHIND the commitment launch while this is on
 void ctx_test_nym_side_after(fabgpu_ctx* ctx, bool on);
 // pinned host memory for WalkOut::memo_* (hipHostMalloc / hipHostFree; nullptr when there is none to be had)

@@ -24,6 +24,7 @@
 #include "kernels.h"
 #include "key_slots.h"
 #include "block_walk_dev.h"
+#include "walk_layout.h"
 #include "worker_pool.h"
 #include "bn_tables29.h"
 #include "p256_tables29.h"
@@ -252,8 +253,7 @@ struct fabgpu_ctx {
     bool pred_has_nym = false;       // the previous block had idemix creators: queue the nym launch without waiting for the gates
     uint32_t pred_nym_rows = 0;      // ... and how many: the launch runs over that many packed rows plus a margin
     Buf gath;         // gathered hashes of an identity batch: spans | running offsets | digests
-    void* d_gscr = nullptr;   // device scratch the gather kernel stitches the messages into
-    size_t gscr_cap = 0;
+    DevBuf gscr;      // device scratch the gather kernel stitches the messages into
     // fabgpu_arena_stage: arenas uploaded ahead of the batches that refer to them.  A few slots, so that the channels of a peer
     // validating at once do not throw each other's block out between "staged" and "submitted" (with one slot, two callers cost
     // more per block than one: the loser uploaded its 50 MB a second time inside its device call).  A slot's mutex is held while
@@ -585,7 +585,7 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
         ctx->tailbuf.release();
         ctx->keyed.release();
         ctx->pre.release();
-        if (ctx->d_gscr) hipFree(ctx->d_gscr);
+        ctx->gscr.release();
         ctx->walk_env.release();
         ctx->walk_tup.release();
         ctx->walk_pin.release();
@@ -620,6 +620,13 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
 }  // extern "C"
 void fab::ctx_test_nym_side_after(fabgpu_ctx* ctx, bool on) {
     if (ctx) ctx->test_nym_side_after.store(on);
+}
+// TEST HOOK support: the capacities of the block pass's buffers - per-envelope, per-tuple, pinned, mapped, gather scratch
+void fab::walk_buffer_caps(fabgpu_ctx* ctx, uint64_t out[5]) {
+    for (int k = 0; k < 5; k++) out[k] = 0;
+    if (!ctx) return;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    out[0] = ctx->walk_env.cap; out[1] = ctx->walk_tup.cap; out[2] = ctx->walk_pin.cap; out[3] = ctx->walk_map.cap; out[4] = ctx->gscr.cap;
 }
 // what the test-hook library's fabgpu_last_kernel_ms reads (FABGPU_FLAG_TIME_KERNELS contexts; block_walk_dev.h)
 float fab::ctx_last_kernel_ms(fabgpu_ctx* ctx) {
@@ -2211,13 +2218,7 @@ int fabgpu_identity_verify_batch(fabgpu_ctx* ctx, const fabgpu_identity_batch* b
     const size_t gsb = round_up((size_t)ng * 24, 64), gob = round_up(((size_t)ng + 1) * 4, 64), gscr = round_up((size_t)gtotal, 4) + 64;
     if (ng) {
         if ((rc = ctx->gath.ensure(gsb + gob + (size_t)ng * 32))) return rc;
-        if (ctx->gscr_cap < gscr) {
-            if (ctx->d_gscr) hipFree(ctx->d_gscr);
-            ctx->d_gscr = nullptr;
-            ctx->gscr_cap = 0;
-            if (hipMalloc(&ctx->d_gscr, gscr + gscr / 4) != hipSuccess) return FABGPU_ENOMEM;
-            ctx->gscr_cap = gscr + gscr / 4;
-        }
+        if ((rc = ctx->gscr.ensure(gscr))) return rc;
         uint32_t* gs = (uint32_t*)ctx->gath.h;
         uint32_t* go = (uint32_t*)((uint8_t*)ctx->gath.h + gsb);
         uint32_t run = 0;
@@ -2236,7 +2237,7 @@ int fabgpu_identity_verify_batch(fabgpu_ctx* ctx, const fabgpu_identity_batch* b
         d.gather_spans = (const uint32_t*)ctx->gath.d;
         d.gather_off = (const uint32_t*)((uint8_t*)ctx->gath.d + gsb);
         d.gather_digests = (uint8_t*)ctx->gath.d + gsb + gob;
-        d.gather_scratch = ctx->d_gscr;
+        d.gather_scratch = ctx->gscr.d;
         d.gather_scratch_bytes = gscr;
     }
     // the pseudonym signatures: staged and launched on the second stream BEFORE the ECDSA kernels are queued, so that the two run
@@ -2425,6 +2426,81 @@ int wait_host_flag(const uint32_t* flag, uint32_t seq, hipStream_t st) {
 }
 }  // namespace
 
+// The pointers of a pass into its buffers, at the places walk_layout.h names: the per-envelope arrays (de = fabgpu_ctx::walk_env) ...
+static void bind_env_arrays(WalkArrays& a, uint8_t* de, const WalkEnvLayout& E, uint32_t ne, bool host_counted) {
+    a.env_spans = (const uint32_t*)(de + E.env.off);
+    a.n_env = ne;
+    a.counts = (uint4*)(de + E.cnt.off);
+    a.stash = host_counted ? nullptr : (bccsp::walk::EnvStash*)(de + E.stash.off);
+    a.bases = (uint4*)(de + E.base.off);
+    a.cbase = (uint32_t*)(de + E.cbase.off);
+    a.totals = (WalkTotals*)(de + E.tot.off);
+    a.tx_type = de + E.type.off;
+    a.tx_understood = de + E.und.off;
+    a.tx_mask = (uint32_t*)(de + E.mask.off);
+    a.tx_flags = de + E.flags.off;
+    a.summary = (WalkSummary*)(de + E.sum.off);
+    a.learn = (WalkLearn*)(de + E.learn.off);
+}
+// ... the per-tuple arrays (dt = fabgpu_ctx::walk_tup); the optional ones stay null unless the pass has them ...
+static void bind_tuple_arrays(WalkArrays& a, uint8_t* dt, const WalkTupleLayout& T, bool nym_rows, bool memo, bool hmemo, bool row_digests, bool tuple_qxy) {
+    a.tuples = (bccsp::BlockTuple*)(dt + T.tup.off);
+    a.pre_off2 = (uint32_t*)(dt + T.pre.off);
+    a.checks = (bccsp::BlockHashCheck*)(dt + T.chk.off);
+    a.gather_spans = (uint32_t*)(dt + T.gsp.off);
+    a.gather_off = (uint32_t*)(dt + T.gof.off);
+    a.gather_digests = dt + T.gdg.off;
+    a.id_idx = (uint32_t*)(dt + T.idx.off);
+    a.off2 = (uint32_t*)(dt + T.off.off);
+    a.pre_idx = (uint32_t*)(dt + T.pix.off);
+    a.key_id = (uint32_t*)(dt + T.kid.off);
+    a.qx = dt + T.qx.off; a.qy = dt + T.qy.off; a.r = dt + T.r.off; a.s = dt + T.s.off;
+    a.gate_st = dt + T.gst.off;
+    a.tflags = dt + T.tfl.off;
+    if (nym_rows) {
+        a.nym_fields = dt + T.nymf.off;
+        a.nym_issuer = (uint32_t*)(dt + T.nymi.off);
+        a.nym_issuer_out = (int32_t*)(dt + T.nymio.off);
+        a.nym_spans = (uint32_t*)(dt + T.nymsp.off);
+    }
+    a.row_of = (uint32_t*)(dt + T.row.off);
+    a.creator_spans = (uint32_t*)(dt + T.cspan.off);
+    a.verdict_bits = (const uint64_t*)(dt + T.bits.off);
+    a.verdict_bits_c = (const uint64_t*)(dt + T.bitc.off);
+    a.row_digests = row_digests ? dt + T.dig.off : nullptr;
+    a.tuple_digests = dt + T.tdig.off;
+    a.tuple_qxy = tuple_qxy ? dt + T.tqxy.off : nullptr;
+    a.summary_parts = (uint32_t*)(dt + T.sparts.off);
+    if (memo) {
+        a.memo_ent = (uint32_t*)(dt + T.ment.off);
+        a.memo_slots = (uint32_t*)(dt + T.mslots.off);
+        a.memo_key_off = (uint32_t*)(dt + T.mkoff.off);
+        a.memo_keys = dt + T.mkeys.off;
+        a.memo_status = dt + T.mst.off;
+        a.memo_totals = (WalkMemoTotals*)(dt + T.mtot.off);
+        a.memo_digests = dt + T.mdig.off;
+        a.memo_tiles = dt + T.mtiles.off;
+        if (hmemo) {
+            a.memo_hspans = (uint32_t*)(dt + T.mhsp.off);
+            a.memo_hslots = (uint32_t*)(dt + T.mhsl.off);
+        }
+    }
+    a.dev_status = dt + T.dst.off;
+    a.tuple_status = dt + T.tst.off;
+    a.tuple_hashed = dt + T.hsh.off;
+}
+// ... and where the last kernel writes what the host waits for (m8 = the device's view of fabgpu_ctx::walk_map)
+static void bind_host_out(WalkHostOut& ho, uint8_t* m8, const WalkMapLayout& M, uint32_t* done, bool memo) {
+    ho.flag = (uint32_t*)(m8 + WALK_MAP_FINFLAG);
+    ho.done = done;
+    ho.summary = (WalkSummary*)(m8 + WALK_MAP_SUM);
+    ho.memo_totals = memo ? (WalkMemoTotals*)(m8 + WALK_MAP_MTOT) : nullptr;
+    ho.learn = (WalkLearn*)(m8 + M.learn.off);
+    ho.tx_flags = m8 + M.flags.off; ho.tx_type = m8 + M.type.off; ho.tx_understood = m8 + M.und.off;
+    ho.tuple_status = m8 + M.tst.off; ho.tuple_hashed = m8 + M.hsh.off;
+    ho.id_idx = (uint32_t*)(m8 + M.idx.off);
+}
+
 int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
     if (!ctx || !rq.sizes || !rq.env_spans || rq.stage_token == 0) return FABGPU_EINVAL;
     if (rq.n_block_sigs && !rq.block_sigs) return FABGPU_EINVAL;
@@ -2457,9 +2533,7 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         if (walk_trace) fprintf(stderr, "fabgpu walk %p %-28s %8.3f ms\n", (void*)&rq, what, ms_since(t_start));
     };
     const uint32_t ne = rq.n_env;
-    // ---- per-envelope arrays ----
-    size_t o = 0;
-    auto carve = [&](size_t bytes) { size_t at = o; o = round_up(o + bytes, 256); return at; };
+    // ---- per-envelope arrays (walk_layout.h) ----
     // (what the host sends up sits together - envelope spans, payload spans, idemix MSPs and, when the host counted, the count kernel's
     //  and the scan's arrays - mirrored at the same offsets in the pinned staging buffer: ONE copy)
     const bool host_counted = rq.host_counts && rq.host_tx_type && rq.host_tx_understood;
@@ -2468,22 +2542,16 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
     // block of a few hundred transactions THE critical path (300 tx: the chain is 240 us of a 600 us device phase).  With the host's
     // outline of where they are they start before anything is walked, beside the walk's two runs and the gates.
     const bool early_hash = rq.payload_spans && !rq.walk_only && ctx->allow_pair && (uint64_t)ne * 2 <= 65536u;
-    const size_t o_env = carve((size_t)ne * 8), o_pay = carve(early_hash ? (size_t)ne * 8 : 0), o_msps = carve(sizeof(DevIdemixMsp) * n_msps),
-                 o_ihash = carve(rq.idemix_issuer_hashes ? (size_t)32 * n_msps : 0),
-                 o_up_small = o,                                                // ... the copy ends here unless the host counted
-                 o_cnt = carve((size_t)ne * 16), o_base = carve((size_t)ne * 16), o_cbase = carve((size_t)ne * 4), o_type = carve(ne), o_und = carve(ne),
-                 o_up_all = o,
-                 o_tot = carve(sizeof(WalkTotals)), o_mask = carve((size_t)ne * 4), o_flags = carve(ne), o_sum = carve(sizeof(WalkSummary)),
-                 o_learn = carve(sizeof(WalkLearn) * WALK_LEARN_SLOTS), o_done = carve(64), o_denv = carve(early_hash ? (size_t)ne * 32 : 0),
-                 o_stash = carve(host_counted ? 0 : (size_t)ne * sizeof(bccsp::walk::EnvStash));   // what the count kernel keeps for the emit kernel
+    WalkEnvShape es;
+    es.ne = ne; es.n_msps = n_msps; es.early_hash = early_hash; es.host_counted = host_counted; es.has_issuer_hashes = rq.idemix_issuer_hashes != nullptr;
+    const WalkEnvLayout E = walk_env_layout(es);
     int rc;
-    if ((rc = ctx->walk_env.ensure(o))) return rc;
+    if ((rc = ctx->walk_env.ensure(E.total))) return rc;
     // pinned staging: the region above as it goes up (the result arrays are sized further down)
-    const size_t up_bytes = host_counted ? o_up_all : o_up_small, p_first = round_up(o_up_all, 256);
-    if ((rc = ctx->walk_pin.ensure(p_first))) return rc;
-    // host-mapped results: [0, 64) the totals' flag, [64, 128) the totals, [128, 192) the final flag, [192, 256) the summary; the arrays follow
-    constexpr size_t m_totflag = 0, m_tot = 64, m_finflag = 128, m_sum = 192, m_mtot = 256, m_arrays = 320;   // (the summary is 48 bytes, the memo's totals 24)
-    if ((rc = ctx->walk_map.ensure(m_arrays + sizeof(WalkLearn) * WALK_LEARN_SLOTS + 3 * round_up(ne, 64) + ((size_t)8 << 10)))) return rc;
+    const size_t up_bytes = host_counted ? E.up_all : E.up_small;
+    if ((rc = ctx->walk_pin.ensure(walk_pin_first(E)))) return rc;
+    // host-mapped results: the fixed cells (WALK_MAP_*), the arrays follow
+    if ((rc = ctx->walk_map.ensure(walk_map_early_bytes(ne)))) return rc;
     if (++ctx->walk_seq == 0) ++ctx->walk_seq;
     const uint32_t seq_tot = ctx->walk_seq;
     uint8_t* de = (uint8_t*)ctx->walk_env.d;
@@ -2491,32 +2559,20 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
     a.block = (const uint8_t*)sl->d;
     a.block_len = (uint32_t)sl->len;
     a.arena_len = has_tail ? rq.tail_base + rq.tail_len : (uint32_t)sl->len;
-    a.env_spans = (const uint32_t*)(de + o_env);
-    a.n_env = ne;
-    a.counts = (uint4*)(de + o_cnt);
-    a.stash = host_counted ? nullptr : (bccsp::walk::EnvStash*)(de + o_stash);
-    a.bases = (uint4*)(de + o_base);
-    a.cbase = (uint32_t*)(de + o_cbase);
-    a.totals = (WalkTotals*)(de + o_tot);
-    a.tx_type = de + o_type;
-    a.tx_understood = de + o_und;
-    a.tx_mask = (uint32_t*)(de + o_mask);
-    a.tx_flags = de + o_flags;
-    a.summary = (WalkSummary*)(de + o_sum);
-    a.learn = (WalkLearn*)(de + o_learn);
+    bind_env_arrays(a, de, E, ne, host_counted);
     uint8_t* up = (uint8_t*)ctx->walk_pin.h;
-    memcpy(up + o_env, rq.env_spans, (size_t)ne * 8);
-    if (early_hash) memcpy(up + o_pay, rq.payload_spans, (size_t)ne * 8);
-    if (n_msps) memcpy(up + o_msps, rq.idemix_msps, sizeof(DevIdemixMsp) * n_msps);
-    if (n_msps && rq.idemix_issuer_hashes) memcpy(up + o_ihash, rq.idemix_issuer_hashes, (size_t)32 * n_msps);
+    memcpy(up + E.env.off, rq.env_spans, E.env.bytes);
+    if (early_hash) memcpy(up + E.pay.off, rq.payload_spans, E.pay.bytes);
+    if (n_msps) memcpy(up + E.msps.off, rq.idemix_msps, E.msps.bytes);
+    if (n_msps && rq.idemix_issuer_hashes) memcpy(up + E.ihash.off, rq.idemix_issuer_hashes, E.ihash.bytes);
     WalkTotals host_tot = {};
     if (host_counted) {
         // the scan, here: exclusive prefix sums per envelope (walk_scan_kernel's outputs), and the totals the host would otherwise wait for
-        memcpy(up + o_cnt, rq.host_counts, (size_t)ne * 16);
-        memcpy(up + o_type, rq.host_tx_type, ne);
-        memcpy(up + o_und, rq.host_tx_understood, ne);
-        uint32_t* bases = (uint32_t*)(up + o_base);
-        uint32_t* cb = (uint32_t*)(up + o_cbase);
+        memcpy(up + E.cnt.off, rq.host_counts, E.cnt.bytes);
+        memcpy(up + E.type.off, rq.host_tx_type, E.type.bytes);
+        memcpy(up + E.und.off, rq.host_tx_understood, E.und.bytes);
+        uint32_t* bases = (uint32_t*)(up + E.base.off);
+        uint32_t* cb = (uint32_t*)(up + E.cbase.off);
         uint64_t bt = 0, bp = 0, bc = 0, bg = 0;
         uint32_t bk = 0;
         for (uint32_t e = 0; e < ne; e++) {
@@ -2530,7 +2586,7 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         host_tot.tuples = (uint32_t)bt; host_tot.prefixes = (uint32_t)bp; host_tot.checks = (uint32_t)bc; host_tot.creators = bk;
         host_tot.gather_bytes = bg;
     }
-    hipError_t err = hipMemcpyAsync(de + o_env, up + o_env, up_bytes, hipMemcpyHostToDevice, st);
+    hipError_t err = hipMemcpyAsync(de + E.env.off, up + E.env.off, up_bytes, hipMemcpyHostToDevice, st);
     bool s2_busy = false;
     struct Drain2 {                                                         // (an early exit must not leave the hashes running)
         hipStream_t s;
@@ -2539,8 +2595,8 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         ~Drain2() { if (armed && *busy) hipStreamSynchronize(s); }
     } drain2{ctx->stream2, &s2_busy};
     if (err == hipSuccess && early_hash) {
-        a.payload_spans = (const uint32_t*)(de + o_pay);
-        a.digest_env = de + o_denv;
+        a.payload_spans = (const uint32_t*)(de + E.pay.off);
+        a.digest_env = de + E.denv.off;
         err = hipEventRecord(ctx->ev_w[3], st);                            // "the span lists are on the device"
         if (err == hipSuccess) err = hipStreamWaitEvent(ctx->stream2, ctx->ev_w[3], 0);
         if (err == hipSuccess) {
@@ -2558,21 +2614,21 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         err = hipMemcpyAsync((uint8_t*)sl->d + rq.tail_base, ctx->tailbuf.h, rq.tail_len, hipMemcpyHostToDevice, st);
         if (err == hipSuccess) err = hipMemsetAsync((uint8_t*)sl->d + rq.tail_base + rq.tail_len, 0, 128, st);
     }
-    if (err == hipSuccess) err = hipMemsetAsync(de + o_mask, 0, (size_t)ne * 4, st);
-    if (err == hipSuccess) err = hipMemsetAsync(de + o_sum, 0, sizeof(WalkSummary), st);
-    if (err == hipSuccess) err = hipMemsetAsync(de + o_learn, 0, sizeof(WalkLearn) * WALK_LEARN_SLOTS, st);
-    if (err == hipSuccess) err = hipMemsetAsync(de + o_done, 0, 64, st);
+    if (err == hipSuccess) err = hipMemsetAsync(de + E.mask.off, 0, E.mask.bytes, st);
+    if (err == hipSuccess) err = hipMemsetAsync(de + E.sum.off, 0, E.sum.bytes, st);
+    if (err == hipSuccess) err = hipMemsetAsync(de + E.learn.off, 0, E.learn.bytes, st);
+    if (err == hipSuccess) err = hipMemsetAsync(de + E.done.off, 0, E.done.bytes, st);
     if (!host_counted) {
         uint8_t* mh = (uint8_t*)ctx->walk_map.h;
         void* md = nullptr;
         if (err == hipSuccess) err = hipHostGetDevicePointer(&md, mh, 0);
-        if (err == hipSuccess) err = launch_walk_count(a, (WalkTotals*)((uint8_t*)md + m_tot), (uint32_t*)((uint8_t*)md + m_totflag), seq_tot, st);
+        if (err == hipSuccess) err = launch_walk_count(a, (WalkTotals*)((uint8_t*)md + WALK_MAP_TOT), (uint32_t*)((uint8_t*)md + WALK_MAP_TOTFLAG), seq_tot, st);
         if (err != hipSuccess) return hip_to_rc(err);
         // the one thing the host must know before it can go on - how many tuples, prefixes, checks - arrives in mapped memory
-        if ((rc = wait_host_flag((const uint32_t*)(mh + m_totflag), seq_tot, st))) return rc;
+        if ((rc = wait_host_flag((const uint32_t*)(mh + WALK_MAP_TOTFLAG), seq_tot, st))) return rc;
     }
     if (err != hipSuccess) return hip_to_rc(err);
-    const WalkTotals tot = host_counted ? host_tot : *(const WalkTotals*)((uint8_t*)ctx->walk_map.h + m_tot);
+    const WalkTotals tot = host_counted ? host_tot : *(const WalkTotals*)((uint8_t*)ctx->walk_map.h + WALK_MAP_TOT);
     if (tot.gather_bytes > 0x7FFFFFF0ull) return decline("gathered hash inputs exceed 2 GiB");
     const uint64_t nt64 = (uint64_t)tot.tuples + rq.n_block_sigs;
     if (nt64 > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
@@ -2584,63 +2640,26 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
     mark("totals known");
     if (!rq.sizes(rq.user, cnts, out)) return FABGPU_ETOOBIG;
     mark("sizes callback");
-    // ---- per-tuple arrays ----
-    o = 0;
-    const size_t words = (nt + 63) / 64;
-    const size_t o_tup = carve((size_t)nt * sizeof(bccsp::BlockTuple)), o_pre = carve(((size_t)np + 1) * 8), o_chk = carve(((size_t)nc + 1) * sizeof(bccsp::BlockHashCheck)),
-                 o_gsp = carve(((size_t)nc + 1) * 24), o_gof = carve(((size_t)nc + 1) * 4), o_gdg = carve(((size_t)nc + 1) * 32), o_idx = carve((size_t)nt * 4),
-                 o_off = carve((size_t)nt * 8), o_pix = carve((size_t)nt * 4), o_kid = carve((size_t)nt * 4), o_qx = carve((size_t)nt * 32),
-                 o_qy = carve((size_t)nt * 32), o_r = carve((size_t)nt * 32), o_s = carve((size_t)nt * 32), o_gst = carve(nt), o_bits = carve(words * 8),
-                 o_dst = carve(nt), o_tst = carve(nt), o_hsh = carve(nt), o_dig = carve((size_t)nt * 32), o_mid = carve(((size_t)np + 1) * 32),
-                 o_row = carve((size_t)nt * 4), o_bitc = carve(words * 8), o_tdig = carve((size_t)nt * 32), o_cspan = carve(((size_t)tot.creators + 1) * 8), o_tfl = carve(nt),
-                 o_nymf = carve(n_msps ? (size_t)tot.creators * 192 : 0), o_nymi = carve(n_msps ? (size_t)tot.creators * 4 : 0),
-                 o_nymsp = carve(n_msps ? (size_t)tot.creators * 8 : 0), o_nymio = carve(n_msps ? (size_t)tot.creators * 4 : 0),
-                 o_nymb = carve(n_msps ? ((size_t)tot.creators + 63) / 64 * 8 + 8 : 0), o_nymst = carve(n_msps ? (size_t)tot.creators + 64 : 0),
-                 o_nymga = carve(n_msps ? (size_t)tot.creators * 4 + 256 : 0), o_nymsl = carve(n_msps ? (size_t)tot.creators * 4 : 0),
-                 o_tqxy = carve(out.tuple_qxy ? (size_t)nt * 64 : 0), o_sparts = carve(((size_t)nt + 255) / 256 * sizeof(WalkSummary)),
-                 o_wide = carve(nt <= (uint32_t)WIDE_LAUNCH_MAX ? (size_t)nt * WIDE_SCRATCH_BYTES : 0),
-                 o_bita = carve(nt <= (uint32_t)WIDE_LAUNCH_MAX ? words * 8 : 0);                        // ... and the one bitmap of their second phase   // w and u2 Q of every row between the two phases of the wide kernels
+    // ---- per-tuple arrays (walk_layout.h) ----
     // the verdict memo, if the caller gave room for it (WalkOut::memo_*): built behind the status kernel, copied straight into that room
     const bool memo = out.memo_slots && out.memo_key_off && out.memo_keys && out.memo_status && out.memo_digests && out.memo_slot_cap >= 16 &&
                       (out.memo_slot_cap & (out.memo_slot_cap - 1)) == 0 && out.memo_slot_cap >= 2 * (uint64_t)nt && out.memo_keys_cap != 0 &&
                       out.memo_keys_cap < 0xFFFFFFF0ull;
-    // (on the device the keys have room for the longest signatures the memo takes - 1 024 bytes each; what is copied ahead is the room
-    //  the caller gave, sized for ordinary signatures; a block that needs more gets the rest through WalkRequest::memo_grow at the end)
-    const size_t dev_keys_cap = memo ? (size_t)std::min<uint64_t>(0xFFFFFFE0ull, std::max<uint64_t>(out.memo_keys_cap, (uint64_t)nt * (141 + 1024) + 256)) : 0;
-    const size_t o_ment = carve(memo ? (size_t)nt * 4 : 0), o_mslots = carve(memo ? (size_t)out.memo_slot_cap * 4 : 0),
-                 o_mkoff = carve(memo ? ((size_t)nt + 1) * 4 : 0), o_mkeys = carve(memo ? dev_keys_cap : 0), o_mst = carve(memo ? nt : 0),
-                 o_mtot = carve(memo ? sizeof(WalkMemoTotals) : 0), o_mdig = carve(memo ? (size_t)nt * 32 : 0);
     // ... and the digest memo's index beside it (message spans by entry + a second slot table), if the caller gave room for that too
     const bool hmemo = memo && out.memo_hspans && out.memo_hslots;
-    const size_t o_mhsp = carve(hmemo ? (size_t)nt * 16 : 0), o_mhsl = carve(hmemo ? (size_t)out.memo_slot_cap * 4 : 0);
-    const size_t o_mtiles = carve(memo ? ((size_t)nt / 2048 + 2) * 24 : 0);                     // the entry scan's tiles (walk_memo_tile_*_kernel)
-    if ((rc = ctx->walk_tup.ensure(o))) return rc;
+    WalkTupleShape ts;
+    ts.nt = nt; ts.np = np; ts.nc = nc; ts.creators = tot.creators; ts.n_msps = n_msps;
+    ts.tuple_qxy = out.tuple_qxy != nullptr; ts.memo = memo; ts.hmemo = hmemo; ts.memo_slot_cap = out.memo_slot_cap; ts.memo_keys_cap = out.memo_keys_cap;
+    const WalkTupleLayout T = walk_tuple_layout(ts);
+    if ((rc = ctx->walk_tup.ensure(T.total))) return rc;
     uint8_t* dt = (uint8_t*)ctx->walk_tup.d;
-    a.tuples = (bccsp::BlockTuple*)(dt + o_tup);
     a.n_tuples = nt;
-    a.pre_off2 = (uint32_t*)(dt + o_pre);
-    a.checks = (bccsp::BlockHashCheck*)(dt + o_chk);
-    a.gather_spans = (uint32_t*)(dt + o_gsp);
-    a.gather_off = (uint32_t*)(dt + o_gof);
-    a.gather_digests = dt + o_gdg;
-    a.id_idx = (uint32_t*)(dt + o_idx);
-    a.off2 = (uint32_t*)(dt + o_off);
-    a.pre_idx = (uint32_t*)(dt + o_pix);
-    a.key_id = (uint32_t*)(dt + o_kid);
-    a.qx = dt + o_qx; a.qy = dt + o_qy; a.r = dt + o_r; a.s = dt + o_s;
-    a.gate_st = dt + o_gst;
-    a.tflags = dt + o_tfl;
     const bool has_nym_rows = n_msps != 0 && tot.creators != 0;
+    bind_tuple_arrays(a, dt, T, has_nym_rows, memo, hmemo, out.tuple_digest || memo /* the memo's keys hold the digests */, out.tuple_qxy != nullptr);
     if (has_nym_rows) {
-        a.idemix_msps = (const DevIdemixMsp*)(de + o_msps);
+        a.idemix_msps = (const DevIdemixMsp*)(de + E.msps.off);
         a.n_idemix_msps = n_msps;
-        a.nym_fields = dt + o_nymf;
-        a.nym_issuer = (uint32_t*)(dt + o_nymi);
-        a.nym_issuer_out = (int32_t*)(dt + o_nymio);
-        a.nym_spans = (uint32_t*)(dt + o_nymsp);
     }
-    a.row_of = (uint32_t*)(dt + o_row);
-    a.creator_spans = (uint32_t*)(dt + o_cspan);
     a.n_dev_tuples = tot.tuples;
     a.n_creators = tot.creators;
     // Split the submission (WalkArrays::row_of) when one launch would have to run one lane per signature (more than VERIFY_PAIR_MAX
@@ -2657,32 +2676,11 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         both_pair = true;
     }
     const bool exclusive = a.split && !both_pair;
-    a.verdict_bits = (const uint64_t*)(dt + o_bits);
-    a.verdict_bits_c = (const uint64_t*)(dt + o_bitc);
-    a.row_digests = (out.tuple_digest || memo) ? dt + o_dig : nullptr;    // (the memo's keys hold the digests)
-    a.tuple_digests = dt + o_tdig;
-    a.tuple_qxy = out.tuple_qxy ? dt + o_tqxy : nullptr;
-    a.summary_parts = (uint32_t*)(dt + o_sparts);
     if (memo) {
-        a.memo_ent = (uint32_t*)(dt + o_ment);
-        a.memo_slots = (uint32_t*)(dt + o_mslots);
         a.memo_mask = out.memo_slot_cap - 1;
-        a.memo_key_off = (uint32_t*)(dt + o_mkoff);
-        a.memo_keys = dt + o_mkeys;
-        a.memo_keys_cap = (uint32_t)dev_keys_cap;
-        a.memo_status = dt + o_mst;
-        a.memo_totals = (WalkMemoTotals*)(dt + o_mtot);
-        a.memo_digests = dt + o_mdig;
-        a.memo_tiles = dt + o_mtiles;
-        if (hmemo) {
-            a.memo_hspans = (uint32_t*)(dt + o_mhsp);
-            a.memo_hslots = (uint32_t*)(dt + o_mhsl);
-        }
-        if (n_msps && rq.idemix_issuer_hashes) a.issuer_hashes = de + o_ihash;
+        a.memo_keys_cap = (uint32_t)T.dev_keys_cap;
+        if (n_msps && rq.idemix_issuer_hashes) a.issuer_hashes = de + E.ihash.off;
     }
-    a.dev_status = dt + o_dst;
-    a.tuple_status = dt + o_tst;
-    a.tuple_hashed = dt + o_hsh;
     if (ctx->d_idtab) {
         a.id_slots = (const uint32_t*)ctx->d_idtab;
         a.id_mask = ctx->idtab_mask;
@@ -2691,43 +2689,27 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         a.id_bytes = (uint8_t*)ctx->d_idtab + ctx->idtab_bytes_off;
     }
     // pinned room for everything that comes back
-    size_t po = p_first;
-    auto pin = [&](size_t bytes) { size_t at = po; po = round_up(po + bytes, 64); return at; };
-    const size_t p_type = pin(ne), p_und = pin(ne), p_tup = pin((size_t)nt * sizeof(bccsp::BlockTuple)), p_dig = pin((size_t)nt * 32),
-                 p_pre = pin(((size_t)np + 1) * 8), p_chk = pin(((size_t)nc + 1) * sizeof(bccsp::BlockHashCheck)),
-                 p_sigs = pin((size_t)rq.n_block_sigs * sizeof(bccsp::BlockTuple) + 64), p_qxy = pin(out.tuple_qxy ? (size_t)nt * 64 : 0),
-                 p_nymi = pin(out.nym_issuer ? (size_t)tot.creators * 4 : 0);
+    const WalkPinLayout P = walk_pin_layout(E, ne, ts, rq.n_block_sigs, out.nym_issuer != nullptr);
     {
         // (growing the pinned buffer moves it: nothing above is still needed from the old one)
-        if ((rc = ctx->walk_pin.ensure(po))) return rc;
+        if ((rc = ctx->walk_pin.ensure(P.total))) return rc;
     }
     uint8_t* ph = (uint8_t*)ctx->walk_pin.h;
     // ... and mapped room for what the last kernel writes itself (flags, statuses, identity indices, learn records, summary)
-    size_t mo = m_arrays;
-    auto mapped = [&](size_t bytes) { size_t at = mo; mo = round_up(mo + bytes, 64); return at; };
-    const size_t m_learn = mapped(sizeof(WalkLearn) * WALK_LEARN_SLOTS), m_flags = mapped(ne), m_type = mapped(ne), m_und = mapped(ne), m_tst = mapped(nt),
-                 m_hsh = mapped(nt), m_idx = mapped((size_t)nt * 4);
-    if ((rc = ctx->walk_map.ensure(mo))) return rc;                        // (may move it: the totals above have been read)
+    const WalkMapLayout M = walk_map_layout(ne, nt);
+    if ((rc = ctx->walk_map.ensure(M.total))) return rc;                   // (may move it: the totals above have been read)
     uint8_t* mh = (uint8_t*)ctx->walk_map.h;
     WalkHostOut ho;
     {
         void* md = nullptr;
         if (hipHostGetDevicePointer(&md, mh, 0) != hipSuccess) return FABGPU_ELAUNCH;
-        uint8_t* m8 = (uint8_t*)md;
-        ho.flag = (uint32_t*)(m8 + m_finflag);
-        ho.done = (uint32_t*)(de + o_done);
-        ho.summary = (WalkSummary*)(m8 + m_sum);
-        ho.memo_totals = memo ? (WalkMemoTotals*)(m8 + m_mtot) : nullptr;
-        ho.learn = (WalkLearn*)(m8 + m_learn);
-        ho.tx_flags = m8 + m_flags; ho.tx_type = m8 + m_type; ho.tx_understood = m8 + m_und;
-        ho.tuple_status = m8 + m_tst; ho.tuple_hashed = m8 + m_hsh;
-        ho.id_idx = (uint32_t*)(m8 + m_idx);
+        bind_host_out(ho, (uint8_t*)md, M, (uint32_t*)(de + E.done.off), memo);
     }
     mark("buffers ensured");
     err = launch_walk_emit(a, tot, st);
     if (err == hipSuccess && rq.n_block_sigs) {
-        memcpy(ph + p_sigs, rq.block_sigs, (size_t)rq.n_block_sigs * sizeof(bccsp::BlockTuple));
-        err = hipMemcpyAsync(a.tuples + tot.tuples, ph + p_sigs, (size_t)rq.n_block_sigs * sizeof(bccsp::BlockTuple), hipMemcpyHostToDevice, st);
+        memcpy(ph + P.sigs.off, rq.block_sigs, (size_t)rq.n_block_sigs * sizeof(bccsp::BlockTuple));
+        err = hipMemcpyAsync(a.tuples + tot.tuples, ph + P.sigs.off, (size_t)rq.n_block_sigs * sizeof(bccsp::BlockTuple), hipMemcpyHostToDevice, st);
     }
     if (err != hipSuccess) return hip_to_rc(err);
     auto fetch = [&](void* host_dst, size_t pin_off, const void* dev_src, size_t bytes) {
@@ -2738,20 +2720,20 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         if (host_dst && bytes) memcpy(host_dst, ph + pin_off, bytes);
     };
     if (rq.walk_only) {
-        fetch(out.tx_type, p_type, a.tx_type, ne);
-        fetch(out.tx_understood, p_und, a.tx_understood, ne);
-        fetch(out.tuples, p_tup, a.tuples, (size_t)nt * sizeof(bccsp::BlockTuple));
-        fetch(out.prefixes, p_pre, a.pre_off2, (size_t)np * 8);
-        fetch(out.checks, p_chk, a.checks, (size_t)nc * sizeof(bccsp::BlockHashCheck));
+        fetch(out.tx_type, P.type.off, a.tx_type, P.type.bytes);
+        fetch(out.tx_understood, P.und.off, a.tx_understood, P.und.bytes);
+        fetch(out.tuples, P.tup.off, a.tuples, P.tup.bytes);
+        fetch(out.prefixes, P.pre.off, a.pre_off2, (size_t)np * 8);
+        fetch(out.checks, P.chk.off, a.checks, (size_t)nc * sizeof(bccsp::BlockHashCheck));
         if (err == hipSuccess) err = hipStreamSynchronize(st);
         if (err != hipSuccess) return hip_to_rc(err);
-        deliver(out.tx_type, p_type, ne);
-        deliver(out.tx_understood, p_und, ne);
-        deliver(out.tuples, p_tup, (size_t)nt * sizeof(bccsp::BlockTuple));
-        deliver(out.checks, p_chk, (size_t)nc * sizeof(bccsp::BlockHashCheck));
+        deliver(out.tx_type, P.type.off, P.type.bytes);
+        deliver(out.tx_understood, P.und.off, P.und.bytes);
+        deliver(out.tuples, P.tup.off, P.tup.bytes);
+        deliver(out.checks, P.chk.off, (size_t)nc * sizeof(bccsp::BlockHashCheck));
         if (out.prefixes)                                          // (start, end) pairs on the device, (offset, length) for the caller
             for (uint32_t p = 0; p < np; p++) {
-                const uint32_t s0 = ((const uint32_t*)(ph + p_pre))[2 * p], s1 = ((const uint32_t*)(ph + p_pre))[2 * p + 1];
+                const uint32_t s0 = ((const uint32_t*)(ph + P.pre.off))[2 * p], s1 = ((const uint32_t*)(ph + P.pre.off))[2 * p + 1];
                 out.prefixes[p].off = s0;
                 out.prefixes[p].len = s1 - s0;
             }
@@ -2779,16 +2761,10 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         pa.m = np;
         pa.pre_off = a.pre_off2;
         pa.pre_idx = a.pre_idx;
-        pa.mid_scratch = dt + o_mid;
+        pa.mid_scratch = dt + T.mid.off;
     }
     const size_t gscr = round_up((size_t)tot.gather_bytes, 4) + 64;
-    if (nc && ctx->gscr_cap < gscr) {
-        if (ctx->d_gscr) hipFree(ctx->d_gscr);
-        ctx->d_gscr = nullptr;
-        ctx->gscr_cap = 0;
-        if (hipMalloc(&ctx->d_gscr, gscr + gscr / 4) != hipSuccess) return FABGPU_ENOMEM;
-        ctx->gscr_cap = gscr + gscr / 4;
-    }
+    if (nc && (rc = ctx->gscr.ensure(gscr))) return rc;
     // the emitted prefixes / hash checks are all stream2 and stream3 need: mid-states and the TxID / proposal-hash digests run while
     // the main stream looks identities up and gates signatures
     hipStream_t sc = s2;                                                   // the creators' stream
@@ -2813,8 +2789,8 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
     if (a.split && early_hash) a.early_creator_hash = 1;
     if (err == hipSuccess && has_nym_rows) {
         // rows of creators that are not idemix stay all-zero; issuer_out -1 = inactive
-        err = hipMemsetAsync(dt + o_nymf, 0, (o_nymio - o_nymf), st);
-        if (err == hipSuccess) err = hipMemsetAsync(dt + o_nymio, 0xFF, (size_t)tot.creators * 4, st);
+        err = hipMemsetAsync(dt + T.nym_zeroed.off, 0, T.nym_zeroed.bytes, st);
+        if (err == hipSuccess) err = hipMemsetAsync(dt + T.nymio.off, 0xFF, T.nymio.bytes, st);
     }
     // With idemix creators expected the creators' tuples are gated in a launch of their own, first: the nym launch (a long kernel: the
     // pass's critical path on such a block) waits for that one only.
@@ -2855,7 +2831,7 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         // [n_creators, nt) - hash only, beside `pre`
         ShaPrefixArgs ph = pa;
         ph.mid_ready = true;
-        ph.digests = dt + o_dig + 32 * (size_t)tot.creators;
+        ph.digests = dt + T.dig.off + 32 * (size_t)tot.creators;
         if (np) ph.pre_idx = a.pre_idx + tot.creators;
         err = hipStreamWaitEvent(s3, ctx->ev_w[3], 0);                     // (recorded behind the gates: the emit kernel's event is implied)
         if (err == hipSuccess)
@@ -2867,7 +2843,7 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         err = hipEventRecord(ctx->ev_w[3], st);                            // the submission arrays are complete (the endorsements' hashes read them)
         // (the order of these calls is the order the kernels start in - the host's calls, 3 us each, set the pace of a small block - and
         //  since the hashes run on eight lanes `pre` is the longer leg of what `post` waits for: 75 us against 62)
-        if (err == hipSuccess) err = launch_p256_wide_pre(nt, a.key_id, nkeys, (const void*)kt, a.r, a.s, ctx->d_gtab, dt + o_wide, st, spread);
+        if (err == hipSuccess) err = launch_p256_wide_pre(nt, a.key_id, nkeys, (const void*)kt, a.r, a.s, ctx->d_gtab, dt + T.wide.off, st, spread);
         if (err == hipSuccess && coop_messages) queue_messages();
     }
     if (err == hipSuccess && a.split) {
@@ -2876,9 +2852,9 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         // is all that is left), or they are hashed now, beside the identity lookup and the gates.
         err = hipStreamWaitEvent(sc, ctx->ev_w[0], 0);
         if (err == hipSuccess && early_hash) {
-            err = launch_walk_creator_digests(a, dt + o_dig, sc);
+            err = launch_walk_creator_digests(a, dt + T.dig.off, sc);
         } else if (err == hipSuccess) {
-            err = launch_sha256_spans(tot.creators, sl->d, arena_bytes, a.creator_spans, dt + o_dig, sc, exclusive ? 84u << 10 : 0u);
+            err = launch_sha256_spans(tot.creators, sl->d, arena_bytes, a.creator_spans, dt + T.dig.off, sc, exclusive ? 84u << 10 : 0u);
         }
         if (err == hipSuccess && wide) err = hipEventRecord(ctx->ev_w[4], sc);   // "the creators' digests are in their rows" (the one `post` launch waits for it)
     }
@@ -2887,12 +2863,12 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
     if (err == hipSuccess && np && coop_messages) queue_midstates();
     if (err == hipSuccess && nc) {       // stream4: the TxID / proposal-hash digests (only the flags at the very end wait for them)
         err = hipStreamWaitEvent(s4, ctx->ev_w[0], 0);
-        if (err == hipSuccess) err = launch_gather_sha256(nc, sl->d, arena_bytes, a.gather_spans, a.gather_off, ctx->d_gscr, gscr, dt + o_gdg, s4, 0, spread);
+        if (err == hipSuccess) err = launch_gather_sha256(nc, sl->d, arena_bytes, a.gather_spans, a.gather_off, ctx->gscr.d, gscr, dt + T.gdg.off, s4, 0, spread);
         if (err == hipSuccess) err = hipEventRecord(ctx->ev_w[2], s4);
     }
     mark("side streams queued");
     if (err == hipSuccess && memo_early_pending) {
-        if (hmemo) err = hipMemsetAsync(dt + o_mhsl, 0, (size_t)out.memo_slot_cap * 4, s4);   // (ahead of the wait for the gates)
+        if (hmemo) err = hipMemsetAsync(dt + T.mhsl.off, 0, T.mhsl.bytes, s4);   // (ahead of the wait for the gates)
         if (err == hipSuccess) err = hipStreamWaitEvent(s4, ctx->ev_w[7], 0);
         // len, the tiled scan (entry indices, key offsets), then the key bytes on stream4 and - beside them, on stream3 - the digest
         // memo's index: both only need the scan (round 6: one after the other they were 85 us between the gates and the keys' copy)
@@ -2901,13 +2877,13 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         if (err == hipSuccess && hmemo) err = launch_walk_memo_index(a, s3);
         if (err == hipSuccess && hmemo) err = hipEventRecord(ctx->ev_w[11], s3);
         mark("memo early launched");
-        if (err == hipSuccess) err = hipMemcpyAsync(out.memo_key_off, dt + o_mkoff, ((size_t)nt + 1) * 4, hipMemcpyDeviceToHost, s4);
+        if (err == hipSuccess) err = hipMemcpyAsync(out.memo_key_off, dt + T.mkoff.off, T.mkoff.bytes, hipMemcpyDeviceToHost, s4);
         mark("memo key_off copy queued");
-        if (err == hipSuccess) err = hipMemcpyAsync(out.memo_keys, dt + o_mkeys, out.memo_keys_cap, hipMemcpyDeviceToHost, s4);
+        if (err == hipSuccess) err = hipMemcpyAsync(out.memo_keys, dt + T.mkeys.off, out.memo_keys_cap, hipMemcpyDeviceToHost, s4);
         mark("memo keys copy queued");
         if (err == hipSuccess && hmemo) err = hipStreamWaitEvent(s4, ctx->ev_w[11], 0);
-        if (err == hipSuccess && hmemo) err = hipMemcpyAsync(out.memo_hspans, dt + o_mhsp, (size_t)nt * 16, hipMemcpyDeviceToHost, s4);
-        if (err == hipSuccess && hmemo) err = hipMemcpyAsync(out.memo_hslots, dt + o_mhsl, (size_t)out.memo_slot_cap * 4, hipMemcpyDeviceToHost, s4);
+        if (err == hipSuccess && hmemo) err = hipMemcpyAsync(out.memo_hspans, dt + T.mhsp.off, T.mhsp.bytes, hipMemcpyDeviceToHost, s4);
+        if (err == hipSuccess && hmemo) err = hipMemcpyAsync(out.memo_hslots, dt + T.mhsl.off, T.mhsl.bytes, hipMemcpyDeviceToHost, s4);
         if (err == hipSuccess) err = hipEventRecord(ctx->ev_w[8], s4);
     }
     // The block's idemix creators: ONE nym launch over their rows, packed (walk_nym_pack_kernel: 2 000 idemix creators among 10 000 are
@@ -2921,23 +2897,23 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         // The launch's rows take their inputs through the pack kernel's list (row -> creator rank); rows nobody claims stay idle (~0).
         // The status bytes start out as "not decided" so that a row the nym kernel never ran over can not read as valid.  (All of that
         // ahead of the wait for the gates.)
-        hipError_t e = hipMemsetAsync(dt + o_nymga, 0xFF, (size_t)cap * 4, s3);
-        if (e == hipSuccess) e = hipMemsetAsync(dt + o_nymb, 0, ((size_t)cap + 63) / 64 * 8 + 8, s3);
-        if (e == hipSuccess) e = hipMemsetAsync(dt + o_nymst, 6 /* FABGPU_NYM_NEEDS_SW */, (size_t)cap + 64, s3);
+        hipError_t e = hipMemsetAsync(dt + T.nymga.off, 0xFF, (size_t)cap * 4, s3);
+        if (e == hipSuccess) e = hipMemsetAsync(dt + T.nymb.off, 0, walk_nym_bits_bytes(cap), s3);
+        if (e == hipSuccess) e = hipMemsetAsync(dt + T.nymst.off, 6 /* FABGPU_NYM_NEEDS_SW */, walk_nym_status_bytes(cap), s3);
         if (e == hipSuccess) e = hipStreamWaitEvent(s3, ctx->ev_w[5], 0);
-        a.nym_slot = (uint32_t*)(dt + o_nymsl);
-        if (e == hipSuccess) e = launch_walk_nym_pack(a, (uint32_t*)(dt + o_nymga), cap, s3);
+        a.nym_slot = (uint32_t*)(dt + T.nymsl.off);
+        if (e == hipSuccess) e = launch_walk_nym_pack(a, (uint32_t*)(dt + T.nymga.off), cap, s3);
         if (e != hipSuccess) return hip_to_rc(e);
-        const size_t col = (size_t)32 * tot.creators;
-        uint8_t* f = dt + o_nymf;
-        int r2 = nym_verify_dev(ctx, cap, sl->d, arena_bytes, dt + o_nymsp, true, dt + o_nymi, f, f + col, f + 2 * col, f + 3 * col, f + 4 * col, f + 5 * col,
-                                dt + o_nymb, dt + o_nymst, s3, false, dt + o_nymga,
+        const size_t col = T.nym_col;
+        uint8_t* f = dt + T.nymf.off;
+        int r2 = nym_verify_dev(ctx, cap, sl->d, arena_bytes, dt + T.nymsp.off, true, dt + T.nymi.off, f, f + col, f + 2 * col, f + 3 * col, f + 4 * col, f + 5 * col,
+                                dt + T.nymb.off, dt + T.nymst.off, s3, false, dt + T.nymga.off,
                                 exclusive ? 84u << 10 : 0u);   // on CUs of its own, like the two ECDSA launches (kernels.h)
         if (r2 != FABGPU_OK) return r2;
         e = hipEventRecord(ctx->ev_w[6], s3);                              // (the main stream waits for it in front of the status kernel, not here:
         if (e != hipSuccess) return hip_to_rc(e);                          // the ECDSA launches queued next must run BESIDE the nym kernel)
         a.nym_cap = cap;
-        a.nym_status = dt + o_nymst;
+        a.nym_status = dt + T.nymst.off;
         nym_ran = true;
         nym_cap = cap;
         return FABGPU_OK;
@@ -2950,7 +2926,7 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
     rq.ms_walk = ms_since(t_start);
     const auto t_verify = now();
     pa.mid_ready = true;
-    pa.digests = (out.tuple_digest || memo) ? dt + o_dig : nullptr;
+    pa.digests = (out.tuple_digest || memo) ? dt + T.dig.off : nullptr;
     // rows [row0, row0 + n) as one fused (hash + verify) launch on stream `ls`
     auto verify_rows = [&](uint32_t row0, uint32_t n, bool prefixed, bool pair, bool keyed, void* bits, hipStream_t ls) -> int {
         ShaPrefixArgs p = pa;
@@ -2962,13 +2938,13 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         } else {
             p.pre_idx = a.pre_idx + row0;
         }
-        if (p.digests) p.digests = dt + o_dig + 32 * (size_t)row0;
+        if (p.digests) p.digests = dt + T.dig.off + 32 * (size_t)row0;
         VerifyLaunch v;
         v.n = n;
         v.arena = sl->d; v.arena_bytes = arena_bytes; v.off = a.off2 + 2 * (size_t)row0; v.pa = p;
         v.r = a.r + 32 * (size_t)row0; v.s = a.s + 32 * (size_t)row0;
         v.gtab = ctx->d_gtab;
-        v.verdict_bits = bits; v.status = dt + o_dst + row0;
+        v.verdict_bits = bits; v.status = dt + T.dst.off + row0;
         v.allow_pair = pair;
         hipError_t e;
         if (keyed) {
@@ -2989,9 +2965,9 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
     auto verify_creators = [&](bool keyed) -> int {
         VerifyLaunch v;
         v.n = tot.creators;
-        v.e = dt + o_dig; v.r = a.r; v.s = a.s;
+        v.e = dt + T.dig.off; v.r = a.r; v.s = a.s;
         v.gtab = ctx->d_gtab;
-        v.verdict_bits = dt + o_bitc; v.status = dt + o_dst;
+        v.verdict_bits = dt + T.bitc.off; v.status = dt + T.dst.off;
         v.allow_pair = true; v.lds_reserve = exclusive ? 84u << 10 : 0u;
         hipError_t e;
         if (keyed) {
@@ -3016,41 +2992,41 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         if (++ctx->walk_seq == 0) ++ctx->walk_seq;
         ho.seq = ctx->walk_seq;
         if (err == hipSuccess && nym_ran) err = hipStreamWaitEvent(st, ctx->ev_w[6], 0);     // the nym kernel's answers
-        if (err == hipSuccess && memo) err = hipMemsetAsync(dt + o_mslots, 0, (size_t)out.memo_slot_cap * 4, st);
-        if (err == hipSuccess && memo) err = hipMemsetAsync(&((WalkMemoTotals*)(dt + o_mtot))->live, 0, 4, st);
+        if (err == hipSuccess && memo) err = hipMemsetAsync(dt + T.mslots.off, 0, T.mslots.bytes, st);
+        if (err == hipSuccess && memo) err = hipMemsetAsync(&((WalkMemoTotals*)(dt + T.mtot.off))->live, 0, 4, st);
         mark("finish: memsets queued");
         if (!memo && !out.tuples && !out.tuple_digest && !out.tuple_qxy && !(has_nym_rows && out.nym_issuer) && walk_small_finish_fits(a, nc)) {
             // a small block, flags only: statuses, digest comparisons and the finish in one launch
             if (err == hipSuccess) err = launch_walk_status_finish_small(a, nc, ho, st);
             mark("finish: last kernel queued");
             if (err != hipSuccess) return hip_to_rc(err);
-            int r2 = wait_host_flag((const uint32_t*)(mh + m_finflag), ho.seq, st);
+            int r2 = wait_host_flag((const uint32_t*)(mh + WALK_MAP_FINFLAG), ho.seq, st);
             if (r2 != FABGPU_OK) return r2;
-            rq.summary = *(const WalkSummary*)(mh + m_sum);
+            rq.summary = *(const WalkSummary*)(mh + WALK_MAP_SUM);
             return FABGPU_OK;
         }
         if (err == hipSuccess) err = launch_walk_status_checks(a, nc, st);
         if (memo) {
             // the LATE half of the memo: digests, status bytes and slots of the candidates that were hashed and decided
             if (err == hipSuccess) err = launch_walk_memo_late(a, st);
-            if (err == hipSuccess) err = hipMemcpyAsync(out.memo_slots, dt + o_mslots, (size_t)out.memo_slot_cap * 4, hipMemcpyDeviceToHost, st);
-            if (err == hipSuccess) err = hipMemcpyAsync(out.memo_digests, dt + o_mdig, (size_t)nt * 32, hipMemcpyDeviceToHost, st);
-            if (err == hipSuccess) err = hipMemcpyAsync(out.memo_status, dt + o_mst, nt, hipMemcpyDeviceToHost, st);
+            if (err == hipSuccess) err = hipMemcpyAsync(out.memo_slots, dt + T.mslots.off, T.mslots.bytes, hipMemcpyDeviceToHost, st);
+            if (err == hipSuccess) err = hipMemcpyAsync(out.memo_digests, dt + T.mdig.off, T.mdig.bytes, hipMemcpyDeviceToHost, st);
+            if (err == hipSuccess) err = hipMemcpyAsync(out.memo_status, dt + T.mst.off, T.mst.bytes, hipMemcpyDeviceToHost, st);
             mark("finish: late memo copies queued");
         }
-        fetch(out.tuples, p_tup, a.tuples, (size_t)nt * sizeof(bccsp::BlockTuple));
-        fetch(out.tuple_digest, p_dig, dt + o_tdig, (size_t)nt * 32);
-        fetch(out.tuple_qxy, p_qxy, dt + o_tqxy, (size_t)nt * 64);
-        if (has_nym_rows) fetch(out.nym_issuer, p_nymi, dt + o_nymio, (size_t)tot.creators * 4);
+        fetch(out.tuples, P.tup.off, a.tuples, P.tup.bytes);
+        fetch(out.tuple_digest, P.dig.off, dt + T.tdig.off, P.dig.bytes);
+        fetch(out.tuple_qxy, P.qxy.off, dt + T.tqxy.off, P.qxy.bytes);
+        if (has_nym_rows) fetch(out.nym_issuer, P.nymi.off, dt + T.nymio.off, P.nymi.bytes);
         if (err == hipSuccess && memo) err = hipStreamWaitEvent(st, ctx->ev_w[8], 0);        // the memo's early half (long done: it ran beside the verify launches)
         if (err == hipSuccess) err = launch_walk_finish(a, ho, st);
         mark("finish: last kernel queued");
         if (err != hipSuccess) return hip_to_rc(err);
-        int r2 = wait_host_flag((const uint32_t*)(mh + m_finflag), ho.seq, st);
+        int r2 = wait_host_flag((const uint32_t*)(mh + WALK_MAP_FINFLAG), ho.seq, st);
         if (r2 != FABGPU_OK) return r2;
-        rq.summary = *(const WalkSummary*)(mh + m_sum);
+        rq.summary = *(const WalkSummary*)(mh + WALK_MAP_SUM);
         if (memo) {
-            const WalkMemoTotals mt = *(const WalkMemoTotals*)(mh + m_mtot);
+            const WalkMemoTotals mt = *(const WalkMemoTotals*)(mh + WALK_MAP_MTOT);
             rq.memo_n = mt.overflow ? 0 : mt.n;
             rq.memo_live = mt.overflow ? 0 : mt.live;
             rq.memo_bytes = mt.overflow ? 0 : mt.bytes;
@@ -3058,7 +3034,7 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
                 // more key bytes than the room that was copied ahead (signatures far longer than an ECDSA signature's 72 bytes): the caller
                 // makes room, the keys are copied again - whole - and the pass answers a little later; no room: no memo for this block
                 uint8_t* big = rq.memo_grow ? rq.memo_grow(rq.user, (size_t)mt.bytes) : nullptr;
-                if (!big || hipMemcpy(big, dt + o_mkeys, (size_t)mt.bytes, hipMemcpyDeviceToHost) != hipSuccess) rq.memo_n = rq.memo_live = 0;
+                if (!big || hipMemcpy(big, dt + T.mkeys.off, (size_t)mt.bytes, hipMemcpyDeviceToHost) != hipSuccess) rq.memo_n = rq.memo_live = 0;
             }
         }
         return FABGPU_OK;
@@ -3071,9 +3047,9 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         // and one cross-stream wait fewer in front of the finish than a launch per class had
         err = hipStreamWaitEvent(st, ctx->ev_w[10], 0);
         if (err == hipSuccess) err = hipStreamWaitEvent(st, ctx->ev_w[4], 0);
-        a.verdict_bits_all = (const uint64_t*)(dt + o_bita);
+        a.verdict_bits_all = (const uint64_t*)(dt + T.bita.off);
         a.all_creators = a.all_others = 1;
-        if (err == hipSuccess) err = launch_p256_wide_post(nt, dt + o_dig, a.r, ctx->d_gtab, dt + o_wide, dt + o_bita, dt + o_dst, st, spread);
+        if (err == hipSuccess) err = launch_p256_wide_post(nt, dt + T.dig.off, a.r, ctx->d_gtab, dt + T.wide.off, dt + T.bita.off, dt + T.dst.off, st, spread);
     } else if (a.split) {
         // creators on stream2 (two lanes per signature), everybody else on the main stream: side by side
         err = hipEventRecord(ctx->ev_w[3], st);                            // the submission arrays are complete
@@ -3082,10 +3058,10 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
         if ((rc = verify_creators(keyed_c))) return rc;
         err = hipEventRecord(ctx->ev_w[4], s2);
         if (err != hipSuccess) return hip_to_rc(err);
-        if ((rc = verify_rows(tot.creators, nt - tot.creators, np != 0, both_pair, keyed_o, dt + o_bits, st))) return rc;
+        if ((rc = verify_rows(tot.creators, nt - tot.creators, np != 0, both_pair, keyed_o, dt + T.bits.off, st))) return rc;
         err = hipStreamWaitEvent(st, ctx->ev_w[4], 0);
     } else {
-        if ((rc = verify_rows(0, nt, np != 0, ctx->allow_pair, keyed_o, dt + o_bits, st))) return rc;
+        if ((rc = verify_rows(0, nt, np != 0, ctx->allow_pair, keyed_o, dt + T.bits.off, st))) return rc;
     }
     if (err == hipSuccess && nc) err = hipStreamWaitEvent(st, ctx->ev_w[2], 0);
     if (err != hipSuccess) return hip_to_rc(err);
@@ -3123,13 +3099,13 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
                 a.all_others = 0;
                 if (!a.split) keyed_c = false;
                 if (wide && np && (err = hipStreamWaitEvent(st, ctx->ev_w[1], 0)) != hipSuccess) return hip_to_rc(err);   // (wide: nobody waited for the mid-states yet)
-                if ((rc = a.split ? verify_rows(tot.creators, nt - tot.creators, np != 0, both_pair, false, dt + o_bits, st)
-                                  : verify_rows(0, nt, np != 0, ctx->allow_pair, false, dt + o_bits, st)))
+                if ((rc = a.split ? verify_rows(tot.creators, nt - tot.creators, np != 0, both_pair, false, dt + T.bits.off, st)
+                                  : verify_rows(0, nt, np != 0, ctx->allow_pair, false, dt + T.bits.off, st)))
                     return rc;
             }
-            err = hipMemsetAsync(de + o_mask, 0, (size_t)ne * 4, st);
+            err = hipMemsetAsync(de + E.mask.off, 0, E.mask.bytes, st);
             if (err == hipSuccess) err = hipMemsetAsync(a.summary, 0, offsetof(WalkSummary, n_learn), st);   // (the status kernel adds them up again)
-            if (err == hipSuccess) err = hipMemsetAsync(de + o_done, 0, 64, st);
+            if (err == hipSuccess) err = hipMemsetAsync(de + E.done.off, 0, E.done.bytes, st);
             if (err != hipSuccess) return hip_to_rc(err);
             if ((rc = finish())) return rc;
         }
@@ -3140,18 +3116,18 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
     auto from_map = [&](void* host_dst, size_t map_off, size_t bytes) {
         if (host_dst && bytes) memcpy(host_dst, mh + map_off, bytes);
     };
-    from_map(out.tx_flags, m_flags, ne);
-    from_map(out.tx_type, m_type, ne);
-    from_map(out.tx_understood, m_und, ne);
-    from_map(out.tuple_status, m_tst, nt);
-    from_map(out.tuple_hashed, m_hsh, nt);
-    from_map(out.id_idx, m_idx, (size_t)nt * 4);
-    from_map(rq.learn_out, m_learn, sizeof(WalkLearn) * WALK_LEARN_SLOTS);
-    deliver(out.tuples, p_tup, (size_t)nt * sizeof(bccsp::BlockTuple));
-    deliver(out.tuple_digest, p_dig, (size_t)nt * 32);
-    deliver(out.tuple_qxy, p_qxy, (size_t)nt * 64);
-    if (has_nym_rows) deliver(out.nym_issuer, p_nymi, (size_t)tot.creators * 4);
-    else if (out.nym_issuer && tot.creators) memset(out.nym_issuer, 0xFF, (size_t)tot.creators * 4);
+    from_map(out.tx_flags, M.flags.off, M.flags.bytes);
+    from_map(out.tx_type, M.type.off, M.type.bytes);
+    from_map(out.tx_understood, M.und.off, M.und.bytes);
+    from_map(out.tuple_status, M.tst.off, M.tst.bytes);
+    from_map(out.tuple_hashed, M.hsh.off, M.hsh.bytes);
+    from_map(out.id_idx, M.idx.off, M.idx.bytes);
+    from_map(rq.learn_out, M.learn.off, M.learn.bytes);
+    deliver(out.tuples, P.tup.off, P.tup.bytes);
+    deliver(out.tuple_digest, P.dig.off, P.dig.bytes);
+    deliver(out.tuple_qxy, P.qxy.off, P.qxy.bytes);
+    if (has_nym_rows) deliver(out.nym_issuer, P.nymi.off, P.nymi.bytes);
+    else if (out.nym_issuer && tot.creators) memset(out.nym_issuer, 0xFF, P.nymi.bytes);
     drain.armed = false;                                                    // (the flag was raised behind everything: all four streams are idle)
     drain2.armed = false;
     return FABGPU_OK;
@@ -3159,7 +3135,7 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
 
 // What `slots` overlapping passes over blocks of up to block_bytes / n_tx transactions / n_tuples signatures need on this device, made
 // NOW (provider construction: ProviderOptions::concurrent_passes) instead of when passes first overlap - the staging slots for uploaded
-// blocks, the pinned staging buffer, the pass's device / pinned / host-mapped arrays at generous upper bounds, the gather scratch.  A peer
+// blocks, the pinned staging buffer, the pass's device / pinned / host-mapped arrays at their worst case (walk_layout.h), the gather scratch.  A peer
 // that joins a channel gets no untimed rounds: measured in round 3, the first overlapping passes of a provider took 5-16 ms (a second
 // and third 63 MB staging slot, the arrays of the first memo-seeding pass).  Best effort: a failed allocation is simply made later.
 int walk_preallocate(fabgpu_ctx* ctx, size_t block_bytes, uint32_t n_tx, uint32_t n_tuples, int slots) {
@@ -3228,20 +3204,14 @@ int walk_preallocate(fabgpu_ctx* ctx, size_t block_bytes, uint32_t n_tx, uint32_
         if (!ctx->stream_keytab) (void)hipStreamCreateWithFlags(&ctx->stream_keytab, hipStreamNonBlocking);
     }
     std::lock_guard<std::mutex> lk(ctx->mu);
-    const size_t ne = n_tx, nt = n_tuples;
-    // upper bounds of walk_block_pass's carves: per envelope 91 bytes of arrays + the count kernel's record slot, per tuple ~1.9 KB with the memo's key room (1 165 bytes)
-    if (ctx->walk_env.ensure(ne * (128 + sizeof(bccsp::walk::EnvStash)) + ((size_t)256 << 10)) != FABGPU_OK) rc = FABGPU_ENOMEM;
-    if (ctx->walk_tup.ensure(nt * 2112 + ne * 256 + ((size_t)1 << 20)) != FABGPU_OK) rc = FABGPU_ENOMEM;
-    if (ctx->walk_pin.ensure(nt * 256 + ne * 160 + ((size_t)256 << 10)) != FABGPU_OK) rc = FABGPU_ENOMEM;
-    if (ctx->walk_map.ensure(nt * 8 + ne * 8 + sizeof(WalkLearn) * WALK_LEARN_SLOTS + ((size_t)64 << 10)) != FABGPU_OK) rc = FABGPU_ENOMEM;
-    const size_t gscr = ne * 4096 + ((size_t)64 << 10);                         // TxID + proposal-hash inputs: a few KB per transaction
-    if (ctx->gscr_cap < gscr) {
-        if (ctx->d_gscr) hipFree(ctx->d_gscr);
-        ctx->d_gscr = nullptr;
-        ctx->gscr_cap = 0;
-        if (hipMalloc(&ctx->d_gscr, gscr) == hipSuccess) ctx->gscr_cap = gscr;
-        else rc = FABGPU_ENOMEM;
-    }
+    // the pass's four buffers at the largest layout a pass of this size can have (walk_layout.h walk_worst_case; never below the
+    // estimates made here before the layout was written down: walk_preallocate_floor)
+    const WalkSizes need_walk = walk_preallocate_sizes(n_tx, n_tuples);
+    if (ctx->walk_env.ensure(need_walk.env) != FABGPU_OK) rc = FABGPU_ENOMEM;
+    if (ctx->walk_tup.ensure(need_walk.tup) != FABGPU_OK) rc = FABGPU_ENOMEM;
+    if (ctx->walk_pin.ensure(need_walk.pin) != FABGPU_OK) rc = FABGPU_ENOMEM;
+    if (ctx->walk_map.ensure(need_walk.map) != FABGPU_OK) rc = FABGPU_ENOMEM;
+    if (ctx->gscr.ensure(walk_gather_scratch_estimate(n_tx)) != FABGPU_OK) rc = FABGPU_ENOMEM;
     if (ctx->tailbuf.ensure((size_t)64 << 10) != FABGPU_OK) rc = FABGPU_ENOMEM;
     // The copy ENGINES, too.  The runtime creates a DMA queue the first time a copy of a direction needs one more of them - ~10 ms each,
     // on the calling thread, inside hipMemcpyAsync: measured (rocprofv3 --memory-copy-trace, profiles/r04_trace_first_memo_passes.txt) as

@@ -28,6 +28,9 @@ long long fabgpu_test_key_tables16(fabgpu_ctx* ctx, uint32_t key_id);
 /* TEST HOOK: while on, the idemix four-lane form queues its side launch (the fixed-base terms) BEHIND the commitment launch, so that
  * every commitment wavefront gives up on its records and computes the terms itself, and every side wavefront skips its rows. */
 void fabgpu_test_nym_side_after(fabgpu_ctx* ctx, int on);
+/* TEST HOOK: the capacities in bytes of the block pass's buffers on ctx - per-envelope arrays, per-tuple arrays, pinned staging, host-mapped
+ * results, gather scratch (walk_layout.h says what a pass needs of each; walk_preallocate makes the worst case ahead of the first pass). */
+void fabgpu_test_walk_buffer_caps(fabgpu_ctx* ctx, uint64_t* out5);
 
 
 /* Synthetic block generator: n tuples, fresh P-256 keypair per signature, low-S, `invalid_permille`

@@ -18,6 +18,7 @@
 #include "block_walk_core.h"
 #include "block_prepass.h"
 #include "sha3_256.h"
+#include "walk_layout.h"
 
 using namespace fab;
 
@@ -481,5 +482,55 @@ void hosttest_summarize_transactions(uint32_t n_tx, const uint8_t* tx_understood
                                      const uint8_t* tuple_status, int hashes_done, const uint8_t* bad_txid, const uint8_t* bad_phash, uint8_t* tx_flags) {
     bccsp::SummarizeTransactions(n_tx, tx_understood, n_tuples, tuple_tx, tuple_kind, tuple_status, hashes_done ? bad_txid : nullptr,
                                  hashes_done ? bad_phash : nullptr, tx_flags);
+}
+// The layout of one of the block pass's four buffers (walk_layout.h; which: 0 per-envelope, 1 per-tuple, 2 pinned, 3 mapped) for a shape
+// of 16 words: ne, n_msps, early_hash, host_counted, has_issuer_hashes, nt, np, nc, creators, tuple_qxy, memo, hmemo, memo_slot_cap,
+// memo_keys_cap, n_block_sigs, nym_issuer.  out: (offset, bytes) of every region in carving order, then the buffer's scalars -
+//   0: up_small, up_all, total      1: dev_keys_cap, nym_zeroed.off, nym_zeroed.bytes, nym_col, "nymf .. nymio lie back to back", total
+//   2: first, total                 3: the six fixed cells, the size ensured before the totals are known, total.
+// Returns the number of words written, -1: `which` is none of the four or `cap` is too small.
+int hosttest_walk_layout(const uint32_t* shape, int which, uint64_t* out, int cap) {
+    WalkEnvShape es;
+    es.ne = shape[0]; es.n_msps = shape[1]; es.early_hash = shape[2] != 0; es.host_counted = shape[3] != 0; es.has_issuer_hashes = shape[4] != 0;
+    WalkTupleShape ts;
+    ts.nt = shape[5]; ts.np = shape[6]; ts.nc = shape[7]; ts.creators = shape[8]; ts.n_msps = shape[1];
+    ts.tuple_qxy = shape[9] != 0; ts.memo = shape[10] != 0; ts.hmemo = shape[11] != 0; ts.memo_slot_cap = shape[12]; ts.memo_keys_cap = shape[13];
+    int n = 0;
+    bool fits = true;
+    auto put = [&](uint64_t v) {
+        if (n < cap) out[n++] = v;
+        else fits = false;
+    };
+    auto regions = [&](const WalkRegion* r, size_t count) {
+        for (size_t i = 0; i < count; i++) { put(r[i].off); put(r[i].bytes); }
+    };
+    const WalkEnvLayout e = walk_env_layout(es);
+    if (which == 0) {
+        regions(e.regions(), e.N);
+        put(e.up_small); put(e.up_all); put(e.total);
+    } else if (which == 1) {
+        const WalkTupleLayout t = walk_tuple_layout(ts);
+        regions(t.regions(), t.N);
+        put(t.dev_keys_cap); put(t.nym_zeroed.off); put(t.nym_zeroed.bytes); put(t.nym_col); put(walk_nym_rows_adjacent(t) ? 1 : 0); put(t.total);
+    } else if (which == 2) {
+        const WalkPinLayout p = walk_pin_layout(e, es.ne, ts, shape[14], shape[15] != 0);
+        regions(p.regions(), p.N);
+        put(p.first); put(p.total);
+    } else if (which == 3) {
+        const WalkMapLayout m = walk_map_layout(es.ne, ts.nt);
+        regions(m.regions(), m.N);
+        put(WALK_MAP_TOTFLAG); put(WALK_MAP_TOT); put(WALK_MAP_FINFLAG); put(WALK_MAP_SUM); put(WALK_MAP_MTOT); put(WALK_MAP_ARRAYS);
+        put(walk_map_early_bytes(es.ne)); put(m.total);
+    } else {
+        return -1;
+    }
+    return fits ? n : -1;
+}
+// out[0..4): walk_worst_case's env, tuple, pinned, mapped totals; out[4..8): the floor kept from before; out[8..12): what walk_preallocate makes
+void hosttest_walk_worst_case(uint32_t n_tx, uint32_t n_tuples, uint64_t* out12) {
+    const WalkSizes s[3] = {walk_worst_case(n_tx, n_tuples), walk_preallocate_floor(n_tx, n_tuples), walk_preallocate_sizes(n_tx, n_tuples)};
+    for (int k = 0; k < 3; k++) {
+        out12[4 * k] = s[k].env; out12[4 * k + 1] = s[k].tup; out12[4 * k + 2] = s[k].pin; out12[4 * k + 3] = s[k].map;
+    }
 }
 }

@@ -73,6 +73,8 @@ int fabgpu_test_key_table_host(const uint8_t* qx32, const uint8_t* qy32, int32_t
 }
 // the idemix four-lane form: order the side launch behind the commitment launch (idemix_kernels.hip: both halves of the fallback)
 void fabgpu_test_nym_side_after(fabgpu_ctx* ctx, int on) { fab::ctx_test_nym_side_after(ctx, on != 0); }
+// how large the block pass's buffers are right now: a pass that fits what walk_preallocate made leaves all five as they were
+void fabgpu_test_walk_buffer_caps(fabgpu_ctx* ctx, uint64_t* out5) { fab::walk_buffer_caps(ctx, out5); }
 
 // TEST HOOK: the device walker against the host walker on one block.  0: identical (or *declined = 1: the device declined, nothing
 // compared); 1: they differ, `diff` says where.

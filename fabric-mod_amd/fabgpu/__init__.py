@@ -149,7 +149,7 @@ HOOK_SYMBOLS = [
     "fabgpu_test_key_table", "fabgpu_test_key_table_host", "fabgpu_test_gtab_compare_with_host", "fabgpu_test_key_tables16",
     "fabgpu_test_audit_sha256", "fabgpu_test_audit_p256_verify", "fabgpu_test_audit_sample", "fabgpu_csp_test_memo_corrupt",
     "fabgpu_test_key_slots_new", "fabgpu_test_key_slots_free", "fabgpu_test_key_slots_register", "fabgpu_test_key_slots_retire",
-    "fabgpu_test_key_slots_drain", "fabgpu_test_key_slots_stats",
+    "fabgpu_test_key_slots_drain", "fabgpu_test_key_slots_stats", "fabgpu_test_walk_buffer_caps",
 ]
 _HOOKS_PATH = os.path.join(os.path.dirname(_LIB_PATH), "libfabgpu_testhooks.so")
 
@@ -174,6 +174,8 @@ def load_hooks():
     H.fabgpu_last_kernel_ms.restype = ctypes.c_float
     H.fabgpu_test_nym_side_after.argtypes = [_vp, ctypes.c_int]
     H.fabgpu_test_nym_side_after.restype = None
+    H.fabgpu_test_walk_buffer_caps.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64)]
+    H.fabgpu_test_walk_buffer_caps.restype = None
     H.fabgpu_test_key_table.argtypes = [_vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32), _sz]
     H.fabgpu_test_key_table_host.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32), _sz]
     H.fabgpu_test_gtab_compare_with_host.argtypes = [_vp]
@@ -1236,6 +1238,13 @@ def idfix_probe(csp: "GPUCSP", idents: Sequence[bytes]):
     code, key = np.zeros(n, np.uint8), np.zeros((n, 64), np.uint8)
     _check(load_hooks().fabgpu_csp_idfix_probe(csp._h, n, _p8(arena), arena.size, spans.ctypes.data_as(_u32p), _p8(code), _p8(key)), "fabgpu_csp_idfix_probe")
     return code, key
+
+
+def walk_buffer_caps(csp: "GPUCSP", d: int = 0):
+    """TEST HOOK: capacities (bytes) of the block pass's buffers on the provider's d-th device: env, tuple, pinned, mapped, gather scratch."""
+    out = (ctypes.c_uint64 * 5)()
+    load_hooks().fabgpu_test_walk_buffer_caps(csp._L.fabgpu_csp_ctx_of(csp._h, d), out)
+    return dict(zip(("env", "tup", "pin", "map", "gscr"), (int(v) for v in out)))
 
 
 def gate_probe(csp: "GPUCSP", sigs: Sequence[bytes]):

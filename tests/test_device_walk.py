@@ -646,6 +646,36 @@ def test_memo_built_by_the_device_equals_the_memo_seeded_on_the_host(csp, monkey
 
 
 @pytest.mark.gpu
+def test_a_block_of_the_preallocated_size_grows_no_buffer():
+    """ProviderOptions::concurrent_passes makes the pass's buffers when the provider is made, at the largest layout a pass of
+    expect_tuples tuples can have (walk_layout.h walk_worst_case).  A memo-seeding device-route pass over a block AT that size - 511 of
+    512 tuples, every kind of envelope the generator knows - answers like the host route and leaves all five capacities (per-envelope,
+    per-tuple, pinned, mapped, gather scratch) as they were: nothing was allocated inside the pass."""
+    rng = np.random.default_rng(57)
+    blk, want = build_block(147, rng)
+    assert fabgpu.block_parse(blk)["n_tuples"] == 511                       # as close below 512 as the generator's four tuples per transaction give
+    csp = fabgpu.GPUCSP(devices=[0], concurrent_passes=1, expect_tuples=512)    # Preallocate: n_tx = max(1024, 512 / 3)
+    try:
+        caps = fabgpu.walk_buffer_caps(csp)
+        assert all(v > 0 for v in caps.values()), caps
+        csp.set_option("pass_device_memo", 1)
+        csp.set_option("pass_stage_min_bytes", 1)
+        before = fabgpu.pass_routes(csp)
+        dev = fabgpu.preverify_block2(csp, blk, block_seq=10, seed_memo=True)
+        assert fabgpu.pass_routes(csp)["device_walks"] - before["device_walks"] == 1
+        assert fabgpu.walk_buffer_caps(csp) == caps
+        assert (dev["tx_flags"] == want).all() and len(dev["tuple_status"]) == 511 and dev["memo_seeded"] > 300
+        csp.set_option("pass_stage_min_bytes", 1 << 40)
+        host = fabgpu.preverify_block2(csp, blk, block_seq=11, seed_memo=True)
+        assert fabgpu.pass_routes(csp)["device_walks"] - before["device_walks"] == 1
+        _same(dev, host, KEYS_ALL)
+        assert dev["memo_seeded"] == host["memo_seeded"]
+        assert fabgpu.walk_buffer_caps(csp) == caps
+    finally:
+        csp.close()
+
+
+@pytest.mark.gpu
 def test_memo_of_a_block_whose_signatures_are_far_longer_than_usual(csp, monkeypatch):
     """The memo's keys travel to the host ahead of the verdicts into room sized for ordinary signatures (96 bytes each on average).  A
     block whose every signature drags 600 bytes behind its SEQUENCE - accepted by the reference, still VALID (bccsp/utils/ecdsa.go:43-67:
