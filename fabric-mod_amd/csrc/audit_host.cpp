@@ -1,13 +1,17 @@
-// CPU audit of device results (audit_host.h): SHA-256 in plain C++, SHA3-256 through sha3_256.h, ECDSA P-256 verification through the kernels' own one-lane header
-// code compiled for the host.  Linked into libfabgpu.so; nothing here touches a device.
+// CPU audit of device results (audit_host.h): SHA-256 in plain C++, SHA3-256 through sha3_256.h, ECDSA P-256 verification and idemix
+// pseudonym-signature verification through the kernels' own one-lane header code compiled for the host.  Linked into libfabgpu.so;
+// nothing here touches a device.
 #include "audit_host.h"
 
 #include <string.h>
 
+#include <memory>
 #include <mutex>
 #include <vector>
 
 #include "bccsp_host.h"
+#include "bn_tables29.h"
+#include "idemix_host.h"
 #include "p256_tables29.h"
 #include "sha3_256.h"
 
@@ -132,6 +136,132 @@ bool audit_p256_verify(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* 
     from_be32(r, r32);
     from_be32(s, s32);
     return verify_core(qx, qy, e, r, s) == ST_VALID;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Idemix pseudonym signature (idemix/nymsignature.go:74-109) on FP256BN's G1
+// ------------------------------------------------------------------------------------------------
+namespace {
+// The 8-bit combs of one issuer's HSk and HRand (what fabgpu_idemix_issuer_register puts on the device), built at the issuer's first
+// audit.  A peer has a handful of idemix MSPs: the last kIssuerTabs issuers are kept, the least recently used one goes first.
+struct IssuerCombs {
+    uint8_t bases[128];                      // hsk_x || hsk_y || hrand_x || hrand_y
+    std::vector<int32_t> hsk, hrand;
+    bool usable = false;                     // both bases are points of G1 with coordinates below p
+    uint64_t used = 0;
+};
+constexpr size_t kIssuerTabs = 8;
+
+bool bn_base_ok(const u256& x, const u256& y) {
+    const u256 P = FAB_BN_P;
+    if (!(lt256(x, P) & lt256(y, P))) return false;
+    fbn mx, my;
+    fe_to_mont(mx, x);
+    fe_to_mont(my, y);
+    return bn_on_curve29(mx, my);
+}
+
+std::shared_ptr<const IssuerCombs> issuer_combs(const uint8_t* hsk_x32, const uint8_t* hsk_y32, const uint8_t* hrand_x32, const uint8_t* hrand_y32) {
+    static std::mutex mu;
+    static std::vector<std::shared_ptr<IssuerCombs>> held;
+    static uint64_t tick = 0;
+    uint8_t bases[128];
+    memcpy(bases, hsk_x32, 32);
+    memcpy(bases + 32, hsk_y32, 32);
+    memcpy(bases + 64, hrand_x32, 32);
+    memcpy(bases + 96, hrand_y32, 32);
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto& c : held)
+            if (!memcmp(c->bases, bases, 128)) {
+                c->used = ++tick;
+                return c;
+            }
+    }
+    // built outside the lock (6 ms a base); two threads that meet a new issuer at once both build, one copy stays
+    std::shared_ptr<IssuerCombs> c(new IssuerCombs);
+    memcpy(c->bases, bases, 128);
+    u256 sx, sy, rx, ry;
+    from_be32(sx, hsk_x32);
+    from_be32(sy, hsk_y32);
+    from_be32(rx, hrand_x32);
+    from_be32(ry, hrand_y32);
+    c->usable = bn_base_ok(sx, sy) && bn_base_ok(rx, ry);
+    if (c->usable) {
+        c->hsk.resize(KeyTab8::TABLE_WORDS);
+        c->hrand.resize(KeyTab8::TABLE_WORDS);
+        build_bn_comb_table8(c->hsk.data(), sx, sy);
+        build_bn_comb_table8(c->hrand.data(), rx, ry);
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& o : held)
+        if (!memcmp(o->bases, bases, 128)) return o;
+    c->used = ++tick;
+    if (held.size() >= kIssuerTabs) {
+        size_t oldest = 0;
+        for (size_t i = 1; i < held.size(); i++)
+            if (held[i]->used < held[oldest]->used) oldest = i;
+        held[oldest] = c;
+    } else {
+        held.push_back(c);
+    }
+    return c;
+}
+
+// HashModOrder (idemix/util.go:46-51): SHA-256 of the bytes as a big-endian number, mod the group order
+void hash_mod_order(u256& out, const uint8_t* data, size_t len) {
+    uint8_t dg[32];
+    audit_sha256(data, len, dg);
+    u256 x;
+    from_be32(x, dg);
+    bn_mod_order(out, x);
+}
+}  // namespace
+
+bool audit_nym_verify(const uint8_t* hsk_x32, const uint8_t* hsk_y32, const uint8_t* hrand_x32, const uint8_t* hrand_y32, const uint8_t* ipk_hash32,
+                      const uint8_t* nym_x32, const uint8_t* nym_y32, const uint8_t* sig, size_t siglen, const uint8_t* msg, size_t msglen) {
+    if (!hsk_x32 || !hsk_y32 || !hrand_x32 || !hrand_y32 || !ipk_hash32 || !nym_x32 || !nym_y32) return false;
+    if (!sig || siglen == 0 || (msglen && !msg)) return false;                             // handlers/nymsigner.go:78-80
+    NymSignatureFields sf;
+    if (!UnmarshalNymSignature(sig, siglen, sf)) return false;
+    for (int k = 0; k < 4; k++)
+        if (sf.len[k] != 32) return false;                                                 // (FP256BN.FromBytes reads exactly 32 bytes)
+    const std::shared_ptr<const IssuerCombs> combs = issuer_combs(hsk_x32, hsk_y32, hrand_x32, hrand_y32);
+    if (!combs->usable) return false;                                                      // (the device registers no such issuer)
+    const KeyTab8 hsk{combs->hsk.data()}, hrand{combs->hrand.data()};
+    u256 nx, ny, c, s_sk, s_rnym, tx, ty;
+    from_be32(nx, nym_x32);
+    from_be32(ny, nym_y32);
+    from_be32(c, sf.f[0]);
+    from_be32(s_sk, sf.f[1]);
+    from_be32(s_rnym, sf.f[2]);
+    LocalQTab<fbn> qtab;
+    // t = HSk s_sk + HRand s_rnym - Nym c; anything but NYM_VALID: c >= r (never equal to a reduced value), or outside the domain the
+    // provider decides (pseudonym off the curve or >= p, s-value >= r, t at infinity) - never handed out as "valid"
+    if (bn_nym_commitment29(tx, ty, nx, ny, c, s_sk, s_rnym, hsk, hrand, qtab) != NYM_VALID) return false;
+    // c' = HashModOrder("sign" || G1(t) || G1(nym) || ipk.Hash || msg)     (idemix/nymsignature.go:90-101; appendBytesG1 is ECP.ToBytes
+    // uncompressed: 0x04 || x || y, appendBytesBig 32 bytes big-endian - idemix/util.go:57-61, 79-83)
+    std::vector<uint8_t> data(4 + 65 + 65 + 32 + msglen);
+    uint8_t* p = data.data();
+    memcpy(p, "sign", 4);
+    p[4] = 0x04;
+    to_be32(p + 5, tx);
+    to_be32(p + 37, ty);
+    p[69] = 0x04;
+    memcpy(p + 70, nym_x32, 32);            // (both below p: the big-endian bytes of the reduced coordinates are the caller's)
+    memcpy(p + 102, nym_y32, 32);
+    memcpy(p + 134, ipk_hash32, 32);
+    if (msglen) memcpy(p + 166, msg, msglen);
+    u256 c1, c2;
+    hash_mod_order(c1, data.data(), data.size());
+    // accept iff ProofC == HashModOrder(c' || Nonce)                       (idemix/nymsignature.go:102-104)
+    uint8_t two[64];
+    to_be32(two, c1);
+    memcpy(two + 32, sf.f[3], 32);
+    hash_mod_order(c2, two, 64);
+    uint8_t c2b[32];
+    to_be32(c2b, c2);
+    return memcmp(c2b, sf.f[0], 32) == 0;
 }
 
 }  // namespace bccsp

@@ -636,8 +636,13 @@ int fabgpu_csp_idemix_nym_verify_batch(fabgpu_csp* csp, int64_t issuer_id, size_
         valid[i] = res[i].valid ? 1 : 0;
         flags[i] = res[i].needs_sw ? 1 : 0;
         put_err(errs + i * errstride, errstride, key_ok[i] ? (res[i].err.ok() ? "" : res[i].err.msg) : import_err[i]);
-        if (valid[i]) csp->csp->NoteUnauditedNym(1);        // no host FP256BN verification: counted, so that the gap shows
+        // a sampled "valid" is verified again on the CPU (a valid item passed NymVerifyBatch's gates: its key is 64 bytes)
+        if (valid[i] && !csp->csp->AuditNymDirect(issuer_id, keys[i].x, keys[i].y, items[i].sig, items[i].siglen, items[i].digest, items[i].dlen)) {
+            valid[i] = 0;
+            put_err(errs + i * errstride, errstride, GPUCSP::PoisonedText());
+        }
     }
-    return FABGPU_OK;
+    // (an item whose audit failed carries PoisonedText instead of "valid"; the whole answer is then not to be used)
+    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
 }
 }  // extern "C"

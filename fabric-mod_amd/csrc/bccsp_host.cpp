@@ -552,8 +552,17 @@ int64_t GPUCSP::ImportIdemixIssuer(const uint8_t* ipk_raw, size_t len, std::stri
             if (g > 0 && e.ok()) pending_issuers_.emplace_back((const char*)ipk_raw, len);
             return -1;
         }
-        if (g == 0) id = k.issuer_id;
-        else if (k.issuer_id != id) {
+        if (g == 0) {
+            id = k.issuer_id;
+            AuditIssuer a;                                     // the pseudonym audit verifies under the same fields, on the host
+            memcpy(a.data(), k.hsk_x, 32);
+            memcpy(a.data() + 32, k.hsk_y, 32);
+            memcpy(a.data() + 64, k.hrand_x, 32);
+            memcpy(a.data() + 96, k.hrand_y, 32);
+            memcpy(a.data() + 128, k.hash, 32);
+            std::lock_guard<std::mutex> alk(audit_issuer_mu_);
+            audit_issuers_[id] = a;
+        } else if (k.issuer_id != id) {
             // ids are handed out in order per context: once they differ they differ for every later issuer too.  Nothing to replay -
             // every device HAS the key - but it is counted and said once, and the issuer is not accelerated (bccsp/idemix serves it).
             reg_id_mismatches_.fetch_add(1, std::memory_order_relaxed);
@@ -994,7 +1003,7 @@ inline void prefetch_span(const uint8_t* p, size_t n) {
 }  // namespace
 
 int GPUCSP::MemoFind(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, uint8_t* status,
-                     const uint8_t* issuer_hash32, uint64_t* seq, uint32_t* entry) const {
+                     const uint8_t* issuer_hash32, uint64_t* seq, uint32_t* entry, NymCapture* nym) const {
     if (!qx32 || !qy32 || !sig || !digest || siglen == 0 || dlen == 0 || siglen > 1024 || dlen > 1024) return 1;
     uint8_t key[1 + 32 + 64 + 8 + 2048];
     const size_t kl = MemoKeyBytes(siglen, dlen, issuer_hash32 != nullptr);
@@ -1013,6 +1022,31 @@ int GPUCSP::MemoFind(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* si
         t_hint.gen = bm.gen;
         t_hint.entry = e - 1;
         memo_hits_.add(1);
+        // A pseudonym hit the audit samples: the proof hashes the message itself, and the caller holds only its digest - the message is
+        // the entry's two spans in the block copy the digest memo keeps (the creator's Envelope.payload), copied while the lock is held.
+        if (nym && audit_sample_nym_.hit(AuditPermille())) {
+            nym->sampled = true;
+            if (bm.hspans_v && bm.copy.p) {
+                const uint32_t* sp = bm.hspans_v + 4 * (size_t)(e - 1);
+                auto resolve = [&](uint32_t off, uint32_t l) -> const uint8_t* {
+                    if ((uint64_t)off + l <= bm.copy.len) return bm.copy.p + off;
+                    if (bm.tail_base && off >= bm.tail_base && (uint64_t)(off - bm.tail_base) + l <= bm.tail.size()) return bm.tail.data() + (off - bm.tail_base);
+                    return nullptr;
+                };
+                const uint8_t* a = resolve(sp[0], sp[1]);
+                const uint8_t* b = resolve(sp[2], sp[3]);
+                if (a && b && (uint64_t)sp[1] + sp[3] != 0) {                // (spans left at zero: the entry remembers no message)
+                    try {
+                        nym->msg.reserve((size_t)sp[1] + sp[3]);
+                        nym->msg.assign(a, a + sp[1]);
+                        nym->msg.insert(nym->msg.end(), b, b + sp[3]);
+                        nym->held = true;
+                    } catch (...) {                                          // bad_alloc: counted as not auditable
+                        nym->held = false;
+                    }
+                }
+            }
+        }
         // What this thread will most likely ask next is Hash of the NEXT entry's message: its bytes in the block's host copy, its digest
         // and its key are requested now, so that they travel while the validator builds that message (append(prp, endorser...)) instead of
         // one DRAM round trip after the other inside the comparison.  (Entry e, 0-based, is the next one; its spans share a cache line
@@ -1162,8 +1196,40 @@ bool GPUCSP::Poisoned(std::string* why) const {
 void GPUCSP::AuditStats(uint64_t out[AUDIT_STATS]) const {
     for (int i = 0; i < AUDIT_STATS; i++) out[i] = audit_count_[i].load(std::memory_order_relaxed);
 }
-void GPUCSP::NoteUnauditedNym(uint64_t n) const {
-    if (n && AuditPermille()) audit_count_[AUDIT_SKIPPED_NYM].fetch_add(n, std::memory_order_relaxed);
+bool GPUCSP::AuditIssuerById(int64_t issuer_id, AuditIssuer& out) const {
+    std::lock_guard<std::mutex> lk(audit_issuer_mu_);
+    auto it = audit_issuers_.find(issuer_id);
+    if (it == audit_issuers_.end()) return false;
+    out = it->second;
+    return true;
+}
+bool GPUCSP::AuditIssuerByHash(const uint8_t* hash32, AuditIssuer& out) const {
+    std::lock_guard<std::mutex> lk(audit_issuer_mu_);
+    for (const auto& kv : audit_issuers_)                                   // (a peer's idemix MSPs: a handful)
+        if (!memcmp(kv.second.data() + 128, hash32, 32)) {
+            out = kv.second;
+            return true;
+        }
+    return false;
+}
+bool GPUCSP::AuditNymDirect(int64_t issuer_id, const uint8_t* nym_x32, const uint8_t* nym_y32, const uint8_t* sig, size_t siglen, const uint8_t* msg,
+                            size_t msglen) const {
+    if (!audit_sample_nym_.hit(AuditPermille())) return true;
+    AuditIssuer iss;
+    if (!AuditIssuerById(issuer_id, iss)) {                                 // an issuer the provider did not import itself: counted, handed out
+        audit_count_[AUDIT_SKIPPED_NYM].fetch_add(1, std::memory_order_relaxed);
+        return true;
+    }
+    bool accept;
+    {
+        AuditClock clk{audit_count_[AUDIT_NS]};
+        accept = audit_nym_verify(iss.data(), iss.data() + 32, iss.data() + 64, iss.data() + 96, iss.data() + 128, nym_x32, nym_y32, sig, siglen, msg, msglen);
+    }
+    audit_count_[AUDIT_NYM].fetch_add(1, std::memory_order_relaxed);
+    if (accept) return true;
+    audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
+    Poison(std::string("pseudonym audit: the device accepted a pseudonym signature in NymVerifier.Verify that the CPU audit rejects (Nym X ") + hex8(nym_x32) + "..)");
+    return false;
 }
 bool GPUCSP::AuditDirect(const ECDSAPublicKey& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
                          const uint8_t* msg, size_t msglen, bool sha3) const {
@@ -1192,9 +1258,40 @@ int GPUCSP::MemoLookup(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* 
     uint64_t seq = 0;
     uint32_t entry = 0;
     uint8_t st = 0xFF;
-    if (MemoFind(qx32, qy32, sig, siglen, digest, dlen, &st, issuer_hash32, &seq, &entry) != 0) return 1;
+    NymCapture nym;
+    if (MemoFind(qx32, qy32, sig, siglen, digest, dlen, &st, issuer_hash32, &seq, &entry, issuer_hash32 && AuditPermille() ? &nym : nullptr) != 0) return 1;
     if (issuer_hash32) {
-        NoteUnauditedNym(1);                                                 // a pseudonym entry: no host FP256BN verification here
+        // a pseudonym entry: first the device's digest over the message the entry remembers, then NymSignature.Ver under the issuer key
+        // the entry is bound to.  No copy of the block, or no fields for that issuer hash: handed out as it is, and counted.
+        AuditIssuer iss;
+        if (!nym.sampled) {                                                  // (not this hit's turn, or auditing is off)
+        } else if (!nym.held || !AuditIssuerByHash(issuer_hash32, iss)) {
+            audit_count_[AUDIT_SKIPPED_NYM].fetch_add(1, std::memory_order_relaxed);
+        } else {
+            uint8_t want[32];
+            bool same_digest, accept = false;
+            {
+                AuditClock clk{audit_count_[AUDIT_NS]};
+                audit_sha256(nym.msg.data(), nym.msg.size(), want);
+                same_digest = dlen == 32 && memcmp(want, digest, 32) == 0;
+                if (same_digest)
+                    accept = audit_nym_verify(iss.data(), iss.data() + 32, iss.data() + 64, iss.data() + 96, iss.data() + 128, qx32, qy32, sig, siglen, nym.msg.data(),
+                                              nym.msg.size());
+            }
+            audit_count_[AUDIT_NYM].fetch_add(1, std::memory_order_relaxed);
+            if (!same_digest) {
+                audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
+                Poison("pseudonym audit: block " + std::to_string(seq) + " entry " + std::to_string(entry) + " holds digest " + hex8(digest) +
+                       ".., the CPU audit computes " + hex8(want) + ".. over the " + std::to_string(nym.msg.size()) + " bytes of the message the entry remembers");
+                return 1;
+            }
+            if (accept != (st == FABGPU_NYM_VALID)) {
+                audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
+                Poison("pseudonym audit: block " + std::to_string(seq) + " entry " + std::to_string(entry) + " holds status " + std::to_string(st) +
+                       ", the CPU audit says " + (accept ? "valid" : "invalid") + " (Nym X " + hex8(qx32) + "..)");
+                return 1;
+            }
+        }
     } else if (audit_sample_[AUDIT_VERDICT].hit(AuditPermille())) {
         bool accept;
         {

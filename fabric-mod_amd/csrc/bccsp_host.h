@@ -282,14 +282,20 @@ class GPUCSP {
     // answers of the direct calls is re-computed on the calling thread before it is returned.  The first disagreement poisons the
     // provider: one flag for every context of the pool and every thread, never cleared.  From then on every lookup misses, every
     // verify / identity / nym / hash / block-pass entry of the C surface answers FABGPU_EPOISONED without launching anything, and a
-    // pass already in flight finishes but publishes no memo table.  Idemix pseudonym entries are not audited (no host FP256BN
-    // verification here): they are counted in AuditStats instead.
-    enum : int { AUDIT_DIGEST = 0, AUDIT_VERDICT = 1, AUDIT_DIRECT = 2, AUDIT_MISMATCHES = 3, AUDIT_SKIPPED_NYM = 4, AUDIT_NS = 5, AUDIT_STATS = 6 };
+    // pass already in flight finishes but publishes no memo table.  Idemix pseudonym results are a sampled kind of their own
+    // (audit_nym_verify): the hits of MemoLookup for pseudonym entries - the message is the span the entry remembers in the block copy
+    // the digest memo holds, checked against the digest first - and the "valid" answers of the nym batch (AuditNymDirect).  A sampled
+    // pseudonym result that cannot be audited (the block copy is gone or was never kept, the issuer's fields are not at hand) is handed
+    // out as it is and counted in AUDIT_SKIPPED_NYM.
+    enum : int { AUDIT_DIGEST = 0, AUDIT_VERDICT = 1, AUDIT_DIRECT = 2, AUDIT_MISMATCHES = 3, AUDIT_SKIPPED_NYM = 4, AUDIT_NS = 5, AUDIT_NYM = 6, AUDIT_STATS = 7 };
     void Poison(const std::string& why) const;                 // the first reason is kept
     bool Poisoned(std::string* why = nullptr) const;
     void AuditStats(uint64_t out[AUDIT_STATS]) const;
     static const char* PoisonedText();                         // the error text of an item whose audit failed
-    void NoteUnauditedNym(uint64_t n) const;                   // pseudonym results handed out while auditing is on
+    // true: the device's "valid" for this pseudonym signature stands (not sampled, not auditable, or the CPU agrees); false: the
+    // provider is now poisoned.  issuer_id: what ImportIdemixIssuer answered; msg: the message itself.
+    bool AuditNymDirect(int64_t issuer_id, const uint8_t* nym_x32, const uint8_t* nym_y32, const uint8_t* sig, size_t siglen, const uint8_t* msg,
+                        size_t msglen) const;
     fabgpu_ctx* ctx() const { return devs_[0]->ctx; }          // the first context (tests, single-device callers)
     // the context a flat batch (Verify / VerifyBatch / IdentityVerifyBatch / a coalesced launch) runs on: round the ring
     fabgpu_ctx* flat_ctx() const { return devs_[flat_rr_.fetch_add(1, std::memory_order_relaxed) % devs_.size()]->ctx; }
@@ -300,8 +306,14 @@ class GPUCSP {
     friend struct TestAccess;                               // testhooks.cpp (libfabgpu_testhooks.so): edits a memo table to show that the audit sees it
     // the lookups proper (shared lock inside); the public entries check the poison flag and audit a sampled hit after the lock is gone.
     // A hit names its table and entry for the audit's report.
+    // nym != nullptr (a pseudonym lookup while auditing is on): a hit asks the pseudonym sampler, and a sampled one leaves here, copied
+    // under the lock, the message its entry remembers - the spans may be gone the moment the lock is (MemoEvictBlock).
+    struct NymCapture {
+        bool sampled = false, held = false;                    // held: the block copy and the entry's spans were there
+        std::vector<uint8_t> msg;
+    };
     int MemoFind(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, uint8_t* status,
-                 const uint8_t* issuer_hash32, uint64_t* seq, uint32_t* entry) const;
+                 const uint8_t* issuer_hash32, uint64_t* seq, uint32_t* entry, NymCapture* nym = nullptr) const;
     int HashFind(const uint8_t* msg, size_t len, uint8_t* digest32, uint64_t* seq, uint32_t* entry) const;
     uint32_t AuditPermille() const { return audit_permille_.load(std::memory_order_relaxed); }
     // true: the device's "valid" for this signature stands (not sampled, or the CPU agrees); false: the provider is now poisoned.
@@ -315,6 +327,13 @@ class GPUCSP {
     mutable std::atomic<bool> poisoned_{false};
     struct alignas(64) HitCounter : AuditSampler {};
     mutable HitCounter audit_sample_[3];                    // one hit counter per audited kind (AUDIT_DIGEST / _VERDICT / _DIRECT)
+    mutable HitCounter audit_sample_nym_;                   // ... and the pseudonym results' (memo hits and "valid" batch answers)
+    // what the pseudonym audit needs of every issuer ImportIdemixIssuer put on the devices: hsk_x || hsk_y || hrand_x || hrand_y || hash
+    typedef std::array<uint8_t, 160> AuditIssuer;
+    mutable std::mutex audit_issuer_mu_;                    // (a leaf: nothing is taken under it)
+    mutable std::map<int64_t, AuditIssuer> audit_issuers_;
+    bool AuditIssuerById(int64_t issuer_id, AuditIssuer& out) const;
+    bool AuditIssuerByHash(const uint8_t* hash32, AuditIssuer& out) const;
     alignas(64) mutable std::atomic<uint64_t> audit_count_[AUDIT_STATS] = {};   // (written by audits only)
     alignas(64) mutable std::mutex poison_mu_;
     mutable std::string poison_why_;

@@ -66,9 +66,14 @@ uint64_t fabgpu_identity_table_hash(const uint8_t* p, size_t len);
 void fabgpu_test_audit_sha256(const uint8_t* msg, size_t len, uint8_t* out32);
 int fabgpu_test_audit_p256_verify(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig_der, size_t siglen, const uint8_t* digest, size_t dlen);
 long long fabgpu_test_audit_sample(uint32_t permille, uint32_t n_hits, uint8_t* audited);
+/* ... and its NymVerifier.Verify over an issuer's HSk, HRand and Hash (32-byte halves), a pseudonym, a marshalled idemix.NymSignature and
+ * the message (1 accept, 0 reject) */
+int fabgpu_test_audit_nym_verify(const uint8_t* hsk_x32, const uint8_t* hsk_y32, const uint8_t* hrand_x32, const uint8_t* hrand_y32, const uint8_t* ipk_hash32,
+                                 const uint8_t* nym_x32, const uint8_t* nym_y32, const uint8_t* sig, size_t siglen, const uint8_t* msg, size_t msglen);
 /* TEST HOOK: corrupts one entry of the memo table published under block_seq - host memory of the library, nothing is launched.  kind 0
- * flips one bit of the index-th stored digest, kind 1 toggles the index-th stored status between valid and bad-signature.
- * 0 done, 1 nothing to corrupt (no such table, no digest memo, a status that is neither), FABGPU_EINVAL. */
+ * flips one bit of the index-th stored digest, kind 1 toggles the index-th stored status between valid and bad-signature (a pseudonym
+ * entry's: between valid and proof-invalid), kind 2 flips one bit of the first byte of the message the index-th entry remembers, in the
+ * held copy of the block.  0 done, 1 nothing to corrupt (no such table, no digest memo / no held copy, a status that is neither), FABGPU_EINVAL. */
 int fabgpu_csp_test_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, int kind, uint32_t index);
 /* TEST HOOK: the allocator of key slots and ids by itself (csrc/key_slots.h; no device, no context).  gen_last: the last generation a
  * slot may reach (0xFFFFF in the product).  register: the id of the next registration, or -1 when no slot can be had; a lowest slot

@@ -36,8 +36,18 @@ struct TestAccess {
             if (kind == 1) {
                 uint8_t* st = const_cast<uint8_t*>(bm.status_v) + index;
                 if (*st != FABGPU_ST_VALID && *st != FABGPU_ST_BAD_MATH) return 1;              // neither valid nor bad-signature: left alone
-                *st = *st == FABGPU_ST_VALID ? FABGPU_ST_BAD_MATH : FABGPU_ST_VALID;
+                *st = *st == FABGPU_ST_VALID ? FABGPU_ST_BAD_MATH : FABGPU_ST_VALID;   // (a pseudonym entry: FABGPU_NYM_VALID <-> _BAD_PROOF, the same two values)
                 return FABGPU_OK;
+            }
+            if (kind == 2) {                                                                     // one byte of the message the entry remembers, in the held block copy
+                if (!bm.hspans_v || !bm.copy.p) return 1;                                        // the block's copy is not held
+                const uint32_t* sp = bm.hspans_v + 4 * (size_t)index;
+                for (int k = 0; k < 2; k++)
+                    if (sp[2 * k + 1] && (uint64_t)sp[2 * k] + sp[2 * k + 1] <= bm.copy.len) {
+                        const_cast<uint8_t*>(bm.copy.p)[sp[2 * k]] ^= 0x01;
+                        return FABGPU_OK;
+                    }
+                return 1;                                                                        // the entry's message does not lie in the copy
             }
             return FABGPU_EINVAL;
         }
@@ -280,11 +290,15 @@ int fabgpu_csp_gate_probe(fabgpu_csp* csp, uint32_t n, const uint8_t* arena, siz
 // TEST HOOK (pure host): the table hash of identity bytes (block_walk_core.h id_hash_host)
 uint64_t fabgpu_identity_table_hash(const uint8_t* p, size_t len) { return walk::id_hash_host(p, (uint32_t)len); }
 
-// TEST HOOKS (pure host): the provider's CPU audit (audit_host.h) - its SHA-256, its bccsp.Verify (1 accept, 0 reject), and its
+// TEST HOOKS (pure host): the provider's CPU audit (audit_host.h) - its SHA-256, its bccsp.Verify and its NymVerifier.Verify (1 accept, 0 reject), and its
 // sampling rule run over n_hits simulated hits of one counter (audited[h - 1] = 1 where hit h is audited; returns how many are)
 void fabgpu_test_audit_sha256(const uint8_t* msg, size_t len, uint8_t* out32) { audit_sha256(msg, len, out32); }
 int fabgpu_test_audit_p256_verify(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig_der, size_t siglen, const uint8_t* digest, size_t dlen) {
     return audit_p256_verify(qx32, qy32, sig_der, siglen, digest, dlen) ? 1 : 0;
+}
+int fabgpu_test_audit_nym_verify(const uint8_t* hsk_x32, const uint8_t* hsk_y32, const uint8_t* hrand_x32, const uint8_t* hrand_y32, const uint8_t* ipk_hash32,
+                                 const uint8_t* nym_x32, const uint8_t* nym_y32, const uint8_t* sig, size_t siglen, const uint8_t* msg, size_t msglen) {
+    return audit_nym_verify(hsk_x32, hsk_y32, hrand_x32, hrand_y32, ipk_hash32, nym_x32, nym_y32, sig, siglen, msg, msglen) ? 1 : 0;
 }
 long long fabgpu_test_audit_sample(uint32_t permille, uint32_t n_hits, uint8_t* audited) {
     AuditSampler s;
@@ -298,7 +312,9 @@ long long fabgpu_test_audit_sample(uint32_t permille, uint32_t n_hits, uint8_t* 
 }
 // TEST HOOK: corrupts one entry of the memo table published under block_seq, in the library's host memory (nothing is launched):
 // kind 0 flips one bit of the index-th stored digest (what fabgpu_csp_hash_lookup hands out), kind 1 toggles the index-th stored status
-// between valid and bad-signature (what fabgpu_csp_memo_lookup hands out).  0 done, 1 nothing to corrupt there, FABGPU_EINVAL.
+// between valid and bad-signature (what fabgpu_csp_memo_lookup hands out; for a pseudonym entry: valid and proof-invalid, what
+// fabgpu_csp_memo_lookup_nym hands out), kind 2 flips one bit of the first byte of the message the index-th entry remembers, in the block
+// copy the digest memo holds (what the pseudonym audit verifies over).  0 done, 1 nothing to corrupt there, FABGPU_EINVAL.
 int fabgpu_csp_test_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, int kind, uint32_t index) {
     if (!csp) return FABGPU_EINVAL;
     return TestAccess::memo_corrupt(*csp->csp, block_seq, kind, index);

@@ -147,7 +147,7 @@ HOOK_SYMBOLS = [
     "fabgpu_synth_batch", "fabgpu_last_kernel_ms", "fabgpu_csp_block_walk_compare", "fabgpu_block_walk_twopass_compare", "fabgpu_gate_sig_fast",
     "fabgpu_gate_sig_any", "fabgpu_csp_idfix_probe", "fabgpu_csp_gate_probe", "fabgpu_identity_table_hash", "fabgpu_test_nym_side_after",
     "fabgpu_test_key_table", "fabgpu_test_key_table_host", "fabgpu_test_gtab_compare_with_host", "fabgpu_test_key_tables16",
-    "fabgpu_test_audit_sha256", "fabgpu_test_audit_p256_verify", "fabgpu_test_audit_sample", "fabgpu_csp_test_memo_corrupt",
+    "fabgpu_test_audit_sha256", "fabgpu_test_audit_p256_verify", "fabgpu_test_audit_nym_verify", "fabgpu_test_audit_sample", "fabgpu_csp_test_memo_corrupt",
     "fabgpu_test_key_slots_new", "fabgpu_test_key_slots_free", "fabgpu_test_key_slots_register", "fabgpu_test_key_slots_retire",
     "fabgpu_test_key_slots_drain", "fabgpu_test_key_slots_stats", "fabgpu_test_walk_buffer_caps",
 ]
@@ -194,6 +194,7 @@ def load_hooks():
     H.fabgpu_test_audit_sha256.argtypes = [ctypes.c_char_p, _sz, ctypes.c_char_p]
     H.fabgpu_test_audit_sha256.restype = None
     H.fabgpu_test_audit_p256_verify.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz]
+    H.fabgpu_test_audit_nym_verify.argtypes = [ctypes.c_char_p] * 8 + [_sz, ctypes.c_char_p, _sz]
     H.fabgpu_test_audit_sample.argtypes = [ctypes.c_uint32, ctypes.c_uint32, _u8p]
     H.fabgpu_test_audit_sample.restype = ctypes.c_longlong
     H.fabgpu_csp_test_memo_corrupt.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32]
@@ -876,12 +877,13 @@ class GPUCSP:
         return (why.value.decode() or "poisoned") if rc else None
 
     def audit_stats(self) -> dict:
-        """Counters of the CPU audit (audit_permille): audits per kind, mismatches, pseudonym results handed out unaudited, time spent."""
-        v = (ctypes.c_uint64 * 6)()
-        n = self._L.fabgpu_csp_audit_stats(self._h, v, 6)
-        if n != 6:
+        """Counters of the CPU audit (audit_permille): audits per kind (nym_audits: idemix pseudonym results), mismatches, sampled
+        pseudonym results that could not be audited (skipped_nym), time spent."""
+        v = (ctypes.c_uint64 * 7)()
+        n = self._L.fabgpu_csp_audit_stats(self._h, v, 7)
+        if n != 7:
             raise FabgpuError("fabgpu_csp_audit_stats: %s" % strerror(n))
-        return dict(zip(("digest_audits", "verdict_audits", "direct_audits", "mismatches", "skipped_nym", "audit_ns"), (int(x) for x in v)))
+        return dict(zip(("digest_audits", "verdict_audits", "direct_audits", "mismatches", "skipped_nym", "audit_ns", "nym_audits"), (int(x) for x in v)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1280,6 +1282,16 @@ def audit_p256_verify(qx32: bytes, qy32: bytes, sig: bytes, digest: bytes) -> bo
     return bool(load_hooks().fabgpu_test_audit_p256_verify(qx32, qy32, sig, len(sig), digest, len(digest)))
 
 
+def audit_nym_verify(hsk_xy: Tuple[bytes, bytes], hrand_xy: Tuple[bytes, bytes], ipk_hash32: bytes, nym_x32: bytes, nym_y32: bytes, sig: bytes, msg: bytes) -> bool:
+    """TEST HOOK (pure host): NymVerifier.Verify(nym, sig, msg) under an issuer's HSk, HRand and Hash (32-byte halves) as the provider's
+    CPU audit decides it - True only for nil.  sig: the marshalled idemix.NymSignature."""
+    for b in (*hsk_xy, *hrand_xy, ipk_hash32, nym_x32, nym_y32):
+        if len(b) != 32:
+            raise ValueError("32-byte fields")
+    return bool(load_hooks().fabgpu_test_audit_nym_verify(hsk_xy[0], hsk_xy[1], hrand_xy[0], hrand_xy[1], ipk_hash32, nym_x32, nym_y32, bytes(sig), len(sig),
+                                                          bytes(msg), len(msg)))
+
+
 def audit_sample(permille: int, n_hits: int) -> np.ndarray:
     """TEST HOOK (pure host): which of n_hits consecutive hits of one counter the audit samples (bool per hit, hit 1 first)."""
     a = np.zeros(max(1, n_hits), np.uint8)
@@ -1290,7 +1302,8 @@ def audit_sample(permille: int, n_hits: int) -> np.ndarray:
 
 def memo_corrupt(csp: "GPUCSP", block_seq: int, kind: int, index: int) -> int:
     """TEST HOOK: corrupts entry `index` of the memo table under block_seq in host memory - kind 0 one bit of its stored digest, kind 1
-    its stored status (valid <-> bad signature).  0 done, 1 nothing to corrupt there."""
+    its stored status (valid <-> bad signature; a pseudonym entry's: valid <-> proof invalid), kind 2 one bit of the message the entry
+    remembers in the held copy of the block.  0 done, 1 nothing to corrupt there."""
     rc = load_hooks().fabgpu_csp_test_memo_corrupt(csp._h, block_seq, kind, index)
     if rc < 0:
         raise FabgpuError("fabgpu_csp_test_memo_corrupt: %s" % strerror(rc))

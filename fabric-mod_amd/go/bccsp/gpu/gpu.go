@@ -134,7 +134,8 @@ type Options struct {
 	// AuditPermille (0 .. 1000): the library re-computes this share of the digests and verdicts it is about to hand out from the device
 	// on the CPU first - digest-memo hits, verdict-memo hits of P-256 entries, "valid" answers of the coalesced Verify - and poisons
 	// the provider at the first disagreement (hit h of a kind is audited iff h*permille/1000 != (h-1)*permille/1000: no randomness).
-	// GPUFactory passes 1 unless the operator says otherwise; 0 switches the audit off.  Idemix pseudonym entries are not audited.
+	// GPUFactory passes 1 unless the operator says otherwise; 0 switches the audit off.  Idemix pseudonym results are a sampled kind of
+	// their own (NymAuditStats).
 	AuditPermille int
 	// RetireEvictedKeys: identities the identity cache evicts give their device comb tables up (option "retire_evicted_keys";
 	// KeyTableStats, gauges bccsp_gpu_key_tables).  GPUFactory passes true unless the operator says otherwise.
@@ -366,13 +367,25 @@ func (p *Provider) markPoisoned() {
 }
 
 // AuditStats: what the library's CPU audit has done - audits of digest-memo hits, of verdict-memo hits and of direct calls, mismatches
-// (the first one poisons), pseudonym results handed out unaudited, and the time the audits took on the calling goroutines' threads.
+// (the first one poisons), sampled pseudonym results that could not be audited, and the time the audits took on the calling goroutines'
+// threads.  (The pseudonym audits themselves: NymAuditStats.)
 func (p *Provider) AuditStats() (digest, verdict, direct, mismatches, skippedNym uint64, spent time.Duration) {
 	var v [6]C.uint64_t
 	if C.fabgpu_csp_audit_stats(p.csp, &v[0], 6) != 6 {
 		return
 	}
 	return uint64(v[0]), uint64(v[1]), uint64(v[2]), uint64(v[3]), uint64(v[4]), time.Duration(v[5])
+}
+
+// NymAuditStats: the idemix pseudonym results the CPU audit verified again (memo hits of pseudonym entries and "valid" answers of the
+// nym batch - the library's seventh counter), and the sampled ones it could not audit: the block copy with the message was no longer
+// held, or the issuer's fields were not at hand.
+func (p *Provider) NymAuditStats() (audits, skipped uint64) {
+	var v [7]C.uint64_t
+	if C.fabgpu_csp_audit_stats(p.csp, &v[0], 7) != 7 {
+		return
+	}
+	return uint64(v[6]), uint64(v[4])
 }
 
 // KeyTableStats: the registered keys' tables on device context d - keys live, slots draining behind a retirement, registrations that
@@ -687,6 +700,11 @@ var (
 		Namespace: "fabgpu", Name: "audit_mismatches",
 		Help: "Results of the device that the provider's sampled CPU audit re-computed and found different (the first one poisons the provider)",
 	}
+	auditNymOpts = metrics.GaugeOpts{
+		Namespace: "fabgpu", Name: "audit_pseudonyms",
+		Help: "Idemix pseudonym results and the provider's sampled CPU audit: verified again on the CPU (audited), sampled but not auditable because the block copy or the issuer's fields were not held (skipped)",
+		LabelNames: []string{"what"}, StatsdFormat: "%{#fqname}.%{what}",
+	}
 	keyTablesOpts = metrics.GaugeOpts{
 		Namespace: "bccsp", Subsystem: "gpu", Name: "key_tables",
 		Help: "Comb tables of registered P-256 keys on the first device context: keys live, slots draining behind a retirement, keys retired for evicted identities, registrations that reused a retired slot, slots parked for good, bytes of device memory held",
@@ -703,6 +721,7 @@ type passMetrics struct {
 	tx, sigs, failed metrics.Counter
 	routes, memo     metrics.Gauge
 	auditMismatches  metrics.Counter
+	auditNym         metrics.Gauge
 	poisoned         metrics.Gauge
 	keyTables        metrics.Gauge
 }
@@ -734,6 +753,7 @@ func (p *Provider) RegisterMetrics(mp metrics.Provider, refresh time.Duration) {
 			duration: mp.NewHistogram(passDurationOpts), tx: mp.NewCounter(passTxOpts), sigs: mp.NewCounter(passSigOpts),
 			failed: mp.NewCounter(passFailedOpts), routes: mp.NewGauge(passRouteOpts), memo: mp.NewGauge(memoOpts),
 			auditMismatches: mp.NewCounter(auditMismatchOpts), poisoned: mp.NewGauge(poisonedOpts),
+			auditNym: mp.NewGauge(auditNymOpts),
 			keyTables: mp.NewGauge(keyTablesOpts),
 		}
 		m.poisoned.Set(0)
@@ -781,6 +801,9 @@ func (p *Provider) RegisterMetrics(mp metrics.Provider, refresh time.Duration) {
 					m.auditMismatches.Add(float64(mm - mismatchesSeen))
 					mismatchesSeen = mm
 				}
+				na, ns := p.NymAuditStats()
+				m.auditNym.With("what", "audited").Set(float64(na))
+				m.auditNym.With("what", "skipped").Set(float64(ns))
 				if p.Poisoned() { // (a lookup that met the mismatch only answers "miss": this is where the Go side learns of it)
 					m.poisoned.Set(1)
 				}

@@ -93,7 +93,14 @@ int fabgpu_csp_key_table_stats(fabgpu_csp* csp, int d, uint64_t* out, int cap);
  *   - "valid" answers of fabgpu_csp_verify, _verify_batch, _verify_coalesced, _identity_verify_batch, _identity_verify_coalesced
  *     (the identity calls hash the message again first - with SHA3-256, through the kernels' own sha3_256.h compiled for the host, when
  *     the call's hash family is SHA3).  Rejects are not sampled: the Go side re-checks every reject in bccsp/sw.
- * Idemix pseudonym entries (fabgpu_csp_memo_lookup_nym, fabgpu_csp_idemix_nym_verify_batch) are NOT audited; they are counted.
+ *   - idemix pseudonym results, a kind with a hit counter of its own: NymSignature.Ver (idemix/nymsignature.go:74-109) in host code
+ *     over FP256BN, under the issuer key's HSk, HRand and Hash as the provider imported them.
+ *       fabgpu_csp_idemix_nym_verify_batch: a sampled "valid" is verified again over the caller's message;
+ *       fabgpu_csp_memo_lookup_nym: the caller holds only SHA-256(message) but the proof hashes the message itself, so a sampled hit
+ *       takes the message from the block copy the digest memo holds (the entry remembers its span: the creator's Envelope.payload),
+ *       first checks that its SHA-256 is the digest of the entry, then verifies against stored status 0 / anything else.
+ *     A sampled pseudonym result that cannot be audited - the block copy is no longer held (evicted, or the pool refused the copy), or
+ *     the provider does not have the issuer's fields - is handed out as it is and counted in out[4].
  * Sampling has no randomness: one hit counter per kind, hit number h (1-based) is audited iff h*permille/1000 != (h-1)*permille/1000 -
  * 1000 audits every hit, 250 exactly every fourth, 0 none.
  * The first disagreement POISONS the provider, for good: one flag shared by every context of the pool and every thread.  The lookup
@@ -103,8 +110,9 @@ int fabgpu_csp_key_table_stats(fabgpu_csp* csp, int d, uint64_t* out, int cap);
  * outputs are not to be used); a pass already in flight finishes but seeds no memo; fabgpu_csp_free still works.  The Go provider
  * serves everything from bccsp/sw from then on.
  * fabgpu_csp_poison poisons by hand (why may be NULL); fabgpu_csp_poisoned returns 1 / 0 and the FIRST reason (why may be NULL).
- * fabgpu_csp_audit_stats: out[0] digest audits, [1] verdict audits, [2] direct-call audits, [3] mismatches, [4] pseudonym results
- * handed out unaudited while audit_permille > 0, [5] nanoseconds spent auditing; returns how many were written (cap < 6: the first cap). */
+ * fabgpu_csp_audit_stats: out[0] digest audits, [1] verdict audits, [2] direct-call audits, [3] mismatches, [4] skipped_nym: sampled
+ * pseudonym results that could not be audited, [5] nanoseconds spent auditing, [6] pseudonym audits; returns how many were written
+ * (cap < 7: the first cap - a caller that asks for 6 gets the six values it always got). */
 int fabgpu_csp_poison(fabgpu_csp* csp, const char* why);
 int fabgpu_csp_poisoned(fabgpu_csp* csp, char* why, size_t cap);
 int fabgpu_csp_audit_stats(fabgpu_csp* csp, uint64_t* out, int cap);

@@ -22,9 +22,15 @@
  * What it prints (one JSON line): the pass as the binding calls it (first block of a fresh provider, i.e. over its caps; warm blocks),
  * the validators' CPU residue per block (hashing + memo lookups on T threads), and end-to-end validated tx/s of the two-stage pipeline.
  *
- * usage: go_call_replay [--audit-permille N] <block file> [blocks=12] [validator threads=16] [devices=1] [hash memo=1] [arrivals in flight=1] [blocks pre-verified ahead=arrivals]
+ *   an idemix creator (--idemix-ipk): bccsp/idemixgpu/nymverifier.go Verify - digest = SHA-256(message) as above, then
+ *           fabgpu_csp_memo_lookup_nym(ipk.Hash, Nym.x, Nym.y, sig, digest)    (nil on a valid hit; else bccsp/idemix - counted, not run)
+ *
+ * usage: go_call_replay [--audit-permille N] [--idemix-ipk FILE] <block file> [blocks=12] [validator threads=16] [devices=1] [hash memo=1] [arrivals in flight=1] [blocks pre-verified ahead=arrivals]
  *   --audit-permille N   GPUOpts.AuditPermille (0 .. 1000; here 0 unless given, gpufactory.go defaults to 1): the provider re-computes that
  *                        share of the digests and verdicts it hands out on the CPU first; the line then carries the audit's counters and its time
+ *   --idemix-ipk FILE    the marshalled idemix.IssuerPublicKey of the block's idemix creators (their MSP id is read from the first such
+ *                        creator): registered as fabgpu_csp_idemix_msp_register does at channel set-up; without it idemix creators are
+ *                        left to bccsp/idemix as before
  * Test / bench infrastructure: links the product library through its C ABI only (include/fabgpu*.h) + libcrypto for the CPU SHA-256.
  */
 #define _GNU_SOURCE
@@ -51,11 +57,49 @@ typedef struct {
     uint32_t ident_off, ident_len, pre_off, pre_len, suf_off, suf_len, sig_off, sig_len;
     uint8_t xy[64];
     int has_key;
+    int is_nym;               /* an idemix creator: xy = Nym.x || Nym.y (msp.SerializedIdemixIdentity) */
 } tuple_t;
 
 static fabgpu_csp* g_csp;
 static uint32_t g_cap_tx = 1024; /* gpu.go Provider.capTx */
 static int g_hash_memo = 1;      /* gpu.go Provider.Hash asks the digest memo first (0: round 5's pass-through to bccsp/sw) */
+static uint8_t g_ipk_hash[32];   /* --idemix-ipk: IssuerPublicKey.Hash, what nymverifier.go passes with every lookup */
+static int g_idemix;
+
+/* one length-delimited field of a protobuf message: 1 found (*out, *len), 0 not there / not parseable.  (single-byte tags: fields 1 .. 15) */
+static int pb_field(const uint8_t* b, size_t n, int want, const uint8_t** out, size_t* len) {
+    size_t i = 0;
+    while (i < n) {
+        const uint8_t tag = b[i++];
+        if (tag & 0x80) return 0;
+        uint64_t v = 0;
+        int sh = 0;
+        for (;;) {
+            if (i >= n || sh > 56) return 0;
+            const uint8_t c = b[i++];
+            v |= (uint64_t)(c & 0x7F) << sh;
+            sh += 7;
+            if (!(c & 0x80)) break;
+        }
+        if ((tag & 7) == 0) continue;
+        if ((tag & 7) != 2 || v > n - i) return 0;
+        if ((tag >> 3) == want) { *out = b + i; *len = (size_t)v; return 1; }
+        i += (size_t)v;
+    }
+    return 0;
+}
+/* msp.SerializedIdentity{1 mspid, 2 id_bytes = msp.SerializedIdemixIdentity{1 nym_x, 2 nym_y, ..}} -> Nym.x || Nym.y, the MSP id */
+static int idemix_identity(const uint8_t* id, size_t n, uint8_t* xy, char* mspid, size_t mspid_cap) {
+    const uint8_t *m, *ib, *x, *y;
+    size_t ml, il, xl, yl;
+    if (!pb_field(id, n, 1, &m, &ml) || !pb_field(id, n, 2, &ib, &il) || ml + 1 > mspid_cap) return 0;
+    if (!pb_field(ib, il, 1, &x, &xl) || !pb_field(ib, il, 2, &y, &yl) || xl != 32 || yl != 32) return 0;
+    memcpy(xy, x, 32);
+    memcpy(xy + 32, y, 32);
+    memcpy(mspid, m, ml);
+    mspid[ml] = 0;
+    return 1;
+}
 
 /* gpu.go PreVerifyBlock */
 static int pre_verify_block(const uint8_t* blk, size_t len, uint64_t seq, uint32_t* n_tx, uint32_t* seeded, int* retries) {
@@ -97,7 +141,7 @@ typedef struct {
     const uint32_t* tx_first; /* n_tx + 1: first tuple of each transaction */
     uint32_t n_tx;
     uint32_t next;            /* atomic */
-    uint64_t hits, misses, hashed_bytes, hash_hits, hash_bytes;
+    uint64_t hits, misses, hashed_bytes, hash_hits, hash_bytes, nym_hits, nym_misses;
     int check;                /* also hash every message on the CPU and compare (block 0 only: outside the medians) */
     uint64_t digest_mismatches;
     double t_cat, t_hash, t_memo, t_thread; /* GO_REPLAY_PROFILE: thread-milliseconds in the copy, in Hash, in Verify, in the worker */
@@ -138,7 +182,7 @@ static void* validator(void* arg) {
     }
 }
 static void validate_some(validate_job* j) {
-    uint64_t hits = 0, misses = 0, bytes = 0, hh = 0, hb = 0;
+    uint64_t hits = 0, misses = 0, bytes = 0, hh = 0, hb = 0, nh = 0, nm = 0;
     uint8_t* cat = NULL;
     size_t cat_cap = 0;
     double p_cat = 0, p_hash = 0, p_memo = 0, p0 = g_profile ? now_ms() : 0, pa = 0, pb = 0;
@@ -181,7 +225,10 @@ static void validate_some(validate_job* j) {
             if (g_profile) { pa = now_ms(); p_hash += pa - pb; }
             uint8_t st = 255;
             /* gpu.go Verify: xyOf(k) -> fabgpu_csp_memo_lookup; (true, nil) only on a valid hit */
-            if (tp->has_key && fabgpu_csp_memo_lookup(g_csp, tp->xy, tp->xy + 32, j->blk + tp->sig_off, tp->sig_len, digest, 32, &st) == 0 && st == FABGPU_ST_VALID) hits++;
+            if (tp->is_nym) { /* nymverifier.go Verify: nil only on a valid hit */
+                if (fabgpu_csp_memo_lookup_nym(g_csp, g_ipk_hash, tp->xy, tp->xy + 32, j->blk + tp->sig_off, tp->sig_len, digest, 32, &st) == 0 && st == FABGPU_NYM_VALID) nh++;
+                else nm++; /* -> bccsp/idemix */
+            } else if (tp->has_key && fabgpu_csp_memo_lookup(g_csp, tp->xy, tp->xy + 32, j->blk + tp->sig_off, tp->sig_len, digest, 32, &st) == 0 && st == FABGPU_ST_VALID) hits++;
             else misses++; /* -> bccsp/sw (not run here: the replay is about the path's own cost) */
             if (g_profile) p_memo += now_ms() - pa;
         }
@@ -197,6 +244,8 @@ static void validate_some(validate_job* j) {
     __atomic_fetch_add(&j->hashed_bytes, bytes, __ATOMIC_RELAXED);
     __atomic_fetch_add(&j->hash_hits, hh, __ATOMIC_RELAXED);
     __atomic_fetch_add(&j->hash_bytes, hb, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&j->nym_hits, nh, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&j->nym_misses, nm, __ATOMIC_RELAXED);
 }
 
 /* ---- the arrival goroutine of one block ---- */
@@ -253,16 +302,18 @@ static double median(double* v, int n) {
 
 int main(int argc, char** argv) {
     long audit_permille = 0;
-    for (int i = 1; i + 1 < argc; i++)
-        if (strcmp(argv[i], "--audit-permille") == 0) {       /* taken out of argv: the positional arguments keep their places */
-            audit_permille = atol(argv[i + 1]);
-            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
-            argc -= 2;
-            break;
-        }
+    const char* ipk_path = NULL;
+    for (int i = 1; i + 1 < argc;) {
+        const int ap = strcmp(argv[i], "--audit-permille") == 0, ik = strcmp(argv[i], "--idemix-ipk") == 0;
+        if (!ap && !ik) { i++; continue; }                    /* taken out of argv: the positional arguments keep their places */
+        if (ap) audit_permille = atol(argv[i + 1]);
+        else ipk_path = argv[i + 1];
+        for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+        argc -= 2;
+    }
     if (audit_permille < 0 || audit_permille > 1000) { fprintf(stderr, "--audit-permille takes 0 .. 1000\n"); return 2; }
     if (argc < 2) {
-        fprintf(stderr, "usage: %s [--audit-permille N] <block file> [blocks=12] [validator threads=16] [devices=1] [hash memo=1] [arrivals in flight=1] [window=arrivals]\n", argv[0]);
+        fprintf(stderr, "usage: %s [--audit-permille N] [--idemix-ipk FILE] <block file> [blocks=12] [validator threads=16] [devices=1] [hash memo=1] [arrivals in flight=1] [window=arrivals]\n", argv[0]);
         return 2;
     }
     int n_blocks = argc > 2 ? atoi(argv[2]) : 12, n_thr = argc > 3 ? atoi(argv[3]) : 16, n_dev = argc > 4 ? atoi(argv[4]) : 1;
@@ -296,7 +347,22 @@ int main(int argc, char** argv) {
     uint32_t* sp = (uint32_t*)malloc(32 * (size_t)n_tuples + 32);
     if (fabgpu_block_tuples(blk, len, n_tuples, &n_tuples, tx, kind, sp, NULL, 0, &tail_len, &tail_base) != 0) { fprintf(stderr, "block does not parse\n"); return 2; }
     tuple_t* tuples = (tuple_t*)calloc(n_tuples + 1, sizeof(tuple_t));
-    uint32_t n_env_tuples = 0, n_tx = 0;
+    uint32_t n_env_tuples = 0, n_tx = 0, n_nym = 0;
+    char idemix_mspid[128] = "";
+    uint8_t* ipk = NULL;
+    size_t ipk_len = 0;
+    if (ipk_path) {
+        FILE* kf = fopen(ipk_path, "rb");
+        if (!kf) { perror(ipk_path); return 2; }
+        ipk = (uint8_t*)malloc(1 << 16);
+        ipk_len = fread(ipk, 1, 1 << 16, kf);
+        fclose(kf);
+        const uint8_t* h;
+        size_t hl;
+        if (!pb_field(ipk, ipk_len, 10, &h, &hl) || hl != 32) { fprintf(stderr, "%s: no 32-byte Hash field\n", ipk_path); return 2; }
+        memcpy(g_ipk_hash, h, 32);
+        g_idemix = 1;
+    }
     for (uint32_t i = 0; i < n_tuples; i++) {
         if (kind[i] == 2) continue; /* orderer block signatures: MCS.VerifyBlock ran before AddPayload (internal/peer/gossip/mcs.go) */
         tuple_t* t = &tuples[n_env_tuples++];
@@ -321,6 +387,15 @@ int main(int argc, char** argv) {
         }
         t->has_key = memo[found].ok;
         memcpy(t->xy, memo[found].xy, 64);
+        /* an idemix creator: every one has a pseudonym of its own (nothing to remember); the MSP id of the first is the one registered */
+        if (g_idemix && !t->has_key && t->kind == 0) {
+            char mspid[128];
+            if (idemix_identity(blk + t->ident_off, t->ident_len, t->xy, mspid, sizeof(mspid)) && (!idemix_mspid[0] || !strcmp(idemix_mspid, mspid))) {
+                if (!idemix_mspid[0]) strcpy(idemix_mspid, mspid);
+                t->is_nym = 1;
+                n_nym++;
+            }
+        }
     }
     uint32_t* tx_first = (uint32_t*)calloc(n_tx + 2, 4);
     for (uint32_t i = 0; i < n_env_tuples; i++) tx_first[tuples[i].tx + 1]++;
@@ -352,6 +427,11 @@ int main(int argc, char** argv) {
         return rc == FABGPU_ENODEV ? 0 : 1;
     }
     t_new = now_ms() - t_new;
+    if (g_idemix && idemix_mspid[0]) {                        /* idemixmsp Setup -> bccsp/idemixgpu: the channel's idemix MSP and its issuer key */
+        int64_t issuer = -1;
+        rc = fabgpu_csp_idemix_msp_register(g_csp, idemix_mspid, ipk, ipk_len, &issuer);
+        if (rc != 0 || issuer < 0) { printf("{\"error\": \"fabgpu_csp_idemix_msp_register: %s, issuer %lld\"}\n", fabgpu_strerror(rc), (long long)issuer); return 1; }
+    }
 
     /* every block a fresh copy: a peer's blocks arrive in memory the runtime has never seen */
     uint8_t** copies = (uint8_t**)malloc(sizeof(uint8_t*) * (size_t)n_blocks);
@@ -362,7 +442,7 @@ int main(int argc, char** argv) {
     arrival_job* arr = (arrival_job*)calloc((size_t)n_blocks, sizeof(arrival_job));
     double* val_ms = (double*)calloc((size_t)n_blocks, sizeof(double));
     double* has_ms = (double*)calloc((size_t)n_blocks, sizeof(double));
-    uint64_t hits = 0, misses = 0, hashed = 0, hash_hits = 0, hash_bytes = 0, mismatches = 0;
+    uint64_t hits = 0, misses = 0, hashed = 0, hash_hits = 0, hash_bytes = 0, mismatches = 0, nym_hits = 0, nym_misses = 0;
     pthread_t* pool = (pthread_t*)malloc(sizeof(pthread_t) * (size_t)n_thr);
     pthread_barrier_init(&g_go, NULL, (unsigned)n_thr + 1);
     pthread_barrier_init(&g_done, NULL, (unsigned)n_thr + 1);
@@ -433,6 +513,7 @@ int main(int argc, char** argv) {
                     job.t_memo, job.t_thread, n_thr);
         hits += job.hits; misses += job.misses; hashed += job.hashed_bytes;
         hash_hits += job.hash_hits; hash_bytes += job.hash_bytes; mismatches += job.digest_mismatches;
+        nym_hits += job.nym_hits; nym_misses += job.nym_misses;
     }
     double wall = now_ms() - wall0;
     for (int a = 0; a < g_arrivals; a++) pthread_join(arr_th[a], NULL);
@@ -481,14 +562,16 @@ int main(int argc, char** argv) {
            (unsigned long long)mismatches, (unsigned long long)hits, (unsigned long long)misses, wall, wall / n_blocks,
            (double)n_tx * n_blocks / (wall * 1e-3), (unsigned long long)dw, (unsigned long long)hw);
     for (int d = 0; d < nd; d++) printf("%s%llu", d ? ", " : "", (unsigned long long)per_dev[d]);
-    uint64_t au[6] = {0, 0, 0, 0, 0, 0};
-    fabgpu_csp_audit_stats(g_csp, au, 6);
+    uint64_t au[7] = {0, 0, 0, 0, 0, 0, 0};
+    fabgpu_csp_audit_stats(g_csp, au, 7);
     char poisoned_why[256];
     const int poisoned = fabgpu_csp_poisoned(g_csp, poisoned_why, sizeof(poisoned_why));
-    printf("], \"audit_permille\": %ld, \"audit\": {\"digest_audits\": %llu, \"verdict_audits\": %llu, \"direct_audits\": %llu, \"mismatches\": %llu, "
-           "\"skipped_nym\": %llu, \"audit_ns\": %llu, \"audit_ms_per_block\": %.4f, \"poisoned\": %d}}\n",
+    printf("], \"nym_signatures_per_block\": %u, \"nym_memo_hits\": %llu, \"nym_memo_misses\": %llu, "
+           "\"audit_permille\": %ld, \"audit\": {\"digest_audits\": %llu, \"verdict_audits\": %llu, \"direct_audits\": %llu, \"mismatches\": %llu, "
+           "\"skipped_nym\": %llu, \"nym_audits\": %llu, \"audit_ns\": %llu, \"audit_ms_per_block\": %.4f, \"poisoned\": %d}}\n",
+           n_nym, (unsigned long long)nym_hits, (unsigned long long)nym_misses,
            audit_permille, (unsigned long long)au[0], (unsigned long long)au[1], (unsigned long long)au[2], (unsigned long long)au[3], (unsigned long long)au[4],
-           (unsigned long long)au[5], au[5] * 1e-6 / n_blocks, poisoned);
+           (unsigned long long)au[6], (unsigned long long)au[5], au[5] * 1e-6 / n_blocks, poisoned);
     if (poisoned) fprintf(stderr, "provider poisoned: %s\n", poisoned_why);
     fabgpu_csp_free(g_csp);
     return 0;
