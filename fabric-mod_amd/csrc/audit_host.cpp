@@ -14,6 +14,7 @@
 #include "idemix_host.h"
 #include "p256_tables29.h"
 #include "sha3_256.h"
+#include "p384.h"
 
 namespace fab {
 namespace bccsp {
@@ -136,6 +137,28 @@ bool audit_p256_verify(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* 
     from_be32(r, r32);
     from_be32(s, s32);
     return verify_core(qx, qy, e, r, s) == ST_VALID;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ECDSA P-384: p384.h compiled for the host (the generator's fifteen multiples are built at the first audit)
+// ------------------------------------------------------------------------------------------------
+bool audit_p384_verify(const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig_der, size_t siglen, const uint8_t* digest, size_t dlen) {
+    if (!qx48 || !qy48 || !sig_der || !digest || siglen == 0 || dlen == 0) return false;
+    BigInt R, S;
+    if (!UnmarshalECDSASignature(sig_der, siglen, R, S).ok()) return false;
+    uint8_t rs[2][48], e48[48];
+    const BigInt* v[2] = {&R, &S};
+    for (int k = 0; k < 2; k++) {
+        const std::vector<uint8_t> m = v[k]->magnitude();
+        if (m.size() > 48) return false;                                                  // above 2^384 > n
+        memset(rs[k], 0, 48);
+        if (!m.empty()) memcpy(rs[k] + 48 - m.size(), m.data(), m.size());
+    }
+    static uint32_t gtab[p384::P384_GTAB_WORDS];
+    static std::once_flag once;
+    std::call_once(once, [] { p384::build_gtab(gtab); });
+    p384::hash_to_int(digest, dlen, e48);
+    return p384::verify_host(gtab, qx48, qy48, e48, rs[0], rs[1]) == p384::ST_VALID;      // (its gate: low s, ranges, the key on the curve)
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -22,6 +22,8 @@ void audit_sha3_256(const uint8_t* msg, size_t len, uint8_t* out32);
 // bccsp.Verify(k, sig, digest) as bccsp/sw decides it (bccsp/sw/impl.go:247-270 -> ecdsa.go:41-57): true = (true, nil), false =
 // everything else - a signature that does not unmarshal, r or s <= 0, high S, r >= n, a key that is not on the curve, an empty
 // signature or digest, a signature that does not verify.
+// the same for a P-384 key (48-byte coordinates): the gates against P-384's order, the arithmetic by the host compilation of p384.h
+bool audit_p384_verify(const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig_der, size_t siglen, const uint8_t* digest, size_t dlen);
 bool audit_p256_verify(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig_der, size_t siglen, const uint8_t* digest, size_t dlen);
 
 // NymVerifier.Verify(k, sig, msg, opts) as bccsp/idemix decides it (bccsp/idemix/handlers/nymsigner.go:62-95 -> idemix/nymsignature.go:

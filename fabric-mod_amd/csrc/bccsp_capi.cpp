@@ -247,6 +247,91 @@ int fabgpu_csp_identity_verify_coalesced2(fabgpu_csp* csp, const uint8_t* qx32, 
     return FABGPU_OK;
 }
 
+// ---- ECDSA P-384 identities (option p384) ----
+int fabgpu_csp_verify_coalesced_p384(fabgpu_csp* csp, const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig, size_t siglen,
+                                     const uint8_t* digest, size_t dlen, int* valid, int* flags, char* err, size_t errcap) {
+    if (!csp || !valid) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
+    ECDSAPublicKey384 k;
+    const ECDSAPublicKey384* kp = nullptr;
+    if (qx48 && qy48) {
+        GPUCSP::KeyImport384(qx48, qy48, k);
+        kp = &k;
+    }
+    VerifyResult r = csp->csp->VerifyCoalescedP384(kp, sig, siglen, digest, dlen);
+    if (r.infrastructure) {
+        put_err(err, errcap, r.err.msg);
+        return FABGPU_ELAUNCH;
+    }
+    *valid = r.valid ? 1 : 0;
+    if (flags) *flags = r.needs_sw ? 1 : 0;
+    put_err(err, errcap, r.err.ok() ? "" : r.err.msg);
+    if (csp->csp->Poisoned()) {
+        *valid = 0;
+        put_err(err, errcap, GPUCSP::PoisonedText());
+        return FABGPU_EPOISONED;
+    }
+    return FABGPU_OK;
+}
+
+int fabgpu_csp_verify_batch_p384(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* sig_arena, const uint32_t* sig_off,
+                                 const uint8_t* dig_arena, const uint32_t* dig_off, const char* hash_family, uint8_t* valid, char* errs,
+                                 size_t errstride) {
+    if (!csp || (n && (!qx || !qy || !sig_off || !dig_off || !valid))) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
+    bool sha3 = false;
+    std::string ferr;
+    const bool refuse = !csp->csp->P384Enabled();
+    if (refuse) ferr = GPUCSP::P384RefusalText();
+    if (refuse || !csp->csp->HashFamily(hash_family, &sha3, &ferr)) {     // (the digests are the caller's: the family is only checked)
+        for (size_t i = 0; i < n; i++) {
+            valid[i] = 0;
+            if (errs && errstride) put_err(errs + i * errstride, errstride, ferr);
+        }
+        return FABGPU_OK;
+    }
+    std::vector<ECDSAPublicKey384> keys(n);
+    std::vector<VerifyItem384> items(n);
+    for (size_t i = 0; i < n; i++) {
+        GPUCSP::KeyImport384(qx + 48 * i, qy + 48 * i, keys[i]);
+        items[i] = {&keys[i], sig_arena + sig_off[i], sig_off[i + 1] - sig_off[i], dig_arena + dig_off[i], dig_off[i + 1] - dig_off[i]};
+    }
+    std::vector<VerifyResult> res;
+    Error e = csp->csp->VerifyBatchP384(items, res);
+    if (!e.ok()) return FABGPU_ELAUNCH;
+    for (size_t i = 0; i < n; i++) {
+        valid[i] = res[i].valid ? 1 : 0;
+        if (errs && errstride) put_err(errs + i * errstride, errstride, res[i].err.ok() ? "" : res[i].err.msg);
+    }
+    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
+}
+
+int fabgpu_csp_identity_verify_batch_p384(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena,
+                                          const uint32_t* msg_off, const uint8_t* sig_arena, const uint32_t* sig_off, const char* hash_family,
+                                          char* errs, size_t errstride) {
+    if (!csp || (n && (!qx || !qy || !msg_off || !sig_off || !errs || !errstride))) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
+    bool sha3 = false;
+    std::string ferr;
+    const bool refuse = !csp->csp->P384Enabled();
+    if (refuse) ferr = std::string("could not determine the validity of the signature: ") + GPUCSP::P384RefusalText();
+    if (refuse || !csp->csp->HashFamily(hash_family, &sha3, &ferr)) {
+        for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, ferr);
+        return FABGPU_OK;
+    }
+    std::vector<ECDSAPublicKey384> keys(n);
+    std::vector<IdentityItem384> items(n);
+    for (size_t i = 0; i < n; i++) {
+        GPUCSP::KeyImport384(qx + 48 * i, qy + 48 * i, keys[i]);
+        items[i] = {&keys[i], msg_arena + msg_off[i], msg_off[i + 1] - msg_off[i], sig_arena + sig_off[i], sig_off[i + 1] - sig_off[i]};
+    }
+    std::vector<std::string> out;
+    Error e = csp->csp->IdentityVerifyBatchP384(items, out, sha3);
+    if (!e.ok()) return FABGPU_ELAUNCH;
+    for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, out[i]);
+    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
+}
+
 int fabgpu_csp_coalescer_configure(fabgpu_csp* csp, uint32_t window_us, uint32_t max_batch) {
     if (!csp) return FABGPU_EINVAL;
     csp->csp->CoalescerConfigure(window_us, max_batch);

@@ -34,6 +34,7 @@
 #include <thread>
 
 #include "p256_point.h"
+#include "p384.h"
 
 namespace fab {
 namespace bccsp {
@@ -227,6 +228,7 @@ Error GPUCSP::New(const ProviderOptions& opts, std::unique_ptr<GPUCSP>& out) {
     p->opts_ = opts;
     p->retire_evicted_.store(opts.retire_evicted_keys > 0, std::memory_order_relaxed);
     p->hash_sha3_.store(opts.hash_sha3 > 0, std::memory_order_relaxed);
+    p->p384_.store(opts.p384 > 0, std::memory_order_relaxed);
     p->opts_.devices = devices;
     p->audit_permille_.store(opts.audit_permille > 1000 ? 1000 : opts.audit_permille, std::memory_order_relaxed);
     for (int32_t ord : devices) {
@@ -280,7 +282,8 @@ const OptField kIntOpts[] = {{"pass_device_walk", &ProviderOptions::pass_device_
                              {"pass_timing", &ProviderOptions::pass_timing},
                              {"pass_hash_memo", &ProviderOptions::pass_hash_memo},
                              {"retire_evicted_keys", &ProviderOptions::retire_evicted_keys},
-                             {"hash_sha3", &ProviderOptions::hash_sha3}};
+                             {"hash_sha3", &ProviderOptions::hash_sha3},
+                             {"p384", &ProviderOptions::p384}};
 }  // namespace
 int64_t GPUCSP::SetOption(const std::string& name, int64_t value) const {
     std::lock_guard<std::mutex> lk(opt_mu_);
@@ -300,6 +303,7 @@ int64_t GPUCSP::SetOption(const std::string& name, int64_t value) const {
             opts_.*(o.f) = (int)value;
             if (name == "retire_evicted_keys") retire_evicted_.store(value > 0, std::memory_order_relaxed);
             if (name == "hash_sha3") hash_sha3_.store(value > 0, std::memory_order_relaxed);
+            if (name == "p384") p384_.store(value > 0, std::memory_order_relaxed);
             return prev;
         }
     return INT64_MIN;
@@ -898,16 +902,18 @@ void GPUCSP::CoalescerConfigure(uint32_t window_us, uint32_t max_batch) const {
     co_verify_.configure(window_us, max_batch);
     co_identity_.configure(window_us, max_batch);
     co_identity_sha3_.configure(window_us, max_batch);
+    co_verify_p384_.configure(window_us, max_batch);
 }
 
 void GPUCSP::CoalescerStats(uint64_t* calls, uint64_t* launches, uint64_t* largest_batch) const {
-    uint64_t c[3], l[3], g[3];
+    uint64_t c[4], l[4], g[4];
     co_verify_.stats(&c[0], &l[0], &g[0]);
     co_identity_.stats(&c[1], &l[1], &g[1]);
     co_identity_sha3_.stats(&c[2], &l[2], &g[2]);
-    if (calls) *calls = c[0] + c[1] + c[2];
-    if (launches) *launches = l[0] + l[1] + l[2];
-    if (largest_batch) *largest_batch = std::max(g[0], std::max(g[1], g[2]));
+    co_verify_p384_.stats(&c[3], &l[3], &g[3]);
+    if (calls) *calls = c[0] + c[1] + c[2] + c[3];
+    if (launches) *launches = l[0] + l[1] + l[2] + l[3];
+    if (largest_batch) *largest_batch = std::max(std::max(g[0], g[1]), std::max(g[2], g[3]));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1252,6 +1258,208 @@ bool GPUCSP::AuditDirect(const ECDSAPublicKey& k, const uint8_t* sig, size_t sig
     Poison(std::string("direct call: the device accepted a signature in ") + what + " that the CPU audit rejects (key X " + hex8(k.x) + "..)");
     return false;
 }
+// ------------------------------------------------------------------------------------------------
+// ECDSA P-384 identities (option p384): the P-256 verbs' answers and texts on the P-384 entries of fabgpu.h
+// ------------------------------------------------------------------------------------------------
+const char* GPUCSP::P384RefusalText() { return "P-384 is served by bccsp/sw, not by the GPU provider"; }
+void GPUCSP::KeyImport384(const uint8_t* qx48, const uint8_t* qy48, ECDSAPublicKey384& out) {
+    memcpy(out.x, qx48, 48);
+    memcpy(out.y, qy48, 48);
+    out.on_curve = p384::pubkey_on_curve(qx48, qy48);
+}
+namespace {
+const char* HALF_ORDER_P384_DECIMAL = "19701003098197239606139520050071806902539869635232723333973452639813829699556631784699478154076147456777216826971321";
+// the low 384 bits of a non-negative value; false: it has more
+bool to_be48(const BigInt& v, uint8_t* out48) {
+    const std::vector<uint8_t> m = v.magnitude();
+    memset(out48, 0, 48);
+    const size_t take = m.size() < 48 ? m.size() : 48;
+    if (take) memcpy(out48 + 48 - take, m.data() + m.size() - take, take);
+    return m.size() <= 48;
+}
+struct Gate384 {
+    bool submit = false;
+    VerifyResult res;
+    uint8_t r[48], s[48], e[48];
+};
+// gate_item for a P-384 key: the same checks in the same order with the same texts; IsLowS against P-384's half order
+// (bccsp/utils/ecdsa.go:84-92 takes the key's own curve), r above 2^384 > n: (false, nil)
+Gate384 gate_item384(const ECDSAPublicKey384* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) {
+    Gate384 g;
+    memset(g.r, 0, 48); memset(g.s, 0, 48); memset(g.e, 0, 48);
+    g.r[47] = g.s[47] = 1;
+    if (k == nullptr) { g.res = {false, Error("Invalid Key. It must not be nil.")}; return g; }
+    if (siglen == 0) { g.res = {false, Error("Invalid signature. Cannot be empty.")}; return g; }
+    if (dlen == 0) { g.res = {false, Error("Invalid digest. Cannot be empty.")}; return g; }
+    const std::string wrap = "Failed verifing with opts [<nil>]: ";   // errors.Wrapf at impl.go:266
+    BigInt R, S;
+    Error e = UnmarshalECDSASignature(sig, siglen, R, S);
+    if (!e.ok()) { g.res = {false, Error(wrap + "Failed unmashalling signature [" + e.msg + "]")}; return g; }
+    uint8_t r48[48], s48[48];
+    const bool s_fits = to_be48(S, s48), r_fits = to_be48(R, r48);
+    if (!s_fits || !p384::is_low_s(s48)) {
+        g.res = {false, Error(wrap + "Invalid S. Must be smaller than half the order [" + S.decimal() + "][" + HALF_ORDER_P384_DECIMAL + "].")};
+        return g;
+    }
+    if (!r_fits) { g.res = {false, Error()}; return g; }
+    if (!k->on_curve) {
+        g.res = {false, Error("public key is not on P-384: the GPU provider does not decide this tuple (use bccsp/sw)")};
+        g.res.needs_sw = true;
+        return g;
+    }
+    memcpy(g.r, r48, 48);
+    memcpy(g.s, s48, 48);
+    p384::hash_to_int(digest, dlen, g.e);
+    g.submit = true;
+    return g;
+}
+// a slot the gate did not submit carries the generator as its key (r = s = 1, e = 0): the batch stays dense
+void put_generator384(uint8_t* qx48, uint8_t* qy48) {
+    p384::u384 gx = FAB_P384_GX_MONT, gy = FAB_P384_GY_MONT, t;
+    p384::fp_from_mont(t, gx); p384::to_be48(qx48, t);
+    p384::fp_from_mont(t, gy); p384::to_be48(qy48, t);
+}
+}  // namespace
+
+Error GPUCSP::VerifyBatchP384(const std::vector<VerifyItem384>& items, std::vector<VerifyResult>& results) const {
+    const size_t n = items.size();
+    results.assign(n, VerifyResult());
+    if (!P384Enabled()) {
+        for (auto& r : results) r.err = Error(P384RefusalText()), r.needs_sw = true;
+        return Error();
+    }
+    std::vector<uint8_t> qx(n * 48), qy(n * 48), e(n * 48), r(n * 48), s(n * 48), st(n), submitted(n, 0);
+    std::vector<uint64_t> bits((n + 63) / 64);
+    for (size_t i = 0; i < n; i++) {
+        const VerifyItem384& it = items[i];
+        Gate384 g = gate_item384(it.key, it.sig, it.siglen, it.digest, it.dlen);
+        results[i] = g.res;
+        submitted[i] = g.submit;
+        if (g.submit) { memcpy(&qx[48 * i], it.key->x, 48); memcpy(&qy[48 * i], it.key->y, 48); }
+        else put_generator384(&qx[48 * i], &qy[48 * i]);
+        memcpy(&e[48 * i], g.e, 48);
+        memcpy(&r[48 * i], g.r, 48);
+        memcpy(&s[48 * i], g.s, 48);
+    }
+    if (n == 0) return Error();
+    int rc = fabgpu_p384_verify_batch(flat_ctx(), n, qx.data(), qy.data(), e.data(), r.data(), s.data(), bits.data(), st.data());
+    if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
+    for (size_t i = 0; i < n; i++) {
+        if (!submitted[i]) continue;
+        if (st[i] == FABGPU_ST_HIGH_S || st[i] == FABGPU_ST_OFF_CURVE) return Error("internal inconsistency between host gate and device status");
+        bool valid = ((bits[i >> 6] >> (i & 63)) & 1) && st[i] == FABGPU_ST_VALID;
+        if (!valid && st[i] == FABGPU_ST_BAD_MATH) {                       // (test hook: a corrupted verdict)
+            uint32_t f = test_p384_flip_.load(std::memory_order_relaxed);
+            while (f && !test_p384_flip_.compare_exchange_weak(f, f - 1)) {}
+            if (f) valid = true;
+        }
+        results[i].valid = valid;
+        results[i].err = Error();
+        if (valid && !AuditDirectP384(*items[i].key, items[i].sig, items[i].siglen, items[i].digest, items[i].dlen, "bccsp.Verify")) {
+            results[i] = VerifyResult();
+            results[i].err = Error(PoisonedText());
+            results[i].poisoned = true;
+        }
+    }
+    return Error();
+}
+
+// identity.Verify for P-384 identities: digest = Hash(msg) in the MSP's family (a launch of its own), then the P-384 kernel
+Error GPUCSP::IdentityVerifyBatchP384(const std::vector<IdentityItem384>& items, std::vector<std::string>& out, bool sha3) const {
+    const size_t n = items.size();
+    out.assign(n, std::string());
+    if (!P384Enabled()) {
+        out.assign(n, std::string("could not determine the validity of the signature: ") + P384RefusalText());
+        return Error();
+    }
+    if (sha3 && !Sha3Enabled()) return Error("SHA3 is served by bccsp/sw, not by the GPU provider");
+    if (n == 0) return Error();
+    std::vector<uint8_t> qx(n * 48), qy(n * 48), r(n * 48), s(n * 48), st(n), submitted(n, 0), arena;
+    std::vector<uint32_t> off(n + 1);
+    std::vector<uint64_t> bits((n + 63) / 64);
+    static const uint8_t one_digest[1] = {1};
+    for (size_t i = 0; i < n; i++) {
+        const IdentityItem384& it = items[i];
+        Gate384 g = gate_item384(it.key, it.sig, it.siglen, one_digest, 1);
+        submitted[i] = g.submit;
+        if (!g.submit) out[i] = g.res.err.ok() ? "The signature is invalid" : "could not determine the validity of the signature: " + g.res.err.msg;
+        if (g.submit) { memcpy(&qx[48 * i], it.key->x, 48); memcpy(&qy[48 * i], it.key->y, 48); }
+        else put_generator384(&qx[48 * i], &qy[48 * i]);
+        memcpy(&r[48 * i], g.r, 48);
+        memcpy(&s[48 * i], g.s, 48);
+        off[i] = (uint32_t)arena.size();
+        if (g.submit && it.msglen) arena.insert(arena.end(), it.msg, it.msg + it.msglen);
+    }
+    off[n] = (uint32_t)arena.size();
+    arena.resize(arena.size() + 8);
+    int rc = sha3 ? fabgpu_sha3_256_p384_verify_batch(flat_ctx(), n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data())
+                  : fabgpu_sha256_p384_verify_batch(flat_ctx(), n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data());
+    if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
+    for (size_t i = 0; i < n; i++) {
+        if (!submitted[i]) continue;
+        const bool ok = ((bits[i >> 6] >> (i & 63)) & 1) && st[i] == FABGPU_ST_VALID;
+        out[i] = ok ? "" : "The signature is invalid";
+        if (ok && !AuditDirectP384(*items[i].key, items[i].sig, items[i].siglen, nullptr, 0, "identity.Verify", items[i].msg, items[i].msglen, sha3)) out[i] = PoisonedText();
+    }
+    return Error();
+}
+
+VerifyResult GPUCSP::VerifyCoalescedP384(const ECDSAPublicKey384* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) const {
+    if (!P384Enabled()) {
+        VerifyResult r;
+        r.err = Error(P384RefusalText());
+        r.needs_sw = true;
+        return r;
+    }
+    Gate384 g = gate_item384(k, sig, siglen, digest, dlen);
+    if (!g.submit) return g.res;
+    CoReqV384 req;
+    req.item = {k, sig, siglen, digest, dlen};
+    co_verify_p384_.submit(&req, [this](std::vector<CoReqV384*>& batch) {
+        std::vector<VerifyResult> res;
+        Error e;
+        try {
+            std::vector<VerifyItem384> items(batch.size());
+            for (size_t i = 0; i < batch.size(); i++) items[i] = batch[i]->item;
+            e = VerifyBatchP384(items, res);
+        } catch (const std::exception& x) {
+            e = Error(std::string("GPU verify failed: ") + x.what());
+        }
+        for (size_t i = 0; i < batch.size(); i++) {
+            if (e.ok()) {
+                batch[i]->res = res[i];
+            } else {
+                batch[i]->res = VerifyResult();
+                batch[i]->res.err = e;
+                batch[i]->res.infrastructure = true;
+            }
+        }
+    });
+    return req.res;
+}
+
+bool GPUCSP::AuditDirectP384(const ECDSAPublicKey384& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
+                             const uint8_t* msg, size_t msglen, bool sha3) const {
+    if (!audit_sample_[AUDIT_DIRECT].hit(AuditPermille())) return true;
+    bool accept;
+    {
+        AuditClock clk{audit_count_[AUDIT_NS]};
+        uint8_t dg[32];
+        if (msg || msglen) {
+            if (sha3) audit_sha3_256(msg, msglen, dg);
+            else audit_sha256(msg, msglen, dg);
+            digest = dg;
+            dlen = 32;
+        }
+        accept = audit_p384_verify(k.x, k.y, sig, siglen, digest, dlen);
+    }
+    audit_count_[AUDIT_DIRECT].fetch_add(1, std::memory_order_relaxed);
+    if (accept) return true;
+    audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
+    Poison(std::string("direct call: the device accepted a P-384 signature in ") + what + " that the CPU audit rejects (key X " + hex8(k.x) + "..)");
+    return false;
+}
+
 int GPUCSP::MemoLookup(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, uint8_t* status,
                        const uint8_t* issuer_hash32) const {
     if (poisoned_.load(std::memory_order_acquire)) return 1;
@@ -2922,5 +3130,33 @@ int fabgpu_ecdsa_unmarshal_signature(const uint8_t* sig, size_t len, uint8_t* r3
 int fabgpu_ecdsa_is_low_s(const uint8_t* s32) { return memcmp(s32, fab::bccsp::HALF_N_BE, 32) <= 0 ? 1 : 0; }
 int fabgpu_p256_pubkey_on_curve(const uint8_t* qx32, const uint8_t* qy32) { return fab::bccsp::PublicKeyOnCurve(qx32, qy32) ? 1 : 0; }
 void fabgpu_hash_to_int(const uint8_t* digest, size_t len, uint8_t* e32) { fab::bccsp::HashToInt(digest, len, e32); }
+
+// ... and their P-384 namesakes (p384.h compiled for the host)
+int fabgpu_ecdsa_unmarshal_signature_p384(const uint8_t* sig, size_t len, uint8_t* r48, uint8_t* s48, int* flags) {
+    fab::bccsp::BigInt R, S;
+    fab::bccsp::Error e = fab::bccsp::UnmarshalECDSASignature(sig, len, R, S);
+    if (!e.ok()) {
+        if (e.msg.find("R must be larger") != std::string::npos) return 2;
+        if (e.msg.find("S must be larger") != std::string::npos) return 3;
+        return 1;
+    }
+    int fl = 0;
+    const fab::bccsp::BigInt* v[2] = {&R, &S};
+    uint8_t* o[2] = {r48, s48};
+    for (int k = 0; k < 2; k++) {
+        const std::vector<uint8_t> m = v[k]->magnitude();       // big-endian, minimal
+        if (m.size() > 48) fl |= 1 << k;
+        if (o[k]) {
+            memset(o[k], 0, 48);
+            const size_t take = m.size() < 48 ? m.size() : 48;
+            memcpy(o[k] + 48 - take, m.data() + m.size() - take, take);
+        }
+    }
+    if (flags) *flags = fl;
+    return 0;
+}
+int fabgpu_ecdsa_is_low_s_p384(const uint8_t* s48) { return fab::p384::is_low_s(s48) ? 1 : 0; }
+int fabgpu_p384_pubkey_on_curve(const uint8_t* qx48, const uint8_t* qy48) { return fab::p384::pubkey_on_curve(qx48, qy48) ? 1 : 0; }
+void fabgpu_hash_to_int_p384(const uint8_t* digest, size_t len, uint8_t* e48) { fab::p384::hash_to_int(digest, len, e48); }
 
 }  // extern "C"

@@ -79,6 +79,25 @@ struct VerifyResult {  // (valid bool, err error)
     bool infrastructure = false;  // device failure: caller falls back to bccsp/sw
     bool poisoned = false;        // the CPU audit of this "valid" disagreed (or the provider was poisoned before the call): no verdict
 };
+// ... and their P-384 namesakes (48-byte coordinates)
+struct ECDSAPublicKey384 {
+    uint8_t x[48], y[48];
+    bool on_curve = false;
+};
+struct VerifyItem384 {
+    const ECDSAPublicKey384* key;
+    const uint8_t* sig;
+    size_t siglen;
+    const uint8_t* digest;
+    size_t dlen;
+};
+struct IdentityItem384 {
+    const ECDSAPublicKey384* key;
+    const uint8_t* msg;
+    size_t msglen;
+    const uint8_t* sig;
+    size_t siglen;
+};
 struct IdentityItem {
     const ECDSAPublicKey* key;
     const uint8_t* msg;
@@ -144,6 +163,8 @@ struct ProviderOptions {
                                        // device; default off: the table stays registered with the contexts)
     int hash_sha3 = 0;                 // > 0: Hash serves SHA3_256Opts and identity.Verify an MSP of the SHA3 hash family on the device (SetOption
                                        // of the same name; default off: "Unsupported 'HashOpt' provided [SHA3_256]", as bccsp/sw is asked then)
+    int p384 = 0;                      // > 0: the *_p384 calls verify ECDSA P-384 identities on the device (SetOption of the same name; default off:
+                                       // they answer that P-384 is served by bccsp/sw)
     uint32_t audit_permille = 0;       // share of the digests / verdicts handed out that is re-computed on the CPU first (0 .. 1000; 0: none)
 };
 constexpr int kMaxProviderDevices = 64;   // contexts per provider (8 GPUs x up to 8 contexts each)
@@ -192,6 +213,14 @@ class GPUCSP {
     // false, and *err says who serves it.
     bool HashFamily(const char* family, bool* sha3, std::string* err) const;
     bool Sha3Enabled() const { return hash_sha3_.load(std::memory_order_relaxed); }
+    // ---- ECDSA P-384 identities (option p384; fresh keys, direct calls only: never the block pass, the memos or registered keys) ----
+    // Answers and error texts are those of the P-256 namesakes.  With the option off every item answers P384RefusalText().
+    bool P384Enabled() const { return p384_.load(std::memory_order_relaxed); }
+    static const char* P384RefusalText();
+    static void KeyImport384(const uint8_t* qx48, const uint8_t* qy48, ECDSAPublicKey384& out);
+    Error VerifyBatchP384(const std::vector<VerifyItem384>& items, std::vector<VerifyResult>& results) const;
+    Error IdentityVerifyBatchP384(const std::vector<IdentityItem384>& items, std::vector<std::string>& out, bool sha3) const;
+    VerifyResult VerifyCoalescedP384(const ECDSAPublicKey384* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) const;
     // The same two one-signature verbs for callers that arrive MANY AT A TIME on their own threads (orderer Broadcast handlers behind
     // SigFilter, validator goroutines on memo misses): blocking, same answers, calls in flight together share a launch (coalescer.h).
     VerifyResult VerifyCoalesced(const ECDSAPublicKey* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) const;
@@ -415,6 +444,13 @@ class GPUCSP {
     void FlushRetirementsRegLocked() const;
     mutable std::atomic<bool> retire_evicted_{false};
     mutable std::atomic<bool> hash_sha3_{false};             // the hash_sha3 option
+    mutable std::atomic<bool> p384_{false};                  // the p384 option
+    // test hook (TestAccess, libfabgpu_testhooks.so): so many of the device's next P-384 arithmetic rejects are read as "valid" - the
+    // corruption the audit must catch.  Nothing in the product sets it.
+    mutable std::atomic<uint32_t> test_p384_flip_{0};
+    // as AuditDirect, for a P-384 "valid": re-computed with the host compilation of p384.h (audit_p384_verify)
+    bool AuditDirectP384(const ECDSAPublicKey384& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
+                         const uint8_t* msg = nullptr, size_t msglen = 0, bool sha3 = false) const;
     mutable std::mutex retire_mu_;                           // retire_queue_, imported_keys_ (a leaf: nothing is taken under it)
     mutable std::vector<std::string> retire_queue_;          // qx || qy
     mutable std::set<std::string> imported_keys_;
@@ -549,7 +585,12 @@ class GPUCSP {
         std::string out;
         bool infra = false;
     };
+    struct CoReqV384 : CoalescedBase {
+        VerifyItem384 item;
+        VerifyResult res;
+    };
     mutable Coalescer<CoReqV> co_verify_;
+    mutable Coalescer<CoReqV384> co_verify_p384_;                     // P-384 callers queue apart: another kernel
     mutable Coalescer<CoReqI> co_identity_;
     mutable Coalescer<CoReqI> co_identity_sha3_;                      // a launch hashes with ONE family: SHA3 callers queue apart
     mutable std::mutex pass_mu_;                                      // guards scratch_free_

@@ -28,6 +28,7 @@
 #include "worker_pool.h"
 #include "bn_tables29.h"
 #include "p256_tables29.h"
+#include "p384.h"
 
 using namespace fab;
 
@@ -141,6 +142,8 @@ struct fabgpu_ctx {
     // "oom" makes every workspace / staging allocation fail.  A non-zero return must then reach the caller and no verdict may be written.
     int fault = 0;
     int32_t* d_gtab = nullptr;
+    uint32_t* d_gtab384 = nullptr;   // P-384: j G, j = 1 .. 15 (p384.h build_gtab), 1 440 bytes; made by the first P-384 call (p384_gtab)
+    std::mutex gtab384_mu;
     std::mutex mu;
     Buf fields;   // qx|qy|e|r|s
     Buf arena;    // message bytes
@@ -559,6 +562,7 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
         ctx->offs.release();
         ctx->out.release();
         if (ctx->d_gtab) hipFree(ctx->d_gtab);
+        if (ctx->d_gtab384) hipFree(ctx->d_gtab384);
         for (auto* t : ctx->ktab_slabs) hipFree(t);              // (every key table lies in a slab)
         for (auto* t : ctx->retired) hipFree(t);
         if (ctx->d_ktab_in) hipFree(ctx->d_ktab_in);
@@ -1454,7 +1458,7 @@ static int stage_messages(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const
 }
 
 // What one host-pointer call stages through the context's pinned buffers, ctx->mu held: its messages (ctx->arena, ctx->offs), its
-// n x 32 byte fields behind an optional column of u32 ids (one Buf), and room in ctx->out for what comes back - verdict words, then
+// n x 32 byte (P-384: n x 48 byte) fields behind an optional column of u32 ids (one Buf), and room in ctx->out for what comes back - verdict words, then
 // status bytes at st_off; or n digests.  A step is skipped once one before it has failed (rc), and every call returns through fetch().
 // THE FAILURE RULE, here and nowhere else: whatever failed - an allocation, an upload, the _dev call, the download - fetch() drains
 // ctx->stream before it returns and nothing is copied to the caller.  Non-zero return, the caller's arrays untouched, nothing in
@@ -1468,8 +1472,8 @@ struct HostStage {
     const size_t out_bytes;              // what comes back at most: n digests, or the verdict words and the status bytes
     int rc = FABGPU_OK;
 
-    HostStage(fabgpu_ctx* c, size_t rows, bool digests = false)
-        : ctx(c), n(rows), fb(rows * 32), words((rows + 63) / 64), st_off(round_up(words * 8, 64)), out_bytes(digests ? n * 32 : st_off + n) {}
+    HostStage(fabgpu_ctx* c, size_t rows, bool digests = false, size_t field_bytes = 32)   // field_bytes: 32, or 48 for the P-384 calls
+        : ctx(c), n(rows), fb(rows * field_bytes), words((rows + 63) / 64), st_off(round_up(words * 8, 64)), out_bytes(digests ? n * 32 : st_off + n) {}
     int room(Buf& b, size_t bytes) const { return ctx->fault == 2 ? FABGPU_ENOMEM : b.ensure(bytes); }   // FABGPU_FAULT_INJECT=oom: no staging either
     void messages(const uint8_t* arena, const uint32_t* off) {
         if (rc == FABGPU_OK) rc = stage_messages(ctx, n, arena, off, &ab);
@@ -1705,6 +1709,113 @@ int fabgpu_sha3_256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* 
 int fabgpu_sha3_256_p256_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
                                             const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
     return hash_verify_keyed_host(fabgpu_sha3_256_p256_verify_batch_keyed_dev, ctx, n, arena, off, key_id, r, s, verdict_bits, status);
+}
+
+// ---- ECDSA P-384 (p384_kernels.hip): fresh keys, direct calls only --------------------------------------------------------------
+// All operands 48 bytes big-endian per tuple.  Not in the block pass, no registered keys, no fabgpu_multi form.
+// P-384's generator table: fifteen affine multiples, built by the host compilation of p384.h and uploaded by the context's first P-384
+// call (a context that never sees a P-384 key allocates nothing and its construction is what it was)
+static int p384_gtab(fabgpu_ctx* ctx) {
+    std::lock_guard<std::mutex> lk(ctx->gtab384_mu);
+    if (ctx->d_gtab384) return FABGPU_OK;
+    uint32_t g384[fab::p384::P384_GTAB_WORDS];
+    fab::p384::build_gtab(g384);
+    uint32_t* d = nullptr;
+    if (hipMalloc((void**)&d, sizeof(g384)) != hipSuccess) return FABGPU_ENOMEM;
+    if (hipMemcpy(d, g384, sizeof(g384), hipMemcpyHostToDevice) != hipSuccess) {      // (synchronous: the table is there when this returns)
+        hipFree(d);
+        return FABGPU_ELAUNCH;
+    }
+    ctx->d_gtab384 = d;
+    return FABGPU_OK;
+}
+
+static int p384_verify_dev(fabgpu_ctx* ctx, size_t n, const void* qx, const void* qy, const void* e, bool e_is_digest32, const void* r, const void* s,
+                           void* verdict_bits, void* status, hipStream_t st) {
+    if (int rc = p384_gtab(ctx)) return rc;
+    P384Launch v;
+    v.n = (uint32_t)n;
+    v.qx = qx; v.qy = qy; v.e = e; v.e_is_digest32 = e_is_digest32; v.r = r; v.s = s;
+    v.gtab = ctx->d_gtab384;
+    v.verdict_bits = verdict_bits; v.status = status;
+    return timed_launch(ctx, st, p384_workspace_bytes((uint32_t)n), [&](void* wsp) {
+        v.qws = wsp;
+        return launch_p384_verify(v, st);
+    });
+}
+
+int fabgpu_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* qx, const void* qy, const void* e, const void* r, const void* s,
+                                 void* verdict_bits, void* status, void* stream) {
+    if (!ctx || (n && (!qx || !qy || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (dev_too_big(n)) return FABGPU_ETOOBIG;
+    DeviceGuard g(ctx->device);
+    if (n == 0) return p384_gtab(ctx);            // the explicit warm call (fabgpu.h): the table, no launch
+    return p384_verify_dev(ctx, n, qx, qy, e, false, r, s, verdict_bits, status, (hipStream_t)stream);
+}
+
+// Hash, then verify: the family's hash launch writes n x 32 digest bytes into a pooled context-owned buffer (as sha3_then_verify_dev
+// does), the P-384 kernel reads them as 256-bit integers - Go's hashToInt for a digest shorter than the order - on the same stream.
+static int hash_then_p384_dev(HashDev hash, fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, const void* qx,
+                              const void* qy, const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
+    if (!ctx || (n && (!arena || !off || !qx || !qy || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (dev_too_big(n, arena_bytes)) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    size_t di = 0;
+    void* dig = nullptr;
+    int rc = ctx->acquire_qws(n * 32, &di, &dig, st);
+    if (rc != FABGPU_OK) return rc;
+    rc = hash(ctx, n, arena, arena_bytes, off, dig, stream);
+    if (rc == FABGPU_OK) rc = p384_verify_dev(ctx, n, qx, qy, dig, true, r, s, verdict_bits, status, st);
+    ctx->release_qws(di, st);
+    return rc;
+}
+int fabgpu_sha256_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, const void* qx,
+                                        const void* qy, const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
+    return hash_then_p384_dev(fabgpu_sha256_batch_dev, ctx, n, arena, arena_bytes, off, qx, qy, r, s, verdict_bits, status, stream);
+}
+int fabgpu_sha3_256_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, const void* qx,
+                                          const void* qy, const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
+    return hash_then_p384_dev(fabgpu_sha3_256_batch_dev, ctx, n, arena, arena_bytes, off, qx, qy, r, s, verdict_bits, status, stream);
+}
+
+int fabgpu_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* e, const uint8_t* r,
+                             const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    if (!ctx || (n && (!qx || !qy || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (n > 0x7FFFFFF0ull / 240) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    HostStage h(ctx, n, false, 48);
+    h.fields(ctx->fields, HostStage::OVERLAP, nullptr, {qx, qy, e, r, s});
+    if (h.ready())
+        h.rc = fabgpu_p384_verify_batch_dev(ctx, n, h.field(0), h.field(1), h.field(2), h.field(3), h.field(4), h.dout(), h.dstatus(status), ctx->stream);
+    return h.fetch_verdicts(verdict_bits, status);
+}
+
+static int hash_p384_verify_host(HashVerifyDev dev, fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx, const uint8_t* qy,
+                                 const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    if (!ctx || (n && (!off || !qx || !qy || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (n > 0x7FFFFFF0ull / 240) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    HostStage h(ctx, n, false, 48);
+    h.messages(arena, off);
+    h.fields(ctx->fields, 0, nullptr, {qx, qy, r, s});
+    if (h.ready())
+        h.rc = dev(ctx, n, ctx->arena.d, h.ab, ctx->offs.d, h.field(0), h.field(1), h.field(2), h.field(3), h.dout(), h.dstatus(status), ctx->stream);
+    return h.fetch_verdicts(verdict_bits, status);
+}
+int fabgpu_sha256_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx, const uint8_t* qy,
+                                    const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    return hash_p384_verify_host(fabgpu_sha256_p384_verify_batch_dev, ctx, n, arena, off, qx, qy, r, s, verdict_bits, status);
+}
+int fabgpu_sha3_256_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx, const uint8_t* qy,
+                                      const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    return hash_p384_verify_host(fabgpu_sha3_256_p384_verify_batch_dev, ctx, n, arena, off, qx, qy, r, s, verdict_bits, status);
 }
 
 // ---- identity.Verify over a described batch: optional shared prefixes, fresh or registered keys ------------------------

@@ -75,6 +75,11 @@ int fabgpu_test_audit_nym_verify(const uint8_t* hsk_x32, const uint8_t* hsk_y32,
  * entry's: between valid and proof-invalid), kind 2 flips one bit of the first byte of the message the index-th entry remembers, in the
  * held copy of the block.  0 done, 1 nothing to corrupt (no such table, no digest memo / no held copy, a status that is neither), FABGPU_EINVAL. */
 int fabgpu_csp_test_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, int kind, uint32_t index);
+/* TEST HOOK: the provider reads the next `count` arithmetic rejects (status 1) the device gives in fabgpu_csp_verify_batch_p384 /
+ * _verify_coalesced_p384 as "valid": a corrupted P-384 verdict, which the sampled audit has to catch. */
+int fabgpu_csp_test_p384_corrupt(fabgpu_csp* csp, uint32_t count);
+/* TEST HOOK (no device, no provider): what the *_p384 calls of a provider answer per item while its p384 option is off. */
+const char* fabgpu_test_p384_refusal_text(void);
 /* TEST HOOK: the allocator of key slots and ids by itself (csrc/key_slots.h; no device, no context).  gen_last: the last generation a
  * slot may reach (0xFFFFF in the product).  register: the id of the next registration, or -1 when no slot can be had; a lowest slot
  * that is still draining is waited for, i.e. drained on the spot and counted.  retire: 0 retired, 1 not live.  drain: what a context

@@ -18,6 +18,7 @@
 #include "block_walk_core.h"
 #include "block_prepass.h"
 #include "sha3_256.h"
+#include "p384.h"
 #include "walk_layout.h"
 
 using namespace fab;
@@ -532,5 +533,94 @@ void hosttest_walk_worst_case(uint32_t n_tx, uint32_t n_tuples, uint64_t* out12)
     for (int k = 0; k < 3; k++) {
         out12[4 * k] = s[k].env; out12[4 * k + 1] = s[k].tup; out12[4 * k + 2] = s[k].pin; out12[4 * k + 3] = s[k].map;
     }
+}
+
+// ---- p384.h compiled for the host, primitive by primitive (tests/test_p384_host.py): 48 big-endian bytes in and out ----
+static const uint32_t* gtab384() {
+    static std::vector<uint32_t> tab = [] { std::vector<uint32_t> t(p384::P384_GTAB_WORDS); p384::build_gtab(t.data()); return t; }();
+    return tab.data();
+}
+// field ops on plain integers in [0, p), carried out in the Montgomery domain.  op: 0 mul 1 sqr 2 add 3 sub 4 round trip 5 inverse
+void hosttest_p384_fp_op(int op, const uint8_t* a48, const uint8_t* b48, uint8_t* out48) {
+    p384::u384 a, b, am, bm, r;
+    p384::from_be48(a, a48);
+    p384::from_be48(b, b48);
+    p384::fp_to_mont(am, a);
+    p384::fp_to_mont(bm, b);
+    switch (op) {
+        case 0: p384::fp_mul(r, am, bm); break;
+        case 1: p384::fp_sqr(r, am); break;
+        case 2: p384::fp_add(r, am, bm); break;
+        case 3: p384::fp_sub(r, am, bm); break;
+        case 5: p384::fp_inv(r, am); break;
+        default: r = am; break;
+    }
+    p384::fp_from_mont(r, r);
+    p384::to_be48(out48, r);
+}
+// raw Montgomery product mod p (field != 0) or mod n of two canonical residues: a b 2^-384 mod m
+void hosttest_p384_mont_mul(int field, const uint8_t* a48, const uint8_t* b48, uint8_t* out48) {
+    p384::u384 a, b, r;
+    p384::from_be48(a, a48);
+    p384::from_be48(b, b48);
+    r = field ? p384::mont_mul<true>(a, b) : p384::mont_mul<false>(a, b);
+    p384::to_be48(out48, r);
+}
+// scalars in [0, n).  op: 0 mul 1 inverse (0 -> 0) 2 reduce a value below 2^384 once
+void hosttest_p384_fn_op(int op, const uint8_t* a48, const uint8_t* b48, uint8_t* out48) {
+    p384::u384 a, b, am, bm, r;
+    p384::from_be48(a, a48);
+    p384::from_be48(b, b48);
+    if (op == 2) {
+        p384::fn_reduce_once(r, a);
+        p384::to_be48(out48, r);
+        return;
+    }
+    p384::fn_to_mont(am, a);
+    p384::fn_to_mont(bm, b);
+    if (op == 0) p384::fn_mul(r, am, bm);
+    else p384::fn_inv(r, am);
+    p384::fn_from_mont(r, r);
+    p384::to_be48(out48, r);
+}
+// Jacobian points as 144 bytes X | Y | Z (plain integers; Z = 0: infinity).  op: 0 doubling of a, 1 a + b, 2 a + b with b affine (Z = 1)
+void hosttest_p384_pt_op(int op, const uint8_t* a144, const uint8_t* b144, uint8_t* out144) {
+    p384::jac a, b, r;
+    p384::u384 t;
+    p384::u384* av[3] = {&a.X, &a.Y, &a.Z};
+    p384::u384* bv[3] = {&b.X, &b.Y, &b.Z};
+    for (int k = 0; k < 3; k++) {
+        p384::from_be48(t, a144 + 48 * k); p384::fp_to_mont(*av[k], t);
+        p384::from_be48(t, b144 + 48 * k); p384::fp_to_mont(*bv[k], t);
+    }
+    if (op == 0) p384::pt_dbl(r, a);
+    else if (op == 1) p384::pt_add<false>(r, a, b);
+    else p384::pt_add<true>(r, a, b);
+    p384::u384* rv[3] = {&r.X, &r.Y, &r.Z};
+    for (int k = 0; k < 3; k++) {
+        p384::fp_from_mont(t, *rv[k]);
+        p384::to_be48(out144 + 48 * k, t);
+    }
+}
+// the generator's table as the contexts upload it: entry j (1 .. 15) as affine x | y, plain integers
+void hosttest_p384_gtab_entry(int j, uint8_t* out96) {
+    p384::jac e;
+    p384::GTabPtr{gtab384()}.load(e, (uint32_t)j);
+    p384::u384 t;
+    p384::fp_from_mont(t, e.X); p384::to_be48(out96, t);
+    p384::fp_from_mont(t, e.Y); p384::to_be48(out96 + 48, t);
+}
+// x(R) mod n == r (both acceptance branches) for a Jacobian point given as in hosttest_p384_pt_op
+int hosttest_p384_x_equals_r(const uint8_t* a144, const uint8_t* r48) {
+    p384::jac a;
+    p384::u384 t, r;
+    p384::u384* av[3] = {&a.X, &a.Y, &a.Z};
+    for (int k = 0; k < 3; k++) { p384::from_be48(t, a144 + 48 * k); p384::fp_to_mont(*av[k], t); }
+    p384::from_be48(r, r48);
+    return p384::x_equals_r(a, r) ? 1 : 0;
+}
+// one tuple through the verification core: status 0 .. 4
+uint32_t hosttest_p384_verify(const uint8_t* qx48, const uint8_t* qy48, const uint8_t* e48, const uint8_t* r48, const uint8_t* s48) {
+    return p384::verify_host(gtab384(), qx48, qy48, e48, r48, s48);
 }
 }

@@ -116,6 +116,20 @@ hipError_t launch_sha3_256_messages(uint32_t n, const void* arena, size_t arena_
 hipError_t launch_sha3_256_batch(uint32_t n, const void* arena, size_t arena_bytes, const void* off, bool spans, void* digests, hipStream_t st);
 int warm_kernel_functions_sha3();
 
+// ---- p384_kernels.hip: ECDSA P-384 verification (p384.h), one signature per lane, fresh keys only ----
+struct P384Launch {
+    uint32_t n = 0;
+    const void *qx = nullptr, *qy = nullptr, *r = nullptr, *s = nullptr;   // n x 48 bytes each, big-endian
+    const void* e = nullptr;                 // n x 48 bytes (hashToInt done), or n x 32 bytes of digests of a 256-bit hash family ...
+    bool e_is_digest32 = false;              // ... which Go's hashToInt takes as a 256-bit integer
+    const void* gtab = nullptr;              // P384_GTAB_WORDS words: j G, j = 1 .. 15 (p384.h build_gtab)
+    void* qws = nullptr;                     // p384_workspace_bytes(n) bytes for the per-signature tables
+    void* verdict_bits = nullptr;            // ceil(n/64) x u64
+    void* status = nullptr;                  // n bytes or nullptr
+};
+size_t p384_workspace_bytes(uint32_t n);
+hipError_t launch_p384_verify(const P384Launch& v, hipStream_t st);
+
 // ---- idemix_kernels.hip: idemix pseudonym signatures on FP256BN ----
 // A registered issuer occupies one slot of idemix_issuer_dev_bytes() bytes in a device array; fill a host copy of the slot
 // with idemix_issuer_dev_fill (device pointers of the two comb tables + ipk.Hash) and copy it up.

@@ -21,6 +21,7 @@ using namespace fab::bccsp;
 namespace fab {
 namespace bccsp {
 struct TestAccess {
+    static void p384_corrupt(const GPUCSP& c, uint32_t count) { c.test_p384_flip_.store(count, std::memory_order_relaxed); }
     static int memo_corrupt(const GPUCSP& c, uint64_t block_seq, int kind, uint32_t index) {
         std::unique_lock<BigReaderLock> lk(c.memo_mu_);
         for (const auto& b : c.memo_blocks_) {
@@ -315,6 +316,12 @@ long long fabgpu_test_audit_sample(uint32_t permille, uint32_t n_hits, uint8_t* 
 // between valid and bad-signature (what fabgpu_csp_memo_lookup hands out; for a pseudonym entry: valid and proof-invalid, what
 // fabgpu_csp_memo_lookup_nym hands out), kind 2 flips one bit of the first byte of the message the index-th entry remembers, in the block
 // copy the digest memo holds (what the pseudonym audit verifies over).  0 done, 1 nothing to corrupt there, FABGPU_EINVAL.
+const char* fabgpu_test_p384_refusal_text(void) { return GPUCSP::P384RefusalText(); }
+int fabgpu_csp_test_p384_corrupt(fabgpu_csp* csp, uint32_t count) {
+    if (!csp) return FABGPU_EINVAL;
+    TestAccess::p384_corrupt(*csp->csp, count);
+    return 0;
+}
 int fabgpu_csp_test_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, int kind, uint32_t index) {
     if (!csp) return FABGPU_EINVAL;
     return TestAccess::memo_corrupt(*csp->csp, block_seq, kind, index);

@@ -118,6 +118,9 @@ ABI_SYMBOLS = [
     "fabgpu_sha256_p256_verify_batch_keyed", "fabgpu_sha256_p256_verify_batch_keyed_dev",
     "fabgpu_sha3_256_batch", "fabgpu_sha3_256_batch_dev", "fabgpu_sha3_256_p256_verify_batch", "fabgpu_sha3_256_p256_verify_batch_dev",
     "fabgpu_sha3_256_p256_verify_batch_keyed", "fabgpu_sha3_256_p256_verify_batch_keyed_dev",
+    "fabgpu_p384_verify_batch", "fabgpu_p384_verify_batch_dev", "fabgpu_sha256_p384_verify_batch", "fabgpu_sha256_p384_verify_batch_dev",
+    "fabgpu_sha3_256_p384_verify_batch", "fabgpu_sha3_256_p384_verify_batch_dev",
+    "fabgpu_ecdsa_unmarshal_signature_p384", "fabgpu_ecdsa_is_low_s_p384", "fabgpu_p384_pubkey_on_curve", "fabgpu_hash_to_int_p384",
     "fabgpu_identity_verify_batch", "fabgpu_identity_verify_batch_dev", "fabgpu_arena_stage",
     "fabgpu_idemix_issuer_register", "fabgpu_idemix_issuer_count", "fabgpu_idemix_nym_verify_batch", "fabgpu_idemix_nym_verify_batch_dev",
     "fabgpu_bn256_g1_on_curve",
@@ -128,6 +131,7 @@ ABI_SYMBOLS = [
     "fabgpu_csp_idemix_issuer_import", "fabgpu_csp_idemix_nym_verify_batch", "fabgpu_csp_idemix_msp_register", "fabgpu_csp_idemix_msp_register2", "fabgpu_block_hash_checks",
     "fabgpu_block_tuples", "fabgpu_csp_block_preverify2", "fabgpu_csp_block_pass_abandon", "fabgpu_idemix_issuer_key_is_canonical", "fabgpu_csp_memo_lookup", "fabgpu_csp_memo_lookup_nym", "fabgpu_csp_memo_has_block", "fabgpu_csp_memo_evict_block",
     "fabgpu_csp_identity_verify_batch2", "fabgpu_csp_identity_verify_coalesced2",
+    "fabgpu_csp_verify_coalesced_p384", "fabgpu_csp_verify_batch_p384", "fabgpu_csp_identity_verify_batch_p384",
     "fabgpu_csp_verify_coalesced", "fabgpu_csp_identity_verify_coalesced", "fabgpu_csp_coalescer_configure", "fabgpu_csp_coalescer_stats",
     "fabgpu_csp_memo_stats", "fabgpu_csp_memo_set_capacity", "fabgpu_csp_identity_cache_limits", "fabgpu_csp_identity_cache_size",
     "fabgpu_multi_init", "fabgpu_multi_shutdown", "fabgpu_multi_device_count", "fabgpu_multi_p256_verify_batch",
@@ -147,7 +151,7 @@ HOOK_SYMBOLS = [
     "fabgpu_synth_batch", "fabgpu_last_kernel_ms", "fabgpu_csp_block_walk_compare", "fabgpu_block_walk_twopass_compare", "fabgpu_gate_sig_fast",
     "fabgpu_gate_sig_any", "fabgpu_csp_idfix_probe", "fabgpu_csp_gate_probe", "fabgpu_identity_table_hash", "fabgpu_test_nym_side_after",
     "fabgpu_test_key_table", "fabgpu_test_key_table_host", "fabgpu_test_gtab_compare_with_host", "fabgpu_test_key_tables16",
-    "fabgpu_test_audit_sha256", "fabgpu_test_audit_p256_verify", "fabgpu_test_audit_nym_verify", "fabgpu_test_audit_sample", "fabgpu_csp_test_memo_corrupt",
+    "fabgpu_test_audit_sha256", "fabgpu_test_audit_p256_verify", "fabgpu_test_audit_nym_verify", "fabgpu_test_audit_sample", "fabgpu_csp_test_memo_corrupt", "fabgpu_csp_test_p384_corrupt", "fabgpu_test_p384_refusal_text",
     "fabgpu_test_key_slots_new", "fabgpu_test_key_slots_free", "fabgpu_test_key_slots_register", "fabgpu_test_key_slots_retire",
     "fabgpu_test_key_slots_drain", "fabgpu_test_key_slots_stats", "fabgpu_test_walk_buffer_caps",
 ]
@@ -198,6 +202,8 @@ def load_hooks():
     H.fabgpu_test_audit_sample.argtypes = [ctypes.c_uint32, ctypes.c_uint32, _u8p]
     H.fabgpu_test_audit_sample.restype = ctypes.c_longlong
     H.fabgpu_csp_test_memo_corrupt.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32]
+    H.fabgpu_csp_test_p384_corrupt.argtypes = [_vp, ctypes.c_uint32]
+    H.fabgpu_test_p384_refusal_text.restype = ctypes.c_char_p
     H.fabgpu_test_key_slots_new.argtypes = [ctypes.c_uint32]
     H.fabgpu_test_key_slots_new.restype = _vp
     H.fabgpu_test_key_slots_free.argtypes = [_vp]
@@ -254,6 +260,18 @@ def load():
     L.fabgpu_sha3_256_p256_verify_batch_dev.argtypes = L.fabgpu_sha256_p256_verify_batch_dev.argtypes
     L.fabgpu_sha3_256_p256_verify_batch_keyed.argtypes = L.fabgpu_sha256_p256_verify_batch_keyed.argtypes
     L.fabgpu_sha3_256_p256_verify_batch_keyed_dev.argtypes = L.fabgpu_sha256_p256_verify_batch_keyed_dev.argtypes
+    # ECDSA P-384: the argument lists of the P-256 namesakes (48-byte fields)
+    L.fabgpu_p384_verify_batch.argtypes = L.fabgpu_p256_verify_batch.argtypes
+    L.fabgpu_p384_verify_batch_dev.argtypes = L.fabgpu_p256_verify_batch_dev.argtypes
+    L.fabgpu_sha256_p384_verify_batch.argtypes = L.fabgpu_sha256_p256_verify_batch.argtypes
+    L.fabgpu_sha256_p384_verify_batch_dev.argtypes = L.fabgpu_sha256_p256_verify_batch_dev.argtypes
+    L.fabgpu_sha3_256_p384_verify_batch.argtypes = L.fabgpu_sha256_p256_verify_batch.argtypes
+    L.fabgpu_sha3_256_p384_verify_batch_dev.argtypes = L.fabgpu_sha256_p256_verify_batch_dev.argtypes
+    L.fabgpu_ecdsa_unmarshal_signature_p384.argtypes = [ctypes.c_char_p, _sz, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
+    L.fabgpu_ecdsa_is_low_s_p384.argtypes = [ctypes.c_char_p]
+    L.fabgpu_p384_pubkey_on_curve.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+    L.fabgpu_hash_to_int_p384.argtypes = [ctypes.c_char_p, _sz, ctypes.c_char_p]
+    L.fabgpu_hash_to_int_p384.restype = None
     L.fabgpu_arena_stage.argtypes = [_vp, _u8p, _sz, ctypes.POINTER(ctypes.c_uint64)]
     L.fabgpu_identity_verify_batch.argtypes = [_vp, ctypes.POINTER(_IdBatch)]
     L.fabgpu_identity_verify_batch_dev.argtypes = [_vp, ctypes.POINTER(_IdBatch), _vp, _vp]
@@ -291,6 +309,9 @@ def load():
     L.fabgpu_csp_identity_verify_coalesced2.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.c_char_p,
                                                         ctypes.c_char_p, _sz]
     L.fabgpu_csp_identity_verify_batch2.argtypes = [_vp, _sz, _u8p, _u8p, _u8p, _u32p, _u8p, _u32p, ctypes.c_char_p, ctypes.c_char_p, _sz]
+    L.fabgpu_csp_verify_coalesced_p384.argtypes = L.fabgpu_csp_verify.argtypes
+    L.fabgpu_csp_verify_batch_p384.argtypes = [_vp, _sz, _u8p, _u8p, _u8p, _u32p, _u8p, _u32p, ctypes.c_char_p, _u8p, ctypes.c_char_p, _sz]
+    L.fabgpu_csp_identity_verify_batch_p384.argtypes = [_vp, _sz, _u8p, _u8p, _u8p, _u32p, _u8p, _u32p, ctypes.c_char_p, ctypes.c_char_p, _sz]
     L.fabgpu_csp_coalescer_configure.argtypes = [_vp, ctypes.c_uint32, ctypes.c_uint32]
     L.fabgpu_csp_coalescer_stats.argtypes = [_vp, _u64p, _u64p, _u64p]
     L.fabgpu_csp_identity_verify_batch.argtypes = [_vp, _sz, _u8p, _u8p, _u8p, _u32p, _u8p, _u32p, ctypes.c_char_p, _sz]
@@ -369,6 +390,28 @@ def unmarshal_ecdsa_signature(raw: bytes) -> Tuple[int, bytes, bytes, int]:
     fl = ctypes.c_int(0)
     rc = load().fabgpu_ecdsa_unmarshal_signature(raw, len(raw), r, s, ctypes.byref(fl))
     return rc, r.raw, s.raw, fl.value
+
+
+def unmarshal_signature_p384(raw: bytes):
+    """fabgpu_ecdsa_unmarshal_signature_p384: (rc, r48, s48, flags)."""
+    r, s = ctypes.create_string_buffer(48), ctypes.create_string_buffer(48)
+    fl = ctypes.c_int(0)
+    rc = load().fabgpu_ecdsa_unmarshal_signature_p384(raw, len(raw), r, s, ctypes.byref(fl))
+    return rc, r.raw, s.raw, fl.value
+
+
+def is_low_s_p384(s48: bytes) -> bool:
+    return bool(load().fabgpu_ecdsa_is_low_s_p384(s48))
+
+
+def p384_pubkey_on_curve(qx48: bytes, qy48: bytes) -> bool:
+    return bool(load().fabgpu_p384_pubkey_on_curve(qx48, qy48))
+
+
+def hash_to_int_p384(digest: bytes) -> bytes:
+    e = ctypes.create_string_buffer(48)
+    load().fabgpu_hash_to_int_p384(digest, len(digest), e)
+    return e.raw
 
 
 def is_low_s(s32: bytes) -> bool:
@@ -505,6 +548,37 @@ class Context:
     def sha3_256_p256_verify_batch_keyed_dev(self, n, arena, arena_bytes, off, key_id, r, s, verdict_bits, status, stream=0):
         _check(self._L.fabgpu_sha3_256_p256_verify_batch_keyed_dev(self._h, n, arena, arena_bytes, off, key_id, r, s, verdict_bits,
                                                                     status or None, stream or None), "fabgpu_sha3_256_p256_verify_batch_keyed_dev")
+
+    # ECDSA P-384 (fresh keys, direct calls): every field n x 48 bytes big-endian
+    def p384_verify_batch(self, qx, qy, e, r, s, want_status=True):
+        qx, qy, e, r, s = map(_a8, (qx, qy, e, r, s))
+        n = qx.size // 48
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8) if want_status else None
+        _check(self._L.fabgpu_p384_verify_batch(self._h, n, _p8(qx), _p8(qy), _p8(e), _p8(r), _p8(s), bits.ctypes.data_as(_u64p), _p8(st)),
+               "fabgpu_p384_verify_batch")
+        return unpack_bits(bits, n), st
+
+    def p384_verify_batch_dev(self, n, qx, qy, e, r, s, verdict_bits, status, stream=0):
+        _check(self._L.fabgpu_p384_verify_batch_dev(self._h, n, qx, qy, e, r, s, verdict_bits, status or None, stream or None),
+               "fabgpu_p384_verify_batch_dev")
+
+    def hash_p384_verify_batch(self, arena, off, qx, qy, r, s, sha3=False, want_status=True):
+        """identity.Verify for P-384 identities: SHA-256 (sha3: SHA3-256) launch, then the P-384 kernel over the 256-bit digests."""
+        arena, qx, qy, r, s = map(_a8, (arena, qx, qy, r, s))
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        n = off.size - 1
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8) if want_status else None
+        fn = self._L.fabgpu_sha3_256_p384_verify_batch if sha3 else self._L.fabgpu_sha256_p384_verify_batch
+        _check(fn(self._h, n, _p8(arena), off.ctypes.data_as(_u32p), _p8(qx), _p8(qy), _p8(r), _p8(s), bits.ctypes.data_as(_u64p), _p8(st)),
+               "fabgpu_sha3_256_p384_verify_batch" if sha3 else "fabgpu_sha256_p384_verify_batch")
+        return unpack_bits(bits, n), st
+
+    def hash_p384_verify_batch_dev(self, n, arena, arena_bytes, off, qx, qy, r, s, verdict_bits, status, stream=0, sha3=False):
+        fn = self._L.fabgpu_sha3_256_p384_verify_batch_dev if sha3 else self._L.fabgpu_sha256_p384_verify_batch_dev
+        _check(fn(self._h, n, arena, arena_bytes, off, qx, qy, r, s, verdict_bits, status or None, stream or None),
+               "fabgpu_sha3_256_p384_verify_batch_dev" if sha3 else "fabgpu_sha256_p384_verify_batch_dev")
 
     # registered public keys (bccsp.KeyImport): a comb table per key on the device, verification without doublings
     def key_register(self, qx32: bytes, qy32: bytes) -> int:
@@ -804,7 +878,7 @@ class GPUCSP:
     """The accelerated verbs of bccsp.BCCSP (bccsp/bccsp.go:90-134); everything else the Go provider delegates to bccsp/sw."""
 
     def __init__(self, device: int = -1, devices: Optional[Sequence[int]] = None, flags: int = 0, concurrent_passes: int = 0,
-                 expect_block_bytes: int = 0, expect_tuples: int = 0, retire_evicted_keys: int = 0, hash_sha3: int = 0, **switches):
+                 expect_block_bytes: int = 0, expect_tuples: int = 0, retire_evicted_keys: int = 0, hash_sha3: int = 0, p384: int = 0, **switches):
         """device: ONE context on that HIP ordinal (fabgpu_csp_new).  devices: one context per entry - an ordinal may repeat; an empty
         list means every visible device - behind ONE provider (fabgpu_csp_new2: what bccsp/factory builds from the `GPU:` section).
         switches: pass_device_walk / pass_stage_min_bytes / pass_device_memo / pass_host_counts / pass_timing / pass_hash_memo (0 default,
@@ -837,6 +911,8 @@ class GPUCSP:
             self.set_option("retire_evicted_keys", retire_evicted_keys)
         if hash_sha3:
             self.set_option("hash_sha3", hash_sha3)
+        if p384:                          # (0, the default: the *_p384 calls answer that bccsp/sw serves P-384)
+            self.set_option("p384", p384)
 
     def device_count(self) -> int:
         """Device contexts behind this provider."""
@@ -954,6 +1030,50 @@ class GPUCSP:
         if err.value:
             raise BCCSPError(err.value.decode())
         return bool(valid.value)
+
+    # ---- ECDSA P-384 identities (option p384): keys are (x, y) integer pairs ----
+    def verify_coalesced_p384(self, key: Optional[Tuple[int, int]], signature: bytes, digest: bytes) -> bool:
+        """CSP.Verify for a P-384 key through a coalescer of its own (fabgpu_csp_verify_coalesced_p384); raises BCCSPError with the error
+        text, the refusal text when the p384 option is off."""
+        valid = ctypes.c_int(0)
+        flags = ctypes.c_int(0)
+        err = ctypes.create_string_buffer(1024)
+        qx, qy = (None, None) if key is None else (key[0].to_bytes(48, "big"), key[1].to_bytes(48, "big"))
+        _check(self._L.fabgpu_csp_verify_coalesced_p384(self._h, qx, qy, signature, len(signature), digest, len(digest), ctypes.byref(valid),
+                                                        ctypes.byref(flags), err, 1024), "fabgpu_csp_verify_coalesced_p384")
+        if err.value:
+            raise BCCSPError(err.value.decode())
+        return bool(valid.value)
+
+    def verify_batch_p384(self, keys: Sequence[Tuple[int, int]], sigs: Sequence[bytes], digests: Sequence[bytes], hash_family: str = "SHA2"):
+        """n independent CSP.Verify calls on P-384 keys in one launch: list of (valid, error-text-or-None)."""
+        n = len(keys)
+        qx = np.frombuffer(b"".join(k[0].to_bytes(48, "big") for k in keys), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
+        qy = np.frombuffer(b"".join(k[1].to_bytes(48, "big") for k in keys), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
+        sa, so = _ragged(sigs)
+        da, do = _ragged(digests)
+        valid = np.zeros(n, np.uint8)
+        stride = 512
+        errs = ctypes.create_string_buffer(max(1, n * stride))
+        _check(self._L.fabgpu_csp_verify_batch_p384(self._h, n, _p8(qx), _p8(qy), _p8(sa), so.ctypes.data_as(_u32p), _p8(da),
+                                                    do.ctypes.data_as(_u32p), hash_family.encode(), _p8(valid), errs, stride),
+               "fabgpu_csp_verify_batch_p384")
+        return [(bool(valid[i]), errs.raw[i * stride:(i + 1) * stride].split(b"\0", 1)[0].decode() or None) for i in range(n)]
+
+    def identity_verify_batch_p384(self, keys: Sequence[Tuple[int, int]], msgs: Sequence[bytes], sigs: Sequence[bytes],
+                                   hash_family: str = "SHA2") -> List[Optional[str]]:
+        """identity.Verify for n P-384 identities of an MSP of the given hash family: None (nil) or the error text."""
+        n = len(keys)
+        qx = np.frombuffer(b"".join(k[0].to_bytes(48, "big") for k in keys), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
+        qy = np.frombuffer(b"".join(k[1].to_bytes(48, "big") for k in keys), dtype=np.uint8).copy() if n else np.zeros(0, np.uint8)
+        ma, mo = _ragged(msgs)
+        sa, so = _ragged(sigs)
+        stride = 512
+        errs = ctypes.create_string_buffer(max(1, n * stride))
+        _check(self._L.fabgpu_csp_identity_verify_batch_p384(self._h, n, _p8(qx), _p8(qy), _p8(ma), mo.ctypes.data_as(_u32p), _p8(sa),
+                                                             so.ctypes.data_as(_u32p), hash_family.encode(), errs, stride),
+               "fabgpu_csp_identity_verify_batch_p384")
+        return [(errs.raw[i * stride:(i + 1) * stride].split(b"\0", 1)[0].decode() or None) for i in range(n)]
 
     def identity_verify_coalesced(self, k: Optional[ECDSAPublicKey], msg: bytes, signature: bytes, hash_family: str = "SHA2") -> Optional[str]:
         """identity.Verify(msg, sig) through the coalescer: None (nil) or the error text.  hash_family: the MSP's ("SHA2"; "SHA3" with
@@ -1298,6 +1418,11 @@ def audit_sample(permille: int, n_hits: int) -> np.ndarray:
     n = load_hooks().fabgpu_test_audit_sample(permille, n_hits, _p8(a))
     assert n == int(a[:n_hits].sum())
     return a[:n_hits].astype(bool)
+
+
+def p384_corrupt(csp: "GPUCSP", count: int) -> None:
+    """TEST HOOK: the provider reads the device's next `count` P-384 arithmetic rejects as "valid" (fabgpu_csp_test_p384_corrupt)."""
+    load_hooks().fabgpu_csp_test_p384_corrupt(csp._h, count)
 
 
 def memo_corrupt(csp: "GPUCSP", block_seq: int, kind: int, index: int) -> int:

@@ -74,6 +74,9 @@ type GPUOpts struct {
 	// (fabgpu_bccsp.h option "hash_sha3").  Unset means true; `SHA3: false` leaves the family to bccsp/sw.  The block pass hashes with
 	// SHA-256 either way: a SHA3 MSP's signatures are decided by bccsp/sw behind it.
 	SHA3 *bool `mapstructure:"sha3" json:"sha3,omitempty" yaml:"SHA3,omitempty"`
+	// P384: Verify on an ECDSA P-384 key asks the device first (fabgpu_bccsp.h option "p384", fabgpu_csp_verify_coalesced_p384) and takes
+	// only "valid" from it.  Default false: P-384 keys stay with bccsp/sw.  The block pass leaves P-384 endorsers to bccsp/sw either way.
+	P384 bool `mapstructure:"p384" json:"p384,omitempty" yaml:"P384,omitempty"`
 }
 
 // DefaultAuditPermille is what GPUOpts.AuditPermille means when the `GPU:` section does not set it.
@@ -110,6 +113,7 @@ func (f *GPUFactory) Get(config *FactoryOpts) (bccsp.BCCSP, error) {
 		opts = gpu.Options{Devices: g.Devices, ConcurrentPasses: g.ConcurrentPasses, ExpectBlockBytes: g.ExpectBlockBytes,
 			ExpectTuples: g.ExpectTuples, MemoBlocks: g.MemoBlocks, HostWalk: g.HostWalk, PassTiming: g.PassTiming,
 			NoHashMemo: g.NoHashMemo, HashMemoBlocks: g.HashMemoBlocks, KeyTables16: g.KeyTables16, AuditPermille: DefaultAuditPermille, RetireEvictedKeys: true, SHA3: true}
+		opts.P384 = g.P384
 		if g.SHA3 != nil {
 			opts.SHA3 = *g.SHA3
 		}

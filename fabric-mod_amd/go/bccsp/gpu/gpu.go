@@ -91,6 +91,10 @@ type Provider struct {
 	// orderer (Broadcast handlers behind SigFilter, orderer/common/msgprocessor/sigfilter.go:50-80).  Off by default: a
 	// lone call costs a launch (0.7 ms) where bccsp/sw costs 0.1 ms; the break-even is about sixteen calls in flight.
 	coalesce bool
+	// p384: Options.P384 - Verify on a P-384 key asks the device first (fabgpu_csp_verify_coalesced_p384); keys384 remembers the
+	// coordinates of the P-384 public keys KeyImport has seen, by SKI (string(ski) -> *[96]byte)
+	p384    bool
+	keys384 sync.Map
 	// noHashMemo: Options.NoHashMemo - Hash goes straight to bccsp/sw
 	noHashMemo bool
 	// poisoned (atomic, 0 / 1): the library's CPU audit disagreed with the device once (Options.AuditPermille; fabgpu_bccsp.h "CPU
@@ -145,6 +149,11 @@ type Options struct {
 	// bccsp/sw whatever this says (Provider.Hash).  Not served: the block pass, which hashes with SHA-256 - a SHA3 MSP's signatures come
 	// back "not valid" from it and are decided by bccsp/sw.  GPUFactory passes true unless the operator says otherwise.
 	SHA3 bool
+	// P384: Verify on an ECDSA P-384 key (bccsp/sw accepts them exactly as P-256 keys, bccsp/sw/keyimport.go, ecdsa.go:41-57) goes to the
+	// device through fabgpu_csp_verify_coalesced_p384 (option "p384") and takes only "valid" from it; everything else, and every error
+	// text, stays bccsp/sw's.  False (the default, also GPUFactory's): a P-384 key flows through untouched.  The block pass never
+	// serves P-384 (TX_NEEDS_SW), whatever this says.
+	P384 bool
 }
 
 // SetCoalesce switches the coalesced device path for memo misses on or off (GPUOpts.CoalesceVerify in gpufactory.go).
@@ -280,6 +289,15 @@ func New(swCSP bccsp.BCCSP, opts Options) (bccsp.BCCSP, error) {
 			return nil, errors.Errorf("Failed initializing GPU BCCSP: hash_sha3: %s", C.GoString(C.fabgpu_strerror(rc)))
 		}
 	}
+	if opts.P384 {
+		name := C.CString("p384")
+		rc := C.fabgpu_csp_set_option(csp, name, 1, nil)
+		C.free(unsafe.Pointer(name))
+		if rc != 0 {
+			C.fabgpu_csp_free(csp)
+			return nil, errors.Errorf("Failed initializing GPU BCCSP: p384: %s", C.GoString(C.fabgpu_strerror(rc)))
+		}
+	}
 	if opts.MemoBlocks > 0 {
 		// (peer.gossip.state.blockBufferSize blocks may be waiting for their validators: the memo must hold them all, or it drops the
 		// oldest - the block the committer needs next - and every block of a catch-up is passed twice)
@@ -295,7 +313,7 @@ func New(swCSP bccsp.BCCSP, opts Options) (bccsp.BCCSP, error) {
 	if opts.ExpectTuples > 1024 {
 		capTx = uint32(opts.ExpectTuples)
 	}
-	return &Provider{BCCSP: swCSP, csp: csp, capTx: capTx, noHashMemo: opts.NoHashMemo}, nil
+	return &Provider{BCCSP: swCSP, csp: csp, capTx: capTx, noHashMemo: opts.NoHashMemo, p384: opts.P384}, nil
 }
 
 // Devices: how many device contexts this provider drives.
@@ -424,6 +442,17 @@ func (p *Provider) KeyImport(raw interface{}, opts bccsp.KeyImportOpts) (bccsp.K
 	case *bccsp.ECDSAGoPublicKeyImportOpts:
 		pub, _ = raw.(*ecdsa.PublicKey)
 	}
+	if p.p384 && pub != nil && pub.Curve == elliptic.P384() && pub.X != nil && pub.Y != nil {
+		// Options.P384: remember an on-curve P-384 key's coordinates for Verify; the key itself stays bccsp/sw's own, as below
+		if pub.X.Sign() >= 0 && pub.Y.Sign() >= 0 && pub.X.BitLen() <= 384 && pub.Y.BitLen() <= 384 && pub.Curve.IsOnCurve(pub.X, pub.Y) {
+			var xy [96]byte
+			bx, by := pub.X.Bytes(), pub.Y.Bytes() // (no big.Int.FillBytes in Go 1.14; BitLen <= 384 was checked)
+			copy(xy[48-len(bx):48], bx)
+			copy(xy[96-len(by):], by)
+			p.keys384.Store(string(k.SKI()), &xy)
+		}
+		return k, nil
+	}
 	if pub == nil || pub.Curve != elliptic.P256() || pub.X == nil || pub.Y == nil {
 		return k, nil // not ours: sw handles it
 	}
@@ -481,6 +510,24 @@ func (p *Provider) Verify(k bccsp.Key, signature, digest []byte, opts bccsp.Sign
 				if rc == C.FABGPU_EPOISONED { // this call's audit failed, or an earlier one: bccsp/sw below, and from now on
 					p.markPoisoned()
 				}
+			}
+		}
+	}
+	if p.p384 && k != nil && !k.Symmetric() && len(signature) != 0 && len(digest) != 0 && atomic.LoadUint32(&p.poisoned) == 0 {
+		if v, ok := p.keys384.Load(string(k.SKI())); ok {
+			// a P-384 identity (Options.P384): no memo holds it - the block pass leaves it to bccsp/sw - so the coalesced entry is asked
+			// directly, and only "valid" is taken from it
+			xy := v.(*[96]byte)
+			var valid, flags C.int
+			var errbuf [8]C.char
+			rc := C.fabgpu_csp_verify_coalesced_p384(p.csp, (*C.uint8_t)(unsafe.Pointer(&xy[0])), (*C.uint8_t)(unsafe.Pointer(&xy[48])),
+				(*C.uint8_t)(unsafe.Pointer(&signature[0])), C.size_t(len(signature)),
+				(*C.uint8_t)(unsafe.Pointer(&digest[0])), C.size_t(len(digest)), &valid, &flags, &errbuf[0], C.size_t(len(errbuf)))
+			if rc == 0 && valid == 1 && errbuf[0] == 0 {
+				return true, nil
+			}
+			if rc == C.FABGPU_EPOISONED {
+				p.markPoisoned()
 			}
 		}
 	}

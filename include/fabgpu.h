@@ -196,6 +196,37 @@ int fabgpu_sha3_256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const
                                                 const void* key_id, const void* r, const void* s, void* verdict_bits, void* status,
                                                 void* stream);
 
+/* ---- ECDSA P-384 (secp384r1): an identity whose certificate carries a P-384 key (bccsp/sw/keyimport.go, ecdsa.go:41-57) ----
+ * Conventions and statuses are those of the P-256 namesakes, with ALL big integers 48 bytes big-endian: field[i] at base + 48*i.
+ * e[i] is fabgpu_hash_to_int_p384(digest): a digest of 48 bytes or fewer is the integer itself, a longer one its leftmost 48 bytes.
+ * Status 2 is decided against the half order of P-384 (utils.IsLowS uses the key's own curve), status 4 means "not a point of P-384".
+ * The hash-then-verify calls run the family's hash launch into a context-owned digest buffer and the P-384 kernel behind it on the
+ * same stream (two launches, no fused kernel); the 32-byte digest enters as a 256-bit e, which is what identity.Verify does for a
+ * P-384 identity: the digest comes from the MSP's hash family, not from the curve.
+ * FIRST CALL.  A context's first P-384 call makes the generator's table (1 440 bytes: one hipMalloc and one synchronous hipMemcpy)
+ * before it queues anything - unlike every other _dev call it then does more than queue on `stream`, and it must not come under
+ * stream capture.  fabgpu_p384_verify_batch_dev with n = 0 (every pointer may be NULL) does exactly that and launches nothing: call it
+ * once, outside a capture and off a latency-sensitive path, and every later call only queues.
+ * FIRST CALL.  A context's first P-384 call makes the generator's table (1 440 bytes: one hipMalloc and one synchronous hipMemcpy)
+ * before it queues anything - unlike every other _dev call it then does more than queue on `stream`, and it must not come under
+ * stream capture.  fabgpu_p384_verify_batch_dev with n = 0 (every pointer but ctx may be NULL) does exactly that and launches nothing:
+ * call it once, outside a capture and off a latency-sensitive path, and every later call only queues.
+ * Fresh keys only.  NOT served: the block pass (a P-384 endorser stays TX_NEEDS_SW), registered keys, fabgpu_multi_*. */
+int fabgpu_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* e, const uint8_t* r,
+                             const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
+int fabgpu_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* qx, const void* qy, const void* e, const void* r, const void* s,
+                                 void* verdict_bits, void* status, void* stream);
+int fabgpu_sha256_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx,
+                                    const uint8_t* qy, const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
+int fabgpu_sha256_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
+                                        const void* qx, const void* qy, const void* r, const void* s, void* verdict_bits,
+                                        void* status, void* stream);
+int fabgpu_sha3_256_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx,
+                                      const uint8_t* qy, const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
+int fabgpu_sha3_256_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
+                                          const void* qx, const void* qy, const void* r, const void* s, void* verdict_bits,
+                                          void* status, void* stream);
+
 /* ---- identity.Verify over a DESCRIBED batch: shared message prefixes, fresh or registered keys ----
  * The endorsements of one transaction all sign  prp || endorser_i  (core/common/validation/statebased/
  * validator_keylevel.go:246-258): the proposal-response payload is a shared PREFIX.  A batch may list m prefixes
@@ -357,6 +388,14 @@ int fabgpu_ecdsa_is_low_s(const uint8_t* s32);
 int fabgpu_p256_pubkey_on_curve(const uint8_t* qx32, const uint8_t* qy32);
 /* hashToInt (Go crypto/ecdsa): leftmost 32 bytes of the digest, left-padded with zeros into e32. */
 void fabgpu_hash_to_int(const uint8_t* digest, size_t len, uint8_t* e32);
+/* The same four for P-384 (48-byte outputs).  fabgpu_ecdsa_unmarshal_signature_p384: the DER rules and return codes of
+ * fabgpu_ecdsa_unmarshal_signature; r48/s48: low 384 bits; *flags bit0: R >= 2^384, bit1: S >= 2^384.  fabgpu_ecdsa_is_low_s_p384:
+ * against the half order of P-384.  fabgpu_hash_to_int_p384: Go 1.14 hashToInt for a 384-bit order - a digest of 48 bytes or fewer
+ * is the integer itself (left-padded), a longer one is cut to its leftmost 48 bytes. */
+int fabgpu_ecdsa_unmarshal_signature_p384(const uint8_t* sig, size_t len, uint8_t* r48, uint8_t* s48, int* flags);
+int fabgpu_ecdsa_is_low_s_p384(const uint8_t* s48);
+int fabgpu_p384_pubkey_on_curve(const uint8_t* qx48, const uint8_t* qy48);
+void fabgpu_hash_to_int_p384(const uint8_t* digest, size_t len, uint8_t* e48);
 
 #ifdef __cplusplus
 }

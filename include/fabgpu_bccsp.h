@@ -77,6 +77,10 @@ int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pa
  * was: "Unsupported 'HashOpt' provided [SHA3_256]", and family "SHA3" answers that bccsp/sw serves it.  NOT served either way: the
  * block pass (it hashes every signed message with SHA-256, so a SHA3 MSP's signatures come back "not valid" from it and their
  * validators' SHA3-256 digests can only miss the verdict memo, never hit a SHA-256 verdict) and the digest memo (SHA-256 only).
+ * "p384" (default off; > 0 on): the *_p384 calls below verify ECDSA P-384 identities on the device.  Off, each of them answers, per item,
+ * "P-384 is served by bccsp/sw, not by the GPU provider" (the identity call behind identity.Verify's "could not determine the validity of
+ * the signature: ") and launches nothing.  NOT served either way: the block pass (a P-384 endorser stays TX_NEEDS_SW), the verdict
+ * and digest memos, registered keys.
  * FABGPU_EINVAL: no such option. */
 int fabgpu_csp_set_option(fabgpu_csp* csp, const char* name, int64_t value, int64_t* previous);
 int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value);
@@ -162,6 +166,22 @@ int fabgpu_csp_identity_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, c
  * reference's text and spelling (msp/identities.go:223) -, FABGPU_OK, nothing launched. */
 int fabgpu_csp_identity_verify_coalesced2(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, const uint8_t* msg, size_t msglen,
                                           const uint8_t* sig, size_t siglen, const char* hash_family, char* err, size_t errcap);
+/* ---- ECDSA P-384 identities (option "p384"; bccsp/sw accepts P-384 keys exactly as P-256 keys: keyimport.go, ecdsa.go:41-57) ----
+ * The argument lists, answers and error texts of fabgpu_csp_verify_coalesced, fabgpu_csp_verify_batch and
+ * fabgpu_csp_identity_verify_batch2, with 48-byte key coordinates (qx[i] at qx + 48*i) and the low-S gate against P-384's half order.
+ * hash_family: the MSP's ("SHA2"; "SHA3" with the hash_sha3 option on; anything else: "hash familiy not recognized [..]" per item) - the
+ * identity call hashes with it (a 32-byte digest enters as a 256-bit e, Go's hashToInt), the digest call only checks it.
+ * The coalesced entry has a queue of its own: P-384 callers share launches with each other only.  "valid" answers are sampled by the CPU
+ * audit like the P-256 ones (re-computed with csrc/p384.h compiled for the host); a disagreement poisons the provider.
+ * *flags bit0 as in fabgpu_csp_verify (the provider does not decide: an off-curve key, or the option is off). */
+int fabgpu_csp_verify_coalesced_p384(fabgpu_csp* csp, const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig, size_t siglen,
+                                     const uint8_t* digest, size_t dlen, int* valid, int* flags, char* err, size_t errcap);
+int fabgpu_csp_verify_batch_p384(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* sig_arena, const uint32_t* sig_off,
+                                 const uint8_t* dig_arena, const uint32_t* dig_off, const char* hash_family, uint8_t* valid, char* errs,
+                                 size_t errstride);
+int fabgpu_csp_identity_verify_batch_p384(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena,
+                                          const uint32_t* msg_off, const uint8_t* sig_arena, const uint32_t* sig_off, const char* hash_family,
+                                          char* errs, size_t errstride);
 int fabgpu_csp_coalescer_configure(fabgpu_csp* csp, uint32_t window_us, uint32_t max_batch);
 int fabgpu_csp_coalescer_stats(fabgpu_csp* csp, uint64_t* calls, uint64_t* launches, uint64_t* largest_batch);
 
