@@ -248,6 +248,15 @@ int fabgpu_csp_identity_verify_coalesced2(fabgpu_csp* csp, const uint8_t* qx32, 
 }
 
 // ---- ECDSA P-384 identities (option p384) ----
+int fabgpu_csp_key_import_p384(fabgpu_csp* csp, const uint8_t* qx48, const uint8_t* qy48, int* on_curve, char* err, size_t errcap) {
+    if (!csp) return FABGPU_EINVAL;
+    ECDSAPublicKey384 k;
+    k.on_curve = false;
+    Error e = csp->csp->KeyImportP384(qx48, qy48, k);
+    put_err(err, errcap, e.ok() ? "" : e.msg);
+    if (on_curve) *on_curve = k.on_curve ? 1 : 0;
+    return FABGPU_OK;
+}
 int fabgpu_csp_verify_coalesced_p384(fabgpu_csp* csp, const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig, size_t siglen,
                                      const uint8_t* digest, size_t dlen, int* valid, int* flags, char* err, size_t errcap) {
     if (!csp || !valid) return FABGPU_EINVAL;

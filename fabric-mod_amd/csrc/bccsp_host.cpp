@@ -1267,7 +1267,41 @@ void GPUCSP::KeyImport384(const uint8_t* qx48, const uint8_t* qy48, ECDSAPublicK
     memcpy(out.y, qy48, 48);
     out.on_curve = p384::pubkey_on_curve(qx48, qy48);
 }
+Error GPUCSP::KeyImportP384(const uint8_t* qx48, const uint8_t* qy48, ECDSAPublicKey384& out) const {
+    if (!qx48 || !qy48) return Error("Invalid raw. It must not be nil.");
+    KeyImport384(qx48, qy48, out);
+    if (!P384Enabled()) return Error(P384RefusalText());
+    if (!out.on_curve) return Error();                        // (as KeyImport: such a key stays with bccsp/sw, nothing is registered)
+    std::lock_guard<std::mutex> lk(reg_mu_);
+    const int G = (int)devs_.size();
+    fabgpu_ctx* cs[kMaxProviderDevices];
+    uint32_t ids[kMaxProviderDevices];
+    for (int g = 0; g < G; g++) cs[g] = devs_[(size_t)g]->ctx;
+    const int rc = fabgpu_p384_key_register_many(cs, G, qx48, qy48, ids);
+    // best effort: a device without the table serves the key on the fresh-key kernel (the choice is made per batch on the batch's device)
+    if (rc != FABGPU_OK && !reg_failure_logged_) {
+        reg_failure_logged_ = true;
+        fprintf(stderr, "fabgpu: a P-384 key table could not be installed on every device (%s); the key verifies on the fresh-key kernel\n", fabgpu_strerror(rc));
+    }
+    return Error();
+}
 namespace {
+// key ids of the submitted items on `ctx` if EVERY submitted item's key is registered there (then the keyed entries apply)
+bool all_registered384(fabgpu_ctx* ctx, size_t n, const std::vector<uint8_t>& submitted, const uint8_t* qx, const uint8_t* qy, std::vector<uint32_t>& ids) {
+    ids.assign(n, 0);
+    uint32_t any = 0;
+    bool have = false;
+    for (size_t i = 0; i < n; i++) {
+        if (!submitted[i]) continue;
+        if (fabgpu_p384_key_lookup(ctx, qx + 48 * i, qy + 48 * i, &ids[i]) != FABGPU_OK) return false;
+        any = ids[i];
+        have = true;
+    }
+    if (!have) return false;
+    for (size_t i = 0; i < n; i++)
+        if (!submitted[i]) ids[i] = any;   // fillers: any registered key, the verdict is ignored
+    return true;
+}
 const char* HALF_ORDER_P384_DECIMAL = "19701003098197239606139520050071806902539869635232723333973452639813829699556631784699478154076147456777216826971321";
 // the low 384 bits of a non-negative value; false: it has more
 bool to_be48(const BigInt& v, uint8_t* out48) {
@@ -1342,7 +1376,12 @@ Error GPUCSP::VerifyBatchP384(const std::vector<VerifyItem384>& items, std::vect
         memcpy(&s[48 * i], g.s, 48);
     }
     if (n == 0) return Error();
-    int rc = fabgpu_p384_verify_batch(flat_ctx(), n, qx.data(), qy.data(), e.data(), r.data(), s.data(), bits.data(), st.data());
+    fabgpu_ctx* ctx = flat_ctx();
+    std::vector<uint32_t> ids;
+    // (a key retired between the lookup and the launch would answer 4 - "internal inconsistency" below; nothing retires a P-384 key here)
+    int rc = all_registered384(ctx, n, submitted, qx.data(), qy.data(), ids)
+                 ? fabgpu_p384_verify_batch_keyed(ctx, n, ids.data(), e.data(), r.data(), s.data(), bits.data(), st.data())
+                 : fabgpu_p384_verify_batch(ctx, n, qx.data(), qy.data(), e.data(), r.data(), s.data(), bits.data(), st.data());
     if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
     for (size_t i = 0; i < n; i++) {
         if (!submitted[i]) continue;
@@ -1392,8 +1431,15 @@ Error GPUCSP::IdentityVerifyBatchP384(const std::vector<IdentityItem384>& items,
     }
     off[n] = (uint32_t)arena.size();
     arena.resize(arena.size() + 8);
-    int rc = sha3 ? fabgpu_sha3_256_p384_verify_batch(flat_ctx(), n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data())
-                  : fabgpu_sha256_p384_verify_batch(flat_ctx(), n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data());
+    fabgpu_ctx* ctx = flat_ctx();
+    std::vector<uint32_t> ids;
+    int rc;
+    if (all_registered384(ctx, n, submitted, qx.data(), qy.data(), ids))
+        rc = sha3 ? fabgpu_sha3_256_p384_verify_batch_keyed(ctx, n, arena.data(), off.data(), ids.data(), r.data(), s.data(), bits.data(), st.data())
+                  : fabgpu_sha256_p384_verify_batch_keyed(ctx, n, arena.data(), off.data(), ids.data(), r.data(), s.data(), bits.data(), st.data());
+    else
+        rc = sha3 ? fabgpu_sha3_256_p384_verify_batch(ctx, n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data())
+                  : fabgpu_sha256_p384_verify_batch(ctx, n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data());
     if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
     for (size_t i = 0; i < n; i++) {
         if (!submitted[i]) continue;

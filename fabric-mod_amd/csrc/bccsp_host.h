@@ -213,11 +213,16 @@ class GPUCSP {
     // false, and *err says who serves it.
     bool HashFamily(const char* family, bool* sha3, std::string* err) const;
     bool Sha3Enabled() const { return hash_sha3_.load(std::memory_order_relaxed); }
-    // ---- ECDSA P-384 identities (option p384; fresh keys, direct calls only: never the block pass, the memos or registered keys) ----
+    // ---- ECDSA P-384 identities (option p384; direct calls only: never the block pass or the memos) ----
     // Answers and error texts are those of the P-256 namesakes.  With the option off every item answers P384RefusalText().
+    // KeyImportP384: bccsp.KeyImport for a P-384 key - KeyImport's texts; an on-curve key gets its comb table on every device of the pool
+    // (fabgpu_p384_key_register_many; best effort), and batches whose submitted items all name registered keys then take the keyed
+    // entries (all_registered384, per batch and per device, as all_registered does for P-256).  Option off: nothing is registered and
+    // the refusal text comes back.  The audit recomputes from the key's coordinates and never reads a table.
     bool P384Enabled() const { return p384_.load(std::memory_order_relaxed); }
     static const char* P384RefusalText();
     static void KeyImport384(const uint8_t* qx48, const uint8_t* qy48, ECDSAPublicKey384& out);
+    Error KeyImportP384(const uint8_t* qx48, const uint8_t* qy48, ECDSAPublicKey384& out) const;
     Error VerifyBatchP384(const std::vector<VerifyItem384>& items, std::vector<VerifyResult>& results) const;
     Error IdentityVerifyBatchP384(const std::vector<IdentityItem384>& items, std::vector<std::string>& out, bool sha3) const;
     VerifyResult VerifyCoalescedP384(const ECDSAPublicKey384* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) const;

@@ -332,6 +332,9 @@ int key_register_batch(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key
 int64_t gtab_compare_with_host(fabgpu_ctx* ctx);   // TEST HOOK support: first differing word of the generator comb vs the host builder's, -1 = identical
 int64_t key_tables16_check(fabgpu_ctx* ctx, uint32_t key_id);   // TEST HOOK support: waits for the 16-bit key tables, cross-checks one against the key's 8-bit table
 int key_table_copy(fabgpu_ctx* ctx, uint32_t key_id, int32_t* out);   // TEST HOOK support: a registered key's device table, to the host
+// ... a registered P-384 key's comb table (generator != 0: the generator's), CombTab384::TABLE_WORDS words; a batch of P-384 keys in one build
+int p384_key_table_copy(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint32_t* out);
+int p384_key_register_batch_hook(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key_ids);
 int key_register_many_prebuilt(fabgpu_ctx* const* ctxs, int n, const uint8_t* qx32, const uint8_t* qy32, const int32_t* table, uint32_t* key_ids);
 // the duration of the last timed launch of a FABGPU_FLAG_TIME_KERNELS context (ms; < 0: none) - read by the test-hook library
 float ctx_last_kernel_ms(fabgpu_ctx* ctx);

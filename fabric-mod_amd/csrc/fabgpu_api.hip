@@ -29,6 +29,8 @@
 #include "bn_tables29.h"
 #include "p256_tables29.h"
 #include "p384.h"
+#include "p384_keys.h"
+#include "p384_tables.h"
 
 using namespace fab;
 
@@ -239,6 +241,45 @@ struct fabgpu_ctx {
     void* d_ktab_scr = nullptr;
     size_t ktab_in_cap = 0, ktab_scr_cap = 0;
     hipStream_t stream_keytab = nullptr;
+    // Registered P-384 keys (p384_keys.h has the book, p384_keytab_kernels.hip the builder, p384_keyed_kernels.hip the reader).  One comb
+    // table of 1.125 MiB per key, allocated at its registration; the generator's comb is the same builder run on G at the first
+    // registration or keyed call - a context that never meets a registered P-384 key allocates none of this.
+    // A keyed launch is handed d_snap384: the book's snapshot, written completely (and waited for) by the registration or retirement
+    // that changed the book, before it replaces the previous array, and never edited afterwards.  Nothing is published under a running
+    // launch.  What a change of the book leaves behind - the previous snapshot array, and a retired key's slot and table - passes one wait
+    // before it is used again (Drain384): at a moment when no launcher is between taking (d_snap384, snap384_n) and its keyed enqueue
+    // (k384_launchers == 0; k384_mu is held, so nobody takes the old array any more) events are recorded on every stream that has carried
+    // a keyed launch, and those events have completed.  Drains advance on the registration, retirement and stats paths, never on a verify
+    // call; a registration whose slot - the lowest reclaimable one, always (key_slots.h) - is still draining waits for that slot.
+    // Lock order: k384_build_mu, k384_mu, k384_lm.
+    std::mutex k384_mu;
+    fab::P384KeyBook k384;
+    uint32_t* d_gcomb384 = nullptr;
+    const fab::P384SlotSnap* d_snap384 = nullptr;
+    uint32_t snap384_n = 0;                  // the high-water mark d_snap384 was taken at
+    size_t snap384_cap = 0;                  // (slots) of d_snap384
+    struct Snap384Room { void* p; size_t cap; };
+    std::vector<Snap384Room> snap384_free;   // drained snapshot arrays (nothing is freed before shutdown: hipFree waits for the device)
+    std::vector<void*> k384_allocs;          // every table and snapshot array ever made
+    uint64_t k384_n_tables = 0, k384_snap_bytes = 0;   // ... how many of them are tables (the generator's included), and the arrays' bytes
+    std::vector<uint32_t*> k384_tab_free;    // tables of retired keys, drained, and of builds that were not installed
+    struct Drain384 {
+        int64_t slot = -1;                   // -1: only an array to give back
+        uint32_t* tab = nullptr;
+        Snap384Room old_snap{nullptr, 0};
+        bool recorded = false;
+        std::vector<hipEvent_t> evs;
+    };
+    std::vector<Drain384> k384_drains;       // oldest first
+    std::vector<hipStream_t> k384_streams;   // every stream a keyed P-384 launch was queued on
+    std::mutex k384_lm;
+    std::condition_variable k384_cv;
+    int k384_launchers = 0;
+    std::atomic<uint64_t> k384_launches{0};  // keyed P-384 launches queued so far (fabgpu_p384_key_table_stats)
+    std::mutex k384_build_mu;                // one build at a time: the builder's room and stream are one
+    void *d_k384_in = nullptr, *d_k384_scr = nullptr;
+    size_t k384_in_cap = 0, k384_scr_cap = 0;
+    hipStream_t stream_k384 = nullptr;       // the builds, and the few bytes of a snapshot
     // Registered idemix issuers: a fixed-capacity device array of slots (idemix_kernels.hip IssuerDev); a slot is written
     // before n_issuers is raised, so launches in flight never read a half-written one.
     std::mutex imu;
@@ -569,6 +610,12 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
         if (ctx->d_ktab_scr) hipFree(ctx->d_ktab_scr);
         if (ctx->stream_keytab) hipStreamDestroy(ctx->stream_keytab);
         if (ctx->stream_kslot) hipStreamDestroy(ctx->stream_kslot);
+        if (ctx->stream_k384) { hipStreamSynchronize(ctx->stream_k384); hipStreamDestroy(ctx->stream_k384); }
+        for (void* t : ctx->k384_allocs) hipFree(t);                 // (P-384 key tables, the generator's comb, snapshot arrays)
+        if (ctx->d_k384_in) hipFree(ctx->d_k384_in);
+        if (ctx->d_k384_scr) hipFree(ctx->d_k384_scr);
+        for (auto& d : ctx->k384_drains)
+            for (hipEvent_t e : d.evs) hipEventDestroy(e);
         for (auto* t : ctx->itabs) hipFree(t);
         if (ctx->d_issuers) hipFree(ctx->d_issuers);
         ctx->nym.release();
@@ -1597,14 +1644,14 @@ static int hash_verify_host(HashVerifyDev dev, fabgpu_ctx* ctx, size_t n, const 
 }
 
 static int hash_verify_keyed_host(HashVerifyKeyedDev dev, fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
-                                  const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+                                  const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status, size_t field_bytes = 32) {
     if (!ctx || (n && (!off || !key_id || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
     if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     if (!arena && off[n] != off[0]) return FABGPU_EINVAL;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
-    HostStage h(ctx, n);
+    HostStage h(ctx, n, false, field_bytes);
     h.messages(arena, off);
     h.fields(ctx->keyed, HostStage::ID_COLUMN, key_id, {r, s});
     if (h.ready()) h.rc = dev(ctx, n, ctx->arena.d, h.ab, ctx->offs.d, h.ids(), h.field(0), h.field(1), h.dout(), h.dstatus(status), ctx->stream);
@@ -1816,6 +1863,396 @@ int fabgpu_sha256_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* ar
 int fabgpu_sha3_256_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx, const uint8_t* qy,
                                       const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
     return hash_p384_verify_host(fabgpu_sha3_256_p384_verify_batch_dev, ctx, n, arena, off, qx, qy, r, s, verdict_bits, status);
+}
+
+// ---- registered P-384 keys (fabgpu_ctx::k384 has the story) ------------------------------------------------------------------------
+namespace {
+
+struct P384KeyName : std::string {      // qx || qy, 96 bytes
+    P384KeyName(const uint8_t* qx48, const uint8_t* qy48) : std::string((const char*)qx48, 48) { append((const char*)qy48, 48); }
+};
+bool k384_stream(fabgpu_ctx* ctx) {
+    return ctx->stream_k384 || hipStreamCreateWithFlags(&ctx->stream_k384, hipStreamNonBlocking) == hipSuccess;
+}
+// (k384_mu held, the context's device current) one drain as far as it goes without waiting for a launcher or a launch (wait: all the
+// way).  true: done - the table and the array are on the free lists, the slot is reclaimable.
+bool k384_drain_step_locked(fabgpu_ctx* ctx, fabgpu_ctx::Drain384& d, bool wait) {
+    if (!d.recorded) {
+        {
+            std::unique_lock<std::mutex> ll(ctx->k384_lm);
+            if (ctx->k384_launchers != 0 && !wait) return false;
+            ctx->k384_cv.wait(ll, [&] { return ctx->k384_launchers == 0; });
+        }
+        // a stream the caller has destroyed since (a keyed _dev call's stream must be idle by then) refuses the record and is forgotten;
+        // one of the context's own that refuses is waited for instead
+        for (size_t i = 0; i < ctx->k384_streams.size();) {
+            hipStream_t s = ctx->k384_streams[i];
+            hipEvent_t e = nullptr;
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess && hipEventRecord(e, s) == hipSuccess) {
+                d.evs.push_back(e);
+                i++;
+                continue;
+            }
+            (void)hipGetLastError();
+            if (e) hipEventDestroy(e);
+            if (s == ctx->stream) {
+                (void)hipStreamSynchronize(s);
+                (void)hipGetLastError();
+                i++;
+            } else {
+                ctx->k384_streams.erase(ctx->k384_streams.begin() + (long)i);
+            }
+        }
+        d.recorded = true;
+    }
+    while (!d.evs.empty()) {
+        const hipError_t e = wait ? hipEventSynchronize(d.evs.back()) : hipEventQuery(d.evs.back());
+        if (e == hipErrorNotReady) {
+            (void)hipGetLastError();
+            return false;
+        }
+        if (e != hipSuccess) (void)hipGetLastError();      // (a failed device: nothing of it runs any more)
+        hipEventDestroy(d.evs.back());
+        d.evs.pop_back();
+    }
+    if (d.tab) ctx->k384_tab_free.push_back(d.tab);
+    if (d.old_snap.p) ctx->snap384_free.push_back(d.old_snap);
+    if (d.slot >= 0) ctx->k384.slots.drained((uint32_t)d.slot);     // (a parked slot stays parked)
+    return true;
+}
+void k384_drain_advance_locked(fabgpu_ctx* ctx) {
+    for (size_t i = 0; i < ctx->k384_drains.size();) {
+        if (k384_drain_step_locked(ctx, ctx->k384_drains[i], false)) ctx->k384_drains.erase(ctx->k384_drains.begin() + (long)i);
+        else i++;
+    }
+}
+bool k384_drain_wait_slot_locked(fabgpu_ctx* ctx, uint32_t slot) {
+    for (size_t i = 0; i < ctx->k384_drains.size(); i++)
+        if (ctx->k384_drains[i].slot == (int64_t)slot) {
+            if (!k384_drain_step_locked(ctx, ctx->k384_drains[i], true)) return false;
+            ctx->k384_drains.erase(ctx->k384_drains.begin() + (long)i);
+            break;
+        }
+    return !ctx->k384.slots.draining(slot);
+}
+// (k384_mu held, the context's device current) the book as it is now becomes the snapshot later launches are handed: a fresh array,
+// written and waited for before it replaces the previous one, which goes into `d` to be drained.  A failure leaves NO snapshot (every
+// keyed row answers 4 until a later change of the book succeeds) - never a stale one.
+int k384_publish_locked(fabgpu_ctx* ctx, fabgpu_ctx::Drain384& d) {
+    const std::vector<fab::P384SlotSnap> snap = ctx->k384.snapshot();
+    d.old_snap = fabgpu_ctx::Snap384Room{(void*)ctx->d_snap384, ctx->snap384_cap};
+    ctx->d_snap384 = nullptr;
+    ctx->snap384_n = 0;
+    ctx->snap384_cap = 0;
+    if (snap.empty()) return FABGPU_OK;
+    fabgpu_ctx::Snap384Room room{nullptr, 0};
+    for (size_t i = 0; i < ctx->snap384_free.size(); i++)
+        if (ctx->snap384_free[i].cap >= snap.size()) {
+            room = ctx->snap384_free[i];
+            ctx->snap384_free.erase(ctx->snap384_free.begin() + (long)i);
+            break;
+        }
+    if (!room.p) {
+        room.cap = 64;
+        while (room.cap < snap.size()) room.cap *= 2;
+        if (ctx->fault == 2 || hipMalloc(&room.p, room.cap * sizeof(fab::P384SlotSnap)) != hipSuccess) return FABGPU_ENOMEM;
+        ctx->k384_allocs.push_back(room.p);
+        ctx->k384_snap_bytes += room.cap * sizeof(fab::P384SlotSnap);
+    }
+    hipError_t e = k384_stream(ctx) ? hipMemcpyAsync(room.p, snap.data(), snap.size() * sizeof(fab::P384SlotSnap), hipMemcpyHostToDevice, ctx->stream_k384)
+                                    : hipErrorLaunchFailure;
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream_k384);      // (`snap` lives on this frame; and no launch is handed a half-written array)
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->snap384_free.push_back(room);
+        return hip_to_rc(e);
+    }
+    ctx->d_snap384 = (const fab::P384SlotSnap*)room.p;
+    ctx->snap384_n = (uint32_t)snap.size();
+    ctx->snap384_cap = room.cap;
+    return FABGPU_OK;
+}
+// (k384_mu held) `d` joins the drains if there is anything in it to wait for
+void k384_drain_push_locked(fabgpu_ctx* ctx, fabgpu_ctx::Drain384&& d) {
+    if (d.slot >= 0 || d.tab || d.old_snap.p) ctx->k384_drains.push_back(std::move(d));
+}
+uint32_t* k384_tab_alloc_locked(fabgpu_ctx* ctx) {
+    if (!ctx->k384_tab_free.empty()) {
+        uint32_t* t = ctx->k384_tab_free.back();
+        ctx->k384_tab_free.pop_back();
+        return t;
+    }
+    void* t = nullptr;
+    if (ctx->fault == 2 || hipMalloc(&t, fab::p384::CombTab384::TABLE_BYTES) != hipSuccess) return nullptr;
+    ctx->k384_allocs.push_back(t);
+    ctx->k384_n_tables++;
+    return (uint32_t*)t;
+}
+// (k384_build_mu held, the context's device current) the comb tables of m points (qxy: m x 96 bytes) into tabs[0 .. m), complete on return
+int k384_build_locked(fabgpu_ctx* ctx, uint32_t m, const uint8_t* qxy, uint32_t* const* tabs) {
+    if (ctx->fault) return ctx->fault == 2 ? FABGPU_ENOMEM : FABGPU_ELAUNCH;
+    const size_t in_bytes = (size_t)96 * m + sizeof(void*) * m, scr_bytes = p384_keytab_scratch_bytes(m);
+    if (ctx->k384_in_cap < in_bytes) {
+        if (ctx->d_k384_in) hipFree(ctx->d_k384_in);
+        ctx->d_k384_in = nullptr;
+        ctx->k384_in_cap = 0;
+        if (hipMalloc(&ctx->d_k384_in, in_bytes * 2) != hipSuccess) return FABGPU_ENOMEM;
+        ctx->k384_in_cap = in_bytes * 2;
+    }
+    if (ctx->k384_scr_cap < scr_bytes) {
+        if (ctx->d_k384_scr) hipFree(ctx->d_k384_scr);
+        ctx->d_k384_scr = nullptr;
+        ctx->k384_scr_cap = 0;
+        if (hipMalloc(&ctx->d_k384_scr, scr_bytes * 2) != hipSuccess) return FABGPU_ENOMEM;
+        ctx->k384_scr_cap = scr_bytes * 2;
+    }
+    if (!k384_stream(ctx)) return FABGPU_ELAUNCH;
+    std::vector<uint8_t> in(in_bytes);
+    memcpy(in.data(), qxy, (size_t)96 * m);
+    memcpy(&in[(size_t)96 * m], tabs, sizeof(void*) * m);
+    hipStream_t st = ctx->stream_k384;
+    hipError_t e = hipMemcpyAsync(ctx->d_k384_in, in.data(), in_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = launch_p384_keytab_build(m, ctx->d_k384_in, (void* const*)((uint8_t*)ctx->d_k384_in + (size_t)96 * m), ctx->d_k384_scr, st);
+    const hipError_t drained = hipStreamSynchronize(st);         // (`in` lives on this frame; a table is complete before anybody learns its address)
+    return hip_to_rc(e != hipSuccess ? e : drained);
+}
+// the generator's comb: the builder run on G, once per context, at the first registration or keyed call
+int p384_gcomb(fabgpu_ctx* ctx) {
+    {
+        std::lock_guard<std::mutex> lk(ctx->k384_mu);
+        if (ctx->d_gcomb384) return FABGPU_OK;
+    }
+    std::lock_guard<std::mutex> blk(ctx->k384_build_mu);
+    uint32_t* t = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->k384_mu);
+        if (ctx->d_gcomb384) return FABGPU_OK;
+        if (!(t = k384_tab_alloc_locked(ctx))) return FABGPU_ENOMEM;
+    }
+    uint8_t g[96];
+    fab::p384::generator_be(g, g + 48);
+    const int rc = k384_build_locked(ctx, 1, g, &t);
+    std::lock_guard<std::mutex> lk(ctx->k384_mu);
+    if (rc != FABGPU_OK) ctx->k384_tab_free.push_back(t);
+    else ctx->d_gcomb384 = t;
+    return rc;
+}
+// n points of the curve (qxy: n x 96 bytes; the caller's gate) registered on one context: one build for those the context does not have
+// yet, ids in the order of qxy (keys the context has keep theirs).  Any failure: nothing was installed that is not complete.
+int p384_key_register_batch(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key_ids) {
+    DeviceGuard g(ctx->device);
+    if (int rc = p384_gcomb(ctx)) return rc;
+    std::lock_guard<std::mutex> blk(ctx->k384_build_mu);
+    std::vector<std::string> names((size_t)n);
+    std::vector<int> todo;                                      // first occurrences of keys the context does not have
+    std::vector<uint32_t*> tabs;
+    auto give_back_locked = [&] {
+        for (uint32_t* t : tabs)
+            if (t) ctx->k384_tab_free.push_back(t);
+    };
+    {
+        std::lock_guard<std::mutex> lk(ctx->k384_mu);
+        for (int i = 0; i < n; i++) {
+            names[(size_t)i].assign((const char*)qxy + 96 * (size_t)i, 96);
+            bool dup = false;
+            uint32_t id;
+            for (int j : todo) dup = dup || names[(size_t)j] == names[(size_t)i];
+            if (!dup && !ctx->k384.lookup(names[(size_t)i], &id)) todo.push_back(i);
+        }
+        if (todo.size() > ctx->k384.slots.room()) return FABGPU_ENOMEM;
+        k384_drain_advance_locked(ctx);
+        for (size_t t = 0; t < todo.size(); t++) {
+            uint32_t* d = k384_tab_alloc_locked(ctx);
+            if (!d) {
+                give_back_locked();
+                return FABGPU_ENOMEM;
+            }
+            tabs.push_back(d);
+        }
+    }
+    const uint32_t m = (uint32_t)todo.size();
+    if (m) {
+        std::vector<uint8_t> keys((size_t)96 * m);
+        for (uint32_t t = 0; t < m; t++) memcpy(&keys[(size_t)96 * t], qxy + 96 * (size_t)todo[t], 96);
+        if (int rc = k384_build_locked(ctx, m, keys.data(), tabs.data())) {
+            std::lock_guard<std::mutex> lk(ctx->k384_mu);
+            give_back_locked();
+            return rc;
+        }
+    }
+    std::lock_guard<std::mutex> lk(ctx->k384_mu);
+    int rc = FABGPU_OK;
+    for (uint32_t t = 0; t < m && rc == FABGPU_OK; t++) {
+        const int64_t slot = ctx->k384.slots.next_slot();
+        if (slot < 0) rc = FABGPU_ENOMEM;
+        else if (ctx->k384.slots.draining((uint32_t)slot) && !k384_drain_wait_slot_locked(ctx, (uint32_t)slot)) rc = FABGPU_ELAUNCH;
+        if (rc != FABGPU_OK) break;
+        ctx->k384.install(names[(size_t)todo[t]], tabs[t]);
+        tabs[t] = nullptr;
+    }
+    give_back_locked();
+    if (m) {
+        fabgpu_ctx::Drain384 d;
+        const int prc = k384_publish_locked(ctx, d);
+        k384_drain_push_locked(ctx, std::move(d));
+        if (rc == FABGPU_OK) rc = prc;
+    }
+    for (int i = 0; i < n && rc == FABGPU_OK; i++)
+        if (!ctx->k384.lookup(names[(size_t)i], &key_ids[i])) rc = FABGPU_ELAUNCH;
+    return rc;
+}
+
+// What a keyed P-384 launch site takes of the book, under k384_mu, and its place among the launchers until its keyed launch is queued
+// (the destructor).  Nothing between the two may take k384_mu.
+struct KeyedSnap384 {
+    fabgpu_ctx* ctx;
+    const fab::P384SlotSnap* snap = nullptr;
+    uint32_t nkeys = 0;
+    const uint32_t* gcomb = nullptr;
+    KeyedSnap384(fabgpu_ctx* c, hipStream_t st) : ctx(c) {
+        std::lock_guard<std::mutex> lk(ctx->k384_mu);
+        snap = ctx->d_snap384;
+        nkeys = ctx->snap384_n;
+        gcomb = ctx->d_gcomb384;
+        if (std::find(ctx->k384_streams.begin(), ctx->k384_streams.end(), st) == ctx->k384_streams.end()) ctx->k384_streams.push_back(st);
+        std::lock_guard<std::mutex> ll(ctx->k384_lm);
+        ctx->k384_launchers++;
+    }
+    ~KeyedSnap384() {
+        std::lock_guard<std::mutex> ll(ctx->k384_lm);
+        if (--ctx->k384_launchers == 0) ctx->k384_cv.notify_all();
+    }
+    KeyedSnap384(const KeyedSnap384&) = delete;
+    KeyedSnap384& operator=(const KeyedSnap384&) = delete;
+};
+
+int p384_verify_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* key_id, const void* e, bool e_is_digest32, const void* r, const void* s,
+                          void* verdict_bits, void* status, hipStream_t st) {
+    if (int rc = p384_gcomb(ctx)) return rc;
+    KeyedSnap384 snap(ctx, st);
+    P384KeyedLaunch v;
+    v.n = (uint32_t)n;
+    v.key_id = key_id; v.e = e; v.e_is_digest32 = e_is_digest32; v.r = r; v.s = s;
+    v.gcomb = snap.gcomb; v.snap = snap.snap; v.nkeys = snap.nkeys;
+    v.verdict_bits = verdict_bits; v.status = status;
+    ctx->k384_launches.fetch_add(1, std::memory_order_relaxed);
+    return timed_launch(ctx, st, 0, [&](void*) { return launch_p384_verify_keyed(v, st); });
+}
+
+int hash_then_p384_keyed_dev(HashDev hash, fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, const void* key_id,
+                             const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
+    if (!ctx || (n && (!arena || !off || !key_id || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (dev_too_big(n, arena_bytes)) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = (hipStream_t)stream;
+    size_t di = 0;
+    void* dig = nullptr;
+    int rc = ctx->acquire_qws(n * 32, &di, &dig, st);
+    if (rc != FABGPU_OK) return rc;
+    rc = hash(ctx, n, arena, arena_bytes, off, dig, stream);
+    if (rc == FABGPU_OK) rc = p384_verify_keyed_dev(ctx, n, key_id, dig, true, r, s, verdict_bits, status, st);
+    ctx->release_qws(di, st);
+    return rc;
+}
+
+}  // namespace
+
+int fabgpu_p384_key_register(fabgpu_ctx* ctx, const uint8_t* qx48, const uint8_t* qy48, uint32_t* key_id) {
+    if (!ctx || !qx48 || !qy48 || !key_id) return FABGPU_EINVAL;
+    if (!fabgpu_p384_pubkey_on_curve(qx48, qy48)) return FABGPU_EINVAL;   // the KeyImport gate: such keys stay with bccsp/sw
+    const P384KeyName k(qx48, qy48);
+    return p384_key_register_batch(ctx, 1, (const uint8_t*)k.data(), key_id);
+}
+
+int fabgpu_p384_key_register_many(fabgpu_ctx* const* ctxs, int n, const uint8_t* qx48, const uint8_t* qy48, uint32_t* key_ids) {
+    if (!ctxs || n <= 0 || !qx48 || !qy48 || !key_ids) return FABGPU_EINVAL;
+    for (int g = 0; g < n; g++)
+        if (!ctxs[g]) return FABGPU_EINVAL;
+    if (!fabgpu_p384_pubkey_on_curve(qx48, qy48)) return FABGPU_EINVAL;
+    const P384KeyName k(qx48, qy48);
+    for (int g = 0; g < n; g++)
+        if (int rc = p384_key_register_batch(ctxs[g], 1, (const uint8_t*)k.data(), &key_ids[g])) return rc;   // (contexts before it keep the key: idempotent)
+    return FABGPU_OK;
+}
+
+int fabgpu_p384_key_lookup(fabgpu_ctx* ctx, const uint8_t* qx48, const uint8_t* qy48, uint32_t* key_id) {
+    if (!ctx || !qx48 || !qy48 || !key_id) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->k384_mu);
+    return ctx->k384.lookup(P384KeyName(qx48, qy48), key_id) ? FABGPU_OK : 1;
+}
+
+int fabgpu_p384_key_count(fabgpu_ctx* ctx) {
+    if (!ctx) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->k384_mu);
+    return (int)ctx->k384.slots.n_live();
+}
+
+int fabgpu_p384_key_unregister(fabgpu_ctx* ctx, uint32_t key_id) {
+    if (!ctx) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->k384_mu);
+    fabgpu_ctx::Drain384 d;
+    if (ctx->k384.retire(key_id, &d.tab)) return 1;
+    d.slot = fab::KeySlots::slot_of(key_id);
+    DeviceGuard g(ctx->device);
+    // launches queued before this moment hold the previous snapshot and answer for the key; none queued from now on can name it
+    (void)k384_publish_locked(ctx, d);
+    k384_drain_push_locked(ctx, std::move(d));
+    k384_drain_advance_locked(ctx);
+    return FABGPU_OK;
+}
+
+int fabgpu_p384_key_table_stats(fabgpu_ctx* ctx, uint64_t* out, int cap) {
+    if (!ctx || (cap > 0 && !out)) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->k384_mu);
+    {
+        DeviceGuard g(ctx->device);
+        k384_drain_advance_locked(ctx);
+    }
+    const uint64_t bytes = ctx->k384_n_tables * (uint64_t)fab::p384::CombTab384::TABLE_BYTES + ctx->k384_snap_bytes;
+    const uint64_t v[FABGPU_P384_KEY_TABLE_STATS] = {ctx->k384.slots.n_live(), ctx->k384.slots.n_draining(), ctx->k384.slots.n_reused(), ctx->k384.slots.n_parked(),
+                                                     ctx->k384_launches.load(std::memory_order_relaxed), bytes, ctx->k384.slots.high_water()};
+    for (int i = 0; i < cap && i < FABGPU_P384_KEY_TABLE_STATS; i++) out[i] = v[i];
+    return FABGPU_P384_KEY_TABLE_STATS;
+}
+
+int fabgpu_p384_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* key_id, const void* e, const void* r, const void* s,
+                                       void* verdict_bits, void* status, void* stream) {
+    if (!ctx || (n && (!key_id || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (dev_too_big(n)) return FABGPU_ETOOBIG;
+    DeviceGuard g(ctx->device);
+    if (n == 0) return p384_gcomb(ctx);            // the explicit warm call (fabgpu.h): the generator's comb, no launch
+    return p384_verify_keyed_dev(ctx, n, key_id, e, false, r, s, verdict_bits, status, (hipStream_t)stream);
+}
+int fabgpu_sha256_p384_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
+                                              const void* key_id, const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
+    return hash_then_p384_keyed_dev(fabgpu_sha256_batch_dev, ctx, n, arena, arena_bytes, off, key_id, r, s, verdict_bits, status, stream);
+}
+int fabgpu_sha3_256_p384_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
+                                                const void* key_id, const void* r, const void* s, void* verdict_bits, void* status, void* stream) {
+    return hash_then_p384_keyed_dev(fabgpu_sha3_256_batch_dev, ctx, n, arena, arena_bytes, off, key_id, r, s, verdict_bits, status, stream);
+}
+
+int fabgpu_p384_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint32_t* key_id, const uint8_t* e, const uint8_t* r, const uint8_t* s,
+                                   uint64_t* verdict_bits, uint8_t* status) {
+    if (!ctx || (n && (!key_id || !e || !r || !s || !verdict_bits))) return FABGPU_EINVAL;
+    if (n > 0x7FFFFFF0ull / 160) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    HostStage h(ctx, n, false, 48);
+    h.fields(ctx->keyed, HostStage::ID_COLUMN, key_id, {e, r, s});
+    if (h.ready())
+        h.rc = fabgpu_p384_verify_batch_keyed_dev(ctx, n, h.ids(), h.field(0), h.field(1), h.field(2), h.dout(), h.dstatus(status), ctx->stream);
+    return h.fetch_verdicts(verdict_bits, status);
+}
+int fabgpu_sha256_p384_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
+                                          const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    return hash_verify_keyed_host(fabgpu_sha256_p384_verify_batch_keyed_dev, ctx, n, arena, off, key_id, r, s, verdict_bits, status, 48);
+}
+int fabgpu_sha3_256_p384_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
+                                            const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status) {
+    return hash_verify_keyed_host(fabgpu_sha3_256_p384_verify_batch_keyed_dev, ctx, n, arena, off, key_id, r, s, verdict_bits, status, 48);
 }
 
 // ---- identity.Verify over a described batch: optional shared prefixes, fresh or registered keys ------------------------
@@ -3494,6 +3931,26 @@ void walk_pinned_free(fabgpu_ctx* ctx, void* p) {
     if (huge) pinned_huge_free(p);
     else (void)hipHostFree(p);
     if (timing) fprintf(stderr, "fabgpu: a memo table's pinned memory freed in %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+}
+
+// TEST HOOK support: the comb table of P-384 key `key_id` (or, generator != 0, the generator's) as it lies on the device
+int p384_key_table_copy(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint32_t* out) {
+    if (!ctx || !out) return FABGPU_EINVAL;
+    const uint32_t* d = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->k384_mu);
+        d = generator ? ctx->d_gcomb384 : ctx->k384.table(key_id);
+    }
+    if (!d) return FABGPU_EINVAL;
+    DeviceGuard g(ctx->device);
+    return hip_to_rc(hipMemcpy(out, d, p384::CombTab384::TABLE_BYTES, hipMemcpyDeviceToHost));
+}
+// ... and a batch of keys (qxy: n x 96 bytes, every one a point of the curve) registered with one build
+int p384_key_register_batch_hook(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key_ids) {
+    if (!ctx || n <= 0 || !qxy || !key_ids) return FABGPU_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!fabgpu_p384_pubkey_on_curve(qxy + 96 * (size_t)i, qxy + 96 * (size_t)i + 48)) return FABGPU_EINVAL;
+    return p384_key_register_batch(ctx, n, qxy, key_ids);
 }
 
 }  // namespace fab

@@ -93,6 +93,25 @@ int fabgpu_test_key_slots_drain(void* h, uint32_t slot);
 void fabgpu_test_key_slots_stats(void* h, uint64_t* out6);
 
 
+/* TEST HOOKS, registered P-384 keys.  key_table: the comb table of key `key_id` (generator != 0: of the generator) as it lies on the
+ * device - 48 windows x 256 entries x 24 words; key_table_host: the table the host builder (p384_tables.h) makes for a key (qx48 or
+ * qy48 NULL: for the generator) - the two must be byte-identical.  verify_keyed_host: p384_tables.h verify_keyed_host over two such
+ * tables in 16-byte aligned host memory (status 0 .. 4).  key_register_batch: n keys (qxy: n x 96 bytes) registered with one build. */
+int fabgpu_test_p384_key_table(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint32_t* out_words, size_t cap_words);
+int fabgpu_test_p384_key_table_host(const uint8_t* qx48, const uint8_t* qy48, uint32_t* out_words, size_t cap_words);
+int fabgpu_test_p384_verify_keyed_host(const uint32_t* gcomb, const uint32_t* qcomb, const uint8_t* e48, const uint8_t* r48, const uint8_t* s48, int key_ok);
+int fabgpu_test_p384_key_register_batch(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key_ids);
+/* ... and a context's book of P-384 keys by itself (csrc/p384_keys.h; no device): register - the id of `name96` (the one it has, or
+ * a new one: a slot still draining is drained on the spot; -1 when no slot can be had) with an opaque tag in the table's place; retire -
+ * 0 retired (*tab_tag: the tag the slot held), 1 not live; snapshot - what a keyed launch would be handed, per slot the tag (0: none)
+ * and the generation (0xFFFFFFFF: none); returns the high-water mark. */
+void* fabgpu_test_p384_book_new(uint32_t gen_last);
+void fabgpu_test_p384_book_free(void* h);
+long long fabgpu_test_p384_book_register(void* h, const uint8_t* name96, uint64_t tab_tag);
+long long fabgpu_test_p384_book_lookup(void* h, const uint8_t* name96);
+int fabgpu_test_p384_book_retire(void* h, uint32_t key_id, uint64_t* tab_tag);
+int fabgpu_test_p384_book_snapshot(void* h, uint64_t* tab_tags, uint32_t* gens, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,25 @@ struct P384Launch {
 size_t p384_workspace_bytes(uint32_t n);
 hipError_t launch_p384_verify(const P384Launch& v, hipStream_t st);
 
+// ---- p384_keytab_kernels.hip / p384_keyed_kernels.hip: registered P-384 keys (p384_tables.h) ----
+// comb tables built on the device (qxy: n_keys x 96 bytes, tabs: n_keys table addresses, both in device memory; see the unit's header)
+size_t p384_keytab_scratch_bytes(uint32_t n_keys);
+hipError_t launch_p384_keytab_build(uint32_t n_keys, const void* qxy, void* const* tabs, void* scratch, hipStream_t st);
+struct P384SlotSnap;   // p384_keys.h: one slot of a keyed launch's snapshot of the context's P-384 keys (table, generation)
+struct P384KeyedLaunch {
+    uint32_t n = 0;
+    const void* key_id = nullptr;            // n x u32: generation << KEY_SLOT_BITS | slot
+    const void *r = nullptr, *s = nullptr;   // n x 48 bytes each, big-endian
+    const void* e = nullptr;                 // n x 48 bytes, or n x 32 bytes of digests (e_is_digest32), as P384Launch takes them
+    bool e_is_digest32 = false;
+    const void* gcomb = nullptr;             // the generator's comb table (CombTab384)
+    const P384SlotSnap* snap = nullptr;      // nkeys slots in device memory, complete before the launch is queued and never edited
+    uint32_t nkeys = 0;                      // the high-water mark the snapshot was taken at
+    void* verdict_bits = nullptr;            // ceil(n/64) x u64
+    void* status = nullptr;                  // n bytes or nullptr
+};
+hipError_t launch_p384_verify_keyed(const P384KeyedLaunch& v, hipStream_t st);
+
 // ---- idemix_kernels.hip: idemix pseudonym signatures on FP256BN ----
 // A registered issuer occupies one slot of idemix_issuer_dev_bytes() bytes in a device array; fill a host copy of the slot
 // with idemix_issuer_dev_fill (device pointers of the two comb tables + ipk.Hash) and copy it up.

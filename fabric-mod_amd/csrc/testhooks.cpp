@@ -14,6 +14,8 @@
 #include "fabgpu_testhooks.h"
 #include "key_slots.h"
 #include "idemix_host.h"
+#include "p384_keys.h"
+#include "p384_tables.h"
 
 using namespace fab::bccsp;
 
@@ -360,5 +362,53 @@ void fabgpu_test_key_slots_stats(void* h, uint64_t* out6) {
     const SlotsProbe& p = *(SlotsProbe*)h;
     out6[0] = p.slots.n_live(); out6[1] = p.slots.n_draining(); out6[2] = p.slots.n_reused();
     out6[3] = p.slots.n_parked(); out6[4] = p.slots.high_water(); out6[5] = p.waits;
+}
+// ---- registered P-384 keys (p384_tables.h, p384_keys.h) ----
+int fabgpu_test_p384_key_table(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint32_t* out_words, size_t cap_words) {
+    if (cap_words < fab::p384::CombTab384::TABLE_WORDS) return FABGPU_ETOOBIG;
+    return fab::p384_key_table_copy(ctx, key_id, generator, out_words);
+}
+int fabgpu_test_p384_key_table_host(const uint8_t* qx48, const uint8_t* qy48, uint32_t* out_words, size_t cap_words) {
+    if (cap_words < fab::p384::CombTab384::TABLE_WORDS || !out_words) return FABGPU_ETOOBIG;
+    if (!qx48 || !qy48) {
+        fab::p384::build_gcomb384(out_words);
+        return FABGPU_OK;
+    }
+    return fab::p384::build_comb384_be(out_words, qx48, qy48) ? FABGPU_OK : FABGPU_EINVAL;
+}
+int fabgpu_test_p384_verify_keyed_host(const uint32_t* gcomb, const uint32_t* qcomb, const uint8_t* e48, const uint8_t* r48, const uint8_t* s48, int key_ok) {
+    if (!gcomb || !qcomb || !e48 || !r48 || !s48 || (((uintptr_t)gcomb | (uintptr_t)qcomb) & 15)) return FABGPU_EINVAL;
+    return (int)fab::p384::verify_keyed_host(gcomb, qcomb, e48, r48, s48, key_ok != 0);
+}
+int fabgpu_test_p384_key_register_batch(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key_ids) { return fab::p384_key_register_batch_hook(ctx, n, qxy, key_ids); }
+void* fabgpu_test_p384_book_new(uint32_t gen_last) { return new fab::P384KeyBook(gen_last); }
+void fabgpu_test_p384_book_free(void* h) { delete (fab::P384KeyBook*)h; }
+long long fabgpu_test_p384_book_register(void* h, const uint8_t* name96, uint64_t tab_tag) {
+    fab::P384KeyBook& b = *(fab::P384KeyBook*)h;
+    const std::string name((const char*)name96, 96);
+    uint32_t id = 0;
+    if (b.lookup(name, &id)) return (long long)id;
+    const int64_t slot = b.slots.next_slot();
+    if (slot < 0) return -1;
+    b.slots.drained((uint32_t)slot);          // (a context waits for the slot's launches here)
+    return (long long)b.install(name, (uint32_t*)(uintptr_t)tab_tag);
+}
+long long fabgpu_test_p384_book_lookup(void* h, const uint8_t* name96) {
+    uint32_t id = 0;
+    return ((fab::P384KeyBook*)h)->lookup(std::string((const char*)name96, 96), &id) ? (long long)id : -1;
+}
+int fabgpu_test_p384_book_retire(void* h, uint32_t key_id, uint64_t* tab_tag) {
+    uint32_t* t = nullptr;
+    const int rc = ((fab::P384KeyBook*)h)->retire(key_id, &t);
+    if (tab_tag) *tab_tag = (uint64_t)(uintptr_t)t;
+    return rc;
+}
+int fabgpu_test_p384_book_snapshot(void* h, uint64_t* tab_tags, uint32_t* gens, int cap) {
+    const std::vector<fab::P384SlotSnap> s = ((fab::P384KeyBook*)h)->snapshot();
+    for (int k = 0; k < cap && k < (int)s.size(); k++) {
+        tab_tags[k] = (uint64_t)(uintptr_t)s[(size_t)k].tab;
+        gens[k] = s[(size_t)k].gen;
+    }
+    return (int)s.size();
 }
 }  // extern "C"

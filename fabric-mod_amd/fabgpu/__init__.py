@@ -108,6 +108,9 @@ class _Cfg(ctypes.Structure):
 
 # what fabgpu_p256_key_table_stats reports, in order
 KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "live_16bit", "bytes_held", "slots_used")
+# ... and fabgpu_p384_key_table_stats
+P384_KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "keyed_launches", "bytes_held", "slots_used")
+P384_COMB_WORDS = 48 * 256 * 24      # one P-384 comb table (csrc/p384_tables.h CombTab384): 1.125 MiB
 
 # every symbol include/fabgpu.h and include/fabgpu_bccsp.h declare (tests check the export list)
 ABI_SYMBOLS = [
@@ -143,6 +146,10 @@ ABI_SYMBOLS = [
     "fabgpu_csp_hash_lookup", "fabgpu_csp_hash_memo_stats",
     "fabgpu_csp_poison", "fabgpu_csp_poisoned", "fabgpu_csp_audit_stats",
     "fabgpu_p256_key_unregister", "fabgpu_p256_key_unregister_many", "fabgpu_p256_key_table_stats", "fabgpu_csp_key_table_stats",
+    "fabgpu_p384_key_register", "fabgpu_p384_key_register_many", "fabgpu_p384_key_lookup", "fabgpu_p384_key_count", "fabgpu_p384_key_unregister",
+    "fabgpu_p384_key_table_stats", "fabgpu_p384_verify_batch_keyed", "fabgpu_p384_verify_batch_keyed_dev",
+    "fabgpu_sha256_p384_verify_batch_keyed", "fabgpu_sha256_p384_verify_batch_keyed_dev",
+    "fabgpu_sha3_256_p384_verify_batch_keyed", "fabgpu_sha3_256_p384_verify_batch_keyed_dev", "fabgpu_csp_key_import_p384",
 ]
 
 # what libfabgpu_testhooks.so exports (fabric-mod_amd/csrc/fabgpu_testhooks.h): probes, walker comparisons, the synthetic block generator, the
@@ -154,6 +161,9 @@ HOOK_SYMBOLS = [
     "fabgpu_test_audit_sha256", "fabgpu_test_audit_p256_verify", "fabgpu_test_audit_nym_verify", "fabgpu_test_audit_sample", "fabgpu_csp_test_memo_corrupt", "fabgpu_csp_test_p384_corrupt", "fabgpu_test_p384_refusal_text",
     "fabgpu_test_key_slots_new", "fabgpu_test_key_slots_free", "fabgpu_test_key_slots_register", "fabgpu_test_key_slots_retire",
     "fabgpu_test_key_slots_drain", "fabgpu_test_key_slots_stats", "fabgpu_test_walk_buffer_caps",
+    "fabgpu_test_p384_key_table", "fabgpu_test_p384_key_table_host", "fabgpu_test_p384_verify_keyed_host", "fabgpu_test_p384_key_register_batch",
+    "fabgpu_test_p384_book_new", "fabgpu_test_p384_book_free", "fabgpu_test_p384_book_register", "fabgpu_test_p384_book_lookup",
+    "fabgpu_test_p384_book_retire", "fabgpu_test_p384_book_snapshot",
 ]
 _HOOKS_PATH = os.path.join(os.path.dirname(_LIB_PATH), "libfabgpu_testhooks.so")
 
@@ -214,6 +224,20 @@ def load_hooks():
     H.fabgpu_test_key_slots_drain.argtypes = [_vp, ctypes.c_uint32]
     H.fabgpu_test_key_slots_stats.argtypes = [_vp, _u64p]
     H.fabgpu_test_key_slots_stats.restype = None
+    H.fabgpu_test_p384_key_table.argtypes = [_vp, ctypes.c_uint32, ctypes.c_int, _u32p, _sz]
+    H.fabgpu_test_p384_key_table_host.argtypes = [ctypes.c_char_p, ctypes.c_char_p, _u32p, _sz]
+    H.fabgpu_test_p384_verify_keyed_host.argtypes = [_u32p, _u32p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]
+    H.fabgpu_test_p384_key_register_batch.argtypes = [_vp, ctypes.c_int, ctypes.c_char_p, _u32p]
+    H.fabgpu_test_p384_book_new.argtypes = [ctypes.c_uint32]
+    H.fabgpu_test_p384_book_new.restype = _vp
+    H.fabgpu_test_p384_book_free.argtypes = [_vp]
+    H.fabgpu_test_p384_book_free.restype = None
+    H.fabgpu_test_p384_book_register.argtypes = [_vp, ctypes.c_char_p, ctypes.c_uint64]
+    H.fabgpu_test_p384_book_register.restype = ctypes.c_longlong
+    H.fabgpu_test_p384_book_lookup.argtypes = [_vp, ctypes.c_char_p]
+    H.fabgpu_test_p384_book_lookup.restype = ctypes.c_longlong
+    H.fabgpu_test_p384_book_retire.argtypes = [_vp, ctypes.c_uint32, _u64p]
+    H.fabgpu_test_p384_book_snapshot.argtypes = [_vp, _u64p, _u32p, ctypes.c_int]
     _hooks = H
     return H
 
@@ -267,6 +291,18 @@ def load():
     L.fabgpu_sha256_p384_verify_batch_dev.argtypes = L.fabgpu_sha256_p256_verify_batch_dev.argtypes
     L.fabgpu_sha3_256_p384_verify_batch.argtypes = L.fabgpu_sha256_p256_verify_batch.argtypes
     L.fabgpu_sha3_256_p384_verify_batch_dev.argtypes = L.fabgpu_sha256_p256_verify_batch_dev.argtypes
+    L.fabgpu_p384_key_register.argtypes = L.fabgpu_p256_key_register.argtypes
+    L.fabgpu_p384_key_register_many.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, _u32p]
+    L.fabgpu_p384_key_lookup.argtypes = L.fabgpu_p256_key_lookup.argtypes
+    L.fabgpu_p384_key_count.argtypes = [_vp]
+    L.fabgpu_p384_key_unregister.argtypes = [_vp, ctypes.c_uint32]
+    L.fabgpu_p384_key_table_stats.argtypes = [_vp, _u64p, ctypes.c_int]
+    L.fabgpu_p384_verify_batch_keyed.argtypes = L.fabgpu_p256_verify_batch_keyed.argtypes
+    L.fabgpu_p384_verify_batch_keyed_dev.argtypes = L.fabgpu_p256_verify_batch_keyed_dev.argtypes
+    L.fabgpu_sha256_p384_verify_batch_keyed.argtypes = L.fabgpu_sha256_p256_verify_batch_keyed.argtypes
+    L.fabgpu_sha256_p384_verify_batch_keyed_dev.argtypes = L.fabgpu_sha256_p256_verify_batch_keyed_dev.argtypes
+    L.fabgpu_sha3_256_p384_verify_batch_keyed.argtypes = L.fabgpu_sha256_p256_verify_batch_keyed.argtypes
+    L.fabgpu_sha3_256_p384_verify_batch_keyed_dev.argtypes = L.fabgpu_sha256_p256_verify_batch_keyed_dev.argtypes
     L.fabgpu_ecdsa_unmarshal_signature_p384.argtypes = [ctypes.c_char_p, _sz, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
     L.fabgpu_ecdsa_is_low_s_p384.argtypes = [ctypes.c_char_p]
     L.fabgpu_p384_pubkey_on_curve.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
@@ -300,6 +336,7 @@ def load():
     L.fabgpu_csp_ctx.argtypes = [_vp]
     L.fabgpu_csp_ctx.restype = _vp
     L.fabgpu_csp_key_import.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), ctypes.c_char_p, _sz]
+    L.fabgpu_csp_key_import_p384.argtypes = L.fabgpu_csp_key_import.argtypes
     L.fabgpu_csp_hash.argtypes = [_vp, ctypes.c_char_p, _sz, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _sz]
     L.fabgpu_csp_verify.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz,
                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_char_p, _sz]
@@ -579,6 +616,65 @@ class Context:
         fn = self._L.fabgpu_sha3_256_p384_verify_batch_dev if sha3 else self._L.fabgpu_sha256_p384_verify_batch_dev
         _check(fn(self._h, n, arena, arena_bytes, off, qx, qy, r, s, verdict_bits, status or None, stream or None),
                "fabgpu_sha3_256_p384_verify_batch_dev" if sha3 else "fabgpu_sha256_p384_verify_batch_dev")
+
+    # registered P-384 keys: ids of their own (not P-256 ids), a 1.125 MiB comb table per key, built on the device
+    def p384_key_register(self, qx48: bytes, qy48: bytes) -> int:
+        kid = ctypes.c_uint32(0)
+        _check(self._L.fabgpu_p384_key_register(self._h, bytes(qx48), bytes(qy48), ctypes.byref(kid)), "fabgpu_p384_key_register")
+        return int(kid.value)
+
+    def p384_key_count(self) -> int:
+        return self._L.fabgpu_p384_key_count(self._h)
+
+    def p384_key_lookup(self, qx48: bytes, qy48: bytes) -> Optional[int]:
+        kid = ctypes.c_uint32(0)
+        rc = self._L.fabgpu_p384_key_lookup(self._h, bytes(qx48), bytes(qy48), ctypes.byref(kid))
+        if rc < 0:
+            raise FabgpuError("fabgpu_p384_key_lookup: %s" % strerror(rc))
+        return int(kid.value) if rc == 0 else None
+
+    def p384_key_unregister(self, key_id: int) -> bool:
+        rc = self._L.fabgpu_p384_key_unregister(self._h, int(key_id))
+        if rc < 0:
+            raise FabgpuError("fabgpu_p384_key_unregister: %s" % strerror(rc))
+        return rc == 0
+
+    def p384_key_table_stats(self) -> dict:
+        v = (ctypes.c_uint64 * len(P384_KEY_TABLE_STATS))()
+        n = self._L.fabgpu_p384_key_table_stats(self._h, v, len(P384_KEY_TABLE_STATS))
+        if n != len(P384_KEY_TABLE_STATS):
+            raise FabgpuError("fabgpu_p384_key_table_stats: %s" % strerror(n))
+        return dict(zip(P384_KEY_TABLE_STATS, (int(x) for x in v)))
+
+    def p384_verify_batch_keyed(self, key_id, e, r, s, want_status=True):
+        e, r, s = map(_a8, (e, r, s))
+        key_id = np.ascontiguousarray(key_id, dtype=np.uint32)
+        n = key_id.size
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8) if want_status else None
+        _check(self._L.fabgpu_p384_verify_batch_keyed(self._h, n, key_id.ctypes.data_as(_u32p), _p8(e), _p8(r), _p8(s),
+                                                       bits.ctypes.data_as(_u64p), _p8(st)), "fabgpu_p384_verify_batch_keyed")
+        return unpack_bits(bits, n), st
+
+    def p384_verify_batch_keyed_dev(self, n, key_id, e, r, s, verdict_bits, status, stream=0):
+        _check(self._L.fabgpu_p384_verify_batch_keyed_dev(self._h, n, key_id, e, r, s, verdict_bits, status or None, stream or None),
+               "fabgpu_p384_verify_batch_keyed_dev")
+
+    def hash_p384_verify_batch_keyed(self, arena, off, key_id, r, s, sha3=False, want_status=True):
+        arena, r, s = map(_a8, (arena, r, s))
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        key_id = np.ascontiguousarray(key_id, dtype=np.uint32)
+        n = off.size - 1
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8) if want_status else None
+        name = "fabgpu_sha3_256_p384_verify_batch_keyed" if sha3 else "fabgpu_sha256_p384_verify_batch_keyed"
+        _check(getattr(self._L, name)(self._h, n, _p8(arena), off.ctypes.data_as(_u32p), key_id.ctypes.data_as(_u32p), _p8(r), _p8(s),
+                                      bits.ctypes.data_as(_u64p), _p8(st)), name)
+        return unpack_bits(bits, n), st
+
+    def hash_p384_verify_batch_keyed_dev(self, n, arena, arena_bytes, off, key_id, r, s, verdict_bits, status, stream=0, sha3=False):
+        name = "fabgpu_sha3_256_p384_verify_batch_keyed_dev" if sha3 else "fabgpu_sha256_p384_verify_batch_keyed_dev"
+        _check(getattr(self._L, name)(self._h, n, arena, arena_bytes, off, key_id, r, s, verdict_bits, status or None, stream or None), name)
 
     # registered public keys (bccsp.KeyImport): a comb table per key on the device, verification without doublings
     def key_register(self, qx32: bytes, qy32: bytes) -> int:
@@ -1032,6 +1128,22 @@ class GPUCSP:
         return bool(valid.value)
 
     # ---- ECDSA P-384 identities (option p384): keys are (x, y) integer pairs ----
+    def key_import_p384(self, key: Tuple[int, int]) -> Tuple[bool, str]:
+        """BCCSP.KeyImport for a P-384 key (fabgpu_csp_key_import_p384): (on the curve, the error text or "")."""
+        err = ctypes.create_string_buffer(256)
+        on = ctypes.c_int(0)
+        _check(self._L.fabgpu_csp_key_import_p384(self._h, key[0].to_bytes(48, "big"), key[1].to_bytes(48, "big"), ctypes.byref(on), err, 256),
+               "fabgpu_csp_key_import_p384")
+        return bool(on.value), err.value.decode()
+
+    def p384_key_table_stats(self, d: int = 0) -> dict:
+        """fabgpu_p384_key_table_stats of the provider's device d."""
+        v = (ctypes.c_uint64 * len(P384_KEY_TABLE_STATS))()
+        n = self._L.fabgpu_p384_key_table_stats(self._L.fabgpu_csp_ctx_of(self._h, d), v, len(P384_KEY_TABLE_STATS))
+        if n != len(P384_KEY_TABLE_STATS):
+            raise FabgpuError("fabgpu_p384_key_table_stats: %s" % strerror(n))
+        return dict(zip(P384_KEY_TABLE_STATS, (int(x) for x in v)))
+
     def verify_coalesced_p384(self, key: Optional[Tuple[int, int]], signature: bytes, digest: bytes) -> bool:
         """CSP.Verify for a P-384 key through a coalescer of its own (fabgpu_csp_verify_coalesced_p384); raises BCCSPError with the error
         text, the refusal text when the p384 option is off."""
@@ -1418,6 +1530,36 @@ def audit_sample(permille: int, n_hits: int) -> np.ndarray:
     n = load_hooks().fabgpu_test_audit_sample(permille, n_hits, _p8(a))
     assert n == int(a[:n_hits].sum())
     return a[:n_hits].astype(bool)
+
+
+def p384_comb_host(qx48: Optional[bytes] = None, qy48: Optional[bytes] = None) -> np.ndarray:
+    """TEST HOOK: the host builder's comb table for a P-384 key (no key: for the generator), P384_COMB_WORDS uint32 words, 16-byte aligned."""
+    raw = np.zeros(P384_COMB_WORDS + 4, dtype=np.uint32)
+    out = raw[(-raw.ctypes.data // 4) % 4:][:P384_COMB_WORDS]
+    _check(load_hooks().fabgpu_test_p384_key_table_host(qx48, qy48, out.ctypes.data_as(_u32p), out.size), "fabgpu_test_p384_key_table_host")
+    return out
+
+
+def p384_comb_device(ctx: "Context", key_id: int = 0, generator: bool = False) -> np.ndarray:
+    """TEST HOOK: the comb table of a registered P-384 key (generator: of the generator) as it lies on the device."""
+    out = np.zeros(P384_COMB_WORDS, dtype=np.uint32)
+    _check(load_hooks().fabgpu_test_p384_key_table(ctx._h, int(key_id), int(generator), out.ctypes.data_as(_u32p), out.size), "fabgpu_test_p384_key_table")
+    return out
+
+
+def p384_verify_keyed_host(gcomb: np.ndarray, qcomb: np.ndarray, e48: bytes, r48: bytes, s48: bytes, key_ok: bool = True) -> int:
+    """TEST HOOK: csrc/p384_tables.h verify_keyed_host over two tables of p384_comb_host."""
+    st = load_hooks().fabgpu_test_p384_verify_keyed_host(gcomb.ctypes.data_as(_u32p), qcomb.ctypes.data_as(_u32p), e48, r48, s48, int(key_ok))
+    if st < 0:
+        raise FabgpuError("fabgpu_test_p384_verify_keyed_host: %s" % strerror(st))
+    return st
+
+
+def p384_key_register_batch(ctx: "Context", keys: Sequence[Tuple[bytes, bytes]]) -> list:
+    """TEST HOOK: several P-384 keys ((qx48, qy48) pairs) registered on one context with ONE device build; their ids."""
+    ids = (ctypes.c_uint32 * len(keys))()
+    _check(load_hooks().fabgpu_test_p384_key_register_batch(ctx._h, len(keys), b"".join(x + y for x, y in keys), ids), "fabgpu_test_p384_key_register_batch")
+    return [int(i) for i in ids]
 
 
 def p384_corrupt(csp: "GPUCSP", count: int) -> None:

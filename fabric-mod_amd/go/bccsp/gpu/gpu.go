@@ -92,7 +92,8 @@ type Provider struct {
 	// lone call costs a launch (0.7 ms) where bccsp/sw costs 0.1 ms; the break-even is about sixteen calls in flight.
 	coalesce bool
 	// p384: Options.P384 - Verify on a P-384 key asks the device first (fabgpu_csp_verify_coalesced_p384); keys384 remembers the
-	// coordinates of the P-384 public keys KeyImport has seen, by SKI (string(ski) -> *[96]byte)
+	// coordinates of the P-384 public keys KeyImport has seen, by SKI (string(ski) -> *[96]byte); each is registered on the device once
+	// (fabgpu_csp_key_import_p384)
 	p384    bool
 	keys384 sync.Map
 	// noHashMemo: Options.NoHashMemo - Hash goes straight to bccsp/sw
@@ -449,7 +450,11 @@ func (p *Provider) KeyImport(raw interface{}, opts bccsp.KeyImportOpts) (bccsp.K
 			bx, by := pub.X.Bytes(), pub.Y.Bytes() // (no big.Int.FillBytes in Go 1.14; BitLen <= 384 was checked)
 			copy(xy[48-len(bx):48], bx)
 			copy(xy[96-len(by):], by)
-			p.keys384.Store(string(k.SKI()), &xy)
+			if _, seen := p.keys384.LoadOrStore(string(k.SKI()), &xy); !seen {
+				// the key's comb table on every device of the pool: Verify's batches then run on the keyed kernel (best effort - a key
+				// without a table is served by the fresh-key kernel, with the same answers)
+				C.fabgpu_csp_key_import_p384(p.csp, (*C.uint8_t)(unsafe.Pointer(&xy[0])), (*C.uint8_t)(unsafe.Pointer(&xy[48])), nil, nil, 0)
+			}
 		}
 		return k, nil
 	}

@@ -211,7 +211,8 @@ int fabgpu_sha3_256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const
  * before it queues anything - unlike every other _dev call it then does more than queue on `stream`, and it must not come under
  * stream capture.  fabgpu_p384_verify_batch_dev with n = 0 (every pointer but ctx may be NULL) does exactly that and launches nothing:
  * call it once, outside a capture and off a latency-sensitive path, and every later call only queues.
- * Fresh keys only.  NOT served: the block pass (a P-384 endorser stays TX_NEEDS_SW), registered keys, fabgpu_multi_*. */
+ * These six take fresh keys; registered keys follow below.  NOT served: the block pass (a P-384 endorser stays TX_NEEDS_SW),
+ * fabgpu_multi_*. */
 int fabgpu_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* e, const uint8_t* r,
                              const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
 int fabgpu_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* qx, const void* qy, const void* e, const void* r, const void* s,
@@ -226,6 +227,46 @@ int fabgpu_sha3_256_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* 
 int fabgpu_sha3_256_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
                                           const void* qx, const void* qy, const void* r, const void* s, void* verdict_bits,
                                           void* status, void* stream);
+
+/* ---- registered P-384 keys (bccsp.KeyImport of a P-384 key) ----
+ * The P-256 scheme for a P-384 key.  Registering a key builds its comb table on the device once: 48 windows x 256 affine multiples of
+ * 96 bytes, 1.125 MiB per key, allocated at the registration; the generator's table of the same format is built once per context, at
+ * its first registration or keyed call (fabgpu_p384_verify_batch_keyed_dev with n = 0 is the explicit warm call, as for the fresh-key
+ * form).  Batches that name registered keys by id verify with 96 mixed additions and no doubling; statuses and verdict words are
+ * byte-identical to fabgpu_p384_verify_batch on the same (key, e, r, s).
+ * fabgpu_p384_key_register: idempotent per (qx, qy); FABGPU_EINVAL for a point that is not on P-384; FABGPU_ENOMEM when FABGPU_MAX_KEYS
+ * keys are live.  Ids are generation << 12 | slot from an allocator of their own: they are NOT P-256 ids, and the two kinds must not
+ * be mixed.  fabgpu_p384_key_unregister retires a key by the rule of fabgpu_p256_key_unregister: no launch queued after it returns
+ * can name the key (a row that does answers status 4, never another key's verdict), a batch queued before always gets the key's own
+ * verdict, and the slot - under the next generation - and the table serve a later registration once those launches have finished.
+ * A stream handed to a keyed _dev entry point must be idle when the caller destroys it.
+ * fabgpu_p384_key_table_stats: out[0 .. min(cap, FABGPU_P384_KEY_TABLE_STATS)): live keys, slots draining, registrations that reused
+ * a slot, slots parked for good, keyed P-384 launches queued so far, bytes of device memory the tables hold (the generator's
+ * included), slots ever used.  Returns FABGPU_P384_KEY_TABLE_STATS.
+ * NOT served for P-384: 16-bit tables, the block pass, the memos, fabgpu_multi_*. */
+int fabgpu_p384_key_register(fabgpu_ctx* ctx, const uint8_t* qx48, const uint8_t* qy48, uint32_t* key_id);
+/* The same key on n contexts, each building its own table; contexts fed the same sequence of calls hand out the same ids.
+ * key_ids[g] = the key's id on ctxs[g].  The first failure is returned (contexts before it keep the key). */
+int fabgpu_p384_key_register_many(fabgpu_ctx* const* ctxs, int n, const uint8_t* qx48, const uint8_t* qy48, uint32_t* key_ids);
+int fabgpu_p384_key_lookup(fabgpu_ctx* ctx, const uint8_t* qx48, const uint8_t* qy48, uint32_t* key_id); /* 0 found, 1 not registered */
+int fabgpu_p384_key_count(fabgpu_ctx* ctx);                      /* live keys */
+int fabgpu_p384_key_unregister(fabgpu_ctx* ctx, uint32_t key_id); /* 0 retired, 1 the id is not live */
+#define FABGPU_P384_KEY_TABLE_STATS 7
+int fabgpu_p384_key_table_stats(fabgpu_ctx* ctx, uint64_t* out, int cap);
+int fabgpu_p384_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint32_t* key_id, const uint8_t* e, const uint8_t* r,
+                                   const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
+int fabgpu_p384_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* key_id, const void* e, const void* r, const void* s,
+                                       void* verdict_bits, void* status, void* stream);
+int fabgpu_sha256_p384_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
+                                          const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
+int fabgpu_sha256_p384_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
+                                              const void* key_id, const void* r, const void* s, void* verdict_bits, void* status,
+                                              void* stream);
+int fabgpu_sha3_256_p384_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint32_t* key_id,
+                                            const uint8_t* r, const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
+int fabgpu_sha3_256_p384_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
+                                                const void* key_id, const void* r, const void* s, void* verdict_bits, void* status,
+                                                void* stream);
 
 /* ---- identity.Verify over a DESCRIBED batch: shared message prefixes, fresh or registered keys ----
  * The endorsements of one transaction all sign  prp || endorser_i  (core/common/validation/statebased/

@@ -79,8 +79,8 @@ int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pa
  * validators' SHA3-256 digests can only miss the verdict memo, never hit a SHA-256 verdict) and the digest memo (SHA-256 only).
  * "p384" (default off; > 0 on): the *_p384 calls below verify ECDSA P-384 identities on the device.  Off, each of them answers, per item,
  * "P-384 is served by bccsp/sw, not by the GPU provider" (the identity call behind identity.Verify's "could not determine the validity of
- * the signature: ") and launches nothing.  NOT served either way: the block pass (a P-384 endorser stays TX_NEEDS_SW), the verdict
- * and digest memos, registered keys.
+ * the signature: ") and launches nothing; fabgpu_csp_key_import_p384 answers the same text and registers nothing.  NOT served either
+ * way: the block pass (a P-384 endorser stays TX_NEEDS_SW), the verdict and digest memos.
  * FABGPU_EINVAL: no such option. */
 int fabgpu_csp_set_option(fabgpu_csp* csp, const char* name, int64_t value, int64_t* previous);
 int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value);
@@ -174,6 +174,10 @@ int fabgpu_csp_identity_verify_coalesced2(fabgpu_csp* csp, const uint8_t* qx32, 
  * The coalesced entry has a queue of its own: P-384 callers share launches with each other only.  "valid" answers are sampled by the CPU
  * audit like the P-256 ones (re-computed with csrc/p384.h compiled for the host); a disagreement poisons the provider.
  * *flags bit0 as in fabgpu_csp_verify (the provider does not decide: an off-curve key, or the option is off). */
+/* BCCSP.KeyImport for a P-384 public key: fabgpu_csp_key_import's answers and texts with 48-byte coordinates.  An on-curve key gets its
+ * comb table on every device of the pool (fabgpu_p384_key_register_many), and the three calls below then take the keyed entries for a
+ * batch whose submitted items ALL name imported keys (otherwise the fresh-key entries, as before); answers and texts do not change. */
+int fabgpu_csp_key_import_p384(fabgpu_csp* csp, const uint8_t* qx48, const uint8_t* qy48, int* on_curve, char* err, size_t errcap);
 int fabgpu_csp_verify_coalesced_p384(fabgpu_csp* csp, const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig, size_t siglen,
                                      const uint8_t* digest, size_t dlen, int* valid, int* flags, char* err, size_t errcap);
 int fabgpu_csp_verify_batch_p384(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* sig_arena, const uint32_t* sig_off,
