@@ -469,6 +469,9 @@ static int block_pass(fabgpu_csp* csp, fabgpu_block_pass* ps, uint32_t uncounted
                     ms_walk, ms_since(t1), v.ms_gates, v.ms_upload_wait, v.ms_device, v.ms_nym, v.ms_memo);
         if (!e.ok()) return FABGPU_ELAUNCH;
     }
+    // the P-384 stage (option p384): the tuples either route left to bccsp/sw that name P-384 certificates, before anything is handed out
+    if (!csp->csp->P384PassStage(ps->block, ps->len, pb, v, &up).ok()) return FABGPU_ELAUNCH;
+    if (csp->csp->P384Enabled() && csp->csp->Poisoned()) return FABGPU_EPOISONED;   // (its audit disagreed: what a poisoned pass answers)
     const size_t nt = v.tuple_status.size();
     if (ps->tx_flags && v.n_tx) memcpy(ps->tx_flags, v.tx_flags.data(), v.n_tx);
     if (ps->tx_type && v.n_tx) memcpy(ps->tx_type, v.tx_type.data(), v.n_tx);
@@ -680,6 +683,25 @@ int fabgpu_identity_to_p256(const uint8_t* ident, size_t len, uint8_t* qxy64) {
         memcpy(qxy64 + 32, qy, 32);
     }
     return 0;
+}
+// (pure host) the same question for P-384, as the P-384 stage of the pass asks it: 0 = a PEM x509 certificate with an on-curve secp384r1
+// key (qxy set), 2 = such a certificate whose point is NOT on the curve (qxy set: decoded, refused by the on-curve gate), 1 = anything else
+int fabgpu_identity_to_p384(const uint8_t* ident, size_t len, uint8_t* qxy96) {
+    uint8_t qx[48], qy[48];
+    if (!ident || !IdentityToP384(ident, len, qx, qy)) return 1;
+    if (qxy96) {
+        memcpy(qxy96, qx, 48);
+        memcpy(qxy96 + 48, qy, 48);
+    }
+    return fabgpu_p384_pubkey_on_curve(qx, qy) ? 0 : 2;
+}
+// the P-384 stage of this provider's passes (GPUCSP::P384PassStats)
+int fabgpu_csp_p384_pass_stats(fabgpu_csp* csp, uint64_t* out, int cap) {
+    if (!csp || (!out && cap > 0)) return FABGPU_EINVAL;
+    uint64_t v[GPUCSP::P384_PASS_STATS];
+    csp->csp->P384PassStats(v);
+    for (int i = 0; i < cap && i < GPUCSP::P384_PASS_STATS; i++) out[i] = v[i];
+    return GPUCSP::P384_PASS_STATS;
 }
 // ---- idemix (idemix_host.h) ----
 int fabgpu_csp_idemix_msp_register(fabgpu_csp* csp, const char* mspid, const uint8_t* ipk_raw, size_t len, int64_t* issuer_id) {

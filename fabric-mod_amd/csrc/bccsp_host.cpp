@@ -954,7 +954,8 @@ Error GPUCSP::PreVerifyBlock(const uint8_t* block, size_t len, BlockVerdicts& ou
     StartBlockUpload(up, block, len, opt.block_seq);      // the block travels while it is walked and its signatures are gated
     static thread_local ParsedBlock pb;                   // storage reused from block to block
     if (!block || !ParseBlock(block, len, pb, WalkThreads())) return Error("block does not parse as common.Block");
-    return PreVerifyParsed(block, pb, out, &up, opt);
+    Error e = PreVerifyParsed(block, pb, out, &up, opt);
+    return e.ok() ? P384PassStage(block, len, pb, out, &up) : e;
 }
 
 
@@ -3149,6 +3150,228 @@ Error GPUCSP::PreVerifyParsed(const uint8_t* block, const ParsedBlock& pb, Block
     CompareHashesAndSummarize(hp);
     RegisterQueued(hp.to_register);
     if (opt.seed_memo) SeedMemo(block, pb, out, opt, hp.ps.sub, kGateMax, up);
+    return Error();
+}
+
+// ------------------------------------------------------------------------------------------------
+// The P-384 stage of the pass (bccsp_host.h P384PassStage): shared by the two routes
+// ------------------------------------------------------------------------------------------------
+void GPUCSP::P384PassStats(uint64_t out[P384_PASS_STATS]) const {
+    for (int i = 0; i < P384_PASS_STATS; i++) out[i] = p384_pass_[i].load(std::memory_order_relaxed);
+}
+
+Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock& parsed, BlockVerdicts& out, BlockUpload* up) const {
+    if (!P384Enabled() || Poisoned() || !block) return Error();
+    const size_t nt = out.tuple_status.size();
+    if (!nt || !memchr(out.tuple_status.data(), TUPLE_ST_NEEDS_SW, nt)) return Error();   // (an all-P-256 block: 40 000 status bytes read once)
+    std::vector<uint32_t> sw;                                            // the tuples the route left to bccsp/sw
+    for (size_t i = 0; i < nt; i++)
+        if (out.tuple_status[i] == TUPLE_ST_NEEDS_SW) sw.push_back((uint32_t)i);
+    // the tuples' own records: the route's, or - the device route brings none back unless its caller asked - a host walk of the block,
+    // which lists the same tuples in the same order (tests/test_device_walk.py holds the two walkers to that)
+    const ParsedBlock* pb = &parsed;
+    ParsedBlock walked;
+    if (parsed.tuples.size() != nt) {
+        if (!ParseBlock(block, len, walked, WalkThreads()) || walked.tuples.size() != nt) return Error();   // (not the route's list: leave its answers)
+        pb = &walked;
+    }
+    // identity -> key, through the identity cache (an entry learns its P-384 answer once); idemix creators and whatever is no on-curve
+    // P-384 certificate key stay NEEDS_SW
+    struct Row {
+        uint32_t tuple;
+        ECDSAPublicKey384 key;
+    };
+    std::vector<Row> rows;
+    std::vector<std::pair<Span, CachedIdentity>> front;                  // a block names few identities
+    static const uint8_t one_digest[1] = {1};
+    std::vector<uint8_t> qx, qy, r, s;
+    uint64_t seen = 0;
+    bool touched = false;
+    for (uint32_t i : sw) {
+        const BlockTuple& tp = pb->tuples[i];
+        if ((uint64_t)tp.identity.off + tp.identity.len > len || (uint64_t)tp.sig.off + tp.sig.len > len) continue;
+        const uint8_t* ident = block + tp.identity.off;
+        const CachedIdentity* ci = nullptr;
+        for (auto& f : front)
+            if (f.first.len == tp.identity.len && memcmp(block + f.first.off, ident, tp.identity.len) == 0) {
+                ci = &f.second;
+                break;
+            }
+        if (!ci) {
+            CachedIdentity c;
+            bool cached = false;
+            std::string key((const char*)ident, tp.identity.len);
+            {
+                std::lock_guard<std::mutex> lk(idmu_);
+                auto it = idcache_.find(key);
+                if (it != idcache_.end()) {
+                    c = it->second->second;
+                    cached = true;
+                }
+            }
+            if (c.p384 == 0) {                                           // decoded outside the lock, as the P-256 key was
+                c.p384 = !c.p256 && IdentityToP384(ident, tp.identity.len, c.qx384, c.qy384) && p384::pubkey_on_curve(c.qx384, c.qy384) ? 1 : 2;
+                if (cached) {
+                    std::lock_guard<std::mutex> lk(idmu_);
+                    auto it = idcache_.find(key);
+                    if (it != idcache_.end() && it->second->second.p384 == 0) {
+                        CachedIdentity& e = it->second->second;
+                        e.p384 = c.p384;
+                        memcpy(e.qx384, c.qx384, 48);
+                        memcpy(e.qy384, c.qy384, 48);
+                    }
+                }
+            }
+            front.emplace_back(tp.identity, c);
+            ci = &front.back().second;
+        }
+        if (ci->p384 != 1) continue;
+        seen++;
+        touched = true;
+        if (tp.sig.len == 0) {
+            out.tuple_status[i] = TUPLE_ST_EMPTY_SIG;
+            continue;
+        }
+        Row row;
+        row.tuple = i;
+        memcpy(row.key.x, ci->qx384, 48);
+        memcpy(row.key.y, ci->qy384, 48);
+        row.key.on_curve = true;
+        const Gate384 g = gate_item384(&row.key, block + tp.sig.off, tp.sig.len, one_digest, 1);
+        if (!g.submit) {                                                 // the outcomes as GateRange maps them for P-256
+            if (g.res.err.ok()) out.tuple_status[i] = FABGPU_ST_RANGE;   // r does not fit the field: (false, nil)
+            else if (g.res.err.msg.find("Invalid S") != std::string::npos) out.tuple_status[i] = FABGPU_ST_HIGH_S;
+            else out.tuple_status[i] = TUPLE_ST_BAD_DER;
+            continue;
+        }
+        rows.push_back(row);
+        qx.insert(qx.end(), row.key.x, row.key.x + 48);
+        qy.insert(qy.end(), row.key.y, row.key.y + 48);
+        r.insert(r.end(), g.r, g.r + 48);
+        s.insert(s.end(), g.s, g.s + 48);
+    }
+    if (!touched) return Error();
+    p384_pass_[P384_PASS_STAGES].fetch_add(1, std::memory_order_relaxed);
+    p384_pass_[P384_PASS_SEEN].fetch_add(seen, std::memory_order_relaxed);
+    const size_t n = rows.size();
+    std::vector<uint8_t> st(n, 0);
+    std::vector<uint64_t> bits((n + 63) / 64, 0);
+    if (n) {
+        // one described batch over the block: message spans and prefixes from the tuples' own records, the orderers' messages in the tail
+        std::vector<uint32_t> off(2 * n), pre_idx(n), pre_off;
+        std::vector<std::pair<uint64_t, uint32_t>> pre_seen;             // (off << 32 | len) -> index, in order of first use
+        for (size_t j = 0; j < n; j++) {
+            const BlockTuple& tp = pb->tuples[rows[j].tuple];
+            off[2 * j] = tp.suffix.off;
+            off[2 * j + 1] = tp.suffix.off + tp.suffix.len;
+            pre_idx[j] = 0xFFFFFFFFu;
+            if (tp.prefix.len == 0) continue;
+            const uint64_t k = (uint64_t)tp.prefix.off << 32 | tp.prefix.len;
+            if (pre_seen.empty() || pre_seen.back().first != k) {        // (a transaction's endorsements follow each other)
+                pre_seen.emplace_back(k, (uint32_t)(pre_off.size() / 2));
+                pre_off.push_back(tp.prefix.off);
+                pre_off.push_back(tp.prefix.off + tp.prefix.len);
+            }
+            pre_idx[j] = pre_seen.back().second;
+        }
+        Dev& dv = *devs_[(size_t)(up && (up->routed || up->started) ? up->dev : 0)];
+        fabgpu_identity_batch_p384 d;
+        memset(&d, 0, sizeof(d));
+        d.n = n;
+        d.arena = block;
+        d.off = off.data();
+        d.n_prefixes = (uint32_t)(pre_off.size() / 2);
+        d.pre_off = pre_off.data();
+        d.pre_idx = pre_idx.data();
+        std::vector<uint32_t> ids;
+        const std::vector<uint8_t> submitted(n, 1);
+        const bool keyed = all_registered384(dv.ctx, n, submitted, qx.data(), qy.data(), ids);
+        if (keyed) {
+            d.key_id = ids.data();
+        } else {
+            d.qx = qx.data();
+            d.qy = qy.data();
+        }
+        d.r = r.data();
+        d.s = s.data();
+        d.verdict_bits = bits.data();
+        d.status = st.data();
+        if (!pb->tail.empty()) {
+            d.tail = pb->tail.data();
+            d.tail_base = pb->tail_base;
+            d.tail_len = (uint32_t)pb->tail.size();
+        }
+        const uint64_t tok = up ? up->join() : 0;
+        int rc = FABGPU_EINVAL;
+        if (tok) {
+            d.flags = FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED;
+            d.stage_token = tok;
+            rc = fabgpu_identity_verify_batch_p384(dv.ctx, &d);          // FABGPU_EINVAL: somebody else's upload replaced ours -> resubmit with the bytes
+        }
+        d.flags = FABGPU_IDB_SPANS;
+        if (!tok || rc == FABGPU_EINVAL) rc = fabgpu_identity_verify_batch_p384(dv.ctx, &d);
+        if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
+        p384_pass_[P384_PASS_SUBMITTED].fetch_add(n, std::memory_order_relaxed);
+        p384_pass_[keyed ? P384_PASS_KEYED : P384_PASS_FRESH].fetch_add(1, std::memory_order_relaxed);
+        std::string msg;
+        for (size_t j = 0; j < n; j++) {
+            const uint32_t i = rows[j].tuple;
+            if (keyed && st[j] == FABGPU_ST_OFF_CURVE) continue;          // (the id was retired under the launch: "use bccsp/sw", never "invalid")
+            bool valid = ((bits[j >> 6] >> (j & 63)) & 1) && st[j] == FABGPU_ST_VALID;
+            if (!valid && st[j] == FABGPU_ST_BAD_MATH) {                 // (test hook: a corrupted verdict)
+                uint32_t f = test_p384_flip_.load(std::memory_order_relaxed);
+                while (f && !test_p384_flip_.compare_exchange_weak(f, f - 1)) {}
+                if (f) valid = true;
+            }
+            out.tuple_status[i] = valid ? FABGPU_ST_VALID : (st[j] == FABGPU_ST_VALID ? FABGPU_ST_BAD_MATH : st[j]);
+            if (!valid || !audit_sample_[AUDIT_DIRECT].hit(AuditPermille())) continue;
+            // the audit: the message bytes of the CALLER's block, hashed and verified on the CPU
+            const BlockTuple& tp = pb->tuples[i];
+            auto bytes_of = [&](const Span& sp) -> const uint8_t* {
+                if (!pb->tail.empty() && sp.off >= pb->tail_base) return (uint64_t)sp.off - pb->tail_base + sp.len <= pb->tail.size() ? pb->tail.data() + (sp.off - pb->tail_base) : nullptr;
+                return (uint64_t)sp.off + sp.len <= len ? block + sp.off : nullptr;
+            };
+            const uint8_t *pp = bytes_of(tp.prefix), *sp = bytes_of(tp.suffix);
+            bool accept = false;
+            {
+                AuditClock clk{audit_count_[AUDIT_NS]};
+                if (pp && sp) {
+                    msg.assign((const char*)pp, tp.prefix.len);
+                    msg.append((const char*)sp, tp.suffix.len);
+                    uint8_t dg[32];
+                    audit_sha256((const uint8_t*)msg.data(), msg.size(), dg);
+                    accept = audit_p384_verify(rows[j].key.x, rows[j].key.y, block + tp.sig.off, tp.sig.len, dg, 32);
+                }
+            }
+            audit_count_[AUDIT_DIRECT].fetch_add(1, std::memory_order_relaxed);
+            p384_pass_[P384_PASS_AUDITED].fetch_add(1, std::memory_order_relaxed);
+            if (!accept) {
+                audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
+                Poison(std::string("block pass: the device accepted a P-384 signature that the CPU audit rejects (key X ") + hex8(rows[j].key.x) + "..)");
+                return Error();                                          // (the caller answers what a poisoned pass answers)
+            }
+        }
+    }
+    // The flags of the affected transactions, folded again.  What the route's fold knew and the tuples do not say - "not understood", a
+    // bad TxID, a bad proposal hash - is read back from the flag it produced: each of them outranks everything below it in the fold, so
+    // a flag that names one of them hides nothing the new fold needs (block_prepass.h SummarizeTransactions).
+    const uint32_t n_tx = (uint32_t)out.tx_flags.size();
+    std::vector<uint8_t> understood(n_tx, 1), bad_txid(n_tx, 0), bad_phash(n_tx, 0), kind(nt), flags(n_tx, 0), affected(n_tx, 0);
+    std::vector<uint32_t> tx(nt);
+    for (uint32_t t = 0; t < n_tx; t++) {
+        understood[t] = out.tx_flags[t] != TX_NOT_UNDERSTOOD;
+        bad_txid[t] = out.tx_flags[t] == TX_BAD_TXID;
+        bad_phash[t] = out.tx_flags[t] == TX_BAD_PROPOSAL_HASH;
+    }
+    for (size_t i = 0; i < nt; i++) {
+        tx[i] = pb->tuples[i].tx;
+        kind[i] = pb->tuples[i].kind;
+    }
+    for (uint32_t i : sw)
+        if (tx[i] < n_tx) affected[tx[i]] = 1;
+    SummarizeTransactions(n_tx, understood.data(), nt, tx.data(), kind.data(), out.tuple_status.data(), bad_txid.data(), bad_phash.data(), flags.data());
+    for (uint32_t t = 0; t < n_tx; t++)
+        if (affected[t]) out.tx_flags[t] = flags[t];
     return Error();
 }
 

@@ -277,6 +277,18 @@ class GPUCSP {
     // device-route statistics since construction: launches repeated after a wrong "everybody is registered" prediction, tuples whose
     // certificate the device decoded itself, identities that entered the cache that way, signatures that took the general DER parser
     void PassStats(uint64_t out[4]) const;
+    // ---- the P-384 stage of the block pass (option p384) ----
+    // One step both routes run once the route has written the tuples' statuses: the tuples it left TUPLE_ST_NEEDS_SW whose identity is a
+    // certificate with an on-curve P-384 key go through gate_item384 and then, in ONE described batch over the block the pass staged
+    // (fabgpu_identity_verify_batch_p384: keyed when every submitted key is registered on the pass's device, fresh otherwise), get their
+    // statuses; the flags of their transactions are folded again (SummarizeTransactions); a sample of the "valid" answers is audited on
+    // the CPU (audit_permille; a disagreement poisons the provider).  Option off, provider poisoned, or no such tuple: nothing is
+    // launched and nothing allocated.  parsed.tuples must hold the route's tuple records, or be empty (the device route without
+    // WANT_TUPLES): the stage then walks the block on the host for the records of the tuples it needs.
+    // NOT here: memo entries for P-384 tuples (tuple_hashed stays 0, tuple_qxy / tuple_digest stay zero), SHA3 MSPs.
+    Error P384PassStage(const uint8_t* block, size_t len, const ParsedBlock& parsed, BlockVerdicts& out, BlockUpload* up) const;
+    enum : int { P384_PASS_STAGES = 0, P384_PASS_SEEN = 1, P384_PASS_SUBMITTED = 2, P384_PASS_KEYED = 3, P384_PASS_FRESH = 4, P384_PASS_AUDITED = 5, P384_PASS_STATS = 6 };
+    void P384PassStats(uint64_t out[P384_PASS_STATS]) const;
     // Starts the upload of a block on a helper thread (blocks of 4 MiB and more) so that it travels while the caller parses
     // and gates; join() returns the token for PreVerifyParsed (0 if nothing was staged).
     struct BlockUpload {
@@ -413,6 +425,10 @@ class GPUCSP {
         bool registering = false;       // some thread is building the device table right now
         uint64_t table_hash = 0;        // walk::id_hash_host of the identity bytes under idtab_seed_ (computed once, when it enters the cache)
         uint64_t serial = 0;            // unique per cache entry: how the device table's indices find their way back (idserial_)
+        // the P-384 stage of the pass (option p384): 0 not asked yet, 1 an on-curve P-384 certificate key (qx384 / qy384), 2 not one.
+        // Internal to the host: the device's identity table (DevIdEntry) carries P-256 keys only and such an identity keeps p256 = false.
+        uint8_t p384 = 0;
+        uint8_t qx384[48], qy384[48];
     };
     // Bounded LRU (the reference's msp cache is one: msp/cache/cache.go:14-18, second_chance.go).  Identities come out of
     // UNVALIDATED blocks, so neither host memory nor device tables may grow with what a block names: at most id_max_ cached
@@ -453,6 +469,7 @@ class GPUCSP {
     // test hook (TestAccess, libfabgpu_testhooks.so): so many of the device's next P-384 arithmetic rejects are read as "valid" - the
     // corruption the audit must catch.  Nothing in the product sets it.
     mutable std::atomic<uint32_t> test_p384_flip_{0};
+    mutable std::atomic<uint64_t> p384_pass_[6] = {};        // P384PassStats
     // as AuditDirect, for a P-384 "valid": re-computed with the host compilation of p384.h (audit_p384_verify)
     bool AuditDirectP384(const ECDSAPublicKey384& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
                          const uint8_t* msg = nullptr, size_t msglen = 0, bool sha3 = false) const;

@@ -83,6 +83,54 @@ bool IdentityToP256(const uint8_t* ident, size_t len, uint8_t qx[32], uint8_t qy
     return CertDerToP256(der.data(), der.size(), qx, qy);
 }
 
+// The P-384 twin of walk::cert_der_p256_key_offset, host only (the device's identity table knows P-256 keys alone): the same road to
+// SubjectPublicKeyInfo, then id-ecPublicKey with secp384r1 and the 97-byte uncompressed point.  Returns the offset of X or -1.
+static int32_t cert_der_p384_key_offset(const uint8_t* der, size_t len) {
+    static const uint8_t OID_EC_PUBLIC_KEY[7] = {0x2A, 0x86, 0x48, 0xCE, 0x3D, 0x02, 0x01};   // 1.2.840.10045.2.1
+    static const uint8_t OID_SECP384R1[5] = {0x2B, 0x81, 0x04, 0x00, 0x22};                   // 1.3.132.0.34
+    Der top{der, der + len};
+    uint8_t tag;
+    const uint8_t* c;
+    size_t l;
+    if (!top.tlv(tag, c, l) || tag != 0x30) return -1;             // Certificate
+    Der cert{c, c + l};
+    if (!cert.tlv(tag, c, l) || tag != 0x30) return -1;            // TBSCertificate
+    Der tbs{c, c + l};
+    if (!tbs.tlv(tag, c, l)) return -1;
+    if (tag == 0xA0) {                                             // [0] version (absent in v1 certificates)
+        if (!tbs.tlv(tag, c, l)) return -1;
+    }
+    if (tag != 0x02) return -1;                                    // serialNumber
+    for (int k = 0; k < 4; k++)                                    // signature, issuer, validity, subject
+        if (!tbs.tlv(tag, c, l) || tag != 0x30) return -1;
+    if (!tbs.tlv(tag, c, l) || tag != 0x30) return -1;             // subjectPublicKeyInfo
+    Der spki{c, c + l};
+    if (!spki.tlv(tag, c, l) || tag != 0x30) return -1;            // AlgorithmIdentifier
+    Der alg{c, c + l};
+    if (!alg.tlv(tag, c, l) || tag != 0x06 || l != 7 || memcmp(c, OID_EC_PUBLIC_KEY, 7) != 0) return -1;
+    if (!alg.tlv(tag, c, l) || tag != 0x06 || l != 5 || memcmp(c, OID_SECP384R1, 5) != 0) return -1;
+    if (!spki.tlv(tag, c, l) || tag != 0x03) return -1;            // BIT STRING: 00 04 X Y
+    if (l != 98 || c[0] != 0x00 || c[1] != 0x04) return -1;
+    return (int32_t)(c + 2 - der);
+}
+
+bool CertDerToP384(const uint8_t* der, size_t len, uint8_t qx[48], uint8_t qy[48]) {
+    const int32_t at = cert_der_p384_key_offset(der, len);
+    if (at < 0) return false;
+    memcpy(qx, der + at, 48);
+    memcpy(qy, der + at + 48, 48);
+    return true;
+}
+
+bool IdentityToP384(const uint8_t* ident, size_t len, uint8_t qx[48], uint8_t qy[48]) {
+    const uint8_t* idb;
+    size_t idl;
+    if (!pb_bytes(ident, len, 2, idb, idl)) return false;             // msp.SerializedIdentity{1 mspid, 2 id_bytes}
+    std::vector<uint8_t> der;
+    if (!PemToDer(idb, idl, der)) return false;
+    return CertDerToP384(der.data(), der.size(), qx, qy);
+}
+
 namespace {
 void der_len(std::vector<uint8_t>& o, size_t n) {
     if (n < 128) { o.push_back((uint8_t)n); return; }

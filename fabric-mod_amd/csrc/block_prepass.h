@@ -131,6 +131,11 @@ bool IdentityToP256(const uint8_t* ident, size_t len, uint8_t qx[32], uint8_t qy
 // DER x509 certificate -> P-256 SubjectPublicKeyInfo point (exposed for tests against the reference's certificate fixtures)
 bool CertDerToP256(const uint8_t* der, size_t len, uint8_t qx[32], uint8_t qy[32]);
 bool PemToDer(const uint8_t* pem, size_t len, std::vector<uint8_t>& der);
+// The same road for a certificate whose key is id-ecPublicKey on secp384r1 (1.3.132.0.34) with a 97-byte uncompressed point -> the
+// point, 48 bytes a coordinate.  false: not such an identity.  Whether the point is ON P-384 is the caller's next question
+// (fabgpu_p384_pubkey_on_curve), as PublicKeyOnCurve is IdentityToP256's.  Host only: the device's identity table keeps P-256 keys.
+bool IdentityToP384(const uint8_t* ident, size_t len, uint8_t qx[48], uint8_t qy[48]);
+bool CertDerToP384(const uint8_t* der, size_t len, uint8_t qx[48], uint8_t qy[48]);
 // protoutil.BlockHeaderBytes (protoutil/blockutils.go:38-58): DER of SEQUENCE{INTEGER number, OCTET STRING previous_hash, OCTET STRING data_hash}
 void BlockHeaderBytes(uint64_t number, const uint8_t* prev, size_t prev_len, const uint8_t* data_hash, size_t dh_len, std::vector<uint8_t>& out);
 // does the 32-byte digest equal what the block says (hex string for HASH_TXID, raw bytes for HASH_PROPOSAL)?

@@ -2845,6 +2845,199 @@ int fabgpu_identity_verify_batch(fabgpu_ctx* ctx, const fabgpu_identity_batch* b
     return FABGPU_OK;
 }
 
+// ---- identity.Verify over a described batch of P-384 identities: the digest rows (p384_described_kernels.hip), then the fresh or
+// the keyed P-384 kernel over them on the same stream --------------------------------------------------------------------------------
+int fabgpu_identity_verify_batch_p384_dev(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* b, void* mid_scratch, void* stream) {
+    if (!ctx || !b) return FABGPU_EINVAL;
+    const size_t n = b->n;
+    const bool keyed = b->key_id != nullptr;
+    DeviceGuard g(ctx->device);
+    if (n == 0) return keyed ? p384_gcomb(ctx) : p384_gtab(ctx);      // the explicit warm call (fabgpu.h): a table, no launch
+    const bool prefixed = b->n_prefixes != 0 && b->pre_idx != nullptr;
+    if (!b->arena || !b->off || !b->r || !b->s || !b->verdict_bits || (!keyed && (!b->qx || !b->qy))) return FABGPU_EINVAL;
+    if (prefixed && (!b->pre_off || !mid_scratch)) return FABGPU_EINVAL;
+    if (b->flags & ~(uint32_t)FABGPU_IDB_SPANS) return FABGPU_EINVAL;   // (FABGPU_IDB_SHA3_256 among them: SHA-256 only)
+    if (dev_too_big(n, b->arena_bytes)) return FABGPU_ETOOBIG;
+    const bool has_tail = b->tail != nullptr && b->tail_len != 0;
+    if (has_tail && (!(b->flags & FABGPU_IDB_SPANS) || (b->tail_base & 63u) || (uint64_t)b->tail_base + b->tail_len > 0xFFFFFFF0ull)) return FABGPU_EINVAL;
+    if (b->arena_bytes < 4 || (b->arena_bytes & 3u) || ((uintptr_t)b->arena & 3u) || (has_tail && ((uintptr_t)b->tail & 3u))) return FABGPU_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    size_t di = 0;
+    void* dig = b->digests;
+    if (!dig) {
+        const int rc = ctx->acquire_qws(n * 32, &di, &dig, st);
+        if (rc != FABGPU_OK) return rc;
+    }
+    P384DescribedLaunch v;
+    v.n = (uint32_t)n;
+    v.arena = b->arena; v.arena_bytes = b->arena_bytes; v.off = b->off;
+    v.pa.spans = (b->flags & FABGPU_IDB_SPANS) != 0;
+    if (prefixed) {
+        v.pa.m = b->n_prefixes;
+        v.pa.pre_off = b->pre_off;
+        v.pa.pre_idx = b->pre_idx;
+        v.pa.mid_scratch = mid_scratch;
+    }
+    if (has_tail) {
+        v.tail = b->tail; v.tail_base = b->tail_base; v.tail_len = b->tail_len;
+    }
+    v.digests = dig;
+    int rc = timed_launch(ctx, st, 0, [&](void*) { return launch_p384_described_digests(v, st); });
+    if (rc == FABGPU_OK)
+        rc = keyed ? p384_verify_keyed_dev(ctx, n, b->key_id, dig, true, b->r, b->s, b->verdict_bits, b->status, st)
+                   : p384_verify_dev(ctx, n, b->qx, b->qy, dig, true, b->r, b->s, b->verdict_bits, b->status, st);
+    if (!b->digests) ctx->release_qws(di, st);
+    return rc;
+}
+
+int fabgpu_identity_verify_batch_p384(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* b) {
+    if (!ctx || !b) return FABGPU_EINVAL;
+    const size_t n = b->n;
+    const bool keyed = b->key_id != nullptr;
+    if (n == 0) return fabgpu_identity_verify_batch_p384_dev(ctx, b, nullptr, nullptr);
+    const uint32_t m = (b->n_prefixes != 0 && b->pre_idx != nullptr) ? b->n_prefixes : 0;
+    if (!b->off || !b->r || !b->s || !b->verdict_bits || (!keyed && (!b->qx || !b->qy)) || (m && !b->pre_off)) return FABGPU_EINVAL;
+    if (n > 0x7FFFFFF0ull / 240) return FABGPU_ETOOBIG;
+    const uint8_t* arena = (const uint8_t*)b->arena;
+    const bool spans = (b->flags & FABGPU_IDB_SPANS) != 0;
+    const bool staged = (b->flags & FABGPU_IDB_ARENA_STAGED) != 0;
+    if (b->flags & ~(uint32_t)(FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED)) return FABGPU_EINVAL;   // (FABGPU_IDB_SHA3_256: SHA-256 only)
+    // a staged arena: its slot stays locked - the stager kept out of it - until this batch has run
+    fabgpu_ctx::Staged* sl = nullptr;
+    std::unique_lock<std::mutex> slk;
+    if (staged) {
+        if (b->stage_token == 0) return FABGPU_EINVAL;
+        for (auto& c : ctx->staged_slots)
+            if (c.token.load() == b->stage_token) sl = &c;
+        if (!sl) return FABGPU_EINVAL;                                                          // replaced meanwhile
+        slk = std::unique_lock<std::mutex>(sl->m);
+        if (sl->token.load() != b->stage_token || sl->len == 0) return FABGPU_EINVAL;           // ... or just now
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    // what the messages and prefixes reference of the caller's arena; spans at or beyond tail_base address the tail, prefixes never do
+    const size_t noff = spans ? 2 * n : n + 1, npre = m ? (spans ? 2 * (size_t)m : (size_t)m + 1) : 0;
+    const bool has_tail = b->tail != nullptr && b->tail_len != 0;
+    const uint32_t tbase = has_tail ? b->tail_base : 0xFFFFFFFFu;
+    if (has_tail && ((tbase & 63u) || !spans || (uint64_t)tbase + b->tail_len > 0xFFFFFFF0ull)) return FABGPU_EINVAL;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    bool tail_used = false, bad = false;
+    auto see = [&](uint32_t s0, uint32_t s1, bool may_be_tail) {
+        if (s1 < s0) { bad = true; return; }
+        if (s1 == s0) return;
+        if (s0 >= tbase) {
+            if (!may_be_tail || (uint64_t)s1 > (uint64_t)tbase + b->tail_len) bad = true;
+            tail_used = true;
+            return;
+        }
+        if (s1 > tbase) { bad = true; return; }            // straddles
+        if (s0 < lo) lo = s0;
+        if (s1 > hi) hi = s1;
+    };
+    auto see_run = [&](const uint32_t* o, size_t k) {     // consecutive messages: empty ones still bound the span
+        for (size_t i = 0; i < k && !bad; i++) {
+            if (o[i + 1] < o[i]) bad = true;
+            if (o[i] < lo) lo = o[i];
+            if (o[i + 1] > hi) hi = o[i + 1];
+        }
+    };
+    if (spans) {
+        for (size_t i = 0; i < n; i++) see(b->off[2 * i], b->off[2 * i + 1], true);
+        for (uint32_t p = 0; p < m; p++) see(b->pre_off[2 * p], b->pre_off[2 * p + 1], false);
+    } else {
+        see_run(b->off, n);
+        if (m) see_run(b->pre_off, m);
+    }
+    if (bad) return FABGPU_EINVAL;
+    if (lo == 0xFFFFFFFFu) lo = hi = 0;                    // nothing references the caller's arena
+    size_t span = (size_t)hi - lo;                         // bytes taken from the caller's arena
+    if (staged) {
+        if (hi > sl->len) return FABGPU_EINVAL;
+        lo = 0;                                            // offsets are offsets into the staged bytes
+    } else if (span && !arena) {
+        return FABGPU_EINVAL;
+    }
+    // the device arena: the staged upload as it lies there (fabgpu_arena_stage zeroed its slack up to the next 64 and beyond), or the
+    // referenced bytes of the caller's arena; the tail in a buffer of its own either way, so a staged upload is read and never written
+    const size_t ab = staged ? round_up(sl->len, 64) : round_up(span, 4) + 64;
+    const size_t ib = round_up(n * 4, 64), pob = round_up((npre + 1) * 4, 64), tb = round_up((size_t)b->tail_len, 4);
+    HostStage h(ctx, n, false, 48);
+    const size_t dg_off = round_up(h.st_off + n, 64);      // out buffer: verdict words | status bytes | digests
+    if ((!staged && (h.rc = h.room(ctx->arena, ab))) || (h.rc = h.room(ctx->offs, noff * 4)) || (m && (h.rc = h.room(ctx->pre, pob + ib + (size_t)m * 32 + 64))) ||
+        (tail_used && (h.rc = h.room(ctx->tailbuf, tb + 64))))
+        return h.rc;
+    hipError_t err = hipSuccess;
+    if (!staged) {
+        if (span >= ((size_t)4 << 20)) {                   // a marshalled block: handed to the driver directly, one host copy less
+            err = hipMemcpyAsync(ctx->arena.d, arena + lo, span, hipMemcpyHostToDevice, ctx->stream);
+            if (err == hipSuccess) err = hipMemsetAsync((uint8_t*)ctx->arena.d + span, 0, ab - span, ctx->stream);
+        } else {
+            if (span) memcpy(ctx->arena.h, arena + lo, span);
+            memset((uint8_t*)ctx->arena.h + span, 0, ab - span);
+            err = hipMemcpyAsync(ctx->arena.d, ctx->arena.h, ab, hipMemcpyHostToDevice, ctx->stream);
+        }
+    }
+    if (err == hipSuccess && tail_used) {
+        memcpy(ctx->tailbuf.h, b->tail, b->tail_len);
+        memset((uint8_t*)ctx->tailbuf.h + b->tail_len, 0, tb + 64 - b->tail_len);
+        err = hipMemcpyAsync(ctx->tailbuf.d, ctx->tailbuf.h, tb + 64, hipMemcpyHostToDevice, ctx->stream);
+    }
+    // offsets relative to what was staged: arena spans move down by lo, spans of the tail (and empty ones: no address) stay
+    uint32_t* ho = (uint32_t*)ctx->offs.h;
+    auto rebase = [&](uint32_t* dst, const uint32_t* src, size_t k) {
+        if (!spans) {
+            for (size_t i = 0; i < k; i++) dst[i] = src[i] - lo;
+            return;
+        }
+        for (size_t i = 0; i < k; i += 2) {
+            const uint32_t s0 = src[i], s1 = src[i + 1], by = s0 >= tbase ? 0 : lo;
+            dst[i] = s1 > s0 ? s0 - by : 0;
+            dst[i + 1] = s1 > s0 ? s1 - by : 0;
+        }
+    };
+    rebase(ho, b->off, noff);
+    if (err == hipSuccess) err = hipMemcpyAsync(ctx->offs.d, ctx->offs.h, noff * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (m) {
+        rebase((uint32_t*)ctx->pre.h, b->pre_off, npre);
+        memcpy((uint8_t*)ctx->pre.h + pob, b->pre_idx, n * 4);
+        if (err == hipSuccess) err = hipMemcpyAsync(ctx->pre.d, ctx->pre.h, pob + ib, hipMemcpyHostToDevice, ctx->stream);
+    }
+    h.rc = hip_to_rc(err);
+    if (keyed) h.fields(ctx->keyed, HostStage::ID_COLUMN, b->key_id, {(const uint8_t*)b->r, (const uint8_t*)b->s});
+    else h.fields(ctx->fields, 0, nullptr, {(const uint8_t*)b->qx, (const uint8_t*)b->qy, (const uint8_t*)b->r, (const uint8_t*)b->s});
+    if (h.ready() && (h.rc = h.room(ctx->out, dg_off + n * 32)) == FABGPU_OK) {
+        uint8_t* pd = (uint8_t*)ctx->pre.d;
+        uint8_t* dout = (uint8_t*)ctx->out.d;
+        fabgpu_identity_batch_p384 d = *b;
+        d.flags = b->flags & FABGPU_IDB_SPANS;
+        d.arena = staged ? sl->d : ctx->arena.d;
+        d.arena_bytes = ab;
+        d.off = (const uint32_t*)ctx->offs.d;
+        d.n_prefixes = m;
+        d.pre_off = m ? (const uint32_t*)pd : nullptr;
+        d.pre_idx = m ? (const uint32_t*)(pd + pob) : nullptr;
+        d.tail = tail_used ? ctx->tailbuf.d : nullptr;
+        d.tail_base = tail_used ? tbase : 0;
+        d.tail_len = tail_used ? b->tail_len : 0;
+        if (keyed) {
+            d.key_id = (const uint32_t*)h.ids();
+            d.qx = d.qy = nullptr;
+            d.r = h.field(0); d.s = h.field(1);
+        } else {
+            d.qx = h.field(0); d.qy = h.field(1); d.r = h.field(2); d.s = h.field(3);
+        }
+        d.verdict_bits = dout;
+        d.status = b->status ? dout + h.st_off : nullptr;
+        d.digests = dout + dg_off;                         // (the rows the verify kernel reads: made here whether the caller wants them or not)
+        h.rc = fabgpu_identity_verify_batch_p384_dev(ctx, &d, m ? pd + pob + ib : nullptr, ctx->stream);
+    }
+    if (h.fetch(b->digests ? dg_off + n * 32 : (b->status ? h.st_off + n : h.words * 8))) return h.rc;
+    memcpy(b->verdict_bits, ctx->out.h, h.words * 8);
+    if (b->status) memcpy(b->status, (uint8_t*)ctx->out.h + h.st_off, n);
+    if (b->digests) memcpy(b->digests, (uint8_t*)ctx->out.h + dg_off, n * 32);
+    return FABGPU_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------

@@ -149,6 +149,23 @@ struct P384KeyedLaunch {
 };
 hipError_t launch_p384_verify_keyed(const P384KeyedLaunch& v, hipStream_t st);
 
+// ---- p384_described_kernels.hip: the SHA-256 digest rows of a described batch, for the E32 form of the two P-384 verify kernels ----
+// Message i = prefix pa.pre_idx[i] (if any) || the span off names: arena bytes below tail_base, tail[offset - tail_base] at or above it.
+// The mid-states of the prefixes (pa.mid_scratch, m x 32 bytes) are made by launch_sha256_midstates on the same stream unless pa.mid_ready.
+// arena and tail are 4-byte aligned, arena_bytes is a multiple of 4 and the tail is readable up to its last dword (hipErrorInvalidValue
+// otherwise for what the host can see); pa.digests is ignored, the rows go to `digests`.
+struct P384DescribedLaunch {
+    uint32_t n = 0;
+    const void* arena = nullptr;
+    size_t arena_bytes = 0;
+    const void* off = nullptr;               // n + 1 offsets, or (pa.spans) n (start, end) pairs
+    ShaPrefixArgs pa;
+    const void* tail = nullptr;              // device memory, or nullptr: no tail
+    uint32_t tail_base = 0, tail_len = 0;
+    void* digests = nullptr;                 // n x 32 bytes
+};
+hipError_t launch_p384_described_digests(const P384DescribedLaunch& v, hipStream_t st);
+
 // ---- idemix_kernels.hip: idemix pseudonym signatures on FP256BN ----
 // A registered issuer occupies one slot of idemix_issuer_dev_bytes() bytes in a device array; fill a host copy of the slot
 // with idemix_issuer_dev_fill (device pointers of the two comb tables + ipk.Hash) and copy it up.

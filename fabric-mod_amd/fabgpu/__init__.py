@@ -25,6 +25,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("FABGPU_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libfabgpu.so")
 
 FABGPU_OK = 0
+IDB_SPANS = 1             # fabgpu.h FABGPU_IDB_SPANS
+IDB_ARENA_STAGED = 2      # fabgpu.h FABGPU_IDB_ARENA_STAGED
 IDB_SHA3_256 = 4          # fabgpu.h FABGPU_IDB_SHA3_256
 FABGPU_EINVAL = -1
 FABGPU_EPOISONED = -6    # fabgpu.h: the provider's CPU audit disagreed with the device once; it serves nothing any more
@@ -74,6 +76,15 @@ class _IdBatch(ctypes.Structure):
                 ("nym_verdict_bits", ctypes.c_void_p), ("nym_status", ctypes.c_void_p)]
 
 
+class _IdBatchP384(ctypes.Structure):
+    """fabgpu_identity_batch_p384 (include/fabgpu.h)."""
+    _fields_ = [("n", ctypes.c_size_t), ("arena", ctypes.c_void_p), ("arena_bytes", ctypes.c_size_t), ("off", ctypes.c_void_p),
+                ("n_prefixes", ctypes.c_uint32), ("pre_off", ctypes.c_void_p), ("pre_idx", ctypes.c_void_p), ("qx", ctypes.c_void_p),
+                ("qy", ctypes.c_void_p), ("key_id", ctypes.c_void_p), ("r", ctypes.c_void_p), ("s", ctypes.c_void_p),
+                ("verdict_bits", ctypes.c_void_p), ("status", ctypes.c_void_p), ("flags", ctypes.c_uint32), ("stage_token", ctypes.c_uint64),
+                ("tail", ctypes.c_void_p), ("tail_base", ctypes.c_uint32), ("tail_len", ctypes.c_uint32), ("digests", ctypes.c_void_p)]
+
+
 class _BlockPass(ctypes.Structure):
     """fabgpu_block_pass (include/fabgpu_bccsp.h)."""
     _fields_ = [("block", ctypes.c_void_p), ("len", ctypes.c_size_t), ("block_seq", ctypes.c_uint64), ("flags", ctypes.c_uint32),
@@ -108,6 +119,8 @@ class _Cfg(ctypes.Structure):
 
 # what fabgpu_p256_key_table_stats reports, in order
 KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "live_16bit", "bytes_held", "slots_used")
+# ... fabgpu_csp_p384_pass_stats
+P384_PASS_STATS = ("stages", "seen", "submitted", "keyed_launches", "fresh_launches", "audited")
 # ... and fabgpu_p384_key_table_stats
 P384_KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "keyed_launches", "bytes_held", "slots_used")
 P384_COMB_WORDS = 48 * 256 * 24      # one P-384 comb table (csrc/p384_tables.h CombTab384): 1.125 MiB
@@ -150,6 +163,7 @@ ABI_SYMBOLS = [
     "fabgpu_p384_key_table_stats", "fabgpu_p384_verify_batch_keyed", "fabgpu_p384_verify_batch_keyed_dev",
     "fabgpu_sha256_p384_verify_batch_keyed", "fabgpu_sha256_p384_verify_batch_keyed_dev",
     "fabgpu_sha3_256_p384_verify_batch_keyed", "fabgpu_sha3_256_p384_verify_batch_keyed_dev", "fabgpu_csp_key_import_p384",
+    "fabgpu_identity_verify_batch_p384", "fabgpu_identity_verify_batch_p384_dev", "fabgpu_identity_to_p384", "fabgpu_csp_p384_pass_stats",
 ]
 
 # what libfabgpu_testhooks.so exports (fabric-mod_amd/csrc/fabgpu_testhooks.h): probes, walker comparisons, the synthetic block generator, the
@@ -311,6 +325,10 @@ def load():
     L.fabgpu_arena_stage.argtypes = [_vp, _u8p, _sz, ctypes.POINTER(ctypes.c_uint64)]
     L.fabgpu_identity_verify_batch.argtypes = [_vp, ctypes.POINTER(_IdBatch)]
     L.fabgpu_identity_verify_batch_dev.argtypes = [_vp, ctypes.POINTER(_IdBatch), _vp, _vp]
+    L.fabgpu_identity_verify_batch_p384.argtypes = [_vp, ctypes.POINTER(_IdBatchP384)]
+    L.fabgpu_identity_verify_batch_p384_dev.argtypes = [_vp, ctypes.POINTER(_IdBatchP384), _vp, _vp]
+    L.fabgpu_identity_to_p384.argtypes = [ctypes.c_char_p, _sz, ctypes.c_char_p]
+    L.fabgpu_csp_p384_pass_stats.argtypes = [_vp, _u64p, ctypes.c_int]
     L.fabgpu_idemix_issuer_register.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _u32p]
     L.fabgpu_idemix_issuer_count.argtypes = [_vp]
     L.fabgpu_idemix_nym_verify_batch.argtypes = [_vp, _sz, _u8p, _u32p, _u32p, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, _u64p, _u8p]
@@ -838,6 +856,49 @@ class Context:
         _check(self._L.fabgpu_identity_verify_batch_dev(self._h, ctypes.byref(desc), mid_scratch or None, stream or None),
                "fabgpu_identity_verify_batch_dev")
 
+    def identity_verify_batch_p384(self, arena, off, r, s, qx=None, qy=None, key_id=None, pre_off=None, pre_idx=None, want_status=True, spans=False,
+                                   stage_token=0, want_digests=False, tail=None, tail_base=0, flags=0):
+        """fabgpu_identity_verify_batch_p384: the described batch for P-384 identities (48-byte fields, SHA-256 messages); arguments as
+        identity_verify_batch.  Returns (verdicts, statuses[, digests n x 32])."""
+        r, s = _a8(r), _a8(s)
+        arena = _a8(arena) if arena is not None else None
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        n = off.size // 2 if spans else off.size - 1
+        keep = [arena, off, r, s]
+        b = _IdBatchP384()
+        b.n = n
+        b.flags = (1 if spans else 0) | (2 if stage_token else 0) | flags
+        b.stage_token = stage_token
+        b.arena, b.off, b.r, b.s = (arena.ctypes.data if arena is not None else None), off.ctypes.data, r.ctypes.data, s.ctypes.data
+        if key_id is not None:
+            key_id = np.ascontiguousarray(key_id, dtype=np.uint32); keep.append(key_id)
+            b.key_id = key_id.ctypes.data
+        else:
+            qx, qy = _a8(qx), _a8(qy); keep += [qx, qy]
+            b.qx, b.qy = qx.ctypes.data, qy.ctypes.data
+        if pre_idx is not None:
+            pre_off = np.ascontiguousarray(pre_off, dtype=np.uint32); pre_idx = np.ascontiguousarray(pre_idx, dtype=np.uint32)
+            keep += [pre_off, pre_idx]
+            b.n_prefixes, b.pre_off, b.pre_idx = (pre_off.size // 2 if spans else pre_off.size - 1), pre_off.ctypes.data, pre_idx.ctypes.data
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        st = np.zeros(n, dtype=np.uint8) if want_status else None
+        b.verdict_bits = bits.ctypes.data
+        b.status = st.ctypes.data if want_status else None
+        mdig = None
+        if want_digests:
+            mdig = np.zeros((n, 32), dtype=np.uint8)
+            b.digests = mdig.ctypes.data
+        if tail is not None:
+            tail = _a8(tail)
+            keep.append(tail)
+            b.tail, b.tail_base, b.tail_len = tail.ctypes.data, tail_base, tail.size
+        _check(self._L.fabgpu_identity_verify_batch_p384(self._h, ctypes.byref(b)), "fabgpu_identity_verify_batch_p384")
+        return (unpack_bits(bits, n), st) + ((mdig,) if mdig is not None else ())
+
+    def identity_verify_batch_p384_dev(self, desc: "_IdBatchP384", mid_scratch, stream=0):
+        _check(self._L.fabgpu_identity_verify_batch_p384_dev(self._h, ctypes.byref(desc), mid_scratch or None, stream or None),
+               "fabgpu_identity_verify_batch_p384_dev")
+
     def p256_verify_batch_keyed_dev(self, n, key_id, e, r, s, verdict_bits, status, stream=0):
         _check(self._L.fabgpu_p256_verify_batch_keyed_dev(self._h, n, key_id, e, r, s, verdict_bits, status or None, stream or None),
                "fabgpu_p256_verify_batch_keyed_dev")
@@ -1128,6 +1189,14 @@ class GPUCSP:
         return bool(valid.value)
 
     # ---- ECDSA P-384 identities (option p384): keys are (x, y) integer pairs ----
+    def p384_pass_stats(self) -> dict:
+        """fabgpu_csp_p384_pass_stats: what the P-384 stage of this provider's block passes has done so far."""
+        v = (ctypes.c_uint64 * len(P384_PASS_STATS))()
+        n = self._L.fabgpu_csp_p384_pass_stats(self._h, v, len(P384_PASS_STATS))
+        if n != len(P384_PASS_STATS):
+            raise FabgpuError("fabgpu_csp_p384_pass_stats: %s" % strerror(n))
+        return dict(zip(P384_PASS_STATS, (int(x) for x in v)))
+
     def key_import_p384(self, key: Tuple[int, int]) -> Tuple[bool, str]:
         """BCCSP.KeyImport for a P-384 key (fabgpu_csp_key_import_p384): (on the curve, the error text or "")."""
         err = ctypes.create_string_buffer(256)
@@ -1459,6 +1528,14 @@ def identity_to_p256(ident: bytes):
     """Pure host: the P-256 key (64 bytes) the host route reads out of a SerializedIdentity, or None."""
     q = ctypes.create_string_buffer(64)
     return q.raw if load().fabgpu_identity_to_p256(ident, len(ident), q) == 0 else None
+
+
+def identity_to_p384(ident: bytes):
+    """Pure host: what the P-384 stage of the pass reads out of a SerializedIdentity: None (no certificate with an uncompressed secp384r1
+    key), or (qx48, qy48, on_curve) - a decoded point that is not on P-384 is refused by the on-curve gate."""
+    q = ctypes.create_string_buffer(96)
+    rc = load().fabgpu_identity_to_p384(ident, len(ident), q)
+    return None if rc == 1 else (q.raw[:48], q.raw[48:], rc == 0)
 
 
 def idfix_probe(csp: "GPUCSP", idents: Sequence[bytes]):

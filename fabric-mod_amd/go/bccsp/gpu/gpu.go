@@ -152,8 +152,9 @@ type Options struct {
 	SHA3 bool
 	// P384: Verify on an ECDSA P-384 key (bccsp/sw accepts them exactly as P-256 keys, bccsp/sw/keyimport.go, ecdsa.go:41-57) goes to the
 	// device through fabgpu_csp_verify_coalesced_p384 (option "p384") and takes only "valid" from it; everything else, and every error
-	// text, stays bccsp/sw's.  False (the default, also GPUFactory's): a P-384 key flows through untouched.  The block pass never
-	// serves P-384 (TX_NEEDS_SW), whatever this says.
+	// text, stays bccsp/sw's.  False (the default, also GPUFactory's): a P-384 key flows through untouched, and the block pass
+	// leaves a P-384 creator or endorser TX_NEEDS_SW.  True: the pass verifies them too (its P-384 stage, fabgpu_csp_p384_pass_stats) and
+	// the transaction's flag says so, but it seeds no memo entry for them - Verify below keeps asking the coalesced entry.
 	P384 bool
 }
 
@@ -520,7 +521,7 @@ func (p *Provider) Verify(k bccsp.Key, signature, digest []byte, opts bccsp.Sign
 	}
 	if p.p384 && k != nil && !k.Symmetric() && len(signature) != 0 && len(digest) != 0 && atomic.LoadUint32(&p.poisoned) == 0 {
 		if v, ok := p.keys384.Load(string(k.SKI())); ok {
-			// a P-384 identity (Options.P384): no memo holds it - the block pass leaves it to bccsp/sw - so the coalesced entry is asked
+			// a P-384 identity (Options.P384): no memo holds it - the block pass verifies it but seeds no entry for it - so the coalesced entry is asked
 			// directly, and only "valid" is taken from it
 			xy := v.(*[96]byte)
 			var valid, flags C.int

@@ -211,8 +211,8 @@ int fabgpu_sha3_256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const
  * before it queues anything - unlike every other _dev call it then does more than queue on `stream`, and it must not come under
  * stream capture.  fabgpu_p384_verify_batch_dev with n = 0 (every pointer but ctx may be NULL) does exactly that and launches nothing:
  * call it once, outside a capture and off a latency-sensitive path, and every later call only queues.
- * These six take fresh keys; registered keys follow below.  NOT served: the block pass (a P-384 endorser stays TX_NEEDS_SW),
- * fabgpu_multi_*. */
+ * These six take fresh keys; registered keys follow below; the described batch of the block pass is fabgpu_identity_verify_batch_p384.
+ * NOT served: fabgpu_multi_*. */
 int fabgpu_p384_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* e, const uint8_t* r,
                              const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);
 int fabgpu_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* qx, const void* qy, const void* e, const void* r, const void* s,
@@ -243,7 +243,7 @@ int fabgpu_sha3_256_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void*
  * fabgpu_p384_key_table_stats: out[0 .. min(cap, FABGPU_P384_KEY_TABLE_STATS)): live keys, slots draining, registrations that reused
  * a slot, slots parked for good, keyed P-384 launches queued so far, bytes of device memory the tables hold (the generator's
  * included), slots ever used.  Returns FABGPU_P384_KEY_TABLE_STATS.
- * NOT served for P-384: 16-bit tables, the block pass, the memos, fabgpu_multi_*. */
+ * NOT served for P-384: 16-bit tables, the memos, fabgpu_multi_*. */
 int fabgpu_p384_key_register(fabgpu_ctx* ctx, const uint8_t* qx48, const uint8_t* qy48, uint32_t* key_id);
 /* The same key on n contexts, each building its own table; contexts fed the same sequence of calls hand out the same ids.
  * key_ids[g] = the key's id on ctxs[g].  The first failure is returned (contexts before it keep the key). */
@@ -348,6 +348,49 @@ typedef struct fabgpu_identity_batch {
 int fabgpu_arena_stage(fabgpu_ctx* ctx, const void* arena, size_t len, uint64_t* token);
 int fabgpu_identity_verify_batch(fabgpu_ctx* ctx, const fabgpu_identity_batch* batch);
 int fabgpu_identity_verify_batch_dev(fabgpu_ctx* ctx, const fabgpu_identity_batch* batch, void* mid_scratch, void* stream);
+
+/* ---- identity.Verify over a DESCRIBED batch of P-384 identities (the P-384 stage of the block pass) ----
+ * The described batch above for keys on secp384r1: message i is  prefix[pre_idx[i]] || arena[off span i)  (the span alone where
+ * pre_idx[i] is 0xFFFFFFFF or the batch has no prefixes), hashed with SHA-256 - one launch writes the n digest rows, continuing from the
+ * prefixes' mid-states (p384_described_kernels.hip) - and verified by the fresh-key P-384 kernel (qx / qy) or the keyed one (key_id: ids
+ * of fabgpu_p384_key_register) behind it on the same stream.  qx, qy, r, s are n x 48 bytes; verdict words and statuses 0-4 are those of
+ * fabgpu_p384_verify_batch on (key, SHA-256 of the concatenated message as a 256-bit e, r, s), in its precedence.  `digests`
+ * (optional, n x 32 bytes): the SHA-256 of every message as it was verified.
+ * flags: FABGPU_IDB_SPANS, and FABGPU_IDB_ARENA_STAGED in the host variant.  FABGPU_IDB_SHA3_256 answers FABGPU_EINVAL HERE: this entry
+ * hashes with SHA-256 only (a SHA3 MSP's P-384 identities stay with bccsp/sw in the pass).  There is no gather part and no pseudonym part.
+ * A malformed description answers what fabgpu_identity_verify_batch answers for the same defect (a reversed span, a span that straddles
+ * tail_base or leaves the tail, a tail without FABGPU_IDB_SPANS or with a tail_base that is no multiple of 64, a stale stage_token:
+ * FABGPU_EINVAL).  n = 0 is the warm call of the form the batch names (fresh: the generator's table; key_id != NULL: the generator's
+ * comb) and launches nothing; every other pointer may be NULL then.
+ * Host variant: all pointers are host memory; the tail rides as in fabgpu_identity_batch, but a staged arena is only READ - the tail
+ * lies in a buffer of its own on the device.  _dev: all pointers are device memory, 4-byte aligned; arena_bytes = readable size of the
+ * arena allocation and a multiple of 4 (FABGPU_EINVAL otherwise) - no read reaches it; `tail` (optional, with FABGPU_IDB_SPANS) is device
+ * memory readable up to its last dword, spans at or above tail_base address tail[offset - tail_base]; mid_scratch = n_prefixes x 32
+ * bytes; asynchronous on `stream`; nothing is validated that lies in device memory - offsets are clamped, never followed out of bounds. */
+typedef struct fabgpu_identity_batch_p384 {
+    size_t n;
+    const void* arena;
+    size_t arena_bytes;          /* _dev only */
+    const uint32_t* off;         /* n + 1, or n (start, end) pairs with FABGPU_IDB_SPANS */
+    uint32_t n_prefixes;         /* 0 = no prefixes */
+    const uint32_t* pre_off;     /* n_prefixes + 1, or n_prefixes pairs */
+    const uint32_t* pre_idx;     /* n */
+    const void* qx;              /* n x 48, or NULL with key_id */
+    const void* qy;
+    const uint32_t* key_id;      /* n, or NULL with qx / qy */
+    const void* r;               /* n x 48 */
+    const void* s;
+    void* verdict_bits;          /* ceil(n/64) x u64 */
+    void* status;                /* n bytes or NULL */
+    uint32_t flags;              /* FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED */
+    uint64_t stage_token;        /* host variant with FABGPU_IDB_ARENA_STAGED */
+    const void* tail;
+    uint32_t tail_base;
+    uint32_t tail_len;
+    void* digests;               /* n x 32 bytes or NULL */
+} fabgpu_identity_batch_p384;
+int fabgpu_identity_verify_batch_p384(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* batch);
+int fabgpu_identity_verify_batch_p384_dev(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* batch, void* mid_scratch, void* stream);
 
 /* ---- idemix pseudonym signatures on FP256BN (BASELINE config 5) ----
  * NymSignature.Ver (idemix/nymsignature.go:74-109), reached per CREATOR signature from msp/idemixmsp.go:584-599 through

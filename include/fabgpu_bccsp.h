@@ -79,8 +79,9 @@ int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pa
  * validators' SHA3-256 digests can only miss the verdict memo, never hit a SHA-256 verdict) and the digest memo (SHA-256 only).
  * "p384" (default off; > 0 on): the *_p384 calls below verify ECDSA P-384 identities on the device.  Off, each of them answers, per item,
  * "P-384 is served by bccsp/sw, not by the GPU provider" (the identity call behind identity.Verify's "could not determine the validity of
- * the signature: ") and launches nothing; fabgpu_csp_key_import_p384 answers the same text and registers nothing.  NOT served either
- * way: the block pass (a P-384 endorser stays TX_NEEDS_SW), the verdict and digest memos.
+ * the signature: ") and launches nothing; fabgpu_csp_key_import_p384 answers the same text and registers nothing.  With the option on the
+ * block pass verifies P-384 creators and endorsers too (fabgpu_csp_p384_pass_stats below); off, a P-384 endorser stays TX_NEEDS_SW.  NOT
+ * served either way: the verdict and digest memos for P-384 tuples.
  * FABGPU_EINVAL: no such option. */
 int fabgpu_csp_set_option(fabgpu_csp* csp, const char* name, int64_t value, int64_t* previous);
 int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value);
@@ -317,6 +318,21 @@ int fabgpu_csp_pass_stats(fabgpu_csp* csp, uint64_t* out4);
 /* what the host route makes of a SerializedIdentity: 0 = PEM x509 certificate with an on-curve P-256 key (qxy64 = X || Y), 1 = anything else
  * (pure host; callers that hold identities as bytes - tools/go_call_replay.c - take the key bccsp.KeyImport would have remembered from it) */
 int fabgpu_identity_to_p256(const uint8_t* ident, size_t len, uint8_t* qxy64);
+/* ... and what the P-384 stage of the pass makes of it: 0 = PEM x509 certificate whose key is id-ecPublicKey on secp384r1 (1.3.132.0.34), a
+ * 97-byte uncompressed point ON the curve (qxy96 = X || Y); 2 = such a certificate whose point is not on P-384 (qxy96 set all the same:
+ * decoded, refused by the on-curve gate - its tuples stay TUPLE_ST_NEEDS_SW); 1 = anything else (another curve, a compressed point,
+ * idemix, truncated bytes).  Pure host. */
+int fabgpu_identity_to_p384(const uint8_t* ident, size_t len, uint8_t* qxy96);
+/* The P-384 stage of the block pass (option "p384"; with the option off every counter stays 0).  After either route has written the
+ * tuples' statuses, the tuples it left TUPLE_ST_NEEDS_SW whose identity is a certificate with an on-curve P-384 key are gated on the host
+ * and verified in one described batch over the staged block (fabgpu_identity_verify_batch_p384: the keyed kernel when every submitted
+ * key came through fabgpu_csp_key_import_p384, the fresh-key kernel otherwise), their statuses written (0-5, 7 as for P-256 tuples) and
+ * the flags of their transactions folded again.  out[0 .. min(cap, 6)): [0] passes that ran the stage, [1] P-384 tuples seen,
+ * [2] tuples submitted to the device, [3] keyed launches, [4] fresh-key launches, [5] tuples the CPU audit recomputed (audit_permille;
+ * a disagreement poisons the provider and the pass answers FABGPU_EPOISONED).  Returns 6.
+ * NOT in the stage: verdict and digest memo entries for P-384 tuples (tuple_hashed = 0, tuple_qxy and tuple_digest zero: the Go Verify
+ * for P-384 keeps asking the coalesced entry), SHA3 MSPs, fabgpu_multi_*, P-384 keys earning a table by hit count. */
+int fabgpu_csp_p384_pass_stats(fabgpu_csp* csp, uint64_t* out, int cap);
 
 /* (An x509 chain-link batch - crypto/x509 CheckSignatureFrom for n certificates - was an entry point of rounds 2-4 WITHOUT a consumer:
  * the only caller on this path is crypto/x509's own Verify (msp/mspimpl.go:721-739), which offers no hook for a pre-computed verdict, and
