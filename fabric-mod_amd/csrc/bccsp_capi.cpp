@@ -470,7 +470,7 @@ static int block_pass(fabgpu_csp* csp, fabgpu_block_pass* ps, uint32_t uncounted
         if (!e.ok()) return FABGPU_ELAUNCH;
     }
     // the P-384 stage (option p384): the tuples either route left to bccsp/sw that name P-384 certificates, before anything is handed out
-    if (!csp->csp->P384PassStage(ps->block, ps->len, pb, v, &up).ok()) return FABGPU_ELAUNCH;
+    if (!csp->csp->P384PassStage(ps->block, ps->len, pb, v, &up, opt).ok()) return FABGPU_ELAUNCH;
     if (csp->csp->P384Enabled() && csp->csp->Poisoned()) return FABGPU_EPOISONED;   // (its audit disagreed: what a poisoned pass answers)
     const size_t nt = v.tuple_status.size();
     if (ps->tx_flags && v.n_tx) memcpy(ps->tx_flags, v.tx_flags.data(), v.n_tx);
@@ -580,6 +580,22 @@ int fabgpu_csp_memo_stats(fabgpu_csp* csp, uint64_t* entries, uint64_t* hits, ui
 int fabgpu_csp_memo_set_capacity(fabgpu_csp* csp, uint64_t max_entries) {
     if (!csp) return FABGPU_EINVAL;
     csp->csp->MemoSetCapacity((size_t)max_entries);
+    return FABGPU_OK;
+}
+// the verdict memo of the pass's P-384 tuples (GPUCSP::MemoLookupP384): fabgpu_csp_memo_lookup's conventions with 48-byte coordinates
+int fabgpu_csp_memo_lookup_p384(fabgpu_csp* csp, const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig, size_t siglen, const uint8_t* digest,
+                                size_t dlen, uint8_t* status, uint64_t* block_seq) {
+    if (!csp) return 1;
+    return csp->csp->MemoLookupP384(qx48, qy48, sig, siglen, digest, dlen, status, block_seq);
+}
+int fabgpu_csp_memo_stats_p384(fabgpu_csp* csp, uint64_t* entries, uint64_t* hits, uint64_t* misses, uint64_t* evicted) {
+    if (!csp) return FABGPU_EINVAL;
+    csp->csp->MemoStatsP384(entries, hits, misses, evicted);
+    return FABGPU_OK;
+}
+int fabgpu_csp_memo_set_capacity_p384(fabgpu_csp* csp, uint64_t max_entries) {
+    if (!csp) return FABGPU_EINVAL;
+    csp->csp->MemoSetCapacityP384((size_t)max_entries);
     return FABGPU_OK;
 }
 int fabgpu_csp_identity_cache_limits(fabgpu_csp* csp, uint64_t max_identities, uint64_t max_registered_keys, uint32_t register_after_hits) {

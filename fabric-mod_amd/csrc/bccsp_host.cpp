@@ -955,7 +955,7 @@ Error GPUCSP::PreVerifyBlock(const uint8_t* block, size_t len, BlockVerdicts& ou
     static thread_local ParsedBlock pb;                   // storage reused from block to block
     if (!block || !ParseBlock(block, len, pb, WalkThreads())) return Error("block does not parse as common.Block");
     Error e = PreVerifyParsed(block, pb, out, &up, opt);
-    return e.ok() ? P384PassStage(block, len, pb, out, &up) : e;
+    return e.ok() ? P384PassStage(block, len, pb, out, &up, opt) : e;
 }
 
 
@@ -1603,15 +1603,16 @@ void GPUCSP::HashMemoStats(uint64_t* hits, uint64_t* misses, uint64_t* blocks_he
     if (refused) *refused = r;
 }
 size_t GPUCSP::MemoHasBlock(uint64_t block_seq) const {
+    size_t n = p384_memo_.HasBlock(block_seq);                               // (its own lock, taken and left before the P-256 table's)
     std::shared_lock<BigReaderLock> lk(memo_mu_);
-    size_t n = 0;
     for (const auto& b : memo_blocks_)
         if (b->seq == block_seq) n += b->n;
     return n;
 }
 size_t GPUCSP::MemoEvictBlock(uint64_t block_seq) const {
+    size_t gone = p384_memo_.EvictBlock(block_seq);                          // the block's P-384 record, counted by that table's own counter
+    const size_t gone384 = gone;
     std::unique_lock<BigReaderLock> lk(memo_mu_);
-    size_t gone = 0;
     for (auto b = memo_blocks_.begin(); b != memo_blocks_.end();) {
         if ((*b)->seq != block_seq) { ++b; continue; }
         gone += (*b)->n;
@@ -1619,7 +1620,7 @@ size_t GPUCSP::MemoEvictBlock(uint64_t block_seq) const {
         if (memo_free_.size() < memo_free_max_) memo_free_.push_back(*b);     // its buffers serve the next block (lookups hold the shared lock: none in flight here)
         b = memo_blocks_.erase(b);
     }
-    memo_evicted_.fetch_add(gone, std::memory_order_relaxed);
+    memo_evicted_.fetch_add(gone - gone384, std::memory_order_relaxed);      // (MemoStats stays about P-256 entries)
     return gone;
 }
 void GPUCSP::MemoStats(uint64_t* entries, uint64_t* hits, uint64_t* misses, uint64_t* evicted) const {
@@ -1635,6 +1636,36 @@ void GPUCSP::MemoSetCapacity(size_t max_entries) const {
     std::unique_lock<BigReaderLock> lk(memo_mu_);
     memo_cap_ = max_entries ? max_entries : 1;
 }
+// ---- the verdict memo of the pass's P-384 tuples (p384_memo.h; seeded by P384PassStage) ----
+int GPUCSP::MemoLookupP384(const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, uint8_t* status,
+                           uint64_t* block_seq) const {
+    if (!P384Enabled() || poisoned_.load(std::memory_order_acquire)) return 1;
+    uint64_t seq = 0;
+    uint32_t entry = 0;
+    uint8_t st = 0xFF;
+    if (p384_memo_.Lookup(qx48, qy48, sig, siglen, digest, dlen, &st, &seq, &entry) != 0) return 1;
+    // sampled as the P-256 entries are: the hit is decided again over the caller's arguments, against stored status 0 / anything else
+    if (audit_sample_p384_memo_.hit(AuditPermille())) {
+        bool accept;
+        {
+            AuditClock clk{audit_count_[AUDIT_NS]};
+            accept = audit_p384_verify(qx48, qy48, sig, siglen, digest, dlen);
+        }
+        audit_count_[AUDIT_VERDICT_P384].fetch_add(1, std::memory_order_relaxed);
+        if (accept != (st == FABGPU_ST_VALID)) {
+            audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
+            Poison("P-384 verdict memo: block " + std::to_string(seq) + " entry " + std::to_string(entry) + " holds status " + std::to_string(st) +
+                   ", the CPU audit says " + (accept ? "valid" : "invalid") + " (key X " + hex8(qx48) + "..)");
+            return 1;
+        }
+    }
+    if (poisoned_.load(std::memory_order_acquire)) return 1;                 // (another thread's audit failed meanwhile)
+    if (status) *status = st;
+    if (block_seq) *block_seq = seq;
+    return 0;
+}
+void GPUCSP::MemoStatsP384(uint64_t* entries, uint64_t* hits, uint64_t* misses, uint64_t* evicted) const { p384_memo_.Stats(entries, hits, misses, evicted); }
+void GPUCSP::MemoSetCapacityP384(size_t max_entries) const { p384_memo_.SetCapacity(max_entries); }
 void GPUCSP::SetIdentityCacheLimits(size_t max_identities, size_t max_registered_keys, uint32_t register_after_hits) const {
     {
         std::lock_guard<std::mutex> lk(idmu_);
@@ -3160,7 +3191,7 @@ void GPUCSP::P384PassStats(uint64_t out[P384_PASS_STATS]) const {
     for (int i = 0; i < P384_PASS_STATS; i++) out[i] = p384_pass_[i].load(std::memory_order_relaxed);
 }
 
-Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock& parsed, BlockVerdicts& out, BlockUpload* up) const {
+Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock& parsed, BlockVerdicts& out, BlockUpload* up, const PassOptions& opt) const {
     if (!P384Enabled() || Poisoned() || !block) return Error();
     const size_t nt = out.tuple_status.size();
     if (!nt || !memchr(out.tuple_status.data(), TUPLE_ST_NEEDS_SW, nt)) return Error();   // (an all-P-256 block: 40 000 status bytes read once)
@@ -3296,6 +3327,11 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
         d.s = s.data();
         d.verdict_bits = bits.data();
         d.status = st.data();
+        std::vector<uint8_t> dig;                                        // seeding: the digests as the device verified them, the memo's keys
+        if (opt.seed_memo) {
+            dig.resize(32 * n);
+            d.digests = dig.data();
+        }
         if (!pb->tail.empty()) {
             d.tail = pb->tail.data();
             d.tail_base = pb->tail_base;
@@ -3349,6 +3385,25 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
                 audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
                 Poison(std::string("block pass: the device accepted a P-384 signature that the CPU audit rejects (key X ") + hex8(rows[j].key.x) + "..)");
                 return Error();                                          // (the caller answers what a poisoned pass answers)
+            }
+        }
+        // The verdict memo of these tuples (p384_memo.h): one entry per row the device decided, with the status written above and the
+        // signature bytes as they sit in the caller's block - the bytes the audit just used.  Rows skipped for a retired id get none.
+        // Published whether or not the block also published a BlockMemo; a provider poisoned meanwhile publishes nothing.
+        if (opt.seed_memo && !Poisoned()) {
+            try {
+                auto rec = std::make_shared<P384Memo::Record>(opt.block_seq, n);
+                for (size_t j = 0; j < n; j++) {
+                    if (keyed && st[j] == FABGPU_ST_OFF_CURVE) continue;
+                    const BlockTuple& tp = pb->tuples[rows[j].tuple];
+                    rec->Add(rows[j].key.x, rows[j].key.y, block + tp.sig.off, tp.sig.len, &dig[32 * j], 32, out.tuple_status[rows[j].tuple]);
+                }
+                const uint32_t added = rec->size();
+                if (p384_memo_.Publish(std::move(rec), &poisoned_)) {
+                    out.memo_seeded += added;
+                    p384_pass_[P384_PASS_MEMO_SEEDED].fetch_add(added, std::memory_order_relaxed);
+                }
+            } catch (const std::bad_alloc&) {                            // no entries for this block: its lookups miss
             }
         }
     }

@@ -19,6 +19,7 @@
 #include <chrono>
 #include <mutex>
 
+#include "p384_memo.h"
 #include "reader_lock.h"
 #include <shared_mutex>
 #include <thread>
@@ -213,7 +214,7 @@ class GPUCSP {
     // false, and *err says who serves it.
     bool HashFamily(const char* family, bool* sha3, std::string* err) const;
     bool Sha3Enabled() const { return hash_sha3_.load(std::memory_order_relaxed); }
-    // ---- ECDSA P-384 identities (option p384; direct calls only: never the block pass or the memos) ----
+    // ---- ECDSA P-384 identities (option p384): the direct calls (the pass's stage and its verdict memo: further down) ----
     // Answers and error texts are those of the P-256 namesakes.  With the option off every item answers P384RefusalText().
     // KeyImportP384: bccsp.KeyImport for a P-384 key - KeyImport's texts; an on-curve key gets its comb table on every device of the pool
     // (fabgpu_p384_key_register_many; best effort), and batches whose submitted items all name registered keys then take the keyed
@@ -269,6 +270,16 @@ class GPUCSP {
     size_t MemoHasBlock(uint64_t block_seq) const;            // entries still held under block_seq (0: never seeded, evicted, or aged out)
     void MemoStats(uint64_t* entries, uint64_t* hits, uint64_t* misses, uint64_t* evicted) const;
     void MemoSetCapacity(size_t max_entries) const;
+    // ... and for the P-384 tuples a pass verified (P384PassStage): a table of its own (p384_memo.h), keyed on 48-byte coordinates, under a
+    // lock of its own - a P-384 lookup never takes the P-256 memo's lock, a P-256 lookup never meets this table.  Same answers as
+    // MemoLookup (0 hit, 1 miss; with the p384 option off or on a poisoned provider: always a miss); hits are sampled by the CPU audit
+    // (audit_p384_verify over the caller's arguments against stored status 0 / anything else; a disagreement poisons the provider and
+    // answers a miss).
+    // MemoEvictBlock and MemoHasBlock count this table's entries too; MemoStats and MemoSetCapacity do not touch it.
+    int MemoLookupP384(const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, uint8_t* status,
+                       uint64_t* block_seq = nullptr) const;
+    void MemoStatsP384(uint64_t* entries, uint64_t* hits, uint64_t* misses, uint64_t* evicted) const;
+    void MemoSetCapacityP384(size_t max_entries) const;
     // identity cache bounds (msp/cache/cache.go keeps 100 deserialized identities; the pass sees every client certificate too)
     void SetIdentityCacheLimits(size_t max_identities, size_t max_registered_keys, uint32_t register_after_hits) const;
     size_t IdentityCacheSize() const;
@@ -285,9 +296,13 @@ class GPUCSP {
     // the CPU (audit_permille; a disagreement poisons the provider).  Option off, provider poisoned, or no such tuple: nothing is
     // launched and nothing allocated.  parsed.tuples must hold the route's tuple records, or be empty (the device route without
     // WANT_TUPLES): the stage then walks the block on the host for the records of the tuples it needs.
-    // NOT here: memo entries for P-384 tuples (tuple_hashed stays 0, tuple_qxy / tuple_digest stay zero), SHA3 MSPs.
-    Error P384PassStage(const uint8_t* block, size_t len, const ParsedBlock& parsed, BlockVerdicts& out, BlockUpload* up) const;
-    enum : int { P384_PASS_STAGES = 0, P384_PASS_SEEN = 1, P384_PASS_SUBMITTED = 2, P384_PASS_KEYED = 3, P384_PASS_FRESH = 4, P384_PASS_AUDITED = 5, P384_PASS_STATS = 6 };
+    // opt.seed_memo: every row the device decided is remembered under opt.block_seq in the P-384 verdict memo (MemoLookupP384), keyed on
+    // the digest the device computed, with the status written here; out.memo_seeded grows by their number.  Rows the host gate decided
+    // (empty, DER, high S, range) and rows skipped for a retired key id get no entry: a miss sends them to bccsp/sw, which owns their texts.
+    // NOT here: the digest memo (tuple_hashed stays 0, tuple_qxy / tuple_digest stay zero: they are framed for 32-byte coordinates, and
+    // bccsp.Hash of these messages stays on the CPU), SHA3 MSPs.
+    Error P384PassStage(const uint8_t* block, size_t len, const ParsedBlock& parsed, BlockVerdicts& out, BlockUpload* up, const PassOptions& opt) const;
+    enum : int { P384_PASS_STAGES = 0, P384_PASS_SEEN = 1, P384_PASS_SUBMITTED = 2, P384_PASS_KEYED = 3, P384_PASS_FRESH = 4, P384_PASS_AUDITED = 5, P384_PASS_MEMO_SEEDED = 6, P384_PASS_STATS = 7 };
     void P384PassStats(uint64_t out[P384_PASS_STATS]) const;
     // Starts the upload of a block on a helper thread (blocks of 4 MiB and more) so that it travels while the caller parses
     // and gates; join() returns the token for PreVerifyParsed (0 if nothing was staged).
@@ -324,7 +339,8 @@ class GPUCSP {
     // out in order of registration per context); -1: not accelerated.  ipk_raw: marshalled idemix.IssuerPublicKey.
     int64_t ImportIdemixIssuer(const uint8_t* ipk_raw, size_t len, std::string* err = nullptr) const;
     // ---- CPU audit of what the device hands out, and poisoning (audit_host.h; DESIGN.md 4.4e addendum) ----
-    // With audit_permille > 0 a fixed share of the digest-memo hits, of the verdict-memo hits for P-256 entries and of the "valid"
+    // With audit_permille > 0 a fixed share of the digest-memo hits, of the verdict-memo hits for P-256 entries, of the hits of
+    // the P-384 verdict memo (a sampler and a counter of their own: AUDIT_VERDICT_P384) and of the "valid"
     // answers of the direct calls is re-computed on the calling thread before it is returned.  The first disagreement poisons the
     // provider: one flag for every context of the pool and every thread, never cleared.  From then on every lookup misses, every
     // verify / identity / nym / hash / block-pass entry of the C surface answers FABGPU_EPOISONED without launching anything, and a
@@ -333,7 +349,7 @@ class GPUCSP {
     // the digest memo holds, checked against the digest first - and the "valid" answers of the nym batch (AuditNymDirect).  A sampled
     // pseudonym result that cannot be audited (the block copy is gone or was never kept, the issuer's fields are not at hand) is handed
     // out as it is and counted in AUDIT_SKIPPED_NYM.
-    enum : int { AUDIT_DIGEST = 0, AUDIT_VERDICT = 1, AUDIT_DIRECT = 2, AUDIT_MISMATCHES = 3, AUDIT_SKIPPED_NYM = 4, AUDIT_NS = 5, AUDIT_NYM = 6, AUDIT_STATS = 7 };
+    enum : int { AUDIT_DIGEST = 0, AUDIT_VERDICT = 1, AUDIT_DIRECT = 2, AUDIT_MISMATCHES = 3, AUDIT_SKIPPED_NYM = 4, AUDIT_NS = 5, AUDIT_NYM = 6, AUDIT_VERDICT_P384 = 7, AUDIT_STATS = 8 };
     void Poison(const std::string& why) const;                 // the first reason is kept
     bool Poisoned(std::string* why = nullptr) const;
     void AuditStats(uint64_t out[AUDIT_STATS]) const;
@@ -374,6 +390,7 @@ class GPUCSP {
     struct alignas(64) HitCounter : AuditSampler {};
     mutable HitCounter audit_sample_[3];                    // one hit counter per audited kind (AUDIT_DIGEST / _VERDICT / _DIRECT)
     mutable HitCounter audit_sample_nym_;                   // ... and the pseudonym results' (memo hits and "valid" batch answers)
+    mutable HitCounter audit_sample_p384_memo_;             // ... and the hits of the P-384 verdict memo (AUDIT_VERDICT_P384)
     // what the pseudonym audit needs of every issuer ImportIdemixIssuer put on the devices: hsk_x || hsk_y || hrand_x || hrand_y || hash
     typedef std::array<uint8_t, 160> AuditIssuer;
     mutable std::mutex audit_issuer_mu_;                    // (a leaf: nothing is taken under it)
@@ -469,7 +486,8 @@ class GPUCSP {
     // test hook (TestAccess, libfabgpu_testhooks.so): so many of the device's next P-384 arithmetic rejects are read as "valid" - the
     // corruption the audit must catch.  Nothing in the product sets it.
     mutable std::atomic<uint32_t> test_p384_flip_{0};
-    mutable std::atomic<uint64_t> p384_pass_[6] = {};        // P384PassStats
+    mutable std::atomic<uint64_t> p384_pass_[P384_PASS_STATS] = {};   // P384PassStats
+    mutable P384Memo p384_memo_;                             // the verdict memo of the pass's P-384 tuples (its own lock and capacity inside)
     // as AuditDirect, for a P-384 "valid": re-computed with the host compilation of p384.h (audit_p384_verify)
     bool AuditDirectP384(const ECDSAPublicKey384& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
                          const uint8_t* msg = nullptr, size_t msglen = 0, bool sha3 = false) const;

@@ -78,6 +78,11 @@ int fabgpu_csp_test_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, int kind, 
 /* TEST HOOK: the provider reads the next `count` arithmetic rejects (status 1) the device gives in fabgpu_csp_verify_batch_p384 /
  * _verify_coalesced_p384 as "valid": a corrupted P-384 verdict, which the sampled audit has to catch. */
 int fabgpu_csp_test_p384_corrupt(fabgpu_csp* csp, uint32_t count);
+/* TEST HOOK: the index-th entry of the P-384 verdict memo's record under block_seq - entries are in the order the pass's P-384 stage
+ * submitted their tuples - gets status 0 where it held a reject: what fabgpu_csp_memo_lookup_p384 would then hand out as "valid", and
+ * what its sampled audit has to catch.  Host memory of the library, nothing is launched.  0 done, 1 nothing to corrupt (no such
+ * record, or the entry is valid already), FABGPU_EINVAL. */
+int fabgpu_csp_test_p384_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, uint32_t index);
 /* TEST HOOK (no device, no provider): what the *_p384 calls of a provider answer per item while its p384 option is off. */
 const char* fabgpu_test_p384_refusal_text(void);
 /* TEST HOOK: the allocator of key slots and ids by itself (csrc/key_slots.h; no device, no context).  gen_last: the last generation a

@@ -24,6 +24,19 @@ namespace fab {
 namespace bccsp {
 struct TestAccess {
     static void p384_corrupt(const GPUCSP& c, uint32_t count) { c.test_p384_flip_.store(count, std::memory_order_relaxed); }
+    // the index-th stored status of the P-384 record under block_seq, from a reject to "valid" (p384_memo.h: host memory, under the table's write lock)
+    static int p384_memo_corrupt(const GPUCSP& c, uint64_t block_seq, uint32_t index) {
+        fab::P384Memo& m = c.p384_memo_;
+        std::unique_lock<BigReaderLock> lk(m.mu_);
+        for (const auto& r : m.blocks_) {
+            if (r->seq_ != block_seq) continue;
+            if (index >= r->size()) return FABGPU_EINVAL;
+            if (r->status_[index] == FABGPU_ST_VALID) return 1;                                  // already "valid": nothing the audit could catch
+            r->status_[index] = FABGPU_ST_VALID;
+            return FABGPU_OK;
+        }
+        return 1;                                                                                // no record under that block_seq
+    }
     static int memo_corrupt(const GPUCSP& c, uint64_t block_seq, int kind, uint32_t index) {
         std::unique_lock<BigReaderLock> lk(c.memo_mu_);
         for (const auto& b : c.memo_blocks_) {
@@ -323,6 +336,13 @@ int fabgpu_csp_test_p384_corrupt(fabgpu_csp* csp, uint32_t count) {
     if (!csp) return FABGPU_EINVAL;
     TestAccess::p384_corrupt(*csp->csp, count);
     return 0;
+}
+// TEST HOOK: the index-th entry of the P-384 verdict memo's record under block_seq (entries are in the order the stage submitted their
+// tuples) gets status 0 where it held a reject - what fabgpu_csp_memo_lookup_p384 would hand out as "valid".  0 done, 1 nothing to
+// corrupt there (no such record, or the entry is valid already), FABGPU_EINVAL.
+int fabgpu_csp_test_p384_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, uint32_t index) {
+    if (!csp) return FABGPU_EINVAL;
+    return TestAccess::p384_memo_corrupt(*csp->csp, block_seq, index);
 }
 int fabgpu_csp_test_memo_corrupt(fabgpu_csp* csp, uint64_t block_seq, int kind, uint32_t index) {
     if (!csp) return FABGPU_EINVAL;

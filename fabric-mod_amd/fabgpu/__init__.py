@@ -120,7 +120,7 @@ class _Cfg(ctypes.Structure):
 # what fabgpu_p256_key_table_stats reports, in order
 KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "live_16bit", "bytes_held", "slots_used")
 # ... fabgpu_csp_p384_pass_stats
-P384_PASS_STATS = ("stages", "seen", "submitted", "keyed_launches", "fresh_launches", "audited")
+P384_PASS_STATS = ("stages", "seen", "submitted", "keyed_launches", "fresh_launches", "audited", "memo_seeded")
 # ... and fabgpu_p384_key_table_stats
 P384_KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "keyed_launches", "bytes_held", "slots_used")
 P384_COMB_WORDS = 48 * 256 * 24      # one P-384 comb table (csrc/p384_tables.h CombTab384): 1.125 MiB
@@ -164,6 +164,7 @@ ABI_SYMBOLS = [
     "fabgpu_sha256_p384_verify_batch_keyed", "fabgpu_sha256_p384_verify_batch_keyed_dev",
     "fabgpu_sha3_256_p384_verify_batch_keyed", "fabgpu_sha3_256_p384_verify_batch_keyed_dev", "fabgpu_csp_key_import_p384",
     "fabgpu_identity_verify_batch_p384", "fabgpu_identity_verify_batch_p384_dev", "fabgpu_identity_to_p384", "fabgpu_csp_p384_pass_stats",
+    "fabgpu_csp_memo_lookup_p384", "fabgpu_csp_memo_stats_p384", "fabgpu_csp_memo_set_capacity_p384",
 ]
 
 # what libfabgpu_testhooks.so exports (fabric-mod_amd/csrc/fabgpu_testhooks.h): probes, walker comparisons, the synthetic block generator, the
@@ -172,7 +173,7 @@ HOOK_SYMBOLS = [
     "fabgpu_synth_batch", "fabgpu_last_kernel_ms", "fabgpu_csp_block_walk_compare", "fabgpu_block_walk_twopass_compare", "fabgpu_gate_sig_fast",
     "fabgpu_gate_sig_any", "fabgpu_csp_idfix_probe", "fabgpu_csp_gate_probe", "fabgpu_identity_table_hash", "fabgpu_test_nym_side_after",
     "fabgpu_test_key_table", "fabgpu_test_key_table_host", "fabgpu_test_gtab_compare_with_host", "fabgpu_test_key_tables16",
-    "fabgpu_test_audit_sha256", "fabgpu_test_audit_p256_verify", "fabgpu_test_audit_nym_verify", "fabgpu_test_audit_sample", "fabgpu_csp_test_memo_corrupt", "fabgpu_csp_test_p384_corrupt", "fabgpu_test_p384_refusal_text",
+    "fabgpu_test_audit_sha256", "fabgpu_test_audit_p256_verify", "fabgpu_test_audit_nym_verify", "fabgpu_test_audit_sample", "fabgpu_csp_test_memo_corrupt", "fabgpu_csp_test_p384_corrupt", "fabgpu_csp_test_p384_memo_corrupt", "fabgpu_test_p384_refusal_text",
     "fabgpu_test_key_slots_new", "fabgpu_test_key_slots_free", "fabgpu_test_key_slots_register", "fabgpu_test_key_slots_retire",
     "fabgpu_test_key_slots_drain", "fabgpu_test_key_slots_stats", "fabgpu_test_walk_buffer_caps",
     "fabgpu_test_p384_key_table", "fabgpu_test_p384_key_table_host", "fabgpu_test_p384_verify_keyed_host", "fabgpu_test_p384_key_register_batch",
@@ -227,6 +228,7 @@ def load_hooks():
     H.fabgpu_test_audit_sample.restype = ctypes.c_longlong
     H.fabgpu_csp_test_memo_corrupt.argtypes = [_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32]
     H.fabgpu_csp_test_p384_corrupt.argtypes = [_vp, ctypes.c_uint32]
+    H.fabgpu_csp_test_p384_memo_corrupt.argtypes = [_vp, ctypes.c_uint64, ctypes.c_uint32]
     H.fabgpu_test_p384_refusal_text.restype = ctypes.c_char_p
     H.fabgpu_test_key_slots_new.argtypes = [ctypes.c_uint32]
     H.fabgpu_test_key_slots_new.restype = _vp
@@ -384,6 +386,9 @@ def load():
     L.fabgpu_csp_memo_evict_block.argtypes = [_vp, ctypes.c_uint64, _u64p]
     L.fabgpu_csp_memo_stats.argtypes = [_vp, _u64p, _u64p, _u64p, _u64p]
     L.fabgpu_csp_memo_set_capacity.argtypes = [_vp, ctypes.c_uint64]
+    L.fabgpu_csp_memo_lookup_p384.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, _u8p, _u64p]
+    L.fabgpu_csp_memo_stats_p384.argtypes = [_vp, _u64p, _u64p, _u64p, _u64p]
+    L.fabgpu_csp_memo_set_capacity_p384.argtypes = [_vp, ctypes.c_uint64]
     L.fabgpu_csp_hash_lookup.argtypes = [_vp, ctypes.c_char_p, _sz, ctypes.c_char_p]
     L.fabgpu_csp_hash_memo_stats.argtypes = [_vp, _u64p, _u64p, _u64p, _u64p, _u64p]
     L.fabgpu_csp_poison.argtypes = [_vp, ctypes.c_char_p]
@@ -1118,6 +1123,15 @@ class GPUCSP:
             raise FabgpuError("fabgpu_csp_audit_stats: %s" % strerror(n))
         return dict(zip(("digest_audits", "verdict_audits", "direct_audits", "mismatches", "skipped_nym", "audit_ns", "nym_audits"), (int(x) for x in v)))
 
+    def p384_verdict_audits(self) -> int:
+        """The slot fabgpu_csp_audit_stats appends behind those seven: hits of the P-384 verdict memo (memo_lookup_p384) the CPU audit
+        recomputed.  Their mismatches are counted with everybody's."""
+        v = (ctypes.c_uint64 * 8)()
+        n = self._L.fabgpu_csp_audit_stats(self._h, v, 8)
+        if n != 8:
+            raise FabgpuError("fabgpu_csp_audit_stats: %s" % strerror(n))
+        return int(v[7])
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.fabgpu_csp_free(self._h)
@@ -1644,6 +1658,15 @@ def p384_corrupt(csp: "GPUCSP", count: int) -> None:
     load_hooks().fabgpu_csp_test_p384_corrupt(csp._h, count)
 
 
+def p384_memo_corrupt(csp: "GPUCSP", block_seq: int, index: int) -> int:
+    """TEST HOOK: entry `index` of the P-384 verdict memo's record under block_seq gets status 0 where it held a reject
+    (fabgpu_csp_test_p384_memo_corrupt).  0 done, 1 nothing to corrupt there."""
+    rc = load_hooks().fabgpu_csp_test_p384_memo_corrupt(csp._h, block_seq, index)
+    if rc < 0:
+        raise FabgpuError("fabgpu_csp_test_p384_memo_corrupt: %s" % strerror(rc))
+    return rc
+
+
 def memo_corrupt(csp: "GPUCSP", block_seq: int, kind: int, index: int) -> int:
     """TEST HOOK: corrupts entry `index` of the memo table under block_seq in host memory - kind 0 one bit of its stored digest, kind 1
     its stored status (valid <-> bad signature; a pseudonym entry's: valid <-> proof invalid), kind 2 one bit of the message the entry
@@ -1707,6 +1730,27 @@ def memo_lookup(csp: "GPUCSP", qx32: bytes, qy32: bytes, sig: bytes, digest: byt
     st = ctypes.c_uint8(255)
     rc = csp._L.fabgpu_csp_memo_lookup(csp._h, qx32, qy32, sig, len(sig), digest, len(digest), ctypes.byref(st))
     return int(st.value) if rc == 0 else None
+
+
+def memo_lookup_p384(csp: "GPUCSP", qx48: bytes, qy48: bytes, sig: bytes, digest: bytes) -> Optional[Tuple[int, int]]:
+    """The bccsp.Verify(k, sig, digest) question for a P-384 key against the verdict memo of the pass's P-384 tuples
+    (fabgpu_csp_memo_lookup_p384): (tuple status, block_seq of the pass that seeded the entry) on a hit, None on a miss."""
+    st = ctypes.c_uint8(255)
+    seq = ctypes.c_uint64(0)
+    rc = csp._L.fabgpu_csp_memo_lookup_p384(csp._h, qx48, qy48, sig, len(sig), digest, len(digest), ctypes.byref(st), ctypes.byref(seq))
+    return (int(st.value), int(seq.value)) if rc == 0 else None
+
+
+def memo_stats_p384(csp: "GPUCSP"):
+    """Counters of the P-384 verdict memo (fabgpu_csp_memo_stats_p384); memo_stats stays about the P-256 table."""
+    v = [ctypes.c_uint64(0) for _ in range(4)]
+    _check(csp._L.fabgpu_csp_memo_stats_p384(csp._h, *[ctypes.byref(x) for x in v]), "fabgpu_csp_memo_stats_p384")
+    return dict(entries=v[0].value, hits=v[1].value, misses=v[2].value, evicted=v[3].value)
+
+
+def memo_set_capacity_p384(csp: "GPUCSP", max_entries: int) -> None:
+    """Entries the P-384 verdict memo may hold (fabgpu_csp_memo_set_capacity_p384); the oldest block goes first while it is over."""
+    _check(csp._L.fabgpu_csp_memo_set_capacity_p384(csp._h, max_entries), "fabgpu_csp_memo_set_capacity_p384")
 
 
 def hash_lookup(csp: "GPUCSP", msg: bytes) -> Optional[bytes]:

@@ -91,7 +91,8 @@ type Provider struct {
 	// orderer (Broadcast handlers behind SigFilter, orderer/common/msgprocessor/sigfilter.go:50-80).  Off by default: a
 	// lone call costs a launch (0.7 ms) where bccsp/sw costs 0.1 ms; the break-even is about sixteen calls in flight.
 	coalesce bool
-	// p384: Options.P384 - Verify on a P-384 key asks the device first (fabgpu_csp_verify_coalesced_p384); keys384 remembers the
+	// p384: Options.P384 - Verify on a P-384 key asks the P-384 verdict memo (fabgpu_csp_memo_lookup_p384) and, on a miss, the device
+	// (fabgpu_csp_verify_coalesced_p384) before bccsp/sw; keys384 remembers the
 	// coordinates of the P-384 public keys KeyImport has seen, by SKI (string(ski) -> *[96]byte); each is registered on the device once
 	// (fabgpu_csp_key_import_p384)
 	p384    bool
@@ -154,7 +155,8 @@ type Options struct {
 	// device through fabgpu_csp_verify_coalesced_p384 (option "p384") and takes only "valid" from it; everything else, and every error
 	// text, stays bccsp/sw's.  False (the default, also GPUFactory's): a P-384 key flows through untouched, and the block pass
 	// leaves a P-384 creator or endorser TX_NEEDS_SW.  True: the pass verifies them too (its P-384 stage, fabgpu_csp_p384_pass_stats) and
-	// the transaction's flag says so, but it seeds no memo entry for them - Verify below keeps asking the coalesced entry.
+	// the transaction's flag says so, and a memo-seeding pass remembers their verdicts in a memo of their own: Verify below asks
+	// fabgpu_csp_memo_lookup_p384 first and the coalesced entry only on a miss.  bccsp.Hash of their messages stays bccsp/sw's.
 	P384 bool
 }
 
@@ -521,9 +523,22 @@ func (p *Provider) Verify(k bccsp.Key, signature, digest []byte, opts bccsp.Sign
 	}
 	if p.p384 && k != nil && !k.Symmetric() && len(signature) != 0 && len(digest) != 0 && atomic.LoadUint32(&p.poisoned) == 0 {
 		if v, ok := p.keys384.Load(string(k.SKI())); ok {
-			// a P-384 identity (Options.P384): no memo holds it - the block pass verifies it but seeds no entry for it - so the coalesced entry is asked
-			// directly, and only "valid" is taken from it
+			// a P-384 identity (Options.P384): first the verdict memo of the pass's P-384 tuples (fabgpu_csp_memo_lookup_p384; digest is
+			// the SHA-256 bccsp/sw just computed - bccsp.Hash of these messages is not served by the digest memo).  Status 0: valid.  A hit
+			// with any other status: the pass rejected exactly this tuple - bccsp/sw decides it again and owns the error text, no launch.
+			// A miss - no pass seeded it, the block was evicted, a tuple the pass's host gate decided - takes the coalesced entry as
+			// before, and only "valid" is taken from it.
 			xy := v.(*[96]byte)
+			var st C.uint8_t
+			hit := C.fabgpu_csp_memo_lookup_p384(p.csp, (*C.uint8_t)(unsafe.Pointer(&xy[0])), (*C.uint8_t)(unsafe.Pointer(&xy[48])),
+				(*C.uint8_t)(unsafe.Pointer(&signature[0])), C.size_t(len(signature)),
+				(*C.uint8_t)(unsafe.Pointer(&digest[0])), C.size_t(len(digest)), &st, nil)
+			if hit == 0 && st == C.FABGPU_ST_VALID {
+				return true, nil
+			}
+			if hit == 0 {
+				return p.BCCSP.Verify(k, signature, digest, opts)
+			}
 			var valid, flags C.int
 			var errbuf [8]C.char
 			rc := C.fabgpu_csp_verify_coalesced_p384(p.csp, (*C.uint8_t)(unsafe.Pointer(&xy[0])), (*C.uint8_t)(unsafe.Pointer(&xy[48])),
@@ -720,6 +735,14 @@ func (p *Provider) MemoStats() (entries, hits, misses, evicted uint64) {
 	return uint64(e), uint64(h), uint64(m), uint64(v)
 }
 
+// MemoStatsP384: the same counters of the verdict memo of the pass's P-384 tuples (Options.P384; a table of its own: MemoStats does not
+// count its entries or lookups).
+func (p *Provider) MemoStatsP384() (entries, hits, misses, evicted uint64) {
+	var e, h, m, v C.uint64_t
+	C.fabgpu_csp_memo_stats_p384(p.csp, &e, &h, &m, &v)
+	return uint64(e), uint64(h), uint64(m), uint64(v)
+}
+
 // ---- metrics (SURVEY.md section 5: next to gossip_privdata_validation_duration, gossip/metrics/metrics.go:161-187) ----
 
 var (
@@ -749,6 +772,11 @@ var (
 		Help: "Verdict memo: entries held, bccsp.Verify lookups answered (hits), lookups left to bccsp/sw (misses), entries evicted; digest memo: bccsp.Hash calls answered (hash_hits) / left to bccsp/sw (hash_misses), block copies held, copies refused",
 		LabelNames: []string{"what"}, StatsdFormat: "%{#fqname}.%{what}",
 	}
+	memoP384Opts = metrics.GaugeOpts{
+		Namespace: "bccsp", Subsystem: "gpu", Name: "verdict_memo_p384",
+		Help: "Verdict memo of the block pass's P-384 tuples (Options.P384): entries held, bccsp.Verify lookups for P-384 keys answered (hits), lookups left to the coalesced entry or bccsp/sw (misses), entries evicted",
+		LabelNames: []string{"what"}, StatsdFormat: "%{#fqname}.%{what}",
+	}
 	auditMismatchOpts = metrics.CounterOpts{
 		Namespace: "fabgpu", Name: "audit_mismatches",
 		Help: "Results of the device that the provider's sampled CPU audit re-computed and found different (the first one poisons the provider)",
@@ -773,6 +801,7 @@ type passMetrics struct {
 	duration         metrics.Histogram
 	tx, sigs, failed metrics.Counter
 	routes, memo     metrics.Gauge
+	memoP384         metrics.Gauge
 	auditMismatches  metrics.Counter
 	auditNym         metrics.Gauge
 	poisoned         metrics.Gauge
@@ -807,6 +836,7 @@ func (p *Provider) RegisterMetrics(mp metrics.Provider, refresh time.Duration) {
 			failed: mp.NewCounter(passFailedOpts), routes: mp.NewGauge(passRouteOpts), memo: mp.NewGauge(memoOpts),
 			auditMismatches: mp.NewCounter(auditMismatchOpts), poisoned: mp.NewGauge(poisonedOpts),
 			auditNym: mp.NewGauge(auditNymOpts),
+			memoP384: mp.NewGauge(memoP384Opts),
 			keyTables: mp.NewGauge(keyTablesOpts),
 		}
 		m.poisoned.Set(0)
@@ -838,6 +868,13 @@ func (p *Provider) RegisterMetrics(mp metrics.Provider, refresh time.Duration) {
 				m.memo.With("what", "hits").Set(float64(hit))
 				m.memo.With("what", "misses").Set(float64(miss))
 				m.memo.With("what", "evicted").Set(float64(ev))
+				if p.p384 {
+					e, hit, miss, ev = p.MemoStatsP384()
+					m.memoP384.With("what", "entries").Set(float64(e))
+					m.memoP384.With("what", "hits").Set(float64(hit))
+					m.memoP384.With("what", "misses").Set(float64(miss))
+					m.memoP384.With("what", "evicted").Set(float64(ev))
+				}
 				hh, hm, hb, _, hr := p.HashMemoStats()
 				m.memo.With("what", "hash_hits").Set(float64(hh))
 				m.memo.With("what", "hash_misses").Set(float64(hm))

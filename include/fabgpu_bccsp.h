@@ -80,8 +80,10 @@ int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pa
  * "p384" (default off; > 0 on): the *_p384 calls below verify ECDSA P-384 identities on the device.  Off, each of them answers, per item,
  * "P-384 is served by bccsp/sw, not by the GPU provider" (the identity call behind identity.Verify's "could not determine the validity of
  * the signature: ") and launches nothing; fabgpu_csp_key_import_p384 answers the same text and registers nothing.  With the option on the
- * block pass verifies P-384 creators and endorsers too (fabgpu_csp_p384_pass_stats below); off, a P-384 endorser stays TX_NEEDS_SW.  NOT
- * served either way: the verdict and digest memos for P-384 tuples.
+ * block pass verifies P-384 creators and endorsers too (fabgpu_csp_p384_pass_stats below); off, a P-384 endorser stays TX_NEEDS_SW.  A
+ * pass with FABGPU_PASS_SEED_MEMO also remembers their verdicts, in a memo of their own (fabgpu_csp_memo_lookup_p384 below).  NOT
+ * served either way: the digest memo for P-384 tuples - fabgpu_csp_hash_lookup misses for their messages and the validators hash
+ * them on the CPU; that SHA-256 is the digest the verdict entries are keyed on.
  * FABGPU_EINVAL: no such option. */
 int fabgpu_csp_set_option(fabgpu_csp* csp, const char* name, int64_t value, int64_t* previous);
 int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value);
@@ -95,6 +97,8 @@ int fabgpu_csp_key_table_stats(fabgpu_csp* csp, int d, uint64_t* out, int cap);
  * re-computes a fixed share of them on the calling thread, in host code, before they are returned:
  *   - fabgpu_csp_hash_lookup hits: SHA-256 of the caller's message;
  *   - fabgpu_csp_memo_lookup hits: bccsp.Verify(k, sig, digest) as bccsp/sw decides it, against stored status 0 / anything else;
+ *   - fabgpu_csp_memo_lookup_p384 hits (a kind and a hit counter of their own): ECDSA P-384 over the caller's key, signature and
+ *     digest with csrc/p384.h compiled for the host, against stored status 0 / anything else;
  *   - "valid" answers of fabgpu_csp_verify, _verify_batch, _verify_coalesced, _identity_verify_batch, _identity_verify_coalesced
  *     (the identity calls hash the message again first - with SHA3-256, through the kernels' own sha3_256.h compiled for the host, when
  *     the call's hash family is SHA3).  Rejects are not sampled: the Go side re-checks every reject in bccsp/sw.
@@ -116,8 +120,8 @@ int fabgpu_csp_key_table_stats(fabgpu_csp* csp, int d, uint64_t* out, int cap);
  * serves everything from bccsp/sw from then on.
  * fabgpu_csp_poison poisons by hand (why may be NULL); fabgpu_csp_poisoned returns 1 / 0 and the FIRST reason (why may be NULL).
  * fabgpu_csp_audit_stats: out[0] digest audits, [1] verdict audits, [2] direct-call audits, [3] mismatches, [4] skipped_nym: sampled
- * pseudonym results that could not be audited, [5] nanoseconds spent auditing, [6] pseudonym audits; returns how many were written
- * (cap < 7: the first cap - a caller that asks for 6 gets the six values it always got). */
+ * pseudonym results that could not be audited, [5] nanoseconds spent auditing, [6] pseudonym audits, [7] audits of P-384 verdict-memo
+ * hits; returns how many were written (cap < 8: the first cap - a caller that asks for 6 or 7 gets the values it always got). */
 int fabgpu_csp_poison(fabgpu_csp* csp, const char* why);
 int fabgpu_csp_poisoned(fabgpu_csp* csp, char* why, size_t cap);
 int fabgpu_csp_audit_stats(fabgpu_csp* csp, uint64_t* out, int cap);
@@ -299,6 +303,28 @@ int fabgpu_csp_memo_has_block(fabgpu_csp* csp, uint64_t block_seq, uint64_t* ent
 int fabgpu_csp_memo_evict_block(fabgpu_csp* csp, uint64_t block_seq, uint64_t* evicted);
 int fabgpu_csp_memo_stats(fabgpu_csp* csp, uint64_t* entries, uint64_t* hits, uint64_t* misses, uint64_t* evicted);
 int fabgpu_csp_memo_set_capacity(fabgpu_csp* csp, uint64_t max_entries);
+/* ---- the verdict memo of the P-384 tuples of a pass (option "p384") ----
+ * A pass with FABGPU_PASS_SEED_MEMO on a provider with the option on remembers, under its block_seq, every P-384 tuple its P-384 stage
+ * submitted to the device: (key X48 || Y48, signature bytes as they sit in the block, the SHA-256 digest the device verified) -> the
+ * status the stage wrote (0, or 1 / 3 / 4 as in fabgpu.h).  The entries live in a table of their own, seeded on the host, beside the
+ * P-256 memo: fabgpu_csp_memo_lookup and its table are unchanged and never meet 48-byte coordinates; this lookup never waits for theirs.
+ * fabgpu_csp_memo_lookup_p384 answers the bccsp.Verify(k, sig, digest) call of msp/identities.go:188 for a P-384 key with the
+ * conventions of fabgpu_csp_memo_lookup: 0 hit, *status set (0 valid; anything else: the reference rejects - ask bccsp/sw for its
+ * text) and *block_seq (may be NULL) = the pass that seeded the entry; 1 miss -> the coalesced entry or bccsp/sw.  With the option
+ * off, or on a poisoned provider, always a miss.  A key seeded twice answers with its first entry.
+ * No entry, so a miss: tuples the stage's host gate decided (empty signature, DER that does not unmarshal, high S, r or s out of range -
+ * bccsp/sw owns their error texts), tuples of a key id retired under the launch, identities that are no on-curve P-384 certificate.
+ * Lifetime: fabgpu_csp_memo_evict_block(seq) also drops the P-384 record of seq and *evicted counts its entries too;
+ * fabgpu_csp_memo_has_block adds them.  The table is bounded by a capacity of its own (default 65 536 entries; the oldest block goes
+ * first while it is over; fabgpu_csp_memo_set_capacity does not touch it), and fabgpu_csp_memo_stats stays about the P-256 table:
+ * fabgpu_csp_memo_stats_p384 reports this one (any pointer may be NULL).
+ * NOT served: bccsp.Hash for these messages (tuple_hashed stays 0, fabgpu_csp_hash_lookup keeps missing: the validators hash them on the
+ * CPU, and that SHA-256 is the digest the entries are keyed on), SHA3 MSPs, fabgpu_multi_*.  The layout of the pass's outputs does not
+ * change: tuple_qxy and tuple_digest stay zero for these tuples - they are framed for 32-byte coordinates. */
+int fabgpu_csp_memo_lookup_p384(fabgpu_csp* csp, const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig, size_t siglen, const uint8_t* digest,
+                                size_t dlen, uint8_t* status, uint64_t* block_seq);
+int fabgpu_csp_memo_stats_p384(fabgpu_csp* csp, uint64_t* entries, uint64_t* hits, uint64_t* misses, uint64_t* evicted);
+int fabgpu_csp_memo_set_capacity_p384(fabgpu_csp* csp, uint64_t max_entries);
 /* Bounds of the pass's identity cache (identities come out of unvalidated blocks): at most max_identities cached (LRU, like
  * msp/cache), a device comb table only for an identity named register_after_hits times, at most max_registered_keys tables. */
 int fabgpu_csp_identity_cache_limits(fabgpu_csp* csp, uint64_t max_identities, uint64_t max_registered_keys, uint32_t register_after_hits);
@@ -327,11 +353,13 @@ int fabgpu_identity_to_p384(const uint8_t* ident, size_t len, uint8_t* qxy96);
  * tuples' statuses, the tuples it left TUPLE_ST_NEEDS_SW whose identity is a certificate with an on-curve P-384 key are gated on the host
  * and verified in one described batch over the staged block (fabgpu_identity_verify_batch_p384: the keyed kernel when every submitted
  * key came through fabgpu_csp_key_import_p384, the fresh-key kernel otherwise), their statuses written (0-5, 7 as for P-256 tuples) and
- * the flags of their transactions folded again.  out[0 .. min(cap, 6)): [0] passes that ran the stage, [1] P-384 tuples seen,
+ * the flags of their transactions folded again.  out[0 .. min(cap, 7)): [0] passes that ran the stage, [1] P-384 tuples seen,
  * [2] tuples submitted to the device, [3] keyed launches, [4] fresh-key launches, [5] tuples the CPU audit recomputed (audit_permille;
- * a disagreement poisons the provider and the pass answers FABGPU_EPOISONED).  Returns 6.
- * NOT in the stage: verdict and digest memo entries for P-384 tuples (tuple_hashed = 0, tuple_qxy and tuple_digest zero: the Go Verify
- * for P-384 keeps asking the coalesced entry), SHA3 MSPs, fabgpu_multi_*, P-384 keys earning a table by hit count. */
+ * a disagreement poisons the provider and the pass answers FABGPU_EPOISONED), [6] entries seeded into the P-384 verdict memo
+ * (FABGPU_PASS_SEED_MEMO; fabgpu_csp_memo_lookup_p384 above; fabgpu_block_pass.memo_seeded includes them).  Returns how many values
+ * there are (7); a caller that passes the old capacity of 6 still gets the first six.
+ * NOT in the stage: digest memo entries for P-384 tuples (tuple_hashed = 0, tuple_qxy and tuple_digest zero; bccsp.Hash of their
+ * messages stays on the CPU), SHA3 MSPs, fabgpu_multi_*, P-384 keys earning a table by hit count. */
 int fabgpu_csp_p384_pass_stats(fabgpu_csp* csp, uint64_t* out, int cap);
 
 /* (An x509 chain-link batch - crypto/x509 CheckSignatureFrom for n certificates - was an entry point of rounds 2-4 WITHOUT a consumer:
