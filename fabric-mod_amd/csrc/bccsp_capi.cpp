@@ -719,6 +719,19 @@ int fabgpu_csp_p384_pass_stats(fabgpu_csp* csp, uint64_t* out, int cap) {
     for (int i = 0; i < cap && i < GPUCSP::P384_PASS_STATS; i++) out[i] = v[i];
     return GPUCSP::P384_PASS_STATS;
 }
+// an MSP's hash family, for the P-384 stage (GPUCSP::SetMspHashFamily)
+int fabgpu_csp_msp_hash_family(fabgpu_csp* csp, const char* mspid, const char* family, char* err, size_t errcap) {
+    if (!csp || !mspid) return FABGPU_EINVAL;
+    std::string text;
+    const bool ok = csp->csp->SetMspHashFamily(mspid, family, &text);
+    put_err(err, errcap, ok ? std::string() : text);
+    return ok ? FABGPU_OK : 1;
+}
+int fabgpu_csp_msp_hash_family_get(fabgpu_csp* csp, const char* mspid, int* sha3) {
+    if (!csp || !mspid || !sha3) return FABGPU_EINVAL;
+    *sha3 = csp->csp->MspSetSha3(mspid) ? 1 : 0;
+    return FABGPU_OK;
+}
 // ---- idemix (idemix_host.h) ----
 int fabgpu_csp_idemix_msp_register(fabgpu_csp* csp, const char* mspid, const uint8_t* ipk_raw, size_t len, int64_t* issuer_id) {
     return fabgpu_csp_idemix_msp_register2(csp, "", mspid, ipk_raw, len, issuer_id);

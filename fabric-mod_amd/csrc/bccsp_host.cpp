@@ -637,19 +637,17 @@ Error GPUCSP::Hash(const uint8_t* msg, size_t len, const HashOpts* opts, std::ve
 }
 // msp/identities.go:216-224 getHashOpt
 bool GPUCSP::HashFamily(const char* family, bool* sha3, std::string* err) const {
-    const std::string f = family ? family : "";
-    *sha3 = false;
-    if (f == "SHA2") return true;
-    if (f == "SHA3") {
-        if (!Sha3Enabled()) {
-            if (err) *err = "failed computing digest: SHA3 is served by bccsp/sw, not by the GPU provider";
-            return false;
-        }
-        *sha3 = true;
-        return true;
+    return ParseHashFamily(family, Sha3Enabled(), sha3, err);                // (msp_family.h: the texts live there)
+}
+// the family the pass hashes an MSP's P-384 tuples with (msp_family.h)
+bool GPUCSP::SetMspHashFamily(const std::string& mspid, const char* family, std::string* err) const {
+    bool sha3 = false;
+    if (!HashFamily(family, &sha3, err)) return false;
+    if (!msp_family_.Set(mspid, sha3)) {
+        if (err) *err = "invalid mspid";
+        return false;
     }
-    if (err) *err = "hash familiy not recognized [" + f + "]";               // (the reference's spelling)
-    return false;
+    return true;
 }
 
 namespace {
@@ -3211,24 +3209,35 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
     struct Row {
         uint32_t tuple;
         ECDSAPublicKey384 key;
+        bool sha3;                                                       // the identity's MSP is set SHA3 (msp_family.h)
     };
+    struct Front {
+        Span identity;
+        CachedIdentity ci;
+        bool sha3;
+    };
+    // what one family's rows send: key, r and s columns, and the rows they belong to
+    struct Family {
+        std::vector<uint32_t> row;
+        std::vector<uint8_t> qx, qy, r, s;
+    } fam[2];                                                            // [0] SHA2 rows, [1] SHA3 rows
     std::vector<Row> rows;
-    std::vector<std::pair<Span, CachedIdentity>> front;                  // a block names few identities
+    std::vector<Front> front;                                            // a block names few identities
     static const uint8_t one_digest[1] = {1};
-    std::vector<uint8_t> qx, qy, r, s;
+    const bool any_sha3 = Sha3Enabled() && msp_family_.AnySha3();        // (read once: a change holds for passes that start after it)
     uint64_t seen = 0;
     bool touched = false;
     for (uint32_t i : sw) {
         const BlockTuple& tp = pb->tuples[i];
         if ((uint64_t)tp.identity.off + tp.identity.len > len || (uint64_t)tp.sig.off + tp.sig.len > len) continue;
         const uint8_t* ident = block + tp.identity.off;
-        const CachedIdentity* ci = nullptr;
+        const Front* fr = nullptr;
         for (auto& f : front)
-            if (f.first.len == tp.identity.len && memcmp(block + f.first.off, ident, tp.identity.len) == 0) {
-                ci = &f.second;
+            if (f.identity.len == tp.identity.len && memcmp(block + f.identity.off, ident, tp.identity.len) == 0) {
+                fr = &f;
                 break;
             }
-        if (!ci) {
+        if (!fr) {
             CachedIdentity c;
             bool cached = false;
             std::string key((const char*)ident, tp.identity.len);
@@ -3253,9 +3262,15 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
                     }
                 }
             }
-            front.emplace_back(tp.identity, c);
-            ci = &front.back().second;
+            // the MSP's family: looked up per pass, never kept in the identity cache
+            bool sha3 = false;
+            const uint8_t* mspid;
+            size_t mspid_len;
+            if (any_sha3 && c.p384 == 1 && IdentityMspId(ident, tp.identity.len, mspid, mspid_len)) sha3 = msp_family_.Sha3(mspid, mspid_len);
+            front.push_back(Front{tp.identity, c, sha3});
+            fr = &front.back();
         }
+        const CachedIdentity* ci = &fr->ci;
         if (ci->p384 != 1) continue;
         seen++;
         touched = true;
@@ -3265,6 +3280,7 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
         }
         Row row;
         row.tuple = i;
+        row.sha3 = fr->sha3;
         memcpy(row.key.x, ci->qx384, 48);
         memcpy(row.key.y, ci->qy384, 48);
         row.key.on_curve = true;
@@ -3275,24 +3291,33 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
             else out.tuple_status[i] = TUPLE_ST_BAD_DER;
             continue;
         }
+        Family& f = fam[row.sha3 ? 1 : 0];
+        f.row.push_back((uint32_t)rows.size());
         rows.push_back(row);
-        qx.insert(qx.end(), row.key.x, row.key.x + 48);
-        qy.insert(qy.end(), row.key.y, row.key.y + 48);
-        r.insert(r.end(), g.r, g.r + 48);
-        s.insert(s.end(), g.s, g.s + 48);
+        f.qx.insert(f.qx.end(), row.key.x, row.key.x + 48);
+        f.qy.insert(f.qy.end(), row.key.y, row.key.y + 48);
+        f.r.insert(f.r.end(), g.r, g.r + 48);
+        f.s.insert(f.s.end(), g.s, g.s + 48);
     }
     if (!touched) return Error();
     p384_pass_[P384_PASS_STAGES].fetch_add(1, std::memory_order_relaxed);
     p384_pass_[P384_PASS_SEEN].fetch_add(seen, std::memory_order_relaxed);
     const size_t n = rows.size();
-    std::vector<uint8_t> st(n, 0);
-    std::vector<uint64_t> bits((n + 63) / 64, 0);
-    if (n) {
-        // one described batch over the block: message spans and prefixes from the tuples' own records, the orderers' messages in the tail
-        std::vector<uint32_t> off(2 * n), pre_idx(n), pre_off;
+    std::vector<uint8_t> st(n, 0), ok(n, 0), from_keyed(n, 0);           // per row: status byte, verdict bit, answered by a keyed launch
+    std::vector<uint8_t> dig;                                            // seeding: the digests as the device verified them, the memo's keys
+    if (opt.seed_memo) dig.resize(32 * n);
+    uint64_t tok = 0;
+    bool joined = false;
+    for (int sha3 = 0; sha3 < 2; sha3++) {
+        // one described batch per family over the block: message spans and prefixes from the tuples' own records, the orderers' messages
+        // in the tail.  A block without SHA3 rows: the one batch there always was.
+        const Family& f = fam[sha3];
+        const size_t fn = f.row.size();
+        if (!fn) continue;
+        std::vector<uint32_t> off(2 * fn), pre_idx(fn), pre_off;
         std::vector<std::pair<uint64_t, uint32_t>> pre_seen;             // (off << 32 | len) -> index, in order of first use
-        for (size_t j = 0; j < n; j++) {
-            const BlockTuple& tp = pb->tuples[rows[j].tuple];
+        for (size_t j = 0; j < fn; j++) {
+            const BlockTuple& tp = pb->tuples[rows[f.row[j]].tuple];
             off[2 * j] = tp.suffix.off;
             off[2 * j + 1] = tp.suffix.off + tp.suffix.len;
             pre_idx[j] = 0xFFFFFFFFu;
@@ -3308,52 +3333,65 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
         Dev& dv = *devs_[(size_t)(up && (up->routed || up->started) ? up->dev : 0)];
         fabgpu_identity_batch_p384 d;
         memset(&d, 0, sizeof(d));
-        d.n = n;
+        d.n = fn;
         d.arena = block;
         d.off = off.data();
         d.n_prefixes = (uint32_t)(pre_off.size() / 2);
         d.pre_off = pre_off.data();
         d.pre_idx = pre_idx.data();
         std::vector<uint32_t> ids;
-        const std::vector<uint8_t> submitted(n, 1);
-        const bool keyed = all_registered384(dv.ctx, n, submitted, qx.data(), qy.data(), ids);
+        const std::vector<uint8_t> submitted(fn, 1);
+        const bool keyed = all_registered384(dv.ctx, fn, submitted, f.qx.data(), f.qy.data(), ids);
         if (keyed) {
             d.key_id = ids.data();
         } else {
-            d.qx = qx.data();
-            d.qy = qy.data();
+            d.qx = f.qx.data();
+            d.qy = f.qy.data();
         }
-        d.r = r.data();
-        d.s = s.data();
+        d.r = f.r.data();
+        d.s = f.s.data();
+        std::vector<uint8_t> fst(fn, 0), fdig;
+        std::vector<uint64_t> bits((fn + 63) / 64, 0);
         d.verdict_bits = bits.data();
-        d.status = st.data();
-        std::vector<uint8_t> dig;                                        // seeding: the digests as the device verified them, the memo's keys
+        d.status = fst.data();
         if (opt.seed_memo) {
-            dig.resize(32 * n);
-            d.digests = dig.data();
+            fdig.resize(32 * fn);
+            d.digests = fdig.data();
         }
         if (!pb->tail.empty()) {
             d.tail = pb->tail.data();
             d.tail_base = pb->tail_base;
             d.tail_len = (uint32_t)pb->tail.size();
         }
-        const uint64_t tok = up ? up->join() : 0;
+        if (!joined) tok = up ? up->join() : 0;                          // (both batches read the same staged block)
+        joined = true;
+        const auto submit = sha3 ? fabgpu_identity_verify_batch_p384_sha3 : fabgpu_identity_verify_batch_p384;   // the family is the entry's
         int rc = FABGPU_EINVAL;
         if (tok) {
             d.flags = FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED;
             d.stage_token = tok;
-            rc = fabgpu_identity_verify_batch_p384(dv.ctx, &d);          // FABGPU_EINVAL: somebody else's upload replaced ours -> resubmit with the bytes
+            rc = submit(dv.ctx, &d);                                     // FABGPU_EINVAL: somebody else's upload replaced ours -> resubmit with the bytes
         }
         d.flags = FABGPU_IDB_SPANS;
-        if (!tok || rc == FABGPU_EINVAL) rc = fabgpu_identity_verify_batch_p384(dv.ctx, &d);
+        if (!tok || rc == FABGPU_EINVAL) rc = submit(dv.ctx, &d);
         if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
-        p384_pass_[P384_PASS_SUBMITTED].fetch_add(n, std::memory_order_relaxed);
+        p384_pass_[P384_PASS_SUBMITTED].fetch_add(fn, std::memory_order_relaxed);
         p384_pass_[keyed ? P384_PASS_KEYED : P384_PASS_FRESH].fetch_add(1, std::memory_order_relaxed);
+        if (sha3) p384_pass_[P384_PASS_SHA3_ROWS].fetch_add(fn, std::memory_order_relaxed);
+        for (size_t j = 0; j < fn; j++) {
+            const uint32_t k = f.row[j];
+            st[k] = fst[j];
+            ok[k] = (uint8_t)((bits[j >> 6] >> (j & 63)) & 1);
+            from_keyed[k] = keyed ? 1 : 0;
+            if (opt.seed_memo) memcpy(&dig[32 * (size_t)k], &fdig[32 * j], 32);
+        }
+    }
+    if (n) {
         std::string msg;
         for (size_t j = 0; j < n; j++) {
             const uint32_t i = rows[j].tuple;
-            if (keyed && st[j] == FABGPU_ST_OFF_CURVE) continue;          // (the id was retired under the launch: "use bccsp/sw", never "invalid")
-            bool valid = ((bits[j >> 6] >> (j & 63)) & 1) && st[j] == FABGPU_ST_VALID;
+            if (from_keyed[j] && st[j] == FABGPU_ST_OFF_CURVE) continue;  // (the id was retired under the launch: "use bccsp/sw", never "invalid")
+            bool valid = ok[j] && st[j] == FABGPU_ST_VALID;
             if (!valid && st[j] == FABGPU_ST_BAD_MATH) {                 // (test hook: a corrupted verdict)
                 uint32_t f = test_p384_flip_.load(std::memory_order_relaxed);
                 while (f && !test_p384_flip_.compare_exchange_weak(f, f - 1)) {}
@@ -3361,7 +3399,7 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
             }
             out.tuple_status[i] = valid ? FABGPU_ST_VALID : (st[j] == FABGPU_ST_VALID ? FABGPU_ST_BAD_MATH : st[j]);
             if (!valid || !audit_sample_[AUDIT_DIRECT].hit(AuditPermille())) continue;
-            // the audit: the message bytes of the CALLER's block, hashed and verified on the CPU
+            // the audit: the message bytes of the CALLER's block, hashed (with the row's family) and verified on the CPU
             const BlockTuple& tp = pb->tuples[i];
             auto bytes_of = [&](const Span& sp) -> const uint8_t* {
                 if (!pb->tail.empty() && sp.off >= pb->tail_base) return (uint64_t)sp.off - pb->tail_base + sp.len <= pb->tail.size() ? pb->tail.data() + (sp.off - pb->tail_base) : nullptr;
@@ -3375,7 +3413,8 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
                     msg.assign((const char*)pp, tp.prefix.len);
                     msg.append((const char*)sp, tp.suffix.len);
                     uint8_t dg[32];
-                    audit_sha256((const uint8_t*)msg.data(), msg.size(), dg);
+                    if (rows[j].sha3) audit_sha3_256((const uint8_t*)msg.data(), msg.size(), dg);
+                    else audit_sha256((const uint8_t*)msg.data(), msg.size(), dg);
                     accept = audit_p384_verify(rows[j].key.x, rows[j].key.y, block + tp.sig.off, tp.sig.len, dg, 32);
                 }
             }
@@ -3394,7 +3433,7 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
             try {
                 auto rec = std::make_shared<P384Memo::Record>(opt.block_seq, n);
                 for (size_t j = 0; j < n; j++) {
-                    if (keyed && st[j] == FABGPU_ST_OFF_CURVE) continue;
+                    if (from_keyed[j] && st[j] == FABGPU_ST_OFF_CURVE) continue;
                     const BlockTuple& tp = pb->tuples[rows[j].tuple];
                     rec->Add(rows[j].key.x, rows[j].key.y, block + tp.sig.off, tp.sig.len, &dig[32 * j], 32, out.tuple_status[rows[j].tuple]);
                 }

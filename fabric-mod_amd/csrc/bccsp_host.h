@@ -19,6 +19,7 @@
 #include <chrono>
 #include <mutex>
 
+#include "msp_family.h"
 #include "p384_memo.h"
 #include "reader_lock.h"
 #include <shared_mutex>
@@ -214,6 +215,12 @@ class GPUCSP {
     // false, and *err says who serves it.
     bool HashFamily(const char* family, bool* sha3, std::string* err) const;
     bool Sha3Enabled() const { return hash_sha3_.load(std::memory_order_relaxed); }
+    // The hash family of an MSP as the block pass knows it (msp_family.h; every MSP is SHA2 until set): family as HashFamily takes it, and
+    // refused as HashFamily refuses it (false, *err the text; also for an empty or overlong mspid).  Read by P384PassStage once per identity
+    // of a pass: a change holds for passes that start after the call returns.  An MSP set SHA3 counts as SHA3 only while the hash_sha3
+    // option is on.  P-256 tuples do not ask: the routes hash them with SHA-256 whatever their MSP.
+    bool SetMspHashFamily(const std::string& mspid, const char* family, std::string* err) const;
+    bool MspSetSha3(const std::string& mspid) const { return msp_family_.Sha3(mspid); }   // what was set, whatever the option says now
     // ---- ECDSA P-384 identities (option p384): the direct calls (the pass's stage and its verdict memo: further down) ----
     // Answers and error texts are those of the P-256 namesakes.  With the option off every item answers P384RefusalText().
     // KeyImportP384: bccsp.KeyImport for a P-384 key - KeyImport's texts; an on-curve key gets its comb table on every device of the pool
@@ -300,9 +307,13 @@ class GPUCSP {
     // the digest the device computed, with the status written here; out.memo_seeded grows by their number.  Rows the host gate decided
     // (empty, DER, high S, range) and rows skipped for a retired key id get no entry: a miss sends them to bccsp/sw, which owns their texts.
     // NOT here: the digest memo (tuple_hashed stays 0, tuple_qxy / tuple_digest stay zero: they are framed for 32-byte coordinates, and
-    // bccsp.Hash of these messages stays on the CPU), SHA3 MSPs.
+    // bccsp.Hash of these messages stays on the CPU).
+    // Hash family: a tuple whose identity names an MSP set SHA3 (SetMspHashFamily) is hashed with SHA3-256.  After gating the rows are
+    // split by family and go out as at most two described batches over the same staged block (SHA2 rows, then SHA3 rows through
+    // fabgpu_identity_verify_batch_p384_sha3), each keyed or fresh on its own keys; the audit hashes a SHA3 row with audit_sha3_256, and the memo entries of
+    // SHA3 rows carry the SHA3-256 digest.  No MSP set SHA3: no mspid is read and one batch goes out, as before.
     Error P384PassStage(const uint8_t* block, size_t len, const ParsedBlock& parsed, BlockVerdicts& out, BlockUpload* up, const PassOptions& opt) const;
-    enum : int { P384_PASS_STAGES = 0, P384_PASS_SEEN = 1, P384_PASS_SUBMITTED = 2, P384_PASS_KEYED = 3, P384_PASS_FRESH = 4, P384_PASS_AUDITED = 5, P384_PASS_MEMO_SEEDED = 6, P384_PASS_STATS = 7 };
+    enum : int { P384_PASS_STAGES = 0, P384_PASS_SEEN = 1, P384_PASS_SUBMITTED = 2, P384_PASS_KEYED = 3, P384_PASS_FRESH = 4, P384_PASS_AUDITED = 5, P384_PASS_MEMO_SEEDED = 6, P384_PASS_SHA3_ROWS = 7, P384_PASS_STATS = 8 };
     void P384PassStats(uint64_t out[P384_PASS_STATS]) const;
     // Starts the upload of a block on a helper thread (blocks of 4 MiB and more) so that it travels while the caller parses
     // and gates; join() returns the token for PreVerifyParsed (0 if nothing was staged).
@@ -487,6 +498,7 @@ class GPUCSP {
     // corruption the audit must catch.  Nothing in the product sets it.
     mutable std::atomic<uint32_t> test_p384_flip_{0};
     mutable std::atomic<uint64_t> p384_pass_[P384_PASS_STATS] = {};   // P384PassStats
+    mutable MspFamilyTable msp_family_;                      // mspid -> hash family, for P384PassStage (its own lock inside)
     mutable P384Memo p384_memo_;                             // the verdict memo of the pass's P-384 tuples (its own lock and capacity inside)
     // as AuditDirect, for a P-384 "valid": re-computed with the host compilation of p384.h (audit_p384_verify)
     bool AuditDirectP384(const ECDSAPublicKey384& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,

@@ -131,6 +131,8 @@ bool IdentityToP384(const uint8_t* ident, size_t len, uint8_t qx[48], uint8_t qy
     return CertDerToP384(der.data(), der.size(), qx, qy);
 }
 
+bool IdentityMspId(const uint8_t* ident, size_t len, const uint8_t*& mspid, size_t& mspid_len) { return pb_bytes(ident, len, 1, mspid, mspid_len); }
+
 namespace {
 void der_len(std::vector<uint8_t>& o, size_t n) {
     if (n < 128) { o.push_back((uint8_t)n); return; }

@@ -135,6 +135,8 @@ bool PemToDer(const uint8_t* pem, size_t len, std::vector<uint8_t>& der);
 // point, 48 bytes a coordinate.  false: not such an identity.  Whether the point is ON P-384 is the caller's next question
 // (fabgpu_p384_pubkey_on_curve), as PublicKeyOnCurve is IdentityToP256's.  Host only: the device's identity table keeps P-256 keys.
 bool IdentityToP384(const uint8_t* ident, size_t len, uint8_t qx[48], uint8_t qy[48]);
+// SerializedIdentity{1 mspid, ..} -> the mspid's bytes inside ident.  false: the field is absent, repeated or malformed.
+bool IdentityMspId(const uint8_t* ident, size_t len, const uint8_t*& mspid, size_t& mspid_len);
 bool CertDerToP384(const uint8_t* der, size_t len, uint8_t qx[48], uint8_t qy[48]);
 // protoutil.BlockHeaderBytes (protoutil/blockutils.go:38-58): DER of SEQUENCE{INTEGER number, OCTET STRING previous_hash, OCTET STRING data_hash}
 void BlockHeaderBytes(uint64_t number, const uint8_t* prev, size_t prev_len, const uint8_t* data_hash, size_t dh_len, std::vector<uint8_t>& out);

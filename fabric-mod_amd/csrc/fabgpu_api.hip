@@ -2845,9 +2845,10 @@ int fabgpu_identity_verify_batch(fabgpu_ctx* ctx, const fabgpu_identity_batch* b
     return FABGPU_OK;
 }
 
-// ---- identity.Verify over a described batch of P-384 identities: the digest rows (p384_described_kernels.hip), then the fresh or
-// the keyed P-384 kernel over them on the same stream --------------------------------------------------------------------------------
-int fabgpu_identity_verify_batch_p384_dev(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* b, void* mid_scratch, void* stream) {
+// ---- identity.Verify over a described batch of P-384 identities: the digest rows (p384_described_kernels.hip; for the _sha3 entries
+// p384_described_sha3_kernels.hip), then the fresh or the keyed P-384 kernel over them on the same stream.  One body per form, the hash
+// family a parameter: the flags a caller may pass are the same for both families (FABGPU_IDB_SHA3_256 is not among them) ------------
+static int identity_verify_batch_p384_dev(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* b, void* mid_scratch, void* stream, bool sha3) {
     if (!ctx || !b) return FABGPU_EINVAL;
     const size_t n = b->n;
     const bool keyed = b->key_id != nullptr;
@@ -2856,7 +2857,8 @@ int fabgpu_identity_verify_batch_p384_dev(fabgpu_ctx* ctx, const fabgpu_identity
     const bool prefixed = b->n_prefixes != 0 && b->pre_idx != nullptr;
     if (!b->arena || !b->off || !b->r || !b->s || !b->verdict_bits || (!keyed && (!b->qx || !b->qy))) return FABGPU_EINVAL;
     if (prefixed && (!b->pre_off || !mid_scratch)) return FABGPU_EINVAL;
-    if (b->flags & ~(uint32_t)FABGPU_IDB_SPANS) return FABGPU_EINVAL;   // (FABGPU_IDB_SHA3_256 among them: SHA-256 only)
+    if (b->flags & ~(uint32_t)FABGPU_IDB_SPANS) return FABGPU_EINVAL;   // (FABGPU_IDB_SHA3_256 among them: the family is the entry's)
+    if (sha3 && prefixed && ((uintptr_t)mid_scratch & 7u)) return FABGPU_EINVAL;   // (mid_scratch: 200 bytes a prefix)
     if (dev_too_big(n, b->arena_bytes)) return FABGPU_ETOOBIG;
     const bool has_tail = b->tail != nullptr && b->tail_len != 0;
     if (has_tail && (!(b->flags & FABGPU_IDB_SPANS) || (b->tail_base & 63u) || (uint64_t)b->tail_base + b->tail_len > 0xFFFFFFF0ull)) return FABGPU_EINVAL;
@@ -2882,7 +2884,7 @@ int fabgpu_identity_verify_batch_p384_dev(fabgpu_ctx* ctx, const fabgpu_identity
         v.tail = b->tail; v.tail_base = b->tail_base; v.tail_len = b->tail_len;
     }
     v.digests = dig;
-    int rc = timed_launch(ctx, st, 0, [&](void*) { return launch_p384_described_digests(v, st); });
+    int rc = timed_launch(ctx, st, 0, [&](void*) { return sha3 ? launch_p384_described_sha3_digests(v, st) : launch_p384_described_digests(v, st); });
     if (rc == FABGPU_OK)
         rc = keyed ? p384_verify_keyed_dev(ctx, n, b->key_id, dig, true, b->r, b->s, b->verdict_bits, b->status, st)
                    : p384_verify_dev(ctx, n, b->qx, b->qy, dig, true, b->r, b->s, b->verdict_bits, b->status, st);
@@ -2890,18 +2892,19 @@ int fabgpu_identity_verify_batch_p384_dev(fabgpu_ctx* ctx, const fabgpu_identity
     return rc;
 }
 
-int fabgpu_identity_verify_batch_p384(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* b) {
+static int identity_verify_batch_p384_host(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* b, bool sha3) {
     if (!ctx || !b) return FABGPU_EINVAL;
     const size_t n = b->n;
     const bool keyed = b->key_id != nullptr;
-    if (n == 0) return fabgpu_identity_verify_batch_p384_dev(ctx, b, nullptr, nullptr);
+    if (n == 0) return identity_verify_batch_p384_dev(ctx, b, nullptr, nullptr, sha3);
     const uint32_t m = (b->n_prefixes != 0 && b->pre_idx != nullptr) ? b->n_prefixes : 0;
     if (!b->off || !b->r || !b->s || !b->verdict_bits || (!keyed && (!b->qx || !b->qy)) || (m && !b->pre_off)) return FABGPU_EINVAL;
     if (n > 0x7FFFFFF0ull / 240) return FABGPU_ETOOBIG;
     const uint8_t* arena = (const uint8_t*)b->arena;
     const bool spans = (b->flags & FABGPU_IDB_SPANS) != 0;
     const bool staged = (b->flags & FABGPU_IDB_ARENA_STAGED) != 0;
-    if (b->flags & ~(uint32_t)(FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED)) return FABGPU_EINVAL;   // (FABGPU_IDB_SHA3_256: SHA-256 only)
+    if (b->flags & ~(uint32_t)(FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED)) return FABGPU_EINVAL;   // (FABGPU_IDB_SHA3_256: the family is the entry's)
+    const size_t mid_bytes = sha3 ? SHA3_MID_BYTES_HOST : 32;   // a SHA3-256 mid-state is the whole Keccak state
     // a staged arena: its slot stays locked - the stager kept out of it - until this batch has run
     fabgpu_ctx::Staged* sl = nullptr;
     std::unique_lock<std::mutex> slk;
@@ -2963,7 +2966,7 @@ int fabgpu_identity_verify_batch_p384(fabgpu_ctx* ctx, const fabgpu_identity_bat
     const size_t ib = round_up(n * 4, 64), pob = round_up((npre + 1) * 4, 64), tb = round_up((size_t)b->tail_len, 4);
     HostStage h(ctx, n, false, 48);
     const size_t dg_off = round_up(h.st_off + n, 64);      // out buffer: verdict words | status bytes | digests
-    if ((!staged && (h.rc = h.room(ctx->arena, ab))) || (h.rc = h.room(ctx->offs, noff * 4)) || (m && (h.rc = h.room(ctx->pre, pob + ib + (size_t)m * 32 + 64))) ||
+    if ((!staged && (h.rc = h.room(ctx->arena, ab))) || (h.rc = h.room(ctx->offs, noff * 4)) || (m && (h.rc = h.room(ctx->pre, pob + ib + (size_t)m * mid_bytes + 64))) ||
         (tail_used && (h.rc = h.room(ctx->tailbuf, tb + 64))))
         return h.rc;
     hipError_t err = hipSuccess;
@@ -3029,7 +3032,7 @@ int fabgpu_identity_verify_batch_p384(fabgpu_ctx* ctx, const fabgpu_identity_bat
         d.verdict_bits = dout;
         d.status = b->status ? dout + h.st_off : nullptr;
         d.digests = dout + dg_off;                         // (the rows the verify kernel reads: made here whether the caller wants them or not)
-        h.rc = fabgpu_identity_verify_batch_p384_dev(ctx, &d, m ? pd + pob + ib : nullptr, ctx->stream);
+        h.rc = identity_verify_batch_p384_dev(ctx, &d, m ? pd + pob + ib : nullptr, ctx->stream, sha3);
     }
     if (h.fetch(b->digests ? dg_off + n * 32 : (b->status ? h.st_off + n : h.words * 8))) return h.rc;
     memcpy(b->verdict_bits, ctx->out.h, h.words * 8);
@@ -3037,6 +3040,16 @@ int fabgpu_identity_verify_batch_p384(fabgpu_ctx* ctx, const fabgpu_identity_bat
     if (b->digests) memcpy(b->digests, (uint8_t*)ctx->out.h + dg_off, n * 32);
     return FABGPU_OK;
 }
+
+int fabgpu_identity_verify_batch_p384_dev(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* b, void* mid_scratch, void* stream) {
+    return identity_verify_batch_p384_dev(ctx, b, mid_scratch, stream, false);
+}
+int fabgpu_identity_verify_batch_p384(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* b) { return identity_verify_batch_p384_host(ctx, b, false); }
+// the same two for the batch of an MSP of the SHA3 hash family: SHA3-256 digest rows, 200 bytes of mid-state a prefix
+int fabgpu_identity_verify_batch_p384_sha3_dev(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* b, void* mid_scratch, void* stream) {
+    return identity_verify_batch_p384_dev(ctx, b, mid_scratch, stream, true);
+}
+int fabgpu_identity_verify_batch_p384_sha3(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* b) { return identity_verify_batch_p384_host(ctx, b, true); }
 
 }  // extern "C"
 

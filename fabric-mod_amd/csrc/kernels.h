@@ -165,6 +165,10 @@ struct P384DescribedLaunch {
     void* digests = nullptr;                 // n x 32 bytes
 };
 hipError_t launch_p384_described_digests(const P384DescribedLaunch& v, hipStream_t st);
+// ---- p384_described_sha3_kernels.hip: the same rows under SHA3-256, for the batch of an MSP of the SHA3 hash family ----
+// The same description and conditions; the mid-states (pa.mid_scratch, m x SHA3_MID_BYTES_HOST bytes, 8-byte aligned) are made by
+// launch_sha3_256_midstates on the same stream unless pa.mid_ready.
+hipError_t launch_p384_described_sha3_digests(const P384DescribedLaunch& v, hipStream_t st);
 
 // ---- idemix_kernels.hip: idemix pseudonym signatures on FP256BN ----
 // A registered issuer occupies one slot of idemix_issuer_dev_bytes() bytes in a device array; fill a host copy of the slot

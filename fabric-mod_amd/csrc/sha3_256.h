@@ -162,9 +162,11 @@ FAB_HD void sha3_fetch(const Arena& ar, int32_t w0, uint32_t blk, uint32_t (&dst
 // absorbed does not enter.  maxblk: the block count the caller loops to - the lane's own (sha3_256_blocks(la + lb)), or on the
 // device the largest of the wavefront, with `active` false for a lane that has no message; a lane past its count idles.
 // any_prefix: some lane of the wavefront has la != 0.  PREFETCH: the 35 dwords of block k + 1 are requested before block k is permuted.
-template <class Arena, bool PREFETCH>
-FAB_HD void sha3_256_stream(const Arena& ar, uint32_t (&a)[SHA3_STATE_WORDS], uint32_t sa, uint32_t la, uint32_t sb, uint32_t lb, bool active,
-                            bool any_prefix, uint32_t maxblk) {
+// sha3_256_stream2: A and B in arenas of their own - arA holds A; arB holds B, and sb is an offset into it (a lane of
+// p384_described_sha3_kernels.hip whose span lies in the tail while its prefix lies in the block).
+template <class ArenaA, class ArenaB, bool PREFETCH>
+FAB_HD void sha3_256_stream2(const ArenaA arA, const ArenaB ar, uint32_t (&a)[SHA3_STATE_WORDS], uint32_t sa, uint32_t la, uint32_t sb, uint32_t lb,
+                             bool active, bool any_prefix, uint32_t maxblk) {
     const uint32_t len = la + lb;
     const uint32_t nblk = active ? sha3_256_blocks(len) : 0;
     // B's bytes sit at stream position la: the B stream starts at arena byte sb - la, whose dword is floor((sb - la) / 4)
@@ -185,7 +187,7 @@ FAB_HD void sha3_256_stream(const Arena& ar, uint32_t (&a)[SHA3_STATE_WORDS], ui
         for (int k = 0; k < SHA3_256_RATE_WORDS; k++) w[k] = k_bytes(raw[k + 1], raw[k], shift);
         if (any_prefix && blk == 0) {                    // uniform: the prefix tail A takes the first la bytes of the first block
             uint32_t rawA[SHA3_256_RATE_WORDS + 1];
-            sha3_fetch(ar, (int32_t)(sa >> 2), 0, rawA);
+            sha3_fetch(arA, (int32_t)(sa >> 2), 0, rawA);
 #pragma unroll
             for (int k = 0; k < SHA3_256_RATE_WORDS; k++) {
                 const uint32_t keepA = k_low_bytes((int32_t)la - 4 * k);
@@ -203,6 +205,12 @@ FAB_HD void sha3_256_stream(const Arena& ar, uint32_t (&a)[SHA3_STATE_WORDS], ui
         if (blk + 1 == nblk) w[SHA3_256_RATE_WORDS - 1] ^= 0x80000000u;   // the lane's last block: byte 135
         if (blk < nblk) sha3_256_absorb(a, w);
     }
+}
+
+template <class Arena, bool PREFETCH>
+FAB_HD void sha3_256_stream(const Arena& ar, uint32_t (&a)[SHA3_STATE_WORDS], uint32_t sa, uint32_t la, uint32_t sb, uint32_t lb, bool active,
+                            bool any_prefix, uint32_t maxblk) {
+    sha3_256_stream2<Arena, Arena, PREFETCH>(ar, ar, a, sa, la, sb, lb, active, any_prefix, maxblk);
 }
 
 // the whole blocks of a prefix arena[start, start + len): nfull = len / 136 of them, looped to maxfull

@@ -120,7 +120,7 @@ class _Cfg(ctypes.Structure):
 # what fabgpu_p256_key_table_stats reports, in order
 KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "live_16bit", "bytes_held", "slots_used")
 # ... fabgpu_csp_p384_pass_stats
-P384_PASS_STATS = ("stages", "seen", "submitted", "keyed_launches", "fresh_launches", "audited", "memo_seeded")
+P384_PASS_STATS = ("stages", "seen", "submitted", "keyed_launches", "fresh_launches", "audited", "memo_seeded", "sha3_rows")
 # ... and fabgpu_p384_key_table_stats
 P384_KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "keyed_launches", "bytes_held", "slots_used")
 P384_COMB_WORDS = 48 * 256 * 24      # one P-384 comb table (csrc/p384_tables.h CombTab384): 1.125 MiB
@@ -163,7 +163,8 @@ ABI_SYMBOLS = [
     "fabgpu_p384_key_table_stats", "fabgpu_p384_verify_batch_keyed", "fabgpu_p384_verify_batch_keyed_dev",
     "fabgpu_sha256_p384_verify_batch_keyed", "fabgpu_sha256_p384_verify_batch_keyed_dev",
     "fabgpu_sha3_256_p384_verify_batch_keyed", "fabgpu_sha3_256_p384_verify_batch_keyed_dev", "fabgpu_csp_key_import_p384",
-    "fabgpu_identity_verify_batch_p384", "fabgpu_identity_verify_batch_p384_dev", "fabgpu_identity_to_p384", "fabgpu_csp_p384_pass_stats",
+    "fabgpu_identity_verify_batch_p384", "fabgpu_identity_verify_batch_p384_dev", "fabgpu_identity_verify_batch_p384_sha3",
+    "fabgpu_identity_verify_batch_p384_sha3_dev", "fabgpu_identity_to_p384", "fabgpu_csp_p384_pass_stats", "fabgpu_csp_msp_hash_family", "fabgpu_csp_msp_hash_family_get",
     "fabgpu_csp_memo_lookup_p384", "fabgpu_csp_memo_stats_p384", "fabgpu_csp_memo_set_capacity_p384",
 ]
 
@@ -329,8 +330,12 @@ def load():
     L.fabgpu_identity_verify_batch_dev.argtypes = [_vp, ctypes.POINTER(_IdBatch), _vp, _vp]
     L.fabgpu_identity_verify_batch_p384.argtypes = [_vp, ctypes.POINTER(_IdBatchP384)]
     L.fabgpu_identity_verify_batch_p384_dev.argtypes = [_vp, ctypes.POINTER(_IdBatchP384), _vp, _vp]
+    L.fabgpu_identity_verify_batch_p384_sha3.argtypes = [_vp, ctypes.POINTER(_IdBatchP384)]
+    L.fabgpu_identity_verify_batch_p384_sha3_dev.argtypes = [_vp, ctypes.POINTER(_IdBatchP384), _vp, _vp]
     L.fabgpu_identity_to_p384.argtypes = [ctypes.c_char_p, _sz, ctypes.c_char_p]
     L.fabgpu_csp_p384_pass_stats.argtypes = [_vp, _u64p, ctypes.c_int]
+    L.fabgpu_csp_msp_hash_family.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+    L.fabgpu_csp_msp_hash_family_get.argtypes = [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
     L.fabgpu_idemix_issuer_register.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _u32p]
     L.fabgpu_idemix_issuer_count.argtypes = [_vp]
     L.fabgpu_idemix_nym_verify_batch.argtypes = [_vp, _sz, _u8p, _u32p, _u32p, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, _u64p, _u8p]
@@ -862,9 +867,10 @@ class Context:
                "fabgpu_identity_verify_batch_dev")
 
     def identity_verify_batch_p384(self, arena, off, r, s, qx=None, qy=None, key_id=None, pre_off=None, pre_idx=None, want_status=True, spans=False,
-                                   stage_token=0, want_digests=False, tail=None, tail_base=0, flags=0):
+                                   stage_token=0, want_digests=False, tail=None, tail_base=0, flags=0, sha3=False):
         """fabgpu_identity_verify_batch_p384: the described batch for P-384 identities (48-byte fields, SHA-256 messages); arguments as
-        identity_verify_batch.  Returns (verdicts, statuses[, digests n x 32])."""
+        identity_verify_batch.  sha3: fabgpu_identity_verify_batch_p384_sha3 instead - messages, prefixes and the returned digests under
+        SHA3-256 (the batch of an MSP of the SHA3 family).  Returns (verdicts, statuses[, digests n x 32])."""
         r, s = _a8(r), _a8(s)
         arena = _a8(arena) if arena is not None else None
         off = np.ascontiguousarray(off, dtype=np.uint32)
@@ -897,12 +903,19 @@ class Context:
             tail = _a8(tail)
             keep.append(tail)
             b.tail, b.tail_base, b.tail_len = tail.ctypes.data, tail_base, tail.size
-        _check(self._L.fabgpu_identity_verify_batch_p384(self._h, ctypes.byref(b)), "fabgpu_identity_verify_batch_p384")
+        if sha3:
+            _check(self._L.fabgpu_identity_verify_batch_p384_sha3(self._h, ctypes.byref(b)), "fabgpu_identity_verify_batch_p384_sha3")
+        else:
+            _check(self._L.fabgpu_identity_verify_batch_p384(self._h, ctypes.byref(b)), "fabgpu_identity_verify_batch_p384")
         return (unpack_bits(bits, n), st) + ((mdig,) if mdig is not None else ())
 
     def identity_verify_batch_p384_dev(self, desc: "_IdBatchP384", mid_scratch, stream=0):
         _check(self._L.fabgpu_identity_verify_batch_p384_dev(self._h, ctypes.byref(desc), mid_scratch or None, stream or None),
                "fabgpu_identity_verify_batch_p384_dev")
+
+    def identity_verify_batch_p384_sha3_dev(self, desc: "_IdBatchP384", mid_scratch, stream=0):
+        _check(self._L.fabgpu_identity_verify_batch_p384_sha3_dev(self._h, ctypes.byref(desc), mid_scratch or None, stream or None),
+               "fabgpu_identity_verify_batch_p384_sha3_dev")
 
     def p256_verify_batch_keyed_dev(self, n, key_id, e, r, s, verdict_bits, status, stream=0):
         _check(self._L.fabgpu_p256_verify_batch_keyed_dev(self._h, n, key_id, e, r, s, verdict_bits, status or None, stream or None),
@@ -1210,6 +1223,21 @@ class GPUCSP:
         if n != len(P384_PASS_STATS):
             raise FabgpuError("fabgpu_csp_p384_pass_stats: %s" % strerror(n))
         return dict(zip(P384_PASS_STATS, (int(x) for x in v)))
+
+    def msp_hash_family(self, mspid: str, family: str) -> None:
+        """fabgpu_csp_msp_hash_family: the hash family ("SHA2" / "SHA3") the block pass hashes this MSP's P-384 tuples with, for the passes
+        that start after the call.  A family the provider refuses raises BCCSPError with identity.getHashOpt's text."""
+        err = ctypes.create_string_buffer(256)
+        rc = self._L.fabgpu_csp_msp_hash_family(self._h, mspid.encode(), family.encode() if family is not None else None, err, 256)
+        if rc == 1:
+            raise BCCSPError(err.value.decode())
+        _check(rc, "fabgpu_csp_msp_hash_family")
+
+    def msp_hash_family_get(self, mspid: str) -> str:
+        """fabgpu_csp_msp_hash_family_get: "SHA3" for an MSP set so, "SHA2" otherwise (every MSP until it is set)."""
+        v = ctypes.c_int(0)
+        _check(self._L.fabgpu_csp_msp_hash_family_get(self._h, mspid.encode(), ctypes.byref(v)), "fabgpu_csp_msp_hash_family_get")
+        return "SHA3" if v.value else "SHA2"
 
     def key_import_p384(self, key: Tuple[int, int]) -> Tuple[bool, str]:
         """BCCSP.KeyImport for a P-384 key (fabgpu_csp_key_import_p384): (on the curve, the error text or "")."""

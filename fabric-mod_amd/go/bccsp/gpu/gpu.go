@@ -715,6 +715,31 @@ func (p *Provider) RegisterIdemixMSP(channelID, mspID string, ipkBytes []byte) b
 	return rc == 0 && id >= 0
 }
 
+// SetMSPHashFamily tells the block pass the hash family of an MSP: family is the MSP config's
+// CryptoConfig.SignatureHashFamily ("SHA2", "SHA3"; msp/mspimplsetup.go:81-101 reads it, identity.getHashOpt uses it).  The P-384
+// creators and endorsers of an MSP set "SHA3" are then hashed with SHA3-256 by the pass (options P384 and SHA3 both on); every MSP is
+// SHA2 until set.  A change holds for the passes that start after the call.  The error is getHashOpt's for an unknown family, and says
+// that bccsp/sw serves SHA3 while the SHA3 option is off: the MSP's signatures are then decided by bccsp/sw, as before.
+func (p *Provider) SetMSPHashFamily(mspID, family string) error {
+	cm := C.CString(mspID)
+	defer C.free(unsafe.Pointer(cm))
+	cf := C.CString(family)
+	defer C.free(unsafe.Pointer(cf))
+	text := make([]byte, 256)
+	rc := C.fabgpu_csp_msp_hash_family(p.csp, cm, cf, (*C.char)(unsafe.Pointer(&text[0])), C.size_t(len(text)))
+	if rc == 0 {
+		return nil
+	}
+	if rc < 0 {
+		return errors.Errorf("fabgpu_csp_msp_hash_family: %s", C.GoString(C.fabgpu_strerror(rc)))
+	}
+	n := 0
+	for n < len(text) && text[n] != 0 {
+		n++
+	}
+	return errors.New(string(text[:n]))
+}
+
 // PassRoutes: how the block passes of this provider went - walked on the device (DESIGN 4.4b) or on the host - and why the last
 // block was declined by the device walk (not staged, idemix MSPs registered, a certificate beyond the device decoder).  For metrics.
 func (p *Provider) PassRoutes() (deviceWalks, hostWalks uint64, lastDecline string) {

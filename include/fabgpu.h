@@ -181,8 +181,9 @@ int fabgpu_sha256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const v
  * arithmetic does not depend on the family: a SHA3-256 digest is 32 bytes, e is the digest itself.  Hash and verify are two launches on
  * one stream - the digests go through a context-owned device buffer into the verify-only kernels, which are chosen by n and the
  * context's flags as for fabgpu_p256_verify_batch(_keyed); no digest leaves the chip.  One message per lane at every size (there is
- * no several-lanes-per-message form for small launches).  Not served: fabgpu_multi_*, and the block pass (fabgpu_bccsp.h), which
- * hashes every signed message with SHA-256. */
+ * no several-lanes-per-message form for small launches).  Not served: fabgpu_multi_*, and the P-256 tuples of the block pass
+ * (fabgpu_bccsp.h), whose routes hash every signed message with SHA-256; its P-384 stage hashes the tuples of an MSP set SHA3
+ * (fabgpu_csp_msp_hash_family) with SHA3-256, through fabgpu_identity_verify_batch_p384_sha3. */
 int fabgpu_sha3_256_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, uint8_t* digests);
 int fabgpu_sha3_256_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, void* stream);
 int fabgpu_sha3_256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx,
@@ -356,8 +357,10 @@ int fabgpu_identity_verify_batch_dev(fabgpu_ctx* ctx, const fabgpu_identity_batc
  * of fabgpu_p384_key_register) behind it on the same stream.  qx, qy, r, s are n x 48 bytes; verdict words and statuses 0-4 are those of
  * fabgpu_p384_verify_batch on (key, SHA-256 of the concatenated message as a 256-bit e, r, s), in its precedence.  `digests`
  * (optional, n x 32 bytes): the SHA-256 of every message as it was verified.
- * flags: FABGPU_IDB_SPANS, and FABGPU_IDB_ARENA_STAGED in the host variant.  FABGPU_IDB_SHA3_256 answers FABGPU_EINVAL HERE: this entry
- * hashes with SHA-256 only (a SHA3 MSP's P-384 identities stay with bccsp/sw in the pass).  There is no gather part and no pseudonym part.
+ * flags: FABGPU_IDB_SPANS, and FABGPU_IDB_ARENA_STAGED in the host variant.  FABGPU_IDB_SHA3_256 answers FABGPU_EINVAL HERE, as it always
+ * did: these two entries hash with SHA-256 only, and a caller's mid_scratch of 32 bytes a prefix is never written as if it were larger.
+ * The batch of an MSP of the SHA3 family has entries of its own, fabgpu_identity_verify_batch_p384_sha3(_dev) below - the P-384 stage of
+ * the block pass takes them for the tuples of an MSP set SHA3.  There is no gather part and no pseudonym part.
  * A malformed description answers what fabgpu_identity_verify_batch answers for the same defect (a reversed span, a span that straddles
  * tail_base or leaves the tail, a tail without FABGPU_IDB_SPANS or with a tail_base that is no multiple of 64, a stale stage_token:
  * FABGPU_EINVAL).  n = 0 is the warm call of the form the batch names (fresh: the generator's table; key_id != NULL: the generator's
@@ -391,6 +394,14 @@ typedef struct fabgpu_identity_batch_p384 {
 } fabgpu_identity_batch_p384;
 int fabgpu_identity_verify_batch_p384(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* batch);
 int fabgpu_identity_verify_batch_p384_dev(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* batch, void* mid_scratch, void* stream);
+/* The same two for the batch of an MSP whose SignatureHashFamily is SHA3: the same description, the same flags (FABGPU_IDB_SHA3_256 is
+ * no flag of theirs either: the family is the entry's), the same answers to a malformed description and the same warm call.  Messages
+ * and prefixes are hashed with SHA3-256 (p384_described_sha3_kernels.hip; the whole 136-byte blocks of a prefix once, by the mid-state
+ * launch fabgpu_identity_verify_batch uses under FABGPU_IDB_SHA3_256), `digests`, if asked for, are SHA3-256, and verdict words and
+ * statuses 0-4 are those of fabgpu_p384_verify_batch on (key, SHA3-256 of the concatenated message as a 256-bit e, r, s).  _dev:
+ * mid_scratch = n_prefixes x 200 bytes, 8-byte aligned (FABGPU_EINVAL otherwise) - a SHA3-256 mid-state is the whole Keccak state. */
+int fabgpu_identity_verify_batch_p384_sha3(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* batch);
+int fabgpu_identity_verify_batch_p384_sha3_dev(fabgpu_ctx* ctx, const fabgpu_identity_batch_p384* batch, void* mid_scratch, void* stream);
 
 /* ---- idemix pseudonym signatures on FP256BN (BASELINE config 5) ----
  * NymSignature.Ver (idemix/nymsignature.go:74-109), reached per CREATOR signature from msp/idemixmsp.go:584-599 through

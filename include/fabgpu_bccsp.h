@@ -74,9 +74,11 @@ int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pa
  * "hash_sha3" (default off; > 0 on): the provider serves the SHA3 hash family on the device - fabgpu_csp_hash answers "SHA3_256"
  * (bccsp.SHA3_256Opts) through fabgpu_sha3_256_batch, and fabgpu_csp_identity_verify_batch2 / _coalesced2 take hash family "SHA3",
  * what identity.Verify selects for an MSP whose SignatureHashFamily is SHA3 (msp/identities.go:216-224).  Off, every answer is what it
- * was: "Unsupported 'HashOpt' provided [SHA3_256]", and family "SHA3" answers that bccsp/sw serves it.  NOT served either way: the
- * block pass (it hashes every signed message with SHA-256, so a SHA3 MSP's signatures come back "not valid" from it and their
- * validators' SHA3-256 digests can only miss the verdict memo, never hit a SHA-256 verdict) and the digest memo (SHA-256 only).
+ * was: "Unsupported 'HashOpt' provided [SHA3_256]", and family "SHA3" answers that bccsp/sw serves it.  The block pass serves the
+ * P-384 tuples of an MSP set SHA3 with fabgpu_csp_msp_hash_family (below; options hash_sha3 and p384 both on).  NOT served either way:
+ * the P-256 tuples of a SHA3 MSP in the block pass (the routes hash every P-256 message with SHA-256, so such signatures come back "not
+ * valid" from it and their validators' SHA3-256 digests can only miss the verdict memo, never hit a SHA-256 verdict) and the digest
+ * memo (SHA-256 only).
  * "p384" (default off; > 0 on): the *_p384 calls below verify ECDSA P-384 identities on the device.  Off, each of them answers, per item,
  * "P-384 is served by bccsp/sw, not by the GPU provider" (the identity call behind identity.Verify's "could not determine the validity of
  * the signature: ") and launches nothing; fabgpu_csp_key_import_p384 answers the same text and registers nothing.  With the option on the
@@ -319,7 +321,8 @@ int fabgpu_csp_memo_set_capacity(fabgpu_csp* csp, uint64_t max_entries);
  * first while it is over; fabgpu_csp_memo_set_capacity does not touch it), and fabgpu_csp_memo_stats stays about the P-256 table:
  * fabgpu_csp_memo_stats_p384 reports this one (any pointer may be NULL).
  * NOT served: bccsp.Hash for these messages (tuple_hashed stays 0, fabgpu_csp_hash_lookup keeps missing: the validators hash them on the
- * CPU, and that SHA-256 is the digest the entries are keyed on), SHA3 MSPs, fabgpu_multi_*.  The layout of the pass's outputs does not
+ * CPU; the digest the entries are keyed on is that hash - SHA3-256 for the tuples of an MSP set SHA3, fabgpu_csp_msp_hash_family),
+ * fabgpu_multi_*.  The layout of the pass's outputs does not
  * change: tuple_qxy and tuple_digest stay zero for these tuples - they are framed for 32-byte coordinates. */
 int fabgpu_csp_memo_lookup_p384(fabgpu_csp* csp, const uint8_t* qx48, const uint8_t* qy48, const uint8_t* sig, size_t siglen, const uint8_t* digest,
                                 size_t dlen, uint8_t* status, uint64_t* block_seq);
@@ -356,11 +359,25 @@ int fabgpu_identity_to_p384(const uint8_t* ident, size_t len, uint8_t* qxy96);
  * the flags of their transactions folded again.  out[0 .. min(cap, 7)): [0] passes that ran the stage, [1] P-384 tuples seen,
  * [2] tuples submitted to the device, [3] keyed launches, [4] fresh-key launches, [5] tuples the CPU audit recomputed (audit_permille;
  * a disagreement poisons the provider and the pass answers FABGPU_EPOISONED), [6] entries seeded into the P-384 verdict memo
- * (FABGPU_PASS_SEED_MEMO; fabgpu_csp_memo_lookup_p384 above; fabgpu_block_pass.memo_seeded includes them).  Returns how many values
- * there are (7); a caller that passes the old capacity of 6 still gets the first six.
+ * (FABGPU_PASS_SEED_MEMO; fabgpu_csp_memo_lookup_p384 above; fabgpu_block_pass.memo_seeded includes them), [7] tuples submitted under
+ * SHA3-256 (a part of [2]).  Returns how many values there are (8); a caller that passes an older capacity of 6 or 7 still gets the
+ * values it always got.
+ * Hash family: the tuples of an MSP set SHA3 (fabgpu_csp_msp_hash_family) go out in a described batch of their own through
+ * fabgpu_identity_verify_batch_p384_sha3, after the SHA2 tuples' batch over the same staged block - at most two batches a block, each keyed or fresh on
+ * its own keys ([3] and [4] count batches); the audit hashes them with SHA3-256 and their memo entries carry the SHA3-256 digest, the
+ * one the validator's bccsp.Verify presents.  A block without such a tuple launches what it always launched.
  * NOT in the stage: digest memo entries for P-384 tuples (tuple_hashed = 0, tuple_qxy and tuple_digest zero; bccsp.Hash of their
- * messages stays on the CPU), SHA3 MSPs, fabgpu_multi_*, P-384 keys earning a table by hit count. */
+ * messages stays on the CPU), the P-256 tuples of a SHA3 MSP (hashed with SHA-256 by the routes, answered "not valid", decided in
+ * bccsp/sw), fabgpu_multi_*, P-384 keys earning a table by hit count. */
 int fabgpu_csp_p384_pass_stats(fabgpu_csp* csp, uint64_t* out, int cap);
+/* The hash family of an MSP, as the block pass knows it: what the MSP's setup read from its config's SignatureHashFamily
+ * (msp/identities.go:216-224).  family: "SHA2" or "SHA3"; anything else answers 1 with identity.getHashOpt's text in err ("hash familiy
+ * not recognized [..]"), and "SHA3" while the hash_sha3 option is off answers 1 with the text that bccsp/sw serves it; an empty mspid or
+ * one longer than 1024 bytes answers 1 with "invalid mspid".  0: set (err = "").  Every MSP is SHA2 until set otherwise.  A change holds
+ * for the passes that start after the call returns; an MSP set SHA3 counts as SHA3 only while hash_sha3 is on.  Only the P-384 stage
+ * reads it.  _get: *sha3 = 1 for an MSP set SHA3, 0 otherwise (also for an MSP nobody has set). */
+int fabgpu_csp_msp_hash_family(fabgpu_csp* csp, const char* mspid, const char* family, char* err, size_t errcap);
+int fabgpu_csp_msp_hash_family_get(fabgpu_csp* csp, const char* mspid, int* sha3);
 
 /* (An x509 chain-link batch - crypto/x509 CheckSignatureFrom for n certificates - was an entry point of rounds 2-4 WITHOUT a consumer:
  * the only caller on this path is crypto/x509's own Verify (msp/mspimpl.go:721-739), which offers no hook for a pre-computed verdict, and

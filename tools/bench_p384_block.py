@@ -7,7 +7,13 @@
     Python integers, tests/p384_ref.py) laid out over the 1 000 - the kernels' control flow does not depend on the operands.
 (b) The 10 000-transaction all-P-256 block of the bench (tests/blockgen.py, as bench.py builds it) through ONE provider, option on
     against off, rounds interleaved (who goes first alternates): the option-on median against the option-off rounds' own spread, and the stage's counters (no launch).
-Passes are the lean form a memo-less caller asks for (tx_flags only), after a clock warm-up."""
+Passes are the lean form a memo-less caller asks for (tx_flags only), after a clock warm-up.
+
+--sha3: another measurement instead, written to profiles/p384_block_pass_sha3.json.  The 1 000-transaction block with a P-384 creator
+    of a SHA2 MSP and three P-384 endorsers of an MSP of the SHA3 family (signatures over SHA3-256): the pass with that MSP registered
+    SHA3 (fabgpu_csp_msp_hash_family: two described batches, 1 000 rows under SHA-256 and 3 000 under SHA3-256) against the same block
+    with the MSP left SHA2 (one batch of 4 000 rows under SHA-256, the endorsements "not valid"), one provider, rounds interleaved (who
+    goes first alternates), on the fresh-key kernel and then on the keyed one."""
 import hashlib
 import json
 import os
@@ -76,6 +82,53 @@ def cpu_verify_seconds(tuples):
         t.join()
     return time.perf_counter() - t0, sum(n_ok)
 
+
+def sha3_mode():
+    import p384_sha3_blocks as pb3
+    rnd = random.Random(384103)
+    creators = [pb3.Signer(rnd, "client%d.org1.example.com" % i, "Org1MSP", sha3=False) for i in range(2)]
+    endorsers = [pb3.Signer(rnd, "peer%d.org3.example.com" % i, "Org3MSP", sha3=True) for i in range(4)]
+    distinct = [pb.endorser_tx(rnd, creators[t % 2], rnd.sample(endorsers, 3), ext_bytes=990) for t in range(16)]
+    blk = bb.block(1, [distinct[t % 16][0] for t in range(N_TX)])
+    csp = fabgpu.GPUCSP(devices=[0], p384=1, hash_sha3=1)
+    want = {"SHA3": fabgpu.TX_ALL_SIGNATURES_VALID, "SHA2": fabgpu.TX_BAD_ENDORSEMENT}
+    res = {"rounds": ROUNDS, "tx": N_TX, "p384_tuples": 4 * N_TX, "sha3_tuples": 3 * N_TX, "block_bytes": len(blk)}
+    for kernel in ("fresh", "keyed"):
+        if kernel == "keyed":
+            for sg in creators + endorsers:
+                csp.key_import_p384(sg.q)
+        for fam in ("SHA3", "SHA2"):                                # every path once, checked in full
+            csp.msp_hash_family("Org3MSP", fam)
+            first = fabgpu.preverify_block2(csp, blk, block_seq=1)
+            assert (first["tx_flags"] == want[fam]).all() and len(first["tuple_status"]) == 4 * N_TX
+        t_end = time.time() + 2.0
+        while time.time() < t_end:
+            timed(csp, blk, 2)
+        per = {"SHA3": [], "SHA2": []}
+        s0 = csp.p384_pass_stats()
+        for i in range(2 * ROUNDS):
+            for fam in (("SHA2", "SHA3") if i % 2 == 0 else ("SHA3", "SHA2")):     # (who goes first alternates)
+                csp.msp_hash_family("Org3MSP", fam)
+                ms, o = timed(csp, blk, 10 + i)
+                assert (o["tx_flags"] == want[fam]).all()
+                per[fam].append(ms)
+        s1 = csp.p384_pass_stats()
+        launches = s1[kernel + "_launches"] - s0[kernel + "_launches"]
+        assert launches == 2 * ROUNDS * 3 and s1["sha3_rows"] - s0["sha3_rows"] == 2 * ROUNDS * 3 * N_TX       # two batches a SHA3 pass, one a SHA2 pass
+        res[kernel] = {"msp_sha3_two_batches": summary(per["SHA3"]), "msp_left_sha2_one_batch": summary(per["SHA2"]),
+                       "sha3_minus_sha2_median_ms": statistics.median(per["SHA3"]) - statistics.median(per["SHA2"])}
+    res["stage_stats"] = csp.p384_pass_stats()
+    csp.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "p384_block_pass_sha3.json"), "w") as fh:
+        json.dump(res, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
+if "--sha3" in sys.argv[1:]:
+    sha3_mode()
+    sys.exit(0)
 
 out = {"rounds": ROUNDS}
 # ---- (a) the P-384 block ----
