@@ -40,6 +40,7 @@ def s64(x):
 
 CONSTS = {"c9": 512, "c18": 262144, "cm21": -2097152, "c24": 16777216, "c28": 268435456}
 RED = [(3, "c9"), (6, "c18"), (7, "cm21"), (8, "c24")]
+EXEC_LANES = {"all": (True, True), "even": (True, False), "odd": (False, True)}     # Program.exec_: which lanes of a pair execute
 
 
 class GenericField:
@@ -118,6 +119,13 @@ class Program:
 
     def lane_const(self, d, odd, even):       # one register: lane is odd ? odd : even  (inline constants)
         self.ins.append(("sel", d, odd, even))
+
+    def exec_(self, lanes):
+        """(round 8) From here on only the "even" or the "odd" lanes of every pair execute - "all" ends it.  A limb-wise operation under
+        such a mask writes its result on one lane and leaves the partner's register as it is: the select that would have merged the two
+        is not needed.  DPP reads and field products run under "all" only (a DPP read of a disabled lane returns nothing)."""
+        assert lanes in ("all", "even", "odd")
+        self.ins.append(("exec", lanes))
 
     def swp_sub(self, d, a, b):               # d = partner's a - own b
         for i in range(9):
@@ -209,6 +217,7 @@ class Program:
         """regs_*: dict "fe.i" -> int (io / in registers must be present).  Executes on the lane pair, returns the dicts."""
         L = [dict(regs_even), dict(regs_odd)]
         acc = [0, 0]
+        active = (True, True)
 
         def val(lane, x):
             if isinstance(x, int):
@@ -219,13 +228,19 @@ class Program:
         for ins in self.ins:
             op = ins[0]
             if op in ("prod_begin", "prod_end"):
+                assert active == (True, True), "a field product under a lane mask"
+                continue
+            if op == "exec":
+                active = EXEC_LANES[ins[1]]
                 continue
             if op == "bc_mov":
+                assert active == (True, True), "a DPP read under a lane mask"
                 v = val(ins[3], ins[2])
                 for lane in (0, 1):
                     L[lane][ins[1]] = v
                 continue
             if op in ("swp_mov", "swp_sub", "swp_add"):
+                assert active == (True, True), "a DPP read under a lane mask"
                 new = []
                 for lane in (0, 1):
                     p = val(1 - lane, ins[2])
@@ -240,6 +255,8 @@ class Program:
                     L[lane][ins[1]] = new[lane]
                 continue
             for lane in (0, 1):
+                if not active[lane]:
+                    continue
                 R = L[lane]
                 if op == "add":
                     R[ins[1]] = s32(val(lane, ins[2]) + val(lane, ins[3]))
@@ -288,6 +305,7 @@ class Program:
         Returns the dicts of output ranges."""
         L = [dict(regs_even), dict(regs_odd)]
         acc = [None, None]
+        active = (True, True)
         I32 = (-(1 << 31), (1 << 31) - 1)
         I64 = (-(1 << 63), (1 << 63) - 1)
 
@@ -323,8 +341,14 @@ class Program:
         for n, ins in enumerate(self.ins):
             op = ins[0]
             if op in ("prod_begin", "prod_end"):
+                assert active == (True, True), "a field product under a lane mask"
+                continue
+            if op == "exec":
+                active = EXEC_LANES[ins[1]]
                 continue
             what = "%s #%d -> %s" % (op, n, ins[1])
+            if op in ("bc_mov", "swp_mov", "swp_sub", "swp_add"):
+                assert active == (True, True), "a DPP read under a lane mask"
             if op == "bc_mov":
                 v = val(ins[3], ins[2])
                 for lane in (0, 1):
@@ -340,6 +364,8 @@ class Program:
                     L[lane][ins[1]] = new[lane]
                 continue
             for lane in (0, 1):
+                if not active[lane]:
+                    continue
                 R = L[lane]
                 if op in ("add", "addc"):
                     R[ins[1]] = fit(add(val(lane, ins[2]), val(lane, ins[3])), I32, what)
@@ -501,6 +527,11 @@ class Program:
                 for i in range(9):
                     num[f"{name}.{i}"] = len(outs)
                     outs.append('"%sv"((%s).v[%d])' % ("+" if self.fes[name] == "io" else "=&", macro_args[name], i))
+        uses_exec = any(x[0] == "exec" for x in self.ins)
+        if uses_exec:       # the wave's own EXEC, and its even / odd lanes: three scalar pairs that live for this statement only
+            for lanes in ("all", "even", "odd"):
+                num["x_" + lanes] = len(outs)
+                outs.append('"=&s"(pair_exec_%s)' % lanes)
         for name in self.order:
             if self.fes[name] == "in":
                 for i in range(9):
@@ -525,24 +556,53 @@ class Program:
         last_write = {}
         nops = 0
         count = 0
+        half = 0           # scalar instructions are 4 bytes: how many of them since the stream was last on an 8-byte boundary (mod 2)
+        scalar = 0         # EXEC switches and their pads
+
+        def put_scalar(text):
+            nonlocal count, half, scalar
+            lines.append(text)
+            count += 1
+            scalar += 1
+            half ^= 1
+
+        def realign():     # a long run of 8-byte instructions follows: it must not start at 4 mod 8 (ALIGN_NOTE of gen_pair_gcn.py)
+            if half:
+                put_scalar("s_nop 0")
 
         def put(text, writes=None, dpp_src=None):
-            nonlocal nops, count
+            nonlocal nops, count, half
             if dpp_src is not None and dpp_src in last_write:
                 between = count - last_write[dpp_src] - 1
                 if between < 2:
                     lines.append("s_nop %d" % (2 - between - 1))
+                    half ^= 1
                     nops += 1
                     count += 1
             lines.append(text)
             if writes is not None:
                 last_write[writes] = count
             count += 1
+        # EXEC is rewritten INSIDE the statement and is the wave's own again at its end (every exec_ sequence of a program ends with "all";
+        # the compiler is told of SCC only).  Hazards: a scalar write of EXEC needs no wait states before a vector instruction, DPP
+        # included - the 5-state "EXEC write -> DPP" rule of the gfx9 family is about VALU writes of EXEC (v_cmpx, v_readlane targets),
+        # which these programs never make.  That is an assumption about gfx950 taken from the ISA's hazard table, and it is what the
+        # register-for-register GPU test of the generated statement checks in practice (tests/test_pair_dbl4.py).
+        if uses_exec:
+            assert [x[1] for x in self.ins if x[0] == "exec"][-1] == "all", "%s would leave the wave with a lane mask" % self.name
+            put_scalar("s_mov_b64 %s, exec" % o("x_all"))
+            put_scalar("s_andn2_b64 %s, exec, %s" % (o("x_even"), o("mask")))
+            put_scalar("s_and_b64 %s, exec, %s" % (o("x_odd"), o("mask")))
+            realign()
         for ins in self.ins:
             op = ins[0]
             if op in ("prod_begin", "prod_end"):
+                if uses_exec:
+                    realign()
                 continue
-            if op == "add" or op == "addc":
+            if op == "exec":
+                put_scalar("s_mov_b64 exec, %s" % o("x_" + ins[1]))
+            elif op == "add" or op == "addc":
                 put("v_add_u32_e64 %s, %s, %s" % (o(ins[1]), o(ins[2]), o(ins[3])), ins[1])
             elif op == "sub":
                 put("v_sub_u32_e64 %s, %s, %s" % (o(ins[1]), o(ins[2]), o(ins[3])), ins[1])
@@ -584,14 +644,26 @@ class Program:
             else:
                 raise ValueError(op)
         args = ", ".join(macro_args[n].strip("()") for n in self.order)
-        text = ["// %s: %d instructions (%d v_mad_i64_i32, %d hazard s_nop)" % (
-            self.name, len(lines), sum(l.startswith("v_mad") for l in lines), nops)]
-        text.append("#define %s(%s) \\" % (self.name, args))
+        if uses_exec:
+            realign()
+            text = ["// %s: %d instructions (%d v_mad_i64_i32, %d hazard s_nop, %d scalar: EXEC switches and their alignment pads)" % (
+                self.name, len(lines), sum(l.startswith("v_mad") for l in lines), nops, scalar)]
+            text.append("#define %s(%s) \\" % (self.name, args))
+            text.append("    do { \\")
+            text.append("    uint64_t pair_exec_all, pair_exec_even, pair_exec_odd; \\")
+        else:
+            text = ["// %s: %d instructions (%d v_mad_i64_i32, %d hazard s_nop)" % (
+                self.name, len(lines), sum(l.startswith("v_mad") for l in lines), nops)]
+            text.append("#define %s(%s) \\" % (self.name, args))
         text.append("    asm( \\")
         text.append("        FE29_GCN_ALIGN \\")
         for l in lines:
             text.append('        "%s\\n\\t" \\' % l)
         text.append("        : %s \\" % ", ".join(outs))
         text.append("        : %s \\" % ", ".join(ins_))
-        text.append('        : "v0", "v1", "vcc")')
-        return "\n".join(text) + "\n", {"instructions": len(lines), "nops": nops}
+        if uses_exec:
+            text.append('        : "v0", "v1", "vcc", "scc"); \\')
+            text.append("    } while (0)")
+        else:
+            text.append('        : "v0", "v1", "vcc")')
+        return "\n".join(text) + "\n", {"instructions": len(lines), "nops": nops, "scalar": scalar}

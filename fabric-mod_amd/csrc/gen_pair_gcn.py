@@ -71,6 +71,135 @@ def build_pair_dbl(uns=UNSIGNED_DBL):
     return p
 
 
+# ---- round 8: N consecutive doublings as ONE program (PAIR29_DBL4: the four doublings of a 4-bit window) ------------------------------
+# Each doubling is the formulas of build_pair_dbl with three differences, none of which PAIR29_DBL itself may take (its users pin it):
+#   * lane-specific operands are WRITTEN under a lane mask (Program.exec_) instead of computed on both lanes and merged by a select:
+#     E's 4X goes into the register that holds O's X - delta, O's X + delta = 2 delta + (X - delta) into the one that holds E's gamma ...
+#     - five selects fewer per doubling (45 instructions), for eight EXEC switches and two 4-byte pads that
+#     keep the products on 8-byte boundaries (scalar instructions; a run of nine 8-byte instructions between two switches is left at
+#     4 mod 8 - padding it would cost more than the misalignment);
+#   * its Y3 / Z3 product writes the register the NEXT doubling reads as B (B and BB alternate; N is even, so the result ends in B);
+#   * per doubling, which product steps leave unsigned digits and whether E squares gamma (factor -8 in the last product's addend) or
+#     2 gamma (factor -2) is chosen by dbln_options(): greedily, every choice kept only if Program.run_intervals still closes
+#     STATE -> DBLN -> STATE.  Nothing about the inner doublings is written by hand: the contract between them is whatever the intervals are
+#     (dbln_inner_contracts reports it).
+DBLN_STEPS = ("fold", "u0", "u1", "u2", "u3")     # per doubling: gamma^2 with -8 instead of (2 gamma)^2 with -2; unsigned digits of product step 0..3
+
+
+def build_pair_dbln(n=4, options=None, name=None):
+    """(A, B) <- 2^n (A, B).  options: one set of DBLN_STEPS names per doubling (None: dbln_options(n), the proved choice)."""
+    assert n >= 2 and n % 2 == 0, "B and BB alternate: an even number of doublings ends in B"
+    options = dbln_options(n) if options is None else options
+    p = Program(name or "PAIR29_DBL%d" % n)
+    A = p.fe("A", "io")
+    B = p.fe("B", "io")
+    U1 = p.fe("U1", "tmp")
+    U2 = p.fe("U2", "tmp")
+    U3 = p.fe("U3", "tmp")
+    P1 = p.fe("P1", "tmp")
+    T0 = p.fe("T0", "tmp")
+    TD = p.fe("TD", "tmp")
+    BB = p.fe("BB", "tmp")
+    for k in range(n):
+        o = options[k]
+        Bi, Bo = (B, BB) if k % 2 == 0 else (BB, B)
+        p.sqr(U1, Bi, TD, unsigned="u0" in o)                 # E: gamma = Y^2            O: delta = Z^2
+        p.swp_sub(P1, A, U1)                                  #                           O: X - delta
+        p.exec_("even")
+        if "fold" in o:
+            p.shl(P1, A, 2)                                   # E: 4X
+        else:
+            p.shl(P1, A, 1)                                   # E: 2X
+            p.shl(U1, U1, 1)                                  # E: 2 gamma
+        p.exec_("odd")
+        p.shladd(U1, U1, 1, P1)                               #                           O: X + delta = 2 delta + (X - delta)
+        p.exec_("all")
+        p.mul(U2, P1, U1, unsigned="u1" in o)                 # E: beta4 = 4 X gamma      O: m = (X - delta)(X + delta)
+        p.exec_("odd")
+        p.shladd(U1, U2, 1, U2)                               #                           O: alpha = 3m         (E keeps gamma or 2 gamma)
+        p.exec_("all")
+        p.swp(T0, U2)                                         #                           O: beta4
+        p.lane_const(TD[8], -2, 0)
+        p.sqr(U3, U1, TD, T0, TD[8], unsigned="u2" in o)      # E: gamma^2 or 4 gamma^2   O: X3 = alpha^2 - 2 beta4
+        p.swp(A, U3)                                          # E: X3
+        p.swp(P1, U1)                                         # E: alpha
+        p.swp(T0, Bi)                                         #                           O: Y
+        p.exec_("even")
+        p.sub(Bi, U2, A)                                      # E: beta4 - X3   (Y is dead; O keeps Z)
+        p.exec_("odd")
+        p.shl(P1, T0, 1)                                      #                           O: 2Y
+        p.exec_("all")
+        p.lane_const(TD[0], 0, -8 if "fold" in o else -2)
+        p.mul(Bo, P1, Bi, U3, TD[0], unsigned="u3" in o)      # E: Y3 = alpha (beta4 - X3) - 8 gamma^2      O: Z3 = 2 Y Z
+    return p
+
+
+def dbln_closed(prog, C=None):
+    """STATE -> prog -> STATE by intervals; returns the output contract, raises OverflowError where a column, a limb or the state leaves."""
+    C = STATE_P256 if C is None else C
+    e, o = {}, {}
+    e.update(fe_range("A", C["X"])); e.update(fe_range("B", C["Y"])); o.update(fe_range("B", C["Z"]))
+    re_, ro = prog.run_intervals(e, o)
+    U = {}
+    for nm, regs, fe in (("X", re_, "A"), ("Y", re_, "B"), ("Z", ro, "B")):
+        U[nm] = (min(regs["%s.%d" % (fe, i)][0] for i in range(8)), max(regs["%s.%d" % (fe, i)][1] for i in range(8))) + tuple(regs[fe + ".8"])
+        u, c = U[nm], C[nm]
+        if not (c[0] <= u[0] and u[1] <= c[1] and c[2] <= u[2] and u[3] <= c[3]):
+            raise OverflowError("%s: %s leaves the state contract: %r not inside %r" % (prog.name, nm, u, c))
+    return U
+
+
+_DBLN_OPTIONS = {}
+
+
+def dbln_options(n=4):
+    """The choice per doubling that the interval proof allows.  Starts from balanced digits and (2 gamma)^2 everywhere - that program must
+    close, or there is no DBLN - and tries every step of every doubling once, in two orders (first doubling first, last doubling first);
+    a step stays only if the whole program still closes.  The order that leaves the shorter program wins."""
+    if n in _DBLN_OPTIONS:
+        return _DBLN_OPTIONS[n]
+
+    def greedy(order):
+        opts = [frozenset() for _ in range(n)]
+        dbln_closed(build_pair_dbln(n, opts))
+        for k in order:
+            for step in DBLN_STEPS:
+                trial = list(opts)
+                trial[k] = opts[k] | {step}
+                try:
+                    dbln_closed(build_pair_dbln(n, trial))
+                    opts = trial
+                except OverflowError:
+                    pass
+        return opts
+    best = max((greedy(range(n)), greedy(range(n - 1, -1, -1))), key=lambda opts: sum(9 if s == "fold" else 8 for o in opts for s in o))
+    _DBLN_OPTIONS[n] = [frozenset(o) for o in best]
+    return _DBLN_OPTIONS[n]
+
+
+def dbln_inner_contracts(n=4, options=None):
+    """What the intervals say a state is after 1 .. n of the doublings of DBLN (the contract BETWEEN them, derived and not written):
+    a list of {"X" | "Y" | "Z": (lo, hi, top lo, top hi)}."""
+    options = dbln_options(n) if options is None else options
+    prog = build_pair_dbln(n, options)
+    bounds = [i for i, x in enumerate(prog.ins) if x[0] == "prod_end"]
+    out = []
+    e, o = {}, {}
+    e.update(fe_range("A", STATE_P256["X"])); e.update(fe_range("B", STATE_P256["Y"])); o.update(fe_range("B", STATE_P256["Z"]))
+    for k in range(n):
+        cut = Program(prog.name)
+        cut.ins = prog.ins[:bounds[4 * k + 3] + 1]
+        re_, ro = cut.run_intervals(e, o)
+        b = "BB" if k % 2 == 0 else "B"
+        rng = lambda regs, fe: (min(regs["%s.%d" % (fe, i)][0] for i in range(8)), max(regs["%s.%d" % (fe, i)][1] for i in range(8))) + tuple(regs[fe + ".8"])
+        out.append({"X": rng(re_, "A"), "Y": rng(re_, b), "Z": rng(ro, b)})
+    return out
+
+
+def build_pair_dbl4():
+    return build_pair_dbln(4)
+
+
 def build_pair_add(name="PAIR29_ADD", field=None, uns=UNSIGNED_ADD):
     """(AO, BO) <- (A, B) + P2 with P2 handed over CROSSED:  E: C = Z2,  O: C = X2, D = Y2.
     in: L(X1) <= 2, L(Y1) <= 3, L(Z1) = 1, L(X2) = 1, L(Y2) <= 3, L(Z2) = 1;  out: L(X) = 1, L(Y) = 1, L(Z) = 1
@@ -276,6 +405,15 @@ def state_outputs(progs, C):
 
 def contracts_closed(progs, C):
     U = state_outputs(progs, C)
+    # P-256 (field None: the structured prime): the fused doublings of a window take a state and must leave one (round 8).  emit() passes
+    # the program it is about to write as progs["dbl4"]; a caller that names only the three classic programs gets the proved default
+    # (dbln_options keeps its search result: one program build and one interval run per call, not a search).
+    dbl4 = progs.get("dbl4")
+    if dbl4 is None and progs["dbl"].field is None:
+        dbl4 = build_pair_dbl4()
+    if dbl4 is not None:
+        d4 = dbln_closed(dbl4, C)
+        U = {k: (min(U[k][0], d4[k][0]), max(U[k][1], d4[k][1]), min(U[k][2], d4[k][2]), max(U[k][3], d4[k][3])) for k in U}
     for k in ("X", "Y", "Z"):
         u, c = U[k], C[k]
         if not (c[0] <= u[0] and u[1] <= c[1] and c[2] <= u[2] and u[3] <= c[3]):
@@ -467,7 +605,7 @@ def build_bn_pair_madd(uns=UNSIGNED_BN_MADD):
 
 BN_PAIR_PROGRAMS = [build_bn_pair_dbl, build_bn_pair_add, build_bn_pair_madd]
 
-PROGRAMS = [build_pair_dbl, build_pair_add, build_pair_madd]
+PROGRAMS = [build_pair_dbl, build_pair_add, build_pair_madd, build_pair_dbl4]
 
 ALIGN_NOTE = """// Every instruction below is 8 bytes (VOP3, VOP2 + DPP, or VOP2 + 32-bit literal): a block started on an 8-byte boundary stays
 // on 8-byte boundaries throughout (8-byte instructions at 4-mod-8 addresses cost 8.5 % of kernel time, measured).
@@ -501,7 +639,7 @@ def emit(path_kind):
     if path_kind == "bnpair":
         contracts_closed({"dbl": build_bn_pair_dbl(), "add": build_bn_pair_add(), "madd": build_bn_pair_madd()}, STATE_BN)
     elif path_kind == "pair":
-        contracts_closed({"dbl": build_pair_dbl(), "add": build_pair_add(), "madd": build_pair_madd()}, STATE_P256)
+        contracts_closed({"dbl": build_pair_dbl(), "add": build_pair_add(), "madd": build_pair_madd(), "dbl4": build_pair_dbl4()}, STATE_P256)
     if path_kind == "bnpair":
         print("// GENERATED by gen_pair_gcn.py bnpair - do not edit.  Two-lanes-per-point operations on FP256BN's G1 (a = 0): the point")
         print("// operations of the four-lanes-per-signature idemix kernel (bn_quad29.h); verified in the DSL interpreter against big integers")

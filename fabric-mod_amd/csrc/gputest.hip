@@ -52,6 +52,8 @@ __global__ void __launch_bounds__(64, 1) gputest_pair_kernel(int op, const int32
         pair_pt R;
         PAIR_MADD(R, P, C, D);
         P = R;
+    } else if (op == 7) {           // the four doublings of a 4-bit window as one program (round 8)
+        PAIR_DBL4(P);
     } else if (op == 4) {           // the same three programs for FP256BN's field and a = 0 (pair29_bn_gcn.h)
         PAIRBN_DBL(P.A, P.B, tU1, tU2, tU3, tU4, tP1, tP2, tT0, tT1, tTD);
     } else if (op == 5) {

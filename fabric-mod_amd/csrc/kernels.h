@@ -73,6 +73,7 @@ struct VerifyLaunch {
     // fresh key, digest given, two lanes per signature only:
     int table_lds = 0;                                // the per-signature table: 1 PairQTabLds, 0 global workspace, -1 by size (PAIR_TABLE_LDS_FROM)
     bool pair_solo = false;                           // LDS table: the one-wave form instead of the helper-wave form
+    bool pair_dbl1 = false;                           // LDS table: the per-doubling loop instead of the four-doubling program
 };
 hipError_t launch_verify(const VerifyLaunch& v, hipStream_t st);
 

@@ -34,6 +34,8 @@ __device__ __forceinline__ void pair_sel(pair_pt& r, bool c, const pair_pt& a, c
 
 #define PAIR_TMPS __attribute__((unused)) fe tU1, tU2, tU3, tU4, tU6, tW, tH, tRR, tP1, tP2, tT0, tT1, tTD
 #define PAIR_DBL(P) PAIR29_DBL((P).A, (P).B, tU1, tU2, tU3, tW, tP1, tP2, tT0, tT1, tTD)
+// Four doublings as one generated program (round 8: the doublings of a 4-bit window); tW is its second B register.
+#define PAIR_DBL4(P) PAIR29_DBL4((P).A, (P).B, tU1, tU2, tU3, tP1, tT0, tTD, tW)
 #define PAIR_ADD(R, P, C, D) PAIR29_ADD((R).A, (R).B, (P).A, (P).B, tH, tRR, tW, tU1, tU2, tU3, tU4, tU6, tP1, tP2, tT0, tT1, tTD, C, D)
 #define PAIR_MADD(R, P, C, D) PAIR29_MADD((R).A, (R).B, (P).A, (P).B, tU1, tU2, tU3, tU4, tH, tRR, tP1, tP2, tT0, tT1, tTD, C, D)
 
@@ -365,7 +367,9 @@ __device__ __forceinline__ void pair_qtab_build29(const pair_pt& Qp, const fe& Q
 
 // T = u2 * Q over the table pair_qtab_build29 wrote (second part of pair_combined_mult29): NWIN signed W-bit windows, the same
 // recoding as p256_combined_mult29 for W = 5, and for W = 4 the scalar u2 = n - 2 (see pair_combined_mult29).
-template <class QTab, int W = 5>
+// The four doublings of a 4-bit window are ONE program (PAIR_DBL4) unless DBL1 asks for the per-doubling loop (FABGPU_FLAG_PAIR_DBL1: A/B
+// runs and parity tests); the two leave the same point, not the same limbs.
+template <class QTab, int W = 5, bool DBL1 = false>
 __device__ __forceinline__ void pair_u2_mult29(pair_pt& T, bool& t_inf, const u256& u2, const pair_pt& Qp, const QTab& qtab, bool odd) {
     constexpr int TAB = 1 << (W - 1);                 // entries j*Q, j = 1..TAB
     constexpr int NWIN = (257 + W - 1) / W;           // windows over bits -1 .. 256 of a scalar below n
@@ -392,8 +396,12 @@ __device__ __forceinline__ void pair_u2_mult29(pair_pt& T, bool& t_inf, const u2
         fe C, D;
         qtab.load_crossed(mag ? mag : 1u, C, D, odd);   // issued ahead of the doublings
         if (i != NWIN - 1) {
+            if constexpr (W == 4 && !DBL1) {
+                PAIR_DBL4(T);
+            } else {
 #pragma unroll 1
-            for (int k = 0; k < W; k++) PAIR_DBL(T);
+                for (int k = 0; k < W; k++) PAIR_DBL(T);
+            }
         }
         {
             const int32_t nm = neg ? -1 : 0, nc = neg ? 1 : 0;        // -y = (y ^ -1) + 1: one v_xad_u32 per limb instead of a negation and a select
@@ -444,7 +452,7 @@ __device__ __forceinline__ void pair_u2_mult29(pair_pt& T, bool& t_inf, const u2
 // |d| == n (mod 2^W).  n mod 32 = 17 > 16: never for W = 5.  n mod 16 = 1: for W = 4 EXACTLY ONE scalar, u2 = n - 2
 // (digit -1 on top of M = n - 1: T = -Q, addend -Q).  That scalar is recognised up front and its product, -2Q, is taken from the
 // table (entry 2, negated) instead of from the loop.
-template <class QTab, int W = 5>
+template <class QTab, int W = 5, bool DBL1 = false>
 __device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, const u256& u1, const u256& u2, const fe& QX, const fe& QY,
                                                      const int32_t* __restrict__ gtab, const QTab& qtab, bool odd) {
     static_assert(W == 4 || W == 5, "signed 4- or 5-bit windows");
@@ -455,7 +463,7 @@ __device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, c
     pair_qtab_build29<QTab, W>(Qp, QX, QY, qtab, odd);
     pair_pt T;
     bool t_inf;
-    pair_u2_mult29<QTab, W>(T, t_inf, u2, Qp, qtab, odd);
+    pair_u2_mult29<QTab, W, DBL1>(T, t_inf, u2, Qp, qtab, odd);
 
     // --- S = u1 * G (16-bit comb), then R = S + T ---
     pair_pt S;
@@ -506,7 +514,7 @@ __device__ __forceinline__ bool pair_x_equals_r29(const pair_pt& Rr, bool r_inf,
 }
 
 // Status of one tuple, valid on the EVEN lane of the pair.
-template <class QTab, int W = 5>
+template <class QTab, int W = 5, bool DBL1 = false>
 __device__ __forceinline__ uint32_t p256_verify_pair29(const u256& qx, const u256& qy, const u256& e, const u256& r, const u256& s,
                                                         const int32_t* __restrict__ gtab, const QTab& qtab, bool odd) {
     const u256 P = FAB_P256_P;
@@ -524,7 +532,7 @@ __device__ __forceinline__ uint32_t p256_verify_pair29(const u256& qx, const u25
 
     pair_pt Rr;
     bool r_inf;
-    pair_combined_mult29<QTab, W>(Rr, r_inf, u1, u2, QX, QY, gtab, qtab, odd);
+    pair_combined_mult29<QTab, W, DBL1>(Rr, r_inf, u1, u2, QX, QY, gtab, qtab, odd);
     bool ok = pair_x_equals_r29(Rr, r_inf, r);
     uint32_t st = ok ? ST_VALID : ST_BAD_MATH;
     return early != ST_VALID ? early : st;

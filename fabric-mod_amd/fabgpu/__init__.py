@@ -38,6 +38,7 @@ FLAG_NO_QUAD = 4         # fabgpu.h FABGPU_FLAG_NO_QUAD (idemix: never the four-
 FLAG_PAIR_TABLE_LDS = 8      # fabgpu.h: the verify-only pair kernel keeps its per-signature table in LDS
 FLAG_PAIR_TABLE_GLOBAL = 16  # ... in the global workspace
 FLAG_PAIR_SOLO = 1024        # fabgpu.h: ... in LDS, one wave per SIMD (no helper waves; A/B runs and parity tests)
+FLAG_PAIR_DBL1 = 2048        # fabgpu.h: ... in LDS, the per-doubling loop instead of the four-doubling program (A/B runs and parity tests)
 FLAG_KEY_TABLES_16BIT = 256  # fabgpu.h: registered keys also get a 16-bit comb (80 MiB each, built behind the registration)
 FLAG_NO_WIDE = 32            # fabgpu.h: registered keys never on the eight-lanes-per-signature two-phase kernels (launches <= 8 192 signatures)
 ST_VALID, ST_BAD_MATH, ST_HIGH_S, ST_RANGE, ST_OFF_CURVE = 0, 1, 2, 3, 4

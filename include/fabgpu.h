@@ -80,6 +80,8 @@ typedef struct fabgpu_ctx fabgpu_ctx;
 /* (512u is left unassigned: the host tests use it as the example of an unknown bit) */
 #define FABGPU_FLAG_PAIR_SOLO 1024u  /* two-lanes-per-signature verify kernel with the table in LDS: one wave per SIMD (round 6's form) instead of
                                         a helper wave beside each that computes s^-1, u1, u2 and u1*G (A/B runs; parity tests run both forms) */
+#define FABGPU_FLAG_PAIR_DBL1 2048u  /* ... in LDS, either form: the four doublings of a window as a loop over the one-doubling program (round 7's
+                                        form) instead of one four-doubling program (A/B runs; parity tests run both forms) */
 
 #define FABGPU_FLAG_KEY_TABLES_16BIT 256u   /* registered keys (fabgpu_p256_key_register): each key also gets a 16-bit comb table - 80 MiB, the
                                             generator's format, built on the device BEHIND the registration (nobody waits for it), up to

@@ -7,6 +7,7 @@ gcn_dsl.py) x the trip counts of p256_verify_pair_lds_kernel (65 signed 4-bit wi
     route    lane-pair routing: v_cndmask on the parity mask, DPP moves / fused DPP add / sub between the two lanes of a signature
     field    limb-wise field additions, subtractions, doublings, the weak normalisation pass      (9 instructions per field op)
     hazard   s_nop in front of a DPP source written less than two instructions earlier
+    scalar   (round 8, PAIR29_DBL4) EXEC switches of the lane-masked writes and the 4-byte pads that keep the products 8-byte aligned
 
 Prints a table (instructions per operation and per verification) and the floor argument's numbers; the measured total to compare with
 is SQ_INSTS_VALU / SQ_WAVES of profiles/r06_pmc_sq.txt.   usage: python tools/instr_classes.py [measured instructions per wave]"""
@@ -24,9 +25,9 @@ CLASS = {"mad0": "mac", "mad": "mac", "q29": "carry", "qn0": "carry", "bfe29": "
 
 def classes(prog):
     text, stats = prog.emit_asm({n: "(%s)" % n for n in prog.order})
-    out = {"mac": 0, "carry": 0, "route": 0, "field": 0, "hazard": stats["nops"]}
+    out = {"mac": 0, "carry": 0, "route": 0, "field": 0, "hazard": stats["nops"], "scalar": stats.get("scalar", 0)}
     for ins in prog.ins:
-        if ins[0] in ("prod_begin", "prod_end"):      # markers for emit_cxx, not instructions
+        if ins[0] in ("prod_begin", "prod_end", "exec"):      # markers for emit_cxx / counted from the emitted text (switches and pads)
             continue
         c = CLASS[ins[0]]
         out[c] += 2 if ins[0] == "qn0" else 1
@@ -35,26 +36,30 @@ def classes(prog):
 
 
 def main():
-    progs = {"doubling (4M + 4S)": g.build_pair_dbl(), "addition (12M + 4S)": g.build_pair_add(), "mixed addition (8M + 3S)": g.build_pair_madd(),
+    progs = {"doubling (4M + 4S)": g.build_pair_dbl(), "four doublings (DBL4)": g.build_pair_dbl4(), "addition (12M + 4S)": g.build_pair_add(), "mixed addition (8M + 3S)": g.build_pair_madd(),
              "field product (one lane)": g.build_fe_mul(), "field square (one lane)": g.build_fe_sqr()}
     rows = {}
-    print("%-28s %7s %7s %7s %7s %7s %7s   %s" % ("per operation", "mac", "carry", "route", "field", "hazard", "total", "mac share"))
+    print("%-28s %7s %7s %7s %7s %7s %7s %7s   %s" % ("per operation", "mac", "carry", "route", "field", "hazard", "scalar", "total", "mac share"))
     for name, p in progs.items():
         c, total = classes(p)
         assert sum(c.values()) == total, (name, c, total)
         rows[name] = (c, total)
-        print("%-28s %7d %7d %7d %7d %7d %7d   %.2f" % (name, c["mac"], c["carry"], c["route"], c["field"], c["hazard"], total, c["mac"] / total))
-    # trip counts of the LDS-table kernel: 64 windows x 4 doublings (the first window has nothing to double) + the table's 4; 65 window
-    # additions + the final one; 16 comb + the table's 3 mixed additions (the final addition's doubling runs for crafted inputs only)
-    trips = {"doubling (4M + 4S)": 64 * 4 + 4, "addition (12M + 4S)": 65 + 1, "mixed addition (8M + 3S)": 16 + 3}
-    tot = {k: 0 for k in ("mac", "carry", "route", "field", "hazard")}
+        print("%-28s %7d %7d %7d %7d %7d %7d %7d   %.2f" % (name, c["mac"], c["carry"], c["route"], c["field"], c["hazard"], c["scalar"], total, c["mac"] / total))
+    # trip counts of the LDS-table kernel: 64 windows x one four-doubling program (the first window has nothing to double; round 7: 64 x 4
+    # doublings) + the table's 4 doublings; 65 window additions + the final one; 16 comb + the table's 3 mixed additions (the final
+    # addition's doubling runs for crafted inputs only)
+    trips = {"doubling (4M + 4S)": 4, "four doublings (DBL4)": 64, "addition (12M + 4S)": 65 + 1, "mixed addition (8M + 3S)": 16 + 3}
+    print()
+    print("window doublings: 64 x %d = %d (round 7: 256 x %d = %d)" % (rows["four doublings (DBL4)"][1], 64 * rows["four doublings (DBL4)"][1],
+                                                                      rows["doubling (4M + 4S)"][1], 256 * rows["doubling (4M + 4S)"][1]))
+    tot = {k: 0 for k in ("mac", "carry", "route", "field", "hazard", "scalar")}
     for name, n in trips.items():
         for k in tot:
             tot[k] += n * rows[name][0][k]
     point = sum(tot.values())
     print()
-    print("per verification (two lanes), point arithmetic: %d doublings, %d additions, %d mixed additions" % tuple(trips.values()))
-    for k in ("mac", "carry", "route", "field", "hazard"):
+    print("per verification (two lanes), point arithmetic: %d doublings, %d four-doubling programs, %d additions, %d mixed additions" % tuple(trips.values()))
+    for k in ("mac", "carry", "route", "field", "hazard", "scalar"):
         print("  %-8s %8d  %5.1f %%" % (k, tot[k], 100.0 * tot[k] / point))
     print("  %-8s %8d" % ("total", point))
     measured = float(sys.argv[1]) if len(sys.argv) > 1 else 354.4e3
