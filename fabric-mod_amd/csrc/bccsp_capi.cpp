@@ -719,6 +719,12 @@ int fabgpu_csp_p384_pass_stats(fabgpu_csp* csp, uint64_t* out, int cap) {
     for (int i = 0; i < cap && i < GPUCSP::P384_PASS_STATS; i++) out[i] = v[i];
     return GPUCSP::P384_PASS_STATS;
 }
+// ... and the rows of its keyed batches that went to the eight-lanes-per-signature form (GPUCSP::P384PassWideRows)
+int fabgpu_csp_p384_pass_wide_rows(fabgpu_csp* csp, uint64_t* rows) {
+    if (!csp || !rows) return FABGPU_EINVAL;
+    *rows = csp->csp->P384PassWideRows();
+    return FABGPU_OK;
+}
 // an MSP's hash family, for the P-384 stage (GPUCSP::SetMspHashFamily)
 int fabgpu_csp_msp_hash_family(fabgpu_csp* csp, const char* mspid, const char* family, char* err, size_t errcap) {
     if (!csp || !mspid) return FABGPU_EINVAL;

@@ -212,6 +212,7 @@ Error GPUCSP::New(const fabgpu_cfg* cfg, std::unique_ptr<GPUCSP>& out) {
     d->ordinal = cfg ? cfg->device : -1;
     p->devs_.push_back(std::move(d));
     p->opts_.ctx_flags = cfg ? cfg->flags : 0;
+    p->opts_.p384_wide = (p->opts_.ctx_flags & FABGPU_FLAG_P384_WIDE) ? 1 : 0;
     out = std::move(p);
     return Error();
 }
@@ -230,12 +231,14 @@ Error GPUCSP::New(const ProviderOptions& opts, std::unique_ptr<GPUCSP>& out) {
     p->hash_sha3_.store(opts.hash_sha3 > 0, std::memory_order_relaxed);
     p->p384_.store(opts.p384 > 0, std::memory_order_relaxed);
     p->opts_.devices = devices;
+    if (opts.p384_wide > 0) p->opts_.ctx_flags |= FABGPU_FLAG_P384_WIDE;             // (the option is the flag, on every context)
+    p->opts_.p384_wide = (p->opts_.ctx_flags & FABGPU_FLAG_P384_WIDE) ? 1 : 0;
     p->audit_permille_.store(opts.audit_permille > 1000 ? 1000 : opts.audit_permille, std::memory_order_relaxed);
     for (int32_t ord : devices) {
         fabgpu_cfg cfg;
         memset(&cfg, 0, sizeof(cfg));
         cfg.device = ord;
-        cfg.flags = opts.ctx_flags;
+        cfg.flags = p->opts_.ctx_flags;
         fabgpu_ctx* ctx = nullptr;
         const int rc = fabgpu_init(&cfg, &ctx);
         if (rc != FABGPU_OK)                                    // (~GPUCSP shuts the contexts made so far down)
@@ -297,6 +300,16 @@ int64_t GPUCSP::SetOption(const std::string& name, int64_t value) const {
         opts_.audit_permille = (uint32_t)value;
         return (int64_t)audit_permille_.exchange((uint32_t)value, std::memory_order_relaxed);
     }
+    if (name == "p384_wide") {                                   // (a context flag: the living contexts are switched, all or none)
+        const int64_t prev = opts_.p384_wide;
+        for (auto& d : devs_)
+            if (ctx_set_p384_wide(d->ctx, value > 0) != FABGPU_OK) {
+                for (auto& u : devs_) (void)ctx_set_p384_wide(u->ctx, prev > 0);
+                return INT64_MIN;
+            }
+        opts_.p384_wide = value > 0 ? 1 : 0;
+        return prev;
+    }
     for (const OptField& o : kIntOpts)
         if (name == o.name) {
             const int64_t prev = opts_.*(o.f);
@@ -313,6 +326,7 @@ int64_t GPUCSP::GetOption(const std::string& name) const {
     if (name == "pass_stage_min_bytes") return opts_.pass_stage_min_bytes;
     if (name == "n_devices") return (int64_t)devs_.size();
     if (name == "audit_permille") return (int64_t)AuditPermille();
+    if (name == "p384_wide") return opts_.p384_wide;
     if (name == "registrations_dropped") return (int64_t)reg_dropped_.load(std::memory_order_relaxed);        // (read-only counters)
     if (name == "registration_id_mismatches") return (int64_t)reg_id_mismatches_.load(std::memory_order_relaxed);
     for (const OptField& o : kIntOpts)
@@ -3366,6 +3380,7 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
         if (!joined) tok = up ? up->join() : 0;                          // (both batches read the same staged block)
         joined = true;
         const auto submit = sha3 ? fabgpu_identity_verify_batch_p384_sha3 : fabgpu_identity_verify_batch_p384;   // the family is the entry's
+        const bool wide = keyed && ctx_p384_wide_serves(dv.ctx, fn);      // (what the context's launch site decides for a keyed batch of fn rows)
         int rc = FABGPU_EINVAL;
         if (tok) {
             d.flags = FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED;
@@ -3378,6 +3393,7 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
         p384_pass_[P384_PASS_SUBMITTED].fetch_add(fn, std::memory_order_relaxed);
         p384_pass_[keyed ? P384_PASS_KEYED : P384_PASS_FRESH].fetch_add(1, std::memory_order_relaxed);
         if (sha3) p384_pass_[P384_PASS_SHA3_ROWS].fetch_add(fn, std::memory_order_relaxed);
+        if (wide) p384_pass_wide_rows_.fetch_add(fn, std::memory_order_relaxed);
         for (size_t j = 0; j < fn; j++) {
             const uint32_t k = f.row[j];
             st[k] = fst[j];

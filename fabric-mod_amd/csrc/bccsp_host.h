@@ -167,6 +167,9 @@ struct ProviderOptions {
                                        // of the same name; default off: "Unsupported 'HashOpt' provided [SHA3_256]", as bccsp/sw is asked then)
     int p384 = 0;                      // > 0: the *_p384 calls verify ECDSA P-384 identities on the device (SetOption of the same name; default off:
                                        // they answer that P-384 is served by bccsp/sw)
+    int p384_wide = 0;                 // > 0: FABGPU_FLAG_P384_WIDE on every context - keyed P-384 launches of at most 8 192 rows on eight lanes per
+                                       // signature.  Read at construction like ctx_flags (which may carry the bit itself); SetOption of the same
+                                       // name switches the living contexts.  Default off
     uint32_t audit_permille = 0;       // share of the digests / verdicts handed out that is re-computed on the CPU first (0 .. 1000; 0: none)
 };
 constexpr int kMaxProviderDevices = 64;   // contexts per provider (8 GPUs x up to 8 contexts each)
@@ -315,6 +318,8 @@ class GPUCSP {
     Error P384PassStage(const uint8_t* block, size_t len, const ParsedBlock& parsed, BlockVerdicts& out, BlockUpload* up, const PassOptions& opt) const;
     enum : int { P384_PASS_STAGES = 0, P384_PASS_SEEN = 1, P384_PASS_SUBMITTED = 2, P384_PASS_KEYED = 3, P384_PASS_FRESH = 4, P384_PASS_AUDITED = 5, P384_PASS_MEMO_SEEDED = 6, P384_PASS_SHA3_ROWS = 7, P384_PASS_STATS = 8 };
     void P384PassStats(uint64_t out[P384_PASS_STATS]) const;
+    // ... and the rows of its keyed batches that the eight-lanes-per-signature form verified (the "p384_wide" option; 0 without it)
+    uint64_t P384PassWideRows() const { return p384_pass_wide_rows_.load(std::memory_order_relaxed); }
     // Starts the upload of a block on a helper thread (blocks of 4 MiB and more) so that it travels while the caller parses
     // and gates; join() returns the token for PreVerifyParsed (0 if nothing was staged).
     struct BlockUpload {
@@ -498,6 +503,7 @@ class GPUCSP {
     // corruption the audit must catch.  Nothing in the product sets it.
     mutable std::atomic<uint32_t> test_p384_flip_{0};
     mutable std::atomic<uint64_t> p384_pass_[P384_PASS_STATS] = {};   // P384PassStats
+    mutable std::atomic<uint64_t> p384_pass_wide_rows_{0};           // P384PassWideRows
     mutable MspFamilyTable msp_family_;                      // mspid -> hash family, for P384PassStage (its own lock inside)
     mutable P384Memo p384_memo_;                             // the verdict memo of the pass's P-384 tuples (its own lock and capacity inside)
     // as AuditDirect, for a P-384 "valid": re-computed with the host compilation of p384.h (audit_p384_verify)

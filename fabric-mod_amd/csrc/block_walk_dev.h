@@ -336,6 +336,11 @@ int key_table_copy(fabgpu_ctx* ctx, uint32_t key_id, int32_t* out);   // TEST HO
 int p384_key_table_copy(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint32_t* out);
 int p384_key_register_batch_hook(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key_ids);
 int key_register_many_prebuilt(fabgpu_ctx* const* ctxs, int n, const uint8_t* qx32, const uint8_t* qy32, const int32_t* table, uint32_t* key_ids);
+// FABGPU_FLAG_P384_WIDE on a living context (the provider's "p384_wide" option): the eight-lane form of the keyed P-384 launches, for the
+// launches queued after the call; turning it on makes the form's scratch (a FABGPU_* code when that fails).  ctx_p384_wide_serves: whether
+// a keyed launch of n rows queued now would take that form - the question the launch site itself asks.
+int ctx_set_p384_wide(fabgpu_ctx* ctx, bool on);
+bool ctx_p384_wide_serves(fabgpu_ctx* ctx, size_t n);
 // the duration of the last timed launch of a FABGPU_FLAG_TIME_KERNELS context (ms; < 0: none) - read by the test-hook library
 float ctx_last_kernel_ms(fabgpu_ctx* ctx);
 // TEST HOOK support: the capacities of the block pass's per-envelope, per-tuple, pinned, mapped and gather-scratch buffers (bytes)

@@ -277,6 +277,11 @@ struct fabgpu_ctx {
     std::condition_variable k384_cv;
     int k384_launchers = 0;
     std::atomic<uint64_t> k384_launches{0};  // keyed P-384 launches queued so far (fabgpu_p384_key_table_stats)
+    // FABGPU_FLAG_P384_WIDE (or fab::ctx_set_p384_wide): keyed launches of at most P384_WIDE_LAUNCH_MAX rows on eight lanes per signature.
+    // Their scratch is a workspace of the qws pool, always asked for at its full size and made when the switch is turned on: a launch
+    // finds it there (a second one is made only when keyed launches of several streams overlap).
+    std::atomic<bool> p384_wide{false};
+    std::atomic<uint64_t> k384_wide_rows{0}; // rows handed to the eight-lane form so far (fabgpu_p384_wide_rows)
     std::mutex k384_build_mu;                // one build at a time: the builder's room and stream are one
     void *d_k384_in = nullptr, *d_k384_scr = nullptr;
     size_t k384_in_cap = 0, k384_scr_cap = 0;
@@ -427,6 +432,9 @@ inline hipError_t launched(const fabgpu_ctx* ctx, hipError_t e) { return ctx->fa
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// the scratch of an eight-lane keyed P-384 launch, whatever its row count: one size, so that the pool's workspace always fits
+constexpr size_t P384_WIDE_WS_BYTES = (size_t)P384_WIDE_LAUNCH_MAX * P384_WIDE_SCRATCH_BYTES;
+
 // what the _dev entry points refuse: more rows or arena bytes than the kernels' 32-bit indices hold
 inline bool dev_too_big(size_t n, size_t arena_bytes = 0) { return n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull; }
 
@@ -490,7 +498,7 @@ int fabgpu_init(const fabgpu_cfg* cfg, fabgpu_ctx** out) {
     *out = nullptr;
     if (cfg && (cfg->flags & ~(uint32_t)(FABGPU_FLAG_ONE_LANE_ONLY | FABGPU_FLAG_TIME_KERNELS | FABGPU_FLAG_NO_QUAD | FABGPU_FLAG_PAIR_TABLE_LDS |
                                           FABGPU_FLAG_PAIR_TABLE_GLOBAL | FABGPU_FLAG_NO_WIDE | FABGPU_FLAG_NYM_FUSED_HASH | FABGPU_FLAG_NYM_NO_SIDE_STREAM |
-                                          FABGPU_FLAG_KEY_TABLES_16BIT | FABGPU_FLAG_PAIR_SOLO | FABGPU_FLAG_PAIR_DBL1)) != 0) return FABGPU_EINVAL;
+                                          FABGPU_FLAG_KEY_TABLES_16BIT | FABGPU_FLAG_PAIR_SOLO | FABGPU_FLAG_PAIR_DBL1 | FABGPU_FLAG_P384_WIDE)) != 0) return FABGPU_EINVAL;
     if (cfg && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_LDS) && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_GLOBAL)) return FABGPU_EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return FABGPU_ENODEV;
@@ -578,6 +586,7 @@ int fabgpu_init(const fabgpu_cfg* cfg, fabgpu_ctx** out) {
                 ctx->stream_keytab16 = nullptr;
             }
         }
+        if (cfg && (cfg->flags & FABGPU_FLAG_P384_WIDE) && (rc = fab::ctx_set_p384_wide(ctx, true))) break;
         if (cfg && cfg->max_batch) {
             size_t n = cfg->max_batch;
             if ((rc = ctx->fields.ensure(n * 160)) || (rc = ctx->offs.ensure((n + 1) * 4)) || (rc = ctx->out.ensure(n * 41 + 64))) break;
@@ -671,6 +680,23 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
 }
 
 }  // extern "C"
+// The eight-lane form of the keyed P-384 launches, on or off, for the launches queued after the call (block_walk_dev.h).  On: the
+// scratch between its two launches joins the workspace pool now, so that no launch has to make it.
+int fab::ctx_set_p384_wide(fabgpu_ctx* ctx, bool on) {
+    if (!ctx) return FABGPU_EINVAL;
+    if (on && !ctx->p384_wide.load(std::memory_order_relaxed)) {
+        DeviceGuard g(ctx->device);
+        size_t wi = 0;
+        void* wsp = nullptr;
+        if (int rc = ctx->acquire_qws(P384_WIDE_WS_BYTES, &wi, &wsp, ctx->stream)) return rc;
+        ctx->release_qws(wi, ctx->stream);
+    }
+    ctx->p384_wide.store(on, std::memory_order_relaxed);
+    return FABGPU_OK;
+}
+bool fab::ctx_p384_wide_serves(fabgpu_ctx* ctx, size_t n) {
+    return ctx && n != 0 && n <= (size_t)P384_WIDE_LAUNCH_MAX && ctx->p384_wide.load(std::memory_order_relaxed);
+}
 void fab::ctx_test_nym_side_after(fabgpu_ctx* ctx, bool on) {
     if (ctx) ctx->test_nym_side_after.store(on);
 }
@@ -2138,6 +2164,13 @@ int p384_verify_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* key_id, const v
     v.gcomb = snap.gcomb; v.snap = snap.snap; v.nkeys = snap.nkeys;
     v.verdict_bits = verdict_bits; v.status = status;
     ctx->k384_launches.fetch_add(1, std::memory_order_relaxed);
+    if (fab::ctx_p384_wide_serves(ctx, n)) {
+        ctx->k384_wide_rows.fetch_add(n, std::memory_order_relaxed);
+        return timed_launch(ctx, st, P384_WIDE_WS_BYTES, [&](void* wsp) {
+            v.wide_scratch = wsp;
+            return launch_p384_verify_keyed_wide(v, st);
+        });
+    }
     return timed_launch(ctx, st, 0, [&](void*) { return launch_p384_verify_keyed(v, st); });
 }
 
@@ -2201,6 +2234,12 @@ int fabgpu_p384_key_unregister(fabgpu_ctx* ctx, uint32_t key_id) {
     (void)k384_publish_locked(ctx, d);
     k384_drain_push_locked(ctx, std::move(d));
     k384_drain_advance_locked(ctx);
+    return FABGPU_OK;
+}
+
+int fabgpu_p384_wide_rows(fabgpu_ctx* ctx, uint64_t* rows) {
+    if (!ctx || !rows) return FABGPU_EINVAL;
+    *rows = ctx->k384_wide_rows.load(std::memory_order_relaxed);
     return FABGPU_OK;
 }
 

@@ -147,8 +147,15 @@ struct P384KeyedLaunch {
     uint32_t nkeys = 0;                      // the high-water mark the snapshot was taken at
     void* verdict_bits = nullptr;            // ceil(n/64) x u64
     void* status = nullptr;                  // n bytes or nullptr
+    void* wide_scratch = nullptr;            // launch_p384_verify_keyed_wide only: n x P384_WIDE_SCRATCH_BYTES, 4-byte aligned, the launch's own until it has run
 };
 hipError_t launch_p384_verify_keyed(const P384KeyedLaunch& v, hipStream_t st);
+// ---- p384_wide_kernels.hip: the same verification on eight lanes per signature, in two launches on st (p384_wide.h) ----
+// For launches of at most P384_WIDE_LAUNCH_MAX rows (hipErrorInvalidValue beyond); the same rows, ids, snapshot rule, verdict words and
+// status bytes as launch_p384_verify_keyed.
+constexpr uint32_t P384_WIDE_LAUNCH_MAX = 8192;
+constexpr size_t P384_WIDE_SCRATCH_BYTES = 100;   // per row between the phases: u1, u2, the early status
+hipError_t launch_p384_verify_keyed_wide(const P384KeyedLaunch& v, hipStream_t st);
 
 // ---- p384_described_kernels.hip: the SHA-256 digest rows of a described batch, for the E32 form of the two P-384 verify kernels ----
 // Message i = prefix pa.pre_idx[i] (if any) || the span off names: arena bytes below tail_base, tail[offset - tail_base] at or above it.

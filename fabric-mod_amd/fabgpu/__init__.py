@@ -41,6 +41,7 @@ FLAG_PAIR_SOLO = 1024        # fabgpu.h: ... in LDS, one wave per SIMD (no helpe
 FLAG_PAIR_DBL1 = 2048        # fabgpu.h: ... in LDS, the per-doubling loop instead of the four-doubling program (A/B runs and parity tests)
 FLAG_KEY_TABLES_16BIT = 256  # fabgpu.h: registered keys also get a 16-bit comb (80 MiB each, built behind the registration)
 FLAG_NO_WIDE = 32            # fabgpu.h: registered keys never on the eight-lanes-per-signature two-phase kernels (launches <= 8 192 signatures)
+FLAG_P384_WIDE = 4096        # fabgpu.h: registered P-384 keys on eight lanes per signature, two launches, for keyed launches <= 8 192 rows (off by default)
 ST_VALID, ST_BAD_MATH, ST_HIGH_S, ST_RANGE, ST_OFF_CURVE = 0, 1, 2, 3, 4
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -121,7 +122,8 @@ class _Cfg(ctypes.Structure):
 # what fabgpu_p256_key_table_stats reports, in order
 KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "live_16bit", "bytes_held", "slots_used")
 # ... fabgpu_csp_p384_pass_stats
-P384_PASS_STATS = ("stages", "seen", "submitted", "keyed_launches", "fresh_launches", "audited", "memo_seeded", "sha3_rows")
+# ... followed by fabgpu_csp_p384_pass_wide_rows
+P384_PASS_STATS = ("stages", "seen", "submitted", "keyed_launches", "fresh_launches", "audited", "memo_seeded", "sha3_rows", "wide_rows")
 # ... and fabgpu_p384_key_table_stats
 P384_KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "keyed_launches", "bytes_held", "slots_used")
 P384_COMB_WORDS = 48 * 256 * 24      # one P-384 comb table (csrc/p384_tables.h CombTab384): 1.125 MiB
@@ -167,6 +169,7 @@ ABI_SYMBOLS = [
     "fabgpu_identity_verify_batch_p384", "fabgpu_identity_verify_batch_p384_dev", "fabgpu_identity_verify_batch_p384_sha3",
     "fabgpu_identity_verify_batch_p384_sha3_dev", "fabgpu_identity_to_p384", "fabgpu_csp_p384_pass_stats", "fabgpu_csp_msp_hash_family", "fabgpu_csp_msp_hash_family_get",
     "fabgpu_csp_memo_lookup_p384", "fabgpu_csp_memo_stats_p384", "fabgpu_csp_memo_set_capacity_p384",
+    "fabgpu_p384_wide_rows", "fabgpu_csp_p384_pass_wide_rows",
 ]
 
 # what libfabgpu_testhooks.so exports (fabric-mod_amd/csrc/fabgpu_testhooks.h): probes, walker comparisons, the synthetic block generator, the
@@ -335,6 +338,8 @@ def load():
     L.fabgpu_identity_verify_batch_p384_sha3_dev.argtypes = [_vp, ctypes.POINTER(_IdBatchP384), _vp, _vp]
     L.fabgpu_identity_to_p384.argtypes = [ctypes.c_char_p, _sz, ctypes.c_char_p]
     L.fabgpu_csp_p384_pass_stats.argtypes = [_vp, _u64p, ctypes.c_int]
+    L.fabgpu_csp_p384_pass_wide_rows.argtypes = [_vp, _u64p]
+    L.fabgpu_p384_wide_rows.argtypes = [_vp, _u64p]
     L.fabgpu_csp_msp_hash_family.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
     L.fabgpu_csp_msp_hash_family_get.argtypes = [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
     L.fabgpu_idemix_issuer_register.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _u32p]
@@ -674,6 +679,12 @@ class Context:
         if n != len(P384_KEY_TABLE_STATS):
             raise FabgpuError("fabgpu_p384_key_table_stats: %s" % strerror(n))
         return dict(zip(P384_KEY_TABLE_STATS, (int(x) for x in v)))
+
+    def p384_wide_rows(self) -> int:
+        """fabgpu_p384_wide_rows: rows of keyed P-384 launches this context handed to the eight-lanes-per-signature form (FLAG_P384_WIDE)."""
+        v = ctypes.c_uint64(0)
+        _check(self._L.fabgpu_p384_wide_rows(self._h, ctypes.byref(v)), "fabgpu_p384_wide_rows")
+        return int(v.value)
 
     def p384_verify_batch_keyed(self, key_id, e, r, s, want_status=True):
         e, r, s = map(_a8, (e, r, s))
@@ -1054,7 +1065,7 @@ class GPUCSP:
     """The accelerated verbs of bccsp.BCCSP (bccsp/bccsp.go:90-134); everything else the Go provider delegates to bccsp/sw."""
 
     def __init__(self, device: int = -1, devices: Optional[Sequence[int]] = None, flags: int = 0, concurrent_passes: int = 0,
-                 expect_block_bytes: int = 0, expect_tuples: int = 0, retire_evicted_keys: int = 0, hash_sha3: int = 0, p384: int = 0, **switches):
+                 expect_block_bytes: int = 0, expect_tuples: int = 0, retire_evicted_keys: int = 0, hash_sha3: int = 0, p384: int = 0, p384_wide: int = 0, **switches):
         """device: ONE context on that HIP ordinal (fabgpu_csp_new).  devices: one context per entry - an ordinal may repeat; an empty
         list means every visible device - behind ONE provider (fabgpu_csp_new2: what bccsp/factory builds from the `GPU:` section).
         switches: pass_device_walk / pass_stage_min_bytes / pass_device_memo / pass_host_counts / pass_timing / pass_hash_memo (0 default,
@@ -1062,7 +1073,11 @@ class GPUCSP:
         of digests / verdicts handed out that is re-computed on the CPU first; 0, the default: none - poison / poisoned / audit_stats).
         retire_evicted_keys (0, the default: off): an identity the cache evicts gives its device comb table up as well (set_option of the
         same name; key_table_stats).  hash_sha3 (0, the default: off): hash(msg, SHA3_256Opts()) and identities of the SHA3 hash family are
-        served on the device (set_option of the same name)."""
+        served on the device (set_option of the same name).  p384_wide (0, the default: off): FLAG_P384_WIDE on every context, read at
+        construction - keyed P-384 launches of at most 8 192 rows on eight lanes per signature (set_option of the same name switches the
+        living contexts)."""
+        if p384_wide > 0:
+            flags |= FLAG_P384_WIDE
         L = load()
         h = _vp()
         err = ctypes.create_string_buffer(512)
@@ -1219,10 +1234,12 @@ class GPUCSP:
     # ---- ECDSA P-384 identities (option p384): keys are (x, y) integer pairs ----
     def p384_pass_stats(self) -> dict:
         """fabgpu_csp_p384_pass_stats: what the P-384 stage of this provider's block passes has done so far."""
-        v = (ctypes.c_uint64 * len(P384_PASS_STATS))()
-        n = self._L.fabgpu_csp_p384_pass_stats(self._h, v, len(P384_PASS_STATS))
-        if n != len(P384_PASS_STATS):
+        k = len(P384_PASS_STATS) - 1                         # (the C call's eight; "wide_rows" has a call of its own)
+        v = (ctypes.c_uint64 * (k + 1))()
+        n = self._L.fabgpu_csp_p384_pass_stats(self._h, v, k)
+        if n != k:
             raise FabgpuError("fabgpu_csp_p384_pass_stats: %s" % strerror(n))
+        _check(self._L.fabgpu_csp_p384_pass_wide_rows(self._h, ctypes.cast(ctypes.byref(v, 8 * k), _u64p)), "fabgpu_csp_p384_pass_wide_rows")
         return dict(zip(P384_PASS_STATS, (int(x) for x in v)))
 
     def msp_hash_family(self, mspid: str, family: str) -> None:

@@ -77,6 +77,9 @@ type GPUOpts struct {
 	// P384: Verify on an ECDSA P-384 key asks the device first (fabgpu_bccsp.h option "p384", fabgpu_csp_verify_coalesced_p384) and takes
 	// only "valid" from it.  Default false: P-384 keys stay with bccsp/sw.  The block pass leaves P-384 endorsers to bccsp/sw either way.
 	P384 bool `mapstructure:"p384" json:"p384,omitempty" yaml:"P384,omitempty"`
+	// P384Wide: registered P-384 keys are verified with eight lanes per signature in launches of at most 8 192 rows (fabgpu.h
+	// FABGPU_FLAG_P384_WIDE, fabgpu_bccsp.h option "p384_wide").  Default false.  Verdicts do not depend on it; it needs P384.
+	P384Wide bool `mapstructure:"p384wide" json:"p384wide,omitempty" yaml:"P384Wide,omitempty"`
 }
 
 // DefaultAuditPermille is what GPUOpts.AuditPermille means when the `GPU:` section does not set it.
@@ -114,6 +117,7 @@ func (f *GPUFactory) Get(config *FactoryOpts) (bccsp.BCCSP, error) {
 			ExpectTuples: g.ExpectTuples, MemoBlocks: g.MemoBlocks, HostWalk: g.HostWalk, PassTiming: g.PassTiming,
 			NoHashMemo: g.NoHashMemo, HashMemoBlocks: g.HashMemoBlocks, KeyTables16: g.KeyTables16, AuditPermille: DefaultAuditPermille, RetireEvictedKeys: true, SHA3: true}
 		opts.P384 = g.P384
+		opts.P384Wide = g.P384Wide
 		if g.SHA3 != nil {
 			opts.SHA3 = *g.SHA3
 		}

@@ -158,6 +158,9 @@ type Options struct {
 	// the transaction's flag says so, and a memo-seeding pass remembers their verdicts in a memo of their own: Verify below asks
 	// fabgpu_csp_memo_lookup_p384 first and the coalesced entry only on a miss.  bccsp.Hash of their messages stays bccsp/sw's.
 	P384 bool
+	// P384Wide: FABGPU_FLAG_P384_WIDE on every context - keyed P-384 launches of at most 8 192 rows run with eight lanes per signature
+	// (a 1 000-transaction P-384 block is 4 000 rows: a sixteenth of what fills the chip one signature per lane).  False by default.
+	P384Wide bool
 }
 
 // SetCoalesce switches the coalesced device path for memo misses on or off (GPUOpts.CoalesceVerify in gpufactory.go).
@@ -244,6 +247,9 @@ func New(swCSP bccsp.BCCSP, opts Options) (bccsp.BCCSP, error) {
 	o.expect_tuples = C.uint32_t(opts.ExpectTuples)
 	if opts.KeyTables16 {
 		o.ctx_flags |= 256 // fabgpu.h FABGPU_FLAG_KEY_TABLES_16BIT
+	}
+	if opts.P384Wide {
+		o.ctx_flags |= 4096 // fabgpu.h FABGPU_FLAG_P384_WIDE
 	}
 	if opts.HostWalk {
 		o.pass_device_walk = -1

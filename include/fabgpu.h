@@ -89,6 +89,11 @@ typedef struct fabgpu_ctx fabgpu_ctx;
                                             u2*Q in 16 mixed additions instead of 32; any other wavefront uses the 8-bit combs as before.
                                             For a peer whose channels have a few dozen signers (msp/cache/cache.go:14-18) */
 
+#define FABGPU_FLAG_P384_WIDE 4096u   /* registered P-384 keys: keyed launches of at most 8 192 rows run with eight lanes per signature in two
+                                        launches (the inverse and the scalars on one lane, the 96 table additions as eight partial sums and a
+                                        tree) instead of one signature per lane.  Off by default.  The context allocates the scratch between
+                                        the two launches (8 192 x 100 bytes) at fabgpu_init.  Statuses and verdict words do not change */
+
 typedef struct fabgpu_cfg {
     int32_t device;      /* HIP device ordinal; -1 = the current device */
     uint32_t max_batch;  /* staging pre-allocation hint in tuples (0 = grow on demand) */
@@ -246,7 +251,12 @@ int fabgpu_sha3_256_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void*
  * fabgpu_p384_key_table_stats: out[0 .. min(cap, FABGPU_P384_KEY_TABLE_STATS)): live keys, slots draining, registrations that reused
  * a slot, slots parked for good, keyed P-384 launches queued so far, bytes of device memory the tables hold (the generator's
  * included), slots ever used.  Returns FABGPU_P384_KEY_TABLE_STATS.
+ * FABGPU_FLAG_P384_WIDE: every keyed P-384 launch of at most 8 192 rows - the three direct entry points below, their _dev twins, the
+ * keyed branch of fabgpu_identity_verify_batch_p384[_sha3][_dev] - takes the eight-lanes-per-signature form; larger launches, and every
+ * launch of a context without the flag, are the one-lane kernel's.  fabgpu_p384_wide_rows: *rows = the rows this context has handed to
+ * the eight-lane form so far.
  * NOT served for P-384: 16-bit tables, the memos, fabgpu_multi_*. */
+int fabgpu_p384_wide_rows(fabgpu_ctx* ctx, uint64_t* rows);
 int fabgpu_p384_key_register(fabgpu_ctx* ctx, const uint8_t* qx48, const uint8_t* qy48, uint32_t* key_id);
 /* The same key on n contexts, each building its own table; contexts fed the same sequence of calls hand out the same ids.
  * key_ids[g] = the key's id on ctxs[g].  The first failure is returned (contexts before it keep the key). */

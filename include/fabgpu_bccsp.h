@@ -86,6 +86,10 @@ int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pa
  * pass with FABGPU_PASS_SEED_MEMO also remembers their verdicts, in a memo of their own (fabgpu_csp_memo_lookup_p384 below).  NOT
  * served either way: the digest memo for P-384 tuples - fabgpu_csp_hash_lookup misses for their messages and the validators hash
  * them on the CPU; that SHA-256 is the digest the verdict entries are keyed on.
+ * "p384_wide" (default off; > 0 on): FABGPU_FLAG_P384_WIDE on every context of the pool - keyed P-384 launches of at most 8 192 rows run
+ * with eight lanes per signature (fabgpu.h).  It is a context flag: a provider reads it at construction from ctx_flags; set on a living
+ * provider, it switches every context for the launches queued from then on (and makes their scratch in that call).  Verdicts, statuses
+ * and flags do not depend on it.
  * FABGPU_EINVAL: no such option. */
 int fabgpu_csp_set_option(fabgpu_csp* csp, const char* name, int64_t value, int64_t* previous);
 int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value);
@@ -370,6 +374,10 @@ int fabgpu_identity_to_p384(const uint8_t* ident, size_t len, uint8_t* qxy96);
  * messages stays on the CPU), the P-256 tuples of a SHA3 MSP (hashed with SHA-256 by the routes, answered "not valid", decided in
  * bccsp/sw), fabgpu_multi_*, P-384 keys earning a table by hit count. */
 int fabgpu_csp_p384_pass_stats(fabgpu_csp* csp, uint64_t* out, int cap);
+/* A ninth value of the stage, read by a call of its own so that fabgpu_csp_p384_pass_stats keeps answering eight: *rows = the tuples of
+ * its keyed batches that the eight-lanes-per-signature form verified (the "p384_wide" option; a part of [2]; 0 with the option off, and
+ * for every fresh-key batch). */
+int fabgpu_csp_p384_pass_wide_rows(fabgpu_csp* csp, uint64_t* rows);
 /* The hash family of an MSP, as the block pass knows it: what the MSP's setup read from its config's SignatureHashFamily
  * (msp/identities.go:216-224).  family: "SHA2" or "SHA3"; anything else answers 1 with identity.getHashOpt's text in err ("hash familiy
  * not recognized [..]"), and "SHA3" while the hash_sha3 option is off answers 1 with the text that bccsp/sw serves it; an empty mspid or

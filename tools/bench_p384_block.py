@@ -126,8 +126,50 @@ def sha3_mode():
     print(json.dumps(res))
 
 
+def wide_mode():
+    """--wide: the 1 000-transaction P-384 block of (a), every signer imported, through ONE provider with the option p384_wide switched
+    between the passes of a round (who goes first alternates): the keyed batch of 4 000 rows on eight lanes per signature against the
+    one-lane keyed kernel.  Written to profiles/p384_block_pass_wide.json."""
+    rnd = random.Random(384100)
+    signers = pb.signers(6, 384100)
+    distinct = [pb.endorser_tx(rnd, signers[t % 2], rnd.sample(signers[2:], 3), ext_bytes=990) for t in range(16)]
+    blk = bb.block(1, [distinct[t % 16][0] for t in range(N_TX)])
+    csp = fabgpu.GPUCSP(devices=[0], p384=1, p384_wide=1)
+    for sg in signers:
+        csp.key_import_p384(sg.q)
+    for on in (1, 0):                                               # both forms once, checked in full
+        csp.set_option("p384_wide", on)
+        first = fabgpu.preverify_block2(csp, blk, block_seq=1)
+        assert (first["tx_flags"] == 0).all() and (first["tuple_status"] == 0).all() and len(first["tuple_status"]) == 4 * N_TX
+    t_end = time.time() + 2.0
+    while time.time() < t_end:
+        timed(csp, blk, 2)
+    per = {"wide": [], "one_lane": []}
+    s0 = csp.p384_pass_stats()
+    for i in range(2 * ROUNDS):
+        for name in (("one_lane", "wide") if i % 2 == 0 else ("wide", "one_lane")):
+            csp.set_option("p384_wide", 1 if name == "wide" else 0)
+            ms, o = timed(csp, blk, 10 + i)
+            assert (o["tx_flags"] == 0).all()
+            per[name].append(ms)
+    s1 = csp.p384_pass_stats()
+    assert s1["keyed_launches"] - s0["keyed_launches"] == 4 * ROUNDS and s1["wide_rows"] - s0["wide_rows"] == 2 * ROUNDS * 4 * N_TX
+    res = {"rounds": 2 * ROUNDS, "tx": N_TX, "p384_tuples": 4 * N_TX, "block_bytes": len(blk), "pass_keyed_wide": summary(per["wide"]),
+           "pass_keyed_one_lane": summary(per["one_lane"]), "stage_stats": s1}
+    res["one_lane_minus_wide_median_ms"] = statistics.median(per["one_lane"]) - statistics.median(per["wide"])
+    csp.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "p384_block_pass_wide.json"), "w") as fh:
+        json.dump(res, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
 if "--sha3" in sys.argv[1:]:
     sha3_mode()
+    sys.exit(0)
+if "--wide" in sys.argv[1:]:
+    wide_mode()
     sys.exit(0)
 
 out = {"rounds": ROUNDS}
