@@ -24,6 +24,7 @@
 #include "kernels.h"
 #include "key_slots.h"
 #include "block_walk_dev.h"
+#include "described_plan.h"
 #include "walk_layout.h"
 #include "worker_pool.h"
 #include "bn_tables29.h"
@@ -1512,23 +1513,18 @@ int fabgpu_sha256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const v
 // ---- host-pointer entry points (what the cgo provider binds) -----------------------------------------
 // copy the span of the arena the offsets reference; returns rebased offsets in ctx->offs.h
 static int stage_messages(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, size_t* arena_bytes_out) {
-    uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (off[i + 1] < off[i]) return FABGPU_EINVAL;
-        if (off[i] < lo) lo = off[i];
-        if (off[i + 1] > hi) hi = off[i + 1];
-    }
-    if (n == 0) { lo = hi = 0; }
-    size_t span = hi >= lo ? (size_t)hi - lo : 0;
+    DescribedPlan p(DescribedPlan::OWN_BUFFER, false, nullptr, 0, 0);
+    p.see_rows(off, n, false);
+    if (p.close()) return p.rc;
+    const size_t span = p.span(), ab = round_up(span, 4) + 64;
     int rc;
-    if ((rc = ctx->arena.ensure(round_up(span, 4) + 128)) || (rc = ctx->offs.ensure((n + 1) * 4))) return rc;
-    if (span) memcpy(ctx->arena.h, arena + lo, span);
-    memset((uint8_t*)ctx->arena.h + span, 0, round_up(span, 4) + 64 - span);
-    uint32_t* ho = (uint32_t*)ctx->offs.h;
-    for (size_t i = 0; i <= n; i++) ho[i] = off[i] - lo;
-    hipError_t err = hipMemcpyAsync(ctx->arena.d, ctx->arena.h, round_up(span, 4) + 64, hipMemcpyHostToDevice, ctx->stream);
+    if ((rc = ctx->arena.ensure(ab + 64)) || (rc = ctx->offs.ensure((n + 1) * 4))) return rc;
+    if (span) memcpy(ctx->arena.h, arena + p.lo, span);
+    memset((uint8_t*)ctx->arena.h + span, 0, ab - span);
+    p.rebase((uint32_t*)ctx->offs.h, off, n + 1, false);
+    hipError_t err = hipMemcpyAsync(ctx->arena.d, ctx->arena.h, ab, hipMemcpyHostToDevice, ctx->stream);
     if (err == hipSuccess) err = hipMemcpyAsync(ctx->offs.d, ctx->offs.h, (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
-    *arena_bytes_out = round_up(span, 4) + 64;
+    *arena_bytes_out = ab;
     return hip_to_rc(err);
 }
 
@@ -1550,6 +1546,7 @@ struct HostStage {
     HostStage(fabgpu_ctx* c, size_t rows, bool digests = false, size_t field_bytes = 32)   // field_bytes: 32, or 48 for the P-384 calls
         : ctx(c), n(rows), fb(rows * field_bytes), words((rows + 63) / 64), st_off(round_up(words * 8, 64)), out_bytes(digests ? n * 32 : st_off + n) {}
     int room(Buf& b, size_t bytes) const { return ctx->fault == 2 ? FABGPU_ENOMEM : b.ensure(bytes); }   // FABGPU_FAULT_INJECT=oom: no staging either
+    int room(DevBuf& b, size_t bytes) const { return ctx->fault == 2 ? FABGPU_ENOMEM : b.ensure(bytes); }
     void messages(const uint8_t* arena, const uint32_t* off) {
         if (rc == FABGPU_OK) rc = stage_messages(ctx, n, arena, off, &ab);
     }
@@ -1589,11 +1586,17 @@ struct HostStage {
     void* dout() const { return ctx->out.d; }
     void* dstatus(const uint8_t* status) const { return status ? (uint8_t*)ctx->out.d + st_off : nullptr; }
     // the first `bytes` of ctx->out to the host behind everything queued, and the wait for it
-    int fetch(size_t bytes) {
-        hipError_t err = rc == FABGPU_OK ? hipMemcpyAsync(ctx->out.h, ctx->out.d, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+    void download(size_t bytes) {
+        if (rc == FABGPU_OK) rc = hip_to_rc(hipMemcpyAsync(ctx->out.h, ctx->out.d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    int drain() {
         const hipError_t drained = hipStreamSynchronize(ctx->stream);
-        if (rc == FABGPU_OK) rc = hip_to_rc(err != hipSuccess ? err : drained);
+        if (rc == FABGPU_OK) rc = hip_to_rc(drained);
         return rc;
+    }
+    int fetch(size_t bytes) {
+        download(bytes);
+        return drain();
     }
     int fetch_verdicts(uint64_t* verdict_bits, uint8_t* status) {
         if (fetch(status ? st_off + n : words * 8)) return rc;
@@ -2613,6 +2616,117 @@ static int arena_stage_impl(fabgpu_ctx* ctx, const void* arena, size_t len, uint
     return FABGPU_OK;
 }
 
+// What a DESCRIBED batch stages on top of HostStage (fabgpu_identity_verify_batch and the P-384 entries): the staged upload it may name, the
+// bytes of the caller's arena its plan references (described_plan.h), the rebased offsets in ctx->offs, pre_off | pre_idx | mid-state
+// room in ctx->pre, and ctx->out as verdict words | status bytes | digest rows.  Every step from the first upload on is skipped once
+// rc is set, and the entry leaves through drain(): HostStage's failure rule, with ctx->stream2 drained too where it carries work (side).
+struct DescribedStage : HostStage {
+    const uint32_t m;                    // prefixes
+    const bool spans;
+    const size_t noff, npre;             // u32 values of off and of pre_off
+    const size_t ib, pob, dg_off;        // bytes of n u32 padded to 64; of pre_off likewise; where the digest rows start in ctx->out
+    fabgpu_ctx::Staged* sl = nullptr;    // the staged upload, or nullptr: the arena is the caller's
+    std::unique_lock<std::mutex> slk;    // its slot stays locked - the stager kept out of it - until this batch has run
+    bool side = false;                   // ctx->stream2 carries work of this call
+
+    DescribedStage(fabgpu_ctx* c, size_t rows, size_t field_bytes, uint32_t prefixes, bool pairs)
+        : HostStage(c, rows, false, field_bytes), m(prefixes), spans(pairs), noff(pairs ? 2 * rows : rows + 1),
+          npre(prefixes ? (pairs ? 2 * (size_t)prefixes : (size_t)prefixes + 1) : 0), ib(round_up(rows * 4, 64)),
+          pob(round_up((npre + 1) * 4, 64)), dg_off(round_up(st_off + rows, 64)) {}
+    // FABGPU_IDB_ARENA_STAGED, before ctx->mu is taken: find the upload and lock its slot
+    int slot(uint64_t token) {
+        rc = FABGPU_EINVAL;
+        if (token == 0) return rc;
+        for (auto& c : ctx->staged_slots)
+            if (c.token.load() == token) sl = &c;
+        if (!sl) return rc;                                                                     // replaced meanwhile
+        slk = std::unique_lock<std::mutex>(sl->m);
+        if (sl->token.load() == token && sl->len != 0) rc = FABGPU_OK;                          // ... or just now
+        return rc;
+    }
+    // the closed plan against what holds the arena
+    int bind(DescribedPlan& p, const uint8_t* arena) {
+        if (sl) {
+            if (p.hi > sl->len) return rc = FABGPU_EINVAL;
+            p.absolute();
+        } else if (p.span() && !arena) {
+            return rc = FABGPU_EINVAL;
+        }
+        return FABGPU_OK;
+    }
+    // small arenas go through the pinned staging buffer; big ones (a marshalled block) are handed to the driver directly - one copy less
+    // on the host, the slack the kernels may touch zeroed on the device
+    bool direct(const DescribedPlan& p) const { return !sl && p.span() >= ((size_t)4 << 20); }
+    int rooms(size_t arena_room, size_t mid_bytes, size_t tail_room, size_t out_room) {
+        if ((!sl && (rc = room(ctx->arena, arena_room))) || (rc = room(ctx->offs, noff * 4)) || (m && (rc = room(ctx->pre, pob + ib + (size_t)m * mid_bytes + 64))) ||
+            (tail_room && (rc = room(ctx->tailbuf, tail_room))))
+            return rc;
+        return rc = room(ctx->out, out_room);
+    }
+    // the referenced bytes of the caller's arena and zeros up to ab; tail_in_arena (or nullptr): the tail, laid at tail_base into the
+    // pinned copy - a direct upload leaves it to upload_tail.  A staged upload is already there.
+    void upload_arena(const DescribedPlan& p, const uint8_t* arena, size_t ab, const void* tail_in_arena) {
+        if (rc != FABGPU_OK || sl) return;
+        const size_t span = p.span();
+        hipError_t err;
+        if (direct(p)) {
+            err = hipMemcpyAsync(ctx->arena.d, arena + p.lo, span, hipMemcpyHostToDevice, ctx->stream);
+            if (err == hipSuccess) err = hipMemsetAsync((uint8_t*)ctx->arena.d + span, 0, ab - span, ctx->stream);
+        } else {
+            if (span) memcpy(ctx->arena.h, arena + p.lo, span);
+            memset((uint8_t*)ctx->arena.h + span, 0, ab - span);
+            if (tail_in_arena) memcpy((uint8_t*)ctx->arena.h + (p.tail_base - p.lo), tail_in_arena, p.tail_len);
+            err = hipMemcpyAsync(ctx->arena.d, ctx->arena.h, ab, hipMemcpyHostToDevice, ctx->stream);
+        }
+        rc = hip_to_rc(err);
+    }
+    // the tail through its own pinned staging: its bytes and zeros up to `bytes`, to dst
+    void upload_tail(const DescribedPlan& p, const void* tail, void* dst, size_t bytes) {
+        if (rc != FABGPU_OK) return;
+        memcpy(ctx->tailbuf.h, tail, p.tail_len);
+        memset((uint8_t*)ctx->tailbuf.h + p.tail_len, 0, bytes - p.tail_len);
+        rc = hip_to_rc(hipMemcpyAsync(dst, ctx->tailbuf.h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    void upload_offsets(const DescribedPlan& p, const uint32_t* off, const uint32_t* pre_off, const uint32_t* pre_idx) {
+        if (rc != FABGPU_OK) return;
+        p.rebase((uint32_t*)ctx->offs.h, off, noff, spans);
+        hipError_t err = hipMemcpyAsync(ctx->offs.d, ctx->offs.h, noff * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (m) {
+            p.rebase((uint32_t*)ctx->pre.h, pre_off, npre, spans);
+            memcpy((uint8_t*)ctx->pre.h + pob, pre_idx, n * 4);
+            if (err == hipSuccess) err = hipMemcpyAsync(ctx->pre.d, ctx->pre.h, pob + ib, hipMemcpyHostToDevice, ctx->stream);
+        }
+        rc = hip_to_rc(err);
+    }
+    void* mid() const { return m ? (uint8_t*)ctx->pre.d + pob + ib : nullptr; }
+    // the device-side batch: what was staged here (fields() has run); arena, tail, flags and digests are the entry's
+    template <class Batch> void describe(Batch& d, bool keyed, bool want_status) const {
+        d.off = (const uint32_t*)ctx->offs.d;
+        d.n_prefixes = m;
+        d.pre_off = m ? (const uint32_t*)ctx->pre.d : nullptr;
+        d.pre_idx = m ? (const uint32_t*)((uint8_t*)ctx->pre.d + pob) : nullptr;
+        d.key_id = keyed ? (const uint32_t*)ids() : nullptr;
+        d.qx = keyed ? nullptr : field(0);
+        d.qy = keyed ? nullptr : field(1);
+        d.r = field(keyed ? 0 : 2);
+        d.s = field(keyed ? 1 : 3);
+        d.verdict_bits = ctx->out.d;
+        d.status = want_status ? (uint8_t*)ctx->out.d + st_off : nullptr;
+    }
+    void download_results(const void* status, const void* digests) { download(digests ? dg_off + n * 32 : (status ? st_off + n : words * 8)); }
+    int drain() {
+        HostStage::drain();
+        const hipError_t drained = side ? hipStreamSynchronize(ctx->stream2) : hipSuccess;
+        if (rc == FABGPU_OK) rc = hip_to_rc(drained);
+        return rc;
+    }
+    void copy_out(void* verdict_bits, void* status, void* digests) const {
+        memcpy(verdict_bits, ctx->out.h, words * 8);
+        if (status) memcpy(status, (uint8_t*)ctx->out.h + st_off, n);
+        if (digests) memcpy(digests, (uint8_t*)ctx->out.h + dg_off, n * 32);
+    }
+};
+
 extern "C" {
 
 int fabgpu_identity_verify_batch(fabgpu_ctx* ctx, const fabgpu_identity_batch* b) {
@@ -2631,253 +2745,89 @@ int fabgpu_identity_verify_batch(fabgpu_ctx* ctx, const fabgpu_identity_batch* b
     const size_t nn = b->n_nym;            // pseudonym signatures over the same arena, on the second stream
     if (nn && (!spans || !b->nym_off || !b->nym_issuer || !b->nym_fields || !b->nym_verdict_bits)) return FABGPU_EINVAL;
     if (nn > 0x7FFFFFF0ull / 200) return FABGPU_ETOOBIG;
-    // a staged arena: its slot stays locked - the stager kept out of it - until this batch has run
-    fabgpu_ctx::Staged* sl = nullptr;
-    std::unique_lock<std::mutex> slk;
-    if (staged) {
-        if (b->stage_token == 0) return FABGPU_EINVAL;
-        for (auto& c : ctx->staged_slots)
-            if (c.token.load() == b->stage_token) sl = &c;
-        if (!sl) return FABGPU_EINVAL;                                                          // replaced meanwhile
-        slk = std::unique_lock<std::mutex>(sl->m);
-        if (sl->token.load() != b->stage_token || sl->len == 0) return FABGPU_EINVAL;           // ... or just now
-    }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    DeviceGuard g(ctx->device);
-    // the span of the arena that messages and prefixes reference; spans at or beyond tail_base address the tail
-    const size_t noff = spans ? 2 * n : n + 1, npre = m ? (spans ? 2 * (size_t)m : (size_t)m + 1) : 0;
-    const bool has_tail = b->tail != nullptr && b->tail_len != 0;
-    const uint32_t tbase = has_tail ? b->tail_base : 0xFFFFFFFFu;
-    if (has_tail && ((tbase & 63u) || !spans || (uint64_t)tbase + b->tail_len > 0xFFFFFFF0ull)) return FABGPU_EINVAL;
-    uint32_t lo = 0xFFFFFFFFu, hi = 0;      // of the caller's arena
-    bool tail_used = false, bad = false;
-    auto see = [&](uint32_t s0, uint32_t s1) {
-        if (s1 < s0) { bad = true; return; }
-        if (s1 == s0) return;
-        if (s0 >= tbase) {
-            if ((uint64_t)s1 > (uint64_t)tbase + b->tail_len) bad = true;
-            tail_used = true;
-            return;
-        }
-        if (s1 > tbase) { bad = true; return; }            // straddles
-        if (s0 < lo) lo = s0;
-        if (s1 > hi) hi = s1;
-    };
-    for (size_t i = 0; i < n; i++) {
-        uint32_t s0 = b->off[spans ? 2 * i : i], s1 = b->off[spans ? 2 * i + 1 : i + 1];
-        if (!spans) {                                      // consecutive messages: empty ones still bound the span
-            if (s1 < s0) return FABGPU_EINVAL;
-            if (s0 < lo) lo = s0;
-            if (s1 > hi) hi = s1;
-        } else {
-            see(s0, s1);
-        }
-    }
-    for (size_t i = 0; i < nn; i++) see(b->nym_off[2 * i], b->nym_off[2 * i + 1]);
-    for (uint32_t p = 0; p < m; p++) {
-        uint32_t s0 = b->pre_off[spans ? 2 * p : p], s1 = b->pre_off[spans ? 2 * p + 1 : p + 1];
-        if (!spans) {
-            if (s1 < s0) return FABGPU_EINVAL;
-            if (s0 < lo) lo = s0;
-            if (s1 > hi) hi = s1;
-        } else {
-            see(s0, s1);
-        }
-    }
     const uint32_t ng = b->n_gather;
     if (ng && (!b->gather_spans || !b->gather_digests)) return FABGPU_EINVAL;
-    uint64_t gtotal = 0;
-    for (size_t j = 0; j < (size_t)ng * 3; j++) {
-        uint32_t s0 = b->gather_spans[2 * j], s1 = b->gather_spans[2 * j + 1];
-        if (s1 < s0) return FABGPU_EINVAL;
-        if (s1 == s0) continue;
-        if (s1 > tbase) return FABGPU_EINVAL;              // gathered pieces come from the caller's arena only
-        if (s0 < lo) lo = s0;
-        if (s1 > hi) hi = s1;
-        gtotal += s1 - s0;
-    }
-    if (bad) return FABGPU_EINVAL;
-    if (gtotal > 0x7FFFFFF0ull) return FABGPU_ETOOBIG;
-    if (lo == 0xFFFFFFFFu) lo = hi = 0;                    // nothing references the caller's arena
-    if (spans && tail_used) lo = 0;                        // keeps tail_base an absolute offset of the device arena
-    size_t span = hi >= lo ? (size_t)hi - lo : 0;          // bytes taken from the caller's arena
-    if (staged) {
-        if (hi > sl->len) return FABGPU_EINVAL;
-        if (tail_used && ((size_t)tbase < round_up(sl->len, 64) || (size_t)tbase + b->tail_len + 128 > sl->cap)) return FABGPU_EINVAL;
-        lo = 0;                                           // offsets are offsets into the staged bytes
-        span = sl->len;
-    } else if (span && !arena) {
-        return FABGPU_EINVAL;
-    }
+    DescribedStage h(ctx, n, 32, m, spans);
+    if (staged && h.slot(b->stage_token)) return h.rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    // the tail is written into the device arena at tail_base
+    DescribedPlan p(DescribedPlan::IN_ARENA, spans, b->tail, b->tail_base, b->tail_len);
+    p.see_rows(b->off, n, true);
+    p.see_rows(b->nym_off, nn, true);
+    p.see_rows(b->pre_off, m, false);                      // prefixes never lie in the tail
+    p.see_gather(b->gather_spans, (size_t)ng * 3);
+    if (p.close() || h.bind(p, arena)) return p.rc ? p.rc : h.rc;
+    const size_t tbase = p.tail_base, tlen = p.tail_len;
+    if (staged && p.tail_used && (tbase < round_up(h.sl->len, 64) || tbase + tlen + 128 > h.sl->cap)) return FABGPU_EINVAL;
     // extent of the device arena: the caller's bytes, then (if used) zero padding up to tail_base and the tail
-    const size_t extent = tail_used ? (size_t)tbase - lo + b->tail_len : span;
-    const size_t fb = n * 32, ib = round_up(n * 4, 64), pob = round_up((npre + 1) * 4, 64), words = (n + 63) / 64;
-    const size_t st_off = round_up(words * 8, 64), ab = round_up(extent, 4) + 64;
-    const size_t dg_off = round_up(st_off + n, 64);        // out buffer: verdict words | status bytes | digests
-    int rc;
-    if ((!staged && (rc = ctx->arena.ensure(ab + 64))) || (rc = ctx->offs.ensure(noff * 4)) || (rc = ctx->fields.ensure(4 * fb + ib)) ||
-        (rc = ctx->out.ensure(dg_off + (b->digests ? fb : 0))) || (rc = ctx->pre.ensure(pob + ib + (size_t)m * mid_bytes + 64)))
-        return rc;
-    // small arenas go through the pinned staging buffer; big ones (a marshalled block) are handed to the driver directly -
-    // one copy less on the host (the tail padding the kernels may touch is zeroed on the device)
-    const bool direct = span >= ((size_t)4 << 20);
-    if (!staged && !direct) {
-        if (span) memcpy(ctx->arena.h, arena + lo, span);
-        memset((uint8_t*)ctx->arena.h + span, 0, ab - span);
-        if (tail_used) memcpy((uint8_t*)ctx->arena.h + (tbase - lo), b->tail, b->tail_len);
+    const size_t held = staged ? h.sl->len : p.span(), extent = p.tail_used ? tbase - p.lo + tlen : held, ab = round_up(extent, 4) + 64;
+    const bool apart = p.tail_used && (staged || h.direct(p));   // the tail travels through its own pinned staging
+    const size_t gsb = round_up((size_t)ng * 24, 64), gob = round_up(((size_t)ng + 1) * 4, 64), gscr = round_up((size_t)p.gather_total, 4) + 64;
+    const size_t nkb = round_up(nn * 4, 64), nfb = nn * 32, nwords = (nn + 63) / 64, nst_off = round_up(nwords * 8, 64);
+    if (h.rooms(ab + 64, mid_bytes, apart ? tlen : 0, h.dg_off + (b->digests ? h.fb : 0)) ||
+        (ng && ((h.rc = h.room(ctx->gath, gsb + gob + (size_t)ng * 32)) || (h.rc = h.room(ctx->gscr, gscr)))) ||
+        (nn && ((h.rc = h.room(ctx->nym, nkb + 6 * nfb + nn * 8)) || (h.rc = h.room(ctx->nymout, nst_off + nn)))))
+        return h.rc;
+    h.side = nn != 0;
+    uint8_t* darena = (uint8_t*)(staged ? h.sl->d : ctx->arena.d);
+    h.upload_arena(p, arena, ab, p.tail_used ? b->tail : nullptr);
+    if (apart) {                                           // a staged upload gets 128 zero bytes behind the tail
+        h.upload_tail(p, b->tail, darena + (tbase - p.lo), tlen);
+        if (staged && h.rc == FABGPU_OK) h.rc = hip_to_rc(hipMemsetAsync(darena + tbase + tlen, 0, 128, ctx->stream));
     }
-    if (tail_used && (staged || direct)) {                 // the tail travels through its own pinned staging
-        if ((rc = ctx->tailbuf.ensure(b->tail_len))) return rc;
-        memcpy(ctx->tailbuf.h, b->tail, b->tail_len);
-    }
-    uint32_t* ho = (uint32_t*)ctx->offs.h;
-    if (spans) {
-        for (size_t i = 0; i < n; i++) {                   // an empty span carries no address
-            const uint32_t s0 = b->off[2 * i], s1 = b->off[2 * i + 1];
-            ho[2 * i] = s1 > s0 ? s0 - lo : 0;
-            ho[2 * i + 1] = s1 > s0 ? s1 - lo : 0;
-        }
-    } else {
-        for (size_t i = 0; i < noff; i++) ho[i] = b->off[i] - lo;
-    }
-    uint8_t* ph = (uint8_t*)ctx->pre.h;
-    if (m) {
-        uint32_t* po = (uint32_t*)ph;
-        if (spans) {
-            for (uint32_t p = 0; p < m; p++) {
-                const uint32_t s0 = b->pre_off[2 * p], s1 = b->pre_off[2 * p + 1];
-                po[2 * p] = s1 > s0 ? s0 - lo : 0;
-                po[2 * p + 1] = s1 > s0 ? s1 - lo : 0;
-            }
-        } else {
-            for (size_t p = 0; p < npre; p++) po[p] = b->pre_off[p] - lo;
-        }
-        memcpy(ph + pob, b->pre_idx, n * 4);
-    }
-    uint8_t* fh = (uint8_t*)ctx->fields.h;
-    if (keyed) {
-        memcpy(fh, b->key_id, n * 4);
-        memcpy(fh + ib, b->r, fb); memcpy(fh + ib + fb, b->s, fb);
-    } else {
-        memcpy(fh, b->qx, fb); memcpy(fh + fb, b->qy, fb); memcpy(fh + 2 * fb, b->r, fb); memcpy(fh + 3 * fb, b->s, fb);
-    }
-    hipError_t err;
-    if (staged) {
-        err = hipSuccess;                                 // fabgpu_arena_stage put the bytes (and their zero tail) there
-        if (tail_used) {
-            err = hipMemcpyAsync((uint8_t*)sl->d + tbase, ctx->tailbuf.h, b->tail_len, hipMemcpyHostToDevice, ctx->stream);
-            if (err == hipSuccess) err = hipMemsetAsync((uint8_t*)sl->d + tbase + b->tail_len, 0, 128, ctx->stream);
-        }
-    } else if (direct) {
-        err = hipMemcpyAsync(ctx->arena.d, arena + lo, span, hipMemcpyHostToDevice, ctx->stream);
-        if (err == hipSuccess) err = hipMemsetAsync((uint8_t*)ctx->arena.d + span, 0, ab - span, ctx->stream);
-        if (err == hipSuccess && tail_used)
-            err = hipMemcpyAsync((uint8_t*)ctx->arena.d + (tbase - lo), ctx->tailbuf.h, b->tail_len, hipMemcpyHostToDevice, ctx->stream);
-    } else {
-        err = hipMemcpyAsync(ctx->arena.d, ctx->arena.h, ab, hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (err == hipSuccess) err = hipMemcpyAsync(ctx->offs.d, ctx->offs.h, noff * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (err == hipSuccess && m) err = hipMemcpyAsync(ctx->pre.d, ctx->pre.h, pob + ib, hipMemcpyHostToDevice, ctx->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(ctx->fields.d, ctx->fields.h, keyed ? ib + 2 * fb : 4 * fb, hipMemcpyHostToDevice, ctx->stream);
-    if (err != hipSuccess) return hip_to_rc(err);
-    uint8_t* fd = (uint8_t*)ctx->fields.d;
-    uint8_t* pd = (uint8_t*)ctx->pre.d;
-    uint8_t* dout = (uint8_t*)ctx->out.d;
+    h.upload_offsets(p, b->off, b->pre_off, b->pre_idx);
+    if (keyed) h.fields(ctx->fields, HostStage::ID_COLUMN, b->key_id, {(const uint8_t*)b->r, (const uint8_t*)b->s});
+    else h.fields(ctx->fields, 0, nullptr, {(const uint8_t*)b->qx, (const uint8_t*)b->qy, (const uint8_t*)b->r, (const uint8_t*)b->s});
     fabgpu_identity_batch d = *b;
+    h.describe(d, keyed, b->status != nullptr);
     d.flags = b->flags & (FABGPU_IDB_SPANS | FABGPU_IDB_SHA3_256);
-    d.arena = staged ? sl->d : ctx->arena.d;
-    d.arena_bytes = staged ? round_up(tail_used ? (size_t)tbase + b->tail_len : span, 4) + 64 : ab;
+    d.arena = darena;
+    d.arena_bytes = staged ? round_up(p.tail_used ? tbase + tlen : held, 4) + 64 : ab;
     d.tail = nullptr;
     d.tail_base = d.tail_len = 0;
-    d.off = (const uint32_t*)ctx->offs.d;
-    d.n_prefixes = m;
-    d.pre_off = m ? (const uint32_t*)pd : nullptr;
-    d.pre_idx = m ? (const uint32_t*)(pd + pob) : nullptr;
-    if (keyed) {
-        d.key_id = (const uint32_t*)fd;
-        d.qx = d.qy = nullptr;
-        d.r = fd + ib;
-        d.s = fd + ib + fb;
-    } else {
-        d.qx = fd; d.qy = fd + fb; d.r = fd + 2 * fb; d.s = fd + 3 * fb;
-    }
-    d.verdict_bits = dout;
-    d.status = b->status ? dout + st_off : nullptr;
-    d.digests = b->digests ? dout + dg_off : nullptr;
-    const size_t gsb = round_up((size_t)ng * 24, 64), gob = round_up(((size_t)ng + 1) * 4, 64), gscr = round_up((size_t)gtotal, 4) + 64;
-    if (ng) {
-        if ((rc = ctx->gath.ensure(gsb + gob + (size_t)ng * 32))) return rc;
-        if ((rc = ctx->gscr.ensure(gscr))) return rc;
-        uint32_t* gs = (uint32_t*)ctx->gath.h;
+    d.digests = b->digests ? (uint8_t*)ctx->out.d + h.dg_off : nullptr;
+    uint8_t* gd = (uint8_t*)ctx->gath.d;
+    if (ng && h.rc == FABGPU_OK) {
         uint32_t* go = (uint32_t*)((uint8_t*)ctx->gath.h + gsb);
+        p.rebase((uint32_t*)ctx->gath.h, b->gather_spans, (size_t)ng * 6, true);
         uint32_t run = 0;
         for (uint32_t j = 0; j < ng; j++) {
             go[j] = run;
-            for (int p = 0; p < 3; p++) {
-                uint32_t s0 = b->gather_spans[6 * (size_t)j + 2 * p], s1 = b->gather_spans[6 * (size_t)j + 2 * p + 1];
-                gs[6 * (size_t)j + 2 * p] = s1 > s0 ? s0 - lo : 0;
-                gs[6 * (size_t)j + 2 * p + 1] = s1 > s0 ? s1 - lo : 0;
-                run += s1 - s0;
-            }
+            for (int k = 0; k < 3; k++) run += b->gather_spans[6 * (size_t)j + 2 * k + 1] - b->gather_spans[6 * (size_t)j + 2 * k];
         }
         go[ng] = run;
-        err = hipMemcpyAsync(ctx->gath.d, ctx->gath.h, gsb + gob, hipMemcpyHostToDevice, ctx->stream);
-        if (err != hipSuccess) return hip_to_rc(err);
-        d.gather_spans = (const uint32_t*)ctx->gath.d;
-        d.gather_off = (const uint32_t*)((uint8_t*)ctx->gath.d + gsb);
-        d.gather_digests = (uint8_t*)ctx->gath.d + gsb + gob;
+        h.rc = hip_to_rc(hipMemcpyAsync(gd, ctx->gath.h, gsb + gob, hipMemcpyHostToDevice, ctx->stream));
+        d.gather_spans = (const uint32_t*)gd;
+        d.gather_off = (const uint32_t*)(gd + gsb);
+        d.gather_digests = gd + gsb + gob;
         d.gather_scratch = ctx->gscr.d;
         d.gather_scratch_bytes = gscr;
     }
     // the pseudonym signatures: staged and launched on the second stream BEFORE the ECDSA kernels are queued, so that the two run
     // side by side (a block's idemix creators are a latency-bound launch of their own: bn_quad29.h)
-    const size_t nkb = round_up(nn * 4, 64), nfb = nn * 32, nwords = (nn + 63) / 64, nst_off = round_up(nwords * 8, 64);
-    if (nn) {
-        if ((rc = ctx->nym.ensure(nkb + 6 * nfb + nn * 8)) || (rc = ctx->nymout.ensure(nst_off + nn))) return rc;
+    uint8_t* nd = (uint8_t*)ctx->nym.d;
+    uint8_t* nout = (uint8_t*)ctx->nymout.d;
+    if (nn && h.rc == FABGPU_OK) {
         uint8_t* nh = (uint8_t*)ctx->nym.h;
         memcpy(nh, b->nym_issuer, nn * 4);
         memcpy(nh + nkb, b->nym_fields, 6 * nfb);
-        uint32_t* no = (uint32_t*)(nh + nkb + 6 * nfb);
-        for (size_t i = 0; i < nn; i++) {
-            const uint32_t s0 = b->nym_off[2 * i], s1 = b->nym_off[2 * i + 1];
-            no[2 * i] = s1 > s0 ? s0 - lo : 0;
-            no[2 * i + 1] = s1 > s0 ? s1 - lo : 0;
-        }
-        err = hipEventRecord(ctx->ev_up, ctx->stream);                       // arena (and tail) uploads are queued on `stream`
+        p.rebase((uint32_t*)(nh + nkb + 6 * nfb), b->nym_off, 2 * nn, true);
+        hipError_t err = hipEventRecord(ctx->ev_up, ctx->stream);            // arena (and tail) uploads are queued on `stream`
         if (err == hipSuccess) err = hipStreamWaitEvent(ctx->stream2, ctx->ev_up, 0);
-        if (err == hipSuccess) err = hipMemcpyAsync(ctx->nym.d, ctx->nym.h, nkb + 6 * nfb + nn * 8, hipMemcpyHostToDevice, ctx->stream2);
-        if (err != hipSuccess) return hip_to_rc(err);
-        uint8_t* nd = (uint8_t*)ctx->nym.d;
-        uint8_t* nout = (uint8_t*)ctx->nymout.d;
-        rc = nym_verify_dev(ctx, nn, d.arena, d.arena_bytes, nd + nkb + 6 * nfb, true, nd, nd + nkb, nd + nkb + nfb, nd + nkb + 2 * nfb, nd + nkb + 3 * nfb,
-                            nd + nkb + 4 * nfb, nd + nkb + 5 * nfb, nout, b->nym_status ? nout + nst_off : nullptr, ctx->stream2, false);
-        if (rc) {
-            hipStreamSynchronize(ctx->stream2);
-            return rc;
-        }
-        err = hipMemcpyAsync(ctx->nymout.h, nout, b->nym_status ? nst_off + nn : nwords * 8, hipMemcpyDeviceToHost, ctx->stream2);
-        if (err != hipSuccess) {
-            hipStreamSynchronize(ctx->stream2);
-            return hip_to_rc(err);
-        }
+        if (err == hipSuccess) err = hipMemcpyAsync(nd, nh, nkb + 6 * nfb + nn * 8, hipMemcpyHostToDevice, ctx->stream2);
+        if ((h.rc = hip_to_rc(err)) == FABGPU_OK)
+            h.rc = nym_verify_dev(ctx, nn, d.arena, d.arena_bytes, nd + nkb + 6 * nfb, true, nd, nd + nkb, nd + nkb + nfb, nd + nkb + 2 * nfb, nd + nkb + 3 * nfb,
+                                  nd + nkb + 4 * nfb, nd + nkb + 5 * nfb, nout, b->nym_status ? nout + nst_off : nullptr, ctx->stream2, false);
+        if (h.rc == FABGPU_OK)
+            h.rc = hip_to_rc(hipMemcpyAsync(ctx->nymout.h, nout, b->nym_status ? nst_off + nn : nwords * 8, hipMemcpyDeviceToHost, ctx->stream2));
     }
-    rc = fabgpu_identity_verify_batch_dev(ctx, &d, m ? pd + pob + ib : nullptr, ctx->stream);
-    if (rc) {
-        if (nn) hipStreamSynchronize(ctx->stream2);                         // nothing of this call may still be running when it returns
-        return rc;
-    }
-    err = hipMemcpyAsync(ctx->out.h, dout, b->digests ? dg_off + fb : (b->status ? st_off + n : words * 8), hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess && ng)
-        err = hipMemcpyAsync((uint8_t*)ctx->gath.h + gsb + gob, (uint8_t*)ctx->gath.d + gsb + gob, (size_t)ng * 32, hipMemcpyDeviceToHost, ctx->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-    if (nn) {
-        hipError_t e2 = hipStreamSynchronize(ctx->stream2);
-        if (err == hipSuccess) err = e2;
-    }
-    if (err != hipSuccess) return hip_to_rc(err);
-    memcpy(b->verdict_bits, ctx->out.h, words * 8);
-    if (b->status) memcpy(b->status, (uint8_t*)ctx->out.h + st_off, n);
-    if (b->digests) memcpy(b->digests, (uint8_t*)ctx->out.h + dg_off, fb);
+    if (h.rc == FABGPU_OK) h.rc = fabgpu_identity_verify_batch_dev(ctx, &d, h.mid(), ctx->stream);
+    h.download_results(b->status, b->digests);
+    if (ng && h.rc == FABGPU_OK)
+        h.rc = hip_to_rc(hipMemcpyAsync((uint8_t*)ctx->gath.h + gsb + gob, gd + gsb + gob, (size_t)ng * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (h.drain()) return h.rc;                            // nothing of this call is running any more, nothing was copied out
+    h.copy_out(b->verdict_bits, b->status, b->digests);
     if (ng) memcpy(b->gather_digests, (uint8_t*)ctx->gath.h + gsb + gob, (size_t)ng * 32);
     if (nn) {
         memcpy(b->nym_verdict_bits, ctx->nymout.h, nwords * 8);
@@ -2946,139 +2896,36 @@ static int identity_verify_batch_p384_host(fabgpu_ctx* ctx, const fabgpu_identit
     const bool staged = (b->flags & FABGPU_IDB_ARENA_STAGED) != 0;
     if (b->flags & ~(uint32_t)(FABGPU_IDB_SPANS | FABGPU_IDB_ARENA_STAGED)) return FABGPU_EINVAL;   // (FABGPU_IDB_SHA3_256: the family is the entry's)
     const size_t mid_bytes = sha3 ? SHA3_MID_BYTES_HOST : 32;   // a SHA3-256 mid-state is the whole Keccak state
-    // a staged arena: its slot stays locked - the stager kept out of it - until this batch has run
-    fabgpu_ctx::Staged* sl = nullptr;
-    std::unique_lock<std::mutex> slk;
-    if (staged) {
-        if (b->stage_token == 0) return FABGPU_EINVAL;
-        for (auto& c : ctx->staged_slots)
-            if (c.token.load() == b->stage_token) sl = &c;
-        if (!sl) return FABGPU_EINVAL;                                                          // replaced meanwhile
-        slk = std::unique_lock<std::mutex>(sl->m);
-        if (sl->token.load() != b->stage_token || sl->len == 0) return FABGPU_EINVAL;           // ... or just now
-    }
+    DescribedStage h(ctx, n, 48, m, spans);
+    if (staged && h.slot(b->stage_token)) return h.rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard g(ctx->device);
-    // what the messages and prefixes reference of the caller's arena; spans at or beyond tail_base address the tail, prefixes never do
-    const size_t noff = spans ? 2 * n : n + 1, npre = m ? (spans ? 2 * (size_t)m : (size_t)m + 1) : 0;
-    const bool has_tail = b->tail != nullptr && b->tail_len != 0;
-    const uint32_t tbase = has_tail ? b->tail_base : 0xFFFFFFFFu;
-    if (has_tail && ((tbase & 63u) || !spans || (uint64_t)tbase + b->tail_len > 0xFFFFFFF0ull)) return FABGPU_EINVAL;
-    uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    bool tail_used = false, bad = false;
-    auto see = [&](uint32_t s0, uint32_t s1, bool may_be_tail) {
-        if (s1 < s0) { bad = true; return; }
-        if (s1 == s0) return;
-        if (s0 >= tbase) {
-            if (!may_be_tail || (uint64_t)s1 > (uint64_t)tbase + b->tail_len) bad = true;
-            tail_used = true;
-            return;
-        }
-        if (s1 > tbase) { bad = true; return; }            // straddles
-        if (s0 < lo) lo = s0;
-        if (s1 > hi) hi = s1;
-    };
-    auto see_run = [&](const uint32_t* o, size_t k) {     // consecutive messages: empty ones still bound the span
-        for (size_t i = 0; i < k && !bad; i++) {
-            if (o[i + 1] < o[i]) bad = true;
-            if (o[i] < lo) lo = o[i];
-            if (o[i + 1] > hi) hi = o[i + 1];
-        }
-    };
-    if (spans) {
-        for (size_t i = 0; i < n; i++) see(b->off[2 * i], b->off[2 * i + 1], true);
-        for (uint32_t p = 0; p < m; p++) see(b->pre_off[2 * p], b->pre_off[2 * p + 1], false);
-    } else {
-        see_run(b->off, n);
-        if (m) see_run(b->pre_off, m);
-    }
-    if (bad) return FABGPU_EINVAL;
-    if (lo == 0xFFFFFFFFu) lo = hi = 0;                    // nothing references the caller's arena
-    size_t span = (size_t)hi - lo;                         // bytes taken from the caller's arena
-    if (staged) {
-        if (hi > sl->len) return FABGPU_EINVAL;
-        lo = 0;                                            // offsets are offsets into the staged bytes
-    } else if (span && !arena) {
-        return FABGPU_EINVAL;
-    }
+    DescribedPlan p(DescribedPlan::OWN_BUFFER, spans, b->tail, b->tail_base, b->tail_len);
+    p.see_rows(b->off, n, true);
+    p.see_rows(b->pre_off, m, false);                      // prefixes never lie in the tail
+    if (p.close() || h.bind(p, arena)) return p.rc ? p.rc : h.rc;
     // the device arena: the staged upload as it lies there (fabgpu_arena_stage zeroed its slack up to the next 64 and beyond), or the
     // referenced bytes of the caller's arena; the tail in a buffer of its own either way, so a staged upload is read and never written
-    const size_t ab = staged ? round_up(sl->len, 64) : round_up(span, 4) + 64;
-    const size_t ib = round_up(n * 4, 64), pob = round_up((npre + 1) * 4, 64), tb = round_up((size_t)b->tail_len, 4);
-    HostStage h(ctx, n, false, 48);
-    const size_t dg_off = round_up(h.st_off + n, 64);      // out buffer: verdict words | status bytes | digests
-    if ((!staged && (h.rc = h.room(ctx->arena, ab))) || (h.rc = h.room(ctx->offs, noff * 4)) || (m && (h.rc = h.room(ctx->pre, pob + ib + (size_t)m * mid_bytes + 64))) ||
-        (tail_used && (h.rc = h.room(ctx->tailbuf, tb + 64))))
-        return h.rc;
-    hipError_t err = hipSuccess;
-    if (!staged) {
-        if (span >= ((size_t)4 << 20)) {                   // a marshalled block: handed to the driver directly, one host copy less
-            err = hipMemcpyAsync(ctx->arena.d, arena + lo, span, hipMemcpyHostToDevice, ctx->stream);
-            if (err == hipSuccess) err = hipMemsetAsync((uint8_t*)ctx->arena.d + span, 0, ab - span, ctx->stream);
-        } else {
-            if (span) memcpy(ctx->arena.h, arena + lo, span);
-            memset((uint8_t*)ctx->arena.h + span, 0, ab - span);
-            err = hipMemcpyAsync(ctx->arena.d, ctx->arena.h, ab, hipMemcpyHostToDevice, ctx->stream);
-        }
-    }
-    if (err == hipSuccess && tail_used) {
-        memcpy(ctx->tailbuf.h, b->tail, b->tail_len);
-        memset((uint8_t*)ctx->tailbuf.h + b->tail_len, 0, tb + 64 - b->tail_len);
-        err = hipMemcpyAsync(ctx->tailbuf.d, ctx->tailbuf.h, tb + 64, hipMemcpyHostToDevice, ctx->stream);
-    }
-    // offsets relative to what was staged: arena spans move down by lo, spans of the tail (and empty ones: no address) stay
-    uint32_t* ho = (uint32_t*)ctx->offs.h;
-    auto rebase = [&](uint32_t* dst, const uint32_t* src, size_t k) {
-        if (!spans) {
-            for (size_t i = 0; i < k; i++) dst[i] = src[i] - lo;
-            return;
-        }
-        for (size_t i = 0; i < k; i += 2) {
-            const uint32_t s0 = src[i], s1 = src[i + 1], by = s0 >= tbase ? 0 : lo;
-            dst[i] = s1 > s0 ? s0 - by : 0;
-            dst[i + 1] = s1 > s0 ? s1 - by : 0;
-        }
-    };
-    rebase(ho, b->off, noff);
-    if (err == hipSuccess) err = hipMemcpyAsync(ctx->offs.d, ctx->offs.h, noff * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (m) {
-        rebase((uint32_t*)ctx->pre.h, b->pre_off, npre);
-        memcpy((uint8_t*)ctx->pre.h + pob, b->pre_idx, n * 4);
-        if (err == hipSuccess) err = hipMemcpyAsync(ctx->pre.d, ctx->pre.h, pob + ib, hipMemcpyHostToDevice, ctx->stream);
-    }
-    h.rc = hip_to_rc(err);
+    const size_t ab = staged ? round_up(h.sl->len, 64) : round_up(p.span(), 4) + 64, tb = round_up((size_t)p.tail_len, 4);
+    if (h.rooms(ab, mid_bytes, p.tail_used ? tb + 64 : 0, h.dg_off + n * 32)) return h.rc;
+    h.upload_arena(p, arena, ab, nullptr);
+    if (p.tail_used) h.upload_tail(p, b->tail, ctx->tailbuf.d, tb + 64);
+    h.upload_offsets(p, b->off, b->pre_off, b->pre_idx);
     if (keyed) h.fields(ctx->keyed, HostStage::ID_COLUMN, b->key_id, {(const uint8_t*)b->r, (const uint8_t*)b->s});
     else h.fields(ctx->fields, 0, nullptr, {(const uint8_t*)b->qx, (const uint8_t*)b->qy, (const uint8_t*)b->r, (const uint8_t*)b->s});
-    if (h.ready() && (h.rc = h.room(ctx->out, dg_off + n * 32)) == FABGPU_OK) {
-        uint8_t* pd = (uint8_t*)ctx->pre.d;
-        uint8_t* dout = (uint8_t*)ctx->out.d;
-        fabgpu_identity_batch_p384 d = *b;
-        d.flags = b->flags & FABGPU_IDB_SPANS;
-        d.arena = staged ? sl->d : ctx->arena.d;
-        d.arena_bytes = ab;
-        d.off = (const uint32_t*)ctx->offs.d;
-        d.n_prefixes = m;
-        d.pre_off = m ? (const uint32_t*)pd : nullptr;
-        d.pre_idx = m ? (const uint32_t*)(pd + pob) : nullptr;
-        d.tail = tail_used ? ctx->tailbuf.d : nullptr;
-        d.tail_base = tail_used ? tbase : 0;
-        d.tail_len = tail_used ? b->tail_len : 0;
-        if (keyed) {
-            d.key_id = (const uint32_t*)h.ids();
-            d.qx = d.qy = nullptr;
-            d.r = h.field(0); d.s = h.field(1);
-        } else {
-            d.qx = h.field(0); d.qy = h.field(1); d.r = h.field(2); d.s = h.field(3);
-        }
-        d.verdict_bits = dout;
-        d.status = b->status ? dout + h.st_off : nullptr;
-        d.digests = dout + dg_off;                         // (the rows the verify kernel reads: made here whether the caller wants them or not)
-        h.rc = identity_verify_batch_p384_dev(ctx, &d, m ? pd + pob + ib : nullptr, ctx->stream, sha3);
-    }
-    if (h.fetch(b->digests ? dg_off + n * 32 : (b->status ? h.st_off + n : h.words * 8))) return h.rc;
-    memcpy(b->verdict_bits, ctx->out.h, h.words * 8);
-    if (b->status) memcpy(b->status, (uint8_t*)ctx->out.h + h.st_off, n);
-    if (b->digests) memcpy(b->digests, (uint8_t*)ctx->out.h + dg_off, n * 32);
+    fabgpu_identity_batch_p384 d = *b;
+    h.describe(d, keyed, b->status != nullptr);
+    d.flags = b->flags & FABGPU_IDB_SPANS;
+    d.arena = staged ? h.sl->d : ctx->arena.d;
+    d.arena_bytes = ab;
+    d.tail = p.tail_used ? ctx->tailbuf.d : nullptr;
+    d.tail_base = p.tail_used ? p.tail_base : 0;
+    d.tail_len = p.tail_used ? p.tail_len : 0;
+    d.digests = (uint8_t*)ctx->out.d + h.dg_off;           // (the rows the verify kernel reads: made here whether the caller wants them or not)
+    if (h.rc == FABGPU_OK) h.rc = identity_verify_batch_p384_dev(ctx, &d, h.mid(), ctx->stream, sha3);
+    h.download_results(b->status, b->digests);
+    if (h.drain()) return h.rc;
+    h.copy_out(b->verdict_bits, b->status, b->digests);
     return FABGPU_OK;
 }
 

@@ -23,45 +23,25 @@
 
 #include "device_common.h"
 #include "kernels.h"
+#include "p384_described.h"
 #include "sha256_coop.h"
 
 namespace fab {
 
-struct described384 {
-    const uint32_t* off;       // n (start, end) pairs, or n + 1 consecutive offsets
-    const uint32_t* pre_idx;   // n, or nullptr: the batch has no prefixes
-    const uint32_t* pre_off;   // m pairs, or m + 1 offsets
-    const uint32_t* mid;       // m x 8 words (sha256_midstate_kernel)
-    uint32_t m;
-    uint32_t spans;
-    const uint32_t* tail32;    // nullptr: no tail
-    uint32_t tail_base;        // 0xFFFFFFFF without a tail
-    uint32_t tail_words;
-};
-
-__global__ void __launch_bounds__(64) p384_described_digest_kernel(uint32_t n, const uint32_t* __restrict__ arena32, uint32_t arena_words, described384 d,
+__global__ void __launch_bounds__(64) p384_described_digest_kernel(uint32_t n, const uint32_t* __restrict__ arena32, uint32_t arena_words, Described384 d,
                                                                    uint32_t* __restrict__ digests) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = i < n;
     const uint32_t ic = active ? i : (n - 1);
-    uint32_t start = d.off[d.spans ? 2 * (size_t)ic : (size_t)ic];
-    const uint32_t end = d.off[d.spans ? 2 * (size_t)ic + 1 : (size_t)ic + 1];
-    const uint32_t len = end >= start ? end - start : 0;                  // (a reversed span is the entry point's to refuse: hashed as empty)
-    // the lane's source: spans at or above tail_base address the tail
-    const bool in_tail = d.tail32 != nullptr && start >= d.tail_base;
-    const uint32_t* __restrict__ src = in_tail ? d.tail32 : arena32;
-    const uint32_t src_words = in_tail ? d.tail_words : arena_words;
-    start = in_tail ? start - d.tail_base : start;
+    const Described384Span sp = described384_span(d, ic, arena32, arena_words);
     uint32_t h[8];
     sha256_iv(h);
     if (d.pre_idx == nullptr) {                                           // wave-uniform
-        sha256_stream_t<ShaTailArena, true>(src, src_words, h, ShaTailArena{arena32, 0, 0}, 0, start, len, 0, active, false);
+        sha256_stream_t<ShaTailArena, true>(sp.src, sp.src_words, h, ShaTailArena{arena32, 0, 0}, 0, sp.start, sp.len, 0, active, false);
     } else {
-        const uint32_t pi = d.pre_idx[ic];
-        const bool has = pi < d.m;
-        const uint32_t ps = has ? d.pre_off[d.spans ? 2 * (size_t)pi : (size_t)pi] : 0;
-        const uint32_t pe = has ? d.pre_off[d.spans ? 2 * (size_t)pi + 1 : (size_t)pi + 1] : 0;
-        const uint32_t pl = pe >= ps ? pe - ps : 0;
+        bool has;
+        uint32_t ps, pl;
+        const uint32_t pi = described384_prefix(d, ic, &has, &ps, &pl);
         const uint32_t base = pl & ~63u, rest = pl & 63u;
         if (has && base) {
             const uint4* mp = reinterpret_cast<const uint4*>(d.mid + 8 * (size_t)pi);
@@ -71,32 +51,18 @@ __global__ void __launch_bounds__(64) p384_described_digest_kernel(uint32_t n, c
         }
         // the prefix's remaining bytes come from the arena (a prefix never lies in the tail), the lane's own from its source
         const ShaTailArena rest_of_prefix{arena32, arena_words ? (int32_t)arena_words - 1 : 0, ps + base};
-        sha256_stream_t<ShaTailArena, true>(src, src_words, h, rest_of_prefix, rest, start, len, base, active, true);
+        sha256_stream_t<ShaTailArena, true>(sp.src, sp.src_words, h, rest_of_prefix, rest, sp.start, sp.len, base, active, true);
     }
     if (active) sha256_coop_store(digests, i, h);
 }
 
 hipError_t launch_p384_described_digests(const P384DescribedLaunch& v, hipStream_t st) {
     if (v.n == 0) return hipSuccess;
-    if (!v.arena || !v.off || !v.digests || v.arena_bytes < 4 || (v.arena_bytes & 3u) || v.arena_bytes > 0xFFFFFFFFull || ((uintptr_t)v.arena & 3u) || ((uintptr_t)v.tail & 3u))
-        return hipErrorInvalidValue;
-    const bool prefixed = v.pa.m != 0 && v.pa.pre_idx != nullptr;
-    if (prefixed && (!v.pa.pre_off || !v.pa.mid_scratch)) return hipErrorInvalidValue;
-    if (prefixed && !v.pa.mid_ready) {
-        const hipError_t e = launch_sha256_midstates(v.arena, v.arena_bytes, v.pa, st);
-        if (e != hipSuccess) return e;
-    }
-    described384 d;
-    d.off = (const uint32_t*)v.off;
-    d.pre_idx = prefixed ? (const uint32_t*)v.pa.pre_idx : nullptr;
-    d.pre_off = (const uint32_t*)v.pa.pre_off;
-    d.mid = (const uint32_t*)v.pa.mid_scratch;
-    d.m = prefixed ? v.pa.m : 0;
-    d.spans = v.pa.spans ? 1u : 0u;
-    const bool has_tail = v.tail != nullptr && v.tail_len != 0;
-    d.tail32 = has_tail ? (const uint32_t*)v.tail : nullptr;
-    d.tail_base = has_tail ? v.tail_base : 0xFFFFFFFFu;
-    d.tail_words = has_tail ? (v.tail_len + 3u) / 4u : 0;
+    Described384 d;
+    bool prefixed;
+    hipError_t e = describe384(v, 1, &d, &prefixed);
+    if (e == hipSuccess && prefixed && !v.pa.mid_ready) e = launch_sha256_midstates(v.arena, v.arena_bytes, v.pa, st);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(p384_described_digest_kernel, dim3((v.n + 63) / 64), dim3(64), 0, st, v.n, (const uint32_t*)v.arena, (uint32_t)(v.arena_bytes / 4), d,
                        (uint32_t*)v.digests);
     return hipGetLastError();
