@@ -213,6 +213,7 @@ Error GPUCSP::New(const fabgpu_cfg* cfg, std::unique_ptr<GPUCSP>& out) {
     p->devs_.push_back(std::move(d));
     p->opts_.ctx_flags = cfg ? cfg->flags : 0;
     p->opts_.p384_wide = (p->opts_.ctx_flags & FABGPU_FLAG_P384_WIDE) ? 1 : 0;
+    p->opts_.p384_key_tables16 = (p->opts_.ctx_flags & FABGPU_FLAG_P384_KEY_TABLES_16BIT) ? 1 : 0;
     out = std::move(p);
     return Error();
 }
@@ -233,6 +234,8 @@ Error GPUCSP::New(const ProviderOptions& opts, std::unique_ptr<GPUCSP>& out) {
     p->opts_.devices = devices;
     if (opts.p384_wide > 0) p->opts_.ctx_flags |= FABGPU_FLAG_P384_WIDE;             // (the option is the flag, on every context)
     p->opts_.p384_wide = (p->opts_.ctx_flags & FABGPU_FLAG_P384_WIDE) ? 1 : 0;
+    if (opts.p384_key_tables16 > 0) p->opts_.ctx_flags |= FABGPU_FLAG_P384_KEY_TABLES_16BIT;
+    p->opts_.p384_key_tables16 = (p->opts_.ctx_flags & FABGPU_FLAG_P384_KEY_TABLES_16BIT) ? 1 : 0;
     p->audit_permille_.store(opts.audit_permille > 1000 ? 1000 : opts.audit_permille, std::memory_order_relaxed);
     for (int32_t ord : devices) {
         fabgpu_cfg cfg;
@@ -327,6 +330,7 @@ int64_t GPUCSP::GetOption(const std::string& name) const {
     if (name == "n_devices") return (int64_t)devs_.size();
     if (name == "audit_permille") return (int64_t)AuditPermille();
     if (name == "p384_wide") return opts_.p384_wide;
+    if (name == "p384_key_tables16") return opts_.p384_key_tables16;       // (read at construction: SetOption does not know the name)
     if (name == "registrations_dropped") return (int64_t)reg_dropped_.load(std::memory_order_relaxed);        // (read-only counters)
     if (name == "registration_id_mismatches") return (int64_t)reg_id_mismatches_.load(std::memory_order_relaxed);
     for (const OptField& o : kIntOpts)

@@ -170,6 +170,7 @@ struct ProviderOptions {
     int p384_wide = 0;                 // > 0: FABGPU_FLAG_P384_WIDE on every context - keyed P-384 launches of at most 8 192 rows on eight lanes per
                                        // signature.  Read at construction like ctx_flags (which may carry the bit itself); SetOption of the same
                                        // name switches the living contexts.  Default off
+    int p384_key_tables16 = 0;         // > 0: FABGPU_FLAG_P384_KEY_TABLES_16BIT on every context - registered P-384 keys also get 16-bit comb tables
     uint32_t audit_permille = 0;       // share of the digests / verdicts handed out that is re-computed on the CPU first (0 .. 1000; 0: none)
 };
 constexpr int kMaxProviderDevices = 64;   // contexts per provider (8 GPUs x up to 8 contexts each)

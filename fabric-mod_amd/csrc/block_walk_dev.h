@@ -335,6 +335,9 @@ int key_table_copy(fabgpu_ctx* ctx, uint32_t key_id, int32_t* out);   // TEST HO
 // ... a registered P-384 key's comb table (generator != 0: the generator's), CombTab384::TABLE_WORDS words; a batch of P-384 keys in one build
 int p384_key_table_copy(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint32_t* out);
 int p384_key_register_batch_hook(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key_ids);
+int p384_tables16_wait(fabgpu_ctx* ctx);
+int p384_tables16_cap(fabgpu_ctx* ctx, uint32_t cap);
+int p384_key_table16_check(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint64_t* bad, uint32_t* out3);
 int key_register_many_prebuilt(fabgpu_ctx* const* ctxs, int n, const uint8_t* qx32, const uint8_t* qy32, const int32_t* table, uint32_t* key_ids);
 // FABGPU_FLAG_P384_WIDE on a living context (the provider's "p384_wide" option): the eight-lane form of the keyed P-384 launches, for the
 // launches queued after the call; turning it on makes the form's scratch (a FABGPU_* code when that fails).  ctx_p384_wide_serves: whether

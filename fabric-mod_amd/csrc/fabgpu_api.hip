@@ -32,6 +32,7 @@
 #include "p384.h"
 #include "p384_keys.h"
 #include "p384_tables.h"
+#include "p384_tables16.h"
 
 using namespace fab;
 
@@ -268,6 +269,7 @@ struct fabgpu_ctx {
     struct Drain384 {
         int64_t slot = -1;                   // -1: only an array to give back
         uint32_t* tab = nullptr;
+        uint32_t* tab16 = nullptr;           // the tenant's 16-bit table, finished or (its event is in evs) still being built
         Snap384Room old_snap{nullptr, 0};
         bool recorded = false;
         std::vector<hipEvent_t> evs;
@@ -283,6 +285,22 @@ struct fabgpu_ctx {
     // finds it there (a second one is made only when keyed launches of several streams overlap).
     std::atomic<bool> p384_wide{false};
     std::atomic<uint64_t> k384_wide_rows{0}; // rows handed to the eight-lane form so far (fabgpu_p384_wide_rows)
+    // FABGPU_FLAG_P384_KEY_TABLES_16BIT (DESIGN 4.2d "16-bit tables").  The generator's 16-bit table is built once, beside its 8-bit one.
+    // A registration queues its key's 16-bit build on stream_k384x16 behind the finished 8-bit table and does NOT wait for it: the
+    // build waits in k384_pending16 with its event.  The launch path (and the stats path) asks hipEventQuery, never a blocking wait for
+    // a build; a finished table goes into the book, and the book's next snapshot - a fresh array, written whole and waited for, as
+    // always - carries its address.  At most k384_tab16_cap tables are live or being built; later keys, and keys whose hipMalloc
+    // failed, have none and stay on the 8-bit stream.  A retired key's 16-bit table (or unfinished build) drains with its slot.
+    bool p384_tab16 = false;
+    uint32_t* d_gcomb384x16 = nullptr;
+    unsigned long long* d_k384_rows16 = nullptr;   // rows of the wavefronts that ran 24 windows (fabgpu_p384_tables16_rows)
+    uint32_t k384_tab16_cap = FABGPU_P384_MAX_TABLES16;
+    struct Pending384x16 { uint32_t id; uint32_t* tab; hipEvent_t ev; };
+    std::vector<Pending384x16> k384_pending16;
+    std::vector<uint32_t*> k384_tab16_free;  // 16-bit tables of retired keys, drained
+    uint64_t k384_n_tables16 = 0;            // 16-bit tables ever allocated (the generator's included)
+    const uint32_t* const* d_snap384x16 = nullptr;   // the second address per slot: behind the slots of d_snap384, in the same array
+    hipStream_t stream_k384x16 = nullptr;
     std::mutex k384_build_mu;                // one build at a time: the builder's room and stream are one
     void *d_k384_in = nullptr, *d_k384_scr = nullptr;
     size_t k384_in_cap = 0, k384_scr_cap = 0;
@@ -499,7 +517,8 @@ int fabgpu_init(const fabgpu_cfg* cfg, fabgpu_ctx** out) {
     *out = nullptr;
     if (cfg && (cfg->flags & ~(uint32_t)(FABGPU_FLAG_ONE_LANE_ONLY | FABGPU_FLAG_TIME_KERNELS | FABGPU_FLAG_NO_QUAD | FABGPU_FLAG_PAIR_TABLE_LDS |
                                           FABGPU_FLAG_PAIR_TABLE_GLOBAL | FABGPU_FLAG_NO_WIDE | FABGPU_FLAG_NYM_FUSED_HASH | FABGPU_FLAG_NYM_NO_SIDE_STREAM |
-                                          FABGPU_FLAG_KEY_TABLES_16BIT | FABGPU_FLAG_PAIR_SOLO | FABGPU_FLAG_PAIR_DBL1 | FABGPU_FLAG_P384_WIDE)) != 0) return FABGPU_EINVAL;
+                                          FABGPU_FLAG_KEY_TABLES_16BIT | FABGPU_FLAG_PAIR_SOLO | FABGPU_FLAG_PAIR_DBL1 | FABGPU_FLAG_P384_WIDE |
+                                          FABGPU_FLAG_P384_KEY_TABLES_16BIT)) != 0) return FABGPU_EINVAL;
     if (cfg && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_LDS) && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_GLOBAL)) return FABGPU_EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return FABGPU_ENODEV;
@@ -588,6 +607,7 @@ int fabgpu_init(const fabgpu_cfg* cfg, fabgpu_ctx** out) {
             }
         }
         if (cfg && (cfg->flags & FABGPU_FLAG_P384_WIDE) && (rc = fab::ctx_set_p384_wide(ctx, true))) break;
+        ctx->p384_tab16 = cfg && (cfg->flags & FABGPU_FLAG_P384_KEY_TABLES_16BIT);      // (nothing is allocated before the first registered P-384 key)
         if (cfg && cfg->max_batch) {
             size_t n = cfg->max_batch;
             if ((rc = ctx->fields.ensure(n * 160)) || (rc = ctx->offs.ensure((n + 1) * 4)) || (rc = ctx->out.ensure(n * 41 + 64))) break;
@@ -623,6 +643,8 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
         if (ctx->stream_keytab) hipStreamDestroy(ctx->stream_keytab);
         if (ctx->stream_kslot) hipStreamDestroy(ctx->stream_kslot);
         if (ctx->stream_k384) { hipStreamSynchronize(ctx->stream_k384); hipStreamDestroy(ctx->stream_k384); }
+        if (ctx->stream_k384x16) { hipStreamSynchronize(ctx->stream_k384x16); hipStreamDestroy(ctx->stream_k384x16); }
+        for (auto& q : ctx->k384_pending16) hipEventDestroy(q.ev);
         for (void* t : ctx->k384_allocs) hipFree(t);                 // (P-384 key tables, the generator's comb, snapshot arrays)
         if (ctx->d_k384_in) hipFree(ctx->d_k384_in);
         if (ctx->d_k384_scr) hipFree(ctx->d_k384_scr);
@@ -1947,6 +1969,7 @@ bool k384_drain_step_locked(fabgpu_ctx* ctx, fabgpu_ctx::Drain384& d, bool wait)
         d.evs.pop_back();
     }
     if (d.tab) ctx->k384_tab_free.push_back(d.tab);
+    if (d.tab16) ctx->k384_tab16_free.push_back(d.tab16);
     if (d.old_snap.p) ctx->snap384_free.push_back(d.old_snap);
     if (d.slot >= 0) ctx->k384.slots.drained((uint32_t)d.slot);     // (a parked slot stays parked)
     return true;
@@ -1971,8 +1994,10 @@ bool k384_drain_wait_slot_locked(fabgpu_ctx* ctx, uint32_t slot) {
 // keyed row answers 4 until a later change of the book succeeds) - never a stale one.
 int k384_publish_locked(fabgpu_ctx* ctx, fabgpu_ctx::Drain384& d) {
     const std::vector<fab::P384SlotSnap> snap = ctx->k384.snapshot();
+    const size_t slot_bytes = sizeof(fab::P384SlotSnap) + (ctx->p384_tab16 ? sizeof(void*) : 0);     // (with the option: a second address per slot)
     d.old_snap = fabgpu_ctx::Snap384Room{(void*)ctx->d_snap384, ctx->snap384_cap};
     ctx->d_snap384 = nullptr;
+    ctx->d_snap384x16 = nullptr;
     ctx->snap384_n = 0;
     ctx->snap384_cap = 0;
     if (snap.empty()) return FABGPU_OK;
@@ -1986,26 +2011,34 @@ int k384_publish_locked(fabgpu_ctx* ctx, fabgpu_ctx::Drain384& d) {
     if (!room.p) {
         room.cap = 64;
         while (room.cap < snap.size()) room.cap *= 2;
-        if (ctx->fault == 2 || hipMalloc(&room.p, room.cap * sizeof(fab::P384SlotSnap)) != hipSuccess) return FABGPU_ENOMEM;
+        if (ctx->fault == 2 || hipMalloc(&room.p, room.cap * slot_bytes) != hipSuccess) return FABGPU_ENOMEM;
         ctx->k384_allocs.push_back(room.p);
-        ctx->k384_snap_bytes += room.cap * sizeof(fab::P384SlotSnap);
+        ctx->k384_snap_bytes += room.cap * slot_bytes;
     }
-    hipError_t e = k384_stream(ctx) ? hipMemcpyAsync(room.p, snap.data(), snap.size() * sizeof(fab::P384SlotSnap), hipMemcpyHostToDevice, ctx->stream_k384)
-                                    : hipErrorLaunchFailure;
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream_k384);      // (`snap` lives on this frame; and no launch is handed a half-written array)
+    // one image of the whole array: the slots, and behind the room's cap slots the 16-bit addresses
+    const size_t off16 = room.cap * sizeof(fab::P384SlotSnap);
+    std::vector<uint8_t> img(ctx->p384_tab16 ? off16 + snap.size() * sizeof(void*) : snap.size() * sizeof(fab::P384SlotSnap));
+    memcpy(img.data(), snap.data(), snap.size() * sizeof(fab::P384SlotSnap));
+    if (ctx->p384_tab16) {
+        const std::vector<const uint32_t*> s16 = ctx->k384.snapshot16();
+        memcpy(img.data() + off16, s16.data(), s16.size() * sizeof(void*));
+    }
+    hipError_t e = k384_stream(ctx) ? hipMemcpyAsync(room.p, img.data(), img.size(), hipMemcpyHostToDevice, ctx->stream_k384) : hipErrorLaunchFailure;
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream_k384);      // (`img` lives on this frame; and no launch is handed a half-written array)
     if (e != hipSuccess) {
         (void)hipGetLastError();
         ctx->snap384_free.push_back(room);
         return hip_to_rc(e);
     }
     ctx->d_snap384 = (const fab::P384SlotSnap*)room.p;
+    if (ctx->p384_tab16) ctx->d_snap384x16 = (const uint32_t* const*)((const uint8_t*)room.p + off16);
     ctx->snap384_n = (uint32_t)snap.size();
     ctx->snap384_cap = room.cap;
     return FABGPU_OK;
 }
 // (k384_mu held) `d` joins the drains if there is anything in it to wait for
 void k384_drain_push_locked(fabgpu_ctx* ctx, fabgpu_ctx::Drain384&& d) {
-    if (d.slot >= 0 || d.tab || d.old_snap.p) ctx->k384_drains.push_back(std::move(d));
+    if (d.slot >= 0 || d.tab || d.tab16 || d.old_snap.p) ctx->k384_drains.push_back(std::move(d));
 }
 uint32_t* k384_tab_alloc_locked(fabgpu_ctx* ctx) {
     if (!ctx->k384_tab_free.empty()) {
@@ -2018,6 +2051,125 @@ uint32_t* k384_tab_alloc_locked(fabgpu_ctx* ctx) {
     ctx->k384_allocs.push_back(t);
     ctx->k384_n_tables++;
     return (uint32_t*)t;
+}
+// ---- the optional 16-bit tables (fabgpu_ctx::p384_tab16 has the story) ----
+bool k384x16_stream(fabgpu_ctx* ctx) {
+    return ctx->stream_k384x16 || hipStreamCreateWithFlags(&ctx->stream_k384x16, hipStreamNonBlocking) == hipSuccess;
+}
+// (k384_mu held) 144 MiB from the drained tables or the device; nullptr: the key (or the generator) simply has no 16-bit table
+uint32_t* k384_tab16_alloc_locked(fabgpu_ctx* ctx) {
+    if (!ctx->k384_tab16_free.empty()) {
+        uint32_t* t = ctx->k384_tab16_free.back();
+        ctx->k384_tab16_free.pop_back();
+        return t;
+    }
+    void* t = nullptr;
+    if (ctx->fault == 2 || hipMalloc(&t, fab::p384::CombTab384x16::TABLE_BYTES) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    ctx->k384_allocs.push_back(t);
+    ctx->k384_n_tables16++;
+    return (uint32_t*)t;
+}
+// (k384_build_mu and k384_mu held, the context's device current) the 16-bit build of the live key `id`, whose 8-bit table tab8 is
+// complete, queued behind nothing the caller waits for.  Any refusal leaves the key without a 16-bit table and is no error.
+void k384_queue16_locked(fabgpu_ctx* ctx, uint32_t id, const uint32_t* tab8) {
+    if (!ctx->p384_tab16 || !ctx->d_gcomb384x16 || ctx->fault) return;
+    if (ctx->k384.n_tables16() + ctx->k384_pending16.size() >= ctx->k384_tab16_cap) return;
+    if (!k384x16_stream(ctx)) {
+        (void)hipGetLastError();
+        return;
+    }
+    hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    uint32_t* t16 = k384_tab16_alloc_locked(ctx);
+    if (!t16) {
+        hipEventDestroy(ev);
+        return;
+    }
+    hipError_t e = launch_p384_keytab16_build(tab8, t16, ctx->stream_k384x16);
+    if (e == hipSuccess) e = hipEventRecord(ev, ctx->stream_k384x16);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(ctx->stream_k384x16);      // (whatever was queued has run before the table is handed out again)
+        (void)hipGetLastError();
+        hipEventDestroy(ev);
+        ctx->k384_tab16_free.push_back(t16);
+        return;
+    }
+    ctx->k384_pending16.push_back(fabgpu_ctx::Pending384x16{id, t16, ev});
+}
+// (k384_mu held, the context's device current) builds that have finished (wait: all of them, waited for - the test hooks only) enter
+// the book, and if any did, the book is published again.  A publication that fails here keeps the snapshot in place: it is not stale,
+// it only lacks the new addresses, and the next change of the book tries again.
+void k384_poll16_locked(fabgpu_ctx* ctx, bool wait = false) {
+    if (ctx->k384_pending16.empty()) return;
+    bool news = false;
+    for (size_t i = 0; i < ctx->k384_pending16.size();) {
+        const fabgpu_ctx::Pending384x16 q = ctx->k384_pending16[i];
+        const hipError_t e = wait ? hipEventSynchronize(q.ev) : hipEventQuery(q.ev);
+        if (e == hipErrorNotReady) {
+            (void)hipGetLastError();
+            i++;
+            continue;
+        }
+        hipEventDestroy(q.ev);
+        ctx->k384_pending16.erase(ctx->k384_pending16.begin() + (long)i);
+        if (e == hipSuccess && ctx->k384.set_table16(q.id, q.tab)) {
+            news = true;
+        } else {                                   // (a failed device: nothing of it runs any more)
+            (void)hipGetLastError();
+            ctx->k384_tab16_free.push_back(q.tab);
+        }
+    }
+    if (!news) return;
+    const fab::P384SlotSnap* keep = ctx->d_snap384;
+    const uint32_t* const* keep16 = ctx->d_snap384x16;
+    const uint32_t keep_n = ctx->snap384_n;
+    const size_t keep_cap = ctx->snap384_cap;
+    fabgpu_ctx::Drain384 d;
+    if (k384_publish_locked(ctx, d) != FABGPU_OK) {
+        ctx->d_snap384 = keep;
+        ctx->d_snap384x16 = keep16;
+        ctx->snap384_n = keep_n;
+        ctx->snap384_cap = keep_cap;
+        return;
+    }
+    k384_drain_push_locked(ctx, std::move(d));
+}
+// (k384_build_mu held, the context's device current) the generator's 16-bit table from its finished 8-bit one, and the counter of the
+// rows the 24-window stream verified: once per context, waited for.  A failure leaves the context on 8-bit tables and is no error.
+void k384_gcomb16_build(fabgpu_ctx* ctx, const uint32_t* g8) {
+    uint32_t* t16 = nullptr;
+    void* ctr = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->k384_mu);
+        if (!ctx->p384_tab16 || ctx->d_gcomb384x16 || ctx->fault || !k384x16_stream(ctx)) {
+            (void)hipGetLastError();
+            return;
+        }
+        if (hipMalloc(&ctr, 16) != hipSuccess) {
+            (void)hipGetLastError();
+            return;
+        }
+        ctx->k384_allocs.push_back(ctr);
+        if (!(t16 = k384_tab16_alloc_locked(ctx))) return;
+    }
+    hipError_t e = hipMemsetAsync(ctr, 0, 16, ctx->stream_k384x16);
+    if (e == hipSuccess) e = launch_p384_keytab16_build(g8, t16, ctx->stream_k384x16);
+    const hipError_t drained = hipStreamSynchronize(ctx->stream_k384x16);
+    std::lock_guard<std::mutex> lk(ctx->k384_mu);
+    if (e != hipSuccess || drained != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->k384_tab16_free.push_back(t16);
+        return;
+    }
+    ctx->d_k384_rows16 = (unsigned long long*)ctr;
+    ctx->d_gcomb384x16 = t16;
 }
 // (k384_build_mu held, the context's device current) the comb tables of m points (qxy: m x 96 bytes) into tabs[0 .. m), complete on return
 int k384_build_locked(fabgpu_ctx* ctx, uint32_t m, const uint8_t* qxy, uint32_t* const* tabs) {
@@ -2063,9 +2215,12 @@ int p384_gcomb(fabgpu_ctx* ctx) {
     uint8_t g[96];
     fab::p384::generator_be(g, g + 48);
     const int rc = k384_build_locked(ctx, 1, g, &t);
-    std::lock_guard<std::mutex> lk(ctx->k384_mu);
-    if (rc != FABGPU_OK) ctx->k384_tab_free.push_back(t);
-    else ctx->d_gcomb384 = t;
+    {
+        std::lock_guard<std::mutex> lk(ctx->k384_mu);
+        if (rc != FABGPU_OK) ctx->k384_tab_free.push_back(t);
+        else ctx->d_gcomb384 = t;
+    }
+    if (rc == FABGPU_OK) k384_gcomb16_build(ctx, t);
     return rc;
 }
 // n points of the curve (qxy: n x 96 bytes; the caller's gate) registered on one context: one build for those the context does not have
@@ -2118,7 +2273,8 @@ int p384_key_register_batch(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t
         if (slot < 0) rc = FABGPU_ENOMEM;
         else if (ctx->k384.slots.draining((uint32_t)slot) && !k384_drain_wait_slot_locked(ctx, (uint32_t)slot)) rc = FABGPU_ELAUNCH;
         if (rc != FABGPU_OK) break;
-        ctx->k384.install(names[(size_t)todo[t]], tabs[t]);
+        const uint32_t id = ctx->k384.install(names[(size_t)todo[t]], tabs[t]);
+        k384_queue16_locked(ctx, id, tabs[t]);
         tabs[t] = nullptr;
     }
     give_back_locked();
@@ -2128,6 +2284,7 @@ int p384_key_register_batch(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t
         k384_drain_push_locked(ctx, std::move(d));
         if (rc == FABGPU_OK) rc = prc;
     }
+    k384_poll16_locked(ctx);
     for (int i = 0; i < n && rc == FABGPU_OK; i++)
         if (!ctx->k384.lookup(names[(size_t)i], &key_ids[i])) rc = FABGPU_ELAUNCH;
     return rc;
@@ -2140,11 +2297,20 @@ struct KeyedSnap384 {
     const fab::P384SlotSnap* snap = nullptr;
     uint32_t nkeys = 0;
     const uint32_t* gcomb = nullptr;
+    const uint32_t* gcomb16 = nullptr;         // all three null without FABGPU_FLAG_P384_KEY_TABLES_16BIT (or without the generator's 16-bit table)
+    const uint32_t* const* snap16 = nullptr;
+    void* rows16 = nullptr;
     KeyedSnap384(fabgpu_ctx* c, hipStream_t st) : ctx(c) {
         std::lock_guard<std::mutex> lk(ctx->k384_mu);
+        k384_poll16_locked(ctx);               // (finished 16-bit builds: hipEventQuery, and a fresh snapshot if there is news)
         snap = ctx->d_snap384;
         nkeys = ctx->snap384_n;
         gcomb = ctx->d_gcomb384;
+        if (ctx->d_gcomb384x16 && (ctx->d_snap384x16 || !nkeys)) {
+            gcomb16 = ctx->d_gcomb384x16;
+            snap16 = ctx->d_snap384x16;
+            rows16 = ctx->d_k384_rows16;
+        }
         if (std::find(ctx->k384_streams.begin(), ctx->k384_streams.end(), st) == ctx->k384_streams.end()) ctx->k384_streams.push_back(st);
         std::lock_guard<std::mutex> ll(ctx->k384_lm);
         ctx->k384_launchers++;
@@ -2165,6 +2331,7 @@ int p384_verify_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* key_id, const v
     v.n = (uint32_t)n;
     v.key_id = key_id; v.e = e; v.e_is_digest32 = e_is_digest32; v.r = r; v.s = s;
     v.gcomb = snap.gcomb; v.snap = snap.snap; v.nkeys = snap.nkeys;
+    v.gcomb16 = snap.gcomb16; v.snap16 = (const void* const*)snap.snap16; v.rows16 = snap.rows16;
     v.verdict_bits = verdict_bits; v.status = status;
     ctx->k384_launches.fetch_add(1, std::memory_order_relaxed);
     if (fab::ctx_p384_wide_serves(ctx, n)) {
@@ -2230,9 +2397,16 @@ int fabgpu_p384_key_unregister(fabgpu_ctx* ctx, uint32_t key_id) {
     if (!ctx) return FABGPU_EINVAL;
     std::lock_guard<std::mutex> lk(ctx->k384_mu);
     fabgpu_ctx::Drain384 d;
-    if (ctx->k384.retire(key_id, &d.tab)) return 1;
+    if (ctx->k384.retire(key_id, &d.tab, &d.tab16)) return 1;
     d.slot = fab::KeySlots::slot_of(key_id);
     DeviceGuard g(ctx->device);
+    for (size_t i = 0; i < ctx->k384_pending16.size(); i++)
+        if (ctx->k384_pending16[i].id == key_id) {             // its 16-bit build is still queued: the drain waits for it too
+            d.tab16 = ctx->k384_pending16[i].tab;
+            d.evs.push_back(ctx->k384_pending16[i].ev);
+            ctx->k384_pending16.erase(ctx->k384_pending16.begin() + (long)i);
+            break;
+        }
     // launches queued before this moment hold the previous snapshot and answer for the key; none queued from now on can name it
     (void)k384_publish_locked(ctx, d);
     k384_drain_push_locked(ctx, std::move(d));
@@ -2246,16 +2420,34 @@ int fabgpu_p384_wide_rows(fabgpu_ctx* ctx, uint64_t* rows) {
     return FABGPU_OK;
 }
 
+int fabgpu_p384_tables16_rows(fabgpu_ctx* ctx, uint64_t* rows) {
+    if (!ctx || !rows) return FABGPU_EINVAL;
+    *rows = 0;
+    std::lock_guard<std::mutex> lk(ctx->k384_mu);
+    if (!ctx->d_k384_rows16) return FABGPU_OK;
+    DeviceGuard g(ctx->device);
+    unsigned long long v = 0;
+    if (hipMemcpy(&v, ctx->d_k384_rows16, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return FABGPU_ELAUNCH;
+    }
+    *rows = v;
+    return FABGPU_OK;
+}
+
 int fabgpu_p384_key_table_stats(fabgpu_ctx* ctx, uint64_t* out, int cap) {
     if (!ctx || (cap > 0 && !out)) return FABGPU_EINVAL;
     std::lock_guard<std::mutex> lk(ctx->k384_mu);
     {
         DeviceGuard g(ctx->device);
         k384_drain_advance_locked(ctx);
+        k384_poll16_locked(ctx);
     }
     const uint64_t bytes = ctx->k384_n_tables * (uint64_t)fab::p384::CombTab384::TABLE_BYTES + ctx->k384_snap_bytes;
+    const uint64_t live16 = ctx->k384.n_tables16();
     const uint64_t v[FABGPU_P384_KEY_TABLE_STATS] = {ctx->k384.slots.n_live(), ctx->k384.slots.n_draining(), ctx->k384.slots.n_reused(), ctx->k384.slots.n_parked(),
-                                                     ctx->k384_launches.load(std::memory_order_relaxed), bytes, ctx->k384.slots.high_water()};
+                                                     ctx->k384_launches.load(std::memory_order_relaxed), bytes, ctx->k384.slots.high_water(),
+                                                     live16, live16 * (uint64_t)fab::p384::CombTab384x16::TABLE_BYTES};
     for (int i = 0; i < cap && i < FABGPU_P384_KEY_TABLE_STATS; i++) out[i] = v[i];
     return FABGPU_P384_KEY_TABLE_STATS;
 }
@@ -4038,6 +4230,53 @@ int p384_key_table_copy(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint32_
     if (!d) return FABGPU_EINVAL;
     DeviceGuard g(ctx->device);
     return hip_to_rc(hipMemcpy(out, d, p384::CombTab384::TABLE_BYTES, hipMemcpyDeviceToHost));
+}
+// ... the 16-bit tables (FABGPU_FLAG_P384_KEY_TABLES_16BIT).  tables16_wait: every queued build waited for and published; how many
+// 16-bit tables are live.  tables16_cap: the cap on live 16-bit tables, for the registrations that follow.  key_table16_check: after
+// the same wait, *bad = the entries of the key's (generator != 0: the generator's) 16-bit table that are not T8[2 w][lo] + T8[2 w + 1][hi]
+// as p384_keytab16_check_kernel recomputes them from the 8-bit table on the device, and out3 (three windows' words, or null) = windows
+// 0, 11 and 23 as they lie on the device.  1: the key has no 16-bit table.
+int p384_tables16_wait(fabgpu_ctx* ctx) {
+    if (!ctx) return FABGPU_EINVAL;
+    DeviceGuard g(ctx->device);
+    std::lock_guard<std::mutex> lk(ctx->k384_mu);
+    k384_poll16_locked(ctx, true);
+    return (int)ctx->k384.n_tables16();
+}
+int p384_tables16_cap(fabgpu_ctx* ctx, uint32_t cap) {
+    if (!ctx || cap > FABGPU_P384_MAX_TABLES16) return FABGPU_EINVAL;
+    std::lock_guard<std::mutex> lk(ctx->k384_mu);
+    ctx->k384_tab16_cap = cap;
+    return FABGPU_OK;
+}
+int p384_key_table16_check(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint64_t* bad, uint32_t* out3) {
+    if (!ctx || !bad) return FABGPU_EINVAL;
+    DeviceGuard g(ctx->device);
+    const uint32_t *t8 = nullptr, *t16 = nullptr;
+    unsigned long long* ctr = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->k384_mu);
+        k384_poll16_locked(ctx, true);
+        t8 = generator ? ctx->d_gcomb384 : ctx->k384.table(key_id);
+        t16 = generator ? ctx->d_gcomb384x16 : ctx->k384.table16(key_id);
+        ctr = ctx->d_k384_rows16;
+    }
+    if (!t8 || !t16 || !ctr) return 1;
+    ctr++;                                         // (the second word of the counter's allocation is the hooks')
+    hipStream_t st = ctx->stream_k384x16;
+    hipError_t e = hipMemsetAsync(ctr, 0, sizeof(*ctr), st);
+    if (e == hipSuccess) e = launch_p384_keytab16_check(t8, t16, ctr, st);
+    unsigned long long v = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&v, ctr, sizeof(v), hipMemcpyDeviceToHost, st);
+    const hipError_t drained = hipStreamSynchronize(st);
+    if (e != hipSuccess || drained != hipSuccess) return hip_to_rc(e != hipSuccess ? e : drained);
+    *bad = v;
+    const uint32_t wins[3] = {0, 11, 23};
+    for (int i = 0; out3 && i < 3; i++)
+        if (int rc = hip_to_rc(hipMemcpy(out3 + (size_t)i * p384::CombTab384x16::WINDOW_WORDS, t16 + p384::CombTab384x16::index(wins[i], 0),
+                                         p384::CombTab384x16::WINDOW_WORDS * 4, hipMemcpyDeviceToHost)))
+            return rc;
+    return FABGPU_OK;
 }
 // ... and a batch of keys (qxy: n x 96 bytes, every one a point of the curve) registered with one build
 int p384_key_register_batch_hook(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key_ids) {

@@ -106,6 +106,17 @@ int fabgpu_test_p384_key_table(fabgpu_ctx* ctx, uint32_t key_id, int generator, 
 int fabgpu_test_p384_key_table_host(const uint8_t* qx48, const uint8_t* qy48, uint32_t* out_words, size_t cap_words);
 int fabgpu_test_p384_verify_keyed_host(const uint32_t* gcomb, const uint32_t* qcomb, const uint8_t* e48, const uint8_t* r48, const uint8_t* s48, int key_ok);
 int fabgpu_test_p384_key_register_batch(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key_ids);
+/* ... their 16-bit tables (FABGPU_FLAG_P384_KEY_TABLES_16BIT; csrc/p384_tables16.h).  tables16_wait: every queued 16-bit build is waited
+ * for and published; returns the number of live 16-bit tables.  tables16_cap: the cap on live 16-bit tables (<= FABGPU_P384_MAX_TABLES16)
+ * for the registrations that follow.  key_table16: after the same wait, *bad = how many of the 24 x 65 536 entries of the key's (generator
+ * != 0: the generator's) 16-bit table differ from T8[2 w][lo] + T8[2 w + 1][hi], recomputed on the device by the complete Jacobian
+ * addition and compared projectively; out_words (NULL, or three windows' words): windows 0, 11 and 23 as they lie on the device.
+ * 1: the key has no 16-bit table.  key_table16_host: windows [w_begin, w_end) as the host builder makes them from an 8-bit table of
+ * key_table_host (16-byte aligned). */
+int fabgpu_test_p384_tables16_wait(fabgpu_ctx* ctx);
+int fabgpu_test_p384_tables16_cap(fabgpu_ctx* ctx, uint32_t cap);
+int fabgpu_test_p384_key_table16(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint64_t* bad, uint32_t* out_words, size_t cap_words);
+int fabgpu_test_p384_key_table16_host(const uint32_t* tab8, uint32_t w_begin, uint32_t w_end, uint32_t* out_words, size_t cap_words);
 /* ... and a context's book of P-384 keys by itself (csrc/p384_keys.h; no device): register - the id of `name96` (the one it has, or
  * a new one: a slot still draining is drained on the spot; -1 when no slot can be had) with an opaque tag in the table's place; retire -
  * 0 retired (*tab_tag: the tag the slot held), 1 not live; snapshot - what a keyed launch would be handed, per slot the tag (0: none)

@@ -135,6 +135,10 @@ hipError_t launch_p384_verify(const P384Launch& v, hipStream_t st);
 // comb tables built on the device (qxy: n_keys x 96 bytes, tabs: n_keys table addresses, both in device memory; see the unit's header)
 size_t p384_keytab_scratch_bytes(uint32_t n_keys);
 hipError_t launch_p384_keytab_build(uint32_t n_keys, const void* qxy, void* const* tabs, void* scratch, hipStream_t st);
+// the optional 16-bit table (p384_tables16.h CombTab384x16, 144 MiB) of ONE key from its finished 8-bit table; both 16-byte aligned, on the device
+hipError_t launch_p384_keytab16_build(const void* tab8, void* tab16, hipStream_t st);
+// (test hooks) *bad, a zeroed u64 on the device, += the entries of tab16 that are not T8[2 w][lo] + T8[2 w + 1][hi], recomputed another way
+hipError_t launch_p384_keytab16_check(const void* tab8, const void* tab16, void* bad, hipStream_t st);
 struct P384SlotSnap;   // p384_keys.h: one slot of a keyed launch's snapshot of the context's P-384 keys (table, generation)
 struct P384KeyedLaunch {
     uint32_t n = 0;
@@ -148,6 +152,12 @@ struct P384KeyedLaunch {
     void* verdict_bits = nullptr;            // ceil(n/64) x u64
     void* status = nullptr;                  // n bytes or nullptr
     void* wide_scratch = nullptr;            // launch_p384_verify_keyed_wide only: n x P384_WIDE_SCRATCH_BYTES, 4-byte aligned, the launch's own until it has run
+    // launch_p384_verify_keyed only, all three or none (none: the 8-bit kernel, as without the option): the generator's 16-bit table, per
+    // slot of the snapshot the key's finished 16-bit table or null (nkeys addresses, part of the same snapshot), and the device counter
+    // (u64) that grows by the rows of the wavefronts that ran 24 windows
+    const void* gcomb16 = nullptr;
+    const void* const* snap16 = nullptr;
+    void* rows16 = nullptr;
 };
 hipError_t launch_p384_verify_keyed(const P384KeyedLaunch& v, hipStream_t st);
 // ---- p384_wide_kernels.hip: the same verification on eight lanes per signature, in two launches on st (p384_wide.h) ----

@@ -11,6 +11,14 @@
 // above the snapshot's high-water mark, whose generation is not the slot's, or whose slot shows no table answers status 4 and never
 // another key's verdict - the rule of RegisteredKey (kernels.hip).  Such a row still runs the whole stream, on the generator's comb.
 // Nothing the kernel reads changes while it runs: no table pointer is published under a running launch.
+//
+// 16-BIT TABLES (FABGPU_FLAG_P384_KEY_TABLES_16BIT; p384_tables16.h).  The T16 instantiations are launched only when the context has the
+// generator's 16-bit table.  The snapshot then carries a second address per slot: the key's finished 16-bit table, or null.  The choice
+// is made PER WAVEFRONT (a workgroup is one wavefront): if every lane's row either names a live key that shows a 16-bit table or
+// answers 4 (it runs on the generator's table, which exists), the wavefront runs verify_core_keyed over 24 windows of 16 bits;
+// otherwise all its lanes run the 48-window stream on the 8-bit tables, as the other instantiations do.  Lanes of one wavefront never
+// take different loops; tail lanes repeat the last row and so vote as it does.  Rows, ids, the rule above, verdict words and status
+// bytes are the same for every input.  rows16 grows by the rows (tail lanes not counted) of the wavefronts that ran 24 windows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -18,6 +26,7 @@
 #include "p384_dev.h"
 #include "p384_keys.h"
 #include "p384_tables.h"
+#include "p384_tables16.h"
 
 namespace fab {
 
@@ -27,12 +36,14 @@ constexpr int P384K_BLOCK = 64;
 constexpr uint32_t P384K_MAX_WGS = 1024;                         // 256 CUs x 4 SIMDs x the kernel's one wavefront per SIMD
 
 // Tail lanes of the last tile compute on the last tuple and write nothing (kernels.hip).
-template <bool E32>
+template <bool E32, bool T16>
 __global__ void __launch_bounds__(P384K_BLOCK) p384_verify_keyed_kernel(uint32_t n, const uint32_t* __restrict__ key_id, const uint8_t* __restrict__ e,
                                                                         const uint8_t* __restrict__ r, const uint8_t* __restrict__ s,
                                                                         const uint32_t* __restrict__ gcomb, const P384SlotSnap* __restrict__ snap,
                                                                         uint32_t nkeys, uint64_t* __restrict__ verdict_bits,
-                                                                        uint8_t* __restrict__ status) {
+                                                                        uint8_t* __restrict__ status, const uint32_t* __restrict__ gcomb16,
+                                                                        const uint32_t* const* __restrict__ snap16,
+                                                                        unsigned long long* __restrict__ rows16) {
     const p384::CombPtr384 gt{gcomb};
     const uint32_t ntiles = (n - 1) / P384K_BLOCK + 1;           // (n >= 1; exact for every u32 n)
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -53,7 +64,20 @@ __global__ void __launch_bounds__(P384K_BLOCK) p384_verify_keyed_kernel(uint32_t
         load_e384<E32>(ve, e, ic);
         load_be_field48(vr, r, ic);
         load_be_field48(vs, s, ic);
-        const uint32_t st = p384::verify_core_keyed(ve, vr, vs, gt, qt, key_ok);
+        uint32_t st;
+        if constexpr (T16) {
+            const uint32_t* qtab16 = key_ok ? snap16[slot] : gcomb16;
+            if (__all(qtab16 != nullptr)) {
+                const p384::CombPtr384x16 gt16{gcomb16}, qt16{qtab16};
+                st = p384::verify_core_keyed(ve, vr, vs, gt16, qt16, key_ok);
+                const uint32_t rows = n - tile * P384K_BLOCK;
+                if (threadIdx.x == 0) atomicAdd(rows16, (unsigned long long)(rows < (uint32_t)P384K_BLOCK ? rows : (uint32_t)P384K_BLOCK));
+            } else {
+                st = p384::verify_core_keyed(ve, vr, vs, gt, qt, key_ok);
+            }
+        } else {
+            st = p384::verify_core_keyed(ve, vr, vs, gt, qt, key_ok);
+        }
         emit_verdict(i, active, st, verdict_bits, status);
     }
 }
@@ -65,12 +89,12 @@ hipError_t launch_p384_verify_keyed(const P384KeyedLaunch& v, hipStream_t st) {
     if (!v.key_id || !v.e || !v.r || !v.s || !v.gcomb || !v.verdict_bits || (v.nkeys && !v.snap) || v.nkeys > (1u << KEY_SLOT_BITS)) return hipErrorInvalidValue;
     const uint32_t ntiles = (v.n - 1) / P384K_BLOCK + 1;
     dim3 grid(ntiles < P384K_MAX_WGS ? ntiles : P384K_MAX_WGS), block(P384K_BLOCK);
-    if (v.e_is_digest32)
-        hipLaunchKernelGGL(p384_verify_keyed_kernel<true>, grid, block, 0, st, v.n, (const uint32_t*)v.key_id, (const uint8_t*)v.e, (const uint8_t*)v.r,
-                           (const uint8_t*)v.s, (const uint32_t*)v.gcomb, v.snap, v.nkeys, (uint64_t*)v.verdict_bits, (uint8_t*)v.status);
-    else
-        hipLaunchKernelGGL(p384_verify_keyed_kernel<false>, grid, block, 0, st, v.n, (const uint32_t*)v.key_id, (const uint8_t*)v.e, (const uint8_t*)v.r,
-                           (const uint8_t*)v.s, (const uint32_t*)v.gcomb, v.snap, v.nkeys, (uint64_t*)v.verdict_bits, (uint8_t*)v.status);
+    const bool t16 = v.gcomb16 && v.rows16 && (v.snap16 || !v.nkeys);
+    auto* kern = v.e_is_digest32 ? (t16 ? p384_verify_keyed_kernel<true, true> : p384_verify_keyed_kernel<true, false>)
+                                 : (t16 ? p384_verify_keyed_kernel<false, true> : p384_verify_keyed_kernel<false, false>);
+    hipLaunchKernelGGL(kern, grid, block, 0, st, v.n, (const uint32_t*)v.key_id, (const uint8_t*)v.e, (const uint8_t*)v.r, (const uint8_t*)v.s,
+                       (const uint32_t*)v.gcomb, v.snap, v.nkeys, (uint64_t*)v.verdict_bits, (uint8_t*)v.status, (const uint32_t*)v.gcomb16,
+                       (const uint32_t* const*)v.snap16, (unsigned long long*)v.rows16);
     return hipGetLastError();
 }
 

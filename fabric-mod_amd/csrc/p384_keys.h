@@ -4,6 +4,8 @@
 // the SNAPSHOT a keyed launch carries: per slot below the high-water mark the live tenant's table and generation, or
 // (nullptr, KTAB_GEN_NONE) for a slot between two tenants.  A snapshot is made from the book as it is at that moment and never
 // edited: a retired key is gone from every snapshot made after the retirement, whatever the device still runs.
+// With FABGPU_FLAG_P384_KEY_TABLES_16BIT a slot has a second address, the tenant's FINISHED 16-bit table (p384_tables16.h) or null; it
+// travels in the same snapshot (snapshot16) and leaves with the tenant.
 #pragma once
 #include <cstdint>
 #include <map>
@@ -38,26 +40,48 @@ public:
         const uint32_t slot = (uint32_t)slots.next_slot();
         if (slot >= tabs_.size()) {
             tabs_.resize((size_t)slot + 1, nullptr);
+            tabs16_.resize((size_t)slot + 1, nullptr);
             names_.resize((size_t)slot + 1);
         }
         tabs_[slot] = tab;
+        tabs16_[slot] = nullptr;
         names_[slot] = name;
         const uint32_t id = slots.take(slot);
         ids_[name] = id;
         return id;
     }
-    // 0: retired, *tab is the table the slot's drain has to keep until no launch reads it; 1: the id is not live
-    int retire(uint32_t id, uint32_t** tab) {
+    // 0: retired, *tab (and *tab16, the tenant's 16-bit table or null) is what the slot's drain has to keep until no launch reads it;
+    // 1: the id is not live
+    int retire(uint32_t id, uint32_t** tab, uint32_t** tab16 = nullptr) {
         if (!slots.live(id)) return 1;
         const uint32_t slot = KeySlots::slot_of(id);
         ids_.erase(names_[slot]);
         names_[slot].clear();
         *tab = tabs_[slot];
         tabs_[slot] = nullptr;
+        if (tab16) *tab16 = tabs16_[slot];
+        n_tabs16_ -= tabs16_[slot] ? 1u : 0u;
+        tabs16_[slot] = nullptr;
         slots.retire(id);
         return 0;
     }
     uint32_t* table(uint32_t id) const { return slots.live(id) ? tabs_[KeySlots::slot_of(id)] : nullptr; }
+    // The optional 16-bit table of a live key: set once, by whoever has seen its build finish.  false: the id is not live (any more).
+    bool set_table16(uint32_t id, uint32_t* tab16) {
+        if (!slots.live(id) || !tab16 || tabs16_[KeySlots::slot_of(id)]) return false;
+        tabs16_[KeySlots::slot_of(id)] = tab16;
+        n_tabs16_++;
+        return true;
+    }
+    uint32_t* table16(uint32_t id) const { return slots.live(id) ? tabs16_[KeySlots::slot_of(id)] : nullptr; }
+    uint32_t n_tables16() const { return n_tabs16_; }
+    // the second address per slot of a snapshot: the live tenant's finished 16-bit table, or null
+    std::vector<const uint32_t*> snapshot16() const {
+        std::vector<const uint32_t*> s(slots.high_water(), nullptr);
+        for (uint32_t k = 0; k < s.size(); k++)
+            if (slots.state(k) == KeySlots::LIVE) s[k] = tabs16_[k];
+        return s;
+    }
     std::vector<P384SlotSnap> snapshot() const {
         std::vector<P384SlotSnap> s(slots.high_water());
         for (uint32_t k = 0; k < s.size(); k++) {
@@ -69,6 +93,8 @@ public:
 
 private:
     std::vector<uint32_t*> tabs_;
+    std::vector<uint32_t*> tabs16_;
+    uint32_t n_tabs16_ = 0;
     std::vector<std::string> names_;
     std::map<std::string, uint32_t> ids_;
 };

@@ -25,9 +25,21 @@ struct CombTab384 {
     static FAB_HD size_t index(uint32_t w, uint32_t d) { return ((size_t)w * DIGITS + d) * ENTRY_WORDS; }
 };
 
+// the low eight bits of u; u >>= 8
+FAB_HD uint32_t take_low_byte(u384& u) {
+    const uint32_t d = u.w[0] & 0xffu;
+#pragma unroll
+    for (int i = 0; i < 11; i++) u.w[i] = (u.w[i] >> 8) | (u.w[i + 1] << 24);
+    u.w[11] >>= 8;
+    return d;
+}
+
 // A comb table as the core reads it: entry (w, d), d in 1 .. 255 -> affine point with Z = one.  t is 16-byte aligned.
+// Tab and take are what verify_core_keyed asks of a comb type: the window count, and the next digit of a scalar.
 struct CombPtr384 {
+    using Tab = CombTab384;
     const uint32_t* t;
+    static FAB_HD uint32_t take(u384& u) { return take_low_byte(u); }
     FAB_HD void load(jac& r, uint32_t w, uint32_t d) const {
         const u384 one = FAB_P384_ONE_MONT;
         const uint32_t* p = (const uint32_t*)__builtin_assume_aligned(t + CombTab384::index(w, d), 16);
@@ -40,19 +52,11 @@ struct CombPtr384 {
     }
 };
 
-// the low eight bits of u; u >>= 8
-FAB_HD uint32_t take_low_byte(u384& u) {
-    const uint32_t d = u.w[0] & 0xffu;
-#pragma unroll
-    for (int i = 0; i < 11; i++) u.w[i] = (u.w[i] >> 8) | (u.w[i + 1] << 24);
-    u.w[11] >>= 8;
-    return d;
-}
-
 // ECDSA verification of one tuple under a registered key: status 0 .. 4, the gate, the vocabulary and the precedence of verify_core.
 // gcomb: the generator's comb; qcomb: the key's.  key_ok == false: the row's id names no live key (p384_keyed_kernels.hip) - the caller
 // hands the generator's comb as qcomb, the whole stream runs, and the answer is 4 unless the gate refuses the row first.
-// The sum runs over 48 windows, lowest first, two mixed additions each (the order is free: every addition is the complete pt_add, so
+// The window count and the digit width are the comb types' (CombPtr384: 48 windows of 8 bits; p384_tables16.h CombPtr384x16: 24 of 16).
+// The sum runs over the windows, lowest first, two mixed additions each (the order is free: every addition is the complete pt_add, so
 // an accumulator at infinity, equal to the entry (-> the doubling) or opposite to it (-> infinity) is decided as crypto/elliptic
 // decides it).  A zero digit adds nothing: entry 1 is loaded, the sum computed and dropped - control flow is lane-uniform.
 template <class GComb, class QComb>
@@ -75,9 +79,10 @@ FAB_HD uint32_t verify_core_keyed(const u384& e, const u384& r_in, const u384& s
     fn_from_mont(u2, u2);
 
     jac acc = pt_infinity();
-    for (uint32_t w = 0; w < (uint32_t)CombTab384::WINDOWS; w++) {
+    static_assert(GComb::Tab::WINDOWS == QComb::Tab::WINDOWS && GComb::Tab::BITS == QComb::Tab::BITS, "both combs of a call have one digit width");
+    for (uint32_t w = 0; w < (uint32_t)GComb::Tab::WINDOWS; w++) {
         jac t, sum;
-        const uint32_t d1 = take_low_byte(u1), d2 = take_low_byte(u2);
+        const uint32_t d1 = GComb::take(u1), d2 = QComb::take(u2);
         gcomb.load(t, w, d1 ? d1 : 1u);
         pt_add<true>(sum, acc, t);
         sel_pt(acc, d1 != 0, sum, acc);

@@ -16,6 +16,7 @@
 #include "idemix_host.h"
 #include "p384_keys.h"
 #include "p384_tables.h"
+#include "p384_tables16.h"
 
 using namespace fab::bccsp;
 
@@ -401,6 +402,18 @@ int fabgpu_test_p384_verify_keyed_host(const uint32_t* gcomb, const uint32_t* qc
     return (int)fab::p384::verify_keyed_host(gcomb, qcomb, e48, r48, s48, key_ok != 0);
 }
 int fabgpu_test_p384_key_register_batch(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t* key_ids) { return fab::p384_key_register_batch_hook(ctx, n, qxy, key_ids); }
+int fabgpu_test_p384_tables16_wait(fabgpu_ctx* ctx) { return fab::p384_tables16_wait(ctx); }
+int fabgpu_test_p384_tables16_cap(fabgpu_ctx* ctx, uint32_t cap) { return fab::p384_tables16_cap(ctx, cap); }
+int fabgpu_test_p384_key_table16(fabgpu_ctx* ctx, uint32_t key_id, int generator, uint64_t* bad, uint32_t* out_words, size_t cap_words) {
+    if (out_words && cap_words < 3 * fab::p384::CombTab384x16::WINDOW_WORDS) return FABGPU_ETOOBIG;
+    return fab::p384_key_table16_check(ctx, key_id, generator, bad, out_words);
+}
+int fabgpu_test_p384_key_table16_host(const uint32_t* tab8, uint32_t w_begin, uint32_t w_end, uint32_t* out_words, size_t cap_words) {
+    if (!tab8 || !out_words || w_begin > w_end || w_end > (uint32_t)fab::p384::CombTab384x16::WINDOWS) return FABGPU_EINVAL;
+    if (cap_words < (size_t)(w_end - w_begin) * fab::p384::CombTab384x16::WINDOW_WORDS) return FABGPU_ETOOBIG;
+    fab::p384::build_comb384x16(tab8, w_begin, w_end, out_words);
+    return FABGPU_OK;
+}
 void* fabgpu_test_p384_book_new(uint32_t gen_last) { return new fab::P384KeyBook(gen_last); }
 void fabgpu_test_p384_book_free(void* h) { delete (fab::P384KeyBook*)h; }
 long long fabgpu_test_p384_book_register(void* h, const uint8_t* name96, uint64_t tab_tag) {

@@ -41,6 +41,7 @@ FLAG_PAIR_SOLO = 1024        # fabgpu.h: ... in LDS, one wave per SIMD (no helpe
 FLAG_PAIR_DBL1 = 2048        # fabgpu.h: ... in LDS, the per-doubling loop instead of the four-doubling program (A/B runs and parity tests)
 FLAG_KEY_TABLES_16BIT = 256  # fabgpu.h: registered keys also get a 16-bit comb (80 MiB each, built behind the registration)
 FLAG_NO_WIDE = 32            # fabgpu.h: registered keys never on the eight-lanes-per-signature two-phase kernels (launches <= 8 192 signatures)
+FLAG_P384_KEY_TABLES_16BIT = 8192   # fabgpu.h: registered P-384 keys also get 16-bit comb tables (144 MiB each, <= 32 per context; off by default)
 FLAG_P384_WIDE = 4096        # fabgpu.h: registered P-384 keys on eight lanes per signature, two launches, for keyed launches <= 8 192 rows (off by default)
 ST_VALID, ST_BAD_MATH, ST_HIGH_S, ST_RANGE, ST_OFF_CURVE = 0, 1, 2, 3, 4
 
@@ -125,7 +126,7 @@ KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "live_16bit", "bytes_
 # ... followed by fabgpu_csp_p384_pass_wide_rows
 P384_PASS_STATS = ("stages", "seen", "submitted", "keyed_launches", "fresh_launches", "audited", "memo_seeded", "sha3_rows", "wide_rows")
 # ... and fabgpu_p384_key_table_stats
-P384_KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "keyed_launches", "bytes_held", "slots_used")
+P384_KEY_TABLE_STATS = ("live", "draining", "reused", "parked", "keyed_launches", "bytes_held", "slots_used", "tables16_live", "tables16_bytes")
 P384_COMB_WORDS = 48 * 256 * 24      # one P-384 comb table (csrc/p384_tables.h CombTab384): 1.125 MiB
 
 # every symbol include/fabgpu.h and include/fabgpu_bccsp.h declare (tests check the export list)
@@ -169,7 +170,7 @@ ABI_SYMBOLS = [
     "fabgpu_identity_verify_batch_p384", "fabgpu_identity_verify_batch_p384_dev", "fabgpu_identity_verify_batch_p384_sha3",
     "fabgpu_identity_verify_batch_p384_sha3_dev", "fabgpu_identity_to_p384", "fabgpu_csp_p384_pass_stats", "fabgpu_csp_msp_hash_family", "fabgpu_csp_msp_hash_family_get",
     "fabgpu_csp_memo_lookup_p384", "fabgpu_csp_memo_stats_p384", "fabgpu_csp_memo_set_capacity_p384",
-    "fabgpu_p384_wide_rows", "fabgpu_csp_p384_pass_wide_rows",
+    "fabgpu_p384_wide_rows", "fabgpu_csp_p384_pass_wide_rows", "fabgpu_p384_tables16_rows",
 ]
 
 # what libfabgpu_testhooks.so exports (fabric-mod_amd/csrc/fabgpu_testhooks.h): probes, walker comparisons, the synthetic block generator, the
@@ -184,6 +185,7 @@ HOOK_SYMBOLS = [
     "fabgpu_test_p384_key_table", "fabgpu_test_p384_key_table_host", "fabgpu_test_p384_verify_keyed_host", "fabgpu_test_p384_key_register_batch",
     "fabgpu_test_p384_book_new", "fabgpu_test_p384_book_free", "fabgpu_test_p384_book_register", "fabgpu_test_p384_book_lookup",
     "fabgpu_test_p384_book_retire", "fabgpu_test_p384_book_snapshot",
+    "fabgpu_test_p384_tables16_wait", "fabgpu_test_p384_tables16_cap", "fabgpu_test_p384_key_table16", "fabgpu_test_p384_key_table16_host",
 ]
 _HOOKS_PATH = os.path.join(os.path.dirname(_LIB_PATH), "libfabgpu_testhooks.so")
 
@@ -249,6 +251,10 @@ def load_hooks():
     H.fabgpu_test_p384_key_table_host.argtypes = [ctypes.c_char_p, ctypes.c_char_p, _u32p, _sz]
     H.fabgpu_test_p384_verify_keyed_host.argtypes = [_u32p, _u32p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]
     H.fabgpu_test_p384_key_register_batch.argtypes = [_vp, ctypes.c_int, ctypes.c_char_p, _u32p]
+    H.fabgpu_test_p384_tables16_wait.argtypes = [_vp]
+    H.fabgpu_test_p384_tables16_cap.argtypes = [_vp, ctypes.c_uint32]
+    H.fabgpu_test_p384_key_table16.argtypes = [_vp, ctypes.c_uint32, ctypes.c_int, _u64p, _u32p, _sz]
+    H.fabgpu_test_p384_key_table16_host.argtypes = [_u32p, ctypes.c_uint32, ctypes.c_uint32, _u32p, _sz]
     H.fabgpu_test_p384_book_new.argtypes = [ctypes.c_uint32]
     H.fabgpu_test_p384_book_new.restype = _vp
     H.fabgpu_test_p384_book_free.argtypes = [_vp]
@@ -340,6 +346,7 @@ def load():
     L.fabgpu_csp_p384_pass_stats.argtypes = [_vp, _u64p, ctypes.c_int]
     L.fabgpu_csp_p384_pass_wide_rows.argtypes = [_vp, _u64p]
     L.fabgpu_p384_wide_rows.argtypes = [_vp, _u64p]
+    L.fabgpu_p384_tables16_rows.argtypes = [_vp, _u64p]
     L.fabgpu_csp_msp_hash_family.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
     L.fabgpu_csp_msp_hash_family_get.argtypes = [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
     L.fabgpu_idemix_issuer_register.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _u32p]
@@ -679,6 +686,12 @@ class Context:
         if n != len(P384_KEY_TABLE_STATS):
             raise FabgpuError("fabgpu_p384_key_table_stats: %s" % strerror(n))
         return dict(zip(P384_KEY_TABLE_STATS, (int(x) for x in v)))
+
+    def p384_tables16_rows(self) -> int:
+        """fabgpu_p384_tables16_rows: rows of the wavefronts of keyed P-384 launches that ran on 16-bit tables (FLAG_P384_KEY_TABLES_16BIT)."""
+        v = ctypes.c_uint64(0)
+        _check(self._L.fabgpu_p384_tables16_rows(self._h, ctypes.byref(v)), "fabgpu_p384_tables16_rows")
+        return int(v.value)
 
     def p384_wide_rows(self) -> int:
         """fabgpu_p384_wide_rows: rows of keyed P-384 launches this context handed to the eight-lanes-per-signature form (FLAG_P384_WIDE)."""
@@ -1065,7 +1078,8 @@ class GPUCSP:
     """The accelerated verbs of bccsp.BCCSP (bccsp/bccsp.go:90-134); everything else the Go provider delegates to bccsp/sw."""
 
     def __init__(self, device: int = -1, devices: Optional[Sequence[int]] = None, flags: int = 0, concurrent_passes: int = 0,
-                 expect_block_bytes: int = 0, expect_tuples: int = 0, retire_evicted_keys: int = 0, hash_sha3: int = 0, p384: int = 0, p384_wide: int = 0, **switches):
+                 expect_block_bytes: int = 0, expect_tuples: int = 0, retire_evicted_keys: int = 0, hash_sha3: int = 0, p384: int = 0, p384_wide: int = 0,
+                 p384_key_tables16: int = 0, **switches):
         """device: ONE context on that HIP ordinal (fabgpu_csp_new).  devices: one context per entry - an ordinal may repeat; an empty
         list means every visible device - behind ONE provider (fabgpu_csp_new2: what bccsp/factory builds from the `GPU:` section).
         switches: pass_device_walk / pass_stage_min_bytes / pass_device_memo / pass_host_counts / pass_timing / pass_hash_memo (0 default,
@@ -1075,7 +1089,10 @@ class GPUCSP:
         same name; key_table_stats).  hash_sha3 (0, the default: off): hash(msg, SHA3_256Opts()) and identities of the SHA3 hash family are
         served on the device (set_option of the same name).  p384_wide (0, the default: off): FLAG_P384_WIDE on every context, read at
         construction - keyed P-384 launches of at most 8 192 rows on eight lanes per signature (set_option of the same name switches the
-        living contexts)."""
+        living contexts).  p384_key_tables16 (0, the default: off): FLAG_P384_KEY_TABLES_16BIT on every context, read at construction -
+        every imported P-384 key also gets a 16-bit comb table."""
+        if p384_key_tables16 > 0:
+            flags |= FLAG_P384_KEY_TABLES_16BIT
         if p384_wide > 0:
             flags |= FLAG_P384_WIDE
         L = load()
@@ -1264,6 +1281,12 @@ class GPUCSP:
         _check(self._L.fabgpu_csp_key_import_p384(self._h, key[0].to_bytes(48, "big"), key[1].to_bytes(48, "big"), ctypes.byref(on), err, 256),
                "fabgpu_csp_key_import_p384")
         return bool(on.value), err.value.decode()
+
+    def p384_tables16_rows(self, d: int = 0) -> int:
+        """fabgpu_p384_tables16_rows of the provider's device d."""
+        v = ctypes.c_uint64(0)
+        _check(self._L.fabgpu_p384_tables16_rows(self._L.fabgpu_csp_ctx_of(self._h, d), ctypes.byref(v)), "fabgpu_p384_tables16_rows")
+        return int(v.value)
 
     def p384_key_table_stats(self, d: int = 0) -> dict:
         """fabgpu_p384_key_table_stats of the provider's device d."""
@@ -1681,6 +1704,42 @@ def p384_comb_device(ctx: "Context", key_id: int = 0, generator: bool = False) -
     """TEST HOOK: the comb table of a registered P-384 key (generator: of the generator) as it lies on the device."""
     out = np.zeros(P384_COMB_WORDS, dtype=np.uint32)
     _check(load_hooks().fabgpu_test_p384_key_table(ctx._h, int(key_id), int(generator), out.ctypes.data_as(_u32p), out.size), "fabgpu_test_p384_key_table")
+    return out
+
+
+P384_COMB16_WINDOW_WORDS = 65536 * 24      # one window of a 16-bit P-384 comb table (csrc/p384_tables16.h CombTab384x16): 6 MiB
+
+
+def p384_tables16_wait(ctx: "Context") -> int:
+    """TEST HOOK: every queued 16-bit build of the context waited for and published; the number of live 16-bit tables."""
+    n = load_hooks().fabgpu_test_p384_tables16_wait(ctx._h)
+    if n < 0:
+        raise FabgpuError("fabgpu_test_p384_tables16_wait: %s" % strerror(n))
+    return n
+
+
+def p384_tables16_cap(ctx: "Context", cap: int) -> None:
+    """TEST HOOK: at most `cap` live 16-bit tables for the registrations that follow."""
+    _check(load_hooks().fabgpu_test_p384_tables16_cap(ctx._h, cap), "fabgpu_test_p384_tables16_cap")
+
+
+def p384_comb16_check(ctx: "Context", key_id: int = 0, generator: bool = False, windows: bool = True):
+    """TEST HOOK: (bad, w) - how many entries of the key's 16-bit table differ from the sum of the two 8-bit entries recomputed on the
+    device, and (windows) its windows 0, 11 and 23 as they lie there, 3 x P384_COMB16_WINDOW_WORDS words.  None: the key has no 16-bit table."""
+    bad = ctypes.c_uint64(0)
+    out = np.zeros(3 * P384_COMB16_WINDOW_WORDS, dtype=np.uint32) if windows else None
+    rc = load_hooks().fabgpu_test_p384_key_table16(ctx._h, int(key_id), int(generator), ctypes.byref(bad),
+                                                   out.ctypes.data_as(_u32p) if windows else None, out.size if windows else 0)
+    if rc == 1:
+        return None
+    _check(rc, "fabgpu_test_p384_key_table16")
+    return int(bad.value), out
+
+
+def p384_comb16_host(tab8: np.ndarray, w_begin: int, w_end: int) -> np.ndarray:
+    """TEST HOOK: windows [w_begin, w_end) of the 16-bit table the host builder makes from an 8-bit table of p384_comb_host."""
+    out = np.zeros((w_end - w_begin) * P384_COMB16_WINDOW_WORDS, dtype=np.uint32)
+    _check(load_hooks().fabgpu_test_p384_key_table16_host(tab8.ctypes.data_as(_u32p), w_begin, w_end, out.ctypes.data_as(_u32p), out.size), "fabgpu_test_p384_key_table16_host")
     return out
 
 

@@ -80,6 +80,10 @@ type GPUOpts struct {
 	// P384Wide: registered P-384 keys are verified with eight lanes per signature in launches of at most 8 192 rows (fabgpu.h
 	// FABGPU_FLAG_P384_WIDE, fabgpu_bccsp.h option "p384_wide").  Default false.  Verdicts do not depend on it; it needs P384.
 	P384Wide bool `mapstructure:"p384wide" json:"p384wide,omitempty" yaml:"P384Wide,omitempty"`
+	// P384KeyTables16: every imported P-384 key also gets a 16-bit comb table on the device, 144 MiB each and at most 32 per context
+	// (fabgpu.h FABGPU_FLAG_P384_KEY_TABLES_16BIT, fabgpu_bccsp.h option "p384_key_tables16").  Default false.  Verdicts do not depend
+	// on it; it needs P384.
+	P384KeyTables16 bool `mapstructure:"p384keytables16" json:"p384keytables16,omitempty" yaml:"P384KeyTables16,omitempty"`
 }
 
 // DefaultAuditPermille is what GPUOpts.AuditPermille means when the `GPU:` section does not set it.
@@ -118,6 +122,7 @@ func (f *GPUFactory) Get(config *FactoryOpts) (bccsp.BCCSP, error) {
 			NoHashMemo: g.NoHashMemo, HashMemoBlocks: g.HashMemoBlocks, KeyTables16: g.KeyTables16, AuditPermille: DefaultAuditPermille, RetireEvictedKeys: true, SHA3: true}
 		opts.P384 = g.P384
 		opts.P384Wide = g.P384Wide
+		opts.P384KeyTables16 = g.P384KeyTables16
 		if g.SHA3 != nil {
 			opts.SHA3 = *g.SHA3
 		}

@@ -161,6 +161,10 @@ type Options struct {
 	// P384Wide: FABGPU_FLAG_P384_WIDE on every context - keyed P-384 launches of at most 8 192 rows run with eight lanes per signature
 	// (a 1 000-transaction P-384 block is 4 000 rows: a sixteenth of what fills the chip one signature per lane).  False by default.
 	P384Wide bool
+	// P384KeyTables16: FABGPU_FLAG_P384_KEY_TABLES_16BIT on every context - each imported P-384 key also gets a 16-bit comb table
+	// (144 MiB, at most 32 per context), and keyed launches run 24 windows of two additions on the wavefronts all of whose keys have
+	// one.  False by default.  Verdicts do not depend on it.
+	P384KeyTables16 bool
 }
 
 // SetCoalesce switches the coalesced device path for memo misses on or off (GPUOpts.CoalesceVerify in gpufactory.go).
@@ -250,6 +254,9 @@ func New(swCSP bccsp.BCCSP, opts Options) (bccsp.BCCSP, error) {
 	}
 	if opts.P384Wide {
 		o.ctx_flags |= 4096 // fabgpu.h FABGPU_FLAG_P384_WIDE
+	}
+	if opts.P384KeyTables16 {
+		o.ctx_flags |= 8192 // fabgpu.h FABGPU_FLAG_P384_KEY_TABLES_16BIT
 	}
 	if opts.HostWalk {
 		o.pass_device_walk = -1

@@ -94,6 +94,15 @@ typedef struct fabgpu_ctx fabgpu_ctx;
                                         tree) instead of one signature per lane.  Off by default.  The context allocates the scratch between
                                         the two launches (8 192 x 100 bytes) at fabgpu_init.  Statuses and verdict words do not change */
 
+#define FABGPU_FLAG_P384_KEY_TABLES_16BIT 8192u   /* registered P-384 keys (fabgpu_p384_key_register): each key also gets a 16-bit comb
+                                        table - 24 windows x 65 536 entries, 144 MiB - built on the device BEHIND the registration
+                                        (nobody waits for it), for up to FABGPU_P384_MAX_TABLES16 live keys (4.5 GiB); the
+                                        generator's is built once, beside its 8-bit table.  A wavefront all of whose keys have one
+                                        verifies with 48 mixed additions instead of 96; any other wavefront, and every eight-lane
+                                        launch of FABGPU_FLAG_P384_WIDE, reads the 8-bit tables as before.  Off by default.
+                                        Statuses and verdict words do not change */
+#define FABGPU_P384_MAX_TABLES16 32
+
 typedef struct fabgpu_cfg {
     int32_t device;      /* HIP device ordinal; -1 = the current device */
     uint32_t max_batch;  /* staging pre-allocation hint in tuples (0 = grow on demand) */
@@ -250,13 +259,22 @@ int fabgpu_sha3_256_p384_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void*
  * A stream handed to a keyed _dev entry point must be idle when the caller destroys it.
  * fabgpu_p384_key_table_stats: out[0 .. min(cap, FABGPU_P384_KEY_TABLE_STATS)): live keys, slots draining, registrations that reused
  * a slot, slots parked for good, keyed P-384 launches queued so far, bytes of device memory the tables hold (the generator's
- * included), slots ever used.  Returns FABGPU_P384_KEY_TABLE_STATS.
+ * included), slots ever used, live 16-bit tables, bytes those hold (FABGPU_FLAG_P384_KEY_TABLES_16BIT; the generator's 16-bit table
+ * and tables kept for reuse are in neither).  Returns FABGPU_P384_KEY_TABLE_STATS; the first seven values are what a caller with
+ * cap = 7 has always got.
  * FABGPU_FLAG_P384_WIDE: every keyed P-384 launch of at most 8 192 rows - the three direct entry points below, their _dev twins, the
  * keyed branch of fabgpu_identity_verify_batch_p384[_sha3][_dev] - takes the eight-lanes-per-signature form; larger launches, and every
  * launch of a context without the flag, are the one-lane kernel's.  fabgpu_p384_wide_rows: *rows = the rows this context has handed to
  * the eight-lane form so far.
- * NOT served for P-384: 16-bit tables, the memos, fabgpu_multi_*. */
+ * FABGPU_FLAG_P384_KEY_TABLES_16BIT: a registration also queues the key's 16-bit table and returns without waiting; the table serves
+ * from the first launch queued after its build has finished (the launch path asks, it never waits).  Keys beyond
+ * FABGPU_P384_MAX_TABLES16 live tables, and keys whose 144 MiB could not be allocated, stay on their 8-bit tables.  Unregistering
+ * retires the 16-bit table with the key; a key registered into the slot later gets one of its own.  The one-lane keyed kernel chooses
+ * per wavefront of 64 rows; fabgpu_p384_tables16_rows: *rows = the rows of the wavefronts that ran on 16-bit tables so far (0 without
+ * the flag).  The eight-lane form reads 8-bit tables only: with both flags a launch of at most 8 192 rows runs wide as before.
+ * NOT served for P-384: the digest memo, fabgpu_multi_*. */
 int fabgpu_p384_wide_rows(fabgpu_ctx* ctx, uint64_t* rows);
+int fabgpu_p384_tables16_rows(fabgpu_ctx* ctx, uint64_t* rows);
 int fabgpu_p384_key_register(fabgpu_ctx* ctx, const uint8_t* qx48, const uint8_t* qy48, uint32_t* key_id);
 /* The same key on n contexts, each building its own table; contexts fed the same sequence of calls hand out the same ids.
  * key_ids[g] = the key's id on ctxs[g].  The first failure is returned (contexts before it keep the key). */
@@ -264,7 +282,7 @@ int fabgpu_p384_key_register_many(fabgpu_ctx* const* ctxs, int n, const uint8_t*
 int fabgpu_p384_key_lookup(fabgpu_ctx* ctx, const uint8_t* qx48, const uint8_t* qy48, uint32_t* key_id); /* 0 found, 1 not registered */
 int fabgpu_p384_key_count(fabgpu_ctx* ctx);                      /* live keys */
 int fabgpu_p384_key_unregister(fabgpu_ctx* ctx, uint32_t key_id); /* 0 retired, 1 the id is not live */
-#define FABGPU_P384_KEY_TABLE_STATS 7
+#define FABGPU_P384_KEY_TABLE_STATS 9
 int fabgpu_p384_key_table_stats(fabgpu_ctx* ctx, uint64_t* out, int cap);
 int fabgpu_p384_verify_batch_keyed(fabgpu_ctx* ctx, size_t n, const uint32_t* key_id, const uint8_t* e, const uint8_t* r,
                                    const uint8_t* s, uint64_t* verdict_bits, uint8_t* status);

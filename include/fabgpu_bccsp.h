@@ -90,6 +90,10 @@ int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pa
  * with eight lanes per signature (fabgpu.h).  It is a context flag: a provider reads it at construction from ctx_flags; set on a living
  * provider, it switches every context for the launches queued from then on (and makes their scratch in that call).  Verdicts, statuses
  * and flags do not depend on it.
+ * "p384_key_tables16" (default off; read-only on a living provider): FABGPU_FLAG_P384_KEY_TABLES_16BIT on every context of the pool, read
+ * at construction from ctx_flags - every imported P-384 key also gets a 16-bit comb table (144 MiB, at most 32 per context), and the
+ * keyed batches of fabgpu_csp_verify_batch_p384, the identity batches, the coalescer and the pass stage run 24 windows on the
+ * wavefronts all of whose keys have one (fabgpu.h).  Verdicts, statuses and flags do not depend on it.
  * FABGPU_EINVAL: no such option. */
 int fabgpu_csp_set_option(fabgpu_csp* csp, const char* name, int64_t value, int64_t* previous);
 int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value);
