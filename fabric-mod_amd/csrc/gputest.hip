@@ -3,7 +3,8 @@
 //     output register with the reference interpreter of gcn_dsl.py;
 //   * the device compilation of the product headers one primitive at a time (field, scalar, inversion, point and scalar-loop code)
 //     over grids of many wavefronts, for tests/test_device_primitives.py to compare with big integers ("primitives on many
-//     wavefronts", below).
+//     wavefronts", below), and the same for the full-word P-384 code of p384.h, p384_dev.h, p384_tables.h, p384_tables16.h and
+//     p384_wide.h, for tests/test_p384_device_primitives.py ("P-384 primitives on many wavefronts", at the end).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -16,6 +17,9 @@
 #include "bn_quad29.h"
 #include "bn_tables29.h"
 #include "device_common.h"
+#include "p384_dev.h"        // p384.h and the row loads of the P-384 kernels
+#include "p384_tables16.h"   // p384_tables.h and the 16-bit comb's digit accessor
+#include "p384_wide.h"
 
 using namespace fab;
 
@@ -697,5 +701,178 @@ extern "C" int gputest_combined(int keyed, uint32_t n, const uint8_t* key_xy64, 
     hipLaunchKernelGGL(gputest_combined_kernel, grid, dim3(PRIM_BLOCK), 0, 0, keyed, n, din, dtab, dkt, dws, dout);
     int rc = prim_sync();
     if (rc == 0 && !prim_back(out, dout, (size_t)n * 28 * 4)) rc = -4;
+    return rc;
+}
+
+// ---- P-384 primitives on many wavefronts ---------------------------------------------------------------------------------------------
+// The DEVICE compilation of p384.h (under __HIP_DEVICE_COMPILE__ mont_mul is ONE out-of-line function taking two u384 by value, which
+// pt_add calls from inside its only divergent branch), the row loads of p384_dev.h and the digit accessors of p384_tables.h,
+// p384_tables16.h and p384_wide.h, one primitive at a time, for tests/test_p384_device_primitives.py to compare with Python integers.
+// One lane per item over the PRIM_BLOCK grids above; lanes past the end clamp to the last item and write nothing.
+//
+// Field and scalar code.  FIELD: the modulus is p, else n.  a, b: 48 big-endian bytes per item, read by load_be_field48 (form 1: a is
+// 32 bytes per item, read by load_e384<true>); out48: 48 big-endian bytes per item through to_be48; flag: one word per item.
+// op:  0 mont_mul<FIELD>(a, b), raw (through fp_mul / fn_mul)   1 mod_add(a, b, m)   2 mod_sub(a, b, m)   3 to_mont(a)   4 from_mont(a)
+//      5 a b as plain integers (to_mont both, product, from_mont)   6 a^2 likewise   7 a^-1 likewise (fp_inv / fn_inv; 0 -> 0)
+//      8 fn_reduce_once(a)   9 add384(a, b), flag = carry   10 sub384(a, b), flag = borrow   11 flag = lt384(a, b)
+//      12 flag = eq384(a, b)   13 flag = is_zero(a)   14 flag = range_status(r = a, s = b)   15 a itself (load, then store)
+// Ops 11 .. 14 store a as out48.
+template <bool FIELD>
+__global__ void __launch_bounds__(PRIM_BLOCK) gputest_p384_field_kernel(int op, int form, uint32_t n, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                                         uint8_t* __restrict__ out48, uint32_t* __restrict__ flag) {
+    const uint32_t i = blockIdx.x * PRIM_BLOCK + threadIdx.x;
+    const bool active = i < n;
+    const uint32_t ic = active ? i : n - 1;
+    const p384::u384 P = FAB_P384_P, N = FAB_P384_N;
+    const p384::u384& M = FIELD ? P : N;
+    p384::u384 A, B, Rr, am, bm;
+    if (form) load_e384<true>(A, a, ic);
+    else load_e384<false>(A, a, ic);
+    load_be_field48(B, b, ic);
+    Rr = A;
+    uint32_t f = 0;
+    switch (op) {
+        case 0:
+            if (FIELD) p384::fp_mul(Rr, A, B);
+            else p384::fn_mul(Rr, A, B);
+            break;
+        case 1: p384::mod_add(Rr, A, B, M); break;
+        case 2: p384::mod_sub(Rr, A, B, M); break;
+        case 3:
+            if (FIELD) p384::fp_to_mont(Rr, A);
+            else p384::fn_to_mont(Rr, A);
+            break;
+        case 4:
+            if (FIELD) p384::fp_from_mont(Rr, A);
+            else p384::fn_from_mont(Rr, A);
+            break;
+        case 5:
+        case 6:
+        case 7:
+            if (FIELD) {
+                p384::fp_to_mont(am, A);
+                p384::fp_to_mont(bm, B);
+                if (op == 5) p384::fp_mul(Rr, am, bm);
+                else if (op == 6) p384::fp_sqr(Rr, am);
+                else p384::fp_inv(Rr, am);
+                p384::fp_from_mont(Rr, Rr);
+            } else {
+                p384::fn_to_mont(am, A);
+                p384::fn_to_mont(bm, B);
+                if (op == 5) p384::fn_mul(Rr, am, bm);
+                else if (op == 6) p384::fn_mul(Rr, am, am);
+                else p384::fn_inv(Rr, am);
+                p384::fn_from_mont(Rr, Rr);
+            }
+            break;
+        case 8: p384::fn_reduce_once(Rr, A); break;
+        case 9: f = p384::add384(Rr, A, B); break;
+        case 10: f = p384::sub384(Rr, A, B); break;
+        case 11: f = p384::lt384(A, B) ? 1u : 0u; break;
+        case 12: f = p384::eq384(A, B) ? 1u : 0u; break;
+        case 13: f = p384::is_zero(A) ? 1u : 0u; break;
+        case 14: f = p384::range_status(A, B); break;
+        default: break;
+    }
+    if (active) {
+        p384::to_be48(out48 + 48 * (size_t)i, Rr);
+        flag[i] = f;
+    }
+}
+
+// modulus: 1 p, 0 n.  0 ok, -1 allocation or copy in, -2 launch or kernel, -3 arguments, -4 copy out.
+extern "C" int gputest_p384_field_op(int modulus, int op, int form, uint32_t n, const uint8_t* a, const uint8_t* b, uint8_t* out48, uint32_t* flag) {
+    if ((modulus | 1) != 1 || op < 0 || op > 15 || (form | 1) != 1 || n == 0 || n > PRIM_MAX_ITEMS || !a || !b || !out48 || !flag) return -3;
+    DevBufs d;
+    const uint8_t* da = (const uint8_t*)d.put(a, (size_t)n * (form ? 32 : 48));
+    const uint8_t* db = (const uint8_t*)d.put(b, (size_t)n * 48);
+    uint8_t* dout = (uint8_t*)d.get((size_t)n * 48);
+    uint32_t* df = (uint32_t*)d.get((size_t)n * 4);
+    if (!da || !db || !dout || !df) return -1;
+    if (modulus) hipLaunchKernelGGL(gputest_p384_field_kernel<true>, prim_grid(n), dim3(PRIM_BLOCK), 0, 0, op, form, n, da, db, dout, df);
+    else hipLaunchKernelGGL(gputest_p384_field_kernel<false>, prim_grid(n), dim3(PRIM_BLOCK), 0, 0, op, form, n, da, db, dout, df);
+    int rc = prim_sync();
+    if (rc == 0 && !(prim_back(out48, dout, (size_t)n * 48) && prim_back(flag, df, (size_t)n * 4))) rc = -4;
+    return rc;
+}
+
+// The digits of a scalar as every P-384 core takes them.  a: 48 big-endian bytes per item;  out per item, GPUTEST_P384_DIGIT_WORDS words:
+//   [0, 96)     take_top_nibble, 96 calls in order (p384.h: verify_core)
+//   [96, 144)   wide_digit(w), w = 0 .. 47 (p384_wide.h)
+//   [144, 192)  take_low_byte, 48 calls in order (p384_tables.h: CombPtr384::take)
+//   [192, 216)  take_low_half, 24 calls in order (p384_tables16.h: CombPtr384x16::take)
+constexpr uint32_t GPUTEST_P384_DIGIT_WORDS = 216;
+__global__ void __launch_bounds__(PRIM_BLOCK) gputest_p384_digits_kernel(uint32_t n, const uint8_t* __restrict__ a, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * PRIM_BLOCK + threadIdx.x;
+    const bool active = i < n;
+    const uint32_t ic = active ? i : n - 1;
+    p384::u384 A, u;
+    load_be_field48(A, a, ic);
+    if (!active) return;                       // nothing below talks to another lane
+    uint32_t* o = out + GPUTEST_P384_DIGIT_WORDS * (size_t)i;
+    u = A;
+    for (int k = 0; k < 96; k++) o[k] = p384::take_top_nibble(u);
+    for (uint32_t w = 0; w < 48; w++) o[96 + w] = p384::wide_digit(A.w, w);
+    u = A;
+    for (int k = 0; k < 48; k++) o[144 + k] = p384::CombPtr384::take(u);
+    u = A;
+    for (int k = 0; k < 24; k++) o[192 + k] = p384::CombPtr384x16::take(u);
+}
+
+extern "C" int gputest_p384_digits(uint32_t n, const uint8_t* a, uint32_t* out) {
+    if (n == 0 || n > PRIM_MAX_ITEMS || !a || !out) return -3;
+    DevBufs d;
+    const uint8_t* da = (const uint8_t*)d.put(a, (size_t)n * 48);
+    uint32_t* dout = (uint32_t*)d.get((size_t)n * GPUTEST_P384_DIGIT_WORDS * 4);
+    if (!da || !dout) return -1;
+    hipLaunchKernelGGL(gputest_p384_digits_kernel, prim_grid(n), dim3(PRIM_BLOCK), 0, 0, n, da, dout);
+    int rc = prim_sync();
+    if (rc == 0 && !prim_back(out, dout, (size_t)n * GPUTEST_P384_DIGIT_WORDS * 4)) rc = -4;
+    return rc;
+}
+
+// The point operations on raw words.  in per item: X1 Y1 Z1 X2 Y2 Z2, twelve little-endian words each, canonical Montgomery form (the
+// caller chooses Z and with it the representative);  out per item: X Y Z (36 words), flag.
+// op: 0 pt_dbl(first)   1 pt_add<false>   2 pt_add<true> (Z2 is one)   3 flag = on_curve(X1, Y1)
+//     4 flag = x_equals_r(first, r), r = the twelve words of the X2 slot as a plain integer.   Ops 3 and 4 store the first triple.
+__global__ void __launch_bounds__(PRIM_BLOCK) gputest_p384_point_kernel(int op, uint32_t n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                                         uint32_t* __restrict__ flag) {
+    const uint32_t i = blockIdx.x * PRIM_BLOCK + threadIdx.x;
+    const bool active = i < n;
+    const uint32_t ic = active ? i : n - 1;
+    const uint32_t* p = in + 72 * (size_t)ic;
+    p384::jac P1, P2, Rr;
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        P1.X.w[k] = p[k]; P1.Y.w[k] = p[12 + k]; P1.Z.w[k] = p[24 + k];
+        P2.X.w[k] = p[36 + k]; P2.Y.w[k] = p[48 + k]; P2.Z.w[k] = p[60 + k];
+    }
+    Rr = P1;
+    uint32_t f = 0;
+    if (op == 0) p384::pt_dbl(Rr, P1);
+    else if (op == 1) p384::pt_add<false>(Rr, P1, P2);
+    else if (op == 2) p384::pt_add<true>(Rr, P1, P2);
+    else if (op == 3) f = p384::on_curve(P1.X, P1.Y) ? 1u : 0u;
+    else f = p384::x_equals_r(P1, P2.X) ? 1u : 0u;
+    if (active) {
+        uint32_t* o = out + 36 * (size_t)i;
+#pragma unroll
+        for (int k = 0; k < 12; k++) {
+            o[k] = Rr.X.w[k]; o[12 + k] = Rr.Y.w[k]; o[24 + k] = Rr.Z.w[k];
+        }
+        flag[i] = f;
+    }
+}
+
+extern "C" int gputest_p384_point_op(int op, uint32_t n, const uint32_t* in, uint32_t* out, uint32_t* flag) {
+    if (op < 0 || op > 4 || n == 0 || n > PRIM_MAX_ITEMS || !in || !out || !flag) return -3;
+    DevBufs d;
+    const uint32_t* din = (const uint32_t*)d.put(in, (size_t)n * 72 * 4);
+    uint32_t* dout = (uint32_t*)d.get((size_t)n * 36 * 4);
+    uint32_t* df = (uint32_t*)d.get((size_t)n * 4);
+    if (!din || !dout || !df) return -1;
+    hipLaunchKernelGGL(gputest_p384_point_kernel, prim_grid(n), dim3(PRIM_BLOCK), 0, 0, op, n, din, dout, df);
+    int rc = prim_sync();
+    if (rc == 0 && !(prim_back(out, dout, (size_t)n * 36 * 4) && prim_back(flag, df, (size_t)n * 4))) rc = -4;
     return rc;
 }

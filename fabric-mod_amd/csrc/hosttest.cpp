@@ -566,6 +566,16 @@ void hosttest_p384_mont_mul(int field, const uint8_t* a48, const uint8_t* b48, u
     r = field ? p384::mont_mul<true>(a, b) : p384::mont_mul<false>(a, b);
     p384::to_be48(out48, r);
 }
+// raw mod_add (sub == 0) / mod_sub of two canonical residues, mod p (field != 0) or mod n: the words as they are, no Montgomery step
+void hosttest_p384_mod_addsub(int field, int sub, const uint8_t* a48, const uint8_t* b48, uint8_t* out48) {
+    const p384::u384 P = FAB_P384_P, N = FAB_P384_N;
+    p384::u384 a, b, r;
+    p384::from_be48(a, a48);
+    p384::from_be48(b, b48);
+    if (sub) p384::mod_sub(r, a, b, field ? P : N);
+    else p384::mod_add(r, a, b, field ? P : N);
+    p384::to_be48(out48, r);
+}
 // scalars in [0, n).  op: 0 mul 1 inverse (0 -> 0) 2 reduce a value below 2^384 once
 void hosttest_p384_fn_op(int op, const uint8_t* a48, const uint8_t* b48, uint8_t* out48) {
     p384::u384 a, b, am, bm, r;

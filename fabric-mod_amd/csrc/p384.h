@@ -198,7 +198,9 @@ FAB_HD void fp_from_mont(u384& r, const u384& a) {
     one.w[0] = 1;
     r = mont_mul<true>(a, one);
 }
-// a^(p-2) (Montgomery form in and out): host-side table building and tests only - the verification never inverts mod p
+// a^(p-2) (Montgomery form in and out; 0 -> 0): table building, on the host (build_gtab, p384_tables.h) and on the device
+// (p384_keytab_kernels.hip makes its entries affine with it) - the verification itself never inverts mod p.  The exponent is a
+// constant: every branch on it is uniform over a wavefront.
 FAB_HD void fp_inv(u384& r, const u384& a) {
     const uint32_t P[12] = FAB_P384_P;
     const u384 one = FAB_P384_ONE_MONT;
