@@ -23,6 +23,7 @@
 #include "../../include/fabgpu.h"
 #include "kernels.h"
 #include "key_slots.h"
+#include "keyed_fence.h"
 #include "block_walk_dev.h"
 #include "described_plan.h"
 #include "walk_layout.h"
@@ -129,6 +130,29 @@ struct PinBuf {  // growable pinned host buffer
     }
 };
 
+// what KeyedFence (keyed_fence.h) asks of the device
+struct HipFenceDev {
+    using Event = hipEvent_t;
+    using Stream = hipStream_t;
+    static bool ok(hipError_t e) {
+        if (e != hipSuccess) (void)hipGetLastError();
+        return e == hipSuccess;
+    }
+    static Event make_event() {
+        Event e = nullptr;
+        return ok(hipEventCreateWithFlags(&e, hipEventDisableTiming)) ? e : nullptr;
+    }
+    static void destroy_event(Event e) { hipEventDestroy(e); }
+    static bool record(Event e, Stream s) { return ok(hipEventRecord(e, s)); }
+    static FenceQuery query(Event e) {
+        const hipError_t r = hipEventQuery(e);
+        return ok(r) ? FenceQuery::DONE : r == hipErrorNotReady ? FenceQuery::NOT_READY : FenceQuery::FAILED;
+    }
+    static void wait(Event e) { (void)ok(hipEventSynchronize(e)); }
+    static bool sync(Stream s) { return ok(hipStreamSynchronize(s)); }
+};
+using HipKeyedFence = KeyedFence<HipFenceDev>;
+
 }  // namespace
 
 struct fabgpu_ctx {
@@ -181,15 +205,15 @@ struct fabgpu_ctx {
     const int32_t** d_ktabs = nullptr;      // KTAB_STRIDE words per slot (kernels.h): the 8-bit comb, the 16-bit comb or nullptr, the generation
     size_t d_ktabs_cap = 0;                 // (in slots)
     // Retiring keys (fabgpu_p256_key_unregister; key_slots.h has the ids).  A retirement takes the key out of key_ids and leaves the
-    // device alone; the slot and its tables then pass two waits before anything of them is used again:
-    //   phase 1  behind events recorded AT the retirement on every stream that has carried a keyed launch (and on the 16-bit builder's,
-    //            if the key had a build queued): whatever was enqueued before the retirement finds the old key and answers for it;
-    //   phase 2  at a moment when no launcher is between its snapshot of (nkeys, d_ktabs) and its last keyed enqueue
-    //            (keyed_launchers == 0) the host sets the slot's generation word to KTAB_GEN_NONE, and events recorded THEN have completed: nothing
-    //            that could have seen the old generation is running.  Only now the tables go to the free lists and the slot may be
-    //            handed out again - pointers first, the new generation last, both written by the host before the new id is returned.
+    // device alone; the slot and its tables then pass the wait of keyed_fence.h (the launchers, the streams, the events: fence256, under
+    // kmu) TWICE before anything of them is used again, because d_ktabs is edited in place, under launches that read it:
+    //   phase 1  behind events recorded AT the retirement (and on the 16-bit builder's stream, if the key had a build queued): whatever
+    //            was enqueued before the retirement finds the old key and answers for it;
+    //   phase 2  at a quiet moment the host sets the slot's generation word to KTAB_GEN_NONE, and events recorded THEN have completed:
+    //            nothing that could have seen the old generation is running.  Only now the tables go to the free lists and the slot may
+    //            be handed out again - pointers first, the new generation last, both written by the host before the new id is returned.
     // Phases advance on the registration paths (kdrain_advance_locked), never on a verify call or a block pass; a registration whose
-    // slot (the LOWEST reclaimable one, always) is still draining waits for that slot's events with hipEventSynchronize.
+    // slot (the LOWEST reclaimable one, always) is still draining waits for that slot's drain alone.
     fab::KeySlots kslots;
     std::vector<std::string> kname;         // per slot: its tenant's qx||qy
     std::vector<uint32_t> kgen_dev;         // per slot: the generation word the device shows
@@ -202,11 +226,7 @@ struct fabgpu_ctx {
         int idx16 = -1;
     };
     std::vector<KeyDrain> kdrains;          // oldest first
-    std::vector<hipEvent_t> kev_pool;
-    std::vector<hipStream_t> keyed_streams; // every stream a keyed launch was queued on (KeyedSnap)
-    std::mutex keyed_lm;                    // (a leaf, taken under kmu or alone)
-    std::condition_variable keyed_cv;
-    int keyed_launchers = 0;                // launchers between their snapshot under kmu and their last keyed enqueue (keyed_lm)
+    HipKeyedFence fence256;                 // (its events also serve k16_pending: one of those may end up in a drain)
     hipStream_t stream_kslot = nullptr;     // the host's few-byte writes into d_ktabs
     std::vector<void*> retired;   // outgrown d_ktabs arrays, freed at shutdown
     // Round 6, FABGPU_FLAG_KEY_TABLES_16BIT: a registered key also gets a 16-bit comb (CombTab<16>, 80 MiB - the generator's own format),
@@ -249,12 +269,11 @@ struct fabgpu_ctx {
     // registration or keyed call - a context that never meets a registered P-384 key allocates none of this.
     // A keyed launch is handed d_snap384: the book's snapshot, written completely (and waited for) by the registration or retirement
     // that changed the book, before it replaces the previous array, and never edited afterwards.  Nothing is published under a running
-    // launch.  What a change of the book leaves behind - the previous snapshot array, and a retired key's slot and table - passes one wait
-    // before it is used again (Drain384): at a moment when no launcher is between taking (d_snap384, snap384_n) and its keyed enqueue
-    // (k384_launchers == 0; k384_mu is held, so nobody takes the old array any more) events are recorded on every stream that has carried
-    // a keyed launch, and those events have completed.  Drains advance on the registration, retirement and stats paths, never on a verify
-    // call; a registration whose slot - the lowest reclaimable one, always (key_slots.h) - is still draining waits for that slot.
-    // Lock order: k384_build_mu, k384_mu, k384_lm.
+    // launch.  What a change of the book leaves behind - the previous snapshot array, and a retired key's slot and table - passes the wait
+    // of keyed_fence.h (fence384, under k384_mu) ONCE before it is used again (Drain384): nobody takes the old array any more, so one
+    // quiet moment and the events recorded then are all it needs.  Drains advance on the registration, retirement and stats paths, never
+    // on a verify call; a registration whose slot - the lowest reclaimable one, always (key_slots.h) - is still draining waits for that slot.
+    // Lock order: k384_build_mu, k384_mu, the fence's leaf.
     std::mutex k384_mu;
     fab::P384KeyBook k384;
     uint32_t* d_gcomb384 = nullptr;
@@ -275,10 +294,7 @@ struct fabgpu_ctx {
         std::vector<hipEvent_t> evs;
     };
     std::vector<Drain384> k384_drains;       // oldest first
-    std::vector<hipStream_t> k384_streams;   // every stream a keyed P-384 launch was queued on
-    std::mutex k384_lm;
-    std::condition_variable k384_cv;
-    int k384_launchers = 0;
+    HipKeyedFence fence384;                  // (its events also serve k384_pending16: one of those may end up in a drain)
     std::atomic<uint64_t> k384_launches{0};  // keyed P-384 launches queued so far (fabgpu_p384_key_table_stats)
     // FABGPU_FLAG_P384_WIDE (or fab::ctx_set_p384_wide): keyed launches of at most P384_WIDE_LAUNCH_MAX rows on eight lanes per signature.
     // Their scratch is a workspace of the qws pool, always asked for at its full size and made when the switch is turned on: a launch
@@ -650,6 +666,7 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
         if (ctx->d_k384_scr) hipFree(ctx->d_k384_scr);
         for (auto& d : ctx->k384_drains)
             for (hipEvent_t e : d.evs) hipEventDestroy(e);
+        ctx->fence384.destroy_all();
         for (auto* t : ctx->itabs) hipFree(t);
         if (ctx->d_issuers) hipFree(ctx->d_issuers);
         ctx->nym.release();
@@ -683,7 +700,7 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
         for (auto& d : ctx->kdrains)
             for (hipEvent_t e : d.evs) hipEventDestroy(e);
         for (auto& p : ctx->k16_pending) hipEventDestroy(p.built);
-        for (hipEvent_t e : ctx->kev_pool) hipEventDestroy(e);
+        ctx->fence256.destroy_all();
         for (void* t : ctx->ktab16_slabs)
             if (t) hipFree(t);
         if (ctx->ktab16_rooms) hipFree(ctx->ktab16_rooms);
@@ -933,79 +950,26 @@ static bool kslot_write_locked(fabgpu_ctx* ctx, size_t word, const void* src, si
     if (e != hipSuccess) (void)hipGetLastError();
     return e == hipSuccess;
 }
-static hipEvent_t kev_get_locked(fabgpu_ctx* ctx) {
-    hipEvent_t e = nullptr;
-    if (!ctx->kev_pool.empty()) {
-        e = ctx->kev_pool.back();
-        ctx->kev_pool.pop_back();
-    } else if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        e = nullptr;
-    }
-    return e;
-}
-// events behind everything queued so far on the streams that carry keyed launches (with16: and on the 16-bit builder's).  A stream the
-// caller has destroyed since (a keyed _dev call's stream must be idle by then) refuses the record and is forgotten.  false: an event
-// could not be made or recorded on a stream of the context's own - the caller falls back to waiting for those streams.
-static bool kdrain_record_locked(fabgpu_ctx* ctx, fabgpu_ctx::KeyDrain& d, bool with16) {
-    bool ok = true;
-    auto one = [&](hipStream_t s, bool own) {
-        hipEvent_t e = kev_get_locked(ctx);
-        if (e && hipEventRecord(e, s) == hipSuccess) {
-            d.evs.push_back(e);
-            return true;
-        }
-        (void)hipGetLastError();
-        if (e) ctx->kev_pool.push_back(e);
-        if (own) {
-            ok = ok && hipStreamSynchronize(s) == hipSuccess;
-            (void)hipGetLastError();
-        }
-        return own;
-    };
-    for (size_t i = 0; i < ctx->keyed_streams.size();) {
-        hipStream_t s = ctx->keyed_streams[i];
-        const bool own = s == ctx->stream || s == ctx->stream2 || s == ctx->stream3 || s == ctx->stream4;
-        if (one(s, own)) i++;
-        else ctx->keyed_streams.erase(ctx->keyed_streams.begin() + (long)i);
-    }
-    if (with16 && ctx->stream_keytab16) one(ctx->stream_keytab16, true);
-    return ok;
-}
-static bool kdrain_events_done_locked(fabgpu_ctx* ctx, fabgpu_ctx::KeyDrain& d, bool wait) {
-    while (!d.evs.empty()) {
-        hipError_t e = wait ? hipEventSynchronize(d.evs.back()) : hipEventQuery(d.evs.back());
-        if (e == hipErrorNotReady) {
-            (void)hipGetLastError();
-            return false;
-        }
-        if (e != hipSuccess) (void)hipGetLastError();      // (a failed device: nothing of it runs any more)
-        ctx->kev_pool.push_back(d.evs.back());
-        d.evs.pop_back();
-    }
-    return true;
-}
+// The streams of the context's own that carry keyed launches of either curve (the block pass runs on all four): one of them that
+// refuses an event is waited for, never forgotten (keyed_fence.h, rule 3).  What record() answers is not asked for: where the
+// stream could not be waited for either, the device has failed and runs nothing more.
+struct KeyedStreamOwned {
+    const fabgpu_ctx* ctx;
+    bool operator()(hipStream_t s) const { return s == ctx->stream || s == ctx->stream2 || s == ctx->stream3 || s == ctx->stream4; }
+};
 // One retired slot as far as it goes without waiting for a launch or a launcher (wait: all the way).  true: drained - tables on the
-// free lists, slot reclaimable.  The step from phase 1 to phase 2 needs a moment at which no launcher is between its snapshot of
-// (nkeys, d_ktabs) and its last keyed enqueue: kmu is held, so no new snapshot is taken while the generation word is written and the
-// second set of events recorded - whoever took a snapshot earlier has enqueued (the events cover it), whoever takes one later finds
-// KTAB_GEN_NONE.  Without `wait` a launcher under way just postpones the step; with it the caller sleeps on keyed_cv (launchers
-// never take kmu while they are counted, so they finish).
+// free lists, slot reclaimable.  kmu is held, so no new snapshot is taken while the generation word is written and the second set of
+// events recorded: whoever took a snapshot earlier has enqueued (the events cover it), whoever takes one later finds KTAB_GEN_NONE.
 static bool kdrain_step_locked(fabgpu_ctx* ctx, fabgpu_ctx::KeyDrain& d, bool wait) {
     if (d.phase == 1) {
-        if (!kdrain_events_done_locked(ctx, d, wait)) return false;
-        {
-            std::unique_lock<std::mutex> ll(ctx->keyed_lm);
-            if (ctx->keyed_launchers != 0 && !wait) return false;
-            ctx->keyed_cv.wait(ll, [&] { return ctx->keyed_launchers == 0; });
-        }
+        if (!ctx->fence256.done(d.evs, wait) || !ctx->fence256.quiet(wait)) return false;
         const uint64_t none = KTAB_GEN_NONE;
         if (!kslot_write_locked(ctx, KTAB_STRIDE * (size_t)d.slot + 2, &none, sizeof(none))) return false;   // (stays in phase 1: tried again)
         ctx->kgen_dev[d.slot] = KTAB_GEN_NONE;
-        kdrain_record_locked(ctx, d, false);
+        (void)ctx->fence256.record(d.evs, KeyedStreamOwned{ctx});
         d.phase = 2;
     }
-    if (!kdrain_events_done_locked(ctx, d, wait)) return false;
+    if (!ctx->fence256.done(d.evs, wait)) return false;
     if (d.t8) ctx->ktab_free.push_back(d.t8);
     if (d.t16) ctx->ktab16_free.push_back(d.t16);
     if (d.idx16 >= 0) ctx->ktab16_idx_free.push_back(d.idx16);
@@ -1013,19 +977,12 @@ static bool kdrain_step_locked(fabgpu_ctx* ctx, fabgpu_ctx::KeyDrain& d, bool wa
     return true;
 }
 static void kdrain_advance_locked(fabgpu_ctx* ctx) {
-    for (size_t i = 0; i < ctx->kdrains.size();) {
-        if (kdrain_step_locked(ctx, ctx->kdrains[i], false)) ctx->kdrains.erase(ctx->kdrains.begin() + (long)i);
-        else i++;
-    }
+    HipKeyedFence::advance(ctx->kdrains, [ctx](fabgpu_ctx::KeyDrain& d, bool wait) { return kdrain_step_locked(ctx, d, wait); });
 }
 static bool kdrain_wait_slot_locked(fabgpu_ctx* ctx, uint32_t slot) {
-    for (size_t i = 0; i < ctx->kdrains.size(); i++)
-        if (ctx->kdrains[i].slot == slot) {
-            if (!kdrain_step_locked(ctx, ctx->kdrains[i], true)) return false;
-            ctx->kdrains.erase(ctx->kdrains.begin() + (long)i);
-            return true;
-        }
-    return !ctx->kslots.draining(slot);
+    return HipKeyedFence::wait_for(ctx->kdrains, [slot](const fabgpu_ctx::KeyDrain& d) { return d.slot == slot; },
+                                   [ctx](fabgpu_ctx::KeyDrain& d, bool wait) { return kdrain_step_locked(ctx, d, wait); }) &&
+           !ctx->kslots.draining(slot);
 }
 // 16-bit combs of reused slots whose build has finished: the host writes their pointers
 static void k16_publish_locked(fabgpu_ctx* ctx) {
@@ -1041,35 +998,25 @@ static void k16_publish_locked(fabgpu_ctx* ctx) {
             DeviceGuard g(ctx->device);
             (void)kslot_write_locked(ctx, KTAB_STRIDE * (size_t)p.slot + 1, &p.tab, sizeof(void*));     // (not written: served by the 8-bit comb)
         }
-        ctx->kev_pool.push_back(p.built);
+        ctx->fence256.put(p.built);
         ctx->k16_pending.erase(ctx->k16_pending.begin() + (long)i);
     }
 }
-// What a keyed launch site needs of the key table, taken under kmu, and the launcher's place in keyed_launchers until its last keyed
-// launch is queued (the destructor).  The streams it will queue keyed launches on are remembered for the retirements' events.
-// Nothing between the constructor and the destructor may take kmu.
+// What a keyed launch site needs of the key table, taken under kmu, and the launcher's ticket of fence256, held until its last keyed
+// launch is queued (the destructor).  Nothing between the constructor and the destructor may take kmu.
 static_assert(KEY_SLOT_BITS == (int)fab::KeySlots::SLOT_BITS && FABGPU_MAX_KEYS == (1 << KEY_SLOT_BITS) && fab::KeySlots::MAX_SLOTS == FABGPU_MAX_KEYS,
               "the kernels' slot bits (kernels.h), the allocator's (key_slots.h) and the public cap on live keys (fabgpu.h) are one number");
 static_assert(KTAB_GEN_NONE > fab::KeySlots::GEN_LAST, "no id may carry the generation word of a slot between two tenants");
 struct KeyedSnap {
-    fabgpu_ctx* ctx;
     uint32_t nkeys = 0;
     const int32_t** kt = nullptr;
-    KeyedSnap(fabgpu_ctx* c, std::initializer_list<hipStream_t> streams) : ctx(c) {
+    HipKeyedFence::Ticket ticket;
+    KeyedSnap(fabgpu_ctx* ctx, std::initializer_list<hipStream_t> streams) {
         std::lock_guard<std::mutex> lk(ctx->kmu);
         nkeys = ctx->kslots.high_water();
         kt = ctx->d_ktabs;
-        for (hipStream_t s : streams)
-            if (std::find(ctx->keyed_streams.begin(), ctx->keyed_streams.end(), s) == ctx->keyed_streams.end()) ctx->keyed_streams.push_back(s);
-        std::lock_guard<std::mutex> ll(ctx->keyed_lm);
-        ctx->keyed_launchers++;
+        ticket = ctx->fence256.enter(streams);
     }
-    ~KeyedSnap() {
-        std::lock_guard<std::mutex> ll(ctx->keyed_lm);
-        if (--ctx->keyed_launchers == 0) ctx->keyed_cv.notify_all();
-    }
-    KeyedSnap(const KeyedSnap&) = delete;
-    KeyedSnap& operator=(const KeyedSnap&) = delete;
 };
 // (kmu held, the context's device current) room for one table: out of the current slab, a new slab when that is used up
 static int32_t* ktab_alloc_locked(fabgpu_ctx* ctx) {
@@ -1160,7 +1107,7 @@ static void key_queue_table16_locked(fabgpu_ctx* ctx, const std::string& k, uint
     uint8_t* head = ctx->ktab16_heads + 128 * idx;
     memcpy(head, k.data(), 64);
     memcpy(head + 64, &tab, sizeof(void*));
-    hipEvent_t built = first_tenant ? nullptr : kev_get_locked(ctx);
+    hipEvent_t built = first_tenant ? nullptr : ctx->fence256.get();
     if (!first_tenant && !built) return;
     hipError_t e = hipMemcpyAsync(room, head, 72, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = launch_keytab16_build(1, room, (void* const*)((uint8_t*)room + 64), (uint8_t*)room + 128, st);
@@ -1170,7 +1117,7 @@ static void key_queue_table16_locked(fabgpu_ctx* ctx, const std::string& k, uint
     if (e != hipSuccess) {
         (void)hipGetLastError();
         hipStreamSynchronize(st);                       // (the table and the room are simply used again by the next key)
-        if (built) ctx->kev_pool.push_back(built);
+        if (built) ctx->fence256.put(built);
         return;
     }
     if (built) ctx->k16_pending.push_back({slot, tab, built});
@@ -1226,7 +1173,7 @@ static int key_install_table_locked(fabgpu_ctx* ctx, const std::string& k, int32
         }
         if (!ctx->ktabs.empty()) {
             // (the 16-bit builds queued on stream_keytab write their pointers into the OLD array: let them land before it is copied.
-            //  A launcher that still holds the old array is counted in keyed_launchers like any other: a slot retired from now on waits
+            //  A launcher that still holds the old array holds a ticket of fence256 like any other: a slot retired from now on waits
             //  for it, and an id handed out from now on is simply out of its range)
             if (ctx->stream_keytab16) hipStreamSynchronize(ctx->stream_keytab16);
             std::vector<const int32_t*> both(ctx->ktabs.size() * KTAB_STRIDE, nullptr);
@@ -1439,7 +1386,9 @@ int fabgpu_p256_key_unregister(fabgpu_ctx* ctx, uint32_t key_id) {
                 break;
             }
     }
-    kdrain_record_locked(ctx, d, d.t16 != nullptr);
+    std::vector<hipStream_t> builder;                    // (phase 1 also waits for the 16-bit builder's stream, if the key had a table)
+    if (d.t16 && ctx->stream_keytab16) builder.push_back(ctx->stream_keytab16);
+    (void)ctx->fence256.record(d.evs, KeyedStreamOwned{ctx}, builder);
     ctx->kdrains.push_back(std::move(d));
     return FABGPU_OK;
 }
@@ -1931,43 +1880,11 @@ bool k384_stream(fabgpu_ctx* ctx) {
 // way).  true: done - the table and the array are on the free lists, the slot is reclaimable.
 bool k384_drain_step_locked(fabgpu_ctx* ctx, fabgpu_ctx::Drain384& d, bool wait) {
     if (!d.recorded) {
-        {
-            std::unique_lock<std::mutex> ll(ctx->k384_lm);
-            if (ctx->k384_launchers != 0 && !wait) return false;
-            ctx->k384_cv.wait(ll, [&] { return ctx->k384_launchers == 0; });
-        }
-        // a stream the caller has destroyed since (a keyed _dev call's stream must be idle by then) refuses the record and is forgotten;
-        // one of the context's own that refuses is waited for instead
-        for (size_t i = 0; i < ctx->k384_streams.size();) {
-            hipStream_t s = ctx->k384_streams[i];
-            hipEvent_t e = nullptr;
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess && hipEventRecord(e, s) == hipSuccess) {
-                d.evs.push_back(e);
-                i++;
-                continue;
-            }
-            (void)hipGetLastError();
-            if (e) hipEventDestroy(e);
-            if (s == ctx->stream) {
-                (void)hipStreamSynchronize(s);
-                (void)hipGetLastError();
-                i++;
-            } else {
-                ctx->k384_streams.erase(ctx->k384_streams.begin() + (long)i);
-            }
-        }
+        if (!ctx->fence384.quiet(wait)) return false;
+        (void)ctx->fence384.record(d.evs, KeyedStreamOwned{ctx});
         d.recorded = true;
     }
-    while (!d.evs.empty()) {
-        const hipError_t e = wait ? hipEventSynchronize(d.evs.back()) : hipEventQuery(d.evs.back());
-        if (e == hipErrorNotReady) {
-            (void)hipGetLastError();
-            return false;
-        }
-        if (e != hipSuccess) (void)hipGetLastError();      // (a failed device: nothing of it runs any more)
-        hipEventDestroy(d.evs.back());
-        d.evs.pop_back();
-    }
+    if (!ctx->fence384.done(d.evs, wait)) return false;
     if (d.tab) ctx->k384_tab_free.push_back(d.tab);
     if (d.tab16) ctx->k384_tab16_free.push_back(d.tab16);
     if (d.old_snap.p) ctx->snap384_free.push_back(d.old_snap);
@@ -1975,19 +1892,12 @@ bool k384_drain_step_locked(fabgpu_ctx* ctx, fabgpu_ctx::Drain384& d, bool wait)
     return true;
 }
 void k384_drain_advance_locked(fabgpu_ctx* ctx) {
-    for (size_t i = 0; i < ctx->k384_drains.size();) {
-        if (k384_drain_step_locked(ctx, ctx->k384_drains[i], false)) ctx->k384_drains.erase(ctx->k384_drains.begin() + (long)i);
-        else i++;
-    }
+    HipKeyedFence::advance(ctx->k384_drains, [ctx](fabgpu_ctx::Drain384& d, bool wait) { return k384_drain_step_locked(ctx, d, wait); });
 }
 bool k384_drain_wait_slot_locked(fabgpu_ctx* ctx, uint32_t slot) {
-    for (size_t i = 0; i < ctx->k384_drains.size(); i++)
-        if (ctx->k384_drains[i].slot == (int64_t)slot) {
-            if (!k384_drain_step_locked(ctx, ctx->k384_drains[i], true)) return false;
-            ctx->k384_drains.erase(ctx->k384_drains.begin() + (long)i);
-            break;
-        }
-    return !ctx->k384.slots.draining(slot);
+    return HipKeyedFence::wait_for(ctx->k384_drains, [slot](const fabgpu_ctx::Drain384& d) { return d.slot == (int64_t)slot; },
+                                   [ctx](fabgpu_ctx::Drain384& d, bool wait) { return k384_drain_step_locked(ctx, d, wait); }) &&
+           !ctx->k384.slots.draining(slot);
 }
 // (k384_mu held, the context's device current) the book as it is now becomes the snapshot later launches are handed: a fresh array,
 // written and waited for before it replaces the previous one, which goes into `d` to be drained.  A failure leaves NO snapshot (every
@@ -2081,14 +1991,11 @@ void k384_queue16_locked(fabgpu_ctx* ctx, uint32_t id, const uint32_t* tab8) {
         (void)hipGetLastError();
         return;
     }
-    hipEvent_t ev = nullptr;
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
+    hipEvent_t ev = ctx->fence384.get();      // (the fence's: a retirement may move it into a drain)
+    if (!ev) return;
     uint32_t* t16 = k384_tab16_alloc_locked(ctx);
     if (!t16) {
-        hipEventDestroy(ev);
+        ctx->fence384.put(ev);
         return;
     }
     hipError_t e = launch_p384_keytab16_build(tab8, t16, ctx->stream_k384x16);
@@ -2097,7 +2004,7 @@ void k384_queue16_locked(fabgpu_ctx* ctx, uint32_t id, const uint32_t* tab8) {
         (void)hipGetLastError();
         (void)hipStreamSynchronize(ctx->stream_k384x16);      // (whatever was queued has run before the table is handed out again)
         (void)hipGetLastError();
-        hipEventDestroy(ev);
+        ctx->fence384.put(ev);
         ctx->k384_tab16_free.push_back(t16);
         return;
     }
@@ -2117,7 +2024,7 @@ void k384_poll16_locked(fabgpu_ctx* ctx, bool wait = false) {
             i++;
             continue;
         }
-        hipEventDestroy(q.ev);
+        ctx->fence384.put(q.ev);
         ctx->k384_pending16.erase(ctx->k384_pending16.begin() + (long)i);
         if (e == hipSuccess && ctx->k384.set_table16(q.id, q.tab)) {
             news = true;
@@ -2290,17 +2197,17 @@ int p384_key_register_batch(fabgpu_ctx* ctx, int n, const uint8_t* qxy, uint32_t
     return rc;
 }
 
-// What a keyed P-384 launch site takes of the book, under k384_mu, and its place among the launchers until its keyed launch is queued
+// What a keyed P-384 launch site takes of the book, under k384_mu, and its ticket of fence384, held until its keyed launch is queued
 // (the destructor).  Nothing between the two may take k384_mu.
 struct KeyedSnap384 {
-    fabgpu_ctx* ctx;
     const fab::P384SlotSnap* snap = nullptr;
     uint32_t nkeys = 0;
     const uint32_t* gcomb = nullptr;
     const uint32_t* gcomb16 = nullptr;         // all three null without FABGPU_FLAG_P384_KEY_TABLES_16BIT (or without the generator's 16-bit table)
     const uint32_t* const* snap16 = nullptr;
     void* rows16 = nullptr;
-    KeyedSnap384(fabgpu_ctx* c, hipStream_t st) : ctx(c) {
+    HipKeyedFence::Ticket ticket;
+    KeyedSnap384(fabgpu_ctx* ctx, hipStream_t st) {
         std::lock_guard<std::mutex> lk(ctx->k384_mu);
         k384_poll16_locked(ctx);               // (finished 16-bit builds: hipEventQuery, and a fresh snapshot if there is news)
         snap = ctx->d_snap384;
@@ -2311,16 +2218,8 @@ struct KeyedSnap384 {
             snap16 = ctx->d_snap384x16;
             rows16 = ctx->d_k384_rows16;
         }
-        if (std::find(ctx->k384_streams.begin(), ctx->k384_streams.end(), st) == ctx->k384_streams.end()) ctx->k384_streams.push_back(st);
-        std::lock_guard<std::mutex> ll(ctx->k384_lm);
-        ctx->k384_launchers++;
+        ticket = ctx->fence384.enter({st});
     }
-    ~KeyedSnap384() {
-        std::lock_guard<std::mutex> ll(ctx->k384_lm);
-        if (--ctx->k384_launchers == 0) ctx->k384_cv.notify_all();
-    }
-    KeyedSnap384(const KeyedSnap384&) = delete;
-    KeyedSnap384& operator=(const KeyedSnap384&) = delete;
 };
 
 int p384_verify_keyed_dev(fabgpu_ctx* ctx, size_t n, const void* key_id, const void* e, bool e_is_digest32, const void* r, const void* s,
