@@ -141,7 +141,17 @@ int fabgpu_sha256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* ar
  * fabgpu_identity_verify_batch_dev with its prefixes and gathered pieces, fabgpu_idemix_nym_verify_batch_dev): it hashes the bytes
  * the offsets name, wherever they lie in an arena of a size it accepts, or it refuses the arena - it never answers from other
  * bytes.  All of them accept the full 2^32 - 1.  One limit remains inside it: a single message (prefix included) must be shorter
- * than 2^31 bytes; the kernels count the bytes left in a message in 31 bits and a longer one is not hashed correctly. */
+ * than 2^31 bytes; the kernels count the bytes left in a message in 31 bits and a longer one is not hashed correctly.
+ * OUTPUT CONTRACT of the _dev entry points (these, the keyed, SHA3-256 and idemix ones below and fabgpu_identity_verify_batch_dev).
+ * After a call that returned 0 and whose stream has been synchronised:
+ *   1. every one of the ceil(n / 64) verdict words is fully written, whatever the caller had in it: bit i < n is 1 exactly when row i
+ *      is valid, every bit >= n is 0 - a consumer may take whole words;
+ *   2. status[0, n) holds the status bytes; with status == NULL nothing is written in its place;
+ *   3. digests[0, n), 32 bytes a row, holds the digests - the hash-only calls, and `digests` / `gather_digests` (n_gather rows) of the
+ *      described batch; that one's mid_scratch and gather_scratch are the call's to use within the sizes stated for them, and its
+ *      pseudonym part is the host variant's alone: the _dev entry writes neither nym_verdict_bits nor nym_status;
+ *   4. no byte outside these ranges is written, in front of them or behind them.
+ * tests/test_dev_output_contract_gpu.py holds every kernel form to it. */
 int fabgpu_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* qx, const void* qy, const void* e, const void* r,
                                  const void* s, void* verdict_bits, void* status, void* stream);
 int fabgpu_sha256_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off,
