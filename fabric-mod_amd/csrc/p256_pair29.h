@@ -12,6 +12,7 @@
 // Replaces crypto/ecdsa.Verify reached from bccsp/sw/ecdsa.go:56.
 #pragma once
 #include "p256_verify29.h"
+#include "p256_odd4.h"
 #include "pair29_gcn.h"
 
 namespace fab {
@@ -111,9 +112,10 @@ struct PairQTab {
     }
 };
 
-// The same table in LDS, EIGHT entries per signature (j*Q, j = 1..8, for signed 4-bit windows): 128 signatures x 8 x 128 B = 128 KiB of
-// the CU's 160 KiB - the pair kernel runs one workgroup per CU anyway.  Costs 13 more additions per verification than the 16-entry
-// table with 5-bit windows (65 windows instead of 52) and saves eight table-building operations; in exchange NOTHING of the
+// The same table in LDS, EIGHT entries per signature (the odd multiples (2j - 1) Q, j = 1..8, for the all-odd 4-bit recoding of
+// pair_u2_mult_odd29 - or j*Q for the Booth form, 65 windows, of FABGPU_FLAG_PAIR_BOOTH4): 128 signatures x 8 x 128 B = 128 KiB of
+// the CU's 160 KiB - the pair kernel runs one workgroup per CU anyway.  Costs 11 more additions per verification than the 16-entry
+// table with 5-bit windows (63 instead of 52) and saves eight table-building operations; in exchange NOTHING of the
 // per-signature table touches the memory system: the global-workspace form writes 60 MB and fetches 2 x 110 MB per 30 000-tuple
 // launch (58x the algorithmic bytes), which is free on an idle chip and costs 4-17 % beside a tenant that streams 1.5-5 TB/s
 // (tools/gpu_hbm_tenant_probe.py).  A signature's entries are 65 cells apart (one cell of padding per signature): a wave's 32 pairs
@@ -442,6 +444,92 @@ __device__ __forceinline__ void pair_u2_mult29(pair_pt& T, bool& t_inf, const u2
     }
 }
 
+// The LDS table for the all-odd recoding (p256_odd4.h): slot j = (2j - 1) Q, j = 1..8 - eight entries like pair_qtab_build29<4>'s.
+// Slot 1 = Q, D = 2Q, slot 2 = D + Q (mixed), slot j = slot j-1 + D.  2Q waits in slot 8, where every addition reads it in crossed
+// layout, until the last addition overwrites it with 15 Q (its load is issued before that store).  None of the additions meets
+// P == +-Q: (2j - 3) Q and 2 Q with 2j - 3 <= 13, Q of prime order (anything else fails the curve gate and its row reports that).
+template <class QTab>
+__device__ __forceinline__ void pair_qtab_build_odd29(const pair_pt& Qp, const fe& QX, const fe& QY, const QTab& qtab, bool odd) {
+    PAIR_TMPS;
+    qtab.store_state(1, Qp, odd);
+    pair_pt d = Qp, cur;
+    PAIR_DBL(d);
+    qtab.store_state(PAIR_LDS_ENTRIES, d, odd);
+    PAIR_MADD(cur, d, QX, QY);
+    qtab.store_state(2, cur, odd);
+#pragma unroll 1
+    for (int j = 3; j <= PAIR_LDS_ENTRIES; j++) {
+        fe C, D;
+        qtab.load_crossed((uint32_t)PAIR_LDS_ENTRIES, C, D, odd);
+        pair_pt sum;
+        PAIR_ADD(sum, cur, C, D);
+        cur = sum;
+        qtab.store_state(j, cur, odd);
+    }
+}
+
+// T = u2 * Q over that table, k = u2_fold_odd(u2): T = entry[h_63], then 63 x (four doublings; one addition).  No digit is zero and T
+// is never infinity: no select, no entry conversion inside the loop, nothing to track.
+//
+// Exceptional additions (the formulas do not handle P == +-Q).  Before window i is added T = M Q, M = 16 P with P the sum of the digits
+// above i: P >= 16^m - 15 (16^m - 1)/15 = 1, so M is a POSITIVE multiple of 16; the addend is d Q, d odd, |d| <= 15 < M.  M + d is the
+// prefix of k down to window i and the digits below it sum to less than 16^i in magnitude: for i >= 1 the prefix is below 2^252 + 1 and
+// M < n - 15: neither M = |d| nor M = n - |d| is possible.  For i = 0, M = k - d with k <= n.  M == d (mod n): k = 2d + t n, k odd
+// and 0 < k < 2n give t = 1, so d < 0 and k = n - 2|d|; M = n - |d| is a multiple of 16 and n mod 16 = 1: |d| = 1, k = n - 2.
+// M == -d: k = t n, k = n, which only u2 = 0 folds to - and the range gate refuses r = 0.  EXACTLY ONE k, n - 2, reached from u2 = n - 2
+// and from u2 = 2 (tests/test_pair_odd_windows_host.py walks the prefixes).  Its product, -2Q (+2Q for u2 = 2), is computed apart
+// behind __any: one doubling of entry 0.
+template <class QTab, bool DBL1 = false>
+__device__ __forceinline__ void pair_u2_mult_odd29(pair_pt& T, const u256& k, const QTab& qtab, bool odd) {
+    PAIR_TMPS;
+    odd_walk4 wk;
+    odd_walk4_start(wk, k);
+    {
+        const odd_digit top = odd_walk4_next(wk);
+        qtab.load_state(top.entry + 1u, T, odd);
+        fe ny;
+#pragma unroll
+        for (int l = 0; l < 9; l++) ny.v[l] = -T.B.v[l];
+        fe_sel(T.B, top.neg & !odd, ny, T.B);      // E holds Y in B, O holds Z
+    }
+#pragma unroll 1
+    for (int i = ODD4_WINDOWS - 2; i >= 0; i--) {
+        const odd_digit dg = odd_walk4_next(wk);
+        fe C, D;
+        qtab.load_crossed(dg.entry + 1u, C, D, odd);    // issued ahead of the doublings
+        if constexpr (!DBL1) {
+            PAIR_DBL4(T);
+        } else {
+#pragma unroll 1
+            for (int j = 0; j < 4; j++) PAIR_DBL(T);
+        }
+        {
+            const int32_t nm = dg.neg ? -1 : 0, nc = dg.neg ? 1 : 0;  // -y = (y ^ -1) + 1, as in pair_u2_mult29
+#pragma unroll
+            for (int l = 0; l < 9; l++) D.v[l] = (D.v[l] ^ nm) + nc;  // -Y2 (lives on O)
+        }
+        pair_pt sum;
+        PAIR_ADD(sum, T, C, D);
+        T = sum;
+    }
+    {
+        const u256 NM2 = {{0xFC63254Fu, 0xF3B9CAC2u, 0xA7179E84u, 0xBCE6FAADu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0x00000000u, 0xFFFFFFFFu}};
+        bool special = (k.w[0] | 1u) == NM2.w[0];
+#pragma unroll
+        for (int l = 1; l < 8; l++) special = special & (k.w[l] == NM2.w[l]);
+        if (__any(special)) {
+            pair_pt two;
+            qtab.load_state(1u, two, odd);
+            PAIR_DBL(two);
+            fe ny;
+#pragma unroll
+            for (int l = 0; l < 9; l++) ny.v[l] = -two.B.v[l];
+            fe_sel(two.B, ((k.w[0] & 1u) == 0) & !odd, ny, two.B);    // k Q = -2Q; the fold's sign turns it back for u2 = 2
+            pair_sel(T, special, two, T);
+        }
+    }
+}
+
 // R = u1*G + u2*Q on a lane pair.  Q: affine Montgomery (both lanes hold both coordinates).  Returns the pair state of R;
 // r_inf as in p256_combined_mult29.  W = width of the signed (Booth) windows over u2: 5 (a 16-entry table j*Q, 52 windows: the
 // global-workspace table) or 4 (8 entries, 65 windows: the LDS table).
@@ -452,7 +540,9 @@ __device__ __forceinline__ void pair_u2_mult29(pair_pt& T, bool& t_inf, const u2
 // |d| == n (mod 2^W).  n mod 32 = 17 > 16: never for W = 5.  n mod 16 = 1: for W = 4 EXACTLY ONE scalar, u2 = n - 2
 // (digit -1 on top of M = n - 1: T = -Q, addend -Q).  That scalar is recognised up front and its product, -2Q, is taken from the
 // table (entry 2, negated) instead of from the loop.
-template <class QTab, int W = 5, bool DBL1 = false>
+// W = 4 runs the all-odd recoding over the table of odd multiples (pair_u2_mult_odd29: 63 windows, no zero digit) unless BOOTH4 asks
+// for the Booth form above (FABGPU_FLAG_PAIR_BOOTH4: A/B runs and parity tests).
+template <class QTab, int W = 5, bool DBL1 = false, bool BOOTH4 = false>
 __device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, const u256& u1, const u256& u2, const fe& QX, const fe& QY,
                                                      const int32_t* __restrict__ gtab, const QTab& qtab, bool odd) {
     static_assert(W == 4 || W == 5, "signed 4- or 5-bit windows");
@@ -460,10 +550,18 @@ __device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, c
     pair_pt Qp;
     Qp.A = QX;
     fe_sel(Qp.B, odd, ONE, QY);
-    pair_qtab_build29<QTab, W>(Qp, QX, QY, qtab, odd);
     pair_pt T;
     bool t_inf;
-    pair_u2_mult29<QTab, W, DBL1>(T, t_inf, u2, Qp, qtab, odd);
+    if constexpr (W == 4 && !BOOTH4) {
+        pair_qtab_build_odd29<QTab>(Qp, QX, QY, qtab, odd);
+        u256 k;
+        u2_fold_odd(k, u2);
+        pair_u2_mult_odd29<QTab, DBL1>(T, k, qtab, odd);
+        t_inf = false;
+    } else {
+        pair_qtab_build29<QTab, W>(Qp, QX, QY, qtab, odd);
+        pair_u2_mult29<QTab, W, DBL1>(T, t_inf, u2, Qp, qtab, odd);
+    }
 
     // --- S = u1 * G (16-bit comb), then R = S + T ---
     pair_pt S;
@@ -514,7 +612,7 @@ __device__ __forceinline__ bool pair_x_equals_r29(const pair_pt& Rr, bool r_inf,
 }
 
 // Status of one tuple, valid on the EVEN lane of the pair.
-template <class QTab, int W = 5, bool DBL1 = false>
+template <class QTab, int W = 5, bool DBL1 = false, bool BOOTH4 = false>
 __device__ __forceinline__ uint32_t p256_verify_pair29(const u256& qx, const u256& qy, const u256& e, const u256& r, const u256& s,
                                                         const int32_t* __restrict__ gtab, const QTab& qtab, bool odd) {
     const u256 P = FAB_P256_P;
@@ -532,7 +630,7 @@ __device__ __forceinline__ uint32_t p256_verify_pair29(const u256& qx, const u25
 
     pair_pt Rr;
     bool r_inf;
-    pair_combined_mult29<QTab, W, DBL1>(Rr, r_inf, u1, u2, QX, QY, gtab, qtab, odd);
+    pair_combined_mult29<QTab, W, DBL1, BOOTH4>(Rr, r_inf, u1, u2, QX, QY, gtab, qtab, odd);
     bool ok = pair_x_equals_r29(Rr, r_inf, r);
     uint32_t st = ok ? ST_VALID : ST_BAD_MATH;
     return early != ST_VALID ? early : st;
@@ -556,10 +654,10 @@ __device__ __forceinline__ uint32_t p256_verify_keyed_pair29(const u256& e, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// HELPER-WAVE FORM of the LDS-table pair kernel (p256_verify_pair_lds_kernel: 512 threads, two waves per SIMD).  The 256 doublings of
+// HELPER-WAVE FORM of the LDS-table pair kernel (p256_verify_pair_lds_kernel: 512 threads, two waves per SIMD).  The 252 doublings of
 // u2*Q are one serial chain; the inversion s^-1 mod n, u1 and u2, and u1*G on the 16-bit comb do not depend on it.  A workgroup
 // therefore runs two roles over the same 128 signatures: MAIN waves (threads 0..255) gate Q, build the 8-entry LDS table, run the
-// 65 windows and the final addition and check; HELPER waves (threads 256..511, lane t + 256 serves the same signature and the same
+// 63 windows and the final addition and check; HELPER waves (threads 256..511, lane t + 256 serves the same signature and the same
 // lane-pair parity as main lane t) do the scalar part and u1*G beside them, in the issue slots a lone wave per SIMD leaves idle.
 // Per tile (A, B: workgroup barriers):
 //     helper:  range gates, s^-1, u1, u2 -> u2 to LDS           | A |  u1*G -> S, s_inf, gate status to LDS | B |
@@ -604,13 +702,19 @@ struct PairHandoffLds {
     }
 };
 
-// Helper, before barrier A: range gates and the scalars; u2 goes to LDS, u1 and the gate status stay.
-template <class Hand>
+// Helper, before barrier A: range gates and the scalars; u2 goes to LDS - folded to its odd representative (u2_fold_odd: one subtraction
+// and a select, off the chain; the sign rides in bit 0, the handoff stays eight words) unless BOOTH4 - u1 and the gate status stay.
+template <class Hand, bool BOOTH4 = false>
 __device__ __forceinline__ void pair_helper_scalars29(u256& u1, uint32_t& early, const u256& e, const u256& r, const u256& s, const Hand& hand,
                                                       bool odd) {
     early = range_status(r, s);
     u256 u2;
     pair_ecdsa_scalars29(u1, u2, e, r, s, odd);
+    if constexpr (!BOOTH4) {
+        u256 k;
+        u2_fold_odd(k, u2);
+        u2 = k;
+    }
     hand.put_u2(u2);
 }
 
@@ -629,8 +733,8 @@ __device__ __forceinline__ void pair_helper_comb29(const u256& u1, uint32_t earl
     hand.put_s(S, s_inf, early);
 }
 
-// Main, before barrier A: Q gates and the table.  Returns q_ok; Qp = Q in pair state.
-template <class QTab>
+// Main, before barrier A: Q gates and the table (odd multiples, or j*Q for BOOTH4).  Returns q_ok; Qp = Q in pair state.
+template <class QTab, bool BOOTH4 = false>
 __device__ __forceinline__ bool pair_main_table29(pair_pt& Qp, const u256& qx, const u256& qy, const QTab& qtab, bool odd) {
     const u256 P = FAB_P256_P;
     const fe ONE = {FE29_R1};
@@ -641,7 +745,8 @@ __device__ __forceinline__ bool pair_main_table29(pair_pt& Qp, const u256& qx, c
     bool q_ok = q_in_field & on_curve29(QX, QY);
     Qp.A = QX;
     fe_sel(Qp.B, odd, ONE, QY);
-    pair_qtab_build29<QTab, 4>(Qp, QX, QY, qtab, odd);
+    if constexpr (BOOTH4) pair_qtab_build29<QTab, 4>(Qp, QX, QY, qtab, odd);
+    else pair_qtab_build_odd29<QTab>(Qp, QX, QY, qtab, odd);
     return q_ok;
 }
 

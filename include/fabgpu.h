@@ -67,7 +67,7 @@ typedef struct fabgpu_ctx fabgpu_ctx;
 #define FABGPU_FLAG_ONE_LANE_ONLY 1u /* never use the two-lanes-per-signature kernel (parity tests run both variants) */
 #define FABGPU_FLAG_NO_QUAD 4u       /* idemix: never use the four-lanes-per-signature kernel (parity tests run all three variants) */
 #define FABGPU_FLAG_TIME_KERNELS 2u  /* bracket every launch with timing events (tools only: read back through the test-hook library's fabgpu_last_kernel_ms) */
-#define FABGPU_FLAG_PAIR_TABLE_LDS 8u    /* two-lanes-per-signature verify kernel: per-signature table in LDS (8 entries, 65 signed 4-bit windows) */
+#define FABGPU_FLAG_PAIR_TABLE_LDS 8u    /* two-lanes-per-signature verify kernel: per-signature table in LDS (8 entries, 63 all-odd signed 4-bit windows) */
 #define FABGPU_FLAG_PAIR_TABLE_GLOBAL 16u /* ... in the global workspace (16 entries, 52 signed 5-bit windows).  Neither: the default */
 #define FABGPU_FLAG_NO_WIDE 32u          /* registered keys: never use the eight-lanes-per-signature, two-phase kernels that serve launches of up to
                                             8 192 signatures (parity tests run both forms) */
@@ -82,6 +82,9 @@ typedef struct fabgpu_ctx fabgpu_ctx;
                                         a helper wave beside each that computes s^-1, u1, u2 and u1*G (A/B runs; parity tests run both forms) */
 #define FABGPU_FLAG_PAIR_DBL1 2048u  /* ... in LDS, either form: the four doublings of a window as a loop over the one-doubling program (round 7's
                                         form) instead of one four-doubling program (A/B runs; parity tests run both forms) */
+#define FABGPU_FLAG_PAIR_BOOTH4 16384u /* ... in LDS, either form: signed (Booth) 4-bit digits over a table of j*Q, 65 windows with zero digits
+                                        (round 8's form) instead of the all-odd recoding over a table of odd multiples, 63 windows, no zero
+                                        digit (A/B runs; parity tests run both forms).  Statuses and verdict words do not change */
 
 #define FABGPU_FLAG_KEY_TABLES_16BIT 256u   /* registered keys (fabgpu_p256_key_register): each key also gets a 16-bit comb table - 80 MiB, the
                                             generator's format, built on the device BEHIND the registration (nobody waits for it), up to

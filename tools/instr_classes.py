@@ -45,13 +45,16 @@ def main():
         assert sum(c.values()) == total, (name, c, total)
         rows[name] = (c, total)
         print("%-28s %7d %7d %7d %7d %7d %7d %7d   %.2f" % (name, c["mac"], c["carry"], c["route"], c["field"], c["hazard"], c["scalar"], total, c["mac"] / total))
-    # trip counts of the LDS-table kernel: 64 windows x one four-doubling program (the first window has nothing to double; round 7: 64 x 4
-    # doublings) + the table's 4 doublings; 65 window additions + the final one; 16 comb + the table's 3 mixed additions (the final
-    # addition's doubling runs for crafted inputs only)
-    trips = {"doubling (4M + 4S)": 4, "four doublings (DBL4)": 64, "addition (12M + 4S)": 65 + 1, "mixed addition (8M + 3S)": 16 + 3}
+    # trip counts of the LDS-table kernel, all-odd recoding over a table of odd multiples: 63 windows x (one four-doubling program; one
+    # addition) under a top window that is a table read; the table's one doubling, one mixed addition and six additions; the final addition;
+    # 16 comb mixed additions (the final addition's doubling runs for crafted inputs only, the doubling for u2 = n - 2 or 2 for that scalar).
+    # The Booth form it replaced (FABGPU_FLAG_PAIR_BOOTH4): 4 doublings, 64 four-doubling programs, 65 + 1 additions, 16 + 3 mixed additions.
+    trips = {"doubling (4M + 4S)": 1, "four doublings (DBL4)": 63, "addition (12M + 4S)": 63 + 6 + 1, "mixed addition (8M + 3S)": 16 + 1}
+    booth4 = {"doubling (4M + 4S)": 4, "four doublings (DBL4)": 64, "addition (12M + 4S)": 65 + 1, "mixed addition (8M + 3S)": 16 + 3}
     print()
-    print("window doublings: 64 x %d = %d (round 7: 256 x %d = %d)" % (rows["four doublings (DBL4)"][1], 64 * rows["four doublings (DBL4)"][1],
-                                                                      rows["doubling (4M + 4S)"][1], 256 * rows["doubling (4M + 4S)"][1]))
+    print("window doublings: 63 x %d = %d (Booth digits: 64 x %d; round 7: 256 x %d = %d)" % (rows["four doublings (DBL4)"][1], 63 * rows["four doublings (DBL4)"][1],
+                                                                      rows["four doublings (DBL4)"][1], rows["doubling (4M + 4S)"][1], 256 * rows["doubling (4M + 4S)"][1]))
+    print("point programs with Booth digits (FABGPU_FLAG_PAIR_BOOTH4): %d" % sum(n * rows[name][1] for name, n in booth4.items()))
     tot = {k: 0 for k in ("mac", "carry", "route", "field", "hazard", "scalar")}
     for name, n in trips.items():
         for k in tot:
