@@ -24,6 +24,92 @@ void put_err(char* dst, size_t cap, const std::string& s) {
     memcpy(dst, s.data(), k);
     dst[k] = 0;
 }
+
+// One CSP.Verify answer as the single-signature entries hand it out: a device failure is FABGPU_ELAUNCH with its text and no
+// verdict; a provider that is poisoned by now answers FABGPU_EPOISONED, valid = 0 and the poisoned text.
+int put_answer(fabgpu_csp* csp, const VerifyResult& r, int* valid, int* flags, char* err, size_t errcap) {
+    if (r.infrastructure) {
+        put_err(err, errcap, r.err.msg);
+        return FABGPU_ELAUNCH;
+    }
+    *valid = r.valid ? 1 : 0;
+    if (flags) *flags = r.needs_sw ? 1 : 0;
+    put_err(err, errcap, r.err.ok() ? "" : r.err.msg);
+    if (csp->csp->Poisoned()) {                              // this call's own audit, or another thread's while it was in flight
+        *valid = 0;
+        put_err(err, errcap, GPUCSP::PoisonedText());
+        return FABGPU_EPOISONED;
+    }
+    return FABGPU_OK;
+}
+
+// a key of a flat batch: unmarshalled only, no device table
+void import_key(const GPUCSP& c, const uint8_t* qx, const uint8_t* qy, ECDSAPublicKey& k) { c.KeyImport(qx, qy, k); }
+void import_key(const GPUCSP&, const uint8_t* qx, const uint8_t* qy, ECDSAPublicKey384& k) { GPUCSP::KeyImport384(qx, qy, k); }
+// the P-384 entries answer the refusal text, item by item, while the p384 option is off
+template <class C>
+bool refused(const GPUCSP& c) { return C::W == 48 && !c.P384Enabled(); }
+
+// n independent CSP.Verify calls in one launch (`verb`: VerifyBatch / VerifyBatchP384).  The digests are the caller's: the family is only checked.
+template <class C, class Verb>
+int verify_batch(fabgpu_csp* csp, Verb verb, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* sig_arena, const uint32_t* sig_off,
+                 const uint8_t* dig_arena, const uint32_t* dig_off, const char* hash_family, uint8_t* valid, char* errs, size_t errstride) {
+    if (!csp || (n && (!qx || !qy || !sig_off || !dig_off || !valid))) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
+    bool sha3 = false;
+    std::string ferr;
+    const bool refuse = refused<C>(*csp->csp);
+    if (refuse) ferr = GPUCSP::P384RefusalText();
+    if (refuse || !csp->csp->HashFamily(hash_family, &sha3, &ferr)) {
+        for (size_t i = 0; i < n; i++) {
+            valid[i] = 0;
+            if (errs && errstride) put_err(errs + i * errstride, errstride, ferr);
+        }
+        return FABGPU_OK;
+    }
+    std::vector<typename C::Key> keys(n);
+    std::vector<VerifyItemT<typename C::Key>> items(n);
+    for (size_t i = 0; i < n; i++) {
+        import_key(*csp->csp, qx + C::W * i, qy + C::W * i, keys[i]);
+        items[i] = {&keys[i], sig_arena + sig_off[i], sig_off[i + 1] - sig_off[i], dig_arena + dig_off[i], dig_off[i + 1] - dig_off[i]};
+    }
+    std::vector<VerifyResult> res;
+    Error e = ((*csp->csp).*verb)(items, res);
+    if (!e.ok()) return FABGPU_ELAUNCH;
+    for (size_t i = 0; i < n; i++) {
+        valid[i] = res[i].valid ? 1 : 0;
+        if (errs && errstride) put_err(errs + i * errstride, errstride, res[i].err.ok() ? "" : res[i].err.msg);
+    }
+    // (an item whose audit failed carries PoisonedText instead of "valid"; the whole answer is then not to be used)
+    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
+}
+
+// identity.Verify for n triples of an MSP of the given family (`verb`: IdentityVerifyBatch / IdentityVerifyBatchP384)
+template <class C, class Verb>
+int identity_verify_batch(fabgpu_csp* csp, Verb verb, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena, const uint32_t* msg_off,
+                          const uint8_t* sig_arena, const uint32_t* sig_off, const char* hash_family, char* errs, size_t errstride) {
+    if (!csp || (n && (!qx || !qy || !msg_off || !sig_off || !errs || !errstride))) return FABGPU_EINVAL;
+    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
+    bool sha3 = false;
+    std::string ferr;
+    const bool refuse = refused<C>(*csp->csp);
+    if (refuse) ferr = std::string("could not determine the validity of the signature: ") + GPUCSP::P384RefusalText();
+    if (refuse || !csp->csp->HashFamily(hash_family, &sha3, &ferr)) {     // identity.Verify fails before it hashes: every item, the same text
+        for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, ferr);
+        return FABGPU_OK;
+    }
+    std::vector<typename C::Key> keys(n);
+    std::vector<IdentityItemT<typename C::Key>> items(n);
+    for (size_t i = 0; i < n; i++) {
+        import_key(*csp->csp, qx + C::W * i, qy + C::W * i, keys[i]);
+        items[i] = {&keys[i], msg_arena + msg_off[i], msg_off[i + 1] - msg_off[i], sig_arena + sig_off[i], sig_off[i + 1] - sig_off[i]};
+    }
+    std::vector<std::string> out;
+    Error e = ((*csp->csp).*verb)(items, out, sha3);
+    if (!e.ok()) return FABGPU_ELAUNCH;
+    for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, out[i]);
+    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -175,19 +261,7 @@ int fabgpu_csp_verify(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32,
         kp = &k;
     }
     VerifyResult r = csp->csp->Verify(kp, sig, siglen, digest, dlen);
-    if (r.infrastructure) {
-        put_err(err, errcap, r.err.msg);
-        return FABGPU_ELAUNCH;
-    }
-    *valid = r.valid ? 1 : 0;
-    if (flags) *flags = r.needs_sw ? 1 : 0;
-    put_err(err, errcap, r.err.ok() ? "" : r.err.msg);
-    if (csp->csp->Poisoned()) {                              // this call's own audit, or another thread's while it was in flight
-        *valid = 0;
-        put_err(err, errcap, GPUCSP::PoisonedText());
-        return FABGPU_EPOISONED;
-    }
-    return FABGPU_OK;
+    return put_answer(csp, r, valid, flags, err, errcap);
 }
 
 int fabgpu_csp_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen,
@@ -201,19 +275,7 @@ int fabgpu_csp_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, const uint
         kp = &k;
     }
     VerifyResult r = csp->csp->VerifyCoalesced(kp, sig, siglen, digest, dlen);
-    if (r.infrastructure) {
-        put_err(err, errcap, r.err.msg);
-        return FABGPU_ELAUNCH;
-    }
-    *valid = r.valid ? 1 : 0;
-    if (flags) *flags = r.needs_sw ? 1 : 0;
-    put_err(err, errcap, r.err.ok() ? "" : r.err.msg);
-    if (csp->csp->Poisoned()) {                              // this call's own audit, or another thread's while it was in flight
-        *valid = 0;
-        put_err(err, errcap, GPUCSP::PoisonedText());
-        return FABGPU_EPOISONED;
-    }
-    return FABGPU_OK;
+    return put_answer(csp, r, valid, flags, err, errcap);
 }
 
 int fabgpu_csp_identity_verify_coalesced(fabgpu_csp* csp, const uint8_t* qx32, const uint8_t* qy32, const uint8_t* msg, size_t msglen,
@@ -268,77 +330,19 @@ int fabgpu_csp_verify_coalesced_p384(fabgpu_csp* csp, const uint8_t* qx48, const
         kp = &k;
     }
     VerifyResult r = csp->csp->VerifyCoalescedP384(kp, sig, siglen, digest, dlen);
-    if (r.infrastructure) {
-        put_err(err, errcap, r.err.msg);
-        return FABGPU_ELAUNCH;
-    }
-    *valid = r.valid ? 1 : 0;
-    if (flags) *flags = r.needs_sw ? 1 : 0;
-    put_err(err, errcap, r.err.ok() ? "" : r.err.msg);
-    if (csp->csp->Poisoned()) {
-        *valid = 0;
-        put_err(err, errcap, GPUCSP::PoisonedText());
-        return FABGPU_EPOISONED;
-    }
-    return FABGPU_OK;
+    return put_answer(csp, r, valid, flags, err, errcap);
 }
 
 int fabgpu_csp_verify_batch_p384(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* sig_arena, const uint32_t* sig_off,
                                  const uint8_t* dig_arena, const uint32_t* dig_off, const char* hash_family, uint8_t* valid, char* errs,
                                  size_t errstride) {
-    if (!csp || (n && (!qx || !qy || !sig_off || !dig_off || !valid))) return FABGPU_EINVAL;
-    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
-    bool sha3 = false;
-    std::string ferr;
-    const bool refuse = !csp->csp->P384Enabled();
-    if (refuse) ferr = GPUCSP::P384RefusalText();
-    if (refuse || !csp->csp->HashFamily(hash_family, &sha3, &ferr)) {     // (the digests are the caller's: the family is only checked)
-        for (size_t i = 0; i < n; i++) {
-            valid[i] = 0;
-            if (errs && errstride) put_err(errs + i * errstride, errstride, ferr);
-        }
-        return FABGPU_OK;
-    }
-    std::vector<ECDSAPublicKey384> keys(n);
-    std::vector<VerifyItem384> items(n);
-    for (size_t i = 0; i < n; i++) {
-        GPUCSP::KeyImport384(qx + 48 * i, qy + 48 * i, keys[i]);
-        items[i] = {&keys[i], sig_arena + sig_off[i], sig_off[i + 1] - sig_off[i], dig_arena + dig_off[i], dig_off[i + 1] - dig_off[i]};
-    }
-    std::vector<VerifyResult> res;
-    Error e = csp->csp->VerifyBatchP384(items, res);
-    if (!e.ok()) return FABGPU_ELAUNCH;
-    for (size_t i = 0; i < n; i++) {
-        valid[i] = res[i].valid ? 1 : 0;
-        if (errs && errstride) put_err(errs + i * errstride, errstride, res[i].err.ok() ? "" : res[i].err.msg);
-    }
-    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
+    return verify_batch<Curve384>(csp, &GPUCSP::VerifyBatchP384, n, qx, qy, sig_arena, sig_off, dig_arena, dig_off, hash_family, valid, errs, errstride);
 }
 
 int fabgpu_csp_identity_verify_batch_p384(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena,
                                           const uint32_t* msg_off, const uint8_t* sig_arena, const uint32_t* sig_off, const char* hash_family,
                                           char* errs, size_t errstride) {
-    if (!csp || (n && (!qx || !qy || !msg_off || !sig_off || !errs || !errstride))) return FABGPU_EINVAL;
-    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
-    bool sha3 = false;
-    std::string ferr;
-    const bool refuse = !csp->csp->P384Enabled();
-    if (refuse) ferr = std::string("could not determine the validity of the signature: ") + GPUCSP::P384RefusalText();
-    if (refuse || !csp->csp->HashFamily(hash_family, &sha3, &ferr)) {
-        for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, ferr);
-        return FABGPU_OK;
-    }
-    std::vector<ECDSAPublicKey384> keys(n);
-    std::vector<IdentityItem384> items(n);
-    for (size_t i = 0; i < n; i++) {
-        GPUCSP::KeyImport384(qx + 48 * i, qy + 48 * i, keys[i]);
-        items[i] = {&keys[i], msg_arena + msg_off[i], msg_off[i + 1] - msg_off[i], sig_arena + sig_off[i], sig_off[i + 1] - sig_off[i]};
-    }
-    std::vector<std::string> out;
-    Error e = csp->csp->IdentityVerifyBatchP384(items, out, sha3);
-    if (!e.ok()) return FABGPU_ELAUNCH;
-    for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, out[i]);
-    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
+    return identity_verify_batch<Curve384>(csp, &GPUCSP::IdentityVerifyBatchP384, n, qx, qy, msg_arena, msg_off, sig_arena, sig_off, hash_family, errs, errstride);
 }
 
 int fabgpu_csp_coalescer_configure(fabgpu_csp* csp, uint32_t window_us, uint32_t max_batch) {
@@ -356,23 +360,9 @@ int fabgpu_csp_coalescer_stats(fabgpu_csp* csp, uint64_t* calls, uint64_t* launc
 int fabgpu_csp_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* sig_arena,
                             const uint32_t* sig_off, const uint8_t* dig_arena, const uint32_t* dig_off, uint8_t* valid,
                             char* errs, size_t errstride) {
-    if (!csp || (n && (!qx || !qy || !sig_off || !dig_off || !valid))) return FABGPU_EINVAL;
-    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
-    std::vector<ECDSAPublicKey> keys(n);
-    std::vector<VerifyItem> items(n);
-    for (size_t i = 0; i < n; i++) {
-        csp->csp->KeyImport(qx + 32 * i, qy + 32 * i, keys[i]);
-        items[i] = {&keys[i], sig_arena + sig_off[i], sig_off[i + 1] - sig_off[i], dig_arena + dig_off[i], dig_off[i + 1] - dig_off[i]};
-    }
-    std::vector<VerifyResult> res;
-    Error e = csp->csp->VerifyBatch(items, res);
-    if (!e.ok()) return FABGPU_ELAUNCH;
-    for (size_t i = 0; i < n; i++) {
-        valid[i] = res[i].valid ? 1 : 0;
-        if (errs && errstride) put_err(errs + i * errstride, errstride, res[i].err.ok() ? "" : res[i].err.msg);
-    }
-    // (an item whose audit failed carries PoisonedText instead of "valid"; the whole answer is then not to be used)
-    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
+    // (this entry takes no hash family: "SHA2" is the one ParseHashFamily always accepts, so the shared body's family check is a no-op
+    // here, and so is its P-384 refusal)
+    return verify_batch<Curve256>(csp, &GPUCSP::VerifyBatch, n, qx, qy, sig_arena, sig_off, dig_arena, dig_off, "SHA2", valid, errs, errstride);
 }
 
 int fabgpu_csp_identity_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena,
@@ -383,25 +373,7 @@ int fabgpu_csp_identity_verify_batch(fabgpu_csp* csp, size_t n, const uint8_t* q
 int fabgpu_csp_identity_verify_batch2(fabgpu_csp* csp, size_t n, const uint8_t* qx, const uint8_t* qy, const uint8_t* msg_arena,
                                       const uint32_t* msg_off, const uint8_t* sig_arena, const uint32_t* sig_off, const char* hash_family,
                                       char* errs, size_t errstride) {
-    if (!csp || (n && (!qx || !qy || !msg_off || !sig_off || !errs || !errstride))) return FABGPU_EINVAL;
-    if (csp->csp->Poisoned()) return FABGPU_EPOISONED;
-    bool sha3 = false;
-    std::string ferr;
-    if (!csp->csp->HashFamily(hash_family, &sha3, &ferr)) {               // identity.Verify fails before it hashes: every item, the same text
-        for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, ferr);
-        return FABGPU_OK;
-    }
-    std::vector<ECDSAPublicKey> keys(n);
-    std::vector<IdentityItem> items(n);
-    for (size_t i = 0; i < n; i++) {
-        csp->csp->KeyImport(qx + 32 * i, qy + 32 * i, keys[i]);
-        items[i] = {&keys[i], msg_arena + msg_off[i], msg_off[i + 1] - msg_off[i], sig_arena + sig_off[i], sig_off[i + 1] - sig_off[i]};
-    }
-    std::vector<std::string> out;
-    Error e = csp->csp->IdentityVerifyBatch(items, out, sha3);
-    if (!e.ok()) return FABGPU_ELAUNCH;
-    for (size_t i = 0; i < n; i++) put_err(errs + i * errstride, errstride, out[i]);
-    return csp->csp->Poisoned() ? FABGPU_EPOISONED : FABGPU_OK;
+    return identity_verify_batch<Curve256>(csp, &GPUCSP::IdentityVerifyBatch, n, qx, qy, msg_arena, msg_off, sig_arena, sig_off, hash_family, errs, errstride);
 }
 
 // The block pass behind both C entries: the walk on the device (block_walk_dev.h); a block it declines takes the host walk.

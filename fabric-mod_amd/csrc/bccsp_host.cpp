@@ -624,24 +624,6 @@ Error GPUCSP::KeyImport(const uint8_t* qx32, const uint8_t* qy32, ECDSAPublicKey
     return Error();
 }
 
-// key ids of the submitted items if EVERY submitted item's key is registered (then the keyed kernels apply)
-static bool all_registered(fabgpu_ctx* ctx, size_t n, const std::vector<uint8_t>& submitted, const uint8_t* qx, const uint8_t* qy,
-                           std::vector<uint32_t>& ids) {
-    ids.assign(n, 0);
-    uint32_t any = 0;
-    bool have = false;
-    for (size_t i = 0; i < n; i++) {
-        if (!submitted[i]) continue;
-        if (fabgpu_p256_key_lookup(ctx, qx + 32 * i, qy + 32 * i, &ids[i]) != FABGPU_OK) return false;
-        any = ids[i];
-        have = true;
-    }
-    if (!have) return false;
-    for (size_t i = 0; i < n; i++)
-        if (!submitted[i]) ids[i] = any;   // fillers: any registered key, the verdict is ignored
-    return true;
-}
-
 // bccsp/sw/impl.go:177-194
 Error GPUCSP::Hash(const uint8_t* msg, size_t len, const HashOpts* opts, std::vector<uint8_t>& digest) const {
     if (opts == nullptr) return Error("Invalid opts. It must not be nil.");
@@ -668,18 +650,56 @@ bool GPUCSP::SetMspHashFamily(const std::string& mspid, const char* family, std:
     return true;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the direct-call verbs: one body each over a curve description (bccsp_host.h Curve256 / Curve384)
+// ------------------------------------------------------------------------------------------------
+bool Curve256::low_s(const uint8_t* s32) { return memcmp(s32, HALF_N_BE, 32) <= 0; }
+void Curve256::generator(uint8_t* qx32, uint8_t* qy32) {
+    static const uint8_t GX[32] = {0x6b, 0x17, 0xd1, 0xf2, 0xe1, 0x2c, 0x42, 0x47, 0xf8, 0xbc, 0xe6, 0xe5, 0x63, 0xa4, 0x40, 0xf2,
+                                   0x77, 0x03, 0x7d, 0x81, 0x2d, 0xeb, 0x33, 0xa0, 0xf4, 0xa1, 0x39, 0x45, 0xd8, 0x98, 0xc2, 0x96};
+    static const uint8_t GY[32] = {0x4f, 0xe3, 0x42, 0xe2, 0xfe, 0x1a, 0x7f, 0x9b, 0x8e, 0xe7, 0xeb, 0x4a, 0x7c, 0x0f, 0x9e, 0x16,
+                                   0x2b, 0xce, 0x33, 0x57, 0x6b, 0x31, 0x5e, 0xce, 0xcb, 0xb6, 0x40, 0x68, 0x37, 0xbf, 0x51, 0xf5};
+    memcpy(qx32, GX, 32);
+    memcpy(qy32, GY, 32);
+}
+const char* Curve384::half_order_decimal() {
+    return "19701003098197239606139520050071806902539869635232723333973452639813829699556631784699478154076147456777216826971321";
+}
+bool Curve384::low_s(const uint8_t* s48) { return p384::is_low_s(s48); }
+void Curve384::hash_to_int(const uint8_t* digest, size_t len, uint8_t* e48) { p384::hash_to_int(digest, len, e48); }
+void Curve384::generator(uint8_t* qx48, uint8_t* qy48) {
+    p384::u384 gx = FAB_P384_GX_MONT, gy = FAB_P384_GY_MONT, t;
+    p384::fp_from_mont(t, gx); p384::to_be48(qx48, t);
+    p384::fp_from_mont(t, gy); p384::to_be48(qy48, t);
+}
+
 namespace {
 // outcome of the pre-arithmetic gates for one item; `submit` means the device decides
-struct Gate {
+template <class C>
+struct GateT {
     bool submit = false;
     VerifyResult res;
-    uint8_t r32[32], s32[32], e32[32];
+    uint8_t r[C::W], s[C::W], e[C::W];
 };
 
-Gate gate_item(const ECDSAPublicKey* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) {
-    Gate g;
-    memset(g.r32, 0, 32); memset(g.s32, 0, 32); memset(g.e32, 0, 32);
-    g.r32[31] = g.s32[31] = 1;
+// the low `w` bytes of a non-negative value; false: it has more
+bool low_bytes(const BigInt& v, uint8_t* out, size_t w) {
+    const std::vector<uint8_t> m = v.magnitude();
+    memset(out, 0, w);
+    const size_t take = m.size() < w ? m.size() : w;
+    if (take) memcpy(out + w - take, m.data() + m.size() - take, take);
+    return m.size() <= w;
+}
+
+// The checks bccsp/sw makes before any arithmetic, in its order and with its texts, for a key of either curve: low S against the
+// half order of the key's own curve (bccsp/utils/ecdsa.go:84-92), r above 2^(8 W) > n: (false, nil).  A row that is not submitted
+// keeps r = s = 1, e = 0.
+template <class C>
+GateT<C> gate_item(const typename C::Key* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) {
+    constexpr size_t W = C::W;
+    GateT<C> g;
+    memset(g.r, 0, W); memset(g.s, 0, W); memset(g.e, 0, W);
+    g.r[W - 1] = g.s[W - 1] = 1;
     // bccsp/sw/impl.go:249-257
     if (k == nullptr) { g.res = {false, Error("Invalid Key. It must not be nil.")}; return g; }
     if (siglen == 0) { g.res = {false, Error("Invalid signature. Cannot be empty.")}; return g; }
@@ -687,30 +707,34 @@ Gate gate_item(const ECDSAPublicKey* k, const uint8_t* sig, size_t siglen, const
     // Fast path for the overwhelmingly common shape - a minimal DER SEQUENCE { INTEGER r, INTEGER s } with positive r, s below
     // 2^256 and low s - which the general parser below would accept with exactly these values; anything else (long-form
     // lengths, trailing bytes, negative or zero integers, high s, oversize r ...) takes the general path and its error texts.
-    if (k->on_curve && siglen >= 8 && siglen <= 72 && sig[0] == 0x30 && sig[1] == siglen - 2 && sig[2] == 0x02) {
-        size_t lr = sig[3];
-        if (lr >= 1 && lr <= 33 && 4 + lr + 2 <= siglen && sig[4 + lr] == 0x02) {
-            size_t ls = sig[5 + lr];
-            const uint8_t* pr = sig + 4;
-            const uint8_t* ps = sig + 6 + lr;
-            auto minimal_positive = [](const uint8_t* p, size_t l) {
-                if (p[0] & 0x80) return false;                                  // negative
-                if (p[0] == 0) return l > 1 && (p[1] & 0x80) != 0 && l <= 33;   // a leading zero must be needed (also excludes zero)
-                return l <= 32;
-            };
-            if (ls >= 1 && ls <= 33 && 6 + lr + ls == siglen && minimal_positive(pr, lr) && minimal_positive(ps, ls)) {
-                if (pr[0] == 0) { pr++; lr--; }
-                if (ps[0] == 0) { ps++; ls--; }
-                memset(g.r32, 0, 32); memset(g.s32, 0, 32);
-                memcpy(g.r32 + 32 - lr, pr, lr);
-                memcpy(g.s32 + 32 - ls, ps, ls);
-                if (memcmp(g.s32, HALF_N_BE, 32) <= 0) {                        // low-S: the device decides (r >= n included)
-                    HashToInt(digest, dlen, g.e32);
-                    g.submit = true;
-                    return g;
+    // P-256 only: a P-384 signature of this shape is past 127 bytes half the time and then has a long-form length.
+    if constexpr (C::kDerFastPath) {
+        static_assert(W == 32, "the lengths below are those of 256-bit integers");
+        if (k->on_curve && siglen >= 8 && siglen <= 72 && sig[0] == 0x30 && sig[1] == siglen - 2 && sig[2] == 0x02) {
+            size_t lr = sig[3];
+            if (lr >= 1 && lr <= 33 && 4 + lr + 2 <= siglen && sig[4 + lr] == 0x02) {
+                size_t ls = sig[5 + lr];
+                const uint8_t* pr = sig + 4;
+                const uint8_t* ps = sig + 6 + lr;
+                auto minimal_positive = [](const uint8_t* p, size_t l) {
+                    if (p[0] & 0x80) return false;                                  // negative
+                    if (p[0] == 0) return l > 1 && (p[1] & 0x80) != 0 && l <= 33;   // a leading zero must be needed (also excludes zero)
+                    return l <= 32;
+                };
+                if (ls >= 1 && ls <= 33 && 6 + lr + ls == siglen && minimal_positive(pr, lr) && minimal_positive(ps, ls)) {
+                    if (pr[0] == 0) { pr++; lr--; }
+                    if (ps[0] == 0) { ps++; ls--; }
+                    memset(g.r, 0, 32); memset(g.s, 0, 32);
+                    memcpy(g.r + 32 - lr, pr, lr);
+                    memcpy(g.s + 32 - ls, ps, ls);
+                    if (C::low_s(g.s)) {                                            // low-S: the device decides (r >= n included)
+                        C::hash_to_int(digest, dlen, g.e);
+                        g.submit = true;
+                        return g;
+                    }
+                    memset(g.r, 0, 32); memset(g.s, 0, 32);
+                    g.r[31] = g.s[31] = 1;
                 }
-                memset(g.r32, 0, 32); memset(g.s32, 0, 32);
-                g.r32[31] = g.s32[31] = 1;
             }
         }
     }
@@ -718,64 +742,95 @@ Gate gate_item(const ECDSAPublicKey* k, const uint8_t* sig, size_t siglen, const
     BigInt R, S;
     Error e = UnmarshalECDSASignature(sig, siglen, R, S);
     if (!e.ok()) { g.res = {false, Error(wrap + "Failed unmashalling signature [" + e.msg + "]")}; return g; }
-    if (!IsLowS(S)) {
-        g.res = {false, Error(wrap + "Invalid S. Must be smaller than half the order [" + S.decimal() + "][" + HALF_ORDER_DECIMAL + "].")};
+    uint8_t r_be[W], s_be[W];                                          // (R and S are positive here)
+    const bool s_fits = low_bytes(S, s_be, W), r_fits = low_bytes(R, r_be, W);
+    if (!s_fits || !C::low_s(s_be)) {
+        g.res = {false, Error(wrap + "Invalid S. Must be smaller than half the order [" + S.decimal() + "][" + C::half_order_decimal() + "].")};
         return g;
     }
-    if (!R.fits256()) { g.res = {false, Error()}; return g; }   // r >= 2^256 > n: ecdsa.Verify returns false
+    if (!r_fits) { g.res = {false, Error()}; return g; }               // r >= 2^(8 W) > n: ecdsa.Verify returns false
     if (!k->on_curve) {
-        g.res = {false, Error("public key is not on P-256: the GPU provider does not decide this tuple (use bccsp/sw)")};
+        g.res = {false, Error(std::string("public key is not on ") + C::kName + ": the GPU provider does not decide this tuple (use bccsp/sw)")};
         g.res.needs_sw = true;
         return g;
     }
-    R.to_be32(g.r32);
-    S.to_be32(g.s32);
-    HashToInt(digest, dlen, g.e32);
+    memcpy(g.r, r_be, W);
+    memcpy(g.s, s_be, W);
+    C::hash_to_int(digest, dlen, g.e);
     g.submit = true;
     return g;
 }
+
+// what the block pass writes for a tuple the gate did not submit (both routes' P-256 tuples and the P-384 stage)
+uint8_t gate_tuple_status(const VerifyResult& res) {
+    if (res.err.ok()) return FABGPU_ST_RANGE;                                            // r does not fit the field: (false, nil)
+    if (res.err.msg.find("Invalid S") != std::string::npos) return FABGPU_ST_HIGH_S;
+    return TUPLE_ST_BAD_DER;
+}
+
+// key ids of the submitted items on `ctx` if EVERY submitted item's key is registered there (then the keyed entries apply)
+template <class C>
+bool all_registered(fabgpu_ctx* ctx, size_t n, const std::vector<uint8_t>& submitted, const uint8_t* qx, const uint8_t* qy, std::vector<uint32_t>& ids) {
+    ids.assign(n, 0);
+    uint32_t any = 0;
+    bool have = false;
+    for (size_t i = 0; i < n; i++) {
+        if (!submitted[i]) continue;
+        if (C::lookup(ctx, qx + C::W * i, qy + C::W * i, &ids[i]) != FABGPU_OK) return false;
+        any = ids[i];
+        have = true;
+    }
+    if (!have) return false;
+    for (size_t i = 0; i < n; i++)
+        if (!submitted[i]) ids[i] = any;   // fillers: any registered key, the verdict is ignored
+    return true;
+}
+
+const char* const kSha3RefusalText = "SHA3 is served by bccsp/sw, not by the GPU provider";
 }  // namespace
 
 // bccsp/sw/impl.go:247-270 -> bccsp/sw/ecdsa.go:41-57, batched
-Error GPUCSP::VerifyBatch(const std::vector<VerifyItem>& items, std::vector<VerifyResult>& results) const {
+template <class C>
+Error GPUCSP::VerifyBatchT(const std::vector<VerifyItemT<typename C::Key>>& items, std::vector<VerifyResult>& results) const {
+    constexpr size_t W = C::W;
     const size_t n = items.size();
     results.assign(n, VerifyResult());
-    std::vector<uint8_t> qx(n * 32), qy(n * 32), e(n * 32), r(n * 32), s(n * 32), st(n);
+    std::vector<uint8_t> qx(n * W), qy(n * W), e(n * W), r(n * W), s(n * W), st(n), submitted(n, 0);
     std::vector<uint64_t> bits((n + 63) / 64);
-    std::vector<uint8_t> submitted(n, 0);
     for (size_t i = 0; i < n; i++) {
-        const VerifyItem& it = items[i];
-        Gate g = gate_item(it.key, it.sig, it.siglen, it.digest, it.dlen);
+        const auto& it = items[i];
+        const GateT<C> g = gate_item<C>(it.key, it.sig, it.siglen, it.digest, it.dlen);
         results[i] = g.res;
         submitted[i] = g.submit;
-        // non-submitted slots carry a harmless dummy tuple so the batch stays dense
-        static const uint8_t GX[32] = {0x6b, 0x17, 0xd1, 0xf2, 0xe1, 0x2c, 0x42, 0x47, 0xf8, 0xbc, 0xe6, 0xe5, 0x63, 0xa4, 0x40, 0xf2,
-                                       0x77, 0x03, 0x7d, 0x81, 0x2d, 0xeb, 0x33, 0xa0, 0xf4, 0xa1, 0x39, 0x45, 0xd8, 0x98, 0xc2, 0x96};
-        static const uint8_t GY[32] = {0x4f, 0xe3, 0x42, 0xe2, 0xfe, 0x1a, 0x7f, 0x9b, 0x8e, 0xe7, 0xeb, 0x4a, 0x7c, 0x0f, 0x9e, 0x16,
-                                       0x2b, 0xce, 0x33, 0x57, 0x6b, 0x31, 0x5e, 0xce, 0xcb, 0xb6, 0x40, 0x68, 0x37, 0xbf, 0x51, 0xf5};
-        memcpy(&qx[32 * i], g.submit ? it.key->x : GX, 32);
-        memcpy(&qy[32 * i], g.submit ? it.key->y : GY, 32);
-        memcpy(&e[32 * i], g.e32, 32);
-        memcpy(&r[32 * i], g.r32, 32);
-        memcpy(&s[32 * i], g.s32, 32);
+        // a slot the gate did not submit carries the generator as its key (r = s = 1, e = 0): the batch stays dense
+        if (g.submit) { memcpy(&qx[W * i], it.key->x, W); memcpy(&qy[W * i], it.key->y, W); }
+        else C::generator(&qx[W * i], &qy[W * i]);
+        memcpy(&e[W * i], g.e, W);
+        memcpy(&r[W * i], g.r, W);
+        memcpy(&s[W * i], g.s, W);
     }
     if (n == 0) return Error();
+    fabgpu_ctx* const ctx = flat_ctx();                      // (one device serves the whole batch; batches take turns round the pool)
     std::vector<uint32_t> ids;
-    fabgpu_ctx* const ctx_ = flat_ctx();                     // (one device serves the whole batch; batches take turns round the pool)
-    int rc = all_registered(ctx_, n, submitted, qx.data(), qy.data(), ids)
-                 ? fabgpu_p256_verify_batch_keyed(ctx_, n, ids.data(), e.data(), r.data(), s.data(), bits.data(), st.data())
-                 : fabgpu_p256_verify_batch(ctx_, n, qx.data(), qy.data(), e.data(), r.data(), s.data(), bits.data(), st.data());
+    // (a key retired between the lookup and the launch would answer 4 - "internal inconsistency" below)
+    int rc = all_registered<C>(ctx, n, submitted, qx.data(), qy.data(), ids)
+                 ? C::verify_keyed(ctx, n, ids.data(), e.data(), r.data(), s.data(), bits.data(), st.data())
+                 : C::verify(ctx, n, qx.data(), qy.data(), e.data(), r.data(), s.data(), bits.data(), st.data());
     if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
     for (size_t i = 0; i < n; i++) {
         if (!submitted[i]) continue;
-        bool bit = (bits[i >> 6] >> (i & 63)) & 1;
         // after the host gates the device can only answer valid / arithmetic reject / r >= n
-        results[i].valid = bit && st[i] == FABGPU_ST_VALID;
+        if (st[i] == FABGPU_ST_HIGH_S || st[i] == FABGPU_ST_OFF_CURVE) return Error("internal inconsistency between host gate and device status");
+        bool valid = ((bits[i >> 6] >> (i & 63)) & 1) && st[i] == FABGPU_ST_VALID;
+        if (C::kTestFlip && !valid && st[i] == FABGPU_ST_BAD_MATH) {          // (test hook: a corrupted verdict)
+            uint32_t f = test_p384_flip_.load(std::memory_order_relaxed);
+            while (f && !test_p384_flip_.compare_exchange_weak(f, f - 1)) {}
+            if (f) valid = true;
+        }
+        results[i].valid = valid;
         results[i].err = Error();
-        if (st[i] == FABGPU_ST_HIGH_S || st[i] == FABGPU_ST_OFF_CURVE)   // cannot happen: host gate already decided
-            return Error("internal inconsistency between host gate and device status");
         // a sampled "valid" is verified again on the CPU before it leaves (rejects are re-checked by bccsp/sw on the Go side anyway)
-        if (results[i].valid && !AuditDirect(*items[i].key, items[i].sig, items[i].siglen, items[i].digest, items[i].dlen, "bccsp.Verify")) {
+        if (valid && !AuditDirect<C>(*items[i].key, items[i].sig, items[i].siglen, items[i].digest, items[i].dlen, "bccsp.Verify")) {
             results[i] = VerifyResult();
             results[i].err = Error(PoisonedText());
             results[i].poisoned = true;
@@ -783,6 +838,7 @@ Error GPUCSP::VerifyBatch(const std::vector<VerifyItem>& items, std::vector<Veri
     }
     return Error();
 }
+Error GPUCSP::VerifyBatch(const std::vector<VerifyItem>& items, std::vector<VerifyResult>& results) const { return VerifyBatchT<Curve256>(items, results); }
 
 VerifyResult GPUCSP::Verify(const ECDSAPublicKey* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) const {
     std::vector<VerifyItem> items(1);
@@ -798,77 +854,80 @@ VerifyResult GPUCSP::Verify(const ECDSAPublicKey* k, const uint8_t* sig, size_t 
     return res[0];
 }
 
-// msp/identities.go:169-196 over a flattened batch: digest = Hash(msg); Verify(pk, sig, digest); the hash is fused
-// into the verify kernel.  out[i]: "" (nil) or the error text identity.Verify would return.
-Error GPUCSP::IdentityVerifyBatch(const std::vector<IdentityItem>& items, std::vector<std::string>& out, bool sha3) const {
+// msp/identities.go:169-196 over a flattened batch: digest = Hash(msg) in the MSP's family; Verify(pk, sig, digest).  The SHA-256
+// hash is fused into the verify kernel, SHA3-256 is a launch of its own ahead of the verify-only kernels (fabgpu.h).
+// out[i]: "" (nil) or the error text identity.Verify would return.
+template <class C>
+Error GPUCSP::IdentityVerifyBatchT(const std::vector<IdentityItemT<typename C::Key>>& items, std::vector<std::string>& out, bool sha3) const {
+    constexpr size_t W = C::W;
     const size_t n = items.size();
     out.assign(n, std::string());
     if (n == 0) return Error();
-    std::vector<uint8_t> qx(n * 32), qy(n * 32), r(n * 32), s(n * 32), st(n), arena;
+    std::vector<uint8_t> qx(n * W), qy(n * W), r(n * W), s(n * W), st(n), submitted(n, 0), arena;
     std::vector<uint32_t> off(n + 1);
     std::vector<uint64_t> bits((n + 63) / 64);
-    std::vector<uint8_t> submitted(n, 0);
     static const uint8_t one_digest[1] = {1};
-    size_t total = 0;
-    for (size_t i = 0; i < n; i++) total += items[i].msglen;
-    if (total > 0xFFFFFFF0ull) return Error("message arena exceeds 32-bit offsets");
-    arena.reserve(total + 4);
+    size_t total = 0;                                        // bytes of the messages that are staged: the submitted rows'
     for (size_t i = 0; i < n; i++) {
-        const IdentityItem& it = items[i];
-        off[i] = (uint32_t)arena.size();
-        arena.insert(arena.end(), it.msg, it.msg + it.msglen);
-        // the digest is non-empty by construction (SHA-256), so only key / signature gates apply here
-        Gate g = gate_item(it.key, it.sig, it.siglen, one_digest, 1);
+        const auto& it = items[i];
+        // the digest is non-empty by construction (a hash), so only key / signature gates apply here
+        const GateT<C> g = gate_item<C>(it.key, it.sig, it.siglen, one_digest, 1);
         submitted[i] = g.submit;
-        if (!g.submit) {
-            if (g.res.err.ok()) out[i] = "The signature is invalid";
-            else out[i] = "could not determine the validity of the signature: " + g.res.err.msg;
-        }
-        const ECDSAPublicKey* k = it.key;
-        if (g.submit) { memcpy(&qx[32 * i], k->x, 32); memcpy(&qy[32 * i], k->y, 32); }
-        else { qx[32 * i + 31] = 1; qy[32 * i + 31] = 1; }   // off-curve filler: device answers status 4, ignored
-        memcpy(&r[32 * i], g.r32, 32);
-        memcpy(&s[32 * i], g.s32, 32);
+        if (!g.submit) out[i] = g.res.err.ok() ? "The signature is invalid" : "could not determine the validity of the signature: " + g.res.err.msg;
+        if (g.submit) { memcpy(&qx[W * i], it.key->x, W); memcpy(&qy[W * i], it.key->y, W); total += it.msglen; }
+        else C::generator(&qx[W * i], &qy[W * i]);          // as in VerifyBatchT; the row's message is an empty span
+        memcpy(&r[W * i], g.r, W);
+        memcpy(&s[W * i], g.s, W);
+    }
+    if (total > 0xFFFFFFF0ull) return Error("message arena exceeds 32-bit offsets");
+    arena.reserve(total + 8);
+    for (size_t i = 0; i < n; i++) {
+        off[i] = (uint32_t)arena.size();
+        if (submitted[i] && items[i].msglen) arena.insert(arena.end(), items[i].msg, items[i].msg + items[i].msglen);
     }
     off[n] = (uint32_t)arena.size();
+    arena.resize(arena.size() + 8);
+    fabgpu_ctx* const ctx = flat_ctx();
+    // The P-256 verb has always refused SHA3 here, behind the empty batch and the arena check.  The P-384 forward refuses it ahead of both
+    // (its own order), so for P-384 this second check never fires.
+    if (sha3 && !Sha3Enabled()) return Error(kSha3RefusalText);
     std::vector<uint32_t> ids;
-    fabgpu_ctx* const ctx_ = flat_ctx();
-    if (sha3 && !Sha3Enabled()) return Error("SHA3 is served by bccsp/sw, not by the GPU provider");
-    const bool keyed = all_registered(ctx_, n, submitted, qx.data(), qy.data(), ids);
-    int rc;
-    if (sha3)   // an MSP of the SHA3 family: SHA3-256 launch, then the verify-only kernels over its digests (fabgpu.h)
-        rc = keyed ? fabgpu_sha3_256_p256_verify_batch_keyed(ctx_, n, arena.data(), off.data(), ids.data(), r.data(), s.data(), bits.data(), st.data())
-                   : fabgpu_sha3_256_p256_verify_batch(ctx_, n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data());
-    else
-        rc = keyed ? fabgpu_sha256_p256_verify_batch_keyed(ctx_, n, arena.data(), off.data(), ids.data(), r.data(), s.data(), bits.data(), st.data())
-                   : fabgpu_sha256_p256_verify_batch(ctx_, n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data());
+    const int rc = all_registered<C>(ctx, n, submitted, qx.data(), qy.data(), ids)
+                       ? (sha3 ? C::sha3_verify_keyed : C::sha256_verify_keyed)(ctx, n, arena.data(), off.data(), ids.data(), r.data(), s.data(), bits.data(), st.data())
+                       : (sha3 ? C::sha3_verify : C::sha256_verify)(ctx, n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data());
     if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
     for (size_t i = 0; i < n; i++) {
         if (!submitted[i]) continue;
-        bool ok = ((bits[i >> 6] >> (i & 63)) & 1) && st[i] == FABGPU_ST_VALID;
+        const bool ok = ((bits[i >> 6] >> (i & 63)) & 1) && st[i] == FABGPU_ST_VALID;
         out[i] = ok ? "" : "The signature is invalid";
-        // as in VerifyBatch; a sampled message is hashed again first
-        if (ok && !AuditDirect(*items[i].key, items[i].sig, items[i].siglen, nullptr, 0, "identity.Verify", items[i].msg, items[i].msglen, sha3)) out[i] = PoisonedText();
+        // as in VerifyBatchT; a sampled message is hashed again first
+        if (ok && !AuditDirect<C>(*items[i].key, items[i].sig, items[i].siglen, nullptr, 0, "identity.Verify", items[i].msg, items[i].msglen, sha3)) out[i] = PoisonedText();
     }
     return Error();
+}
+Error GPUCSP::IdentityVerifyBatch(const std::vector<IdentityItem>& items, std::vector<std::string>& out, bool sha3) const {
+    return IdentityVerifyBatchT<Curve256>(items, out, sha3);
 }
 
 // ------------------------------------------------------------------------------------------------
 // one-signature calls from many threads, sharing launches (coalescer.h)
 // ------------------------------------------------------------------------------------------------
-VerifyResult GPUCSP::VerifyCoalesced(const ECDSAPublicKey* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) const {
+template <class C, class Queue, class BatchVerb>
+VerifyResult GPUCSP::VerifyCoalescedT(Queue& queue, BatchVerb verb, const typename C::Key* k, const uint8_t* sig, size_t siglen, const uint8_t* digest,
+                                      size_t dlen) const {
     // the argument checks and the DER / low-S gates need no device: decided here, on the caller's thread, like Verify would
-    Gate g = gate_item(k, sig, siglen, digest, dlen);
+    const GateT<C> g = gate_item<C>(k, sig, siglen, digest, dlen);
     if (!g.submit) return g.res;
-    CoReqV req;
+    typedef CoReqVT<typename C::Key> Req;
+    Req req;
     req.item = {k, sig, siglen, digest, dlen};
-    co_verify_.submit(&req, [this](std::vector<CoReqV*>& batch) {
+    queue.submit(&req, [this, verb](std::vector<Req*>& batch) {
         std::vector<VerifyResult> res;
         Error e;
         try {                                                     // a runner must not throw: followers would sleep forever
-            std::vector<VerifyItem> items(batch.size());
+            std::vector<VerifyItemT<typename C::Key>> items(batch.size());
             for (size_t i = 0; i < batch.size(); i++) items[i] = batch[i]->item;
-            e = VerifyBatch(items, res);
+            e = (this->*verb)(items, res);
         } catch (const std::exception& x) {
             e = Error(std::string("GPU verify failed: ") + x.what());
         }
@@ -884,12 +943,15 @@ VerifyResult GPUCSP::VerifyCoalesced(const ECDSAPublicKey* k, const uint8_t* sig
     });
     return req.res;
 }
+VerifyResult GPUCSP::VerifyCoalesced(const ECDSAPublicKey* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) const {
+    return VerifyCoalescedT<Curve256>(co_verify_, &GPUCSP::VerifyBatch, k, sig, siglen, digest, dlen);
+}
 
 std::string GPUCSP::IdentityVerifyCoalesced(const ECDSAPublicKey* k, const uint8_t* msg, size_t msglen, const uint8_t* sig, size_t siglen,
                                             bool* infrastructure, bool sha3) const {
     if (infrastructure) *infrastructure = false;
     static const uint8_t one_digest[1] = {1};
-    Gate g = gate_item(k, sig, siglen, one_digest, 1);           // as in IdentityVerifyBatch: the digest is non-empty by construction
+    const GateT<Curve256> g = gate_item<Curve256>(k, sig, siglen, one_digest, 1);   // as in IdentityVerifyBatchT: the digest is non-empty by construction
     if (!g.submit) return g.res.err.ok() ? "The signature is invalid" : "could not determine the validity of the signature: " + g.res.err.msg;
     CoReqI req;
     req.item = {k, msg, msglen, sig, siglen};
@@ -1254,7 +1316,8 @@ bool GPUCSP::AuditNymDirect(int64_t issuer_id, const uint8_t* nym_x32, const uin
     Poison(std::string("pseudonym audit: the device accepted a pseudonym signature in NymVerifier.Verify that the CPU audit rejects (Nym X ") + hex8(nym_x32) + "..)");
     return false;
 }
-bool GPUCSP::AuditDirect(const ECDSAPublicKey& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
+template <class C>
+bool GPUCSP::AuditDirect(const typename C::Key& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
                          const uint8_t* msg, size_t msglen, bool sha3) const {
     if (!audit_sample_[AUDIT_DIRECT].hit(AuditPermille())) return true;
     bool accept;
@@ -1267,12 +1330,12 @@ bool GPUCSP::AuditDirect(const ECDSAPublicKey& k, const uint8_t* sig, size_t sig
             digest = dg;
             dlen = 32;
         }
-        accept = audit_p256_verify(k.x, k.y, sig, siglen, digest, dlen);
+        accept = C::audit(k.x, k.y, sig, siglen, digest, dlen);
     }
     audit_count_[AUDIT_DIRECT].fetch_add(1, std::memory_order_relaxed);
     if (accept) return true;
     audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
-    Poison(std::string("direct call: the device accepted a signature in ") + what + " that the CPU audit rejects (key X " + hex8(k.x) + "..)");
+    Poison(std::string("direct call: the device accepted ") + C::kAuditNoun + " in " + what + " that the CPU audit rejects (key X " + hex8(k.x) + "..)");
     return false;
 }
 // ------------------------------------------------------------------------------------------------
@@ -1302,171 +1365,24 @@ Error GPUCSP::KeyImportP384(const uint8_t* qx48, const uint8_t* qy48, ECDSAPubli
     }
     return Error();
 }
-namespace {
-// key ids of the submitted items on `ctx` if EVERY submitted item's key is registered there (then the keyed entries apply)
-bool all_registered384(fabgpu_ctx* ctx, size_t n, const std::vector<uint8_t>& submitted, const uint8_t* qx, const uint8_t* qy, std::vector<uint32_t>& ids) {
-    ids.assign(n, 0);
-    uint32_t any = 0;
-    bool have = false;
-    for (size_t i = 0; i < n; i++) {
-        if (!submitted[i]) continue;
-        if (fabgpu_p384_key_lookup(ctx, qx + 48 * i, qy + 48 * i, &ids[i]) != FABGPU_OK) return false;
-        any = ids[i];
-        have = true;
-    }
-    if (!have) return false;
-    for (size_t i = 0; i < n; i++)
-        if (!submitted[i]) ids[i] = any;   // fillers: any registered key, the verdict is ignored
-    return true;
-}
-const char* HALF_ORDER_P384_DECIMAL = "19701003098197239606139520050071806902539869635232723333973452639813829699556631784699478154076147456777216826971321";
-// the low 384 bits of a non-negative value; false: it has more
-bool to_be48(const BigInt& v, uint8_t* out48) {
-    const std::vector<uint8_t> m = v.magnitude();
-    memset(out48, 0, 48);
-    const size_t take = m.size() < 48 ? m.size() : 48;
-    if (take) memcpy(out48 + 48 - take, m.data() + m.size() - take, take);
-    return m.size() <= 48;
-}
-struct Gate384 {
-    bool submit = false;
-    VerifyResult res;
-    uint8_t r[48], s[48], e[48];
-};
-// gate_item for a P-384 key: the same checks in the same order with the same texts; IsLowS against P-384's half order
-// (bccsp/utils/ecdsa.go:84-92 takes the key's own curve), r above 2^384 > n: (false, nil)
-Gate384 gate_item384(const ECDSAPublicKey384* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) {
-    Gate384 g;
-    memset(g.r, 0, 48); memset(g.s, 0, 48); memset(g.e, 0, 48);
-    g.r[47] = g.s[47] = 1;
-    if (k == nullptr) { g.res = {false, Error("Invalid Key. It must not be nil.")}; return g; }
-    if (siglen == 0) { g.res = {false, Error("Invalid signature. Cannot be empty.")}; return g; }
-    if (dlen == 0) { g.res = {false, Error("Invalid digest. Cannot be empty.")}; return g; }
-    const std::string wrap = "Failed verifing with opts [<nil>]: ";   // errors.Wrapf at impl.go:266
-    BigInt R, S;
-    Error e = UnmarshalECDSASignature(sig, siglen, R, S);
-    if (!e.ok()) { g.res = {false, Error(wrap + "Failed unmashalling signature [" + e.msg + "]")}; return g; }
-    uint8_t r48[48], s48[48];
-    const bool s_fits = to_be48(S, s48), r_fits = to_be48(R, r48);
-    if (!s_fits || !p384::is_low_s(s48)) {
-        g.res = {false, Error(wrap + "Invalid S. Must be smaller than half the order [" + S.decimal() + "][" + HALF_ORDER_P384_DECIMAL + "].")};
-        return g;
-    }
-    if (!r_fits) { g.res = {false, Error()}; return g; }
-    if (!k->on_curve) {
-        g.res = {false, Error("public key is not on P-384: the GPU provider does not decide this tuple (use bccsp/sw)")};
-        g.res.needs_sw = true;
-        return g;
-    }
-    memcpy(g.r, r48, 48);
-    memcpy(g.s, s48, 48);
-    p384::hash_to_int(digest, dlen, g.e);
-    g.submit = true;
-    return g;
-}
-// a slot the gate did not submit carries the generator as its key (r = s = 1, e = 0): the batch stays dense
-void put_generator384(uint8_t* qx48, uint8_t* qy48) {
-    p384::u384 gx = FAB_P384_GX_MONT, gy = FAB_P384_GY_MONT, t;
-    p384::fp_from_mont(t, gx); p384::to_be48(qx48, t);
-    p384::fp_from_mont(t, gy); p384::to_be48(qy48, t);
-}
-}  // namespace
-
+// the P-384 direct calls: with the option off every item answers the refusal, nothing is gated or launched
 Error GPUCSP::VerifyBatchP384(const std::vector<VerifyItem384>& items, std::vector<VerifyResult>& results) const {
-    const size_t n = items.size();
-    results.assign(n, VerifyResult());
     if (!P384Enabled()) {
+        results.assign(items.size(), VerifyResult());
         for (auto& r : results) r.err = Error(P384RefusalText()), r.needs_sw = true;
         return Error();
     }
-    std::vector<uint8_t> qx(n * 48), qy(n * 48), e(n * 48), r(n * 48), s(n * 48), st(n), submitted(n, 0);
-    std::vector<uint64_t> bits((n + 63) / 64);
-    for (size_t i = 0; i < n; i++) {
-        const VerifyItem384& it = items[i];
-        Gate384 g = gate_item384(it.key, it.sig, it.siglen, it.digest, it.dlen);
-        results[i] = g.res;
-        submitted[i] = g.submit;
-        if (g.submit) { memcpy(&qx[48 * i], it.key->x, 48); memcpy(&qy[48 * i], it.key->y, 48); }
-        else put_generator384(&qx[48 * i], &qy[48 * i]);
-        memcpy(&e[48 * i], g.e, 48);
-        memcpy(&r[48 * i], g.r, 48);
-        memcpy(&s[48 * i], g.s, 48);
-    }
-    if (n == 0) return Error();
-    fabgpu_ctx* ctx = flat_ctx();
-    std::vector<uint32_t> ids;
-    // (a key retired between the lookup and the launch would answer 4 - "internal inconsistency" below; nothing retires a P-384 key here)
-    int rc = all_registered384(ctx, n, submitted, qx.data(), qy.data(), ids)
-                 ? fabgpu_p384_verify_batch_keyed(ctx, n, ids.data(), e.data(), r.data(), s.data(), bits.data(), st.data())
-                 : fabgpu_p384_verify_batch(ctx, n, qx.data(), qy.data(), e.data(), r.data(), s.data(), bits.data(), st.data());
-    if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
-    for (size_t i = 0; i < n; i++) {
-        if (!submitted[i]) continue;
-        if (st[i] == FABGPU_ST_HIGH_S || st[i] == FABGPU_ST_OFF_CURVE) return Error("internal inconsistency between host gate and device status");
-        bool valid = ((bits[i >> 6] >> (i & 63)) & 1) && st[i] == FABGPU_ST_VALID;
-        if (!valid && st[i] == FABGPU_ST_BAD_MATH) {                       // (test hook: a corrupted verdict)
-            uint32_t f = test_p384_flip_.load(std::memory_order_relaxed);
-            while (f && !test_p384_flip_.compare_exchange_weak(f, f - 1)) {}
-            if (f) valid = true;
-        }
-        results[i].valid = valid;
-        results[i].err = Error();
-        if (valid && !AuditDirectP384(*items[i].key, items[i].sig, items[i].siglen, items[i].digest, items[i].dlen, "bccsp.Verify")) {
-            results[i] = VerifyResult();
-            results[i].err = Error(PoisonedText());
-            results[i].poisoned = true;
-        }
-    }
-    return Error();
+    return VerifyBatchT<Curve384>(items, results);
 }
-
-// identity.Verify for P-384 identities: digest = Hash(msg) in the MSP's family (a launch of its own), then the P-384 kernel
 Error GPUCSP::IdentityVerifyBatchP384(const std::vector<IdentityItem384>& items, std::vector<std::string>& out, bool sha3) const {
-    const size_t n = items.size();
-    out.assign(n, std::string());
     if (!P384Enabled()) {
-        out.assign(n, std::string("could not determine the validity of the signature: ") + P384RefusalText());
+        out.assign(items.size(), std::string("could not determine the validity of the signature: ") + P384RefusalText());
         return Error();
     }
-    if (sha3 && !Sha3Enabled()) return Error("SHA3 is served by bccsp/sw, not by the GPU provider");
-    if (n == 0) return Error();
-    std::vector<uint8_t> qx(n * 48), qy(n * 48), r(n * 48), s(n * 48), st(n), submitted(n, 0), arena;
-    std::vector<uint32_t> off(n + 1);
-    std::vector<uint64_t> bits((n + 63) / 64);
-    static const uint8_t one_digest[1] = {1};
-    for (size_t i = 0; i < n; i++) {
-        const IdentityItem384& it = items[i];
-        Gate384 g = gate_item384(it.key, it.sig, it.siglen, one_digest, 1);
-        submitted[i] = g.submit;
-        if (!g.submit) out[i] = g.res.err.ok() ? "The signature is invalid" : "could not determine the validity of the signature: " + g.res.err.msg;
-        if (g.submit) { memcpy(&qx[48 * i], it.key->x, 48); memcpy(&qy[48 * i], it.key->y, 48); }
-        else put_generator384(&qx[48 * i], &qy[48 * i]);
-        memcpy(&r[48 * i], g.r, 48);
-        memcpy(&s[48 * i], g.s, 48);
-        off[i] = (uint32_t)arena.size();
-        if (g.submit && it.msglen) arena.insert(arena.end(), it.msg, it.msg + it.msglen);
-    }
-    off[n] = (uint32_t)arena.size();
-    arena.resize(arena.size() + 8);
-    fabgpu_ctx* ctx = flat_ctx();
-    std::vector<uint32_t> ids;
-    int rc;
-    if (all_registered384(ctx, n, submitted, qx.data(), qy.data(), ids))
-        rc = sha3 ? fabgpu_sha3_256_p384_verify_batch_keyed(ctx, n, arena.data(), off.data(), ids.data(), r.data(), s.data(), bits.data(), st.data())
-                  : fabgpu_sha256_p384_verify_batch_keyed(ctx, n, arena.data(), off.data(), ids.data(), r.data(), s.data(), bits.data(), st.data());
-    else
-        rc = sha3 ? fabgpu_sha3_256_p384_verify_batch(ctx, n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data())
-                  : fabgpu_sha256_p384_verify_batch(ctx, n, arena.data(), off.data(), qx.data(), qy.data(), r.data(), s.data(), bits.data(), st.data());
-    if (rc != FABGPU_OK) return Error(std::string("GPU verify failed: ") + fabgpu_strerror(rc));
-    for (size_t i = 0; i < n; i++) {
-        if (!submitted[i]) continue;
-        const bool ok = ((bits[i >> 6] >> (i & 63)) & 1) && st[i] == FABGPU_ST_VALID;
-        out[i] = ok ? "" : "The signature is invalid";
-        if (ok && !AuditDirectP384(*items[i].key, items[i].sig, items[i].siglen, nullptr, 0, "identity.Verify", items[i].msg, items[i].msglen, sha3)) out[i] = PoisonedText();
-    }
-    return Error();
+    out.assign(items.size(), std::string());
+    if (sha3 && !Sha3Enabled()) return Error(kSha3RefusalText);   // (ahead of the empty batch, as this verb always had it)
+    return IdentityVerifyBatchT<Curve384>(items, out, sha3);
 }
-
 VerifyResult GPUCSP::VerifyCoalescedP384(const ECDSAPublicKey384* k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen) const {
     if (!P384Enabled()) {
         VerifyResult r;
@@ -1474,53 +1390,7 @@ VerifyResult GPUCSP::VerifyCoalescedP384(const ECDSAPublicKey384* k, const uint8
         r.needs_sw = true;
         return r;
     }
-    Gate384 g = gate_item384(k, sig, siglen, digest, dlen);
-    if (!g.submit) return g.res;
-    CoReqV384 req;
-    req.item = {k, sig, siglen, digest, dlen};
-    co_verify_p384_.submit(&req, [this](std::vector<CoReqV384*>& batch) {
-        std::vector<VerifyResult> res;
-        Error e;
-        try {
-            std::vector<VerifyItem384> items(batch.size());
-            for (size_t i = 0; i < batch.size(); i++) items[i] = batch[i]->item;
-            e = VerifyBatchP384(items, res);
-        } catch (const std::exception& x) {
-            e = Error(std::string("GPU verify failed: ") + x.what());
-        }
-        for (size_t i = 0; i < batch.size(); i++) {
-            if (e.ok()) {
-                batch[i]->res = res[i];
-            } else {
-                batch[i]->res = VerifyResult();
-                batch[i]->res.err = e;
-                batch[i]->res.infrastructure = true;
-            }
-        }
-    });
-    return req.res;
-}
-
-bool GPUCSP::AuditDirectP384(const ECDSAPublicKey384& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
-                             const uint8_t* msg, size_t msglen, bool sha3) const {
-    if (!audit_sample_[AUDIT_DIRECT].hit(AuditPermille())) return true;
-    bool accept;
-    {
-        AuditClock clk{audit_count_[AUDIT_NS]};
-        uint8_t dg[32];
-        if (msg || msglen) {
-            if (sha3) audit_sha3_256(msg, msglen, dg);
-            else audit_sha256(msg, msglen, dg);
-            digest = dg;
-            dlen = 32;
-        }
-        accept = audit_p384_verify(k.x, k.y, sig, siglen, digest, dlen);
-    }
-    audit_count_[AUDIT_DIRECT].fetch_add(1, std::memory_order_relaxed);
-    if (accept) return true;
-    audit_count_[AUDIT_MISMATCHES].fetch_add(1, std::memory_order_relaxed);
-    Poison(std::string("direct call: the device accepted a P-384 signature in ") + what + " that the CPU audit rejects (key X " + hex8(k.x) + "..)");
-    return false;
+    return VerifyCoalescedT<Curve384>(co_verify_p384_, &GPUCSP::VerifyBatchP384, k, sig, siglen, digest, dlen);
 }
 
 int GPUCSP::MemoLookup(const uint8_t* qx32, const uint8_t* qy32, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, uint8_t* status,
@@ -2818,14 +2688,12 @@ void GPUCSP::GateRange(HostPass& hp, const std::map<std::string, int64_t>& idemi
         memcpy(k.x, ci.qx, 32);
         memcpy(k.y, ci.qy, 32);
         k.on_curve = true;
-        Gate g = gate_item(&k, block + tp.sig.off, tp.sig.len, one_digest, 1);
+        const GateT<Curve256> g = gate_item<Curve256>(&k, block + tp.sig.off, tp.sig.len, one_digest, 1);
         if (!g.submit) {
-            if (g.res.err.ok()) out.tuple_status[i] = FABGPU_ST_RANGE;                                   // r >= n: (false, nil)
-            else if (g.res.err.msg.find("Invalid S") != std::string::npos) out.tuple_status[i] = FABGPU_ST_HIGH_S;
-            else out.tuple_status[i] = TUPLE_ST_BAD_DER;
+            out.tuple_status[i] = gate_tuple_status(g.res);
             continue;
         }
-        memcpy(g0.qx, ci.qx, 32); memcpy(g0.qy, ci.qy, 32); memcpy(g0.r, g.r32, 32); memcpy(g0.s, g.s32, 32);
+        memcpy(g0.qx, ci.qx, 32); memcpy(g0.qy, ci.qy, 32); memcpy(g0.r, g.r, 32); memcpy(g0.s, g.s, 32);
         g0.key_id = ci.key_id;
         g0.submit = true;
     }
@@ -3302,11 +3170,9 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
         memcpy(row.key.x, ci->qx384, 48);
         memcpy(row.key.y, ci->qy384, 48);
         row.key.on_curve = true;
-        const Gate384 g = gate_item384(&row.key, block + tp.sig.off, tp.sig.len, one_digest, 1);
-        if (!g.submit) {                                                 // the outcomes as GateRange maps them for P-256
-            if (g.res.err.ok()) out.tuple_status[i] = FABGPU_ST_RANGE;   // r does not fit the field: (false, nil)
-            else if (g.res.err.msg.find("Invalid S") != std::string::npos) out.tuple_status[i] = FABGPU_ST_HIGH_S;
-            else out.tuple_status[i] = TUPLE_ST_BAD_DER;
+        const GateT<Curve384> g = gate_item<Curve384>(&row.key, block + tp.sig.off, tp.sig.len, one_digest, 1);
+        if (!g.submit) {
+            out.tuple_status[i] = gate_tuple_status(g.res);
             continue;
         }
         Family& f = fam[row.sha3 ? 1 : 0];
@@ -3359,7 +3225,7 @@ Error GPUCSP::P384PassStage(const uint8_t* block, size_t len, const ParsedBlock&
         d.pre_idx = pre_idx.data();
         std::vector<uint32_t> ids;
         const std::vector<uint8_t> submitted(fn, 1);
-        const bool keyed = all_registered384(dv.ctx, fn, submitted, f.qx.data(), f.qy.data(), ids);
+        const bool keyed = all_registered<Curve384>(dv.ctx, fn, submitted, f.qx.data(), f.qy.data(), ids);
         if (keyed) {
             d.key_id = ids.data();
         } else {

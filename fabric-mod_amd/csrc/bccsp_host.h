@@ -60,20 +60,37 @@ bool PublicKeyOnCurve(const uint8_t* qx32, const uint8_t* qy32);
 void HashToInt(const uint8_t* digest, size_t len, uint8_t* e32);
 extern const char* HALF_ORDER_DECIMAL;
 
-struct ECDSAPublicKey {  // bccsp/sw/ecdsakey.go:72-117 (X, Y only)
-    uint8_t x[32], y[32];
+// A public key and the items of the direct-call verbs, by coordinate width: 32 bytes for P-256, 48 for P-384
+template <size_t W>
+struct PublicKeyT {  // bccsp/sw/ecdsakey.go:72-117 (X, Y only)
+    uint8_t x[W], y[W];
     bool on_curve = false;
 };
+typedef PublicKeyT<32> ECDSAPublicKey;
+typedef PublicKeyT<48> ECDSAPublicKey384;
 struct HashOpts {  // bccsp/hashopts.go:20-70
     std::string algorithm;  // "SHA256" is the only family on this path (msp/identities.go:216-224)
 };
-struct VerifyItem {
-    const ECDSAPublicKey* key;
+template <class Key>
+struct VerifyItemT {
+    const Key* key;
     const uint8_t* sig;
     size_t siglen;
     const uint8_t* digest;
     size_t dlen;
 };
+template <class Key>
+struct IdentityItemT {
+    const Key* key;
+    const uint8_t* msg;
+    size_t msglen;
+    const uint8_t* sig;
+    size_t siglen;
+};
+typedef VerifyItemT<ECDSAPublicKey> VerifyItem;
+typedef VerifyItemT<ECDSAPublicKey384> VerifyItem384;
+typedef IdentityItemT<ECDSAPublicKey> IdentityItem;
+typedef IdentityItemT<ECDSAPublicKey384> IdentityItem384;
 struct VerifyResult {  // (valid bool, err error)
     bool valid = false;
     Error err;
@@ -81,31 +98,49 @@ struct VerifyResult {  // (valid bool, err error)
     bool infrastructure = false;  // device failure: caller falls back to bccsp/sw
     bool poisoned = false;        // the CPU audit of this "valid" disagreed (or the provider was poisoned before the call): no verdict
 };
-// ... and their P-384 namesakes (48-byte coordinates)
-struct ECDSAPublicKey384 {
-    uint8_t x[48], y[48];
-    bool on_curve = false;
+
+// What the direct-call verbs need to know about a curve.  Each verb - the gate, the registered-key scan, VerifyBatch,
+// IdentityVerifyBatch, VerifyCoalesced, AuditDirect - has ONE body over such a description (bccsp_host.cpp); the public P-256 and
+// P-384 methods of GPUCSP forward to it.
+struct Curve256 {
+    static constexpr size_t W = 32;                       // bytes of a coordinate and of a scalar
+    typedef ECDSAPublicKey Key;
+    static constexpr bool kDerFastPath = true;            // gate_item tries the minimal-DER shape before the general parser
+    static constexpr bool kTestFlip = false;
+    static constexpr const char* kName = "P-256";
+    static constexpr const char* kAuditNoun = "a signature";
+    static const char* half_order_decimal() { return HALF_ORDER_DECIMAL; }
+    static bool low_s(const uint8_t* s32);                // s <= n >> 1
+    static void hash_to_int(const uint8_t* digest, size_t len, uint8_t* e32) { HashToInt(digest, len, e32); }
+    static void generator(uint8_t* qx32, uint8_t* qy32);  // G's affine coordinates: the key of a row the gate did not submit
+    static constexpr auto lookup = fabgpu_p256_key_lookup;
+    static constexpr auto verify = fabgpu_p256_verify_batch;
+    static constexpr auto verify_keyed = fabgpu_p256_verify_batch_keyed;
+    static constexpr auto sha256_verify = fabgpu_sha256_p256_verify_batch;
+    static constexpr auto sha256_verify_keyed = fabgpu_sha256_p256_verify_batch_keyed;
+    static constexpr auto sha3_verify = fabgpu_sha3_256_p256_verify_batch;
+    static constexpr auto sha3_verify_keyed = fabgpu_sha3_256_p256_verify_batch_keyed;
+    static constexpr auto audit = audit_p256_verify;
 };
-struct VerifyItem384 {
-    const ECDSAPublicKey384* key;
-    const uint8_t* sig;
-    size_t siglen;
-    const uint8_t* digest;
-    size_t dlen;
-};
-struct IdentityItem384 {
-    const ECDSAPublicKey384* key;
-    const uint8_t* msg;
-    size_t msglen;
-    const uint8_t* sig;
-    size_t siglen;
-};
-struct IdentityItem {
-    const ECDSAPublicKey* key;
-    const uint8_t* msg;
-    size_t msglen;
-    const uint8_t* sig;
-    size_t siglen;
+struct Curve384 {
+    static constexpr size_t W = 48;
+    typedef ECDSAPublicKey384 Key;
+    static constexpr bool kDerFastPath = false;           // every signature takes the general parser
+    static constexpr bool kTestFlip = true;               // VerifyBatch honours GPUCSP::test_p384_flip_
+    static constexpr const char* kName = "P-384";
+    static constexpr const char* kAuditNoun = "a P-384 signature";
+    static const char* half_order_decimal();
+    static bool low_s(const uint8_t* s48);                // (bccsp/utils/ecdsa.go:84-92 takes the key's own curve)
+    static void hash_to_int(const uint8_t* digest, size_t len, uint8_t* e48);
+    static void generator(uint8_t* qx48, uint8_t* qy48);
+    static constexpr auto lookup = fabgpu_p384_key_lookup;
+    static constexpr auto verify = fabgpu_p384_verify_batch;
+    static constexpr auto verify_keyed = fabgpu_p384_verify_batch_keyed;
+    static constexpr auto sha256_verify = fabgpu_sha256_p384_verify_batch;
+    static constexpr auto sha256_verify_keyed = fabgpu_sha256_p384_verify_batch_keyed;
+    static constexpr auto sha3_verify = fabgpu_sha3_256_p384_verify_batch;
+    static constexpr auto sha3_verify_keyed = fabgpu_sha3_256_p384_verify_batch_keyed;
+    static constexpr auto audit = audit_p384_verify;
 };
 
 struct BlockVerdicts {
@@ -229,7 +264,7 @@ class GPUCSP {
     // Answers and error texts are those of the P-256 namesakes.  With the option off every item answers P384RefusalText().
     // KeyImportP384: bccsp.KeyImport for a P-384 key - KeyImport's texts; an on-curve key gets its comb table on every device of the pool
     // (fabgpu_p384_key_register_many; best effort), and batches whose submitted items all name registered keys then take the keyed
-    // entries (all_registered384, per batch and per device, as all_registered does for P-256).  Option off: nothing is registered and
+    // entries (all_registered, per batch and per device, as for P-256).  Option off: nothing is registered and
     // the refusal text comes back.  The audit recomputes from the key's coordinates and never reads a table.
     bool P384Enabled() const { return p384_.load(std::memory_order_relaxed); }
     static const char* P384RefusalText();
@@ -301,7 +336,7 @@ class GPUCSP {
     void PassStats(uint64_t out[4]) const;
     // ---- the P-384 stage of the block pass (option p384) ----
     // One step both routes run once the route has written the tuples' statuses: the tuples it left TUPLE_ST_NEEDS_SW whose identity is a
-    // certificate with an on-curve P-384 key go through gate_item384 and then, in ONE described batch over the block the pass staged
+    // certificate with an on-curve P-384 key go through gate_item and then, in ONE described batch over the block the pass staged
     // (fabgpu_identity_verify_batch_p384: keyed when every submitted key is registered on the pass's device, fresh otherwise), get their
     // statuses; the flags of their transactions are folded again (SummarizeTransactions); a sample of the "valid" answers is audited on
     // the CPU (audit_permille; a disagreement poisons the provider).  Option off, provider poisoned, or no such tuple: nothing is
@@ -396,9 +431,19 @@ class GPUCSP {
     int HashFind(const uint8_t* msg, size_t len, uint8_t* digest32, uint64_t* seq, uint32_t* entry) const;
     uint32_t AuditPermille() const { return audit_permille_.load(std::memory_order_relaxed); }
     // true: the device's "valid" for this signature stands (not sampled, or the CPU agrees); false: the provider is now poisoned.
-    // msg != nullptr: the digest is SHA-256(msg), computed here (identity.Verify)
-    bool AuditDirect(const ECDSAPublicKey& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
+    // msg != nullptr: the digest is the hash of msg in the call's family, computed here (identity.Verify).  Re-computed by C::audit
+    // from the key's coordinates: no table is read.
+    template <class C>
+    bool AuditDirect(const typename C::Key& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
                      const uint8_t* msg = nullptr, size_t msglen = 0, bool sha3 = false) const;
+    // the bodies of the direct-call verbs (C: Curve256 / Curve384); the option refusal of the P-384 verbs is in their forwards
+    template <class C>
+    Error VerifyBatchT(const std::vector<VerifyItemT<typename C::Key>>& items, std::vector<VerifyResult>& results) const;
+    template <class C>
+    Error IdentityVerifyBatchT(const std::vector<IdentityItemT<typename C::Key>>& items, std::vector<std::string>& out, bool sha3) const;
+    template <class C, class Queue, class BatchVerb>
+    VerifyResult VerifyCoalescedT(Queue& queue, BatchVerb verb, const typename C::Key* k, const uint8_t* sig, size_t siglen, const uint8_t* digest,
+                                  size_t dlen) const;
     // Every lookup of every validator thread READS the two switches and, while auditing is on, BUMPS its kind's hit counter: the
     // switches share a cache line nobody writes, each counter has a line of its own (the memo's counters are sharded for the same
     // reason - reader_lock.h - but a sampling rule that is exact over all threads needs ONE counter per kind).
@@ -507,9 +552,6 @@ class GPUCSP {
     mutable std::atomic<uint64_t> p384_pass_wide_rows_{0};           // P384PassWideRows
     mutable MspFamilyTable msp_family_;                      // mspid -> hash family, for P384PassStage (its own lock inside)
     mutable P384Memo p384_memo_;                             // the verdict memo of the pass's P-384 tuples (its own lock and capacity inside)
-    // as AuditDirect, for a P-384 "valid": re-computed with the host compilation of p384.h (audit_p384_verify)
-    bool AuditDirectP384(const ECDSAPublicKey384& k, const uint8_t* sig, size_t siglen, const uint8_t* digest, size_t dlen, const char* what,
-                         const uint8_t* msg = nullptr, size_t msglen = 0, bool sha3 = false) const;
     mutable std::mutex retire_mu_;                           // retire_queue_, imported_keys_ (a leaf: nothing is taken under it)
     mutable std::vector<std::string> retire_queue_;          // qx || qy
     mutable std::set<std::string> imported_keys_;
@@ -635,18 +677,17 @@ class GPUCSP {
         std::vector<WalkLearn> learn;              // identities the device decoded and offers to the cache
         std::vector<int32_t> nym_issuer_rank;      // device route: issuer id of an idemix creator's row, by creator rank (-1: not one)
     };
-    struct CoReqV : CoalescedBase {
-        VerifyItem item;
+    template <class Key>
+    struct CoReqVT : CoalescedBase {
+        VerifyItemT<Key> item;
         VerifyResult res;
     };
+    typedef CoReqVT<ECDSAPublicKey> CoReqV;
+    typedef CoReqVT<ECDSAPublicKey384> CoReqV384;
     struct CoReqI : CoalescedBase {
         IdentityItem item;
         std::string out;
         bool infra = false;
-    };
-    struct CoReqV384 : CoalescedBase {
-        VerifyItem384 item;
-        VerifyResult res;
     };
     mutable Coalescer<CoReqV> co_verify_;
     mutable Coalescer<CoReqV384> co_verify_p384_;                     // P-384 callers queue apart: another kernel
