@@ -697,6 +697,11 @@ int fabgpu_csp_p384_pass_wide_rows(fabgpu_csp* csp, uint64_t* rows) {
     *rows = csp->csp->P384PassWideRows();
     return FABGPU_OK;
 }
+// the rows the pool's contexts hashed on 32 lanes (GPUCSP::Sha3CoopRows)
+int fabgpu_csp_sha3_coop_rows(fabgpu_csp* csp, uint64_t* rows) {
+    if (!csp || !rows) return FABGPU_EINVAL;
+    return csp->csp->Sha3CoopRows(rows);
+}
 // an MSP's hash family, for the P-384 stage (GPUCSP::SetMspHashFamily)
 int fabgpu_csp_msp_hash_family(fabgpu_csp* csp, const char* mspid, const char* family, char* err, size_t errcap) {
     if (!csp || !mspid) return FABGPU_EINVAL;

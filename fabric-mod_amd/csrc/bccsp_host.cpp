@@ -214,6 +214,7 @@ Error GPUCSP::New(const fabgpu_cfg* cfg, std::unique_ptr<GPUCSP>& out) {
     p->opts_.ctx_flags = cfg ? cfg->flags : 0;
     p->opts_.p384_wide = (p->opts_.ctx_flags & FABGPU_FLAG_P384_WIDE) ? 1 : 0;
     p->opts_.p384_key_tables16 = (p->opts_.ctx_flags & FABGPU_FLAG_P384_KEY_TABLES_16BIT) ? 1 : 0;
+    p->opts_.sha3_coop = (p->opts_.ctx_flags & FABGPU_FLAG_SHA3_COOP) ? 1 : 0;
     out = std::move(p);
     return Error();
 }
@@ -236,6 +237,8 @@ Error GPUCSP::New(const ProviderOptions& opts, std::unique_ptr<GPUCSP>& out) {
     p->opts_.p384_wide = (p->opts_.ctx_flags & FABGPU_FLAG_P384_WIDE) ? 1 : 0;
     if (opts.p384_key_tables16 > 0) p->opts_.ctx_flags |= FABGPU_FLAG_P384_KEY_TABLES_16BIT;
     p->opts_.p384_key_tables16 = (p->opts_.ctx_flags & FABGPU_FLAG_P384_KEY_TABLES_16BIT) ? 1 : 0;
+    if (opts.sha3_coop > 0) p->opts_.ctx_flags |= FABGPU_FLAG_SHA3_COOP;
+    p->opts_.sha3_coop = (p->opts_.ctx_flags & FABGPU_FLAG_SHA3_COOP) ? 1 : 0;
     p->audit_permille_.store(opts.audit_permille > 1000 ? 1000 : opts.audit_permille, std::memory_order_relaxed);
     for (int32_t ord : devices) {
         fabgpu_cfg cfg;
@@ -264,6 +267,15 @@ GPUCSP::BlockUpload::~BlockUpload() {
     if (th.joinable()) th.join();
     host_copy_release(&copy);                               // (a pass that published a memo table took it along: nothing left to release)
     if (routed && owner) owner->devs_[(size_t)dev]->in_flight.fetch_sub(1, std::memory_order_acq_rel);
+}
+int GPUCSP::Sha3CoopRows(uint64_t* rows) const {
+    *rows = 0;
+    for (auto& d : devs_) {
+        uint64_t v = 0;
+        if (int rc = fabgpu_sha3_coop_rows(d->ctx, &v)) return rc;
+        *rows += v;
+    }
+    return FABGPU_OK;
 }
 int GPUCSP::RouteBlock(uint64_t block_seq) const {
     const int G = (int)devs_.size();
@@ -313,6 +325,16 @@ int64_t GPUCSP::SetOption(const std::string& name, int64_t value) const {
         opts_.p384_wide = value > 0 ? 1 : 0;
         return prev;
     }
+    if (name == "sha3_coop") {                                   // (a context flag, as above)
+        const int64_t prev = opts_.sha3_coop;
+        for (auto& d : devs_)
+            if (ctx_set_sha3_coop(d->ctx, value > 0) != FABGPU_OK) {
+                for (auto& u : devs_) (void)ctx_set_sha3_coop(u->ctx, prev > 0);
+                return INT64_MIN;
+            }
+        opts_.sha3_coop = value > 0 ? 1 : 0;
+        return prev;
+    }
     for (const OptField& o : kIntOpts)
         if (name == o.name) {
             const int64_t prev = opts_.*(o.f);
@@ -330,6 +352,7 @@ int64_t GPUCSP::GetOption(const std::string& name) const {
     if (name == "n_devices") return (int64_t)devs_.size();
     if (name == "audit_permille") return (int64_t)AuditPermille();
     if (name == "p384_wide") return opts_.p384_wide;
+    if (name == "sha3_coop") return opts_.sha3_coop;
     if (name == "p384_key_tables16") return opts_.p384_key_tables16;       // (read at construction: SetOption does not know the name)
     if (name == "registrations_dropped") return (int64_t)reg_dropped_.load(std::memory_order_relaxed);        // (read-only counters)
     if (name == "registration_id_mismatches") return (int64_t)reg_id_mismatches_.load(std::memory_order_relaxed);

@@ -206,6 +206,9 @@ struct ProviderOptions {
                                        // signature.  Read at construction like ctx_flags (which may carry the bit itself); SetOption of the same
                                        // name switches the living contexts.  Default off
     int p384_key_tables16 = 0;         // > 0: FABGPU_FLAG_P384_KEY_TABLES_16BIT on every context - registered P-384 keys also get 16-bit comb tables
+    int sha3_coop = 0;                 // > 0: FABGPU_FLAG_SHA3_COOP on every context - SHA3-256 launches of at most 4 096 messages on 32 lanes per message,
+                                       // the long messages of larger plain launches likewise.  Read at construction like ctx_flags (which may carry the
+                                       // bit itself); SetOption of the same name switches the living contexts.  Default off
     uint32_t audit_permille = 0;       // share of the digests / verdicts handed out that is re-computed on the CPU first (0 .. 1000; 0: none)
 };
 constexpr int kMaxProviderDevices = 64;   // contexts per provider (8 GPUs x up to 8 contexts each)
@@ -355,6 +358,8 @@ class GPUCSP {
     enum : int { P384_PASS_STAGES = 0, P384_PASS_SEEN = 1, P384_PASS_SUBMITTED = 2, P384_PASS_KEYED = 3, P384_PASS_FRESH = 4, P384_PASS_AUDITED = 5, P384_PASS_MEMO_SEEDED = 6, P384_PASS_SHA3_ROWS = 7, P384_PASS_STATS = 8 };
     void P384PassStats(uint64_t out[P384_PASS_STATS]) const;
     // ... and the rows of its keyed batches that the eight-lanes-per-signature form verified (the "p384_wide" option; 0 without it)
+    // fabgpu_sha3_coop_rows summed over the pool's contexts (the "sha3_coop" option; 0 without it) -> FABGPU_OK or the first context's error
+    int Sha3CoopRows(uint64_t* rows) const;
     uint64_t P384PassWideRows() const { return p384_pass_wide_rows_.load(std::memory_order_relaxed); }
     // Starts the upload of a block on a helper thread (blocks of 4 MiB and more) so that it travels while the caller parses
     // and gates; join() returns the token for PreVerifyParsed (0 if nothing was staged).

@@ -344,6 +344,12 @@ int key_register_many_prebuilt(fabgpu_ctx* const* ctxs, int n, const uint8_t* qx
 // a keyed launch of n rows queued now would take that form - the question the launch site itself asks.
 int ctx_set_p384_wide(fabgpu_ctx* ctx, bool on);
 bool ctx_p384_wide_serves(fabgpu_ctx* ctx, size_t n);
+// FABGPU_FLAG_SHA3_COOP on a living context (the provider's "sha3_coop" option): the 32-lanes-per-message SHA3-256 roads, for the launches
+// queued after the call; turning it on for the first time makes the mixed kernel's row counter (a FABGPU_* code when that fails).
+int ctx_set_sha3_coop(fabgpu_ctx* ctx, bool on);
+// TEST HOOK support: the 32-lane kernel over a plain batch of ANY size, whatever the context's switch and SHA3_COOP_MAX say - what
+// tools/bench_sha3_coop.py times beyond the cap to place it.  The contract of fabgpu_sha3_256_batch_dev; counts no row.
+int sha3_coop_batch_uncapped(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, void* stream);
 // the duration of the last timed launch of a FABGPU_FLAG_TIME_KERNELS context (ms; < 0: none) - read by the test-hook library
 float ctx_last_kernel_ms(fabgpu_ctx* ctx);
 // TEST HOOK support: the capacities of the block pass's per-envelope, per-tuple, pinned, mapped and gather-scratch buffers (bytes)

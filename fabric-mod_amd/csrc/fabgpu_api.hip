@@ -302,6 +302,12 @@ struct fabgpu_ctx {
     // finds it there (a second one is made only when keyed launches of several streams overlap).
     std::atomic<bool> p384_wide{false};
     std::atomic<uint64_t> k384_wide_rows{0}; // rows handed to the eight-lane form so far (fabgpu_p384_wide_rows)
+    // FABGPU_FLAG_SHA3_COOP (or fab::ctx_set_sha3_coop): SHA3-256 launches of at most SHA3_COOP_MAX messages on 32 lanes per message, larger
+    // plain ones through the mixed kernel (sha3_coop_kernels.hip).  sha3_coop_rows: the rows of the small launches, counted when they are
+    // queued; d_sha3_coop_rows: the long rows the mixed kernel picked out, counted on the device (made when the switch is first turned on).
+    std::atomic<bool> sha3_coop{false};
+    std::atomic<uint64_t> sha3_coop_rows{0};
+    unsigned long long* d_sha3_coop_rows = nullptr;
     // FABGPU_FLAG_P384_KEY_TABLES_16BIT (DESIGN 4.2d "16-bit tables").  The generator's 16-bit table is built once, beside its 8-bit one.
     // A registration queues its key's 16-bit build on stream_k384x16 behind the finished 8-bit table and does NOT wait for it: the
     // build waits in k384_pending16 with its event.  The launch path (and the stats path) asks hipEventQuery, never a blocking wait for
@@ -535,7 +541,7 @@ int fabgpu_init(const fabgpu_cfg* cfg, fabgpu_ctx** out) {
     if (cfg && (cfg->flags & ~(uint32_t)(FABGPU_FLAG_ONE_LANE_ONLY | FABGPU_FLAG_TIME_KERNELS | FABGPU_FLAG_NO_QUAD | FABGPU_FLAG_PAIR_TABLE_LDS |
                                           FABGPU_FLAG_PAIR_TABLE_GLOBAL | FABGPU_FLAG_NO_WIDE | FABGPU_FLAG_NYM_FUSED_HASH | FABGPU_FLAG_NYM_NO_SIDE_STREAM |
                                           FABGPU_FLAG_KEY_TABLES_16BIT | FABGPU_FLAG_PAIR_SOLO | FABGPU_FLAG_PAIR_DBL1 | FABGPU_FLAG_PAIR_BOOTH4 | FABGPU_FLAG_P384_WIDE |
-                                          FABGPU_FLAG_P384_KEY_TABLES_16BIT)) != 0) return FABGPU_EINVAL;
+                                          FABGPU_FLAG_P384_KEY_TABLES_16BIT | FABGPU_FLAG_SHA3_COOP)) != 0) return FABGPU_EINVAL;
     if (cfg && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_LDS) && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_GLOBAL)) return FABGPU_EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return FABGPU_ENODEV;
@@ -625,6 +631,7 @@ int fabgpu_init(const fabgpu_cfg* cfg, fabgpu_ctx** out) {
             }
         }
         if (cfg && (cfg->flags & FABGPU_FLAG_P384_WIDE) && (rc = fab::ctx_set_p384_wide(ctx, true))) break;
+        if (cfg && (cfg->flags & FABGPU_FLAG_SHA3_COOP) && (rc = fab::ctx_set_sha3_coop(ctx, true))) break;
         ctx->p384_tab16 = cfg && (cfg->flags & FABGPU_FLAG_P384_KEY_TABLES_16BIT);      // (nothing is allocated before the first registered P-384 key)
         if (cfg && cfg->max_batch) {
             size_t n = cfg->max_batch;
@@ -663,6 +670,7 @@ void fabgpu_shutdown(fabgpu_ctx* ctx) {
         if (ctx->stream_k384) { hipStreamSynchronize(ctx->stream_k384); hipStreamDestroy(ctx->stream_k384); }
         if (ctx->stream_k384x16) { hipStreamSynchronize(ctx->stream_k384x16); hipStreamDestroy(ctx->stream_k384x16); }
         for (auto& q : ctx->k384_pending16) hipEventDestroy(q.ev);
+        if (ctx->d_sha3_coop_rows) hipFree(ctx->d_sha3_coop_rows);
         for (void* t : ctx->k384_allocs) hipFree(t);                 // (P-384 key tables, the generator's comb, snapshot arrays)
         if (ctx->d_k384_in) hipFree(ctx->d_k384_in);
         if (ctx->d_k384_scr) hipFree(ctx->d_k384_scr);
@@ -738,6 +746,37 @@ int fab::ctx_set_p384_wide(fabgpu_ctx* ctx, bool on) {
 }
 bool fab::ctx_p384_wide_serves(fabgpu_ctx* ctx, size_t n) {
     return ctx && n != 0 && n <= (size_t)P384_WIDE_LAUNCH_MAX && ctx->p384_wide.load(std::memory_order_relaxed);
+}
+// The 32-lanes-per-message SHA3-256 roads, on or off, for the launches queued after the call (block_walk_dev.h).  On for the first
+// time: the device-side row counter of the mixed kernel is made and zeroed.
+int fab::ctx_set_sha3_coop(fabgpu_ctx* ctx, bool on) {
+    if (!ctx) return FABGPU_EINVAL;
+    if (on && !ctx->d_sha3_coop_rows) {
+        if (ctx->fault == 2) return FABGPU_ENOMEM;
+        DeviceGuard g(ctx->device);
+        void* ctr = nullptr;
+        if (hipMalloc(&ctr, 16) != hipSuccess) {
+            (void)hipGetLastError();
+            return FABGPU_ENOMEM;
+        }
+        if (hipMemset(ctr, 0, 16) != hipSuccess) {
+            (void)hipGetLastError();
+            hipFree(ctr);
+            return FABGPU_ELAUNCH;
+        }
+        ctx->d_sha3_coop_rows = (unsigned long long*)ctr;
+    }
+    ctx->sha3_coop.store(on, std::memory_order_relaxed);
+    return FABGPU_OK;
+}
+int fab::sha3_coop_batch_uncapped(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, void* stream) {
+    if (!ctx || (n && (!arena || !off || !digests))) return FABGPU_EINVAL;
+    if (n > 0xFFFFFFF0ull || arena_bytes > 0xFFFFFFFFull) return FABGPU_ETOOBIG;
+    if (n == 0) return FABGPU_OK;
+    DeviceGuard g(ctx->device);
+    ShaPrefixArgs pa;
+    pa.digests = digests;
+    return hip_to_rc(launch_sha3_256_messages_coop((uint32_t)n, arena, arena_bytes, off, pa, (hipStream_t)stream));
 }
 void fab::ctx_test_nym_side_after(fabgpu_ctx* ctx, bool on) {
     if (ctx) ctx->test_nym_side_after.store(on);
@@ -1699,13 +1738,38 @@ int fabgpu_idemix_nym_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* are
 // one of the pooled workspaces, under their rule (acquire_qws: reserved until an event is recorded behind the launch that read it) -
 // and the unchanged verify-only entry point consumes that buffer as `e`: the digest never leaves the chip, and the verify kernel is
 // chosen by n and the context's flags exactly as for a caller who brings digests.
+// The SHA3-256 launches of a (possibly prefixed) batch, chosen by the context's switch.  Without FABGPU_FLAG_SHA3_COOP: the mid-state
+// launch (unless pa.mid_ready) and the one-lane kernel, as ever.  With it: up to SHA3_COOP_MAX messages on 32 lanes each, prefixed ones
+// hashed whole - no mid-state launch, pa.mid_scratch is not touched -; larger plain launches through the mixed kernel; larger prefixed
+// ones on the one-lane road with its mid-states.
+static hipError_t sha3_launch_messages(fabgpu_ctx* ctx, uint32_t n, const void* arena, size_t arena_bytes, const void* off, const ShaPrefixArgs& pa,
+                                       hipStream_t st) {
+    const bool prefixed = pa.m != 0 && pa.pre_idx != nullptr;
+    if (ctx->sha3_coop.load(std::memory_order_relaxed)) {
+        if (n <= SHA3_COOP_MAX) {
+            const hipError_t err = launch_sha3_256_messages_coop(n, arena, arena_bytes, off, pa, st);
+            if (err == hipSuccess) ctx->sha3_coop_rows.fetch_add(n, std::memory_order_relaxed);
+            return err;
+        }
+        if (!prefixed) return launch_sha3_256_mixed(n, arena, arena_bytes, off, pa.spans, pa.digests, ctx->d_sha3_coop_rows, st);
+    }
+    hipError_t err = hipSuccess;
+    if (prefixed && !pa.mid_ready) err = launch_sha3_256_midstates(arena, arena_bytes, pa, st);
+    if (err == hipSuccess) err = launch_sha3_256_messages(n, arena, arena_bytes, off, pa, st);
+    return err;
+}
+
 int fabgpu_sha3_256_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, void* stream) {
     if (!ctx || (n && (!arena || !off || !digests))) return FABGPU_EINVAL;
     if (dev_too_big(n, arena_bytes)) return FABGPU_ETOOBIG;
     if (n == 0) return FABGPU_OK;
     DeviceGuard g(ctx->device);
     hipStream_t st = (hipStream_t)stream;
-    return timed_launch(ctx, st, 0, [&](void*) { return launch_sha3_256_batch((uint32_t)n, arena, arena_bytes, off, false, digests, st); });
+    return timed_launch(ctx, st, 0, [&](void*) {
+        ShaPrefixArgs pa;
+        pa.digests = digests;
+        return sha3_launch_messages(ctx, (uint32_t)n, arena, arena_bytes, off, pa, st);
+    });
 }
 
 // the digests of a (possibly prefixed) batch into `dig`, then the verify-only entry point over them; key_id == nullptr: fresh keys
@@ -1718,11 +1782,8 @@ static int sha3_then_verify_dev(fabgpu_ctx* ctx, size_t n, const void* arena, si
         int rc = ctx->acquire_qws(n * 32, &di, &dig, st);
         if (rc != FABGPU_OK) return rc;
     }
-    hipError_t err = hipSuccess;
-    if (pa.m && pa.pre_idx && !pa.mid_ready) err = launch_sha3_256_midstates(arena, arena_bytes, pa, st);
     pa.digests = dig;
-    if (err == hipSuccess) err = launch_sha3_256_messages((uint32_t)n, arena, arena_bytes, off, pa, st);
-    int rc = hip_to_rc(launched(ctx, err));
+    int rc = hip_to_rc(launched(ctx, sha3_launch_messages(ctx, (uint32_t)n, arena, arena_bytes, off, pa, st)));
     if (rc == FABGPU_OK)
         rc = key_id ? fabgpu_p256_verify_batch_keyed_dev(ctx, n, key_id, dig, r, s, verdict_bits, status, st)
                     : fabgpu_p256_verify_batch_dev(ctx, n, qx, qy, dig, r, s, verdict_bits, status, st);
@@ -2318,6 +2379,21 @@ int fabgpu_p384_key_unregister(fabgpu_ctx* ctx, uint32_t key_id) {
 int fabgpu_p384_wide_rows(fabgpu_ctx* ctx, uint64_t* rows) {
     if (!ctx || !rows) return FABGPU_EINVAL;
     *rows = ctx->k384_wide_rows.load(std::memory_order_relaxed);
+    return FABGPU_OK;
+}
+
+// rows hashed on 32 lanes so far: the small launches as queued, the long rows of the mixed kernel as the device has counted them
+int fabgpu_sha3_coop_rows(fabgpu_ctx* ctx, uint64_t* rows) {
+    if (!ctx || !rows) return FABGPU_EINVAL;
+    *rows = ctx->sha3_coop_rows.load(std::memory_order_relaxed);
+    if (!ctx->d_sha3_coop_rows) return FABGPU_OK;
+    DeviceGuard g(ctx->device);
+    unsigned long long v = 0;
+    if (hipMemcpy(&v, ctx->d_sha3_coop_rows, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return FABGPU_ELAUNCH;
+    }
+    *rows += v;
     return FABGPU_OK;
 }
 

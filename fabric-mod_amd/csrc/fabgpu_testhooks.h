@@ -28,6 +28,9 @@ long long fabgpu_test_key_tables16(fabgpu_ctx* ctx, uint32_t key_id);
 /* TEST HOOK: while on, the idemix four-lane form queues its side launch (the fixed-base terms) BEHIND the commitment launch, so that
  * every commitment wavefront gives up on its records and computes the terms itself, and every side wavefront skips its rows. */
 void fabgpu_test_nym_side_after(fabgpu_ctx* ctx, int on);
+/* TEST HOOK: fabgpu_sha3_256_batch_dev through the 32-lanes-per-message kernel at ANY n, whatever the context's FABGPU_FLAG_SHA3_COOP and
+ * SHA3_COOP_MAX say (tools/bench_sha3_coop.py times it beyond the cap, to place the cap); counts no row. */
+int fabgpu_test_sha3_coop_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, void* stream);
 /* TEST HOOK: the capacities in bytes of the block pass's buffers on ctx - per-envelope arrays, per-tuple arrays, pinned staging, host-mapped
  * results, gather scratch (walk_layout.h says what a pass needs of each; walk_preallocate makes the worst case ahead of the first pass). */
 void fabgpu_test_walk_buffer_caps(fabgpu_ctx* ctx, uint64_t* out5);

@@ -118,6 +118,20 @@ hipError_t launch_sha3_256_messages(uint32_t n, const void* arena, size_t arena_
 hipError_t launch_sha3_256_batch(uint32_t n, const void* arena, size_t arena_bytes, const void* off, bool spans, void* digests, hipStream_t st);
 int warm_kernel_functions_sha3();
 
+// ---- sha3_coop_kernels.hip: SHA3-256 with 32 lanes on a message (sha3_coop.h), behind FABGPU_FLAG_SHA3_COOP ----
+// The contract of launch_sha3_256_messages for launches that cannot fill the chip: two messages a wavefront, a prefixed message hashed
+// whole - NO mid-states are read, pa.mid_scratch may be null and is not written.  A reversed span hashes as empty.  The largest launch the
+// context's call sites give it is SHA3_COOP_MAX messages: the largest power of two at which tools/bench_sha3_coop.py measured its median
+// at or below the one-lane kernel's (profiles/sha3_coop.json).
+constexpr uint32_t SHA3_COOP_MAX = 4096;
+hipError_t launch_sha3_256_messages_coop(uint32_t n, const void* arena, size_t arena_bytes, const void* off, const ShaPrefixArgs& pa, hipStream_t st);
+// Larger plain launches: one lane per message (sha3_256_stream), except that messages well above the launch's average length (a quarter
+// above arena_bytes / n, at least 2 KiB, as launch_sha256_mixed) are hashed on 32 lanes each - at most two per 64 messages - by wavefronts
+// of their own inside the same launch.  pairs: off holds (start, end) pairs.  coop_rows (optional, device): += the rows hashed on 32 lanes.
+hipError_t launch_sha3_256_mixed(uint32_t n, const void* arena, size_t arena_bytes, const void* off, bool pairs, void* digests, void* coop_rows,
+                                 hipStream_t st);
+int warm_kernel_functions_sha3_coop();
+
 // ---- p384_kernels.hip: ECDSA P-384 verification (p384.h), one signature per lane, fresh keys only ----
 struct P384Launch {
     uint32_t n = 0;

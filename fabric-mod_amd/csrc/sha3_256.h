@@ -10,7 +10,7 @@
 // bit operation per half (v_bitop3_b32 on gfx950).  Keccak's lanes are little-endian: a message word is the arena's dword shifted to
 // the message's byte phase, no byte swap.
 //
-// Not here: a 5- or 25-lanes-per-message form for launches that cannot fill the chip (the analogue of sha256_coop.h).
+// The 32-lanes-per-message form for launches that cannot fill the chip and for long messages is sha3_coop.h.
 #pragma once
 #include <stdint.h>
 
@@ -57,6 +57,24 @@ FAB_HD uint32_t k_chi(uint32_t a, uint32_t b, uint32_t c) {
 // the low n bytes of a word, n any integer (n <= 0: none, n >= 4: all)
 FAB_HD uint32_t k_low_bytes(int32_t n) { return n >= 4 ? 0xFFFFFFFFu : (n <= 0 ? 0u : (0xFFFFFFFFu >> (32 - 8 * n))); }
 
+// Keccak-f[1600]'s constants, for this file and for sha3_coop.h (functions, so that device code may index them by a lane or a loop count)
+FAB_HD constexpr uint64_t sha3_rc(int round) {               // iota
+    constexpr uint64_t RC[24] = {0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808aull, 0x8000000080008000ull, 0x000000000000808bull,
+                                 0x0000000080000001ull, 0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008aull, 0x0000000000000088ull,
+                                 0x0000000080008009ull, 0x000000008000000aull, 0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull,
+                                 0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull, 0x000000000000800aull, 0x800000008000000aull,
+                                 0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
+    return RC[round];
+}
+FAB_HD constexpr int sha3_rho(int i) {                       // rho: the rotation of lane A[x, y], i = x + 5 y
+    constexpr int RHO[25] = {0,  1,  62, 28, 27,
+                             36, 44, 6,  55, 20,
+                             3,  10, 43, 25, 39,
+                             41, 45, 15, 21, 8,
+                             18, 2,  61, 56, 14};
+    return RHO[i];
+}
+
 // (lo, hi) <- rotl64((lo, hi), N), N a constant
 template <int N>
 FAB_HD void k_rotl(uint32_t lo, uint32_t hi, uint32_t& olo, uint32_t& ohi) {
@@ -73,20 +91,15 @@ FAB_HD void k_rotl(uint32_t lo, uint32_t hi, uint32_t& olo, uint32_t& ohi) {
     }
 }
 
-// rho and pi for lane (X, Y): B[Y, 2 X + 3 Y] = rotl(A[X, Y] ^ D[X], R)
-template <int X, int Y, int R>
+// rho and pi for lane (X, Y): B[Y, 2 X + 3 Y] = rotl(A[X, Y] ^ D[X], sha3_rho(X + 5 Y))
+template <int X, int Y>
 FAB_HD void k_rho_pi(const uint32_t (&a)[SHA3_STATE_WORDS], const uint32_t (&d)[10], uint32_t (&b)[SHA3_STATE_WORDS]) {
     constexpr int src = X + 5 * Y, dst = Y + 5 * ((2 * X + 3 * Y) % 5);
-    k_rotl<R>(a[2 * src] ^ d[2 * X], a[2 * src + 1] ^ d[2 * X + 1], b[2 * dst], b[2 * dst + 1]);
+    k_rotl<sha3_rho(src)>(a[2 * src] ^ d[2 * X], a[2 * src + 1] ^ d[2 * X + 1], b[2 * dst], b[2 * dst + 1]);
 }
 
 template <int ROUND>
 FAB_HD void keccak_round(uint32_t (&a)[SHA3_STATE_WORDS]) {
-    constexpr uint64_t RC[24] = {0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808aull, 0x8000000080008000ull, 0x000000000000808bull,
-                                 0x0000000080000001ull, 0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008aull, 0x0000000000000088ull,
-                                 0x0000000080008009ull, 0x000000008000000aull, 0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull,
-                                 0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull, 0x000000000000800aull, 0x800000008000000aull,
-                                 0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
     uint32_t c[10], d[10], b[SHA3_STATE_WORDS];
     // theta: column parities, D[x] = C[x - 1] ^ rotl(C[x + 1], 1)
 #pragma unroll
@@ -103,11 +116,11 @@ FAB_HD void keccak_round(uint32_t (&a)[SHA3_STATE_WORDS]) {
         d[2 * x + 1] = c[2 * p + 1] ^ rh;
     }
     // rho + pi, with theta's xor folded in
-    k_rho_pi<0, 0, 0>(a, d, b);  k_rho_pi<1, 0, 1>(a, d, b);  k_rho_pi<2, 0, 62>(a, d, b); k_rho_pi<3, 0, 28>(a, d, b); k_rho_pi<4, 0, 27>(a, d, b);
-    k_rho_pi<0, 1, 36>(a, d, b); k_rho_pi<1, 1, 44>(a, d, b); k_rho_pi<2, 1, 6>(a, d, b);  k_rho_pi<3, 1, 55>(a, d, b); k_rho_pi<4, 1, 20>(a, d, b);
-    k_rho_pi<0, 2, 3>(a, d, b);  k_rho_pi<1, 2, 10>(a, d, b); k_rho_pi<2, 2, 43>(a, d, b); k_rho_pi<3, 2, 25>(a, d, b); k_rho_pi<4, 2, 39>(a, d, b);
-    k_rho_pi<0, 3, 41>(a, d, b); k_rho_pi<1, 3, 45>(a, d, b); k_rho_pi<2, 3, 15>(a, d, b); k_rho_pi<3, 3, 21>(a, d, b); k_rho_pi<4, 3, 8>(a, d, b);
-    k_rho_pi<0, 4, 18>(a, d, b); k_rho_pi<1, 4, 2>(a, d, b);  k_rho_pi<2, 4, 61>(a, d, b); k_rho_pi<3, 4, 56>(a, d, b); k_rho_pi<4, 4, 14>(a, d, b);
+    k_rho_pi<0, 0>(a, d, b); k_rho_pi<1, 0>(a, d, b); k_rho_pi<2, 0>(a, d, b); k_rho_pi<3, 0>(a, d, b); k_rho_pi<4, 0>(a, d, b); 
+    k_rho_pi<0, 1>(a, d, b); k_rho_pi<1, 1>(a, d, b); k_rho_pi<2, 1>(a, d, b); k_rho_pi<3, 1>(a, d, b); k_rho_pi<4, 1>(a, d, b); 
+    k_rho_pi<0, 2>(a, d, b); k_rho_pi<1, 2>(a, d, b); k_rho_pi<2, 2>(a, d, b); k_rho_pi<3, 2>(a, d, b); k_rho_pi<4, 2>(a, d, b); 
+    k_rho_pi<0, 3>(a, d, b); k_rho_pi<1, 3>(a, d, b); k_rho_pi<2, 3>(a, d, b); k_rho_pi<3, 3>(a, d, b); k_rho_pi<4, 3>(a, d, b); 
+    k_rho_pi<0, 4>(a, d, b); k_rho_pi<1, 4>(a, d, b); k_rho_pi<2, 4>(a, d, b); k_rho_pi<3, 4>(a, d, b); k_rho_pi<4, 4>(a, d, b); 
     // chi
 #pragma unroll
     for (int y = 0; y < 5; y++) {
@@ -119,8 +132,8 @@ FAB_HD void keccak_round(uint32_t (&a)[SHA3_STATE_WORDS]) {
         }
     }
     // iota
-    if ((uint32_t)RC[ROUND]) a[0] ^= (uint32_t)RC[ROUND];
-    if ((uint32_t)(RC[ROUND] >> 32)) a[1] ^= (uint32_t)(RC[ROUND] >> 32);
+    if ((uint32_t)sha3_rc(ROUND)) a[0] ^= (uint32_t)sha3_rc(ROUND);
+    if ((uint32_t)(sha3_rc(ROUND) >> 32)) a[1] ^= (uint32_t)(sha3_rc(ROUND) >> 32);
 }
 
 // Keccak-f[1600]: 24 rounds, unrolled

@@ -100,6 +100,9 @@ int fabgpu_test_key_table_host(const uint8_t* qx32, const uint8_t* qy32, int32_t
 }
 // the idemix four-lane form: order the side launch behind the commitment launch (idemix_kernels.hip: both halves of the fallback)
 void fabgpu_test_nym_side_after(fabgpu_ctx* ctx, int on) { fab::ctx_test_nym_side_after(ctx, on != 0); }
+int fabgpu_test_sha3_coop_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, void* stream) {
+    return fab::sha3_coop_batch_uncapped(ctx, n, arena, arena_bytes, off, digests, stream);
+}
 // how large the block pass's buffers are right now: a pass that fits what walk_preallocate made leaves all five as they were
 void fabgpu_test_walk_buffer_caps(fabgpu_ctx* ctx, uint64_t* out5) { fab::walk_buffer_caps(ctx, out5); }
 

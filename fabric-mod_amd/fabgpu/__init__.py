@@ -44,6 +44,7 @@ FLAG_KEY_TABLES_16BIT = 256  # fabgpu.h: registered keys also get a 16-bit comb 
 FLAG_NO_WIDE = 32            # fabgpu.h: registered keys never on the eight-lanes-per-signature two-phase kernels (launches <= 8 192 signatures)
 FLAG_P384_KEY_TABLES_16BIT = 8192   # fabgpu.h: registered P-384 keys also get 16-bit comb tables (144 MiB each, <= 32 per context; off by default)
 FLAG_P384_WIDE = 4096        # fabgpu.h: registered P-384 keys on eight lanes per signature, two launches, for keyed launches <= 8 192 rows (off by default)
+FLAG_SHA3_COOP = 32768       # fabgpu.h: SHA3-256 on 32 lanes per message for launches <= 4 096 messages and for the long messages of larger plain ones (off by default)
 ST_VALID, ST_BAD_MATH, ST_HIGH_S, ST_RANGE, ST_OFF_CURVE = 0, 1, 2, 3, 4
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -172,6 +173,7 @@ ABI_SYMBOLS = [
     "fabgpu_identity_verify_batch_p384_sha3_dev", "fabgpu_identity_to_p384", "fabgpu_csp_p384_pass_stats", "fabgpu_csp_msp_hash_family", "fabgpu_csp_msp_hash_family_get",
     "fabgpu_csp_memo_lookup_p384", "fabgpu_csp_memo_stats_p384", "fabgpu_csp_memo_set_capacity_p384",
     "fabgpu_p384_wide_rows", "fabgpu_csp_p384_pass_wide_rows", "fabgpu_p384_tables16_rows",
+    "fabgpu_sha3_coop_rows", "fabgpu_csp_sha3_coop_rows",
 ]
 
 # what libfabgpu_testhooks.so exports (fabric-mod_amd/csrc/fabgpu_testhooks.h): probes, walker comparisons, the synthetic block generator, the
@@ -186,7 +188,7 @@ HOOK_SYMBOLS = [
     "fabgpu_test_p384_key_table", "fabgpu_test_p384_key_table_host", "fabgpu_test_p384_verify_keyed_host", "fabgpu_test_p384_key_register_batch",
     "fabgpu_test_p384_book_new", "fabgpu_test_p384_book_free", "fabgpu_test_p384_book_register", "fabgpu_test_p384_book_lookup",
     "fabgpu_test_p384_book_retire", "fabgpu_test_p384_book_snapshot",
-    "fabgpu_test_p384_tables16_wait", "fabgpu_test_p384_tables16_cap", "fabgpu_test_p384_key_table16", "fabgpu_test_p384_key_table16_host",
+    "fabgpu_test_sha3_coop_batch_dev", "fabgpu_test_p384_tables16_wait", "fabgpu_test_p384_tables16_cap", "fabgpu_test_p384_key_table16", "fabgpu_test_p384_key_table16_host",
 ]
 _HOOKS_PATH = os.path.join(os.path.dirname(_LIB_PATH), "libfabgpu_testhooks.so")
 
@@ -347,6 +349,8 @@ def load():
     L.fabgpu_csp_p384_pass_stats.argtypes = [_vp, _u64p, ctypes.c_int]
     L.fabgpu_csp_p384_pass_wide_rows.argtypes = [_vp, _u64p]
     L.fabgpu_p384_wide_rows.argtypes = [_vp, _u64p]
+    L.fabgpu_sha3_coop_rows.argtypes = [_vp, _u64p]
+    L.fabgpu_csp_sha3_coop_rows.argtypes = [_vp, _u64p]
     L.fabgpu_p384_tables16_rows.argtypes = [_vp, _u64p]
     L.fabgpu_csp_msp_hash_family.argtypes = [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
     L.fabgpu_csp_msp_hash_family_get.argtypes = [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
@@ -692,6 +696,13 @@ class Context:
         """fabgpu_p384_tables16_rows: rows of the wavefronts of keyed P-384 launches that ran on 16-bit tables (FLAG_P384_KEY_TABLES_16BIT)."""
         v = ctypes.c_uint64(0)
         _check(self._L.fabgpu_p384_tables16_rows(self._h, ctypes.byref(v)), "fabgpu_p384_tables16_rows")
+        return int(v.value)
+
+    def sha3_coop_rows(self) -> int:
+        """fabgpu_sha3_coop_rows: rows of SHA3-256 launches this context hashed on 32 lanes per message (FLAG_SHA3_COOP) - the small
+        launches as queued, the long rows of large launches as counted by the launches that have finished."""
+        v = ctypes.c_uint64(0)
+        _check(self._L.fabgpu_sha3_coop_rows(self._h, ctypes.byref(v)), "fabgpu_sha3_coop_rows")
         return int(v.value)
 
     def p384_wide_rows(self) -> int:
@@ -1080,7 +1091,7 @@ class GPUCSP:
 
     def __init__(self, device: int = -1, devices: Optional[Sequence[int]] = None, flags: int = 0, concurrent_passes: int = 0,
                  expect_block_bytes: int = 0, expect_tuples: int = 0, retire_evicted_keys: int = 0, hash_sha3: int = 0, p384: int = 0, p384_wide: int = 0,
-                 p384_key_tables16: int = 0, **switches):
+                 p384_key_tables16: int = 0, sha3_coop: int = 0, **switches):
         """device: ONE context on that HIP ordinal (fabgpu_csp_new).  devices: one context per entry - an ordinal may repeat; an empty
         list means every visible device - behind ONE provider (fabgpu_csp_new2: what bccsp/factory builds from the `GPU:` section).
         switches: pass_device_walk / pass_stage_min_bytes / pass_device_memo / pass_host_counts / pass_timing / pass_hash_memo (0 default,
@@ -1091,7 +1102,11 @@ class GPUCSP:
         served on the device (set_option of the same name).  p384_wide (0, the default: off): FLAG_P384_WIDE on every context, read at
         construction - keyed P-384 launches of at most 8 192 rows on eight lanes per signature (set_option of the same name switches the
         living contexts).  p384_key_tables16 (0, the default: off): FLAG_P384_KEY_TABLES_16BIT on every context, read at construction -
-        every imported P-384 key also gets a 16-bit comb table."""
+        every imported P-384 key also gets a 16-bit comb table.  sha3_coop (0, the default: off): FLAG_SHA3_COOP on every context, read
+        at construction - SHA3-256 launches of at most 4 096 messages on 32 lanes per message, the long messages of larger plain ones
+        likewise (set_option of the same name switches the living contexts; sha3_coop_rows)."""
+        if sha3_coop > 0:
+            flags |= FLAG_SHA3_COOP
         if p384_key_tables16 > 0:
             flags |= FLAG_P384_KEY_TABLES_16BIT
         if p384_wide > 0:
@@ -1248,6 +1263,12 @@ class GPUCSP:
         if err.value:
             raise BCCSPError(err.value.decode())
         return bool(valid.value)
+
+    def sha3_coop_rows(self) -> int:
+        """fabgpu_csp_sha3_coop_rows: Context.sha3_coop_rows summed over the pool's contexts (option sha3_coop; 0 without it)."""
+        v = ctypes.c_uint64(0)
+        _check(self._L.fabgpu_csp_sha3_coop_rows(self._h, ctypes.byref(v)), "fabgpu_csp_sha3_coop_rows")
+        return int(v.value)
 
     # ---- ECDSA P-384 identities (option p384): keys are (x, y) integer pairs ----
     def p384_pass_stats(self) -> dict:

@@ -84,6 +84,10 @@ type GPUOpts struct {
 	// (fabgpu.h FABGPU_FLAG_P384_KEY_TABLES_16BIT, fabgpu_bccsp.h option "p384_key_tables16").  Default false.  Verdicts do not depend
 	// on it; it needs P384.
 	P384KeyTables16 bool `mapstructure:"p384keytables16" json:"p384keytables16,omitempty" yaml:"P384KeyTables16,omitempty"`
+	// SHA3Coop: SHA3-256 launches of at most 4 096 messages run with 32 lanes on a message, and larger launches hash their few long
+	// messages that way (fabgpu.h FABGPU_FLAG_SHA3_COOP, fabgpu_bccsp.h option "sha3_coop").  Default false.  Digests and verdicts do
+	// not depend on it; it matters only where SHA3 is served.
+	SHA3Coop bool `mapstructure:"sha3coop" json:"sha3coop,omitempty" yaml:"SHA3Coop,omitempty"`
 }
 
 // DefaultAuditPermille is what GPUOpts.AuditPermille means when the `GPU:` section does not set it.
@@ -123,6 +127,7 @@ func (f *GPUFactory) Get(config *FactoryOpts) (bccsp.BCCSP, error) {
 		opts.P384 = g.P384
 		opts.P384Wide = g.P384Wide
 		opts.P384KeyTables16 = g.P384KeyTables16
+		opts.SHA3Coop = g.SHA3Coop
 		if g.SHA3 != nil {
 			opts.SHA3 = *g.SHA3
 		}

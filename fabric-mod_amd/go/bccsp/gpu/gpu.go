@@ -165,6 +165,9 @@ type Options struct {
 	// (144 MiB, at most 32 per context), and keyed launches run 24 windows of two additions on the wavefronts all of whose keys have
 	// one.  False by default.  Verdicts do not depend on it.
 	P384KeyTables16 bool
+	// SHA3Coop: FABGPU_FLAG_SHA3_COOP on every context - SHA3-256 launches of at most 4 096 messages run with 32 lanes on a message, and
+	// larger plain launches hash their few long messages that way.  False by default.  Digests and verdicts do not depend on it.
+	SHA3Coop bool
 }
 
 // SetCoalesce switches the coalesced device path for memo misses on or off (GPUOpts.CoalesceVerify in gpufactory.go).
@@ -257,6 +260,9 @@ func New(swCSP bccsp.BCCSP, opts Options) (bccsp.BCCSP, error) {
 	}
 	if opts.P384KeyTables16 {
 		o.ctx_flags |= 8192 // fabgpu.h FABGPU_FLAG_P384_KEY_TABLES_16BIT
+	}
+	if opts.SHA3Coop {
+		o.ctx_flags |= 32768 // fabgpu.h FABGPU_FLAG_SHA3_COOP
 	}
 	if opts.HostWalk {
 		o.pass_device_walk = -1

@@ -106,6 +106,12 @@ typedef struct fabgpu_ctx fabgpu_ctx;
                                         Statuses and verdict words do not change */
 #define FABGPU_P384_MAX_TABLES16 32
 
+#define FABGPU_FLAG_SHA3_COOP 32768u  /* SHA3-256: launches of at most 4 096 messages run with 32 lanes on a message, two messages a wavefront
+                                        (a prefixed message is hashed whole: no mid-state launch), and larger plain launches hash the first
+                                        two messages in every 64 that are well above the launch's average length on 32 lanes each, inside the
+                                        same launch.  Every fabgpu_sha3_256_* entry and the described batch under FABGPU_IDB_SHA3_256.  Off by
+                                        default.  Digests, statuses and verdict words do not change (fabgpu_sha3_coop_rows counts) */
+
 typedef struct fabgpu_cfg {
     int32_t device;      /* HIP device ordinal; -1 = the current device */
     uint32_t max_batch;  /* staging pre-allocation hint in tuples (0 = grow on demand) */
@@ -151,7 +157,9 @@ int fabgpu_sha256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* ar
  *      is valid, every bit >= n is 0 - a consumer may take whole words;
  *   2. status[0, n) holds the status bytes; with status == NULL nothing is written in its place;
  *   3. digests[0, n), 32 bytes a row, holds the digests - the hash-only calls, and `digests` / `gather_digests` (n_gather rows) of the
- *      described batch; that one's mid_scratch and gather_scratch are the call's to use within the sizes stated for them, and its
+ *      described batch; that one's mid_scratch and gather_scratch are the call's to use within the sizes stated for them (mid_scratch
+ *      under FABGPU_IDB_SHA3_256: n_prefixes x 200 bytes or nothing - a context with FABGPU_FLAG_SHA3_COOP does not write it at all for
+ *      a batch of at most 4 096 messages, whose prefixed messages it hashes whole), and its
  *      pseudonym part is the host variant's alone: the _dev entry writes neither nym_verdict_bits nor nym_status;
  *   4. no byte outside these ranges is written, in front of them or behind them.
  * tests/test_dev_output_contract_gpu.py holds every kernel form to it. */
@@ -209,10 +217,14 @@ int fabgpu_sha256_p256_verify_batch_keyed_dev(fabgpu_ctx* ctx, size_t n, const v
  * Argument lists, conventions and verdicts are those of the sha256 namesakes above; the digest is SHA3-256 (FIPS 202).  The curve
  * arithmetic does not depend on the family: a SHA3-256 digest is 32 bytes, e is the digest itself.  Hash and verify are two launches on
  * one stream - the digests go through a context-owned device buffer into the verify-only kernels, which are chosen by n and the
- * context's flags as for fabgpu_p256_verify_batch(_keyed); no digest leaves the chip.  One message per lane at every size (there is
- * no several-lanes-per-message form for small launches).  Not served: fabgpu_multi_*, and the P-256 tuples of the block pass
+ * context's flags as for fabgpu_p256_verify_batch(_keyed); no digest leaves the chip.  One message per lane at every size, unless the
+ * context has FABGPU_FLAG_SHA3_COOP: then launches of at most 4 096 messages take 32 lanes per message, and larger ones without prefixes
+ * take them for their few long messages.  fabgpu_sha3_coop_rows: *rows = the rows this context has hashed on 32 lanes so far - the small
+ * launches as they are queued, the long rows of large launches as the device has counted them in the launches that have finished (0
+ * without the flag).  Not served: fabgpu_multi_*, and the P-256 tuples of the block pass
  * (fabgpu_bccsp.h), whose routes hash every signed message with SHA-256; its P-384 stage hashes the tuples of an MSP set SHA3
  * (fabgpu_csp_msp_hash_family) with SHA3-256, through fabgpu_identity_verify_batch_p384_sha3. */
+int fabgpu_sha3_coop_rows(fabgpu_ctx* ctx, uint64_t* rows);
 int fabgpu_sha3_256_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, uint8_t* digests);
 int fabgpu_sha3_256_batch_dev(fabgpu_ctx* ctx, size_t n, const void* arena, size_t arena_bytes, const void* off, void* digests, void* stream);
 int fabgpu_sha3_256_p256_verify_batch(fabgpu_ctx* ctx, size_t n, const uint8_t* arena, const uint32_t* off, const uint8_t* qx,

@@ -94,6 +94,10 @@ int fabgpu_csp_route_block(fabgpu_csp* csp, uint64_t block_seq);   /* where a pa
  * at construction from ctx_flags - every imported P-384 key also gets a 16-bit comb table (144 MiB, at most 32 per context), and the
  * keyed batches of fabgpu_csp_verify_batch_p384, the identity batches, the coalescer and the pass stage run 24 windows on the
  * wavefronts all of whose keys have one (fabgpu.h).  Verdicts, statuses and flags do not depend on it.
+ * "sha3_coop" (default off; > 0 on): FABGPU_FLAG_SHA3_COOP on every context of the pool - SHA3-256 launches of at most 4 096 messages run
+ * with 32 lanes on a message, larger plain ones take them for their long messages (fabgpu.h).  A context flag like "p384_wide": read at
+ * construction from ctx_flags, and set on a living provider it switches every context for the launches queued from then on.  Digests,
+ * verdicts and statuses do not depend on it; fabgpu_csp_sha3_coop_rows counts.
  * FABGPU_EINVAL: no such option. */
 int fabgpu_csp_set_option(fabgpu_csp* csp, const char* name, int64_t value, int64_t* previous);
 int fabgpu_csp_get_option(fabgpu_csp* csp, const char* name, int64_t* value);
@@ -382,6 +386,9 @@ int fabgpu_csp_p384_pass_stats(fabgpu_csp* csp, uint64_t* out, int cap);
  * its keyed batches that the eight-lanes-per-signature form verified (the "p384_wide" option; a part of [2]; 0 with the option off, and
  * for every fresh-key batch). */
 int fabgpu_csp_p384_pass_wide_rows(fabgpu_csp* csp, uint64_t* rows);
+/* *rows = fabgpu_sha3_coop_rows summed over the contexts of the pool: the rows of this provider's SHA3-256 launches (and of anyone else's
+ * on its contexts) that were hashed on 32 lanes (the "sha3_coop" option; 0 with the option off). */
+int fabgpu_csp_sha3_coop_rows(fabgpu_csp* csp, uint64_t* rows);
 /* The hash family of an MSP, as the block pass knows it: what the MSP's setup read from its config's SignatureHashFamily
  * (msp/identities.go:216-224).  family: "SHA2" or "SHA3"; anything else answers 1 with identity.getHashOpt's text in err ("hash familiy
  * not recognized [..]"), and "SHA3" while the hash_sha3 option is off answers 1 with the text that bccsp/sw serves it; an empty mspid or

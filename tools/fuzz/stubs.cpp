@@ -21,6 +21,7 @@ int fabgpu_p256_key_register_many(fabgpu_ctx* const*, int, const uint8_t*, const
 int fabgpu_p256_key_unregister_many(fabgpu_ctx* const*, int, const uint8_t*, const uint8_t*) { return -1; }
 int fabgpu_p256_key_table_stats(fabgpu_ctx*, uint64_t*, int) { return -1; }
 int fabgpu_sha3_256_batch(fabgpu_ctx*, size_t, const uint8_t*, const uint32_t*, uint8_t*) { return -1; }
+int fabgpu_sha3_coop_rows(fabgpu_ctx*, uint64_t*) { return -1; }
 int fabgpu_sha3_256_p256_verify_batch(fabgpu_ctx*, size_t, const uint8_t*, const uint32_t*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, uint64_t*, uint8_t*) { return -1; }
 int fabgpu_sha3_256_p256_verify_batch_keyed(fabgpu_ctx*, size_t, const uint8_t*, const uint32_t*, const uint32_t*, const uint8_t*, const uint8_t*, uint64_t*, uint8_t*) { return -1; }
 // the P-384 entries of the direct-call verbs and of the pass's P-384 stage
@@ -54,5 +55,6 @@ void host_copy_limit(fabgpu_ctx*, uint32_t) {}
 void host_copy_preallocate(fabgpu_ctx*, size_t, uint32_t) {}
 int ctx_set_p384_wide(fabgpu_ctx*, bool) { return -1; }
 bool ctx_p384_wide_serves(fabgpu_ctx*, size_t) { return false; }
+int ctx_set_sha3_coop(fabgpu_ctx*, bool) { return -1; }
 void host_copy_stats(fabgpu_ctx*, uint64_t* a, uint64_t* b, uint64_t* c) { if (a) *a = 0; if (b) *b = 0; if (c) *c = 0; }
 }
