@@ -166,6 +166,7 @@ struct fabgpu_ctx {
     int pair_table_lds = -1;       // the verify-only pair kernel's per-signature table: 1 in LDS, 0 in the global workspace, -1 by batch size (kernels.h)
     bool pair_solo = false;        // FABGPU_FLAG_PAIR_SOLO: the LDS-table pair kernel without helper waves
     bool pair_dbl1 = false;        // FABGPU_FLAG_PAIR_DBL1: the LDS-table pair kernels with the per-doubling loop
+    bool pair_table_add = false;   // FABGPU_FLAG_PAIR_TABLE_ADD: the LDS-table pair kernels with the odd multiples by general additions
     bool pair_booth4 = false;      // FABGPU_FLAG_PAIR_BOOTH4: the LDS-table pair kernels with Booth digits and 65 windows
     hipStream_t stream = nullptr;
     // FABGPU_FAULT_INJECT (tests of the failure contract only): "launch" makes every kernel submission report hipErrorLaunchFailure,
@@ -540,7 +541,7 @@ int fabgpu_init(const fabgpu_cfg* cfg, fabgpu_ctx** out) {
     *out = nullptr;
     if (cfg && (cfg->flags & ~(uint32_t)(FABGPU_FLAG_ONE_LANE_ONLY | FABGPU_FLAG_TIME_KERNELS | FABGPU_FLAG_NO_QUAD | FABGPU_FLAG_PAIR_TABLE_LDS |
                                           FABGPU_FLAG_PAIR_TABLE_GLOBAL | FABGPU_FLAG_NO_WIDE | FABGPU_FLAG_NYM_FUSED_HASH | FABGPU_FLAG_NYM_NO_SIDE_STREAM |
-                                          FABGPU_FLAG_KEY_TABLES_16BIT | FABGPU_FLAG_PAIR_SOLO | FABGPU_FLAG_PAIR_DBL1 | FABGPU_FLAG_PAIR_BOOTH4 | FABGPU_FLAG_P384_WIDE |
+                                          FABGPU_FLAG_KEY_TABLES_16BIT | FABGPU_FLAG_PAIR_SOLO | FABGPU_FLAG_PAIR_DBL1 | FABGPU_FLAG_PAIR_BOOTH4 | FABGPU_FLAG_PAIR_TABLE_ADD | FABGPU_FLAG_P384_WIDE |
                                           FABGPU_FLAG_P384_KEY_TABLES_16BIT | FABGPU_FLAG_SHA3_COOP)) != 0) return FABGPU_EINVAL;
     if (cfg && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_LDS) && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_GLOBAL)) return FABGPU_EINVAL;
     int ndev = 0;
@@ -568,6 +569,7 @@ int fabgpu_init(const fabgpu_cfg* cfg, fabgpu_ctx** out) {
     ctx->pair_solo = cfg && (cfg->flags & FABGPU_FLAG_PAIR_SOLO);
     ctx->pair_dbl1 = cfg && (cfg->flags & FABGPU_FLAG_PAIR_DBL1);
     ctx->pair_booth4 = cfg && (cfg->flags & FABGPU_FLAG_PAIR_BOOTH4);
+    ctx->pair_table_add = cfg && (cfg->flags & FABGPU_FLAG_PAIR_TABLE_ADD);
     // The LDS form of the pair kernel asks for 157 KiB of dynamic LDS per workgroup (130 KiB of tables, p256_pair29.h PAIR_LDS_CELLS_PER_SIG,
     // and the helper waves' handoff, PAIR_HAND_WORDS; 130 KiB in the one-wave form): a device that grants less keeps the table in the
     // global workspace instead of failing every large launch.  (That allocation is also what keeps other kernels off the
@@ -810,7 +812,7 @@ int fabgpu_p256_verify_batch_dev(fabgpu_ctx* ctx, size_t n, const void* qx, cons
     VerifyLaunch v = verify_launch_common(ctx, n, r, s, verdict_bits, status);
     v.qx = qx; v.qy = qy;
     v.e = e;
-    v.table_lds = ctx->pair_table_lds; v.pair_solo = ctx->pair_solo; v.pair_dbl1 = ctx->pair_dbl1; v.pair_booth4 = ctx->pair_booth4;   // (the verify-only fresh-key form alone has the two table homes)
+    v.table_lds = ctx->pair_table_lds; v.pair_solo = ctx->pair_solo; v.pair_dbl1 = ctx->pair_dbl1; v.pair_booth4 = ctx->pair_booth4; v.pair_table_add = ctx->pair_table_add;   // (the verify-only fresh-key form alone has the two table homes)
     return timed_launch(ctx, st, verify_workspace_bytes((uint32_t)n, ctx->allow_pair), [&](void* wsp) {
         v.qws = wsp;
         return launch_verify(v, st);
@@ -3790,7 +3792,7 @@ int walk_block_pass(fabgpu_ctx* ctx, WalkRequest& rq) {
             int r2 = ctx->acquire_qws(verify_workspace_bytes(tot.creators, true), &wi, &wsp, s2);
             if (r2 != FABGPU_OK) return r2;
             v.qx = a.qx; v.qy = a.qy; v.qws = wsp;
-            v.table_lds = ctx->pair_table_lds; v.pair_solo = ctx->pair_solo; v.pair_dbl1 = ctx->pair_dbl1; v.pair_booth4 = ctx->pair_booth4;
+            v.table_lds = ctx->pair_table_lds; v.pair_solo = ctx->pair_solo; v.pair_dbl1 = ctx->pair_dbl1; v.pair_booth4 = ctx->pair_booth4; v.pair_table_add = ctx->pair_table_add;
             e = launch_verify(v, s2);
             ctx->release_qws(wi, s2);
         }

@@ -322,6 +322,8 @@ class Program:
             return iv
 
         def mul(a, b):
+            if a == (0, 0) or b == (0, 0):         # a lane whose coefficient is the constant 0 adds nothing, whatever its other operand holds
+                return (0, 0)
             if a is None or b is None:
                 return None
             c = (a[0] * b[0], a[0] * b[1], a[1] * b[0], a[1] * b[1])

@@ -311,6 +311,153 @@ def build_pair_madd(name="PAIR29_MADD", field=None, uns=UNSIGNED_MADD):
     return p
 
 
+# ---- round 10: the table of odd multiples by co-Z additions (Meloni; Longa-Miri's precomputation) ---------------------------------------
+# Two points that share their Z add in 5M + 2S, and the same products re-express the first of them over the sum's Z:
+#     C = (X1 - X2)^2, D = (Y1 - Y2)^2, W1 = X1 C, W2 = X2 C, A1 = Y1 (W1 - W2), Z3 = Z (X1 - X2),
+#     X3 = D - W1 - W2, Y3 = (Y1 - Y2)(W1 - X3) - A1;      P1 + P2 = (X3, Y3, Z3),  P1 = (W1, A1, Z3).
+# With P1 = 2Q and P2 = (2j - 3) Q every call leaves (2j - 1) Q and 2Q over its Z: the table {Q, 3Q, .., 15Q} is one doubling with
+# update and seven of these, four product steps each where the general addition takes eight.
+UNSIGNED_ZADDU = (0, 1, 3)
+UNSIGNED_DBLU = ()          # beta4 and gg feed the update (2 gg must stay a state's Y), Y3 is the first DY: all balanced
+
+
+def build_pair_zaddu(uns=UNSIGNED_ZADDU):
+    """(AO, BO) <- (DX, DY) + (A, B) for two points over ONE Z, and (DXO, DYO) <- (DX, DY) over the sum's Z.
+    in:  E: A = X2, B = Y2, DX = X1, DY = Y1     O: B = Z          (a state, and the other point's X, Y on E)
+    out: E: AO = X3, BO = Y3, DXO = W1, DYO = A1   O: BO = Z3
+    Step 3 has no work for O (its product is of leftovers and is multiplied by zero where step 4 adds it)."""
+    p = Program("PAIR29_ZADDU")
+    AO = p.fe("AO", "tmp")
+    BO = p.fe("BO", "tmp")
+    DXO = p.fe("DXO", "tmp")
+    DYO = p.fe("DYO", "tmp")
+    A = p.fe("A", "in")
+    B = p.fe("B", "in")
+    DX = p.fe("DX", "in")
+    DY = p.fe("DY", "in")
+    H = p.fe("H", "tmp")
+    RR = p.fe("RR", "tmp")
+    U1 = p.fe("U1", "tmp")
+    P1 = p.fe("P1", "tmp")
+    P2 = p.fe("P2", "tmp")
+    T0 = p.fe("T0", "tmp")
+    T1 = p.fe("T1", "tmp")
+    T2 = p.fe("T2", "tmp")
+    TD = p.fe("TD", "tmp")
+    p.sub(H, DX, A)                  # E: dx = X1 - X2
+    p.sub(RR, DY, B)                 # E: dy = Y1 - Y2
+    p.swp(T0, RR)                    #                           O: dy
+    p.sel(P1, T0, H)
+    p.sqr(U1, P1, TD, unsigned=0 in uns)                # E: C = dx^2               O: D = dy^2
+    p.swp(T0, A)                     #                           O: X2
+    p.sel(P1, T0, DX)                # E: X1                     O: X2
+    p.bce(P2, U1)                    # C on both lanes
+    p.mul(DXO, P1, P2, unsigned=1 in uns)               # E: W1 = X1 C              O: W2 = X2 C
+    p.swp(T1, DXO)                   # E: W2
+    p.sub(T0, DXO, T1)               # E: W1 - W2
+    p.mul(DYO, DY, T0, unsigned=2 in uns)               # E: A1 = Y1 (W1 - W2)      (O: nothing)
+    p.swp_sub(T2, U1, DXO)           # E: D - W1
+    p.sub(T2, T2, T1)                # E: D - W1 - W2        (L3)
+    p.wnorm(AO, T2, TD)              # E: X3
+    p.sub(T0, DXO, AO)               # E: W1 - X3            (L2)
+    p.swp(T1, H)                     #                           O: dx
+    p.sel(P1, B, RR)                 # E: dy                     O: Z
+    p.sel(P2, T1, T0)                # E: W1 - X3                O: dx
+    p.lane_const(TD[0], 0, -1)
+    p.mul(BO, P1, P2, DYO, TD[0], unsigned=3 in uns)    # E: Y3 = dy (W1 - X3) - A1   O: Z3 = Z dx
+    return p
+
+
+def build_pair_dblu(uns=UNSIGNED_DBLU):
+    """(A, B) <- 2 (A, B) as build_pair_dbl computes it, and for Z = 1 the point itself over the double's Z = 2y:
+    E: DXO = x Z3^2 = 4 x y^2 = beta4,  DYO = y Z3^3 = 8 y^4 = 2 gg - both are products the doubling makes anyway.
+    in: an affine point as a state (E: A = x, B = y; O: B = one);  out: E: A = X3, B = Y3, DXO, DYO   O: B = Z3."""
+    p = Program("PAIR29_DBLU")
+    A = p.fe("A", "io")
+    B = p.fe("B", "io")
+    DXO = p.fe("DXO", "tmp")
+    DYO = p.fe("DYO", "tmp")
+    U1 = p.fe("U1", "tmp")
+    U3 = p.fe("U3", "tmp")
+    W3 = p.fe("W3", "tmp")
+    P1 = p.fe("P1", "tmp")
+    P2 = p.fe("P2", "tmp")
+    T0 = p.fe("T0", "tmp")
+    T1 = p.fe("T1", "tmp")
+    TD = p.fe("TD", "tmp")
+    p.sqr(U1, B, TD, unsigned=0 in uns)                 # E: gamma = Y^2            O: delta = Z^2
+    p.swp_sub(P1, A, U1)             #                           O: X - delta
+    p.swp_add(P2, A, U1)             #                           O: X + delta
+    p.shl(T0, A, 2)                  # E: 4X
+    p.sel(P1, P1, T0)
+    p.sel(P2, P2, U1)                # E: gamma
+    p.mul(DXO, P1, P2, unsigned=1 in uns)               # E: beta4 = 4 X gamma      O: m = (X - delta)(X + delta)
+    p.shladd(T0, DXO, 1, DXO)        #                           O: alpha = 3m
+    p.shl(T1, U1, 1)                 # E: 2 gamma
+    p.sel(W3, T0, T1)
+    p.swp(T0, DXO)                   #                           O: beta4
+    p.lane_const(TD[8], -2, 0)
+    p.sqr(U3, W3, TD, T0, TD[8], unsigned=2 in uns)     # E: gg = 4 gamma^2         O: X3 = alpha^2 - 2 beta4
+    p.swp(A, U3)                     # E: X3
+    p.shl(DYO, U3, 1)                # E: 2 gg = 8 y^4
+    p.sub(T0, DXO, A)                # E: beta4 - X3         (L2)
+    p.swp(T1, W3)                    # E: alpha
+    p.swp(P1, B)                     #                           O: Y
+    p.shl(P1, P1, 1)                 #                           O: 2Y
+    p.sel(P1, P1, T1)
+    p.sel(P2, B, T0)                 #                           O: Z
+    p.lane_const(TD[0], 0, -2)
+    p.mul(B, P1, P2, U3, TD[0], unsigned=3 in uns)      # E: Y3 = alpha (beta4 - X3) - 2 gg      O: Z3 = 2 Y Z
+    return p
+
+
+def _rng(regs, fe):
+    return (min(regs["%s.%d" % (fe, i)][0] for i in range(8)), max(regs["%s.%d" % (fe, i)][1] for i in range(8))) + tuple(regs[fe + ".8"])
+
+
+def _inside(name, what, u, c):
+    if not (c[0] <= u[0] and u[1] <= c[1] and c[2] <= u[2] and u[3] <= c[3]):
+        raise OverflowError("%s: %s leaves the state contract: %r not inside %r" % (name, what, u, c))
+
+
+def coz_other(C):
+    """What ZADDU takes as (DX, DY): the X of a state, a Y with balanced digits and a state's top digit."""
+    return {"X": C["X"], "Y": (-B28, B28, C["Y"][2], C["Y"][3])}
+
+
+def coz_closed(zaddu, dblu, C=None, affine=None):
+    """The contracts of the co-Z table build, by intervals.  Every table entry is a STATE (PAIR29_ADD reads it as P2, load_state as the
+    top window's T, PAIR29_DBL in the k = n - 2 path).  The other point (2Q: DX, DY) has the X of a state and a Y with BALANCED digits
+    (coz_other: dy = DY - B is squared, and two Y of a state apart would overflow the doubled limbs of the square).
+        DBLU:   an affine point as a state  ->  (A, B) a state whose Y is balanced (it is the first DX, DY);  (DXO, DYO): X, Y of a state
+        ZADDU:  (A, B) a state, (DX, DY) as above  ->  (AO, BO) a state;  (DXO, DYO) as above - its own next input.
+    Returns the union of what the two leave as states; raises OverflowError where a column, a limb or a contract does not hold."""
+    C = STATE_P256 if C is None else C
+    affine = AFFINE if affine is None else affine
+    e, o = {}, {}
+    e.update(fe_range("A", affine)); e.update(fe_range("B", affine)); o.update(fe_range("B", affine))
+    re_, ro = dblu.run_intervals(e, o)
+    outs = [(dblu.name, _rng(re_, "A"), _rng(re_, "B"), _rng(ro, "B"), _rng(re_, "DXO"), _rng(re_, "DYO"))]
+    e, o = {}, {}
+    e.update(fe_range("A", C["X"])); e.update(fe_range("B", C["Y"])); o.update(fe_range("B", C["Z"]))
+    D = coz_other(C)
+    e.update(fe_range("DX", D["X"])); e.update(fe_range("DY", D["Y"]))
+    re_, ro = zaddu.run_intervals(e, o)
+    outs.append((zaddu.name, _rng(re_, "AO"), _rng(re_, "BO"), _rng(ro, "BO"), _rng(re_, "DXO"), _rng(re_, "DYO")))
+    U = {}
+    for name, x, y, z, dx, dy in outs:
+        for k, u in (("X", x), ("Y", y), ("Z", z)):
+            _inside(name, k, u, C[k])
+            U[k] = u if k not in U else (min(U[k][0], u[0]), max(U[k][1], u[1]), min(U[k][2], u[2]), max(U[k][3], u[3]))
+    # DBLU: its state is the first (DX, DY), its update the first (A, B);  ZADDU: its update is its own next (DX, DY)
+    name, x, y, z, dx, dy = outs[0]
+    _inside(name, "2Q's X", x, D["X"]); _inside(name, "2Q's Y", y, D["Y"])
+    _inside(name, "Q's X over 2Q's Z", dx, C["X"]); _inside(name, "Q's Y over 2Q's Z", dy, C["Y"])
+    name, x, y, z, dx, dy = outs[1]
+    _inside(name, "2Q's X over the sum's Z", dx, D["X"]); _inside(name, "2Q's Y over the sum's Z", dy, D["Y"])
+    return U
+
+
 def build_fe_mul():
     """R = A * B / 2^261 mod p (fe29.h fe_mul_body); R must not alias A or B."""
     p = Program("FE29_GCN_MUL")
@@ -414,6 +561,11 @@ def contracts_closed(progs, C):
     if dbl4 is not None:
         d4 = dbln_closed(dbl4, C)
         U = {k: (min(U[k][0], d4[k][0]), max(U[k][1], d4[k][1]), min(U[k][2], d4[k][2]), max(U[k][3], d4[k][3])) for k in U}
+    # ... and the co-Z table build leaves states and feeds itself (round 10); the same rule for a caller that does not name the two programs
+    zaddu, dblu = progs.get("zaddu"), progs.get("dblu")
+    if progs["dbl"].field is None:
+        cz = coz_closed(build_pair_zaddu() if zaddu is None else zaddu, build_pair_dblu() if dblu is None else dblu, C)
+        U = {k: (min(U[k][0], cz[k][0]), max(U[k][1], cz[k][1]), min(U[k][2], cz[k][2]), max(U[k][3], cz[k][3])) for k in U}
     for k in ("X", "Y", "Z"):
         u, c = U[k], C[k]
         if not (c[0] <= u[0] and u[1] <= c[1] and c[2] <= u[2] and u[3] <= c[3]):
@@ -605,7 +757,7 @@ def build_bn_pair_madd(uns=UNSIGNED_BN_MADD):
 
 BN_PAIR_PROGRAMS = [build_bn_pair_dbl, build_bn_pair_add, build_bn_pair_madd]
 
-PROGRAMS = [build_pair_dbl, build_pair_add, build_pair_madd, build_pair_dbl4]
+PROGRAMS = [build_pair_dbl, build_pair_add, build_pair_madd, build_pair_dbl4, build_pair_dblu, build_pair_zaddu]
 
 ALIGN_NOTE = """// Every instruction below is 8 bytes (VOP3, VOP2 + DPP, or VOP2 + 32-bit literal): a block started on an 8-byte boundary stays
 // on 8-byte boundaries throughout (8-byte instructions at 4-mod-8 addresses cost 8.5 % of kernel time, measured).
@@ -639,7 +791,8 @@ def emit(path_kind):
     if path_kind == "bnpair":
         contracts_closed({"dbl": build_bn_pair_dbl(), "add": build_bn_pair_add(), "madd": build_bn_pair_madd()}, STATE_BN)
     elif path_kind == "pair":
-        contracts_closed({"dbl": build_pair_dbl(), "add": build_pair_add(), "madd": build_pair_madd(), "dbl4": build_pair_dbl4()}, STATE_P256)
+        contracts_closed({"dbl": build_pair_dbl(), "add": build_pair_add(), "madd": build_pair_madd(), "dbl4": build_pair_dbl4(),
+                          "dblu": build_pair_dblu(), "zaddu": build_pair_zaddu()}, STATE_P256)
     if path_kind == "bnpair":
         print("// GENERATED by gen_pair_gcn.py bnpair - do not edit.  Two-lanes-per-point operations on FP256BN's G1 (a = 0): the point")
         print("// operations of the four-lanes-per-signature idemix kernel (bn_quad29.h); verified in the DSL interpreter against big integers")

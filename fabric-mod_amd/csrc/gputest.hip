@@ -58,6 +58,15 @@ __global__ void __launch_bounds__(64, 1) gputest_pair_kernel(int op, const int32
         P = R;
     } else if (op == 7) {           // the four doublings of a 4-bit window as one program (round 8)
         PAIR_DBL4(P);
+    } else if (op == 8) {           // the co-Z table build's doubling with update (round 10): out H, RR = the point over the double's Z
+        PAIR_DBLU(P, tH, tRR);
+    } else if (op == 9) {           // ... and its co-Z addition with update: in C, D = the other point's X, Y; out H, RR = its update
+        pair_pt R;
+        fe nx, ny;
+        PAIR_ZADDU(R, nx, ny, P, C, D);
+        P = R;
+        tH = nx;
+        tRR = ny;
     } else if (op == 4) {           // the same three programs for FP256BN's field and a = 0 (pair29_bn_gcn.h)
         PAIRBN_DBL(P.A, P.B, tU1, tU2, tU3, tU4, tP1, tP2, tT0, tT1, tTD);
     } else if (op == 5) {

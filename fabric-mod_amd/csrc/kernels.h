@@ -74,6 +74,7 @@ struct VerifyLaunch {
     int table_lds = 0;                                // the per-signature table: 1 PairQTabLds, 0 global workspace, -1 by size (PAIR_TABLE_LDS_FROM)
     bool pair_solo = false;                           // LDS table: the one-wave form instead of the helper-wave form
     bool pair_dbl1 = false;                           // LDS table: the per-doubling loop instead of the four-doubling program
+    bool pair_table_add = false;                      // LDS table, all-odd digits: the odd multiples by general additions instead of co-Z additions
     bool pair_booth4 = false;                         // LDS table: Booth digits over j*Q, 65 windows, instead of all-odd digits over odd multiples, 63
 };
 hipError_t launch_verify(const VerifyLaunch& v, hipStream_t st);

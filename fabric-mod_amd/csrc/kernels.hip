@@ -129,7 +129,7 @@ struct DigestHashed {
 // Key and core.  Fresh keys: (qx, qy) by row and a table of j*Q per signature that the core builds - GlobalQTab29 (one lane),
 // PairQTab (global workspace, 16 entries, 5-bit windows) or PairQTabLds (LDS, 8 entries, W = 4: the all-odd recoding over odd multiples,
 // or Booth digits over j*Q for BOOTH4).
-template <int LANE_COUNT, class QTab, int W = 5, bool DBL1 = false, bool BOOTH4 = false>
+template <int LANE_COUNT, class QTab, int W = 5, bool DBL1 = false, bool BOOTH4 = false, bool TABLE_ADD = false>
 struct FreshKey {
     static constexpr int LANES = LANE_COUNT;
     const uint8_t *qx, *qy;
@@ -145,7 +145,7 @@ struct FreshKey {
             GTab16 gt{gtab};
             return p256_verify_core29(k.x, k.y, e, r, s, gt, qtab);
         } else {
-            return p256_verify_pair29<QTab, W, DBL1, BOOTH4>(k.x, k.y, e, r, s, gtab, qtab, odd);
+            return p256_verify_pair29<QTab, W, DBL1, BOOTH4, TABLE_ADD>(k.x, k.y, e, r, s, gtab, qtab, odd);
         }
     }
 };
@@ -230,20 +230,22 @@ __global__ void __launch_bounds__(BLOCK, 1) p256_verify_pair_kernel(uint32_t n, 
 // table traffic at all (p256_pair29.h says what that is worth).  Dynamic LDS: 128 signatures x 1040 bytes.  One wave per SIMD: the
 // A/B form of the helper-wave kernel below (FABGPU_FLAG_PAIR_SOLO).  DBL1: the per-doubling loop instead of PAIR_DBL4 (FABGPU_FLAG_PAIR_DBL1).
 // BOOTH4: Booth digits over j*Q, 65 windows, instead of the all-odd recoding over odd multiples, 63 windows (FABGPU_FLAG_PAIR_BOOTH4).
-template <int BLOCK, bool DBL1 = false, bool BOOTH4 = false>
+// TABLE_ADD: the table of odd multiples by general additions instead of co-Z additions (FABGPU_FLAG_PAIR_TABLE_ADD; the default instance only:
+// the DBL1 instances build it that way regardless, the Booth instances have the table j*Q).
+template <int BLOCK, bool DBL1 = false, bool BOOTH4 = false, bool TABLE_ADD = false>
 __global__ void __launch_bounds__(BLOCK, 1) p256_verify_pair_lds_solo_kernel(uint32_t n, const uint8_t* __restrict__ qx, const uint8_t* __restrict__ qy,
                                                                              const uint8_t* __restrict__ e, const uint8_t* __restrict__ r,
                                                                              const uint8_t* __restrict__ s, const int32_t* __restrict__ gtab,
                                                                              uint64_t* __restrict__ verdict_bits, uint8_t* __restrict__ status) {
     extern __shared__ uint4 pair_lds[];
-    verify_tiles<BLOCK>(n, DigestGiven{e}, FreshKey<2, PairQTabLds, 4, DBL1, BOOTH4>{qx, qy, gtab, PairQTabLds::of(pair_lds, threadIdx.x >> 1)}, r, s, verdict_bits, status);
+    verify_tiles<BLOCK>(n, DigestGiven{e}, FreshKey<2, PairQTabLds, 4, DBL1, BOOTH4, TABLE_ADD>{qx, qy, gtab, PairQTabLds::of(pair_lds, threadIdx.x >> 1)}, r, s, verdict_bits, status);
 }
 
 // The LDS-table pair kernel with HELPER WAVES (p256_pair29.h, "HELPER-WAVE FORM"): 2 x BLOCK threads, the same 128 signatures per
 // tile.  Threads 0..BLOCK-1 (main) run the u2*Q chain and emit the verdicts; threads BLOCK..2 BLOCK-1 (helper) run s^-1, u1, u2 and
 // u1*G on the same SIMDs and hand u2 and S over through LDS.  Every wave reaches both barriers of every tile (TileGeom::row).
 // Two roles and two barriers: a tile loop of its own, on the same geometry.  Dynamic LDS: pair_table_lds_bytes().
-template <int BLOCK, bool DBL1 = false, bool BOOTH4 = false>
+template <int BLOCK, bool DBL1 = false, bool BOOTH4 = false, bool TABLE_ADD = false>
 __global__ void __launch_bounds__(2 * BLOCK, 1) p256_verify_pair_lds_kernel(uint32_t n, const uint8_t* __restrict__ qx, const uint8_t* __restrict__ qy,
                                                                                  const uint8_t* __restrict__ e, const uint8_t* __restrict__ r,
                                                                                  const uint8_t* __restrict__ s, const int32_t* __restrict__ gtab,
@@ -260,25 +262,25 @@ __global__ void __launch_bounds__(2 * BLOCK, 1) p256_verify_pair_lds_kernel(uint
     const uint32_t ntiles = Geom::ntiles(n);
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const TileRow t = Geom::row(tile, sub, n);
-        u256 u1;                      // helper
+        u256 he, hw;                  // helper: e, and w = s^-1 (u1 = e w is computed behind barrier A)
         uint32_t early = 0;           // helper: range gates
         pair_pt Qp, T;                // main
         bool q_ok = false, t_inf = true;
         if (helper) {
-            u256 ve, vr, vs;
-            load_be_field(ve, e, t.ic);
+            u256 vr, vs;
+            load_be_field(he, e, t.ic);
             load_be_field(vr, r, t.ic);
             load_be_field(vs, s, t.ic);
-            pair_helper_scalars29<PairHandoffLds<BLOCK>, BOOTH4>(u1, early, ve, vr, vs, hand, odd);
+            pair_helper_scalars29<PairHandoffLds<BLOCK>, BOOTH4>(hw, early, vr, vs, hand, odd);
         } else {
             u256 vqx, vqy;
             load_be_field(vqx, qx, t.ic);
             load_be_field(vqy, qy, t.ic);
-            q_ok = pair_main_table29<PairQTabLds, BOOTH4>(Qp, vqx, vqy, qtab, odd);
+            q_ok = pair_main_table29<PairQTabLds, BOOTH4, TABLE_ADD || DBL1>(Qp, vqx, vqy, qtab, odd);
         }
         __syncthreads();              // A: u2 in LDS
         if (helper) {
-            pair_helper_comb29(u1, early, gtab, hand, odd);
+            pair_helper_comb29(he, hw, early, gtab, hand, odd);
         } else {
             u256 u2;                  // (folded by the helper unless BOOTH4)
             hand.get_u2(u2);
@@ -459,13 +461,16 @@ size_t verify_workspace_bytes(uint32_t n, bool allow_pair) {
     return (size_t)g.wgs * g.block * QWS_UINT4_PER_LANE * 16;
 }
 
-// The LDS-table pair kernels by [one-wave form][per-doubling loop][Booth digits]: the first is the product's, the rest are A/B forms.
+// The LDS-table pair kernels by [one-wave form][per-doubling loop][Booth digits]: the first is the product's, the rest are A/B forms;
+// and the product's two forms with the table of odd multiples by general additions (FABGPU_FLAG_PAIR_TABLE_ADD), by [one-wave form].
 using PairLdsKernel = void (*)(uint32_t, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*, const int32_t*, uint64_t*, uint8_t*);
 static const PairLdsKernel pair_lds_kernels[2][2][2] = {
     {{p256_verify_pair_lds_kernel<VERIFY_BLOCK, false, false>, p256_verify_pair_lds_kernel<VERIFY_BLOCK, false, true>},
      {p256_verify_pair_lds_kernel<VERIFY_BLOCK, true, false>, p256_verify_pair_lds_kernel<VERIFY_BLOCK, true, true>}},
     {{p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK, false, false>, p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK, false, true>},
      {p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK, true, false>, p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK, true, true>}}};
+static const PairLdsKernel pair_lds_table_add_kernels[2] = {p256_verify_pair_lds_kernel<VERIFY_BLOCK, false, false, true>,
+                                                            p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK, false, false, true>};
 
 // One ECDSA P-256 verify launch (kernels.h VerifyLaunch): picks the kernel by key source, digest source, batch size and table home.
 hipError_t launch_verify(const VerifyLaunch& v, hipStream_t st) {
@@ -501,7 +506,10 @@ hipError_t launch_verify(const VerifyLaunch& v, hipStream_t st) {
         // Either with the four doublings of a window as one program, or (FABGPU_FLAG_PAIR_DBL1, A/B runs) as the per-doubling loop.
         // And with the all-odd recoding over a table of odd multiples, 63 windows, or (FABGPU_FLAG_PAIR_BOOTH4, A/B runs) Booth digits, 65.
         if (g.pair && table_lds) {
-            const PairLdsKernel k = pair_lds_kernels[v.pair_solo ? 1 : 0][v.pair_dbl1 ? 1 : 0][v.pair_booth4 ? 1 : 0];
+            // The table of odd multiples by co-Z additions, or (FABGPU_FLAG_PAIR_TABLE_ADD, A/B runs) by general ones: the flag selects among
+            // the default instances; the DBL1 instances build it by general additions anyway and the Booth instances have another table.
+            const PairLdsKernel k = v.pair_table_add && !v.pair_dbl1 && !v.pair_booth4 ? pair_lds_table_add_kernels[v.pair_solo ? 1 : 0]
+                                                                                        : pair_lds_kernels[v.pair_solo ? 1 : 0][v.pair_dbl1 ? 1 : 0][v.pair_booth4 ? 1 : 0];
             if (v.pair_solo) hipLaunchKernelGGL(k, grid, block, pair_table_lds_solo_bytes(), st, n, qx, qy, e, r, s, gtab, verdict_bits, status);
             else hipLaunchKernelGGL(k, grid, dim3(2 * VERIFY_BLOCK), pair_table_lds_bytes(), st, n, qx, qy, e, r, s, gtab, verdict_bits, status);
         } else if (g.pair)
@@ -547,6 +555,7 @@ int warm_kernel_functions_kernels() {
                          (const void*)p256_verify_pair_lds_kernel<VERIFY_BLOCK, true>, (const void*)p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK, true>,
                          (const void*)p256_verify_pair_lds_kernel<VERIFY_BLOCK, false, true>, (const void*)p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK, false, true>,
                          (const void*)p256_verify_pair_lds_kernel<VERIFY_BLOCK, true, true>, (const void*)p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK, true, true>,
+                         (const void*)p256_verify_pair_lds_kernel<VERIFY_BLOCK, false, false, true>, (const void*)p256_verify_pair_lds_solo_kernel<VERIFY_BLOCK, false, false, true>,
                          (const void*)p256_verify_keyed_kernel<VERIFY_BLOCK>,
                          (const void*)p256_verify_keyed_pair_kernel<VERIFY_BLOCK>, (const void*)sha256_p256_verify_keyed_kernel<VERIFY_BLOCK>,
                          (const void*)sha256_p256_verify_keyed_pair_kernel<VERIFY_BLOCK>, (const void*)sha256_p256_verify_pair_kernel<VERIFY_BLOCK>,

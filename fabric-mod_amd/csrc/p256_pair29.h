@@ -39,6 +39,10 @@ __device__ __forceinline__ void pair_sel(pair_pt& r, bool c, const pair_pt& a, c
 #define PAIR_DBL4(P) PAIR29_DBL4((P).A, (P).B, tU1, tU2, tU3, tP1, tT0, tTD, tW)
 #define PAIR_ADD(R, P, C, D) PAIR29_ADD((R).A, (R).B, (P).A, (P).B, tH, tRR, tW, tU1, tU2, tU3, tU4, tU6, tP1, tP2, tT0, tT1, tTD, C, D)
 #define PAIR_MADD(R, P, C, D) PAIR29_MADD((R).A, (R).B, (P).A, (P).B, tU1, tU2, tU3, tU4, tH, tRR, tP1, tP2, tT0, tT1, tTD, C, D)
+// The co-Z table build (round 10).  PAIR_DBLU: P <- 2P, and for an affine P (Z = 1) the point itself over the double's Z in (QX, QY) on E.
+// PAIR_ZADDU: R <- (DX, DY) + P for two points over P's Z, and (NDX, NDY) <- (DX, DY) over R's Z.
+#define PAIR_DBLU(P, QX, QY) PAIR29_DBLU((P).A, (P).B, QX, QY, tU1, tU3, tW, tP1, tP2, tT0, tT1, tTD)
+#define PAIR_ZADDU(R, NDX, NDY, P, DX, DY) PAIR29_ZADDU((R).A, (R).B, NDX, NDY, (P).A, (P).B, DX, DY, tH, tRR, tU1, tP1, tP2, tT0, tT1, tW, tTD)
 
 // Per-signature table j*Q (j = 1..16) in the global workspace.  Per workgroup slot: [entry][q 0..7][pair NP] x 16 bytes;
 // q 0..4 = X[9] Y[9] pad, q 5..7 = Z[9] pad.  E stores / owns the X,Y quads, O the Z quads.
@@ -256,20 +260,29 @@ __device__ __forceinline__ void pair_modinv(u256& out, const u256& x, const modi
     }
 }
 
-// ecdsa_scalars29 with the inversion shared by the pair
-__device__ __forceinline__ void pair_ecdsa_scalars29(u256& u1, u256& u2, const u256& e, const u256& r, const u256& s, bool odd) {
-    const u256 N = FAB_P256_N;
-    u256 w, ered, t;
+// ecdsa_scalars29 with the inversion shared by the pair, in two parts: w = s^-1 and u2 = r w, then u1 = e w.  The helper wave runs the
+// second part after barrier A (round 10: the barrier waits for u2 alone, and u1 is used by the comb behind it and nowhere else).
+__device__ __forceinline__ void pair_ecdsa_u2_29(u256& w, u256& u2, const u256& r, const u256& s, bool odd) {
+    u256 t;
     {
         const modinv_info NI = MODINV_N_INFO;
         pair_modinv(w, s, NI, odd);
     }
+    fn_to_mont(t, r);
+    fn_mul(u2, t, w);
+}
+__device__ __forceinline__ void pair_ecdsa_u1_29(u256& u1, const u256& e, const u256& w) {
+    const u256 N = FAB_P256_N;
+    u256 ered, t;
     uint32_t br = sub256(t, e, N);
     sel256(ered, br == 0, t, e);
     fn_to_mont(t, ered);
     fn_mul(u1, t, w);
-    fn_to_mont(t, r);
-    fn_mul(u2, t, w);
+}
+__device__ __forceinline__ void pair_ecdsa_scalars29(u256& u1, u256& u2, const u256& e, const u256& r, const u256& s, bool odd) {
+    u256 w;
+    pair_ecdsa_u2_29(w, u2, r, s, odd);
+    pair_ecdsa_u1_29(u1, e, w);
 }
 
 // S = k * B over a comb table of B on a lane pair (comb_mult29).  seed: any valid point in pair state.
@@ -445,11 +458,43 @@ __device__ __forceinline__ void pair_u2_mult29(pair_pt& T, bool& t_inf, const u2
 }
 
 // The LDS table for the all-odd recoding (p256_odd4.h): slot j = (2j - 1) Q, j = 1..8 - eight entries like pair_qtab_build29<4>'s.
+// By co-Z additions (round 10; gen_pair_gcn.py has the formulas): slot 1 = Q; one doubling with update leaves D = 2Q and Q over the
+// same Z = 2y; then seven times  slot j = slot j-1 + D  with both over one Z, which also re-expresses D over the sum's Z for the next
+// step: four product steps where the general addition takes eight.  D lives in registers (X and Y on the even lane; its Z is the
+// current entry's) - no slot is borrowed.  The entries are states like any other: every consumer reads them as before.
+// Exceptional inputs.  The co-Z addition degenerates only for X1 = X2 over the common Z, i.e. (2j - 3) Q = +-2Q, (2j - 1) Q or
+// (2j - 5) Q the point at infinity with 2j - 1 <= 15: impossible for a Q on the curve, whose order is the prime n > 15.  A Q off the
+// curve (or out of the field) is refused by the curve gate and its row's status comes from the gate, not from the table.  The programs
+// are branch-free and compute no address from data: such a row leaves garbage entries in its own slots and nothing else.
+// TABLE_ADD (FABGPU_FLAG_PAIR_TABLE_ADD: A/B runs and parity tests) keeps the build by general additions it replaces, below.
+template <class QTab>
+__device__ __forceinline__ void pair_qtab_build_odd29(const pair_pt& Qp, const QTab& qtab, bool odd) {
+    PAIR_TMPS;
+    qtab.store_state(1, Qp, odd);
+    pair_pt d = Qp, cur;                      // d: 2Q, then only a carrier of (DX, DY)
+    fe DX, DY, qy;
+    PAIR_DBLU(d, cur.A, qy);                  // E: cur.A, qy = Q over Z(2Q)
+    fe_sel(cur.B, odd, d.B, qy);              // cur = Q as a state over Z(2Q)
+    DX = d.A;
+    DY = d.B;
+#pragma unroll 1
+    for (int j = 2; j <= PAIR_LDS_ENTRIES; j++) {
+        pair_pt sum;
+        fe ndx, ndy;
+        PAIR_ZADDU(sum, ndx, ndy, cur, DX, DY);
+        cur = sum;
+        DX = ndx;
+        DY = ndy;
+        qtab.store_state(j, cur, odd);
+    }
+}
+
+// The same table by general additions (round 9: the form behind FABGPU_FLAG_PAIR_TABLE_ADD, and the table of the DBL1 instances).
 // Slot 1 = Q, D = 2Q, slot 2 = D + Q (mixed), slot j = slot j-1 + D.  2Q waits in slot 8, where every addition reads it in crossed
 // layout, until the last addition overwrites it with 15 Q (its load is issued before that store).  None of the additions meets
 // P == +-Q: (2j - 3) Q and 2 Q with 2j - 3 <= 13, Q of prime order (anything else fails the curve gate and its row reports that).
 template <class QTab>
-__device__ __forceinline__ void pair_qtab_build_odd29(const pair_pt& Qp, const fe& QX, const fe& QY, const QTab& qtab, bool odd) {
+__device__ __forceinline__ void pair_qtab_build_odd_add29(const pair_pt& Qp, const fe& QX, const fe& QY, const QTab& qtab, bool odd) {
     PAIR_TMPS;
     qtab.store_state(1, Qp, odd);
     pair_pt d = Qp, cur;
@@ -542,7 +587,8 @@ __device__ __forceinline__ void pair_u2_mult_odd29(pair_pt& T, const u256& k, co
 // table (entry 2, negated) instead of from the loop.
 // W = 4 runs the all-odd recoding over the table of odd multiples (pair_u2_mult_odd29: 63 windows, no zero digit) unless BOOTH4 asks
 // for the Booth form above (FABGPU_FLAG_PAIR_BOOTH4: A/B runs and parity tests).
-template <class QTab, int W = 5, bool DBL1 = false, bool BOOTH4 = false>
+// TABLE_ADD: the table of odd multiples by general additions (pair_qtab_build_odd_add29) instead of co-Z additions; DBL1 implies it.
+template <class QTab, int W = 5, bool DBL1 = false, bool BOOTH4 = false, bool TABLE_ADD = false>
 __device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, const u256& u1, const u256& u2, const fe& QX, const fe& QY,
                                                      const int32_t* __restrict__ gtab, const QTab& qtab, bool odd) {
     static_assert(W == 4 || W == 5, "signed 4- or 5-bit windows");
@@ -553,7 +599,8 @@ __device__ __forceinline__ void pair_combined_mult29(pair_pt& Rr, bool& r_inf, c
     pair_pt T;
     bool t_inf;
     if constexpr (W == 4 && !BOOTH4) {
-        pair_qtab_build_odd29<QTab>(Qp, QX, QY, qtab, odd);
+        if constexpr (TABLE_ADD || DBL1) pair_qtab_build_odd_add29<QTab>(Qp, QX, QY, qtab, odd);
+        else pair_qtab_build_odd29<QTab>(Qp, qtab, odd);
         u256 k;
         u2_fold_odd(k, u2);
         pair_u2_mult_odd29<QTab, DBL1>(T, k, qtab, odd);
@@ -612,7 +659,7 @@ __device__ __forceinline__ bool pair_x_equals_r29(const pair_pt& Rr, bool r_inf,
 }
 
 // Status of one tuple, valid on the EVEN lane of the pair.
-template <class QTab, int W = 5, bool DBL1 = false, bool BOOTH4 = false>
+template <class QTab, int W = 5, bool DBL1 = false, bool BOOTH4 = false, bool TABLE_ADD = false>
 __device__ __forceinline__ uint32_t p256_verify_pair29(const u256& qx, const u256& qy, const u256& e, const u256& r, const u256& s,
                                                         const int32_t* __restrict__ gtab, const QTab& qtab, bool odd) {
     const u256 P = FAB_P256_P;
@@ -630,7 +677,7 @@ __device__ __forceinline__ uint32_t p256_verify_pair29(const u256& qx, const u25
 
     pair_pt Rr;
     bool r_inf;
-    pair_combined_mult29<QTab, W, DBL1, BOOTH4>(Rr, r_inf, u1, u2, QX, QY, gtab, qtab, odd);
+    pair_combined_mult29<QTab, W, DBL1, BOOTH4, TABLE_ADD>(Rr, r_inf, u1, u2, QX, QY, gtab, qtab, odd);
     bool ok = pair_x_equals_r29(Rr, r_inf, r);
     uint32_t st = ok ? ST_VALID : ST_BAD_MATH;
     return early != ST_VALID ? early : st;
@@ -702,14 +749,14 @@ struct PairHandoffLds {
     }
 };
 
-// Helper, before barrier A: range gates and the scalars; u2 goes to LDS - folded to its odd representative (u2_fold_odd: one subtraction
-// and a select, off the chain; the sign rides in bit 0, the handoff stays eight words) unless BOOTH4 - u1 and the gate status stay.
+// Helper, before barrier A: range gates, w = s^-1 and u2 = r w; u2 goes to LDS - folded to its odd representative (u2_fold_odd: one
+// subtraction and a select, off the chain; the sign rides in bit 0, the handoff stays eight words) unless BOOTH4 - w and the gate status
+// stay.  u1 = e w is not wanted before the comb: pair_helper_comb29 computes it behind the barrier (round 10).
 template <class Hand, bool BOOTH4 = false>
-__device__ __forceinline__ void pair_helper_scalars29(u256& u1, uint32_t& early, const u256& e, const u256& r, const u256& s, const Hand& hand,
-                                                      bool odd) {
+__device__ __forceinline__ void pair_helper_scalars29(u256& w, uint32_t& early, const u256& r, const u256& s, const Hand& hand, bool odd) {
     early = range_status(r, s);
     u256 u2;
-    pair_ecdsa_scalars29(u1, u2, e, r, s, odd);
+    pair_ecdsa_u2_29(w, u2, r, s, odd);
     if constexpr (!BOOTH4) {
         u256 k;
         u2_fold_odd(k, u2);
@@ -718,10 +765,14 @@ __device__ __forceinline__ void pair_helper_scalars29(u256& u1, uint32_t& early,
     hand.put_u2(u2);
 }
 
-// Helper, between A and B: S = u1*G on the 16-bit comb (seeded with G: the seed is any valid point, and this role has no Q), to LDS.
+// Helper, between A and B: u1 = e w, then S = u1*G on the 16-bit comb (seeded with G: the seed is any valid point, and this role has
+// no Q), to LDS.
 template <class Hand>
-__device__ __forceinline__ void pair_helper_comb29(const u256& u1, uint32_t early, const int32_t* __restrict__ gtab, const Hand& hand, bool odd) {
+__device__ __forceinline__ void pair_helper_comb29(const u256& e, const u256& w, uint32_t early, const int32_t* __restrict__ gtab, const Hand& hand,
+                                                   bool odd) {
     const fe ONE = {FE29_R1};
+    u256 u1;
+    pair_ecdsa_u1_29(u1, e, w);
     fe gx, gy;
     GTab16 gt{gtab};
     gt.load(0, 1u, gx, gy);
@@ -733,8 +784,9 @@ __device__ __forceinline__ void pair_helper_comb29(const u256& u1, uint32_t earl
     hand.put_s(S, s_inf, early);
 }
 
-// Main, before barrier A: Q gates and the table (odd multiples, or j*Q for BOOTH4).  Returns q_ok; Qp = Q in pair state.
-template <class QTab, bool BOOTH4 = false>
+// Main, before barrier A: Q gates and the table (odd multiples - by co-Z additions, or by general ones for TABLE_ADD - or j*Q for BOOTH4).
+// Returns q_ok; Qp = Q in pair state.
+template <class QTab, bool BOOTH4 = false, bool TABLE_ADD = false>
 __device__ __forceinline__ bool pair_main_table29(pair_pt& Qp, const u256& qx, const u256& qy, const QTab& qtab, bool odd) {
     const u256 P = FAB_P256_P;
     const fe ONE = {FE29_R1};
@@ -746,7 +798,8 @@ __device__ __forceinline__ bool pair_main_table29(pair_pt& Qp, const u256& qx, c
     Qp.A = QX;
     fe_sel(Qp.B, odd, ONE, QY);
     if constexpr (BOOTH4) pair_qtab_build29<QTab, 4>(Qp, QX, QY, qtab, odd);
-    else pair_qtab_build_odd29<QTab>(Qp, QX, QY, qtab, odd);
+    else if constexpr (TABLE_ADD) pair_qtab_build_odd_add29<QTab>(Qp, QX, QY, qtab, odd);
+    else pair_qtab_build_odd29<QTab>(Qp, qtab, odd);
     return q_ok;
 }
 

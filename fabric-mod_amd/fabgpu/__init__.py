@@ -40,6 +40,7 @@ FLAG_PAIR_TABLE_GLOBAL = 16  # ... in the global workspace
 FLAG_PAIR_SOLO = 1024        # fabgpu.h: ... in LDS, one wave per SIMD (no helper waves; A/B runs and parity tests)
 FLAG_PAIR_DBL1 = 2048        # fabgpu.h: ... in LDS, the per-doubling loop instead of the four-doubling program (A/B runs and parity tests)
 FLAG_PAIR_BOOTH4 = 16384     # fabgpu.h: ... in LDS, Booth digits over j*Q and 65 windows instead of all-odd digits over odd multiples and 63 (A/B runs and parity tests)
+FLAG_PAIR_TABLE_ADD = 65536  # fabgpu.h: ... in LDS, the table of odd multiples by general additions instead of co-Z additions (A/B runs and parity tests)
 FLAG_KEY_TABLES_16BIT = 256  # fabgpu.h: registered keys also get a 16-bit comb (80 MiB each, built behind the registration)
 FLAG_NO_WIDE = 32            # fabgpu.h: registered keys never on the eight-lanes-per-signature two-phase kernels (launches <= 8 192 signatures)
 FLAG_P384_KEY_TABLES_16BIT = 8192   # fabgpu.h: registered P-384 keys also get 16-bit comb tables (144 MiB each, <= 32 per context; off by default)

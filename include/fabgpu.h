@@ -85,6 +85,9 @@ typedef struct fabgpu_ctx fabgpu_ctx;
 #define FABGPU_FLAG_PAIR_BOOTH4 16384u /* ... in LDS, either form: signed (Booth) 4-bit digits over a table of j*Q, 65 windows with zero digits
                                         (round 8's form) instead of the all-odd recoding over a table of odd multiples, 63 windows, no zero
                                         digit (A/B runs; parity tests run both forms).  Statuses and verdict words do not change */
+#define FABGPU_FLAG_PAIR_TABLE_ADD 65536u /* ... in LDS, either form, all-odd recoding: the table of odd multiples by one doubling, one mixed and
+                                        six general additions (round 9's form) instead of a doubling with update and seven co-Z additions
+                                        (A/B runs; parity tests run both forms).  Statuses and verdict words do not change */
 
 #define FABGPU_FLAG_KEY_TABLES_16BIT 256u   /* registered keys (fabgpu_p256_key_register): each key also gets a 16-bit comb table - 80 MiB, the
                                             generator's format, built on the device BEHIND the registration (nobody waits for it), up to

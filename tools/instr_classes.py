@@ -37,6 +37,7 @@ def classes(prog):
 
 def main():
     progs = {"doubling (4M + 4S)": g.build_pair_dbl(), "four doublings (DBL4)": g.build_pair_dbl4(), "addition (12M + 4S)": g.build_pair_add(), "mixed addition (8M + 3S)": g.build_pair_madd(),
+             "doubling with update (DBLU)": g.build_pair_dblu(), "co-Z addition (5M + 2S)": g.build_pair_zaddu(),
              "field product (one lane)": g.build_fe_mul(), "field square (one lane)": g.build_fe_sqr()}
     rows = {}
     print("%-28s %7s %7s %7s %7s %7s %7s %7s   %s" % ("per operation", "mac", "carry", "route", "field", "hazard", "scalar", "total", "mac share"))
@@ -46,22 +47,30 @@ def main():
         rows[name] = (c, total)
         print("%-28s %7d %7d %7d %7d %7d %7d %7d   %.2f" % (name, c["mac"], c["carry"], c["route"], c["field"], c["hazard"], c["scalar"], total, c["mac"] / total))
     # trip counts of the LDS-table kernel, all-odd recoding over a table of odd multiples: 63 windows x (one four-doubling program; one
-    # addition) under a top window that is a table read; the table's one doubling, one mixed addition and six additions; the final addition;
-    # 16 comb mixed additions (the final addition's doubling runs for crafted inputs only, the doubling for u2 = n - 2 or 2 for that scalar).
-    # The Booth form it replaced (FABGPU_FLAG_PAIR_BOOTH4): 4 doublings, 64 four-doubling programs, 65 + 1 additions, 16 + 3 mixed additions.
-    trips = {"doubling (4M + 4S)": 1, "four doublings (DBL4)": 63, "addition (12M + 4S)": 63 + 6 + 1, "mixed addition (8M + 3S)": 16 + 1}
+    # addition) under a top window that is a table read; the table's doubling with update and seven co-Z additions (round 10); the final
+    # addition; 16 comb mixed additions (the final addition's doubling runs for crafted inputs only, the doubling for u2 = n - 2 or 2 for
+    # that scalar).  The table by general additions it replaced (FABGPU_FLAG_PAIR_TABLE_ADD): one doubling, one mixed addition, six additions.
+    # The Booth form before that (FABGPU_FLAG_PAIR_BOOTH4): 4 doublings, 64 four-doubling programs, 65 + 1 additions, 16 + 3 mixed additions.
+    trips = {"doubling (4M + 4S)": 0, "four doublings (DBL4)": 63, "addition (12M + 4S)": 63 + 1, "mixed addition (8M + 3S)": 16,
+             "doubling with update (DBLU)": 1, "co-Z addition (5M + 2S)": 7}
+    table_add = {"doubling (4M + 4S)": 1, "mixed addition (8M + 3S)": 1, "addition (12M + 4S)": 6}
+    table_coz = {"doubling with update (DBLU)": 1, "co-Z addition (5M + 2S)": 7}
     booth4 = {"doubling (4M + 4S)": 4, "four doublings (DBL4)": 64, "addition (12M + 4S)": 65 + 1, "mixed addition (8M + 3S)": 16 + 3}
     print()
     print("window doublings: 63 x %d = %d (Booth digits: 64 x %d; round 7: 256 x %d = %d)" % (rows["four doublings (DBL4)"][1], 63 * rows["four doublings (DBL4)"][1],
                                                                       rows["four doublings (DBL4)"][1], rows["doubling (4M + 4S)"][1], 256 * rows["doubling (4M + 4S)"][1]))
     print("point programs with Booth digits (FABGPU_FLAG_PAIR_BOOTH4): %d" % sum(n * rows[name][1] for name, n in booth4.items()))
+    print("table of odd multiples: %d by co-Z additions (+ 9 for the select that makes Q a state over 2Q's Z); %d by general additions (FABGPU_FLAG_PAIR_TABLE_ADD)" %
+          (sum(n * rows[name][1] for name, n in table_coz.items()), sum(n * rows[name][1] for name, n in table_add.items())))
+    for k in ("mac", "carry", "route", "field"):
+        print("  %-8s %6d against %6d" % (k, sum(n * rows[name][0][k] for name, n in table_coz.items()), sum(n * rows[name][0][k] for name, n in table_add.items())))
     tot = {k: 0 for k in ("mac", "carry", "route", "field", "hazard", "scalar")}
     for name, n in trips.items():
         for k in tot:
             tot[k] += n * rows[name][0][k]
     point = sum(tot.values())
     print()
-    print("per verification (two lanes), point arithmetic: %d doublings, %d four-doubling programs, %d additions, %d mixed additions" % tuple(trips.values()))
+    print("per verification (two lanes), point arithmetic: %d doublings, %d four-doubling programs, %d additions, %d mixed additions, %d doubling with update, %d co-Z additions" % tuple(trips.values()))
     for k in ("mac", "carry", "route", "field", "hazard", "scalar"):
         print("  %-8s %8d  %5.1f %%" % (k, tot[k], 100.0 * tot[k] / point))
     print("  %-8s %8d" % ("total", point))
